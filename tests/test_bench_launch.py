@@ -69,6 +69,13 @@ def test_rccl_job_on_too_few_gpus_fails_loudly_instead_of_running_one_rank():
     assert "needs 2 visible GPUs" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_options_full_and_dump_outputs_and_steps_below_one_refused():
+    r = run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = run(["--gpus", "1", "--steps", "0"])      # refused by the argument check, before anything touches a GPU
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
 def test_world_size_mismatch_is_an_error():
     r = run(["--gpus", "2", "--dry-run"], RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MGEA_DIST_BACKEND="gloo")
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)

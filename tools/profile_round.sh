@@ -24,7 +24,7 @@ step() {  # step <name> <seconds> <cmd...>: a pass that TIMES OUT ends the scrip
   [ $rc -lt 124 ] || [ $rc -eq 139 ] || exit 1
   return $rc
 }
-BENCH1="python3 bench.py --steps 1 --warmup 1 --no-cpu --no-extra"
+BENCH1="python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-extra"
 GEN1="python3 bench.py --steps 1 --warmup 0 --no-cpu --no-extra --profile-stride 0"
 
 step bench_under_rocprof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $T/bench -- $BENCH1 && stats $T/bench $OUT/bench_kernel_stats.csv
