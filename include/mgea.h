@@ -291,10 +291,11 @@ int mgea_op_skinny(int32_t epi, const float* a_dev, const float* w_dev, const fl
                    const float* ln_c1_dev, const float* stats_in_dev, int32_t n_part,
                    int32_t part_cnt, float* out_dev, float* stats_out_dev, int32_t M, int32_t N, int32_t K,
                    int32_t act, int32_t dbg, void* stream);
-/* Number P of (max, argmax) partials per row that mgea_op_skinny(epi = 3) of this shape writes: stats_out_dev receives the maxima as
- * float [row][P] (row stride P) followed, 64 * P floats in, by the int32 argmax indices in the same layout.  (The decode-step head of
- * api_cache.py:105 runs as ONE balanced round of the chip where the shape allows -- csrc/head_gemm.hip, P = the CU count -- and on
- * the generic skinny kernel otherwise; switch head_balanced.) */
+/* Number P of (max, argmax) partials per row that mgea_op_skinny(epi = 3, dbg = 0) of this shape writes, or 0 for a shape it refuses:
+ * stats_out_dev receives the maxima as float [row][P] (row stride P) followed, max(64, M) * P floats in, by the int32 argmax indices in
+ * the same layout.  (The decode-step head of api_cache.py:105 runs as ONE balanced round of the chip where the shape allows --
+ * csrc/head_gemm.hip, P = the CU count -- and on the generic skinny kernel otherwise; switch head_balanced.)  epi = 3 takes no
+ * ln_c1_dev. */
 int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K);
 /* Sampler on a logits matrix [B,V]; step selects the Philox counter.  probs_out_dev [B,V] or NULL
  * receives the pre-multinomial distribution. */

@@ -224,17 +224,22 @@ int mgea_op_skinny(int32_t epi, const float* a_dev, const float* w_dev, const fl
     a.ln_c1 = ln_c1_dev; a.eps = 1e-5f; a.stats_in = stats_in_dev; a.n_part = n_part; a.part_cnt = part_cnt;
     a.out = out_dev; a.ldo = N; a.stats_out = stats_out_dev; a.act = act; a.dbg = dbg;
     MGEA_REQUIRE(epi == EPI_ACT || epi == EPI_RES || epi == EPI_LOGITS, MGEA_EINVAL, "op_skinny: epilogue %d not exposed", epi);
-    if (epi == EPI_LOGITS) {   // LM head: logits [M,N] row-major in out_dev (or NULL); per-tile (max, argmax) partials in stats_out_dev
-        MGEA_REQUIRE(stats_out_dev, MGEA_EINVAL, "op_skinny: the LOGITS epilogue writes its partials to stats_out_dev");
-        // (tools that pass ablation / timestamp bits in dbg run the generic kernel, whose partial count differs from the balanced head kernel's)
-        const int tiles = (dbg & ~(1 << 21)) ? skinny_logits_tiles(M, N, 0) : skinny_logits_tiles(M, N, K);
+    MGEA_REQUIRE(epi != EPI_LOGITS || stats_out_dev, MGEA_EINVAL, "op_skinny: the LOGITS epilogue writes its partials to stats_out_dev");
+    DecodeGemmPlan p;
+    MGEA_TRY(plan_decode_gemm(epi, a, false, &p));
+    if (epi == EPI_LOGITS) {   // LM head: logits [M,N] row-major in out_dev (or NULL); (max, argmax) partials in stats_out_dev (mgea.h)
         a.pmax_val = stats_out_dev;
-        a.pmax_idx = reinterpret_cast<int32_t*>(stats_out_dev + (int64_t)64 * tiles);
+        a.pmax_idx = reinterpret_cast<int32_t*>(stats_out_dev + (int64_t)(M > 64 ? M : 64) * p.n_partials);
     }
-    return launch_skinny(epi, a, (hipStream_t)stream);
+    return launch_decode_gemm(epi, p, a, (hipStream_t)stream);
 }
 
-int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K) { return skinny_logits_tiles(M, N, K); }
+int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K) {
+    SkinnyArgs a{};
+    a.M = M; a.N = N; a.K = K;   // (no LayerNorm, dbg = 0)
+    DecodeGemmPlan p;
+    return plan_decode_gemm(EPI_LOGITS, a, false, &p) == MGEA_OK ? p.n_partials : 0;
+}
 
 int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s, int64_t step,
                    int32_t* ids_out_dev, float* probs_out_dev, void* stream) {

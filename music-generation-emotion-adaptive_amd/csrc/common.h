@@ -298,7 +298,7 @@ struct SkinnyArgs {
     // folded LayerNorm (ln_c1 != NULL): W holds gamma * W, ln_c1 [N] = its row sums, bias = beta @ W^T + bias
     // (launch_ln_fold); per-row partial stats [64][n_part][2], each over `part_cnt` elements
     const float* ln_c1; float eps;
-    const float* ln_g; const float* ln_b;   // launch_gemv: LayerNorm gamma / beta applied directly (W row-major, unfolded);
+    const float* ln_g; const float* ln_b;   // gemv: LayerNorm gamma / beta applied directly (W row-major, unfolded);
                                             // w_f16 with ln_c1: gamma is applied to A on load (W stays the plain rounded matrix,
                                             // ln_c1 = sum_k gamma_k W[n,k], bias = sum_k beta_k W[n,k] + b[n])
     const float* stats_in; int n_part; int part_cnt;
@@ -311,18 +311,44 @@ struct SkinnyArgs {
     KvPool pool; int layer; const int32_t* page_table; int max_pages; const int32_t* ctx_len;
     const int32_t* lens; int T; int C;
     // LOGITS
-    float* pmax_val; int32_t* pmax_idx;   // [64][n_tiles]
+    float* pmax_val; int32_t* pmax_idx;   // [M][n_partials] (DecodeGemmPlan)
     int dbg;                   // ablation bits for tools/skinny_bench.py (0 in production)
     int nw;                    // waves per workgroup (set by the launcher)
 };
-int launch_skinny(int epi, const SkinnyArgs& a, hipStream_t st);
-// M <= 2 rows (single-stream decode): wave-level dot products on the ROW-MAJOR arena weights (gemv_small.hip)
-bool gemv_shape_ok(int M, int N, int K);
-int launch_gemv(int epi, const SkinnyArgs& a, hipStream_t st);
-int skinny_logits_tiles(int M, int N, int K);   // (max, argmax) partials per row that launch_skinny(EPI_LOGITS) of this shape writes
-// head_gemm.hip: the LM head of a decode step as one balanced round of the chip; launch returns 1 when the shape is not its own
-int head_balanced_partials(int M, int N, int K);
-int launch_head_balanced(const SkinnyArgs& a, hipStream_t st);
+
+// ---- decode GEMMs: one launch plan per call (gemm_skinny.hip) ----------------------------------------------------
+// Three kernel families serve them: gemm_skinny_kernel (tiled, LayerNorm-folded operands), head_balanced_kernel (head_gemm.hip:
+// the LM head as one round of the chip) and gemv_rows_kernel (gemv_small.hip: <= 2 rows on the ROW-MAJOR weights, LayerNorm applied
+// directly from ln_g / ln_b).  plan_decode_gemm makes every choice -- family, template parameters, geometry, the LOGITS partial
+// count -- and launch_decode_gemm launches exactly that plan.
+enum { DG_SKINNY = 0, DG_HEAD = 1, DG_GEMV = 2 };
+struct DecodeGemmPlan {
+    int kind;
+    int mt, nt, nw;          // skinny: gemm_skinny_kernel<epi, ln, mt, nt, f16, nch>, nw waves per workgroup
+    int base, n_extra;       // head: head_balanced_kernel<base, nch, f16, stamped>; n_extra = workgroups with an extra unit
+    int cw, mr;              // gemv: gemv_rows_kernel<epi, ln, cw, mr>
+    int nch;                 // skinny, head: k-chunks of 32 per wave (skinny: 0 = the generic instruction stream)
+    bool ln, f16, stamped;   // ln: folded LayerNorm (skinny, ln_c1) or direct LayerNorm (gemv, ln_g)
+    dim3 grid, block;
+    int shmem;               // dynamic LDS bytes
+    bool raise_lds;          // raise the kernel's dynamic-LDS limit to shmem before the launch
+    int n_partials;          // LOGITS: (max, argmax) partials per row, at pmax_val / pmax_idx [row * n_partials + i]
+};
+// rowmajor_gemv: a.W is the row-major [N, K] matrix (with a.ln_g / a.ln_b) for the dot-product kernel; otherwise the tiled copy
+int plan_decode_gemm(int epi, const SkinnyArgs& a, bool rowmajor_gemv, DecodeGemmPlan* p);
+int launch_decode_gemm(int epi, const DecodeGemmPlan& p, const SkinnyArgs& a, hipStream_t st);
+bool gemv_shape_ok(int M, int N, int K);   // the shapes gemv_rows_kernel takes
+// a kernel's host address and its per-device "dynamic-LDS limit raised" bits (set_max_dynamic_lds): one pair per instantiation
+struct KernelRef { const void* fn; uint64_t* lds_raised; };
+template <auto K> KernelRef kernel_ref() {
+    static uint64_t raised = 0;
+    return KernelRef{reinterpret_cast<const void*>(K), &raised};
+}
+// the instantiation a plan names, per family (head_gemm.hip, gemv_small.hip); {nullptr, nullptr} when there is none
+KernelRef head_kernel(const DecodeGemmPlan& p);
+KernelRef gemv_kernel(int epi, const DecodeGemmPlan& p);
+constexpr int HB_PITCH = 20;   // head_balanced_kernel: floats per LDS row of a partial tile (16 + 4: the 16 rows of one ds_write_b128
+                               // start in different banks)
 int launch_embed_stats(const int32_t* ids, const int32_t* lens, const int32_t* ctx_len, const float* tok_emb,
                        const float* pos_emb, float* x, float* stats, int B, int T, int C, int vocab, int pos_rows,
                        int absolute_pos, int32_t* err_flag, hipStream_t st);

@@ -97,6 +97,7 @@ struct mgea_decoder {
     float *x = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *hbuf = nullptr, *slabs = nullptr,
           *logits = nullptr, *stats = nullptr, *pmax_val = nullptr;
     int32_t* pmax_idx = nullptr;
+    int64_t pmax_cap = 0;        // entries of pmax_val / pmax_idx
     bool no_graph = false;       // MGEA_DECODER_NOGRAPH=1: launch every step eagerly (rocprofv3 --pmc runs)
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
@@ -243,8 +244,9 @@ int ensure_ws(mgea_decoder* h, int64_t M) {
     ALLOC(h->logits, (int64_t)h->cfg.max_batch * h->cfg.vocab);
     const int64_t fr = M < MGEA_FUSED_MAX_ROWS ? M : MGEA_FUSED_MAX_ROWS;   // rows of the fused path
     ALLOC(h->stats, fr * (C / 16 + 1) * 2);
-    ALLOC(h->pmax_val, fr * ceil_div(h->cfg.vocab, 16));
-    if (hipMalloc((void**)&h->pmax_idx, (size_t)fr * ceil_div(h->cfg.vocab, 16) * sizeof(int32_t)) != hipSuccess) {
+    h->pmax_cap = fr * ceil_div(h->cfg.vocab, 16);   // every head plan leaves at most one partial per 16 columns (checked in decode_gemm)
+    ALLOC(h->pmax_val, h->pmax_cap);
+    if (hipMalloc((void**)&h->pmax_idx, (size_t)h->pmax_cap * sizeof(int32_t)) != hipSuccess) {
         set_error("decoder workspace: out of device memory");
         free_ws(h);
         return MGEA_ENOMEM;
@@ -363,6 +365,32 @@ bool gemv_ok(const mgea_decoder* h, int M, int T, const int32_t* lens, bool use_
            gemv_shape_ok(M, c.d_model, c.d_ff);
 }
 
+// One decode GEMM -- g = 0 in_proj, 1 out_proj, 2 fc1, 3 fc2 of layer l, 4 the head -- on the weights of its family: the arena's
+// row-major matrices with LayerNorm applied directly (gv: gemv_rows_kernel) or the tiled copies with LayerNorm folded in.
+// `a` brings the activations and the epilogue's buffers; *plan (optional) receives what ran (the head's partial count).
+int decode_gemm(mgea_decoder* h, int l, int g, SkinnyArgs a, bool gv, hipStream_t st, DecodeGemmPlan* plan = nullptr) {
+    static const int kEpi[5] = {EPI_QKV, EPI_RES, EPI_ACT, EPI_RES, EPI_LOGITS};
+    static const int kW[4] = {L_INW, L_OUTW, L_FC1W, L_FC2W}, kB[4] = {L_INB, L_OUTB, L_FC1B, L_FC2B};
+    const bool ln = g == 0 || g == 2;
+    const int lnw = g == 0 ? L_LN1W : L_LN2W, lnb = g == 0 ? L_LN1B : L_LN2B;
+    a.w_f16 = h->f16;
+    a.W = g == 4 ? (gv ? h->head_w() : h->head_tw()) : (gv ? h->lw(l, kW[g]) : h->tw(l, g));
+    a.bias = g == 4 ? h->head_b() : h->lw(l, kB[g]);
+    if (ln && gv) {
+        a.ln_g = h->lw(l, lnw); a.ln_b = h->lw(l, lnb);
+    } else if (ln) {   // LN(x) @ W^T + b = rstd * (x @ (gamma W)^T - mean * c1) + c2 (launch_ln_fold); fp16 tiles: gamma on A
+        a.ln_c1 = g == 0 ? h->qkv_c1(l) : h->fc1_c1(l);
+        a.bias = g == 0 ? h->qkv_c2(l) : h->fc1_c2(l);
+        if (h->f16) a.ln_g = h->lw(l, lnw);
+    }
+    DecodeGemmPlan p;
+    MGEA_TRY(plan_decode_gemm(kEpi[g], a, gv, &p));
+    MGEA_REQUIRE(!a.pmax_val || (int64_t)a.M * p.n_partials <= h->pmax_cap, MGEA_EINVAL,
+                 "decoder: %d rows x %d head partials exceed the workspace (%lld)", a.M, p.n_partials, (long long)h->pmax_cap);
+    if (plan) *plan = p;
+    return launch_decode_gemm(kEpi[g], p, a, st);
+}
+
 int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t* lens, bool use_cache_attn, hipStream_t st,
                      bool kv_only_last = false) {
     const auto& c = h->cfg;
@@ -370,21 +398,14 @@ int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t
     const bool gv = gemv_ok(h, M, T, lens, use_cache_attn);
     int n_part = 2, part_cnt = C / 2;  // the embedding kernel leaves the whole-row statistics as two equal halves
     for (int l = 0; l < c.n_layer; ++l) {
-        SkinnyArgs a{};
-        a.M = M; a.eps = c.ln_eps; a.w_f16 = h->f16;
-        if (h->f16) a.ln_g = h->lw(l, L_LN1W);
         // ln1 + in_proj + KV append
-        a.A = u.x; a.lda = C; a.W = h->tw(l, 0); a.bias = h->qkv_c2(l); a.N = 3 * C; a.K = C;
-        a.ln_c1 = h->qkv_c1(l); a.stats_in = u.stats; a.n_part = n_part; a.part_cnt = part_cnt;
+        SkinnyArgs a{};
+        a.M = M; a.eps = c.ln_eps; a.A = u.x; a.lda = C; a.N = 3 * C; a.K = C;
+        a.stats_in = u.stats; a.n_part = n_part; a.part_cnt = part_cnt;
         a.out = u.qkv; a.ldo = 3 * C;
         a.pool = h->kv; a.layer = l; a.page_table = u.page_table; a.max_pages = h->max_pages; a.ctx_len = u.ctx_len;
         a.lens = lens; a.T = T; a.C = C;
-        if (gv) {
-            a.W = h->lw(l, L_INW); a.bias = h->lw(l, L_INB); a.ln_c1 = nullptr; a.ln_g = h->lw(l, L_LN1W); a.ln_b = h->lw(l, L_LN1B);
-            PROF(PC_GEMM, launch_gemv(EPI_QKV, a, st));
-        } else {
-            PROF(PC_GEMM, launch_skinny(EPI_QKV, a, st));
-        }
+        PROF(PC_GEMM, decode_gemm(h, l, 0, a, gv, st));
         if (kv_only_last && l + 1 == c.n_layer) break;       // (run_blocks: the logits are dropped, the last block's K | V are appended)
         if (use_cache_attn) {
             PROF(PC_ATTN_PAGED, launch_attn_paged(u.qkv, h->kv, l, u.page_table, h->max_pages, u.ctx_len, lens, u.att, B, T, C, 1, st, &h->attn_split));
@@ -393,40 +414,21 @@ int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t
         }
         // out_proj + residual (+ stats for ln2)
         SkinnyArgs o{};
-        o.M = M; o.eps = c.ln_eps; o.w_f16 = h->f16;
-        o.A = u.att; o.lda = C; o.W = h->tw(l, 1); o.bias = h->lw(l, L_OUTB); o.N = C; o.K = C;
+        o.M = M; o.eps = c.ln_eps; o.A = u.att; o.lda = C; o.N = C; o.K = C;
         o.out = u.x; o.ldo = C; o.stats_out = u.stats;
-        if (gv) {
-            o.W = h->lw(l, L_OUTW);
-            PROF(PC_GEMM, launch_gemv(EPI_RES, o, st));
-        } else {
-            PROF(PC_GEMM, launch_skinny(EPI_RES, o, st));
-        }
+        PROF(PC_GEMM, decode_gemm(h, l, 1, o, gv, st));
         n_part = C / 16; part_cnt = 16;
         // ln2 + mlp.0 + GELU
         SkinnyArgs f{};
-        f.M = M; f.eps = c.ln_eps; f.w_f16 = h->f16;
-        if (h->f16) f.ln_g = h->lw(l, L_LN2W);
-        f.A = u.x; f.lda = C; f.W = h->tw(l, 2); f.bias = h->fc1_c2(l); f.N = F; f.K = C;
-        f.ln_c1 = h->fc1_c1(l); f.stats_in = u.stats; f.n_part = n_part; f.part_cnt = part_cnt;
+        f.M = M; f.eps = c.ln_eps; f.A = u.x; f.lda = C; f.N = F; f.K = C;
+        f.stats_in = u.stats; f.n_part = n_part; f.part_cnt = part_cnt;
         f.out = u.hbuf; f.ldo = F; f.act = ACT_GELU;
-        if (gv) {
-            f.W = h->lw(l, L_FC1W); f.bias = h->lw(l, L_FC1B); f.ln_c1 = nullptr; f.ln_g = h->lw(l, L_LN2W); f.ln_b = h->lw(l, L_LN2B);
-            PROF(PC_GEMM, launch_gemv(EPI_ACT, f, st));
-        } else {
-            PROF(PC_GEMM, launch_skinny(EPI_ACT, f, st));
-        }
+        PROF(PC_GEMM, decode_gemm(h, l, 2, f, gv, st));
         // mlp.2 + residual (+ stats for the next ln1)
         SkinnyArgs r{};
-        r.M = M; r.eps = c.ln_eps; r.w_f16 = h->f16;
-        r.A = u.hbuf; r.lda = F; r.W = h->tw(l, 3); r.bias = h->lw(l, L_FC2B); r.N = C; r.K = F;
+        r.M = M; r.eps = c.ln_eps; r.A = u.hbuf; r.lda = F; r.N = C; r.K = F;
         r.out = u.x; r.ldo = C; r.stats_out = u.stats;
-        if (gv) {
-            r.W = h->lw(l, L_FC2W);
-            PROF(PC_GEMM, launch_gemv(EPI_RES, r, st));
-        } else {
-            PROF(PC_GEMM, launch_skinny(EPI_RES, r, st));
-        }
+        PROF(PC_GEMM, decode_gemm(h, l, 3, r, gv, st));
     }
     return MGEA_OK;
 }
@@ -463,22 +465,17 @@ int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler
                                           c.seq_len, abs_pos, h->err_flag, st));
     MGEA_TRY(run_blocks_fused(h, u, B, 1, nullptr, true, st));
     SkinnyArgs a{};
-    a.w_f16 = h->f16;
-    a.M = B; a.A = u.x; a.lda = C; a.W = h->head_tw(); a.bias = h->head_b(); a.N = V; a.K = C;
+    a.M = B; a.A = u.x; a.lda = C; a.N = V; a.K = C;
     a.out = logits_out ? logits_out : (greedy ? nullptr : u.logits);
     a.ldo = V; a.pmax_val = u.pmax_val; a.pmax_idx = u.pmax_idx;
-    if (gemv_ok(h, B, 1, nullptr, true) && gemv_shape_ok(B, V, C)) {   // partial count = ceil(V / 16) = skinny_logits_tiles(B <= 2, V, C)
-        a.W = h->head_w();
-        PROF(PC_GEMM, launch_gemv(EPI_LOGITS, a, st));
-    } else {
-        PROF(PC_GEMM, launch_skinny(EPI_LOGITS, a, st));
-    }
+    DecodeGemmPlan head;   // its partial count is what the greedy tail merges
+    PROF(PC_GEMM, decode_gemm(h, 0, 4, a, gemv_ok(h, B, 1, nullptr, true) && gemv_shape_ok(B, V, C), st, &head));
     if (greedy && primed) {
-        PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, skinny_logits_tiles(B, V, C), step_state(h, u, sc.eos_id, pd),
+        PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, head.n_partials, step_state(h, u, sc.eos_id, pd),
                                                     u.sampled, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, C, V, c.seq_len,
                                                     abs_pos, st));
     } else if (greedy) {
-        PROF(PC_SAMPLE, launch_argmax_advance(u.pmax_val, u.pmax_idx, skinny_logits_tiles(B, V, C), step_state(h, u, sc.eos_id, pd),
+        PROF(PC_SAMPLE, launch_argmax_advance(u.pmax_val, u.pmax_idx, head.n_partials, step_state(h, u, sc.eos_id, pd),
                                               u.sampled, B, st));
     } else {
         if (primed) {   // sampler + loop bookkeeping + next step's embedding in one launch
@@ -785,11 +782,10 @@ int do_forward(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int B, 
     }
     if (p16) {
     } else if (logits_out && fused_ok(h, (int)M)) {
-        SkinnyArgs a{};  // x is k-tiled on the fused path: the head is the skinny LOGITS kernel
-        a.w_f16 = h->f16;
-        a.M = (int)M; a.A = h->x; a.lda = C; a.W = h->head_tw(); a.bias = h->head_b(); a.N = V; a.K = C;
+        SkinnyArgs a{};  // x is k-tiled on the fused path: the head is a decode GEMM (LOGITS epilogue) on the tiled weights
+        a.M = (int)M; a.A = h->x; a.lda = C; a.N = V; a.K = C;
         a.out = logits_out; a.ldo = V;
-        MGEA_TRY(launch_skinny(EPI_LOGITS, a, st));
+        MGEA_TRY(decode_gemm(h, 0, 4, a, false, st));
     } else if (logits_out) {
         for (int64_t r0 = 0; r0 < M; r0 += 4096) {
             const int rows = (int)((M - r0) < 4096 ? (M - r0) : 4096);

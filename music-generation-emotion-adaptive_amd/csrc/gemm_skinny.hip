@@ -388,104 +388,142 @@ static int pick_waves(int K, bool ln, int mt) {
     return 1;
 }
 
-template <int EPI, int MT, int NT = 1>
-static int launch_skinny_mt(const SkinnyArgs& a_in, int nw, hipStream_t st) {
-    const bool ln = a_in.ln_c1 != nullptr;
-    SkinnyArgs a = a_in;
-    a.nw = nw;
-    if (ln) {
-        a.inv_n_part = (float)(1.0 / (double)a.n_part);
-        a.inv_k = (float)(1.0 / ((double)a.n_part * (double)a.part_cnt));
-    }
-    dim3 grid((unsigned)round_up(ceil_div(a.N, 16 * NT), 8), ceil_div(a.M, 16 * MT)), block(64 * nw);
-    const size_t shmem = ((size_t)nw * 16 * MT * (16 * NT + 4) + (ln ? 2 * 16 * MT : 0)) * sizeof(float);
-    // compile-time chunk counts for the decode shapes (8 waves x NCH chunks of 32): K = 512 (NCH 2), 768 (3), 2048 (8); anything
-    // else, other wave counts and the timestamp mode of tools/skinny_phases.py take the generic stream (NCH 0)
-    const int nch = (nw == 8 && !(a.dbg & (1 << 20)) && a.K % 256 == 0) ? a.K / 256 : 0;
-    // switch skinny_one_per_cu (A/B, round 4): pad the dynamic LDS request beyond half a CU's 160 KB so that no two workgroups of a launch with
-    // <= 256 workgroups can share a CU (the head kernel of head_gemm.hip relies on the same effect)
-    const bool one_per_cu = tune(TUNE_SKINNY_ONE_PER_CU) && grid.x * grid.y <= 256;
-    const size_t shmem_go = one_per_cu && shmem < 84 * 1024 ? 84 * 1024 : shmem;
-#define MGEA_SKINNY_GO(LNV, NTV, F16V, NCHV)                                                                                              \
-    do {                                                                                                                                 \
-        if (one_per_cu) {                                                                                                                \
-            static uint64_t attr_done = 0;                                                                                               \
-            DeviceInfo di;                                                                                                               \
-            MGEA_TRY(device_info(&di));                                                                                                  \
-            MGEA_TRY(set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_skinny_kernel<EPI, LNV, MT, NTV, F16V, NCHV>), 84 * 1024, di.dev, &attr_done)); \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((gemm_skinny_kernel<EPI, LNV, MT, NTV, F16V, NCHV>), grid, block, shmem_go, st, a);                           \
-    } while (0)
-#define MGEA_SKINNY_NCH(LNV, NTV, F16V)                                                                  \
-    do {                                                                                                 \
-        if (nch == 2) MGEA_SKINNY_GO(LNV, NTV, F16V, 2);                                                  \
-        else if (nch == 3) MGEA_SKINNY_GO(LNV, NTV, F16V, 3);                                             \
-        else if (nch == 8 && MT * NTV <= 2) MGEA_SKINNY_GO(LNV, NTV, F16V, 8);                            \
-        else MGEA_SKINNY_GO(LNV, NTV, F16V, 0);                                                           \
-    } while (0)
-    if (a.w_f16) {
-        if (ln && NT == 1) MGEA_SKINNY_NCH(true, 1, true);
-        else               MGEA_SKINNY_NCH(false, NT, true);
-    } else {
-        if (ln && NT == 1) MGEA_SKINNY_NCH(true, 1, false);
-        else               MGEA_SKINNY_NCH(false, NT, false);
-    }
-#undef MGEA_SKINNY_NCH
-#undef MGEA_SKINNY_GO
-    MGEA_CHECK_HIP(hipGetLastError());
+// the LM head as one balanced round of the chip (head_gemm.hip) where the shape allows: 3..64 rows (1-2 rows run as dot products),
+// K = 8 waves x NCH chunks of 32, at least one column tile per CU and at most one extra unit per workgroup
+static bool plan_head(const SkinnyArgs& a, DecodeGemmPlan* p) {
+    if (!tune(TUNE_HEAD_BALANCED) || a.M < 3 || a.M > 64) return false;
+    if (a.K != 256 && a.K != 512 && a.K != 768) return false;
+    DeviceInfo di;
+    if (device_info(&di) != MGEA_OK) return false;
+    const int G = di.n_cu / 8 * 8;
+    if (G < 8) return false;
+    const int J = ceil_div(a.N, 16), base = J / G, rem = J - base * G;
+    if (base < 1 || base > 3 || 4 * rem > G) return false;
+    if (base == 3 && a.K == 768) return false;          // (13 accumulator tiles + 3-chunk fragments of 4 + 4 tiles: over the register budget)
+    const bool stamped = (a.dbg >> 21) & 1;             // tools/head_phases.py: the stamped build of the benchmark's instantiation
+    if (stamped && (base != 2 || a.K != 512 || a.w_f16 || !a.stats_out)) return false;
+    const int NU = 4 * base + 1, NS = 4 * (base + 1);
+    const int shmem = (8 * NU * 16 * HB_PITCH + 64 * NS * 2) * (int)sizeof(float);
+    p->kind = DG_HEAD;
+    p->base = base; p->nch = a.K / 256; p->f16 = a.w_f16; p->stamped = stamped; p->n_extra = 4 * rem;
+    p->grid = dim3(G); p->block = dim3(512);
+    p->shmem = shmem < 84 * 1024 ? 84 * 1024 : shmem;   // more than half of a CU's 160 KB: one workgroup per CU
+    p->raise_lds = true;
+    p->n_partials = G;
+    return true;
+}
+
+static int plan_gemv(int epi, const SkinnyArgs& a, DecodeGemmPlan* p) {
+    MGEA_REQUIRE(gemv_shape_ok(a.M, a.N, a.K), MGEA_EINVAL, "gemv: M=%d (1..2) N=%d K=%d (multiple of 256)", a.M, a.N, a.K);
+    MGEA_REQUIRE(epi == EPI_LOGITS || a.N % 8 == 0, MGEA_EINVAL, "gemv: N=%d must be a multiple of 8", a.N);
+    MGEA_REQUIRE(epi != EPI_QKV || (a.T == 1 && !a.lens), MGEA_EINVAL, "gemv: the QKV epilogue handles single-token decode steps only");
+    MGEA_REQUIRE(!a.w_f16 && !(epi == EPI_QKV && a.pool.f16), MGEA_EINVAL, "gemv: fp32 weights and KV pages only");
+    MGEA_REQUIRE(!a.ln_g || (a.ln_b && a.K <= 1024), MGEA_EINVAL, "gemv: LayerNorm prologue needs beta and K <= 1024 (K=%d)", a.K);
+    p->kind = DG_GEMV;
+    p->ln = a.ln_g != nullptr;
+    p->cw = epi == EPI_LOGITS ? 4 : (a.N >= 2048 ? 2 : 1);   // columns per wave: enough workgroups for the chip, not more than ~2 per CU
+    p->mr = a.M;
+    p->grid = dim3(ceil_div(a.N, 4 * p->cw)); p->block = dim3(256);
+    p->n_partials = epi == EPI_LOGITS ? (int)p->grid.x : 0;   // one per workgroup
     return MGEA_OK;
 }
 
-template <int EPI>
-static int launch_skinny_t(const SkinnyArgs& a, hipStream_t st) {
+int plan_decode_gemm(int epi, const SkinnyArgs& a, bool rowmajor_gemv, DecodeGemmPlan* p) {
+    *p = DecodeGemmPlan{};
+    MGEA_REQUIRE(epi >= EPI_QKV && epi <= EPI_LOGITS, MGEA_EINVAL, "decode gemm: bad epilogue %d", epi);
+    if (rowmajor_gemv) return plan_gemv(epi, a, p);
     const bool ln = a.ln_c1 != nullptr;
     MGEA_REQUIRE(a.M >= 1 && a.M <= MGEA_FUSED_MAX_ROWS, MGEA_EINVAL, "skinny gemm: M=%d not in 1..%d", a.M, MGEA_FUSED_MAX_ROWS);
     MGEA_REQUIRE(a.K % 32 == 0, MGEA_EINVAL, "skinny gemm: K=%d must be a multiple of 32", a.K);
-    MGEA_REQUIRE(EPI == EPI_LOGITS || a.N % 16 == 0, MGEA_EINVAL, "skinny gemm: N=%d must be a multiple of 16", a.N);
-    if (EPI == EPI_LOGITS) {   // decode-step head: one balanced round of the chip where the shape allows (head_gemm.hip)
-        const int rc = launch_head_balanced(a, st);
-        if (rc != 1) return rc;
+    MGEA_REQUIRE(epi == EPI_LOGITS || a.N % 16 == 0, MGEA_EINVAL, "skinny gemm: N=%d must be a multiple of 16", a.N);
+    MGEA_REQUIRE(!(epi == EPI_LOGITS && ln), MGEA_EINVAL, "skinny gemm: the LOGITS epilogue takes no folded LayerNorm (ln_c1)");
+    MGEA_REQUIRE(!(epi == EPI_QKV && !ln), MGEA_EINVAL, "skinny gemm: the QKV epilogue needs the folded LayerNorm (ln_c1)");
+    if (epi == EPI_LOGITS && !(a.dbg & ~(1 << 21)) && plan_head(a, p)) return MGEA_OK;
+    int mt, nt = 1, nw;
+    if (epi == EPI_LOGITS && a.M > 32 && a.N >= 4096 && !((a.dbg >> 8) & 0x1FF)) {
+        mt = 2; nt = 2;   // LM head: 32 rows x 32 columns per workgroup, W fetched from HBM once
+        nw = pick_waves(a.K, false, 2);
+    } else {
+        mt = ((a.dbg >> 8) & 15) ? ((a.dbg >> 8) & 15) : pick_mt(a.M, a.N);
+        nw = pick_waves(a.K, ln, mt);
+        if ((a.dbg >> 12) & 31) nw = (a.dbg >> 12) & 31;  // tools/skinny_bench.py override
+        while (ln && mt > 1 && nw * 64 < 16 * mt * 16) mt /= 2;   // the LN merge wants 16 lanes per tile row
+        MGEA_REQUIRE((a.K / 32) % nw == 0 && nw <= 8, MGEA_EINVAL, "skinny gemm: bad wave count %d", nw);
+        MGEA_REQUIRE(!ln || a.n_part <= 64, MGEA_EINVAL, "skinny gemm: more than 64 LayerNorm partials per row (%d)", a.n_part);
+        MGEA_REQUIRE(!(ln && a.w_f16) || a.ln_g, MGEA_EINVAL, "skinny gemm: the fp16 folded LayerNorm needs gamma (ln_g)");
+        MGEA_REQUIRE(!ln || a.n_part % 2 == 0, MGEA_EINVAL, "skinny gemm: odd number of LayerNorm partials per row (%d)", a.n_part);
+        MGEA_REQUIRE(!ln || nw * 64 >= 16 * mt * 16, MGEA_EINVAL,
+                     "skinny gemm: the LayerNorm merge needs 16 lanes per tile row (K=%d, %d-row tiles, %d waves)", a.K, 16 * mt, nw);
+        MGEA_REQUIRE(mt == 1 || mt == 2 || mt == 4, MGEA_EINVAL, "skinny gemm: bad row-tile count %d", mt);
     }
-    if (EPI == EPI_LOGITS && !ln && a.M > 32 && a.N >= 4096 && !((a.dbg >> 8) & 0x1FF)) {
-        // LM head: 32 rows x 32 columns per workgroup, W fetched from HBM once
-        const int nw_head = pick_waves(a.K, false, 2);
-        return launch_skinny_mt<EPI_LOGITS, 2, 2>(a, nw_head, st);
-    }
-    int mt = ((a.dbg >> 8) & 15) ? ((a.dbg >> 8) & 15) : pick_mt(a.M, a.N);
-    int nw = pick_waves(a.K, ln, mt);
-    if ((a.dbg >> 12) & 31) nw = (a.dbg >> 12) & 31;  // tools/skinny_bench.py override
-    while (ln && mt > 1 && nw * 64 < 16 * mt * 16) mt /= 2;   // the LN merge wants 16 lanes per tile row
-    MGEA_REQUIRE((a.K / 32) % nw == 0 && nw <= 8, MGEA_EINVAL, "skinny gemm: bad wave count %d", nw);
-    MGEA_REQUIRE(!ln || a.n_part <= 64, MGEA_EINVAL, "skinny gemm: more than 64 LayerNorm partials per row (%d)", a.n_part);
-    MGEA_REQUIRE(!(ln && a.w_f16) || a.ln_g, MGEA_EINVAL, "skinny gemm: the fp16 folded LayerNorm needs gamma (ln_g)");
-    MGEA_REQUIRE(!ln || a.n_part % 2 == 0, MGEA_EINVAL, "skinny gemm: odd number of LayerNorm partials per row (%d)", a.n_part);
-    MGEA_REQUIRE(!ln || nw * 64 >= 16 * mt * 16, MGEA_EINVAL,
-                 "skinny gemm: the LayerNorm merge needs 16 lanes per tile row (K=%d, %d-row tiles, %d waves)", a.K, 16 * mt, nw);
-    switch (mt) {
-        case 1: return launch_skinny_mt<EPI, 1>(a, nw, st);
-        case 2: return launch_skinny_mt<EPI, 2>(a, nw, st);
-        case 4: return launch_skinny_mt<EPI, 4>(a, nw, st);
-    }
-    set_error("skinny gemm: bad row-tile count %d", mt);
-    return MGEA_EINVAL;
+    // compile-time chunk counts for the decode shapes (8 waves x NCH chunks of 32): K = 512 (NCH 2), 768 (3), 2048 (8, <= 32 x 16
+    // tiles); anything else, other wave counts and the timestamp mode of tools/skinny_phases.py take the generic stream (NCH 0)
+    const int nch = (nw == 8 && !(a.dbg & (1 << 20)) && a.K % 256 == 0) ? a.K / 256 : 0;
+    p->kind = DG_SKINNY;
+    p->mt = mt; p->nt = nt; p->nw = nw; p->ln = ln; p->f16 = a.w_f16;
+    p->nch = (nch == 2 || nch == 3 || (nch == 8 && mt * nt <= 2)) ? nch : 0;
+    p->grid = dim3((unsigned)round_up(ceil_div(a.N, 16 * nt), 8), ceil_div(a.M, 16 * mt));
+    p->block = dim3(64 * nw);
+    p->shmem = (nw * 16 * mt * (16 * nt + 4) + (ln ? 2 * 16 * mt : 0)) * (int)sizeof(float);
+    // switch skinny_one_per_cu (A/B, round 4): pad the dynamic LDS request beyond half a CU's 160 KB so that no two workgroups of a launch with
+    // <= 256 workgroups can share a CU (the head kernel relies on the same effect)
+    p->raise_lds = tune(TUNE_SKINNY_ONE_PER_CU) && p->grid.x * p->grid.y <= 256;
+    if (p->raise_lds && p->shmem < 84 * 1024) p->shmem = 84 * 1024;
+    p->n_partials = epi == EPI_LOGITS ? ceil_div(a.N, 16 * nt) : 0;   // one per column tile (gemm_skinny_kernel's n_tiles)
+    return MGEA_OK;
 }
 
-// number of per-row partial (max, argmax) entries the LOGITS epilogue writes = its grid.x
-int skinny_logits_tiles(int M, int N, int K) {   // K = 0: the generic kernel's count whatever the shape
-    const int g = K > 0 ? head_balanced_partials(M, N, K) : 0;
-    if (g) return g;
-    return (M > 32 && N >= 4096) ? ceil_div(N, 32) : ceil_div(N, 16);
+// the gemm_skinny_kernel instantiation a DG_SKINNY plan names
+template <int EPI, bool LN, int MT, int NT, bool F16>
+static KernelRef skinny_nch(int nch) {
+    switch (nch) {
+        case 2: return kernel_ref<&gemm_skinny_kernel<EPI, LN, MT, NT, F16, 2>>();
+        case 3: return kernel_ref<&gemm_skinny_kernel<EPI, LN, MT, NT, F16, 3>>();
+        case 8: return kernel_ref<&gemm_skinny_kernel<EPI, LN, MT, NT, F16, 8>>();
+    }
+    return kernel_ref<&gemm_skinny_kernel<EPI, LN, MT, NT, F16, 0>>();
+}
+template <int EPI, bool LN, int MT, int NT>
+static KernelRef skinny_f16(const DecodeGemmPlan& p) {
+    return p.f16 ? skinny_nch<EPI, LN, MT, NT, true>(p.nch) : skinny_nch<EPI, LN, MT, NT, false>(p.nch);
+}
+template <int EPI, bool LN>
+static KernelRef skinny_tiles(const DecodeGemmPlan& p) {
+    if constexpr (EPI == EPI_LOGITS) {
+        if (p.nt == 2) return skinny_f16<EPI, LN, 2, 2>(p);
+    }
+    if (p.mt == 1) return skinny_f16<EPI, LN, 1, 1>(p);
+    if (p.mt == 2) return skinny_f16<EPI, LN, 2, 1>(p);
+    return skinny_f16<EPI, LN, 4, 1>(p);
+}
+static KernelRef skinny_kernel(int epi, const DecodeGemmPlan& p) {
+    switch (epi) {   // (the plan gives QKV always and LOGITS never a folded LayerNorm)
+        case EPI_QKV: return skinny_tiles<EPI_QKV, true>(p);
+        case EPI_RES: return p.ln ? skinny_tiles<EPI_RES, true>(p) : skinny_tiles<EPI_RES, false>(p);
+        case EPI_ACT: return p.ln ? skinny_tiles<EPI_ACT, true>(p) : skinny_tiles<EPI_ACT, false>(p);
+        case EPI_LOGITS: return skinny_tiles<EPI_LOGITS, false>(p);
+    }
+    return KernelRef{};
 }
 
-int launch_skinny(int epi, const SkinnyArgs& a, hipStream_t st) {
-    switch (epi) {
-        case EPI_QKV: return launch_skinny_t<EPI_QKV>(a, st);
-        case EPI_RES: return launch_skinny_t<EPI_RES>(a, st);
-        case EPI_ACT: return launch_skinny_t<EPI_ACT>(a, st);
-        case EPI_LOGITS: return launch_skinny_t<EPI_LOGITS>(a, st);
+int launch_decode_gemm(int epi, const DecodeGemmPlan& p, const SkinnyArgs& a_in, hipStream_t st) {
+    SkinnyArgs a = a_in;
+    int n_extra = p.n_extra;
+    void* args[] = {&a, &n_extra};   // (only head_balanced_kernel takes the second)
+    const KernelRef k = p.kind == DG_HEAD ? head_kernel(p) : p.kind == DG_GEMV ? gemv_kernel(epi, p) : skinny_kernel(epi, p);
+    if (p.kind == DG_SKINNY) a.nw = p.nw;
+    if (p.kind == DG_SKINNY && p.ln) {
+        a.inv_n_part = (float)(1.0 / (double)a.n_part);
+        a.inv_k = (float)(1.0 / ((double)a.n_part * (double)a.part_cnt));
     }
-    set_error("skinny gemm: bad epilogue %d", epi);
-    return MGEA_EINVAL;
+    MGEA_REQUIRE(k.fn, MGEA_EINVAL, "decode gemm: no kernel for plan family %d, epilogue %d", p.kind, epi);
+    if (p.raise_lds) {
+        DeviceInfo di;
+        MGEA_TRY(device_info(&di));
+        MGEA_TRY(set_max_dynamic_lds(k.fn, p.shmem, di.dev, k.lds_raised));
+    }
+    MGEA_CHECK_HIP(hipLaunchKernel(k.fn, p.grid, p.block, args, p.shmem, st));
+    return MGEA_OK;
 }
 
 // ------------------------------------------------------------------------------------------

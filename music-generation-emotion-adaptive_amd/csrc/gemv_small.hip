@@ -211,44 +211,29 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(SkinnyArgs a) {
 // -> the MFMA path takes over from 3 rows
 bool gemv_shape_ok(int M, int N, int K) { return M >= 1 && M <= 2 && K % 256 == 0 && K <= 4096 && N >= 4; }
 
-// columns per wave: enough workgroups for the chip, not more than ~2 per CU
-static int gemv_cw(int epi, int N) {
-    if (epi == EPI_LOGITS) return 4;   // 16 columns per workgroup = the partial count of skinny_logits_tiles (M <= 32)
-    return N >= 2048 ? 2 : 1;
-}
-
+// the instantiation a DG_GEMV plan names (plan_decode_gemm, gemm_skinny.hip)
 template <int EPI, int CW, int MR>
-static int launch_gemv_m(const SkinnyArgs& a, hipStream_t st) {
-    const dim3 grid(ceil_div(a.N, 4 * CW)), block(256);
-    if (a.ln_g) hipLaunchKernelGGL((gemv_rows_kernel<EPI, true, CW, MR>), grid, block, 0, st, a);
-    else        hipLaunchKernelGGL((gemv_rows_kernel<EPI, false, CW, MR>), grid, block, 0, st, a);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
+static KernelRef gemv_ln(const DecodeGemmPlan& p) {
+    return p.ln ? kernel_ref<&gemv_rows_kernel<EPI, true, CW, MR>>() : kernel_ref<&gemv_rows_kernel<EPI, false, CW, MR>>();
 }
-
 template <int EPI, int CW>
-static int launch_gemv_t(const SkinnyArgs& a, hipStream_t st) {
-    if (a.M == 1) return launch_gemv_m<EPI, CW, 1>(a, st);
-    if (a.M == 2) return launch_gemv_m<EPI, CW, 2>(a, st);
-    return launch_gemv_m<EPI, CW, 4>(a, st);
+static KernelRef gemv_mr(const DecodeGemmPlan& p) {
+    if (p.mr == 1) return gemv_ln<EPI, CW, 1>(p);
+    if (p.mr == 2) return gemv_ln<EPI, CW, 2>(p);
+    return gemv_ln<EPI, CW, 4>(p);
 }
-
-// a.W = ROW-MAJOR [N, K] weights, a.ln_g / a.ln_b = LayerNorm gamma / beta (or NULL), a.A / a.out k-tiled as in launch_skinny
-int launch_gemv(int epi, const SkinnyArgs& a, hipStream_t st) {
-    MGEA_REQUIRE(gemv_shape_ok(a.M, a.N, a.K), MGEA_EINVAL, "gemv: M=%d (1..2) N=%d K=%d (multiple of 256)", a.M, a.N, a.K);
-    MGEA_REQUIRE(epi == EPI_LOGITS || a.N % 8 == 0, MGEA_EINVAL, "gemv: N=%d must be a multiple of 8", a.N);
-    MGEA_REQUIRE(epi != EPI_QKV || (a.T == 1 && !a.lens), MGEA_EINVAL, "gemv: the QKV epilogue handles single-token decode steps only");
-    MGEA_REQUIRE(!a.w_f16 && !(epi == EPI_QKV && a.pool.f16), MGEA_EINVAL, "gemv: fp32 weights and KV pages only");
-    MGEA_REQUIRE(!a.ln_g || (a.ln_b && a.K <= 1024), MGEA_EINVAL, "gemv: LayerNorm prologue needs beta and K <= 1024 (K=%d)", a.K);
-    const int cw = gemv_cw(epi, a.N);
+template <int EPI>
+static KernelRef gemv_cw(const DecodeGemmPlan& p) {
+    return p.cw == 2 ? gemv_mr<EPI, 2>(p) : gemv_mr<EPI, 1>(p);
+}
+KernelRef gemv_kernel(int epi, const DecodeGemmPlan& p) {
     switch (epi) {
-        case EPI_QKV: return cw == 2 ? launch_gemv_t<EPI_QKV, 2>(a, st) : launch_gemv_t<EPI_QKV, 1>(a, st);
-        case EPI_RES: return cw == 2 ? launch_gemv_t<EPI_RES, 2>(a, st) : launch_gemv_t<EPI_RES, 1>(a, st);
-        case EPI_ACT: return cw == 2 ? launch_gemv_t<EPI_ACT, 2>(a, st) : launch_gemv_t<EPI_ACT, 1>(a, st);
-        case EPI_LOGITS: return launch_gemv_t<EPI_LOGITS, 4>(a, st);
+        case EPI_QKV: return gemv_cw<EPI_QKV>(p);
+        case EPI_RES: return gemv_cw<EPI_RES>(p);
+        case EPI_ACT: return gemv_cw<EPI_ACT>(p);
+        case EPI_LOGITS: return gemv_mr<EPI_LOGITS, 4>(p);
     }
-    set_error("gemv: unknown epilogue %d", epi);
-    return MGEA_EINVAL;
+    return KernelRef{};
 }
 
 }  // namespace mgea

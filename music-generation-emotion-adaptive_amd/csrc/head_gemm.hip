@@ -29,8 +29,6 @@
 namespace mgea {
 
 namespace {
-constexpr int HB_PITCH = 20;   // floats per LDS row of a partial tile (16 + 4: the 16 rows of one ds_write_b128 start in different banks)
-
 // TS (tools/head_phases.py only, dbg bit 21; never in an engine): lane 0 of every wave writes 100 MHz stamps of its phases to stats_out
 template <int BASE, int NCH, bool F16, bool TS = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void head_balanced_kernel(SkinnyArgs a, int n_extra) {
@@ -212,70 +210,31 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef HB_TS
 }
 
-struct HeadPlan { int G, base, n_extra, nch; };
-
-// the shapes this kernel takes: 3..64 rows (1-2 rows run as dot products, gemv_small.hip), K = 8 waves x NCH chunks of 32,
-// at least one column tile per CU and at most one extra unit per workgroup
-bool head_plan(int M, int N, int K, HeadPlan* p) {
-    if (!tune(TUNE_HEAD_BALANCED) || M < 3 || M > 64) return false;
-    if (K != 256 && K != 512 && K != 768) return false;
-    DeviceInfo di;
-    if (device_info(&di) != MGEA_OK) return false;
-    const int G = di.n_cu / 8 * 8;
-    if (G < 8) return false;
-    const int J = ceil_div(N, 16), base = J / G, rem = J - base * G;
-    if (base < 1 || base > 3 || 4 * rem > G) return false;
-    if (base == 3 && K == 768) return false;          // (13 accumulator tiles + 3-chunk fragments of 4 + 4 tiles: over the register budget)
-    *p = HeadPlan{G, base, 4 * rem, K / 256};
-    return true;
+// the instantiation a DG_HEAD plan names (plan_decode_gemm, gemm_skinny.hip)
+template <int BASE, int NCH>
+KernelRef head_f16(const DecodeGemmPlan& p) {
+    return p.f16 ? kernel_ref<&head_balanced_kernel<BASE, NCH, true>>() : kernel_ref<&head_balanced_kernel<BASE, NCH, false>>();
+}
+template <int BASE>
+KernelRef head_nch(const DecodeGemmPlan& p) {
+    switch (p.nch) {
+        case 1: return head_f16<BASE, 1>(p);
+        case 2: return head_f16<BASE, 2>(p);
+        case 3:
+            if constexpr (BASE < 3) return head_f16<BASE, 3>(p);   // (3, 3) is over the register budget: the plan never names it
+    }
+    return KernelRef{};
 }
 }  // namespace
 
-// partial (max, argmax) entries per row the LOGITS launch of this shape writes, or 0 when the balanced kernel does not take it
-int head_balanced_partials(int M, int N, int K) {
-    HeadPlan p;
-    return head_plan(M, N, K, &p) ? p.G : 0;
-}
-
-template <int BASE, int NCH, bool F16>
-static int launch_head_t(const SkinnyArgs& a, const HeadPlan& p, hipStream_t st) {
-    constexpr int NU = 4 * BASE + 1, NS = 4 * (BASE + 1);
-    int shmem = (8 * NU * 16 * HB_PITCH + 64 * NS * 2) * (int)sizeof(float);
-    if (shmem < 84 * 1024) shmem = 84 * 1024;           // more than half of a CU's 160 KB: one workgroup per CU
-    DeviceInfo di;
-    MGEA_TRY(device_info(&di));
-    static uint64_t attr_done = 0;
-    MGEA_TRY(set_max_dynamic_lds(reinterpret_cast<const void*>(&head_balanced_kernel<BASE, NCH, F16>), shmem, di.dev, &attr_done));
-    hipLaunchKernelGGL((head_balanced_kernel<BASE, NCH, F16>), dim3(p.G), dim3(512), shmem, st, a, p.n_extra);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// returns MGEA_OK after launching, or 1 when the shape is not this kernel's (the caller falls back to gemm_skinny_kernel)
-int launch_head_balanced(const SkinnyArgs& a, hipStream_t st) {
-    HeadPlan p;
-    if (a.ln_c1 || (a.dbg & ~(1 << 21)) || !head_plan(a.M, a.N, a.K, &p)) return 1;
-    if (a.dbg & (1 << 21)) {    // tools/head_phases.py: the stamped build of the benchmark's instantiation
-        if (p.base != 2 || p.nch != 2 || a.w_f16 || !a.stats_out) return 1;
-        constexpr int NU = 9, NS = 12;
-        int shmem = (8 * NU * 16 * HB_PITCH + 64 * NS * 2) * (int)sizeof(float);
-        if (shmem < 84 * 1024) shmem = 84 * 1024;
-        DeviceInfo di;
-        MGEA_TRY(device_info(&di));
-        static uint64_t ts_done = 0;
-        MGEA_TRY(set_max_dynamic_lds(reinterpret_cast<const void*>(&head_balanced_kernel<2, 2, false, true>), shmem, di.dev, &ts_done));
-        hipLaunchKernelGGL((head_balanced_kernel<2, 2, false, true>), dim3(p.G), dim3(512), shmem, st, a, p.n_extra);
-        MGEA_CHECK_HIP(hipGetLastError());
-        return MGEA_OK;
+KernelRef head_kernel(const DecodeGemmPlan& p) {
+    if (p.stamped) return kernel_ref<&head_balanced_kernel<2, 2, false, true>>();   // tools/head_phases.py
+    switch (p.base) {
+        case 1: return head_nch<1>(p);
+        case 2: return head_nch<2>(p);
+        case 3: return head_nch<3>(p);
     }
-#define MGEA_HEAD_GO(B_, N_)                                                              \
-    if (p.base == B_ && p.nch == N_)                                                      \
-        return a.w_f16 ? launch_head_t<B_, N_, true>(a, p, st) : launch_head_t<B_, N_, false>(a, p, st);
-    MGEA_HEAD_GO(1, 1) MGEA_HEAD_GO(1, 2) MGEA_HEAD_GO(1, 3)
-    MGEA_HEAD_GO(2, 1) MGEA_HEAD_GO(2, 2) MGEA_HEAD_GO(2, 3)
-    MGEA_HEAD_GO(3, 1) MGEA_HEAD_GO(3, 2)
-#undef MGEA_HEAD_GO
-    return 1;
+    return KernelRef{};
 }
 
 }  // namespace mgea

@@ -222,11 +222,12 @@ def head(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, want_logits: bool
     N = w.shape[0]
     at, wt, b = tile_rows(a), tile_weights(w), _dev(bias.float())
     P = int(lib.mgea_op_skinny_logits_partials(M, N, K))
-    part = torch.full((2 * 64 * P + 64,), float("nan"), dtype=torch.float32, device=a.device)
+    R = max(64, M)   # rows of each half of the partials buffer (mgea.h)
+    part = torch.full((2 * R * P + 64,), float("nan"), dtype=torch.float32, device=a.device)
     out = torch.full((M, N), float("nan"), dtype=torch.float32, device=a.device) if want_logits else None
     check(lib.mgea_op_skinny(3, ptr(at), ptr(wt), ptr(b), None, None, 0, 16, ptr(out), ptr(part), M, N, K, 0, 0, stream_ptr()))
-    val = part[: 64 * P].view(64, P)[:M]
-    idx = part[64 * P: 2 * 64 * P].view(torch.int32).view(64, P)[:M].long()
+    val = part[: R * P].view(R, P)[:M]
+    idx = part[R * P: 2 * R * P].view(torch.int32).view(R, P)[:M].long()
     best = val.max(1, keepdim=True).values
     cand = torch.where(val == best, idx, torch.full_like(idx, 2 ** 31 - 1))
     return out, cand.min(1).values, P

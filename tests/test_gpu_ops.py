@@ -324,3 +324,60 @@ def test_lm_head_balanced_one_round_kernel_equals_the_generic_kernel_bitwise(ops
         tune("head_balanced", sw)
         lg, am, _ = ops.head(a.cuda(), w.cuda(), b2.cuda(), want_logits=(sw == 1))
         assert am.cpu().tolist() == [hi[0]] * M
+
+
+def _head_operands(ops, M, N, K, seed):
+    a = rnd(M, K, seed=seed)
+    w = rnd(N, K, seed=seed + 1, scale=K ** -0.5)
+    b = rnd(N, seed=seed + 2)
+    return ops.tile_rows(a.cuda()), ops.tile_weights(w.cuda()), b.cuda()
+
+
+@pytest.mark.parametrize("M,N,K", [(3, 8324, 512), (64, 5008, 256), (48, 8324, 1024), (64, 300, 512), (2, 8324, 512), (96, 8324, 512)])
+def test_lm_head_partials_fill_exactly_the_documented_layout(ops, M, N, K):
+    """mgea_op_skinny(epi = 3) on one shape of every head plan -- the balanced one-round kernel (3 and 64 rows), the generic kernel with
+    32 x 32 tiles (48 rows at K = 1024, and 96 rows: more than 64), with 16-column tiles (N = 300) and on two rows -- writes its P
+    (max, argmax) partials per row into a buffer of exactly the layout mgea.h documents (values [max(64, M)][P], then the indices in
+    the same layout): every partial of rows < M is written, nothing else is touched, not even the canary behind the buffer, and the
+    partials merge to torch.argmax of the logits the same launch returns."""
+    from mgea import _lib
+    lib = _lib.load()
+    at, wt, b = _head_operands(ops, M, N, K, seed=81)
+    P = int(lib.mgea_op_skinny_logits_partials(M, N, K))
+    assert P > 0
+    R, CANARY = max(64, M), 4096
+    buf = torch.full((2 * R * P + CANARY,), float("nan"), dtype=torch.float32, device="cuda")
+    buf[2 * R * P:] = 1234.5
+    out = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+    _lib.check(lib.mgea_op_skinny(3, _lib.ptr(at), _lib.ptr(wt), _lib.ptr(b), None, None, 0, 16, _lib.ptr(out), _lib.ptr(buf),
+                                  M, N, K, 0, 0, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    buf, lg = buf.cpu(), out.cpu()
+    assert bool((buf[2 * R * P:] == 1234.5).all()), "the partials overran their buffer"
+    val = buf[:R * P].view(R, P)
+    idx_f = buf[R * P:2 * R * P].view(R, P)
+    idx = idx_f.view(torch.int32)
+    assert not bool(val[:M].isnan().any()), "a value partial of a live row was not written"
+    assert not bool(idx_f[:M].isnan().any()), "an index partial of a live row was not written"
+    assert bool(val[M:].isnan().all()) and bool(idx_f[M:].isnan().all()), "rows >= M were written"
+    assert not bool(lg.isnan().any())
+    best = val[:M].max(1, keepdim=True).values
+    merged = torch.where(val[:M] == best, idx[:M], torch.full_like(idx[:M], 2 ** 31 - 1)).min(1).values
+    assert merged.long().tolist() == lg.argmax(1).tolist()
+
+
+def test_lm_head_refuses_a_folded_layernorm(ops):
+    """The LOGITS epilogue has no folded-LayerNorm form: mgea_op_skinny(epi = 3) with ln_c1 returns MGEA_EINVAL and launches nothing."""
+    from mgea import _lib
+    lib = _lib.load()
+    M, N, K = 64, 8324, 512
+    at, wt, b = _head_operands(ops, M, N, K, seed=91)
+    c1 = torch.ones(N, dtype=torch.float32, device="cuda")
+    stats = torch.zeros(M * (K // 16) * 2, dtype=torch.float32, device="cuda")
+    buf = torch.full((2 * 64 * ((N + 15) // 16) + 64,), float("nan"), dtype=torch.float32, device="cuda")
+    out = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+    rc = lib.mgea_op_skinny(3, _lib.ptr(at), _lib.ptr(wt), _lib.ptr(b), _lib.ptr(c1), _lib.ptr(stats), K // 16, 16, _lib.ptr(out),
+                            _lib.ptr(buf), M, N, K, 0, 0, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == _lib.EINVAL
+    assert bool(buf.isnan().all()) and bool(out.isnan().all())
