@@ -143,6 +143,23 @@ int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const 
                           int32_t B, int32_t Tp, int32_t n_steps, const mgea_sampler_config* s,
                           int32_t* ids_out_dev, void* stream);
 
+/* mgea_decoder_generate with a repetition penalty (HF RepetitionPenaltyLogitsProcessor; the paper's decoding setting is top_p 0.92
+ * with penalty 1.1).  At every decode step of row b, seen_b = the SET of row b's real prompt tokens (padding of a ragged prompt
+ * excluded) and of the ids the row generated so far; the raw head logit x of every id in seen_b becomes x < 0 ? x * p : x / p (one
+ * correctly rounded fp32 operation, p as fp32), unseen ids are untouched, and the sampler then runs unchanged on the result:
+ * / temperature, top-k, top-p, softmax, Philox draw.  top_k == 1 is the argmax of the penalized row (ties to the lowest id).  A row
+ * that drew eos_id is finished and its set is no longer updated.  The penalty travels in the device record with the other sampler
+ * scalars, so one captured graph per (batch size, greedy | sampled) serves every penalty value.  repetition_penalty must be finite
+ * and > 0 (MGEA_EINVAL otherwise); < 1 favours repeats; == 1 IS mgea_decoder_generate (same launches, same results). */
+int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev,
+                                    int32_t B, int32_t Tp, int32_t n_steps, const mgea_sampler_config* s,
+                                    float repetition_penalty, int32_t* ids_out_dev, void* stream);
+
+/* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
+ * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
+ * generate applied no penalty. */
+int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream);
+
 /* Current cached length of each row -> lens_out_dev [B] (device int32). */
 int mgea_decoder_context_lengths(mgea_decoder* h, int32_t* lens_out_dev, void* stream);
 
@@ -157,7 +174,8 @@ int mgea_decoder_profile_read(mgea_decoder* h, double* ms_by_class, int64_t* lau
 
 /* out[0] kernels in the step graph last used, [1] graph replays of the last generate(), [2] graph
  * captures + instantiations over the handle's lifetime, [4] graphs cached now, [5] forwards that ran on the f16 matrix-core
- * prefill path (MGEA_DTYPE_F16 engines, empty cache, batch * T big enough: csrc/decoder.hip run_prefill16); others 0. */
+ * prefill path (MGEA_DTYPE_F16 engines, empty cache, batch * T big enough: csrc/decoder.hip run_prefill16), [6] decode steps
+ * of the last generate() that applied a repetition penalty (0 if it applied none); others 0. */
 int mgea_decoder_stats(mgea_decoder* h, int64_t* out /* [8] */);
 
 /* Token ids outside [0, vocab) make nn.Embedding raise IndexError in the reference (api_cache.py:99).
@@ -301,6 +319,12 @@ int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K);
  * receives the pre-multinomial distribution. */
 int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s,
                    int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream);
+/* mgea_op_sample on the repetition-penalized logits (mgea_decoder_generate_penalized): presence_dev [B][ceil(V / 32)] uint32 holds
+ * each row's seen ids (bit id & 31 of word id >> 5).  top_k == 1 takes the argmax of the penalized row, ties to the lowest id.
+ * repetition_penalty must be finite and > 0; == 1 is mgea_op_sample (presence_dev may then be NULL). */
+int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s,
+                             float repetition_penalty, const uint32_t* presence_dev, int64_t step,
+                             int32_t* ids_out_dev, float* probs_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

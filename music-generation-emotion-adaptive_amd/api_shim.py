@@ -11,7 +11,11 @@ the accelerated path).
 from __future__ import annotations
 
 
-def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50):
+def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None):
+    """top_p / repetition_penalty (None = none) reach sample_kvcache; the paper's decoding setting (§10.3) is
+    create_app(model, seq_len, top_k=0, top_p=0.92, repetition_penalty=1.1)."""
+    from mgea.ops import check_repetition_penalty
+    check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     from fastapi import FastAPI, Form
     from fastapi.middleware.cors import CORSMiddleware
     from fastapi.responses import Response
@@ -41,7 +45,7 @@ def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50):
             instruments.extend(gen.FAMILY_TO_INSTRUMENTS.get(fam, []))
         gen_prompt = ["[START_SEQUENCE]", bpm_tok, key] + [f"[INSTRUMENT] {i}" for i in instruments]   # :203
         tokens = gen.sample_kvcache(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k,
-                                    device="cpu")                             # :204
+                                    device="cpu", top_p=top_p, repetition_penalty=repetition_penalty)   # :204
         midi = tokens_to_midi(tokens)                                         # :208-221 (+ pm.write)
         return Response(content=midi, media_type="audio/midi",
                         headers={"X-Emotion": label, "X-Prompt-Tokens": str(len(gen_prompt)),

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 
 #include "common.h"
@@ -251,6 +252,18 @@ int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sam
         return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, nullptr, probs_out_dev, st);
     }
     return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, ids_out_dev, probs_out_dev, st);
+}
+
+int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s, float repetition_penalty,
+                             const uint32_t* presence_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream) {
+    MGEA_REQUIRE(logits_dev && s, MGEA_EINVAL, "op_sample_penalized: NULL argument");
+    MGEA_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, MGEA_EINVAL,
+                 "op_sample_penalized: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
+    if (repetition_penalty == 1.0f) return mgea_op_sample(logits_dev, B, V, s, step, ids_out_dev, probs_out_dev, stream);
+    MGEA_REQUIRE(presence_dev, MGEA_EINVAL, "op_sample_penalized: presence_dev is NULL");
+    // the kernel only reads the bitmap (it writes one only in the decoder's fused tail)
+    return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, ids_out_dev, probs_out_dev, (hipStream_t)stream, nullptr,
+                         const_cast<uint32_t*>(presence_dev), repetition_penalty);
 }
 
 }  // extern "C"

@@ -186,14 +186,18 @@ int launch_attn_dense(const float* qkv, const int32_t* lens, const int32_t* mask
 // The sampler's scalars as the kernels read them from DEVICE memory (one 32-byte record per engine): a captured
 // decode-step graph holds only the pointer, so one graph serves every request whatever its seed / temperature /
 // top-k / top-p / EOS id (mgea_sampler_config, api_cache.py:160,204).
+// penalty: the repetition penalty of a penalized generation (read only by the PENALTY sampler; 1 otherwise).
 struct SamplerParams {
     float temperature; int32_t top_k; float top_p; int32_t eos_id;
-    uint32_t seed_lo, seed_hi; int32_t pad0, pad1;
+    uint32_t seed_lo, seed_hi; float penalty; int32_t pad1;
 };
-static inline SamplerParams sampler_params(const mgea_sampler_config& s) {
-    return SamplerParams{s.temperature, s.top_k, s.top_p, s.eos_id, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), 0, 0};
+static inline SamplerParams sampler_params(const mgea_sampler_config& s, float penalty = 1.0f) {
+    return SamplerParams{s.temperature, s.top_k, s.top_p, s.eos_id, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), penalty, 0};
 }
 constexpr int MGEA_SAMPLER_MAX_VOCAB = 14336;   // the sampler keeps a row in registers: 256 threads x 56 logits
+// Repetition penalty (mgea_decoder_generate_penalized): per row a presence bitmap of ceil(V / 32) words, bit id & 31 of word id >> 5
+// set once the id is in the row's prompt or was generated by it.  Rows follow each other at that stride.
+__host__ __device__ static inline int presence_words(int V) { return (V + 31) >> 5; }
 
 // logits row epilogue: v = sum P + bias; optional store to logits[m, V]; greedy argmax path writes
 // next ids and advances the per-row state (see decoder.hip).
@@ -223,13 +227,19 @@ struct TailArgs {
     int C, vocab, pos_rows, absolute_pos;
 };
 // params_dev != NULL: the scalars come from that device record instead of `s`
+// presence != NULL: the PENALTY form -- the logits of the ids whose bit is set in the row's presence bitmap (presence_words(V) words
+// per row) are penalized first, x < 0 ? x * p : x / p, p = penalty (or params_dev->penalty); with a tail the row's new token is then
+// added to that bitmap.  top_k == 1 there is the exact argmax of the penalized row (no temperature division, ties to the lowest id).
 int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
                   const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st,
-                  const TailArgs* tail = nullptr);
-int launch_set_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, hipStream_t st);
+                  const TailArgs* tail = nullptr, uint32_t* presence = nullptr, float penalty = 1.0f);
+int launch_set_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, hipStream_t st, float penalty = 1.0f);
 // after ids for this step are in `sampled` [B]: apply EOS/done logic, write ids_out[b, step],
-// cur_ids, ctx_len += 1, row_step += 1
-int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st);
+// cur_ids, ctx_len += 1, row_step += 1; presence != NULL (bitmap of presence_words(V) words per row): also set the bit of the
+// token of every row that was not finished yet
+int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence = nullptr, int V = 0);
+// presence rows [0, B) <- the set of the real tokens of ids [B, T] (lens: first lens[b] of row b, NULL: all T; ids outside [0, V) skipped)
+int launch_presence_seed(const int32_t* ids, const int32_t* lens, int B, int T, int V, uint32_t* presence, hipStream_t st);
 // ctx_len[b] += (lens ? lens[b] : T)
 int launch_add_lens(int32_t* ctx_len, const int32_t* lens, int T, int B, hipStream_t st);
 // cur_ids[b] = ids[b, (lens ? lens[b] : T) - 1]
@@ -410,8 +420,11 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 // the sampler-loop bookkeeping of api_cache.py:179-181 (append, EOS stop) and the NEXT step's embedding
 // x[b] = tok_emb[fed] + pos_emb[pos] (k-tiled) with its LayerNorm statistics (two equal half-row partials).
 // st_* = the row's state as loaded by thread 0 at kernel start.  sh: >= 6 floats of shared scratch.
+// PENALTY: also set the token's bit in the row's presence bitmap (presence_words(vocab) words per row) while the row is not finished:
+// one writer per row, read by a later kernel, so a plain read-modify-write of the word.
+template <bool PENALTY = false>
 __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::TailArgs& t, int32_t* sampled, int st_step, int st_fed,
-                                                  int st_len, int st_done, float* sh) {
+                                                  int st_len, int st_done, float* sh, uint32_t* presence = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int* shi = reinterpret_cast<int*>(sh);
     if (tid == 0) {
@@ -427,6 +440,12 @@ __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::Ta
             if (tok == s.eos()) {
                 s.done[b] = 1;
                 atomicAdd(s.n_done, 1);
+            }
+            if constexpr (PENALTY) {
+                if ((unsigned)tok < (unsigned)t.vocab) {
+                    uint32_t* w = presence + (int64_t)b * mgea::presence_words(t.vocab) + (tok >> 5);
+                    *w = *w | (1u << (tok & 31));
+                }
             }
         }
         if (s.ids_out && st_step < s.n_steps) s.ids_out[(int64_t)b * s.n_steps + st_step] = out;

@@ -8,6 +8,7 @@
 // therefore sits in the cache twice).
 #include <stdlib.h>
 
+#include <cmath>
 #include <mutex>
 #include <vector>
 
@@ -102,13 +103,18 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, greedy | sampled).  Everything a step reads besides its structure
-    // lives in device memory (per-row state, page table, and the sampler's scalars in samp_dev), so a request with a
-    // new seed / temperature / top-k / top-p / EOS id replays an existing graph: no capture, no instantiate.
-    struct GraphEntry { int batch; bool greedy; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
+    // Captured decode-step graphs, one per (batch, greedy | sampled, penalized or not, steps).  Everything a step reads besides its
+    // structure lives in device memory (per-row state, page table, presence bitmaps, and the sampler's scalars in samp_dev), so a
+    // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty replays an existing graph: no capture, no
+    // instantiate.
+    struct GraphEntry { int batch; bool greedy; bool penalized; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
     std::vector<GraphEntry> graphs;
     uint64_t use_clock = 0;
     SamplerParams* samp_dev = nullptr;
+    // repetition penalty: per row the set of ids it has seen (prompt + generated), [max_batch][presence_words(vocab)] (common.h);
+    // seeded by a penalized generate() after its prefill, then updated by the kernel that commits each row's token
+    uint32_t* presence = nullptr;
+    bool last_penalized = false;   // the last generate() applied a penalty: presence holds its rows
     int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped)
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     int64_t counters[8] = {0};
@@ -452,12 +458,16 @@ StepState step_state(mgea_decoder* h, const Bufs& u, int eos, const SamplerParam
 // primed: x already holds the embedding (+ LN statistics) of cur_ids -- generate() keeps that invariant by
 // fusing the next step's embedding into this step's tail, so a replayed step is 32 launches.
 // pd: device-resident sampler scalars (generate()) or NULL (mgea_decoder_step: `sc` by value).  Only sc.top_k == 1
-// (greedy or not) shapes the launch sequence.
+// (greedy or not) and pen shape the launch sequence.
+// pen: a penalized generate() step (pd holds the penalty, h->presence the rows' bitmaps).  Its greedy steps take the sampled sequence
+// too: the head writes the logits row and the PENALTY sampler keeps top_k = 1 entry of the penalized row (the head's per-tile argmax
+// partials know nothing of the penalty).
 int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler_config& sc, const SamplerParams* pd,
-                       float* logits_out, hipStream_t st, bool primed) {
+                       float* logits_out, hipStream_t st, bool primed, bool pen = false) {
     const auto& c = h->cfg;
     const int C = c.d_model, V = c.vocab;
-    const bool greedy = sc.top_k == 1;
+    const bool greedy = sc.top_k == 1 && !pen;
+    uint32_t* pres = pen ? h->presence : nullptr;
     // [embed,] 6 x (qkv, attention, out-proj, fc1, fc2), head (+ per-tile argmax), finalize [+ next embed]
     const int abs_pos = c.pos_mode == MGEA_POS_ABSOLUTE;
     if (!primed)
@@ -480,10 +490,10 @@ int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler
     } else {
         if (primed) {   // sampler + loop bookkeeping + next step's embedding in one launch
             TailArgs t{step_state(h, u, sc.eos_id, pd), h->w(T_TOK), h->w(T_POS), u.x, u.stats, C, V, c.seq_len, abs_pos};
-            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, &t));
+            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, &t, pres));
         } else {
-            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st));
-            PROF(PC_ROWOP, launch_advance(u.sampled, step_state(h, u, sc.eos_id, pd), B, st));
+            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, nullptr, pres));
+            PROF(PC_ROWOP, launch_advance(u.sampled, step_state(h, u, sc.eos_id, pd), B, st, pres, V));
         }
     }
     return MGEA_OK;
@@ -491,12 +501,13 @@ int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler
 
 // one decode step on cur_ids (T = 1) for the whole batch; logits_out optional
 int enqueue_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, const SamplerParams* pd, float* logits_out,
-                 hipStream_t st, bool primed = false) {
+                 hipStream_t st, bool primed = false, bool pen = false) {
     const auto& c = h->cfg;
     const int C = c.d_model, V = c.vocab;
     const bool post = c.block_mode == MGEA_BLOCK_POSTLN_RELU;
-    const bool greedy = sc.top_k == 1;
-    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), B, sc, pd, logits_out, st, primed);
+    const bool greedy = sc.top_k == 1 && !pen;   // (enqueue_step_fused: penalized greedy steps sample with top_k = 1)
+    uint32_t* pres = pen ? h->presence : nullptr;
+    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), B, sc, pd, logits_out, st, primed, pen);
     const Bufs u = main_bufs(h);
     PROF(PC_ROWOP, launch_embed_ln(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                              post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, 1, C,
@@ -507,15 +518,15 @@ int enqueue_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, const Sa
     float* lg = logits_out ? logits_out : (greedy ? nullptr : h->logits);
     PROF(PC_SAMPLE, launch_logits_argmax(h->slabs, S, slab_floats(B, V), (int)slab_ld(V), h->head_b(), lg, B, V,
                                   greedy ? h->sampled : nullptr, st));
-    if (!greedy) PROF(PC_SAMPLE, launch_sample(lg, B, V, sc, pd, h->row_step, 0, h->sampled, nullptr, st));
-    PROF(PC_ROWOP, launch_advance(h->sampled, step_state(h, u, sc.eos_id, pd), B, st));
+    if (!greedy) PROF(PC_SAMPLE, launch_sample(lg, B, V, sc, pd, h->row_step, 0, h->sampled, nullptr, st, nullptr, pres));
+    PROF(PC_ROWOP, launch_advance(h->sampled, step_state(h, u, sc.eos_id, pd), B, st, pres, V));
     return MGEA_OK;
 }
 
 // The decode step of generate(): x arrives primed on the fused path.
-int enqueue_gen_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st) {
-    if (!fused_ok(h, B)) return enqueue_step(h, B, sc, h->samp_dev, nullptr, st, false);
-    return enqueue_step_fused(h, main_bufs(h), B, sc, h->samp_dev, nullptr, st, true);
+int enqueue_gen_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, bool pen) {
+    if (!fused_ok(h, B)) return enqueue_step(h, B, sc, h->samp_dev, nullptr, st, false, pen);
+    return enqueue_step_fused(h, main_bufs(h), B, sc, h->samp_dev, nullptr, st, true, pen);
 }
 
 // embedding (+ LN statistics) of cur_ids into the buffers the next generate() step will read
@@ -527,15 +538,15 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
-// The captured decode step for (B, greedy): from the cache, or captured + instantiated now (least recently used
+// The captured decode step for (B, greedy, pen): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond MAX_GRAPHS).
-constexpr size_t MAX_GRAPHS = 16;   // two per (batch, greedy | sampled): the single step and the 8-step graph
+constexpr size_t MAX_GRAPHS = 16;   // two per (batch, greedy | sampled, penalized or not): the single step and the 8-step graph
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, hipGraphExec_t* out, int steps = 1) {
+int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, hipGraphExec_t* out, int steps, bool pen) {
     const bool greedy = sc.top_k == 1;
     for (auto& g : h->graphs)
-        if (g.batch == B && g.greedy == greedy && g.steps == steps) {
+        if (g.batch == B && g.greedy == greedy && g.penalized == pen && g.steps == steps) {
             g.last_use = ++h->use_clock;
             if (steps == 1) h->counters[0] = g.nodes;
             *out = g.exec;
@@ -552,7 +563,7 @@ int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_
     }
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, sc, st);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, sc, st, pen);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -568,7 +579,7 @@ int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_
     }
     size_t nn = 0;
     (void)hipGraphGetNodes(g, nullptr, &nn);
-    h->graphs.push_back({B, greedy, steps, g, ex, (int64_t)nn, ++h->use_clock});
+    h->graphs.push_back({B, greedy, pen, steps, g, ex, (int64_t)nn, ++h->use_clock});
     if (steps == 1) h->counters[0] = (int64_t)nn;
     h->counters[2] += 1;   // lifetime captures + instantiations
     h->counters[4] = (int64_t)h->graphs.size();
@@ -936,6 +947,7 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         hipMalloc((void**)&h->row_step, nb) != hipSuccess || hipMalloc((void**)&h->sampled, nb) != hipSuccess ||
         hipMalloc((void**)&h->n_done, 16) != hipSuccess || hipMalloc((void**)&h->samp_dev, sizeof(SamplerParams)) != hipSuccess ||
         hipMalloc((void**)&h->err_flag, 16) != hipSuccess ||
+        hipMalloc((void**)&h->presence, (size_t)cfg->max_batch * presence_words(cfg->vocab) * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc((void**)&h->ids_hist, nb * h->ids_hist_stride) != hipSuccess)
         return fail(MGEA_ENOMEM, "state allocation failed");
     h->attn_split.max_split = MGEA_ATTN_MAX_SPLIT;
@@ -983,7 +995,7 @@ int mgea_decoder_destroy(mgea_decoder* h) {
     free_ws(h);
     free_p16(h);
     void* p[] = {h->kv.base, h->page_table, h->ctx_len, h->cur_ids, h->done, h->row_step, h->n_done, h->sampled, h->ids_hist, h->wt, h->lnv,
-                 h->samp_dev, h->err_flag, h->arena_own, h->attn_split.part, h->attn_split.count};
+                 h->samp_dev, h->err_flag, h->presence, h->arena_own, h->attn_split.part, h->attn_split.count};
     for (void* q : p)
         if (q) (void)hipFree(q);
     delete h;
@@ -1022,30 +1034,37 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
     return MGEA_OK;
 }
 
-int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
-                          int32_t Tp, int32_t n_steps, const mgea_sampler_config* s, int32_t* ids_out_dev,
-                          void* stream) {
-    MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+// mgea_decoder_generate(_penalized); the caller holds h->mu.  penalty == 1: no penalty, exactly the unpenalized launch sequence.
+int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
+                const mgea_sampler_config* s, float penalty, int32_t* ids_out_dev, hipStream_t st) {
     const auto& c = h->cfg;
+    const bool pen = penalty != 1.0f;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
     MGEA_REQUIRE(Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
     MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
+    h->last_penalized = false;
+    h->counters[6] = 0;
     MGEA_TRY(do_reset(h, B, Tp + n_steps, st));
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
+    if (pen) {   // every row's set starts as its real prompt tokens
+        MGEA_TRY(launch_presence_seed(prompt_ids_dev, lens_dev, B, Tp, c.vocab, h->presence, st));
+        h->last_penalized = true;
+    }
     if (n_steps == 0) return MGEA_OK;
 
     // the request's sampler scalars -> device memory (stream-ordered), then the cached step graph of this batch size:
     // all per-step state lives in device memory, so one graph serves every step of every request
-    MGEA_TRY(launch_set_sampler_params(h->samp_dev, *s, st));
+    MGEA_TRY(launch_set_sampler_params(h->samp_dev, *s, st, penalty));
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, *s, st, &gexec));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, *s, st, &gexec, 1, pen));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, *s, st, &gexec_k, K));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, *s, st, &gexec_k, K, pen));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1053,12 +1072,12 @@ int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const 
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, *s, st);
+            const int rc = enqueue_gen_step(h, B, *s, st, pen);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, *s, st));
+            MGEA_TRY(enqueue_gen_step(h, B, *s, st, pen));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1075,11 +1094,42 @@ int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const 
     }
     h->host_max_len += launched;
     h->counters[1] = launched;
+    h->counters[6] = pen ? launched : 0;
     // rows: ids_hist[b, 0:launched]; steps never run are -1
     MGEA_CHECK_HIP(hipMemsetAsync(ids_out_dev, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));
     MGEA_CHECK_HIP(hipMemcpy2DAsync(ids_out_dev, (size_t)n_steps * sizeof(int32_t), h->ids_hist,
                                     (size_t)h->ids_hist_stride * sizeof(int32_t), (size_t)launched * sizeof(int32_t), B,
                                     hipMemcpyDeviceToDevice, st));
+    return MGEA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
+                          int32_t Tp, int32_t n_steps, const mgea_sampler_config* s, int32_t* ids_out_dev,
+                          void* stream) {
+    MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, ids_out_dev, (hipStream_t)stream);
+}
+
+int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
+                                    int32_t Tp, int32_t n_steps, const mgea_sampler_config* s, float repetition_penalty,
+                                    int32_t* ids_out_dev, void* stream) {
+    MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
+    MGEA_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, MGEA_EINVAL,
+                 "decoder_generate: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
+    std::lock_guard<std::mutex> lk(h->mu);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, ids_out_dev, (hipStream_t)stream);
+}
+
+int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream) {
+    MGEA_REQUIRE(h && bits_out_dev, MGEA_EINVAL, "decoder_presence: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    MGEA_REQUIRE(h->last_penalized && h->cur_batch > 0, MGEA_EINVAL, "decoder_presence: the last generate() applied no penalty");
+    MGEA_CHECK_HIP(hipMemcpyAsync(bits_out_dev, h->presence, (size_t)h->cur_batch * presence_words(h->cfg.vocab) * sizeof(uint32_t),
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MGEA_OK;
 }
 

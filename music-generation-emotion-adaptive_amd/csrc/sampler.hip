@@ -22,9 +22,15 @@
 //             stream cannot be reproduced on device: equality with the reference is
 //             distributional, the pre-draw probabilities are compared exactly (probs_out).
 // top_k == 1 is the argmax path (rowops.hip, ties to the lowest id) for the ids.
+// Repetition penalty (PENALTY instantiations; HF RepetitionPenaltyLogitsProcessor): before everything above, every logit whose id is
+// set in the row's presence bitmap becomes x < 0 ? x * p : x / p (one correctly rounded fp32 operation).  The row's bitmap words are
+// staged in LDS first (<= 448 words: two per thread at most).  top_k == 1 there is the greedy step of a penalized generation: the
+// kept entry is the penalized argmax (lowest id among equals), so the temperature division -- which could merge neighbours -- is skipped.
 // The sampler's scalars (temperature, top_k, top_p, seed; eos for the fused tail) are read from a SamplerParams
 // record in DEVICE memory when the caller passes one: the captured decode graph then serves every request, whatever
 // its seed (the reference's endpoint draws a fresh one per call, api_cache.py:204).
+#include <cmath>
+
 #include "common.h"
 
 namespace mgea {
@@ -291,12 +297,13 @@ __device__ __forceinline__ float funkey(uint32_t k) {   // inverse of fkey
 
 // One SAMP_NT-thread workgroup per row; thread t owns the logits t, t + SAMP_NT, ... in registers (MAXE of them), so the row is
 // read from memory once, in one batch of loads, and never goes through LDS.
-template <int MAXE>
+// PENALTY: presence = the rows' bitmaps (presence_words(V) words per row), updated by the fused tail; unused otherwise.
+template <int MAXE, bool PENALTY>
 __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict__ logits, int V, SamplerParams pv,
                                                     const SamplerParams* __restrict__ pd,
                                                     const int32_t* __restrict__ row_step, int64_t step_host,
                                                     int32_t* __restrict__ ids_out, float* __restrict__ probs_out,
-                                                    TailArgs tail, int fuse_tail, int wave_select) {
+                                                    TailArgs tail, int fuse_tail, int wave_select, uint32_t* __restrict__ presence) {
     constexpr int NT = SAMP_NT, NW = SAMP_NW;
     static_assert(SAMP_KFAST == 64, "wave_publish_ge fills one slot per lane");
     __shared__ unsigned long long red64[2 * NW];
@@ -327,8 +334,20 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         const int i = tid + NT * j;
         x[j] = i < V ? lg[i] : -INFINITY;
     }
+    if constexpr (PENALTY) {
+        __shared__ uint32_t s_pres[MAXE * NT / 32];
+        const int nw = presence_words(V);   // <= MAXE * NT / 32
+        for (int w = tid; w < nw; w += NT) s_pres[w] = presence[(int64_t)b * nw + w];
+        __syncthreads();
+        const float pen = pv.penalty;
+#pragma unroll
+        for (int j = 0; j < MAXE; ++j) {
+            const int i = tid + NT * j;
+            if (i < V && ((s_pres[i >> 5] >> (i & 31)) & 1u)) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
+        }
+    }
     float mx = -INFINITY;
-    if (temperature != 1.0f) {   // logits / temperature (api_cache.py:170); x / 1 is x
+    if (temperature != 1.0f && !(PENALTY && top_k == 1)) {   // logits / temperature (api_cache.py:170); x / 1 is x
 #pragma unroll
         for (int j = 0; j < MAXE; ++j) x[j] = x[j] / temperature;
     }
@@ -545,25 +564,27 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     }
     __syncthreads();
     const int tok = s_choice >= 0 ? s_choice : 0;
-    if (fuse_tail) advance_embed_row(b, tok, tail, ids_out, st_step, st_fed, st_len, st_done, sh_tail);   // writes ids_out[b] too
+    if (fuse_tail) advance_embed_row<PENALTY>(b, tok, tail, ids_out, st_step, st_fed, st_len, st_done, sh_tail, presence);   // writes ids_out[b] too
     else if (tid == 0) ids_out[b] = tok;
 }
 
 int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
-                  const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st, const TailArgs* tail) {
+                  const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st, const TailArgs* tail,
+                  uint32_t* presence, float penalty) {
     MGEA_REQUIRE(params_dev || s.temperature > 0.f, MGEA_EINVAL, "sampler: temperature must be > 0");
     MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "sampler: vocab %d exceeds the register-resident row (%d)", V,
                  MGEA_SAMPLER_MAX_VOCAB);
     MGEA_REQUIRE(!tail || (ids_out && tail->C % 4 == 0 && tail->C <= 4096), MGEA_EINVAL, "sampler: bad fused-tail arguments");
+    MGEA_REQUIRE(!presence || params_dev || (std::isfinite(penalty) && penalty > 0.f), MGEA_EINVAL,
+                 "sampler: the repetition penalty must be finite and > 0");
     const TailArgs t = tail ? *tail : TailArgs{};
-    const SamplerParams pv = sampler_params(s);
+    const SamplerParams pv = sampler_params(s, penalty);
     static_assert(SAMP_NT * 56 >= MGEA_SAMPLER_MAX_VOCAB, "the register-resident row must hold the largest vocabulary");
-    if (V <= SAMP_NT * 36)
-        hipLaunchKernelGGL(sample_kernel<36>, dim3(B), dim3(SAMP_NT), 0, st, logits, V, pv, params_dev, row_step_dev, step_host, ids_out,
-                           probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT));
-    else
-        hipLaunchKernelGGL(sample_kernel<56>, dim3(B), dim3(SAMP_NT), 0, st, logits, V, pv, params_dev, row_step_dev, step_host, ids_out,
-                           probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT));
+    const bool narrow = V <= SAMP_NT * 36;
+    auto kern = presence ? (narrow ? sample_kernel<36, true> : sample_kernel<56, true>)
+                         : (narrow ? sample_kernel<36, false> : sample_kernel<56, false>);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(SAMP_NT), 0, st, logits, V, pv, params_dev, row_step_dev, step_host, ids_out, probs_out, t,
+                       tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), presence);
     MGEA_CHECK_HIP(hipGetLastError());
     return MGEA_OK;
 }
@@ -571,8 +592,8 @@ int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& 
 // params_dev <- s, stream-ordered (a kernel argument, so no host buffer has to outlive the call)
 __global__ void set_sampler_params_kernel(SamplerParams* dst, SamplerParams v) { *dst = v; }
 
-int launch_set_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, hipStream_t st) {
-    hipLaunchKernelGGL(set_sampler_params_kernel, dim3(1), dim3(1), 0, st, params_dev, sampler_params(s));
+int launch_set_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, hipStream_t st, float penalty) {
+    hipLaunchKernelGGL(set_sampler_params_kernel, dim3(1), dim3(1), 0, st, params_dev, sampler_params(s, penalty));
     MGEA_CHECK_HIP(hipGetLastError());
     return MGEA_OK;
 }

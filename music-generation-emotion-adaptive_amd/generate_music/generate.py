@@ -197,12 +197,15 @@ def _draw_seed() -> int:
 
 
 def sample_kvcache(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
-                   top_p: Optional[float] = None, seed: Optional[int] = None) -> List[str]:
+                   top_p: Optional[float] = None, seed: Optional[int] = None,
+                   repetition_penalty: Optional[float] = None) -> List[str]:
     """api_cache.py:159-184 with the same signature: prefill the prompt (logits dropped), then up to
     max_len - len(prompt) steps of /temperature, top-k mask, softmax, one multinomial draw; stops
     after [END_SEQUENCE].  Runs as one native generate() call (prefill + hipGraph-replayed decode
     steps).  `device` is accepted for compatibility; the work happens on the model's MI355X.
-    top_k=1 is exactly greedy; other settings match torch.multinomial in distribution only."""
+    top_k=1 is exactly greedy; other settings match torch.multinomial in distribution only.
+    repetition_penalty (None = none) penalizes the ids of the prompt and of everything generated so far like
+    transformers' RepetitionPenaltyLogitsProcessor; the paper's setting is top_k=0, top_p=0.92, repetition_penalty=1.1."""
     m = _as_model(model)
     eng = m._need()
     ids = [tok2id[t] for t in prompt]          # KeyError for an unknown token, like api_cache.py:162
@@ -213,21 +216,22 @@ def sample_kvcache(model, prompt: Sequence[str], max_len=512, temperature=1.0, t
         raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
     out = eng.generate([ids], n_steps, temperature=temperature, top_k=top_k, top_p=top_p, eos_id=eos,
-                       seed=_draw_seed() if seed is None else seed)
+                       seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty)
     gen = [int(i) for i in out[0].cpu().tolist() if i >= 0]
     return [id2tok[i] for i in ids + gen]
 
 
 def generate_sequence(model_or_weights, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50,
                       device=_DEFAULT_DEVICE, top_p: Optional[float] = None, seed: Optional[int] = None,
-                      n_head: int = 8) -> List[str]:
+                      n_head: int = 8, repetition_penalty: Optional[float] = None) -> List[str]:
     """North-star name (BASELINE.json): sample_kvcache on a model object or a weights/checkpoint dict."""
     return sample_kvcache(_as_model(model_or_weights, n_head, device), prompt, max_len, temperature, top_k,
-                          device, top_p, seed)
+                          device, top_p, seed, repetition_penalty=repetition_penalty)
 
 
 def generate_batch(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
-                   top_p: Optional[float] = None, seed: Optional[int] = None) -> List[List[str]]:
+                   top_p: Optional[float] = None, seed: Optional[int] = None,
+                   repetition_penalty: Optional[float] = None) -> List[List[str]]:
     """New surface: many prompts in one batch (ragged lengths allowed); every row equals the
     reference run on that prompt alone (greedy) -- rows are independent."""
     m = _as_model(model)
@@ -236,7 +240,7 @@ def generate_batch(model, prompts: Sequence[Sequence[str]], max_len=512, tempera
     n_steps = int(max_len) - max(len(p) for p in ids)
     eos = tok2id.get("[END_SEQUENCE]", -1)
     out = eng.generate(ids, max(n_steps, 0), temperature=temperature, top_k=top_k, top_p=top_p, eos_id=eos,
-                       seed=_draw_seed() if seed is None else seed).cpu().tolist()
+                       seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty).cpu().tolist()
     return [[id2tok[i] for i in p + [g for g in row if g >= 0]] for p, row in zip(ids, out)]
 
 

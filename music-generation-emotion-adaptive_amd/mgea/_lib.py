@@ -58,6 +58,8 @@ PROTOTYPES = {
     "mgea_decoder_forward": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
     "mgea_decoder_step": (C.c_int, [_P, _P, C.POINTER(SamplerConfig), _P, _P, _P]),
     "mgea_decoder_generate": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(SamplerConfig), _P, _P]),
+    "mgea_decoder_generate_penalized": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _P]),
+    "mgea_decoder_presence": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_context_lengths": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_stats": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_error_flags": (C.c_int, [_P, C.POINTER(_I32), _P]),
@@ -89,6 +91,7 @@ PROTOTYPES = {
     "mgea_op_skinny": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_skinny_logits_partials": (C.c_int, [_I32, _I32, _I32]),
     "mgea_op_sample": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _I64, _P, _P, _P]),
+    "mgea_op_sample_penalized": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _I64, _P, _P, _P]),
 }
 
 _lib = None

@@ -250,12 +250,18 @@ class DecoderEngine:
 
     # ------------------------------------------------------------------ sample_kvcache surface
     def generate(self, prompts, n_steps: int, temperature: float = 1.0, top_k: Optional[int] = 50,
-                 top_p: Optional[float] = None, eos_id: int = -1, seed: int = 0, check_ids: bool = True) -> torch.Tensor:
+                 top_p: Optional[float] = None, eos_id: int = -1, seed: int = 0, check_ids: bool = True,
+                 repetition_penalty: Optional[float] = None) -> torch.Tensor:
         """Batched sample_kvcache (api_cache.py:159-184).  prompts: list of id lists (ragged ok) or
         an int tensor [B, Tp].  Returns int32 [B, n_steps] of generated ids (-1 after a row's EOS).
         check_ids: prompts given as a DEVICE tensor are range-checked through the device flag once the
         generation has been enqueued (one sync at the end, which the caller's read of the ids needs anyway);
-        False skips even that and leaves the flag for id_errors()."""
+        False skips even that and leaves the flag for id_errors().
+        repetition_penalty: None (or 1.0) = none; else a finite p > 0 (ValueError otherwise) applied like
+        transformers' RepetitionPenaltyLogitsProcessor to every id of the row's prompt and of what it generated
+        (mgea_decoder_generate_penalized); presence() then returns those sets."""
+        from . import ops
+        pen = ops.check_repetition_penalty(repetition_penalty)
         if isinstance(prompts, torch.Tensor):
             ids = prompts.to(torch.int32)
             lens = None
@@ -275,13 +281,26 @@ class DecoderEngine:
             ids = ids.to(self.device).contiguous()
             lens = None if lens is None else lens.to(self.device).contiguous()
             out = torch.empty(B, max(n_steps, 1), dtype=torch.int32, device=self.device)
-            check(self.lib.mgea_decoder_generate(self.h, ptr(ids), ptr(lens), B, Tp, int(n_steps), C.byref(samp), ptr(out),
-                                                 self._sp()))
+            if pen is None:
+                check(self.lib.mgea_decoder_generate(self.h, ptr(ids), ptr(lens), B, Tp, int(n_steps), C.byref(samp), ptr(out),
+                                                     self._sp()))
+            else:
+                check(self.lib.mgea_decoder_generate_penalized(self.h, ptr(ids), ptr(lens), B, Tp, int(n_steps), C.byref(samp),
+                                                               pen, ptr(out), self._sp()))
         self._cur_batch = B
         self._epoch += 1
         if check_ids and not checked:
             self.id_errors()
         return out[:, :n_steps]
+
+    def presence(self) -> torch.Tensor:
+        """bool [B, vocab] on the device: the ids each row of the last (penalized) generate() has seen -- its real prompt
+        tokens and the ids it generated, EOS included.  RuntimeError if that generate() applied no penalty."""
+        from . import ops
+        with self._on_stream():
+            words = torch.empty(self._cur_batch, ops.presence_words(self.vocab), dtype=torch.int32, device=self.device)
+            check(self.lib.mgea_decoder_presence(self.h, ptr(words), self._sp()))
+            return ops.unpack_presence(words, self.vocab)
 
     def reset_and_prefill(self, idx: torch.Tensor, lens=None, want_logits=True, max_len=None):
         self.reset(idx.shape[0], max_len)
@@ -302,4 +321,5 @@ class DecoderEngine:
     def stats(self):
         out = (C.c_int64 * 8)()
         check(self.lib.mgea_decoder_stats(self.h, out))
-        return dict(graph_nodes=out[0], graph_replays=out[1], graph_instantiates=out[2], graphs_cached=out[4], prefill16_forwards=out[5])
+        return dict(graph_nodes=out[0], graph_replays=out[1], graph_instantiates=out[2], graphs_cached=out[4], prefill16_forwards=out[5],
+                    penalized_steps=out[6])

@@ -3,8 +3,10 @@ Used by the parity tests to check single kernels; the engines do not go through 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -133,7 +135,58 @@ def layernorm_bf16(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float
     return y
 
 
-def sample(logits: torch.Tensor, temperature=1.0, top_k=50, top_p=None, seed=0, step=0, want_probs=False):
+def check_repetition_penalty(penalty) -> Optional[float]:
+    """None -> None (no penalty).  Otherwise the penalty as a float, which must be finite and > 0 also once held as
+    fp32 (the kernels' precision): ValueError otherwise, as transformers' RepetitionPenaltyLogitsProcessor raises."""
+    if penalty is None:
+        return None
+    p = float(penalty)
+    with np.errstate(over="ignore"):
+        p32 = float(np.float32(p))
+    if not (math.isfinite(p32) and p32 > 0):
+        raise ValueError(f"`repetition_penalty` has to be a finite, strictly positive float, but is {penalty}")
+    return p
+
+
+def presence_words(vocab: int) -> int:
+    return (int(vocab) + 31) // 32
+
+
+def pack_presence(presence, B: int, V: int) -> np.ndarray:
+    """The presence bitmaps of the penalized sampler, uint32 [B, ceil(V / 32)]: bit id & 31 of word id >> 5 of row b is set iff
+    id is seen in row b.  presence: a bool [B, V] mask (tensor or array), or B sequences of ids (repeats allowed)."""
+    W = presence_words(V)
+    if isinstance(presence, (torch.Tensor, np.ndarray)):
+        m = presence.detach().cpu().numpy() if isinstance(presence, torch.Tensor) else np.asarray(presence)
+        if m.shape != (B, V):
+            raise ValueError(f"presence mask must be [{B}, {V}], got {list(m.shape)}")
+        m = np.concatenate([m.astype(bool), np.zeros((B, W * 32 - V), bool)], axis=1).reshape(B, W, 32)
+        return (m.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    rows = list(presence)
+    if len(rows) != B:
+        raise ValueError(f"presence needs {B} id lists, got {len(rows)}")
+    out = np.zeros((B, W), np.uint32)
+    for b, ids in enumerate(rows):
+        ids = np.asarray(list(ids), dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= V):
+            raise ValueError("presence ids must lie in [0, vocab)")
+        np.bitwise_or.at(out[b], ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+    return out
+
+
+def unpack_presence(words: torch.Tensor, V: int) -> torch.Tensor:
+    """int32 / uint32 words [B, ceil(V / 32)] -> bool mask [B, V] (on the words' device)"""
+    w = words.view(torch.int32) if words.dtype != torch.int32 else words
+    bits = (w.unsqueeze(-1) >> torch.arange(32, dtype=torch.int32, device=w.device)) & 1
+    return bits.reshape(w.shape[0], -1)[:, :V].bool()
+
+
+def sample(logits: torch.Tensor, temperature=1.0, top_k=50, top_p=None, seed=0, step=0, want_probs=False,
+           repetition_penalty=None, presence=None):
+    """repetition_penalty (None = none): the logits of the ids in `presence` (a bool [B, V] mask or B id lists; none if
+    None) are penalized first, x < 0 ? x * p : x / p, as in mgea_decoder_generate_penalized; top_k=1 then takes the argmax of
+    the penalized row."""
+    pen = check_repetition_penalty(repetition_penalty)
     lib = _lib.load()
     logits = _dev(logits.float())
     B, V = logits.shape
@@ -141,7 +194,13 @@ def sample(logits: torch.Tensor, temperature=1.0, top_k=50, top_p=None, seed=0, 
                       top_p=float(top_p) if top_p else 0.0, eos_id=-1, seed=int(seed))
     ids = torch.empty(B, dtype=torch.int32, device=logits.device)
     probs = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_probs else None
-    check(lib.mgea_op_sample(ptr(logits), B, V, C.byref(s), int(step), ptr(ids), ptr(probs), stream_ptr()))
+    if pen is None:
+        check(lib.mgea_op_sample(ptr(logits), B, V, C.byref(s), int(step), ptr(ids), ptr(probs), stream_ptr()))
+    else:
+        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
+        bits = torch.from_numpy(words.view(np.int32)).to(logits.device)
+        check(lib.mgea_op_sample_penalized(ptr(logits), B, V, C.byref(s), pen, ptr(bits), int(step), ptr(ids), ptr(probs),
+                                           stream_ptr()))
     return (ids, probs) if want_probs else ids
 
 
