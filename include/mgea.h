@@ -138,7 +138,8 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
  * scalars (seed, temperature, top_k, top_p, eos_id) live in device memory, so a new request with
  * other values reuses the graph (mgea_decoder_stats counts instantiations).  ids_out_dev
  * [B, n_steps] int32; entries after a row's EOS are -1.  Host-synchronises only if eos_id >= 0
- * (to stop early once all rows ended). */
+ * (to stop early once all rows ended).  Row b draws from Philox stream b under key seed
+ * (mgea_row_sampler: this is mgea_decoder_generate_rows with stream_b = b and no budget). */
 int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev,
                           int32_t B, int32_t Tp, int32_t n_steps, const mgea_sampler_config* s,
                           int32_t* ids_out_dev, void* stream);
@@ -154,6 +155,39 @@ int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const 
 int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev,
                                     int32_t B, int32_t Tp, int32_t n_steps, const mgea_sampler_config* s,
                                     float repetition_penalty, int32_t* ids_out_dev, void* stream);
+
+/* Per-row sampler settings (mgea_decoder_generate_rows, mgea_op_sample_rows): one record per batch row.
+ *   temperature > 0 and finite; 0 <= top_k <= vocab (0 = no cut, 1 = greedy); top_p as in mgea_sampler_config;
+ *   repetition_penalty finite and > 0 (1 = none); eos_id -1 = none;
+ *   max_new_tokens: the row's step budget, 0 <= max_new_tokens <= n_steps (0 = n_steps): the row finishes after that many ids;
+ *   seed, stream: the row's Philox4x32-10 stream.  Row b draws its step-t number from counter {stream, t, 0, const} under key seed.
+ * mgea_decoder_generate is the special case seed_b = seed, stream_b = b, no budget, the same settings on every row.  A row's ids
+ * therefore depend on its own record, its prompt and on B (the batch size picks the GEMM / attention forms, whose sums run in other
+ * orders) -- not on its index in the batch, nor on the other rows' records: the same (prompt, record) at rows 0 and 5 of a batch of B
+ * gives the same ids. */
+typedef struct mgea_row_sampler {
+    float    temperature;
+    int32_t  top_k;
+    float    top_p;
+    float    repetition_penalty;
+    int32_t  eos_id;
+    int32_t  max_new_tokens;   /* 0 = n_steps */
+    uint64_t seed;
+    uint32_t stream;
+    uint32_t reserved;         /* 0 */
+} mgea_row_sampler;
+
+/* mgea_decoder_generate with one sampler record per row, rows [B] (host memory, read before the call returns): concurrent requests
+ * with different settings, seeds and budgets in one batch.  ids_out_dev [B, n_steps] int32; entries after a row's EOS or budget are -1.
+ * A row with top_k == 1 takes the exact argmax of its (penalized) logits row, ties to the lowest id, without the temperature division.
+ * The step graphs are those of mgea_decoder_generate: the greedy form if every row is top_k == 1 without a penalty, the penalized form
+ * (presence bitmaps for every row, mgea_decoder_presence) if any row's penalty is not 1, the sampled form otherwise -- a mixed batch
+ * replays what a uniform batch of that size captured.  The call stops early (host poll every 16 steps) once every row has finished.
+ * Context: each row needs lens[b] + its budget <= max_ctx; the call reserves min(Tp + n_steps, max_ctx) tokens per row and needs
+ * Tp < max_ctx and n_steps <= max_ctx -- a row that would run past the reservation finishes there.  Bad records: MGEA_EINVAL naming
+ * the row. */
+int mgea_decoder_generate_rows(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                               int32_t n_steps, const mgea_row_sampler* rows, int32_t* ids_out_dev, void* stream);
 
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
@@ -325,6 +359,13 @@ int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sam
 int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s,
                              float repetition_penalty, const uint32_t* presence_dev, int64_t step,
                              int32_t* ids_out_dev, float* probs_out_dev, void* stream);
+
+/* mgea_op_sample with one record per row (rows [B], host): row b reads rows[b] (max_new_tokens and eos_id are ignored) and draws from
+ * counter {rows[b].stream, step, step >> 32, const} under key rows[b].seed.  presence_dev as in mgea_op_sample_penalized, needed only
+ * if some row's repetition_penalty is not 1 (rows with penalty 1 are then unchanged: x * 1 and x / 1 are exact).  top_k == 1 rows take
+ * the exact argmax of their (penalized) row, without the temperature division.  Synchronises `stream` before it returns. */
+int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                        int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,21 @@ from __future__ import annotations
 
 def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None):
     """top_p / repetition_penalty (None = none) reach sample_kvcache; the paper's decoding setting (§10.3) is
-    create_app(model, seq_len, top_k=0, top_p=0.92, repetition_penalty=1.1)."""
+    create_app(model, seq_len, top_k=0, top_p=0.92, repetition_penalty=1.1).  One sample_kvcache call per request (they queue
+    behind the engine's lock); create_batched_app serves concurrent requests as batches."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False)
+
+
+def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                       max_batch=None):
+    """create_app with request batching: concurrent requests are coalesced into batched generations by app.state.batcher
+    (mgea.serve.RequestBatcher, up to max_batch rows each -- default the model's max_batch) instead of one sample_kvcache call per
+    request.  Each request keeps its own seed and budget; the response also carries X-Batch-Rows, the number of requests its
+    generation served.  app.state.batcher.close() stops the worker."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=True, max_batch=max_batch)
+
+
+def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     from fastapi import FastAPI, Form
@@ -33,6 +47,10 @@ def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, t
         from fastapi import Query
         prompt_param = Query(...)
     app.state.prompt_in = "form" if prompt_param.__class__.__name__ == "Form" else "query"
+    app.state.batcher = None
+    if batch_requests:
+        from mgea.serve import RequestBatcher
+        app.state.batcher = RequestBatcher(model, max_batch=max_batch)
 
     @app.post("/generate")
     def generate_music(prompt: str = prompt_param):
@@ -44,11 +62,18 @@ def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, t
         for fam in mapping["all_families"]:                                   # :196-198
             instruments.extend(gen.FAMILY_TO_INSTRUMENTS.get(fam, []))
         gen_prompt = ["[START_SEQUENCE]", bpm_tok, key] + [f"[INSTRUMENT] {i}" for i in instruments]   # :203
-        tokens = gen.sample_kvcache(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k,
-                                    device="cpu", top_p=top_p, repetition_penalty=repetition_penalty)   # :204
+        extra = {}
+        if app.state.batcher is not None:   # the same request, served inside whatever batch is forming
+            fut = app.state.batcher.submit(gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, top_p=top_p,
+                                           repetition_penalty=repetition_penalty)
+            tokens = fut.result()
+            extra = {"X-Batch-Rows": str(fut.batch_rows)}
+        else:
+            tokens = gen.sample_kvcache(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k,
+                                        device="cpu", top_p=top_p, repetition_penalty=repetition_penalty)   # :204
         midi = tokens_to_midi(tokens)                                         # :208-221 (+ pm.write)
         return Response(content=midi, media_type="audio/midi",
                         headers={"X-Emotion": label, "X-Prompt-Tokens": str(len(gen_prompt)),
-                                 "X-Generated-Tokens": str(len(tokens))})
+                                 "X-Generated-Tokens": str(len(tokens)), **extra})
 
     return app

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cmath>
 #include <mutex>
+#include <vector>
 
 #include "common.h"
 
@@ -264,6 +265,34 @@ int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, cons
     // the kernel only reads the bitmap (it writes one only in the decoder's fused tail)
     return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, ids_out_dev, probs_out_dev, (hipStream_t)stream, nullptr,
                          const_cast<uint32_t*>(presence_dev), repetition_penalty);
+}
+
+int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                        int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream) {
+    MGEA_REQUIRE(logits_dev && rows && B > 0, MGEA_EINVAL, "op_sample_rows: NULL argument or empty batch");
+    MGEA_TRY(check_row_samplers(rows, B, V, -1, "op_sample_rows"));
+    std::vector<SamplerParams> rec((size_t)B);
+    bool pen = false;
+    for (int b = 0; b < B; ++b) {
+        rec[(size_t)b] = sampler_params(rows[b]);
+        pen = pen || rows[b].repetition_penalty != 1.0f;
+    }
+    MGEA_REQUIRE(!pen || presence_dev, MGEA_EINVAL, "op_sample_rows: a row is penalized but presence_dev is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    SamplerParams* rec_dev = nullptr;
+    MGEA_CHECK_HIP(hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)));
+    const mgea_sampler_config unused{1.0f, 0, 0.0f, -1, 0};   // every scalar comes from rec_dev
+    int rc = MGEA_EHIP;
+    if (hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st) == hipSuccess)
+        rc = launch_sample(logits_dev, B, V, unused, rec_dev, nullptr, step, ids_out_dev, probs_out_dev, st, nullptr,
+                           pen ? const_cast<uint32_t*>(presence_dev) : nullptr);
+    else
+        set_error("op_sample_rows: copy of the records failed");
+    const hipError_t e = hipStreamSynchronize(st);   // rec and rec_dev are freed below
+    (void)hipFree(rec_dev);
+    MGEA_TRY(rc);
+    MGEA_CHECK_HIP(e);
+    return MGEA_OK;
 }
 
 }  // extern "C"

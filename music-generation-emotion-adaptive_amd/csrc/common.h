@@ -183,17 +183,31 @@ int launch_attn_paged(const float* qkv, const KvPool& pool, int layer, const int
 int launch_attn_dense(const float* qkv, const int32_t* lens, const int32_t* mask, float* out, int B, int T,
                       int H, int dh, int tiled_out, hipStream_t st, const int32_t* cu = nullptr);   // cu: packed rows (T = the longest sequence)
 
-// The sampler's scalars as the kernels read them from DEVICE memory (one 32-byte record per engine): a captured
-// decode-step graph holds only the pointer, so one graph serves every request whatever its seed / temperature /
-// top-k / top-p / EOS id (mgea_sampler_config, api_cache.py:160,204).
+// The sampler's scalars as the kernels read them from DEVICE memory: one 48-byte record per row, [max_batch] per engine.  A captured
+// decode-step graph holds only the pointer, so one graph serves every request whatever its seed / temperature / top-k / top-p / EOS id
+// (mgea_sampler_config, api_cache.py:160,204) -- and a batch whose rows carry different ones (mgea_decoder_generate_rows).
 // penalty: the repetition penalty of a penalized generation (read only by the PENALTY sampler; 1 otherwise).
+// stream: word 0 of the row's Philox counter (the key is the seed); generate() writes stream = b.
+// max_new: the row's step budget -- it finishes after producing that many tokens (end_row_step); INT32_MAX = none.
+// ctx_cap: the tokens the row's KV pages hold when that is less than the longest prompt + the steps (launch_clamp_budgets); INT32_MAX = none.
 struct SamplerParams {
     float temperature; int32_t top_k; float top_p; int32_t eos_id;
-    uint32_t seed_lo, seed_hi; float penalty; int32_t pad1;
+    uint32_t seed_lo, seed_hi; float penalty; uint32_t stream;
+    int32_t max_new; int32_t ctx_cap; int32_t pad[2];
 };
+constexpr int32_t MGEA_NO_BUDGET = 0x7fffffff;
 static inline SamplerParams sampler_params(const mgea_sampler_config& s, float penalty = 1.0f) {
-    return SamplerParams{s.temperature, s.top_k, s.top_p, s.eos_id, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), penalty, 0};
+    return SamplerParams{s.temperature, s.top_k, s.top_p, s.eos_id, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), penalty, 0u,
+                         MGEA_NO_BUDGET, MGEA_NO_BUDGET, {0, 0}};
 }
+// a per-row record of the C ABI -> the device record (max_new_tokens 0 = no budget: the call's n_steps bound the row anyway)
+static inline SamplerParams sampler_params(const mgea_row_sampler& r) {
+    return SamplerParams{r.temperature, r.top_k, r.top_p, r.eos_id, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.repetition_penalty,
+                         r.stream, r.max_new_tokens > 0 ? r.max_new_tokens : MGEA_NO_BUDGET, MGEA_NO_BUDGET, {0, 0}};
+}
+// host check of rows[0, B) (mgea_decoder_generate_rows, mgea_op_sample_rows): MGEA_EINVAL naming the first bad row; n_steps < 0 skips the
+// budget check
+int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who);
 constexpr int MGEA_SAMPLER_MAX_VOCAB = 14336;   // the sampler keeps a row in registers: 256 threads x 56 logits
 // Repetition penalty (mgea_decoder_generate_penalized): per row a presence bitmap of ceil(V / 32) words, bit id & 31 of word id >> 5
 // set once the id is in the row's prompt or was generated by it.  Rows follow each other at that stride.
@@ -209,9 +223,8 @@ struct StepState {
     int32_t* n_done;    // [1]
     int32_t* ids_out;   // [B, n_steps] or NULL
     int32_t  n_steps;
-    int32_t  eos_id;            // used when params == NULL
-    const SamplerParams* params;   // device record whose eos_id wins (NULL: eos_id above)
-    __host__ __device__ int eos() const { return params ? params->eos_id : eos_id; }
+    int32_t  eos_id;            // used when params == NULL (no budget then)
+    const SamplerParams* params;   // [B] device records: row b's eos_id and max_new win (NULL: eos_id above)
 };
 // one query per sequence (the [CLS] position, fp32 q [B, D]) against the K | V columns of a packed qkv buffer [B * S, 3 D] (fp32 or bf16) -> fp32 [B, D]
 int launch_attn_cls(const float* q, const void* qkv, int qkv_bf16, const int32_t* mask, float* out, int B, int S, int H, int dh, hipStream_t st,
@@ -226,14 +239,21 @@ struct TailArgs {
     float* x; float* stats;     // k-tiled residual stream and its LayerNorm partials (fused decode path)
     int C, vocab, pos_rows, absolute_pos;
 };
-// params_dev != NULL: the scalars come from that device record instead of `s`
+// params_dev != NULL: row b's scalars come from the device record params_dev[b] instead of `s` (Philox counter word 0 = its stream instead
+// of b), and a row with top_k == 1 takes the exact argmax of its (penalized) row: no temperature division, ties to the lowest id
 // presence != NULL: the PENALTY form -- the logits of the ids whose bit is set in the row's presence bitmap (presence_words(V) words
 // per row) are penalized first, x < 0 ? x * p : x / p, p = penalty (or params_dev->penalty); with a tail the row's new token is then
 // added to that bitmap.  top_k == 1 there is the exact argmax of the penalized row (no temperature division, ties to the lowest id).
 int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
                   const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st,
                   const TailArgs* tail = nullptr, uint32_t* presence = nullptr, float penalty = 1.0f);
-int launch_set_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, hipStream_t st, float penalty = 1.0f);
+// params_dev[0, B) <- s (stream = b, no budget), stream-ordered: the uniform form of the records
+int launch_fill_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, int B, hipStream_t st, float penalty = 1.0f);
+// params_dev[b].max_new <- min(max_new, reserved - len_b), len_b = lens[b] (NULL: T) clamped to [1, T], and ctx_cap <- reserved: a row
+// stops where its KV pages end
+int launch_clamp_budgets(SamplerParams* params_dev, const int32_t* lens, int T, int B, int reserved, hipStream_t st);
+// after a generation with capped rows: done 2 (parked, end_row_step) -> 1 with ctx_len + 1
+int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st);
 // after ids for this step are in `sampled` [B]: apply EOS/done logic, write ids_out[b, step],
 // cur_ids, ctx_len += 1, row_step += 1; presence != NULL (bitmap of presence_words(V) words per row): also set the bit of the
 // token of every row that was not finished yet
@@ -422,34 +442,49 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 // st_* = the row's state as loaded by thread 0 at kernel start.  sh: >= 6 floats of shared scratch.
 // PENALTY: also set the token's bit in the row's presence bitmap (presence_words(vocab) words per row) while the row is not finished:
 // one writer per row, read by a later kernel, so a plain read-modify-write of the word.
+// The end of row b's decode step on every path (fused sampler tail, greedy argmax tails, advance_kernel), so the rule cannot drift between
+// them: a row that is not finished (done = its flag at step start, len = its ctx_len then) appends tok -- ids_out, cur_ids, ctx_len + 1 --
+// and finishes on its EOS id or when this was its last budgeted step (row_step + 1 == max_new): done = 1, n_done + 1.  row_step advances
+// either way.  Returns the token fed to the next step.
+// A finished row still runs every later step of its batch (fed its last token at position ctx_len, attending to ctx_len + 1 keys).  A
+// row that finishes with its pages full (ctx_len = ctx_cap) would read one key past them: it is parked one position short instead --
+// done = 2, ctx_len - 1, where its later steps only rewrite the last key -- and launch_unpark_rows restores both after the loop.
+__device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int tok, int step, int fed, int len, int done) {
+    int out = -1;
+    if (!done) {
+        out = tok;
+        fed = tok;
+        s.cur_ids[b] = tok;
+        s.ctx_len[b] = len + 1;
+        int eos = s.eos_id, max_new = mgea::MGEA_NO_BUDGET, cap = mgea::MGEA_NO_BUDGET;
+        if (s.params) { eos = s.params[b].eos_id; max_new = s.params[b].max_new; cap = s.params[b].ctx_cap; }
+        if (tok == eos || step + 1 == max_new) {
+            const bool park = len + 1 >= cap;
+            s.done[b] = park ? 2 : 1;
+            if (park) s.ctx_len[b] = len;
+            atomicAdd(s.n_done, 1);
+        }
+    }
+    if (s.ids_out && step < s.n_steps) s.ids_out[(int64_t)b * s.n_steps + step] = out;
+    s.row_step[b] = step + 1;
+    return fed;
+}
+
 template <bool PENALTY = false>
 __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::TailArgs& t, int32_t* sampled, int st_step, int st_fed,
                                                   int st_len, int st_done, float* sh, uint32_t* presence = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int* shi = reinterpret_cast<int*>(sh);
     if (tid == 0) {
-        const mgea::StepState& s = t.s;
         sampled[b] = tok;
-        int out = -1, fed = st_fed, len = st_len;
-        if (!st_done) {
-            out = tok;
-            fed = tok;
-            s.cur_ids[b] = tok;
-            len += 1;
-            s.ctx_len[b] = len;
-            if (tok == s.eos()) {
-                s.done[b] = 1;
-                atomicAdd(s.n_done, 1);
-            }
-            if constexpr (PENALTY) {
-                if ((unsigned)tok < (unsigned)t.vocab) {
-                    uint32_t* w = presence + (int64_t)b * mgea::presence_words(t.vocab) + (tok >> 5);
-                    *w = *w | (1u << (tok & 31));
-                }
+        const int fed = end_row_step(t.s, b, tok, st_step, st_fed, st_len, st_done);
+        const int len = st_done ? st_len : st_len + 1;
+        if constexpr (PENALTY) {
+            if (!st_done && (unsigned)tok < (unsigned)t.vocab) {
+                uint32_t* w = presence + (int64_t)b * mgea::presence_words(t.vocab) + (tok >> 5);
+                *w = *w | (1u << (tok & 31));
             }
         }
-        if (s.ids_out && st_step < s.n_steps) s.ids_out[(int64_t)b * s.n_steps + st_step] = out;
-        s.row_step[b] = st_step + 1;
         shi[4] = fed < 0 ? 0 : (fed >= t.vocab ? t.vocab - 1 : fed);
         const int pos = t.absolute_pos ? len : 0;   // reference: a decode step adds pos_emb[:1] = row 0 (api_cache.py:99)
         shi[5] = pos < t.pos_rows ? pos : t.pos_rows - 1;

@@ -104,13 +104,15 @@ struct mgea_decoder {
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
     // Captured decode-step graphs, one per (batch, greedy | sampled, penalized or not, steps).  Everything a step reads besides its
-    // structure lives in device memory (per-row state, page table, presence bitmaps, and the sampler's scalars in samp_dev), so a
-    // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty replays an existing graph: no capture, no
-    // instantiate.
+    // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
+    // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
+    // them -- replays an existing graph: no capture, no instantiate.
     struct GraphEntry { int batch; bool greedy; bool penalized; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
     std::vector<GraphEntry> graphs;
     uint64_t use_clock = 0;
-    SamplerParams* samp_dev = nullptr;
+    SamplerParams* samp_dev = nullptr;     // [max_batch] records, one per row (common.h)
+    SamplerParams* samp_stage = nullptr;   // [max_batch] pinned host records of mgea_decoder_generate_rows, copied to samp_dev in stream order
+    hipEvent_t stage_free = nullptr;       // recorded after that copy: the staging buffer may be rewritten once it has completed
     // repetition penalty: per row the set of ids it has seen (prompt + generated), [max_batch][presence_words(vocab)] (common.h);
     // seeded by a penalized generate() after its prefill, then updated by the kernel that commits each row's token
     uint32_t* presence = nullptr;
@@ -945,7 +947,9 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     if (hipMalloc((void**)&h->page_table, nb * h->max_pages) != hipSuccess || hipMalloc((void**)&h->ctx_len, nb) != hipSuccess ||
         hipMalloc((void**)&h->cur_ids, nb) != hipSuccess || hipMalloc((void**)&h->done, nb) != hipSuccess ||
         hipMalloc((void**)&h->row_step, nb) != hipSuccess || hipMalloc((void**)&h->sampled, nb) != hipSuccess ||
-        hipMalloc((void**)&h->n_done, 16) != hipSuccess || hipMalloc((void**)&h->samp_dev, sizeof(SamplerParams)) != hipSuccess ||
+        hipMalloc((void**)&h->n_done, 16) != hipSuccess || hipMalloc((void**)&h->samp_dev, cfg->max_batch * sizeof(SamplerParams)) != hipSuccess ||
+        hipHostMalloc((void**)&h->samp_stage, cfg->max_batch * sizeof(SamplerParams), 0) != hipSuccess ||
+        hipEventCreateWithFlags(&h->stage_free, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void**)&h->err_flag, 16) != hipSuccess ||
         hipMalloc((void**)&h->presence, (size_t)cfg->max_batch * presence_words(cfg->vocab) * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc((void**)&h->ids_hist, nb * h->ids_hist_stride) != hipSuccess)
@@ -962,7 +966,7 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     (void)hipMemset(h->row_step, 0, nb);
     (void)hipMemset(h->cur_ids, 0, nb);
     (void)hipMemset(h->n_done, 0, 16);
-    (void)hipMemset(h->samp_dev, 0, sizeof(SamplerParams));
+    (void)hipMemset(h->samp_dev, 0, cfg->max_batch * sizeof(SamplerParams));
     (void)hipMemset(h->err_flag, 0, 16);
     const int rc = ensure_ws(h, cfg->max_batch > 64 ? cfg->max_batch : 64);
     if (rc != MGEA_OK) {
@@ -998,6 +1002,8 @@ int mgea_decoder_destroy(mgea_decoder* h) {
                  h->samp_dev, h->err_flag, h->presence, h->arena_own, h->attn_split.part, h->attn_split.count};
     for (void* q : p)
         if (q) (void)hipFree(q);
+    if (h->samp_stage) (void)hipHostFree(h->samp_stage);
+    if (h->stage_free) (void)hipEventDestroy(h->stage_free);
     delete h;
     return MGEA_OK;
 }
@@ -1037,18 +1043,45 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
 }  // extern "C"
 
 namespace {
-// mgea_decoder_generate(_penalized); the caller holds h->mu.  penalty == 1: no penalty, exactly the unpenalized launch sequence.
+// mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
+// (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
+// are then ignored.
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
-                const mgea_sampler_config* s, float penalty, int32_t* ids_out_dev, hipStream_t st) {
+                const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, int32_t* ids_out_dev, hipStream_t st) {
     const auto& c = h->cfg;
-    const bool pen = penalty != 1.0f;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
-    MGEA_REQUIRE(Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
-    MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
+    // the step graphs' form: greedy only if every row is, penalized if any row is (p = 1 rows are unchanged by it: x * 1, x / 1 exact);
+    // the host poll for early stops when some row can finish before n_steps
+    mgea_sampler_config form{1.0f, 0, 0.0f, -1, 0};
+    bool pen = false, poll = false;
+    int reserve = Tp + n_steps;
+    if (rows) {
+        MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
+        MGEA_TRY(check_row_samplers(rows, B, c.vocab, n_steps, "decoder_generate_rows"));
+        // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
+        MGEA_REQUIRE(Tp < c.max_ctx && n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp, n_steps,
+                     c.max_ctx);
+        reserve = reserve < c.max_ctx ? reserve : c.max_ctx;
+        bool all_greedy = true;
+        for (int b = 0; b < B; ++b) {
+            const bool p1 = rows[b].repetition_penalty == 1.0f;
+            all_greedy = all_greedy && rows[b].top_k == 1 && p1;
+            pen = pen || !p1;
+            poll = poll || rows[b].eos_id >= 0 || (rows[b].max_new_tokens > 0 && rows[b].max_new_tokens < n_steps);
+        }
+        poll = poll || reserve < Tp + n_steps;
+        form.top_k = all_greedy ? 1 : 0;
+    } else {
+        MGEA_REQUIRE(Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
+        MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
+        form = *s;
+        pen = penalty != 1.0f;
+        poll = s->eos_id >= 0;
+    }
     h->last_penalized = false;
     h->counters[6] = 0;
-    MGEA_TRY(do_reset(h, B, Tp + n_steps, st));
+    MGEA_TRY(do_reset(h, B, reserve, st));
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
     if (pen) {   // every row's set starts as its real prompt tokens
         MGEA_TRY(launch_presence_seed(prompt_ids_dev, lens_dev, B, Tp, c.vocab, h->presence, st));
@@ -1056,15 +1089,23 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     }
     if (n_steps == 0) return MGEA_OK;
 
-    // the request's sampler scalars -> device memory (stream-ordered), then the cached step graph of this batch size:
+    // the rows' sampler records -> device memory (stream-ordered, no host sync), then the cached step graph of this batch size:
     // all per-step state lives in device memory, so one graph serves every step of every request
-    MGEA_TRY(launch_set_sampler_params(h->samp_dev, *s, st, penalty));
+    if (rows) {
+        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free));   // the previous call's copy out of the staging buffer has run
+        for (int b = 0; b < B; ++b) h->samp_stage[b] = sampler_params(rows[b]);
+        MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
+        MGEA_CHECK_HIP(hipEventRecord(h->stage_free, st));
+        if (reserve < Tp + n_steps) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
+    } else {
+        MGEA_TRY(launch_fill_sampler_params(h->samp_dev, *s, B, st, penalty));
+    }
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, *s, st, &gexec, 1, pen));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, st, &gexec, 1, pen));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, *s, st, &gexec_k, K, pen));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, st, &gexec_k, K, pen));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1072,12 +1113,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, *s, st, pen);
+            const int rc = enqueue_gen_step(h, B, form, st, pen);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, *s, st, pen));
+            MGEA_TRY(enqueue_gen_step(h, B, form, st, pen));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1086,12 +1127,13 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             MGEA_CHECK_HIP(hipGraphLaunch(gexec, st));
             ++launched;
         }
-        if (s->eos_id >= 0 && (launched % 16) == 0) {  // stop once every row has drawn EOS (api_cache.py:181)
+        if (poll && (launched % 16) == 0) {  // stop once every row has drawn EOS (api_cache.py:181) or spent its budget
             MGEA_CHECK_HIP(hipMemcpyAsync(&host_done, h->n_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             MGEA_CHECK_HIP(hipStreamSynchronize(st));
             if (host_done >= B) break;
         }
     }
+    if (reserve < Tp + n_steps) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
     h->host_max_len += launched;
     h->counters[1] = launched;
     h->counters[6] = pen ? launched : 0;
@@ -1111,7 +1153,7 @@ int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const 
                           void* stream) {
     MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, ids_out_dev, (hipStream_t)stream);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, nullptr, ids_out_dev, (hipStream_t)stream);
 }
 
 int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
@@ -1121,7 +1163,14 @@ int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_d
     MGEA_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, MGEA_EINVAL,
                  "decoder_generate: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
     std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, ids_out_dev, (hipStream_t)stream);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, nullptr, ids_out_dev, (hipStream_t)stream);
+}
+
+int mgea_decoder_generate_rows(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                               int32_t n_steps, const mgea_row_sampler* rows, int32_t* ids_out_dev, void* stream) {
+    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, ids_out_dev, (hipStream_t)stream);
 }
 
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream) {

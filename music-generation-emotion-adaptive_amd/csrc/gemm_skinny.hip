@@ -718,7 +718,7 @@ int launch_embed_stats(const int32_t* ids, const int32_t* lens, const int32_t* c
 
 // ------------------------------------------------------------------------------------------
 // greedy finalize: argmax over the per-tile partials of each row, then the sampler-loop
-// bookkeeping of api_cache.py:179-181 (append, EOS stop) -- one 64-thread workgroup per row.
+// bookkeeping of api_cache.py:179-181 (append, EOS or budget stop: end_row_step) -- one 64-thread workgroup per row.
 __global__ __launch_bounds__(64) void argmax_advance_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
                                                            int n_tiles, StepState s, int32_t* __restrict__ sampled) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -738,19 +738,7 @@ __global__ __launch_bounds__(64) void argmax_advance_kernel(const float* __restr
     if (lane == 0) {
         const int tok = bi == 0x7fffffff ? 0 : bi;
         sampled[b] = tok;
-        const int step = s.row_step[b];
-        int out = -1;
-        if (!s.done[b]) {
-            out = tok;
-            s.cur_ids[b] = tok;
-            s.ctx_len[b] += 1;
-            if (tok == s.eos()) {
-                s.done[b] = 1;
-                atomicAdd(s.n_done, 1);
-            }
-        }
-        if (s.ids_out && step < s.n_steps) s.ids_out[(int64_t)b * s.n_steps + step] = out;
-        s.row_step[b] = step + 1;
+        end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], s.done[b]);
     }
 }
 

@@ -361,26 +361,14 @@ template <bool PENALTY>
 __global__ void advance_kernel(const int32_t* __restrict__ sampled, StepState s, int B, uint32_t* __restrict__ presence, int V) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int step = s.row_step[b];
-    int out = -1;
-    if (!s.done[b]) {
-        const int tok = sampled[b];
-        out = tok;
-        s.cur_ids[b] = tok;
-        s.ctx_len[b] += 1;  // the token fed this step now sits in the cache
-        if (tok == s.eos()) {
-            s.done[b] = 1;
-            atomicAdd(s.n_done, 1);
-        }
-        if constexpr (PENALTY) {
-            if ((unsigned)tok < (unsigned)V) {
-                uint32_t* w = presence + (int64_t)b * presence_words(V) + (tok >> 5);
-                *w = *w | (1u << (tok & 31));
-            }
+    const int done = s.done[b], tok = sampled[b];
+    end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], done);   // ctx_len + 1: the token fed this step now sits in the cache
+    if constexpr (PENALTY) {
+        if (!done && (unsigned)tok < (unsigned)V) {
+            uint32_t* w = presence + (int64_t)b * presence_words(V) + (tok >> 5);
+            *w = *w | (1u << (tok & 31));
         }
     }
-    if (s.ids_out && step < s.n_steps) s.ids_out[(int64_t)b * s.n_steps + step] = out;
-    s.row_step[b] = step + 1;
 }
 
 int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence, int V) {

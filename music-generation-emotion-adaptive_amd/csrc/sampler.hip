@@ -26,9 +26,11 @@
 // set in the row's presence bitmap becomes x < 0 ? x * p : x / p (one correctly rounded fp32 operation).  The row's bitmap words are
 // staged in LDS first (<= 448 words: two per thread at most).  top_k == 1 there is the greedy step of a penalized generation: the
 // kept entry is the penalized argmax (lowest id among equals), so the temperature division -- which could merge neighbours -- is skipped.
-// The sampler's scalars (temperature, top_k, top_p, seed; eos for the fused tail) are read from a SamplerParams
-// record in DEVICE memory when the caller passes one: the captured decode graph then serves every request, whatever
-// its seed (the reference's endpoint draws a fresh one per call, api_cache.py:204).
+// The sampler's scalars (temperature, top_k, top_p, seed, Philox stream; eos and budget for the fused tail) are read from the row's
+// SamplerParams record in DEVICE memory when the caller passes the records: the captured decode graph then serves every request, whatever
+// its seed (the reference's endpoint draws a fresh one per call, api_cache.py:204), and rows with different settings share one launch
+// (workgroup b reads record b, so every setting stays block-uniform).  With records, a top_k == 1 row is the exact argmax of its
+// (penalized) row as in the PENALTY form: no temperature division.
 #include <cmath>
 
 #include "common.h"
@@ -311,7 +313,8 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     __shared__ unsigned long long s_hist[NT];
     static_assert(NT == 256, "the mass histogram has one bucket per thread");
     __shared__ int s_tie[NW], s_fit[NW];
-    if (pd) pv = *pd;   // device-resident scalars (one 32-byte scalar load) win over the by-value copy
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (pd) pv = pd[b];   // the row's device-resident scalars win over the by-value copy
     const float temperature = pv.temperature, top_p = pv.top_p;
     const int top_k = pv.top_k;
     const uint64_t seed = ((uint64_t)pv.seed_hi << 32) | pv.seed_lo;
@@ -320,7 +323,6 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     __shared__ int s_thread, s_choice;
     __shared__ float sh_tail[8];
 
-    const int b = blockIdx.x, tid = threadIdx.x;
     const float* lg = logits + (int64_t)b * V;
     int st_step = 0, st_fed = 0, st_len = 0, st_done = 0;   // the row's loop state, for the fused tail
     if (fuse_tail && tid == 0) {
@@ -347,7 +349,7 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         }
     }
     float mx = -INFINITY;
-    if (temperature != 1.0f && !(PENALTY && top_k == 1)) {   // logits / temperature (api_cache.py:170); x / 1 is x
+    if (temperature != 1.0f && !((PENALTY || pd) && top_k == 1)) {   // logits / temperature (api_cache.py:170); x / 1 is x
 #pragma unroll
         for (int j = 0; j < MAXE; ++j) x[j] = x[j] / temperature;
     }
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
             if (tid + NT * j < V) probs_out[(int64_t)b * V + tid + NT * j] = e[j] * inv;
     }
     if (!ids_out) return;
-    uint32_t ctr[4] = {(uint32_t)b, (uint32_t)(row_step ? row_step[b] : (int32_t)step_host),
+    uint32_t ctr[4] = {pd ? pv.stream : (uint32_t)b, (uint32_t)(row_step ? row_step[b] : (int32_t)step_host),
                        (uint32_t)(step_host >> 32), 0x6d676561u};
     philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), ctr);
     const float u = (float)(ctr[0] >> 8) * (1.0f / 16777216.0f);  // [0, 1)
@@ -589,12 +591,63 @@ int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& 
     return MGEA_OK;
 }
 
-// params_dev <- s, stream-ordered (a kernel argument, so no host buffer has to outlive the call)
-__global__ void set_sampler_params_kernel(SamplerParams* dst, SamplerParams v) { *dst = v; }
+// params_dev[0, B) <- v with stream = b, stream-ordered (a kernel argument, so no host buffer has to outlive the call)
+__global__ void fill_sampler_params_kernel(SamplerParams* __restrict__ dst, SamplerParams v, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    v.stream = (uint32_t)b;
+    dst[b] = v;
+}
 
-int launch_set_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, hipStream_t st, float penalty) {
-    hipLaunchKernelGGL(set_sampler_params_kernel, dim3(1), dim3(1), 0, st, params_dev, sampler_params(s, penalty));
+int launch_fill_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, int B, hipStream_t st, float penalty) {
+    hipLaunchKernelGGL(fill_sampler_params_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, params_dev, sampler_params(s, penalty), B);
     MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+__global__ void clamp_budgets_kernel(SamplerParams* __restrict__ p, const int32_t* __restrict__ lens, int T, int B, int reserved) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int n = lens ? lens[b] : T;
+    n = n < 1 ? 1 : (n > T ? T : n);
+    const int room = reserved - n;   // >= 1: the caller checked T < reserved
+    if (p[b].max_new > room) p[b].max_new = room;
+    p[b].ctx_cap = reserved;
+}
+
+int launch_clamp_budgets(SamplerParams* params_dev, const int32_t* lens, int T, int B, int reserved, hipStream_t st) {
+    MGEA_REQUIRE(T < reserved, MGEA_EINVAL, "budgets: prompt width %d leaves no room in %d tokens", T, reserved);
+    hipLaunchKernelGGL(clamp_budgets_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, params_dev, lens, T, B, reserved);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+__global__ void unpark_rows_kernel(int32_t* __restrict__ done, int32_t* __restrict__ ctx_len, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B && done[b] == 2) {
+        done[b] = 1;
+        ctx_len[b] += 1;
+    }
+}
+
+int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st) {
+    hipLaunchKernelGGL(unpark_rows_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, done, ctx_len, B);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who) {
+    MGEA_REQUIRE(rows, MGEA_EINVAL, "%s: rows is NULL", who);
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_sampler& r = rows[b];
+        MGEA_REQUIRE(std::isfinite(r.temperature) && r.temperature > 0.f, MGEA_EINVAL, "%s: row %d: temperature must be finite and > 0 (got %g)",
+                     who, b, (double)r.temperature);
+        MGEA_REQUIRE(r.top_k >= 0 && r.top_k <= V, MGEA_EINVAL, "%s: row %d: top_k %d outside [0, %d]", who, b, r.top_k, V);
+        MGEA_REQUIRE(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f, MGEA_EINVAL,
+                     "%s: row %d: repetition_penalty must be finite and > 0 (got %g)", who, b, (double)r.repetition_penalty);
+        MGEA_REQUIRE(n_steps < 0 || (r.max_new_tokens >= 0 && r.max_new_tokens <= n_steps), MGEA_EINVAL,
+                     "%s: row %d: max_new_tokens %d outside [0, %d]", who, b, r.max_new_tokens, n_steps);
+    }
     return MGEA_OK;
 }
 

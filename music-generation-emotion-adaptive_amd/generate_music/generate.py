@@ -24,11 +24,11 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from mgea.decoder import DecoderEngine, geometry_from_state_dict, remap_state_dict  # noqa: F401
+from mgea.decoder import DecoderEngine, RowSampling, geometry_from_state_dict, remap_state_dict  # noqa: F401
 
 __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab", "encode", "decode",
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
-           "generate_sequence", "sample", "tok2id", "id2tok"]
+           "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
 tok2id: Dict[str, int] = {}
@@ -242,6 +242,52 @@ def generate_batch(model, prompts: Sequence[Sequence[str]], max_len=512, tempera
     out = eng.generate(ids, max(n_steps, 0), temperature=temperature, top_k=top_k, top_p=top_p, eos_id=eos,
                        seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty).cpu().tolist()
     return [[id2tok[i] for i in p + [g for g in row if g >= 0]] for p, row in zip(ids, out)]
+
+
+def _per_prompt(value, n: int, name: str) -> list:
+    """a scalar for every prompt, or a list / tuple of exactly one value per prompt"""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{name}: {len(value)} values for {n} prompts")
+        return list(value)
+    return [value] * n
+
+
+def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
+                      top_p: Optional[float] = None, seed=None, repetition_penalty=None) -> List[List[str]]:
+    """Independent sample_kvcache requests served by one batched generation (up to the engine's max_batch rows per
+    generation; more prompts take several).  Every argument may be a scalar or a list with one value per prompt.  Prompt i
+    gets max_len_i - len(prompt_i) new tokens and stops after [END_SEQUENCE], like sample_kvcache; a seed of None is drawn
+    with torch's generator (torch.manual_seed makes it reproducible).  Each row draws from Philox stream 0 under its own
+    seed, the stream sample_kvcache uses for that seed.  Returns the prompt + generated tokens of each request, in order.
+    Greedy rows (top_k=1) equal the reference run of their prompt alone; sampled rows depend on their own settings and on
+    the batch size (kernel choice), not on the other requests."""
+    m = _as_model(model)
+    eng = m._need()
+    n = len(prompts)
+    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
+    temps = _per_prompt(temperature, n, "temperature")
+    ks = _per_prompt(top_k, n, "top_k")
+    ps = _per_prompt(top_p, n, "top_p")
+    seeds = _per_prompt(seed, n, "seed")
+    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
+    ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
+    budgets = [L - len(p) for L, p in zip(max_lens, ids)]
+    for L, p in zip(max_lens, ids):
+        if L > len(p) and L > eng.max_ctx:
+            raise RuntimeError(f"max_len={L} exceeds the engine's reserved context {eng.max_ctx}")
+    eos = tok2id.get("[END_SEQUENCE]", -1)
+    live = [i for i in range(n) if budgets[i] > 0]
+    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
+                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0)
+            for i in live}
+    gen: Dict[int, List[int]] = {}
+    for c0 in range(0, len(live), eng.max_batch):
+        part = live[c0:c0 + eng.max_batch]
+        out = eng.generate_rows([ids[i] for i in part], [rows[i] for i in part], max(budgets[i] for i in part)).cpu().tolist()
+        for i, row in zip(part, out):
+            gen[i] = [g for g in row if g >= 0]
+    return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]
 
 
 def sample(prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu") -> List[str]:

@@ -34,6 +34,13 @@ class SamplerConfig(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class RowSampler(C.Structure):
+    """mgea_row_sampler: one batch row's sampler settings (mgea_decoder_generate_rows, mgea_op_sample_rows)."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+                ("eos_id", C.c_int32), ("max_new_tokens", C.c_int32), ("seed", C.c_uint64), ("stream", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -59,6 +66,7 @@ PROTOTYPES = {
     "mgea_decoder_step": (C.c_int, [_P, _P, C.POINTER(SamplerConfig), _P, _P, _P]),
     "mgea_decoder_generate": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(SamplerConfig), _P, _P]),
     "mgea_decoder_generate_penalized": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _P]),
+    "mgea_decoder_generate_rows": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), _P, _P]),
     "mgea_decoder_presence": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_context_lengths": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_stats": (C.c_int, [_P, C.POINTER(_I64)]),
@@ -92,6 +100,7 @@ PROTOTYPES = {
     "mgea_op_skinny_logits_partials": (C.c_int, [_I32, _I32, _I32]),
     "mgea_op_sample": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _I64, _P, _P, _P]),
     "mgea_op_sample_penalized": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _I64, _P, _P, _P]),
+    "mgea_op_sample_rows": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, _I64, _P, _P, _P]),
 }
 
 _lib = None

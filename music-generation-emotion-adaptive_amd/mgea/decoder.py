@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
+import math
 import re
 from typing import Dict, List, Optional, Sequence
 
@@ -15,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DecoderConfig, SamplerConfig, check, ptr
+from ._lib import DecoderConfig, RowSampler, SamplerConfig, check, ptr
 
 _LAYER_TENSORS = ["ln1.weight", "ln1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
                   "attn.out_proj.bias", "ln2.weight", "ln2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
@@ -71,6 +73,70 @@ def arena_layout(geometry: Dict[str, int], n_head: int = 8):
 # training-checkpoint tensor-name suffixes of the matrices the fp16 mode stores in fp16 (everything else stays fp32)
 F16_ROUNDED_KEYS = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight", "fc.weight",
                     "attn.in_proj_weight", "attn.out_proj.weight", "mlp.0.weight", "mlp.2.weight", "head.weight")
+
+
+@dataclasses.dataclass
+class RowSampling:
+    """One batch row's sampler settings (mgea_row_sampler, include/mgea.h) for DecoderEngine.generate_rows / ops.sample_rows.
+    top_k None or 0 = no cut, 1 = greedy (the exact argmax, no temperature division); top_p None = no nucleus cut;
+    repetition_penalty None = 1 = none; max_new_tokens 0 = the call's n_steps; stream None = the row's index in the batch (what
+    generate() uses).  The row draws its step-t number from Philox counter (stream, t) under key seed."""
+    temperature: float = 1.0
+    top_k: Optional[int] = 50
+    top_p: Optional[float] = None
+    repetition_penalty: Optional[float] = None
+    eos_id: int = -1
+    max_new_tokens: int = 0
+    seed: int = 0
+    stream: Optional[int] = None
+
+    def check(self, row: int, vocab: int, n_steps: Optional[int] = None) -> None:
+        """ValueError naming the row for what the native call would refuse (MGEA_EINVAL)."""
+        from . import ops
+        t = float(self.temperature)
+        if not (math.isfinite(t) and t > 0 and math.isfinite(float(np.float32(t))) and float(np.float32(t)) > 0):
+            raise ValueError(f"row {row}: temperature must be finite and > 0, got {self.temperature}")
+        k = int(self.top_k or 0)
+        if not 0 <= k <= vocab:
+            raise ValueError(f"row {row}: top_k {k} outside [0, {vocab}]")
+        try:
+            ops.check_repetition_penalty(self.repetition_penalty)
+        except ValueError as e:
+            raise ValueError(f"row {row}: {e}") from None
+        if n_steps is not None and not 0 <= int(self.max_new_tokens) <= n_steps:
+            raise ValueError(f"row {row}: max_new_tokens {self.max_new_tokens} outside [0, {n_steps}]")
+        if self.stream is not None and not 0 <= int(self.stream) < 2 ** 32:
+            raise ValueError(f"row {row}: stream {self.stream} is not a 32-bit word")
+
+    def record(self, row: int) -> RowSampler:
+        pen = self.repetition_penalty
+        return RowSampler(temperature=float(self.temperature), top_k=int(self.top_k or 0), top_p=float(self.top_p or 0.0),
+                          repetition_penalty=1.0 if pen is None else float(pen), eos_id=int(self.eos_id),
+                          max_new_tokens=int(self.max_new_tokens), seed=int(self.seed) & (2 ** 64 - 1),
+                          stream=(row if self.stream is None else int(self.stream)) & 0xFFFFFFFF, reserved=0)
+
+
+def pack_rows(rows: Sequence[RowSampling], vocab: int, n_steps: Optional[int] = None):
+    """Check every record (ValueError naming the row) and pack them as the C array mgea_row_sampler[B]."""
+    rows = list(rows)
+    for b, r in enumerate(rows):
+        r.check(b, vocab, n_steps)
+    return (RowSampler * len(rows))(*[r.record(b) for b, r in enumerate(rows)])
+
+
+def _prompt_ids(prompts):
+    """prompts (id lists, ragged ok, or an int tensor [B, Tp]) -> (int32 ids [B, Tp] on the host, lens [B] or None)"""
+    if isinstance(prompts, torch.Tensor):
+        return prompts.to(torch.int32), None
+    B = len(prompts)
+    if B == 0 or min(len(p) for p in prompts) < 1:
+        raise ValueError("empty prompt")
+    Tp = max(len(p) for p in prompts)
+    ids = torch.zeros(B, Tp, dtype=torch.int32)
+    for b, p in enumerate(prompts):
+        ids[b, :len(p)] = torch.tensor(list(p), dtype=torch.int32)
+    lens = None if all(len(p) == Tp for p in prompts) else torch.tensor([len(p) for p in prompts], dtype=torch.int32)
+    return ids, lens
 
 
 class DecoderEngine:
@@ -262,18 +328,7 @@ class DecoderEngine:
         (mgea_decoder_generate_penalized); presence() then returns those sets."""
         from . import ops
         pen = ops.check_repetition_penalty(repetition_penalty)
-        if isinstance(prompts, torch.Tensor):
-            ids = prompts.to(torch.int32)
-            lens = None
-        else:
-            B = len(prompts)
-            Tp = max(len(p) for p in prompts)
-            if min(len(p) for p in prompts) < 1:
-                raise ValueError("empty prompt")
-            ids = torch.zeros(B, Tp, dtype=torch.int32)
-            for b, p in enumerate(prompts):
-                ids[b, :len(p)] = torch.tensor(list(p), dtype=torch.int32)
-            lens = None if all(len(p) == Tp for p in prompts) else torch.tensor([len(p) for p in prompts], dtype=torch.int32)
+        ids, lens = _prompt_ids(prompts)
         B, Tp = ids.shape
         checked = self._check_ids(ids)
         samp = self.sampler(temperature, top_k, top_p, eos_id, seed)
@@ -287,6 +342,38 @@ class DecoderEngine:
             else:
                 check(self.lib.mgea_decoder_generate_penalized(self.h, ptr(ids), ptr(lens), B, Tp, int(n_steps), C.byref(samp),
                                                                pen, ptr(out), self._sp()))
+        self._cur_batch = B
+        self._epoch += 1
+        if check_ids and not checked:
+            self.id_errors()
+        return out[:, :n_steps]
+
+    def generate_rows(self, prompts, rows: Sequence[RowSampling], n_steps: Optional[int] = None,
+                      check_ids: bool = True) -> torch.Tensor:
+        """generate() with one RowSampling per prompt (mgea_decoder_generate_rows): concurrent requests with their own temperature,
+        top-k, top-p, repetition penalty, EOS id, seed, Philox stream and step budget in one batch.  n_steps None = the largest
+        max_new_tokens (every row then needs one > 0).  Returns int32 [B, n_steps]; -1 after a row's EOS or budget.  A row's ids
+        depend on its prompt, its record and B, not on its index or on the other rows; with stream = b and no budget on every row
+        this is generate().  Each row needs len(prompt) + its budget <= max_ctx: a row that would run past the context reserved
+        for the batch, min(longest prompt + n_steps, max_ctx), finishes there."""
+        rows = list(rows)
+        ids, lens = _prompt_ids(prompts)
+        B, Tp = ids.shape
+        if len(rows) != B:
+            raise ValueError(f"{B} prompts but {len(rows)} sampler rows")
+        if n_steps is None:
+            budgets = [int(r.max_new_tokens) for r in rows]
+            if min(budgets) <= 0:
+                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
+            n_steps = max(budgets)
+        n_steps = int(n_steps)
+        recs = pack_rows(rows, self.vocab, n_steps)
+        checked = self._check_ids(ids)
+        with self._on_stream():
+            ids = ids.to(self.device).contiguous()
+            lens = None if lens is None else lens.to(self.device).contiguous()
+            out = torch.empty(B, max(n_steps, 1), dtype=torch.int32, device=self.device)
+            check(self.lib.mgea_decoder_generate_rows(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, ptr(out), self._sp()))
         self._cur_batch = B
         self._epoch += 1
         if check_ids and not checked:

@@ -204,6 +204,27 @@ def sample(logits: torch.Tensor, temperature=1.0, top_k=50, top_p=None, seed=0, 
     return (ids, probs) if want_probs else ids
 
 
+def sample_rows(logits: torch.Tensor, rows, step=0, want_probs=False, presence=None):
+    """sample() with one mgea.decoder.RowSampling per row (mgea_op_sample_rows): row b reads rows[b] and draws from Philox counter
+    (stream_b, step) under key seed_b (stream None = b).  presence (a bool [B, V] mask or B id lists) is what the penalized rows
+    penalize; none if None.  top_k=1 rows take the exact argmax of their (penalized) row, without the temperature division."""
+    from .decoder import pack_rows
+    lib = _lib.load()
+    logits = _dev(logits.float())
+    B, V = logits.shape
+    recs = pack_rows(rows, V)
+    if len(recs) != B:
+        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
+    bits = None
+    if any(r.repetition_penalty != 1.0 for r in recs):
+        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
+        bits = torch.from_numpy(words.view(np.int32)).to(logits.device)
+    ids = torch.empty(B, dtype=torch.int32, device=logits.device)
+    probs = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_probs else None
+    check(lib.mgea_op_sample_rows(ptr(logits), B, V, recs, ptr(bits), int(step), ptr(ids), ptr(probs), stream_ptr()))
+    return (ids, probs) if want_probs else ids
+
+
 def tile_weights(w: torch.Tensor) -> torch.Tensor:
     """W [N,K] row-major -> the fragment-ordered layout the skinny GEMM reads (rows padded to 32)."""
     lib = _lib.load()
