@@ -189,9 +189,41 @@ typedef struct mgea_row_sampler {
 int mgea_decoder_generate_rows(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
                                int32_t n_steps, const mgea_row_sampler* rows, int32_t* ids_out_dev, void* stream);
 
+/* Per-row logit bias and minimum length (mgea_decoder_generate_rows_biased, mgea_op_sample_rows_biased): one record per batch row,
+ * next to the row's mgea_row_sampler.  Build-defined (the reference has no logits processors); the HuggingFace equivalents are
+ * sequence_bias / suppress_tokens / min_new_tokens, OpenAI's is logit_bias.  At every decode step of row b, on the raw head logits x:
+ *   1. the repetition penalty over seen_b, exactly as in mgea_decoder_generate_penalized;
+ *   2. x[i] += bias_dev[i], one fp32 add (-inf bans id i); a row with bias_dev == NULL is not touched (no + 0);
+ *   3. if the row's eos_id >= 0 and it has produced fewer than min_new_tokens ids so far (its step index, word 1 of its Philox
+ *      counter), x[eos_id] = -inf;
+ *   4. the sampler runs unchanged on the result: / temperature, top-k, top-p, softmax, Philox draw.  top_k == 1 is the exact argmax
+ *      of the processed row (ties to the lowest id, no temperature division).  A banned id has probability exactly 0 and is never
+ *      drawn, also where it is among the top_k kept because fewer than top_k ids are admissible.
+ * Checked on the host (MGEA_EINVAL naming the row): reserved == 0 and 0 <= min_new_tokens <= n_steps.  The caller guarantees the rest,
+ * as for cu_seqlens: bias_dev holds vocab fp32 values in device memory, none of them NaN or +inf, at least one finite -- and at least
+ * one finite besides eos_id if min_new_tokens > 0 and eos_id >= 0.  A row with no admissible id neither hangs nor faults; it yields
+ * id 0. */
+typedef struct mgea_row_logits {
+    const float* bias_dev;         /* [vocab] fp32 device, NULL = none; rows may share one vector */
+    int32_t      min_new_tokens;   /* 0 = none */
+    int32_t      reserved;         /* 0 */
+} mgea_row_logits;
+
+/* mgea_decoder_generate_rows with one mgea_row_logits per row, logits_rows [B] (host memory, read before the call returns);
+ * logits_rows == NULL is exactly mgea_decoder_generate_rows.  The engine copies each row's vector into its own [max_batch][vocab]
+ * buffer in stream order (no host sync: the caller's vectors must stay valid until `stream` has passed the call), so the step graphs
+ * hold stable pointers and a request with other bias values replays the cached graph.  If any row has a bias or min_new_tokens > 0
+ * the generation takes the biased form: the logits-row + sampler sequence of the penalized form with the bias applied in the
+ * sampler's registers, presence bitmaps for every row (a penalty of 1 changes nothing), its own step graphs.  Rows without a bias
+ * keep the ids they get in a batch of that size in which no row has one.  Otherwise the forms of mgea_decoder_generate_rows are
+ * untouched.  mgea_decoder_stats out[7] counts the biased steps. */
+int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                      int32_t* ids_out_dev, void* stream);
+
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
- * generate applied no penalty. */
+ * generate applied no penalty (a biased generation keeps the bitmaps too). */
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream);
 
 /* Current cached length of each row -> lens_out_dev [B] (device int32). */
@@ -209,7 +241,8 @@ int mgea_decoder_profile_read(mgea_decoder* h, double* ms_by_class, int64_t* lau
 /* out[0] kernels in the step graph last used, [1] graph replays of the last generate(), [2] graph
  * captures + instantiations over the handle's lifetime, [4] graphs cached now, [5] forwards that ran on the f16 matrix-core
  * prefill path (MGEA_DTYPE_F16 engines, empty cache, batch * T big enough: csrc/decoder.hip run_prefill16), [6] decode steps
- * of the last generate() that applied a repetition penalty (0 if it applied none); others 0. */
+ * of the last generate() that applied a repetition penalty (0 if it applied none), [7] decode steps of the last generate() that
+ * applied a logit bias or min_new_tokens (0 if it applied none); others 0. */
 int mgea_decoder_stats(mgea_decoder* h, int64_t* out /* [8] */);
 
 /* Token ids outside [0, vocab) make nn.Embedding raise IndexError in the reference (api_cache.py:99).
@@ -366,6 +399,12 @@ int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, cons
  * the exact argmax of their (penalized) row, without the temperature division.  Synchronises `stream` before it returns. */
 int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                         int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream);
+/* mgea_op_sample_rows on the processed logits of mgea_decoder_generate_rows_biased: logits_rows [B] (host) or NULL (then exactly
+ * mgea_op_sample_rows).  Row b adds logits_rows[b].bias_dev (V fp32, device) after its penalty and bans rows[b].eos_id (when >= 0)
+ * while step < logits_rows[b].min_new_tokens.  The vectors are gathered into a temporary [B][V] buffer; synchronises `stream`. */
+int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows,
+                               const uint32_t* presence_dev, const mgea_row_logits* logits_rows, int64_t step, int32_t* ids_out_dev,
+                               float* probs_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,25 +11,51 @@ the accelerated path).
 from __future__ import annotations
 
 
+CONSTRAINTS = (None, "notes", "scale")
+
+
 def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None):
     """top_p / repetition_penalty (None = none) reach sample_kvcache; the paper's decoding setting (§10.3) is
     create_app(model, seq_len, top_k=0, top_p=0.92, repetition_penalty=1.1).  One sample_kvcache call per request (they queue
-    behind the engine's lock); create_batched_app serves concurrent requests as batches."""
+    behind the engine's lock); create_batched_app serves concurrent requests as batches; create_constrained_app is this
+    endpoint with a constraint on what may be drawn."""
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False)
 
 
+def create_constrained_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                           constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
+    """create_app with a constraint on the tokens a request may draw (create_app keeps its parameter list; create_batched_app takes
+    the same three options).
+    constrain (build-defined, the reference samples the raw vocabulary): None = no constraint; "notes" = after the prompt only
+    note, instrument and [END_SEQUENCE] tokens can be drawn (the detokeniser drops everything else); "scale" = also only notes of
+    the emotion's key (mapping["key"]; out_of_scale_bias = -inf bans the others, a finite value is added to their logits instead).
+    min_new_tokens > 0 keeps [END_SEQUENCE] from being drawn before that many tokens.  The bias vectors (generate_music.constraints)
+    are built once per key and kept on the device; the response carries X-Constraint."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens)
+
+
 def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                       max_batch=None):
+                       max_batch=None, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
     """create_app with request batching: concurrent requests are coalesced into batched generations by app.state.batcher
     (mgea.serve.RequestBatcher, up to max_batch rows each -- default the model's max_batch) instead of one sample_kvcache call per
     request.  Each request keeps its own seed and budget; the response also carries X-Batch-Rows, the number of requests its
     generation served.  app.state.batcher.close() stops the worker."""
-    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=True, max_batch=max_batch)
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=True, max_batch=max_batch,
+                      constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens)
 
 
-def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None):
+def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
+               out_of_scale_bias=float("-inf"), min_new_tokens=0):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
+    if constrain not in CONSTRAINTS:
+        raise ValueError(f"constrain must be one of {CONSTRAINTS}, got {constrain!r}")
+    out_of_scale_bias = float(out_of_scale_bias)
+    if out_of_scale_bias != out_of_scale_bias or out_of_scale_bias == float("inf"):
+        raise ValueError("out_of_scale_bias must be finite or -inf")
+    if int(min_new_tokens) < 0:
+        raise ValueError(f"min_new_tokens {min_new_tokens} is negative")
     from fastapi import FastAPI, Form
     from fastapi.middleware.cors import CORSMiddleware
     from fastapi.responses import Response
@@ -48,9 +74,23 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
         prompt_param = Query(...)
     app.state.prompt_in = "form" if prompt_param.__class__.__name__ == "Form" else "query"
     app.state.batcher = None
+    app.state.on_tokens = None   # a callable set here receives every response's token list (tests look behind the MIDI with it)
     if batch_requests:
         from mgea.serve import RequestBatcher
         app.state.batcher = RequestBatcher(model, max_batch=max_batch)
+
+    bias_cache = {}   # key token (None for "notes") -> the constraint's bias vector on the model's device
+
+    def constraint_bias(key_token):
+        if constrain is None:
+            return None
+        k = key_token if constrain == "scale" else None
+        if k not in bias_cache:
+            import torch
+            from generate_music import constraints
+            vec = constraints.logit_bias(gen.tok2id, key=k, notes_only=True, out_of_scale=out_of_scale_bias)
+            bias_cache[k] = torch.from_numpy(vec).to(model._need().device)
+        return bias_cache[k]
 
     @app.post("/generate")
     def generate_music(prompt: str = prompt_param):
@@ -63,14 +103,21 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             instruments.extend(gen.FAMILY_TO_INSTRUMENTS.get(fam, []))
         gen_prompt = ["[START_SEQUENCE]", bpm_tok, key] + [f"[INSTRUMENT] {i}" for i in instruments]   # :203
         extra = {}
+        bias = constraint_bias(key)
+        if constrain is not None:
+            extra["X-Constraint"] = constrain
+        more = {} if bias is None and not min_new_tokens else dict(logit_bias=bias, min_new_tokens=int(min_new_tokens))
         if app.state.batcher is not None:   # the same request, served inside whatever batch is forming
             fut = app.state.batcher.submit(gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, top_p=top_p,
-                                           repetition_penalty=repetition_penalty)
+                                           repetition_penalty=repetition_penalty, **more)
             tokens = fut.result()
-            extra = {"X-Batch-Rows": str(fut.batch_rows)}
+            extra["X-Batch-Rows"] = str(fut.batch_rows)
         else:
-            tokens = gen.sample_kvcache(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k,
-                                        device="cpu", top_p=top_p, repetition_penalty=repetition_penalty)   # :204
+            call = gen.sample_kvcache_biased if more else gen.sample_kvcache
+            tokens = call(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu", top_p=top_p,
+                          repetition_penalty=repetition_penalty, **more)   # :204
+        if app.state.on_tokens is not None:
+            app.state.on_tokens(tokens)
         midi = tokens_to_midi(tokens)                                         # :208-221 (+ pm.write)
         return Response(content=midi, media_type="audio/midi",
                         headers={"X-Emotion": label, "X-Prompt-Tokens": str(len(gen_prompt)),

@@ -269,27 +269,51 @@ int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, cons
 
 int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                         int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream) {
+    return mgea_op_sample_rows_biased(logits_dev, B, V, rows, presence_dev, nullptr, step, ids_out_dev, probs_out_dev, stream);
+}
+
+int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows,
+                               const uint32_t* presence_dev, const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev,
+                               float* probs_out_dev, void* stream) {
     MGEA_REQUIRE(logits_dev && rows && B > 0, MGEA_EINVAL, "op_sample_rows: NULL argument or empty batch");
     MGEA_TRY(check_row_samplers(rows, B, V, -1, "op_sample_rows"));
+    if (lrows) MGEA_TRY(check_row_logits(lrows, B, -1, "op_sample_rows"));
     std::vector<SamplerParams> rec((size_t)B);
-    bool pen = false;
+    bool pen = false, biased = false;
     for (int b = 0; b < B; ++b) {
         rec[(size_t)b] = sampler_params(rows[b]);
         pen = pen || rows[b].repetition_penalty != 1.0f;
+        if (lrows) {
+            rec[(size_t)b].bias_on = lrows[b].bias_dev ? 1 : 0;
+            rec[(size_t)b].min_new = lrows[b].min_new_tokens;
+            biased = biased || lrows[b].bias_dev || lrows[b].min_new_tokens > 0;
+        }
     }
     MGEA_REQUIRE(!pen || presence_dev, MGEA_EINVAL, "op_sample_rows: a row is penalized but presence_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     SamplerParams* rec_dev = nullptr;
     MGEA_CHECK_HIP(hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)));
+    float* bias_dev = nullptr;   // the rows' vectors, row b at b * V (rows without one are never read)
+    if (biased && hipMalloc((void**)&bias_dev, (size_t)B * V * sizeof(float)) != hipSuccess) {
+        (void)hipFree(rec_dev);
+        set_error("op_sample_rows: allocation of the bias rows failed");
+        return MGEA_ENOMEM;
+    }
     const mgea_sampler_config unused{1.0f, 0, 0.0f, -1, 0};   // every scalar comes from rec_dev
     int rc = MGEA_EHIP;
-    if (hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st) == hipSuccess)
+    bool copied = hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st) == hipSuccess;
+    for (int b = 0; biased && copied && b < B; ++b)
+        if (lrows[b].bias_dev)
+            copied = hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st) ==
+                     hipSuccess;
+    if (copied)
         rc = launch_sample(logits_dev, B, V, unused, rec_dev, nullptr, step, ids_out_dev, probs_out_dev, st, nullptr,
-                           pen ? const_cast<uint32_t*>(presence_dev) : nullptr);
+                           pen ? const_cast<uint32_t*>(presence_dev) : nullptr, 1.0f, bias_dev);
     else
         set_error("op_sample_rows: copy of the records failed");
-    const hipError_t e = hipStreamSynchronize(st);   // rec and rec_dev are freed below
+    const hipError_t e = hipStreamSynchronize(st);   // rec, rec_dev and bias_dev are freed below
     (void)hipFree(rec_dev);
+    if (bias_dev) (void)hipFree(bias_dev);
     MGEA_TRY(rc);
     MGEA_CHECK_HIP(e);
     return MGEA_OK;

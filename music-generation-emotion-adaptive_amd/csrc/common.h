@@ -190,24 +190,28 @@ int launch_attn_dense(const float* qkv, const int32_t* lens, const int32_t* mask
 // stream: word 0 of the row's Philox counter (the key is the seed); generate() writes stream = b.
 // max_new: the row's step budget -- it finishes after producing that many tokens (end_row_step); INT32_MAX = none.
 // ctx_cap: the tokens the row's KV pages hold when that is less than the longest prompt + the steps (launch_clamp_budgets); INT32_MAX = none.
+// bias_on: the row adds its row of the bias buffer to its logits; min_new: no eos_id before the row has produced that many ids (both
+// read only by the BIAS sampler; 0 otherwise).
 struct SamplerParams {
     float temperature; int32_t top_k; float top_p; int32_t eos_id;
     uint32_t seed_lo, seed_hi; float penalty; uint32_t stream;
-    int32_t max_new; int32_t ctx_cap; int32_t pad[2];
+    int32_t max_new; int32_t ctx_cap; int32_t bias_on; int32_t min_new;
 };
 constexpr int32_t MGEA_NO_BUDGET = 0x7fffffff;
 static inline SamplerParams sampler_params(const mgea_sampler_config& s, float penalty = 1.0f) {
     return SamplerParams{s.temperature, s.top_k, s.top_p, s.eos_id, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), penalty, 0u,
-                         MGEA_NO_BUDGET, MGEA_NO_BUDGET, {0, 0}};
+                         MGEA_NO_BUDGET, MGEA_NO_BUDGET, 0, 0};
 }
 // a per-row record of the C ABI -> the device record (max_new_tokens 0 = no budget: the call's n_steps bound the row anyway)
 static inline SamplerParams sampler_params(const mgea_row_sampler& r) {
     return SamplerParams{r.temperature, r.top_k, r.top_p, r.eos_id, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.repetition_penalty,
-                         r.stream, r.max_new_tokens > 0 ? r.max_new_tokens : MGEA_NO_BUDGET, MGEA_NO_BUDGET, {0, 0}};
+                         r.stream, r.max_new_tokens > 0 ? r.max_new_tokens : MGEA_NO_BUDGET, MGEA_NO_BUDGET, 0, 0};
 }
 // host check of rows[0, B) (mgea_decoder_generate_rows, mgea_op_sample_rows): MGEA_EINVAL naming the first bad row; n_steps < 0 skips the
 // budget check
 int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who);
+// host check of the rows' mgea_row_logits records: reserved == 0, 0 <= min_new_tokens <= n_steps (n_steps < 0: no upper bound)
+int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who);
 constexpr int MGEA_SAMPLER_MAX_VOCAB = 14336;   // the sampler keeps a row in registers: 256 threads x 56 logits
 // Repetition penalty (mgea_decoder_generate_penalized): per row a presence bitmap of ceil(V / 32) words, bit id & 31 of word id >> 5
 // set once the id is in the row's prompt or was generated by it.  Rows follow each other at that stride.
@@ -244,9 +248,11 @@ struct TailArgs {
 // presence != NULL: the PENALTY form -- the logits of the ids whose bit is set in the row's presence bitmap (presence_words(V) words
 // per row) are penalized first, x < 0 ? x * p : x / p, p = penalty (or params_dev->penalty); with a tail the row's new token is then
 // added to that bitmap.  top_k == 1 there is the exact argmax of the penalized row (no temperature division, ties to the lowest id).
+// bias != NULL (needs params_dev): the BIAS form -- after the penalty, row b adds bias[b * V + i] to logit i if its record has bias_on,
+// and bans its eos_id while its step index is below the record's min_new.
 int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
                   const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st,
-                  const TailArgs* tail = nullptr, uint32_t* presence = nullptr, float penalty = 1.0f);
+                  const TailArgs* tail = nullptr, uint32_t* presence = nullptr, float penalty = 1.0f, const float* bias = nullptr);
 // params_dev[0, B) <- s (stream = b, no budget), stream-ordered: the uniform form of the records
 int launch_fill_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, int B, hipStream_t st, float penalty = 1.0f);
 // params_dev[b].max_new <- min(max_new, reserved - len_b), len_b = lens[b] (NULL: T) clamped to [1, T], and ctx_cap <- reserved: a row

@@ -103,11 +103,11 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, greedy | sampled, penalized or not, steps).  Everything a step reads besides its
+    // Captured decode-step graphs, one per (batch, greedy | sampled, plain | penalized | biased, steps).  Everything a step reads besides its
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
-    struct GraphEntry { int batch; bool greedy; bool penalized; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
+    struct GraphEntry { int batch; bool greedy; bool penalized; bool biased; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
     std::vector<GraphEntry> graphs;
     uint64_t use_clock = 0;
     SamplerParams* samp_dev = nullptr;     // [max_batch] records, one per row (common.h)
@@ -116,7 +116,10 @@ struct mgea_decoder {
     // repetition penalty: per row the set of ids it has seen (prompt + generated), [max_batch][presence_words(vocab)] (common.h);
     // seeded by a penalized generate() after its prefill, then updated by the kernel that commits each row's token
     uint32_t* presence = nullptr;
-    bool last_penalized = false;   // the last generate() applied a penalty: presence holds its rows
+    bool last_penalized = false;   // the last generate() applied a penalty (or a bias): presence holds its rows
+    // logit bias: [max_batch][vocab] fp32, row b = the vector row b adds to its logits when its record has bias_on.  A biased generate()
+    // copies the rows' vectors here in stream order, so the captured graphs hold this pointer whatever the request's values.
+    float* bias = nullptr;
     int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped)
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     int64_t counters[8] = {0};
@@ -465,11 +468,12 @@ StepState step_state(mgea_decoder* h, const Bufs& u, int eos, const SamplerParam
 // too: the head writes the logits row and the PENALTY sampler keeps top_k = 1 entry of the penalized row (the head's per-tile argmax
 // partials know nothing of the penalty).
 int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler_config& sc, const SamplerParams* pd,
-                       float* logits_out, hipStream_t st, bool primed, bool pen = false) {
+                       float* logits_out, hipStream_t st, bool primed, bool pen = false, bool biased = false) {
     const auto& c = h->cfg;
     const int C = c.d_model, V = c.vocab;
     const bool greedy = sc.top_k == 1 && !pen;
     uint32_t* pres = pen ? h->presence : nullptr;
+    const float* bias = biased ? h->bias : nullptr;   // the biased form (always with pen): the BIAS sampler
     // [embed,] 6 x (qkv, attention, out-proj, fc1, fc2), head (+ per-tile argmax), finalize [+ next embed]
     const int abs_pos = c.pos_mode == MGEA_POS_ABSOLUTE;
     if (!primed)
@@ -492,9 +496,9 @@ int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler
     } else {
         if (primed) {   // sampler + loop bookkeeping + next step's embedding in one launch
             TailArgs t{step_state(h, u, sc.eos_id, pd), h->w(T_TOK), h->w(T_POS), u.x, u.stats, C, V, c.seq_len, abs_pos};
-            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, &t, pres));
+            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, &t, pres, 1.0f, bias));
         } else {
-            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, nullptr, pres));
+            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, nullptr, pres, 1.0f, bias));
             PROF(PC_ROWOP, launch_advance(u.sampled, step_state(h, u, sc.eos_id, pd), B, st, pres, V));
         }
     }
@@ -503,13 +507,13 @@ int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler
 
 // one decode step on cur_ids (T = 1) for the whole batch; logits_out optional
 int enqueue_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, const SamplerParams* pd, float* logits_out,
-                 hipStream_t st, bool primed = false, bool pen = false) {
+                 hipStream_t st, bool primed = false, bool pen = false, bool biased = false) {
     const auto& c = h->cfg;
     const int C = c.d_model, V = c.vocab;
     const bool post = c.block_mode == MGEA_BLOCK_POSTLN_RELU;
     const bool greedy = sc.top_k == 1 && !pen;   // (enqueue_step_fused: penalized greedy steps sample with top_k = 1)
     uint32_t* pres = pen ? h->presence : nullptr;
-    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), B, sc, pd, logits_out, st, primed, pen);
+    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), B, sc, pd, logits_out, st, primed, pen, biased);
     const Bufs u = main_bufs(h);
     PROF(PC_ROWOP, launch_embed_ln(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                              post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, 1, C,
@@ -520,15 +524,17 @@ int enqueue_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, const Sa
     float* lg = logits_out ? logits_out : (greedy ? nullptr : h->logits);
     PROF(PC_SAMPLE, launch_logits_argmax(h->slabs, S, slab_floats(B, V), (int)slab_ld(V), h->head_b(), lg, B, V,
                                   greedy ? h->sampled : nullptr, st));
-    if (!greedy) PROF(PC_SAMPLE, launch_sample(lg, B, V, sc, pd, h->row_step, 0, h->sampled, nullptr, st, nullptr, pres));
+    if (!greedy)
+        PROF(PC_SAMPLE, launch_sample(lg, B, V, sc, pd, h->row_step, 0, h->sampled, nullptr, st, nullptr, pres, 1.0f,
+                                      biased ? h->bias : nullptr));
     PROF(PC_ROWOP, launch_advance(h->sampled, step_state(h, u, sc.eos_id, pd), B, st, pres, V));
     return MGEA_OK;
 }
 
 // The decode step of generate(): x arrives primed on the fused path.
-int enqueue_gen_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, bool pen) {
-    if (!fused_ok(h, B)) return enqueue_step(h, B, sc, h->samp_dev, nullptr, st, false, pen);
-    return enqueue_step_fused(h, main_bufs(h), B, sc, h->samp_dev, nullptr, st, true, pen);
+int enqueue_gen_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, bool pen, bool biased) {
+    if (!fused_ok(h, B)) return enqueue_step(h, B, sc, h->samp_dev, nullptr, st, false, pen, biased);
+    return enqueue_step_fused(h, main_bufs(h), B, sc, h->samp_dev, nullptr, st, true, pen, biased);
 }
 
 // embedding (+ LN statistics) of cur_ids into the buffers the next generate() step will read
@@ -542,13 +548,14 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
 
 // The captured decode step for (B, greedy, pen): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond MAX_GRAPHS).
-constexpr size_t MAX_GRAPHS = 16;   // two per (batch, greedy | sampled, penalized or not): the single step and the 8-step graph
+constexpr size_t MAX_GRAPHS = 16;   // two per (batch, greedy | sampled, plain | penalized | biased): the single step and the 8-step graph
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, hipGraphExec_t* out, int steps, bool pen) {
+int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, hipGraphExec_t* out, int steps, bool pen,
+               bool biased) {
     const bool greedy = sc.top_k == 1;
     for (auto& g : h->graphs)
-        if (g.batch == B && g.greedy == greedy && g.penalized == pen && g.steps == steps) {
+        if (g.batch == B && g.greedy == greedy && g.penalized == pen && g.biased == biased && g.steps == steps) {
             g.last_use = ++h->use_clock;
             if (steps == 1) h->counters[0] = g.nodes;
             *out = g.exec;
@@ -565,7 +572,7 @@ int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_
     }
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, sc, st, pen);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, sc, st, pen, biased);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -581,7 +588,7 @@ int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_
     }
     size_t nn = 0;
     (void)hipGraphGetNodes(g, nullptr, &nn);
-    h->graphs.push_back({B, greedy, pen, steps, g, ex, (int64_t)nn, ++h->use_clock});
+    h->graphs.push_back({B, greedy, pen, biased, steps, g, ex, (int64_t)nn, ++h->use_clock});
     if (steps == 1) h->counters[0] = (int64_t)nn;
     h->counters[2] += 1;   // lifetime captures + instantiations
     h->counters[4] = (int64_t)h->graphs.size();
@@ -959,6 +966,9 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     if (hipMalloc((void**)&h->attn_split.part, (size_t)MGEA_ATTN_SPLIT_ITEMS * MGEA_ATTN_MAX_SPLIT * attn_part_floats(h->dh) * sizeof(float)) != hipSuccess ||
         hipMalloc((void**)&h->attn_split.count, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess)
         return fail(MGEA_ENOMEM, "state allocation failed");
+    // (last of the state buffers: the ones above keep the places they had before this buffer existed)
+    if (hipMalloc((void**)&h->bias, (size_t)cfg->max_batch * cfg->vocab * sizeof(float)) != hipSuccess)
+        return fail(MGEA_ENOMEM, "state allocation failed");
     (void)hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t));
     (void)hipMemset(h->page_table, 0, nb * h->max_pages);
     (void)hipMemset(h->ctx_len, 0, nb);
@@ -999,7 +1009,7 @@ int mgea_decoder_destroy(mgea_decoder* h) {
     free_ws(h);
     free_p16(h);
     void* p[] = {h->kv.base, h->page_table, h->ctx_len, h->cur_ids, h->done, h->row_step, h->n_done, h->sampled, h->ids_hist, h->wt, h->lnv,
-                 h->samp_dev, h->err_flag, h->presence, h->arena_own, h->attn_split.part, h->attn_split.count};
+                 h->samp_dev, h->err_flag, h->presence, h->bias, h->arena_own, h->attn_split.part, h->attn_split.count};
     for (void* q : p)
         if (q) (void)hipFree(q);
     if (h->samp_stage) (void)hipHostFree(h->samp_stage);
@@ -1045,20 +1055,24 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
 namespace {
 // mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
 // (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
-// are then ignored.
+// are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  The generation
+// is "processed" if any row has a penalty != 1, a bias or min_new_tokens > 0: the logits-row + PENALTY sampler sequence; with a bias
+// or min_new_tokens anywhere it is the biased form of that sequence (BIAS sampler, its own graphs), presence bitmaps included.
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
-                const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, int32_t* ids_out_dev, hipStream_t st) {
+                const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
+                int32_t* ids_out_dev, hipStream_t st) {
     const auto& c = h->cfg;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
     // the step graphs' form: greedy only if every row is, penalized if any row is (p = 1 rows are unchanged by it: x * 1, x / 1 exact);
     // the host poll for early stops when some row can finish before n_steps
     mgea_sampler_config form{1.0f, 0, 0.0f, -1, 0};
-    bool pen = false, poll = false;
+    bool pen = false, poll = false, biased = false, any_penalty = false;
     int reserve = Tp + n_steps;
     if (rows) {
         MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
         MGEA_TRY(check_row_samplers(rows, B, c.vocab, n_steps, "decoder_generate_rows"));
+        if (lrows) MGEA_TRY(check_row_logits(lrows, B, n_steps, "decoder_generate_rows"));
         // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
         MGEA_REQUIRE(Tp < c.max_ctx && n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp, n_steps,
                      c.max_ctx);
@@ -1068,19 +1082,23 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             const bool p1 = rows[b].repetition_penalty == 1.0f;
             all_greedy = all_greedy && rows[b].top_k == 1 && p1;
             pen = pen || !p1;
+            biased = biased || (lrows && (lrows[b].bias_dev || lrows[b].min_new_tokens > 0));
             poll = poll || rows[b].eos_id >= 0 || (rows[b].max_new_tokens > 0 && rows[b].max_new_tokens < n_steps);
         }
         poll = poll || reserve < Tp + n_steps;
         form.top_k = all_greedy ? 1 : 0;
+        any_penalty = pen;
+        pen = pen || biased;   // the biased form keeps the bitmaps: a penalty of 1 leaves a row as it is
     } else {
         MGEA_REQUIRE(Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
         MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
         form = *s;
-        pen = penalty != 1.0f;
+        pen = any_penalty = penalty != 1.0f;
         poll = s->eos_id >= 0;
     }
     h->last_penalized = false;
     h->counters[6] = 0;
+    h->counters[7] = 0;
     MGEA_TRY(do_reset(h, B, reserve, st));
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
     if (pen) {   // every row's set starts as its real prompt tokens
@@ -1093,7 +1111,15 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     // all per-step state lives in device memory, so one graph serves every step of every request
     if (rows) {
         MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free));   // the previous call's copy out of the staging buffer has run
-        for (int b = 0; b < B; ++b) h->samp_stage[b] = sampler_params(rows[b]);
+        for (int b = 0; b < B; ++b) {
+            h->samp_stage[b] = sampler_params(rows[b]);
+            if (!biased) continue;
+            h->samp_stage[b].bias_on = lrows[b].bias_dev ? 1 : 0;
+            h->samp_stage[b].min_new = lrows[b].min_new_tokens;
+            if (lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
+                MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)b * c.vocab, lrows[b].bias_dev, (size_t)c.vocab * sizeof(float),
+                                              hipMemcpyDeviceToDevice, st));
+        }
         MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free, st));
         if (reserve < Tp + n_steps) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
@@ -1101,11 +1127,11 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         MGEA_TRY(launch_fill_sampler_params(h->samp_dev, *s, B, st, penalty));
     }
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, st, &gexec, 1, pen));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, st, &gexec, 1, pen, biased));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, st, &gexec_k, K, pen));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, st, &gexec_k, K, pen, biased));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1113,12 +1139,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, st, pen);
+            const int rc = enqueue_gen_step(h, B, form, st, pen, biased);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, st, pen));
+            MGEA_TRY(enqueue_gen_step(h, B, form, st, pen, biased));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1136,7 +1162,8 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     if (reserve < Tp + n_steps) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
     h->host_max_len += launched;
     h->counters[1] = launched;
-    h->counters[6] = pen ? launched : 0;
+    h->counters[6] = any_penalty ? launched : 0;
+    h->counters[7] = biased ? launched : 0;
     // rows: ids_hist[b, 0:launched]; steps never run are -1
     MGEA_CHECK_HIP(hipMemsetAsync(ids_out_dev, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));
     MGEA_CHECK_HIP(hipMemcpy2DAsync(ids_out_dev, (size_t)n_steps * sizeof(int32_t), h->ids_hist,
@@ -1153,7 +1180,7 @@ int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const 
                           void* stream) {
     MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, nullptr, ids_out_dev, (hipStream_t)stream);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, nullptr, nullptr, ids_out_dev, (hipStream_t)stream);
 }
 
 int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
@@ -1163,14 +1190,29 @@ int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_d
     MGEA_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, MGEA_EINVAL,
                  "decoder_generate: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
     std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, nullptr, ids_out_dev, (hipStream_t)stream);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, nullptr, nullptr, ids_out_dev,
+                       (hipStream_t)stream);
 }
 
 int mgea_decoder_generate_rows(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
                                int32_t n_steps, const mgea_row_sampler* rows, int32_t* ids_out_dev, void* stream) {
     MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, ids_out_dev, (hipStream_t)stream);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, nullptr, ids_out_dev, (hipStream_t)stream);
+}
+
+int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                      int32_t* ids_out_dev, void* stream) {
+    MGEA_REQUIRE(rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
+    // what the records alone decide is checked before anything else is looked at (do_generate checks it again with the sampler records)
+    if (logits_rows) {
+        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows: empty batch");
+        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows"));
+    }
+    MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream);
 }
 
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream) {

@@ -31,6 +31,11 @@
 // its seed (the reference's endpoint draws a fresh one per call, api_cache.py:204), and rows with different settings share one launch
 // (workgroup b reads record b, so every setting stays block-uniform).  With records, a top_k == 1 row is the exact argmax of its
 // (penalized) row as in the PENALTY form: no temperature division.
+// Logit bias (BIAS instantiations; HF sequence_bias / suppress_tokens, OpenAI logit_bias -- build-defined, the reference has none): after
+// the penalty and before everything else, a row whose record says so adds its fp32 bias row, x[i] += bias[i] (-inf = the id is banned),
+// and a row that has produced fewer than its record's min_new ids has x[eos_id] = -inf.  A banned entry is an ordinary logit from there
+// on: its key is the smallest a real entry can have, exp(-inf - max) is exactly 0, so it carries no mass, is never drawn, and may sit
+// among the top_k kept when fewer than top_k ids are admissible.  A row without a bias is not touched (no + 0).
 #include <cmath>
 
 #include "common.h"
@@ -300,12 +305,14 @@ __device__ __forceinline__ float funkey(uint32_t k) {   // inverse of fkey
 // One SAMP_NT-thread workgroup per row; thread t owns the logits t, t + SAMP_NT, ... in registers (MAXE of them), so the row is
 // read from memory once, in one batch of loads, and never goes through LDS.
 // PENALTY: presence = the rows' bitmaps (presence_words(V) words per row), updated by the fused tail; unused otherwise.
-template <int MAXE, bool PENALTY>
+// BIAS: bias = the rows' bias vectors (V floats per row, row b at b * V), read by the rows whose record has bias_on; unused otherwise.
+template <int MAXE, bool PENALTY, bool BIAS>
 __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict__ logits, int V, SamplerParams pv,
                                                     const SamplerParams* __restrict__ pd,
                                                     const int32_t* __restrict__ row_step, int64_t step_host,
                                                     int32_t* __restrict__ ids_out, float* __restrict__ probs_out,
-                                                    TailArgs tail, int fuse_tail, int wave_select, uint32_t* __restrict__ presence) {
+                                                    TailArgs tail, int fuse_tail, int wave_select, uint32_t* __restrict__ presence,
+                                                    const float* __restrict__ bias) {
     constexpr int NT = SAMP_NT, NW = SAMP_NW;
     static_assert(SAMP_KFAST == 64, "wave_publish_ge fills one slot per lane");
     __shared__ unsigned long long red64[2 * NW];
@@ -336,6 +343,22 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         const int i = tid + NT * j;
         x[j] = i < V ? lg[i] : -INFINITY;
     }
+    // BIAS: the row's bias travels in the same batch of loads (nothing above waits for the logits yet); block-uniform
+    [[maybe_unused]] float bz[BIAS ? MAXE : 1];
+    [[maybe_unused]] const bool biased = BIAS && pv.bias_on != 0;
+    if constexpr (BIAS) {
+        // (the condition stays outside the unrolled loads: selected per element, every load gets a branch and a wait of its own)
+        const float* br = bias + (int64_t)b * V;
+#pragma unroll
+        for (int j = 0; j < MAXE; ++j) bz[j] = 0.f;
+        if (biased) {
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) {
+                const int i = tid + NT * j;
+                bz[j] = i < V ? br[i] : 0.f;
+            }
+        }
+    }
     if constexpr (PENALTY) {
         __shared__ uint32_t s_pres[MAXE * NT / 32];
         const int nw = presence_words(V);   // <= MAXE * NT / 32
@@ -348,8 +371,21 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
             if (i < V && ((s_pres[i >> 5] >> (i & 31)) & 1u)) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
         }
     }
+    if constexpr (BIAS) {
+        if (biased) {
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) x[j] += bz[j];
+        }
+        // min_new: no EOS before the row has produced that many ids (its step index, the Philox counter's word 1)
+        const int eos = pv.eos_id;
+        if (eos >= 0 && eos < V && pv.min_new > 0 && (row_step ? row_step[b] : (int32_t)step_host) < pv.min_new) {
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j)
+                if (tid + NT * j == eos) x[j] = -INFINITY;
+        }
+    }
     float mx = -INFINITY;
-    if (temperature != 1.0f && !((PENALTY || pd) && top_k == 1)) {   // logits / temperature (api_cache.py:170); x / 1 is x
+    if (temperature != 1.0f && !((PENALTY || BIAS || pd) && top_k == 1)) {   // logits / temperature (api_cache.py:170); x / 1 is x
 #pragma unroll
         for (int j = 0; j < MAXE; ++j) x[j] = x[j] / temperature;
     }
@@ -572,7 +608,7 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
 
 int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
                   const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st, const TailArgs* tail,
-                  uint32_t* presence, float penalty) {
+                  uint32_t* presence, float penalty, const float* bias) {
     MGEA_REQUIRE(params_dev || s.temperature > 0.f, MGEA_EINVAL, "sampler: temperature must be > 0");
     MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "sampler: vocab %d exceeds the register-resident row (%d)", V,
                  MGEA_SAMPLER_MAX_VOCAB);
@@ -583,10 +619,13 @@ int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& 
     const SamplerParams pv = sampler_params(s, penalty);
     static_assert(SAMP_NT * 56 >= MGEA_SAMPLER_MAX_VOCAB, "the register-resident row must hold the largest vocabulary");
     const bool narrow = V <= SAMP_NT * 36;
-    auto kern = presence ? (narrow ? sample_kernel<36, true> : sample_kernel<56, true>)
-                         : (narrow ? sample_kernel<36, false> : sample_kernel<56, false>);
+    MGEA_REQUIRE(!bias || params_dev, MGEA_EINVAL, "sampler: a bias needs the rows' device records");
+    auto kern = bias ? (presence ? (narrow ? sample_kernel<36, true, true> : sample_kernel<56, true, true>)
+                                 : (narrow ? sample_kernel<36, false, true> : sample_kernel<56, false, true>))
+                     : (presence ? (narrow ? sample_kernel<36, true, false> : sample_kernel<56, true, false>)
+                                 : (narrow ? sample_kernel<36, false, false> : sample_kernel<56, false, false>));
     hipLaunchKernelGGL(kern, dim3(B), dim3(SAMP_NT), 0, st, logits, V, pv, params_dev, row_step_dev, step_host, ids_out, probs_out, t,
-                       tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), presence);
+                       tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), presence, bias);
     MGEA_CHECK_HIP(hipGetLastError());
     return MGEA_OK;
 }
@@ -633,6 +672,16 @@ __global__ void unpark_rows_kernel(int32_t* __restrict__ done, int32_t* __restri
 int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st) {
     hipLaunchKernelGGL(unpark_rows_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, done, ctx_len, B);
     MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who) {
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_logits& l = lrows[b];
+        MGEA_REQUIRE(l.reserved == 0, MGEA_EINVAL, "%s: row %d: mgea_row_logits.reserved must be 0", who, b);
+        MGEA_REQUIRE(l.min_new_tokens >= 0 && (n_steps < 0 || l.min_new_tokens <= n_steps), MGEA_EINVAL,
+                     "%s: row %d: min_new_tokens %d outside [0, %d]", who, b, l.min_new_tokens, n_steps < 0 ? 0x7fffffff : n_steps);
+    }
     return MGEA_OK;
 }
 

@@ -28,7 +28,8 @@ from mgea.decoder import DecoderEngine, RowSampling, geometry_from_state_dict, r
 
 __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab", "encode", "decode",
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
-           "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok"]
+           "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
+           "generate_batch_biased", "generate_sequence_biased"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
 tok2id: Dict[str, int] = {}
@@ -191,6 +192,13 @@ def _as_model(model_or_weights, n_head=8, device=_DEFAULT_DEVICE) -> GPTWithKV:
     raise TypeError("expected a GPTWithKV or a state dict / checkpoint dict")
 
 
+def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, **kw):
+    """eng.generate(), or eng.generate_biased() when a bias or a minimum length is set (capped at the steps there are)"""
+    if logit_bias is None and not min_new_tokens:
+        return eng.generate(ids, n_steps, **kw)
+    return eng.generate_biased(ids, n_steps, logit_bias=logit_bias, min_new_tokens=min(int(min_new_tokens), n_steps), **kw)
+
+
 def _draw_seed() -> int:
     # torch.manual_seed(s) therefore makes a sampled generation reproducible, like the reference
     return int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -205,7 +213,19 @@ def sample_kvcache(model, prompt: Sequence[str], max_len=512, temperature=1.0, t
     steps).  `device` is accepted for compatibility; the work happens on the model's MI355X.
     top_k=1 is exactly greedy; other settings match torch.multinomial in distribution only.
     repetition_penalty (None = none) penalizes the ids of the prompt and of everything generated so far like
-    transformers' RepetitionPenaltyLogitsProcessor; the paper's setting is top_k=0, top_p=0.92, repetition_penalty=1.1."""
+    transformers' RepetitionPenaltyLogitsProcessor; the paper's setting is top_k=0, top_p=0.92, repetition_penalty=1.1.
+    (sample_kvcache_biased: the same with a logit bias and a minimum length.)"""
+    return sample_kvcache_biased(model, prompt, max_len, temperature, top_k, device, top_p, seed, repetition_penalty)
+
+
+def sample_kvcache_biased(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
+                          top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                          logit_bias=None, min_new_tokens: int = 0) -> List[str]:
+    """sample_kvcache with a constraint on what may be drawn (sample_kvcache keeps the reference's parameter list).
+    logit_bias (None, a dict id -> bias, a host array or a device tensor [vocab]; -inf bans an id -- generate_music.constraints
+    builds the note / scale ones) is added to the penalized logits at every step; min_new_tokens > 0 keeps [END_SEQUENCE] from
+    being drawn before that many new tokens (capped at the steps there are).  Both are build-defined (include/mgea.h); with
+    neither this is sample_kvcache, the same engine call."""
     m = _as_model(model)
     eng = m._need()
     ids = [tok2id[t] for t in prompt]          # KeyError for an unknown token, like api_cache.py:162
@@ -215,8 +235,8 @@ def sample_kvcache(model, prompt: Sequence[str], max_len=512, temperature=1.0, t
     if len(ids) + n_steps > eng.max_ctx:
         raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
-    out = eng.generate([ids], n_steps, temperature=temperature, top_k=top_k, top_p=top_p, eos_id=eos,
-                       seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty)
+    out = _engine_generate(eng, [ids], n_steps, logit_bias, min_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
+                           eos_id=eos, seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty)
     gen = [int(i) for i in out[0].cpu().tolist() if i >= 0]
     return [id2tok[i] for i in ids + gen]
 
@@ -229,18 +249,34 @@ def generate_sequence(model_or_weights, prompt: Sequence[str], max_len=512, temp
                           device, top_p, seed, repetition_penalty=repetition_penalty)
 
 
+def generate_sequence_biased(model_or_weights, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50,
+                             device=_DEFAULT_DEVICE, top_p: Optional[float] = None, seed: Optional[int] = None, n_head: int = 8,
+                             repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0) -> List[str]:
+    """generate_sequence with a logit bias and a minimum length: sample_kvcache_biased on a model object or a weights dict."""
+    return sample_kvcache_biased(_as_model(model_or_weights, n_head, device), prompt, max_len, temperature, top_k, device, top_p,
+                                 seed, repetition_penalty, logit_bias, min_new_tokens)
+
+
 def generate_batch(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
                    top_p: Optional[float] = None, seed: Optional[int] = None,
                    repetition_penalty: Optional[float] = None) -> List[List[str]]:
     """New surface: many prompts in one batch (ragged lengths allowed); every row equals the
     reference run on that prompt alone (greedy) -- rows are independent."""
+    return generate_batch_biased(model, prompts, max_len, temperature, top_k, top_p, seed, repetition_penalty)
+
+
+def generate_batch_biased(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
+                          top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                          logit_bias=None, min_new_tokens: int = 0) -> List[List[str]]:
+    """generate_batch with a logit bias (one vector for every row, or [B, vocab]) and min_new_tokens, as in sample_kvcache_biased."""
     m = _as_model(model)
     eng = m._need()
     ids = [[tok2id[t] for t in p] for p in prompts]
     n_steps = int(max_len) - max(len(p) for p in ids)
     eos = tok2id.get("[END_SEQUENCE]", -1)
-    out = eng.generate(ids, max(n_steps, 0), temperature=temperature, top_k=top_k, top_p=top_p, eos_id=eos,
-                       seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty).cpu().tolist()
+    out = _engine_generate(eng, ids, max(n_steps, 0), logit_bias, min_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
+                           eos_id=eos, seed=_draw_seed() if seed is None else seed,
+                           repetition_penalty=repetition_penalty).cpu().tolist()
     return [[id2tok[i] for i in p + [g for g in row if g >= 0]] for p, row in zip(ids, out)]
 
 
@@ -254,14 +290,17 @@ def _per_prompt(value, n: int, name: str) -> list:
 
 
 def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
-                      top_p: Optional[float] = None, seed=None, repetition_penalty=None) -> List[List[str]]:
+                      top_p: Optional[float] = None, seed=None, repetition_penalty=None, logit_bias=None,
+                      min_new_tokens=0) -> List[List[str]]:
     """Independent sample_kvcache requests served by one batched generation (up to the engine's max_batch rows per
     generation; more prompts take several).  Every argument may be a scalar or a list with one value per prompt.  Prompt i
     gets max_len_i - len(prompt_i) new tokens and stops after [END_SEQUENCE], like sample_kvcache; a seed of None is drawn
     with torch's generator (torch.manual_seed makes it reproducible).  Each row draws from Philox stream 0 under its own
     seed, the stream sample_kvcache uses for that seed.  Returns the prompt + generated tokens of each request, in order.
     Greedy rows (top_k=1) equal the reference run of their prompt alone; sampled rows depend on their own settings and on
-    the batch size (kernel choice), not on the other requests."""
+    the batch size (kernel choice), not on the other requests.  logit_bias (one vector -- a dict, a host array or a device
+    tensor [vocab] -- for every prompt, or a list with one per prompt, None = none) and min_new_tokens (capped at the prompt's
+    budget) travel in the rows' records."""
     m = _as_model(model)
     eng = m._need()
     n = len(prompts)
@@ -271,6 +310,8 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     ps = _per_prompt(top_p, n, "top_p")
     seeds = _per_prompt(seed, n, "seed")
     pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
+    biases = _per_prompt(logit_bias, n, "logit_bias")
+    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
     ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
     budgets = [L - len(p) for L, p in zip(max_lens, ids)]
     for L, p in zip(max_lens, ids):
@@ -278,8 +319,12 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
             raise RuntimeError(f"max_len={L} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
     live = [i for i in range(n) if budgets[i] > 0]
+    for i in range(n):
+        if mins[i] < 0:
+            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
     rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
-                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0)
+                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]))
             for i in live}
     gen: Dict[int, List[int]] = {}
     for c0 in range(0, len(live), eng.max_batch):

@@ -41,6 +41,11 @@ class RowSampler(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class RowLogits(C.Structure):
+    """mgea_row_logits: one batch row's logit bias and minimum length (mgea_decoder_generate_rows_biased, mgea_op_sample_rows_biased)."""
+    _fields_ = [("bias_dev", C.c_void_p), ("min_new_tokens", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -67,6 +72,7 @@ PROTOTYPES = {
     "mgea_decoder_generate": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(SamplerConfig), _P, _P]),
     "mgea_decoder_generate_penalized": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _P]),
     "mgea_decoder_generate_rows": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), _P, _P]),
+    "mgea_decoder_generate_rows_biased": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P, _P]),
     "mgea_decoder_presence": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_context_lengths": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_stats": (C.c_int, [_P, C.POINTER(_I64)]),
@@ -101,6 +107,7 @@ PROTOTYPES = {
     "mgea_op_sample": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _I64, _P, _P, _P]),
     "mgea_op_sample_penalized": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _I64, _P, _P, _P]),
     "mgea_op_sample_rows": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, _I64, _P, _P, _P]),
+    "mgea_op_sample_rows_biased": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P]),
 }
 
 _lib = None

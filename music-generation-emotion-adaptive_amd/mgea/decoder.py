@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DecoderConfig, RowSampler, SamplerConfig, check, ptr
+from ._lib import DecoderConfig, RowLogits, RowSampler, SamplerConfig, check, ptr
 
 _LAYER_TENSORS = ["ln1.weight", "ln1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
                   "attn.out_proj.bias", "ln2.weight", "ln2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
@@ -75,12 +75,63 @@ F16_ROUNDED_KEYS = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "li
                     "attn.in_proj_weight", "attn.out_proj.weight", "mlp.0.weight", "mlp.2.weight", "head.weight")
 
 
+def dense_logit_bias(bias, vocab: int):
+    """A logit bias as a dense float32 [vocab] vector: a dict id -> bias is packed on the host (ids not named get 0), a host array
+    or tensor is converted, a DEVICE tensor is returned as it is (float32, contiguous).  -inf bans an id.  None stays None."""
+    if bias is None:
+        return None
+    if isinstance(bias, dict):
+        out = np.zeros(vocab, np.float32)
+        for k, v in bias.items():
+            if not 0 <= int(k) < vocab:
+                raise ValueError(f"logit_bias id {k} outside [0, {vocab})")
+            out[int(k)] = v
+        return out
+    if isinstance(bias, torch.Tensor) and bias.is_cuda:
+        if bias.dim() != 1 or bias.numel() != vocab:
+            raise ValueError(f"logit_bias must be [{vocab}], got {list(bias.shape)}")
+        return bias.detach().to(torch.float32).contiguous()
+    arr = bias.detach().numpy() if isinstance(bias, torch.Tensor) else np.asarray(bias)
+    if arr.shape != (vocab,):
+        raise ValueError(f"logit_bias must be [{vocab}], got {list(arr.shape)}")
+    return np.ascontiguousarray(arr, dtype=np.float32)
+
+
+def check_logit_bias(vec, row: int, eos_id: int = -1, min_new_tokens: int = 0, check: bool = True) -> None:
+    """The validity rules of include/mgea.h (mgea_row_logits) as ValueErrors naming the row: no NaN, no +inf, at least one finite
+    entry, and one besides eos_id when min_new_tokens > 0 bans the EOS.  vec: dense_logit_bias()'s result.  A host vector is always
+    checked; a device tensor is read back through ONE reduction, which check=False skips (the caller then guarantees the rules)."""
+    if vec is None:
+        return
+    if isinstance(vec, torch.Tensor):
+        if not check:
+            return
+        fin = torch.isfinite(vec)
+        n_fin = fin.sum()
+        eos_fin = fin[eos_id].to(n_fin.dtype) if 0 <= eos_id < vec.numel() else torch.zeros_like(n_fin)
+        nan, pinf, n_fin, eos_fin = torch.stack([torch.isnan(vec).sum(), (vec == math.inf).sum(), n_fin, eos_fin]).tolist()
+    else:
+        fin = np.isfinite(vec)
+        nan, pinf, n_fin = int(np.isnan(vec).sum()), int((vec == np.inf).sum()), int(fin.sum())
+        eos_fin = int(fin[eos_id]) if 0 <= eos_id < vec.size else 0
+    if nan:
+        raise ValueError(f"row {row}: logit_bias holds NaN")
+    if pinf:
+        raise ValueError(f"row {row}: logit_bias holds +inf (only finite values and -inf are allowed)")
+    if n_fin < 1:
+        raise ValueError(f"row {row}: logit_bias bans every token")
+    if min_new_tokens > 0 and eos_id >= 0 and n_fin - eos_fin < 1:
+        raise ValueError(f"row {row}: logit_bias admits only eos_id {eos_id}, which min_new_tokens {min_new_tokens} bans")
+
+
 @dataclasses.dataclass
 class RowSampling:
     """One batch row's sampler settings (mgea_row_sampler, include/mgea.h) for DecoderEngine.generate_rows / ops.sample_rows.
     top_k None or 0 = no cut, 1 = greedy (the exact argmax, no temperature division); top_p None = no nucleus cut;
     repetition_penalty None = 1 = none; max_new_tokens 0 = the call's n_steps; stream None = the row's index in the batch (what
-    generate() uses).  The row draws its step-t number from Philox counter (stream, t) under key seed."""
+    generate() uses).  The row draws its step-t number from Philox counter (stream, t) under key seed.
+    logit_bias (None, a dict id -> bias, a host array or a device tensor [vocab]; -inf bans an id) is added to the row's penalized
+    logits at every step; min_new_tokens > 0 bans eos_id until the row has produced that many ids (mgea_row_logits)."""
     temperature: float = 1.0
     top_k: Optional[int] = 50
     top_p: Optional[float] = None
@@ -89,6 +140,8 @@ class RowSampling:
     max_new_tokens: int = 0
     seed: int = 0
     stream: Optional[int] = None
+    logit_bias: object = None
+    min_new_tokens: int = 0
 
     def check(self, row: int, vocab: int, n_steps: Optional[int] = None) -> None:
         """ValueError naming the row for what the native call would refuse (MGEA_EINVAL)."""
@@ -107,6 +160,9 @@ class RowSampling:
             raise ValueError(f"row {row}: max_new_tokens {self.max_new_tokens} outside [0, {n_steps}]")
         if self.stream is not None and not 0 <= int(self.stream) < 2 ** 32:
             raise ValueError(f"row {row}: stream {self.stream} is not a 32-bit word")
+        m = int(self.min_new_tokens)
+        if m < 0 or (n_steps is not None and m > n_steps):
+            raise ValueError(f"row {row}: min_new_tokens {m} outside [0, {'n_steps' if n_steps is None else n_steps}]")
 
     def record(self, row: int) -> RowSampler:
         pen = self.repetition_penalty
@@ -122,6 +178,40 @@ def pack_rows(rows: Sequence[RowSampling], vocab: int, n_steps: Optional[int] = 
     for b, r in enumerate(rows):
         r.check(b, vocab, n_steps)
     return (RowSampler * len(rows))(*[r.record(b) for b, r in enumerate(rows)])
+
+
+def pack_row_logits(rows: Sequence[RowSampling], vocab: int, device, check: bool = True):
+    """The rows' logit_bias / min_new_tokens as the C array mgea_row_logits[B] plus the device tensors it points into (keep them
+    alive until the call's stream has passed), or (None, []) when no row sets either -- the caller then makes the unbiased call.
+    Every vector is checked (check_logit_bias; check=False skips the read-back of device tensors); rows that share one bias object
+    share one upload."""
+    rows = list(rows)
+    if all(r.logit_bias is None and int(r.min_new_tokens) == 0 for r in rows):
+        return None, []
+    recs = (RowLogits * len(rows))()
+    dense, keep = {}, []
+    for b, r in enumerate(rows):
+        recs[b].min_new_tokens = int(r.min_new_tokens)
+        recs[b].reserved = 0
+        if r.logit_bias is None:
+            continue
+        key = id(r.logit_bias)
+        if key not in dense:
+            try:
+                dense[key] = [dense_logit_bias(r.logit_bias, vocab), None, set()]
+            except ValueError as e:
+                raise ValueError(f"row {b}: {e}") from None
+        vec, dev, seen = dense[key]
+        rule = (int(r.eos_id), int(r.min_new_tokens) > 0)
+        if rule not in seen:   # the verdict depends on the row only through these
+            check_logit_bias(vec, b, int(r.eos_id), int(r.min_new_tokens), check)
+            seen.add(rule)
+        if dev is None:
+            dev = vec.to(device) if isinstance(vec, torch.Tensor) else torch.from_numpy(vec).to(device)
+            dense[key][1] = dev
+            keep.append(dev)
+        recs[b].bias_dev = dev.data_ptr()
+    return recs, keep
 
 
 def _prompt_ids(prompts):
@@ -325,7 +415,7 @@ class DecoderEngine:
         False skips even that and leaves the flag for id_errors().
         repetition_penalty: None (or 1.0) = none; else a finite p > 0 (ValueError otherwise) applied like
         transformers' RepetitionPenaltyLogitsProcessor to every id of the row's prompt and of what it generated
-        (mgea_decoder_generate_penalized); presence() then returns those sets."""
+        (mgea_decoder_generate_penalized); presence() then returns those sets.  (generate_biased: the same with a logit bias.)"""
         from . import ops
         pen = ops.check_repetition_penalty(repetition_penalty)
         ids, lens = _prompt_ids(prompts)
@@ -348,14 +438,40 @@ class DecoderEngine:
             self.id_errors()
         return out[:, :n_steps]
 
+    def generate_biased(self, prompts, n_steps: int, temperature: float = 1.0, top_k: Optional[int] = 50,
+                        top_p: Optional[float] = None, eos_id: int = -1, seed: int = 0, check_ids: bool = True,
+                        repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0,
+                        check_bias: bool = True) -> torch.Tensor:
+        """generate() with a logit bias and a minimum length (generate()'s own parameter list is kept as it is).
+        logit_bias: None, or one vector for all rows (a dict id -> bias, a host array or a device tensor [vocab]), or [B, vocab]:
+        added to the penalized logits at every step, -inf bans an id.  min_new_tokens > 0 bans eos_id until a row has produced that
+        many ids.  With either one this is generate_rows() with the same record on every row (stream = the row's index): the
+        draws of generate(); with neither it IS generate().  check_bias=False skips the read-back that validates a DEVICE bias
+        (check_logit_bias)."""
+        from . import ops
+        if logit_bias is None and int(min_new_tokens) == 0:
+            return self.generate(prompts, n_steps, temperature, top_k, top_p, eos_id, seed, check_ids, repetition_penalty)
+        pen = ops.check_repetition_penalty(repetition_penalty)
+        B = prompts.shape[0] if isinstance(prompts, torch.Tensor) else len(prompts)
+        per_row = [logit_bias] * B
+        if not isinstance(logit_bias, dict) and logit_bias is not None and getattr(logit_bias, "ndim", 1) == 2:
+            if logit_bias.shape[0] != B:
+                raise ValueError(f"logit_bias must be [{self.vocab}] or [{B}, {self.vocab}], got {list(logit_bias.shape)}")
+            per_row = [logit_bias[b] for b in range(B)]
+        rows = [RowSampling(temperature, top_k, top_p, pen, eos_id, 0, seed, None, per_row[b], int(min_new_tokens))
+                for b in range(B)]
+        return self.generate_rows(prompts, rows, n_steps, check_ids, check_bias)
+
     def generate_rows(self, prompts, rows: Sequence[RowSampling], n_steps: Optional[int] = None,
-                      check_ids: bool = True) -> torch.Tensor:
+                      check_ids: bool = True, check_bias: bool = True) -> torch.Tensor:
         """generate() with one RowSampling per prompt (mgea_decoder_generate_rows): concurrent requests with their own temperature,
         top-k, top-p, repetition penalty, EOS id, seed, Philox stream and step budget in one batch.  n_steps None = the largest
         max_new_tokens (every row then needs one > 0).  Returns int32 [B, n_steps]; -1 after a row's EOS or budget.  A row's ids
         depend on its prompt, its record and B, not on its index or on the other rows; with stream = b and no budget on every row
         this is generate().  Each row needs len(prompt) + its budget <= max_ctx: a row that would run past the context reserved
-        for the batch, min(longest prompt + n_steps, max_ctx), finishes there."""
+        for the batch, min(longest prompt + n_steps, max_ctx), finishes there.
+        Rows with a logit_bias or min_new_tokens make it mgea_decoder_generate_rows_biased (the order of the processing steps and the
+        validity rules: include/mgea.h); with none set this is the call it always was."""
         rows = list(rows)
         ids, lens = _prompt_ids(prompts)
         B, Tp = ids.shape
@@ -368,12 +484,19 @@ class DecoderEngine:
             n_steps = max(budgets)
         n_steps = int(n_steps)
         recs = pack_rows(rows, self.vocab, n_steps)
+        lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
         checked = self._check_ids(ids)
         with self._on_stream():
             ids = ids.to(self.device).contiguous()
             lens = None if lens is None else lens.to(self.device).contiguous()
             out = torch.empty(B, max(n_steps, 1), dtype=torch.int32, device=self.device)
-            check(self.lib.mgea_decoder_generate_rows(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, ptr(out), self._sp()))
+            if lrecs is None:
+                check(self.lib.mgea_decoder_generate_rows(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, ptr(out), self._sp()))
+            else:
+                for t in keep:   # uploaded on the caller's stream, read by the engine's
+                    t.record_stream(self.stream)
+                check(self.lib.mgea_decoder_generate_rows_biased(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, ptr(out),
+                                                                 self._sp()))
         self._cur_batch = B
         self._epoch += 1
         if check_ids and not checked:
@@ -409,4 +532,4 @@ class DecoderEngine:
         out = (C.c_int64 * 8)()
         check(self.lib.mgea_decoder_stats(self.h, out))
         return dict(graph_nodes=out[0], graph_replays=out[1], graph_instantiates=out[2], graphs_cached=out[4], prefill16_forwards=out[5],
-                    penalized_steps=out[6])
+                    penalized_steps=out[6], biased_steps=out[7])

@@ -204,11 +204,38 @@ def sample(logits: torch.Tensor, temperature=1.0, top_k=50, top_p=None, seed=0, 
     return (ids, probs) if want_probs else ids
 
 
-def sample_rows(logits: torch.Tensor, rows, step=0, want_probs=False, presence=None):
+def sample_biased(logits: torch.Tensor, temperature=1.0, top_k=50, top_p=None, seed=0, step=0, want_probs=False,
+                  repetition_penalty=None, presence=None, logit_bias=None):
+    """sample() with a logit bias (sample()'s own parameter list is kept as it is).  logit_bias: None (then this IS sample()), one
+    vector for all rows -- a dict id -> bias, a host array or a device tensor [V] -- or [B, V]: added to the penalized logits, -inf
+    bans an id.  With a bias this is sample_rows() with the same record on every row: the same draws."""
+    if logit_bias is None:
+        return sample(logits, temperature, top_k, top_p, seed, step, want_probs, repetition_penalty, presence)
+    from .decoder import RowSampling
+    row = RowSampling(temperature, top_k, top_p, check_repetition_penalty(repetition_penalty), -1, 0, seed)
+    return sample_rows(logits, [row] * logits.shape[0], step, want_probs, presence, logit_bias=logit_bias)
+
+
+def sample_rows(logits: torch.Tensor, rows, step=0, want_probs=False, presence=None, logit_bias=None, min_new_tokens=None):
     """sample() with one mgea.decoder.RowSampling per row (mgea_op_sample_rows): row b reads rows[b] and draws from Philox counter
     (stream_b, step) under key seed_b (stream None = b).  presence (a bool [B, V] mask or B id lists) is what the penalized rows
-    penalize; none if None.  top_k=1 rows take the exact argmax of their (penalized) row, without the temperature division."""
-    from .decoder import pack_rows
+    penalize; none if None.  top_k=1 rows take the exact argmax of their (penalized) row, without the temperature division.
+    logit_bias (one vector for all rows or [B, V]) and min_new_tokens (an int or one per row) override the rows' own fields; a row
+    with either goes through mgea_op_sample_rows_biased: bias added after the penalty, eos_id banned while step < min_new_tokens."""
+    import dataclasses
+    from .decoder import pack_row_logits, pack_rows
+    rows = list(rows)
+    if logit_bias is not None or min_new_tokens is not None:
+        nb = len(rows)
+        per_row = [logit_bias] * nb
+        if logit_bias is not None and not isinstance(logit_bias, dict) and getattr(logit_bias, "ndim", 1) == 2:
+            if logit_bias.shape[0] != nb:
+                raise ValueError(f"logit_bias must be [V] or [{nb}, V], got {list(logit_bias.shape)}")
+            per_row = [logit_bias[b] for b in range(nb)]
+        mins = list(min_new_tokens) if isinstance(min_new_tokens, (list, tuple)) else [min_new_tokens] * nb
+        rows = [dataclasses.replace(r, logit_bias=r.logit_bias if logit_bias is None else per_row[b],
+                                    min_new_tokens=r.min_new_tokens if mins[b] is None else int(mins[b]))
+                for b, r in enumerate(rows)]
     lib = _lib.load()
     logits = _dev(logits.float())
     B, V = logits.shape
@@ -221,7 +248,11 @@ def sample_rows(logits: torch.Tensor, rows, step=0, want_probs=False, presence=N
         bits = torch.from_numpy(words.view(np.int32)).to(logits.device)
     ids = torch.empty(B, dtype=torch.int32, device=logits.device)
     probs = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_probs else None
-    check(lib.mgea_op_sample_rows(ptr(logits), B, V, recs, ptr(bits), int(step), ptr(ids), ptr(probs), stream_ptr()))
+    lrecs, keep = pack_row_logits(rows, V, logits.device)
+    if lrecs is None:
+        check(lib.mgea_op_sample_rows(ptr(logits), B, V, recs, ptr(bits), int(step), ptr(ids), ptr(probs), stream_ptr()))
+    else:
+        check(lib.mgea_op_sample_rows_biased(ptr(logits), B, V, recs, ptr(bits), lrecs, int(step), ptr(ids), ptr(probs), stream_ptr()))
     return (ids, probs) if want_probs else ids
 
 

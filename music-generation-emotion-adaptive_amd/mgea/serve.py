@@ -46,9 +46,10 @@ class RequestBatcher:
                 self._thread.start()
 
     def submit(self, prompt_tokens: Sequence[str], max_len=512, temperature=1.0, top_k=50, top_p=None,
-               repetition_penalty=None, seed: Optional[int] = None) -> "Future[List[str]]":
+               repetition_penalty=None, seed: Optional[int] = None, logit_bias=None, min_new_tokens: int = 0) -> "Future[List[str]]":
         """Queue one sample_kvcache request; the future's result is its prompt + generated tokens.  Unknown tokens raise KeyError
-        and a bad repetition penalty ValueError here, in the caller's thread.  A seed of None is drawn here too, so
+        and a bad repetition penalty, logit_bias (a dict id -> bias, a host array or a device tensor [vocab]; a host one is checked
+        in full, a device one for its shape) or min_new_tokens ValueError here, in the caller's thread.  A seed of None is drawn here too, so
         torch.manual_seed in the caller makes it reproducible whatever the batch it lands in."""
         import generate_music.generate as gen
         from .ops import check_repetition_penalty
@@ -57,8 +58,16 @@ class RequestBatcher:
             if t not in gen.tok2id:
                 raise KeyError(t)
         check_repetition_penalty(repetition_penalty)
+        if int(min_new_tokens) < 0:
+            raise ValueError(f"min_new_tokens {min_new_tokens} is negative")
+        if logit_bias is not None:
+            from .decoder import check_logit_bias, dense_logit_bias
+            eos = gen.tok2id.get("[END_SEQUENCE]", -1)
+            logit_bias = dense_logit_bias(logit_bias, self.model._need().vocab)   # packed once, here, at the engine's vocabulary
+            check_logit_bias(logit_bias, 0, eos, int(min_new_tokens), check=False)
         kwargs = dict(max_len=int(max_len), temperature=temperature, top_k=top_k, top_p=top_p,
-                      repetition_penalty=repetition_penalty, seed=gen._draw_seed() if seed is None else int(seed))
+                      repetition_penalty=repetition_penalty, seed=gen._draw_seed() if seed is None else int(seed),
+                      logit_bias=logit_bias, min_new_tokens=int(min_new_tokens))
         fut: Future = Future()
         with self._cv:
             if self._closed:
