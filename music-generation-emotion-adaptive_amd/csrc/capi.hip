@@ -94,6 +94,13 @@ int set_max_dynamic_lds(const void* fn, int bytes, int dev, uint64_t* done) {
 
 using namespace mgea;
 
+// a sampler launch on caller buffers: no fused tail, the host's step index
+static SampleCall op_sample_call(const float* logits_dev, int B, int V, int64_t step, int32_t* ids_out_dev, float* probs_out_dev) {
+    SampleCall c{};
+    c.logits = logits_dev; c.B = B; c.V = V; c.step_host = step; c.ids_out = ids_out_dev; c.probs_out = probs_out_dev;
+    return c;
+}
+
 extern "C" {
 
 const char* mgea_last_error(void) { return get_error(); }
@@ -247,12 +254,14 @@ int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sam
                    int32_t* ids_out_dev, float* probs_out_dev, void* stream) {
     MGEA_REQUIRE(logits_dev && s, MGEA_EINVAL, "op_sample: NULL argument");
     hipStream_t st = (hipStream_t)stream;
+    SampleCall c = op_sample_call(logits_dev, B, V, step, ids_out_dev, probs_out_dev);
+    c.params = sampler_params(*s);
     if (s->top_k == 1 && ids_out_dev) {
         MGEA_TRY(launch_logits_argmax(logits_dev, 1, 0, V, nullptr, nullptr, B, V, ids_out_dev, st));
         if (!probs_out_dev) return MGEA_OK;
-        return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, nullptr, probs_out_dev, st);
+        c.ids_out = nullptr;
     }
-    return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, ids_out_dev, probs_out_dev, st);
+    return launch_sample(c, st);
 }
 
 int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s, float repetition_penalty,
@@ -262,9 +271,10 @@ int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, cons
                  "op_sample_penalized: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
     if (repetition_penalty == 1.0f) return mgea_op_sample(logits_dev, B, V, s, step, ids_out_dev, probs_out_dev, stream);
     MGEA_REQUIRE(presence_dev, MGEA_EINVAL, "op_sample_penalized: presence_dev is NULL");
-    // the kernel only reads the bitmap (it writes one only in the decoder's fused tail)
-    return launch_sample(logits_dev, B, V, *s, nullptr, nullptr, step, ids_out_dev, probs_out_dev, (hipStream_t)stream, nullptr,
-                         const_cast<uint32_t*>(presence_dev), repetition_penalty);
+    SampleCall c = op_sample_call(logits_dev, B, V, step, ids_out_dev, probs_out_dev);
+    c.params = sampler_params(*s, repetition_penalty);
+    c.presence = const_cast<uint32_t*>(presence_dev);   // the kernel only reads the bitmap (it writes one only in the decoder's fused tail)
+    return launch_sample(c, (hipStream_t)stream);
 }
 
 int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
@@ -279,17 +289,9 @@ int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, co
     MGEA_TRY(check_row_samplers(rows, B, V, -1, "op_sample_rows"));
     if (lrows) MGEA_TRY(check_row_logits(lrows, B, -1, "op_sample_rows"));
     std::vector<SamplerParams> rec((size_t)B);
-    bool pen = false, biased = false;
-    for (int b = 0; b < B; ++b) {
-        rec[(size_t)b] = sampler_params(rows[b]);
-        pen = pen || rows[b].repetition_penalty != 1.0f;
-        if (lrows) {
-            rec[(size_t)b].bias_on = lrows[b].bias_dev ? 1 : 0;
-            rec[(size_t)b].min_new = lrows[b].min_new_tokens;
-            biased = biased || lrows[b].bias_dev || lrows[b].min_new_tokens > 0;
-        }
-    }
-    MGEA_REQUIRE(!pen || presence_dev, MGEA_EINVAL, "op_sample_rows: a row is penalized but presence_dev is NULL");
+    const RowRecords rr = build_row_records(rows, lrows, B, -1, rec.data());
+    const bool biased = rr.form == StepForm::BIASED;
+    MGEA_REQUIRE(!rr.any_penalty || presence_dev, MGEA_EINVAL, "op_sample_rows: a row is penalized but presence_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     SamplerParams* rec_dev = nullptr;
     MGEA_CHECK_HIP(hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)));
@@ -299,7 +301,10 @@ int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, co
         set_error("op_sample_rows: allocation of the bias rows failed");
         return MGEA_ENOMEM;
     }
-    const mgea_sampler_config unused{1.0f, 0, 0.0f, -1, 0};   // every scalar comes from rec_dev
+    SampleCall c = op_sample_call(logits_dev, B, V, step, ids_out_dev, probs_out_dev);
+    c.params_dev = rec_dev;   // every scalar comes from the records
+    c.presence = rr.any_penalty ? const_cast<uint32_t*>(presence_dev) : nullptr;   // (a bias alone needs no bitmap here: nothing is written)
+    c.bias = bias_dev;
     int rc = MGEA_EHIP;
     bool copied = hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st) == hipSuccess;
     for (int b = 0; biased && copied && b < B; ++b)
@@ -307,8 +312,7 @@ int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, co
             copied = hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st) ==
                      hipSuccess;
     if (copied)
-        rc = launch_sample(logits_dev, B, V, unused, rec_dev, nullptr, step, ids_out_dev, probs_out_dev, st, nullptr,
-                           pen ? const_cast<uint32_t*>(presence_dev) : nullptr, 1.0f, bias_dev);
+        rc = launch_sample(c, st);
     else
         set_error("op_sample_rows: copy of the records failed");
     const hipError_t e = hipStreamSynchronize(st);   // rec, rec_dev and bias_dev are freed below

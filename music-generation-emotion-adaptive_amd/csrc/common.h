@@ -207,11 +207,27 @@ static inline SamplerParams sampler_params(const mgea_row_sampler& r) {
     return SamplerParams{r.temperature, r.top_k, r.top_p, r.eos_id, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.repetition_penalty,
                          r.stream, r.max_new_tokens > 0 ? r.max_new_tokens : MGEA_NO_BUDGET, MGEA_NO_BUDGET, 0, 0};
 }
+// The tail of a decode step -- everything after the LM head -- has four launch sequences, and a generation runs one of them on every step:
+//   GREEDY (every row has top_k == 1)  the head leaves per-tile (max, argmax) partials and no logits row; an argmax tail merges them
+//   SAMPLED                            the head writes the logits row; the plain sampler draws from it
+//   PENALIZED (a row's penalty != 1)   as SAMPLED with the PENALTY sampler over the rows' presence bitmaps, which the tail keeps up to
+//                                      date; a greedy row is top_k = 1 of its penalized row (the head's partials know no penalty)
+//   BIASED (a row's bias or min_new)   as PENALIZED with the BIAS sampler and the rows' bias buffer (a penalty of 1 changes nothing)
+// The form is the key of the captured step graphs: every other setting of a request lives in the rows' device records.
+enum class StepForm { GREEDY = 0, SAMPLED, PENALIZED, BIASED };
+static inline StepForm step_form(bool all_greedy, bool any_penalized, bool any_biased) {
+    return any_biased ? StepForm::BIASED : any_penalized ? StepForm::PENALIZED : all_greedy ? StepForm::GREEDY : StepForm::SAMPLED;
+}
+static inline bool form_has_presence(StepForm f) { return f == StepForm::PENALIZED || f == StepForm::BIASED; }
+
 // host check of rows[0, B) (mgea_decoder_generate_rows, mgea_op_sample_rows): MGEA_EINVAL naming the first bad row; n_steps < 0 skips the
 // budget check
 int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who);
 // host check of the rows' mgea_row_logits records: reserved == 0, 0 <= min_new_tokens <= n_steps (n_steps < 0: no upper bound)
 int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who);
+// checked rows [B] (+ lrows [B] or NULL) -> out[B] and the batch's form; may_stop_early: some row has an EOS id or a budget below n_steps
+struct RowRecords { StepForm form; bool any_penalty; bool may_stop_early; };
+RowRecords build_row_records(const mgea_row_sampler* rows, const mgea_row_logits* lrows, int B, int n_steps, SamplerParams* out);
 constexpr int MGEA_SAMPLER_MAX_VOCAB = 14336;   // the sampler keeps a row in registers: 256 threads x 56 logits
 // Repetition penalty (mgea_decoder_generate_penalized): per row a presence bitmap of ceil(V / 32) words, bit id & 31 of word id >> 5
 // set once the id is in the row's prompt or was generated by it.  Rows follow each other at that stride.
@@ -235,26 +251,38 @@ int launch_attn_cls(const float* q, const void* qkv, int qkv_bf16, const int32_t
                     const int32_t* cu = nullptr);
 int launch_logits_argmax(const float* P, int S, int64_t ps, int ldp, const float* bias, float* logits,
                          int M, int V, int32_t* argmax_out, hipStream_t st);
-// sampler over logits [B,V] (top_k != 1); writes ids[b]; probs_out optional
-// tail != NULL: the sampler also does the loop bookkeeping of the row and the NEXT step's embedding (advance_embed_row)
+// The fused tail of the sampler: it also does the loop bookkeeping of the row and the NEXT step's embedding (advance_embed_row)
 struct TailArgs {
     StepState s;
     const float* tok_emb; const float* pos_emb;
     float* x; float* stats;     // k-tiled residual stream and its LayerNorm partials (fused decode path)
     int C, vocab, pos_rows, absolute_pos;
 };
-// params_dev != NULL: row b's scalars come from the device record params_dev[b] instead of `s` (Philox counter word 0 = its stream instead
-// of b), and a row with top_k == 1 takes the exact argmax of its (penalized) row: no temperature division, ties to the lowest id
-// presence != NULL: the PENALTY form -- the logits of the ids whose bit is set in the row's presence bitmap (presence_words(V) words
-// per row) are penalized first, x < 0 ? x * p : x / p, p = penalty (or params_dev->penalty); with a tail the row's new token is then
-// added to that bitmap.  top_k == 1 there is the exact argmax of the penalized row (no temperature division, ties to the lowest id).
-// bias != NULL (needs params_dev): the BIAS form -- after the penalty, row b adds bias[b * V + i] to logit i if its record has bias_on,
-// and bans its eos_id while its step index is below the record's min_new.
-int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
-                  const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st,
-                  const TailArgs* tail = nullptr, uint32_t* presence = nullptr, float penalty = 1.0f, const float* bias = nullptr);
-// params_dev[0, B) <- s (stream = b, no budget), stream-ordered: the uniform form of the records
-int launch_fill_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, int B, hipStream_t st, float penalty = 1.0f);
+// One sampler launch over logits [B, V] (sampler.hip); every optional part is a named field, NULL = absent.
+struct SampleCall {
+    const float* logits; int B, V;
+    // the scalars: the rows' device records (Philox counter word 0 = the record's stream), or `params` by value on every row
+    // (sampler_params(s, penalty); counter word 0 = b).  With records, or in the PENALTY / BIAS forms, a row with top_k == 1 takes the
+    // exact argmax of its processed row: no temperature division, ties to the lowest id.
+    const SamplerParams* params_dev; SamplerParams params;
+    // the step index (Philox counter word 1; what min_new is compared with): per row from device memory, or step_host
+    const int32_t* row_step_dev; int64_t step_host;
+    int32_t* ids_out; float* probs_out;   // [B] (NULL: nothing is drawn); [B, V] pre-draw probabilities
+    const TailArgs* tail;                 // the fused tail; NULL: the sampler only writes ids_out
+    // PENALTY form: the logits of the ids set in the row's bitmap (presence_words(V) words per row) are penalized first, x < 0 ? x * p :
+    // x / p; a fused tail then adds the row's new token to the bitmap.  BIAS form (records only): after the penalty, row b adds
+    // bias[b * V + i] to logit i if its record has bias_on, and bans its eos_id while its step index is below the record's min_new
+    uint32_t* presence; const float* bias;
+};
+int launch_sample(const SampleCall& c, hipStream_t st);
+// ---- the kernels that end a step, and the rows' records (step_tail.hip) ----
+int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
+                          int B, hipStream_t st);
+int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
+                                const float* tok_emb, const float* pos_emb, float* x, float* stats, int B, int C, int vocab,
+                                int pos_rows, int absolute_pos, hipStream_t st);
+// params_dev[0, B) <- v with stream = b, stream-ordered: the uniform form of the records
+int launch_fill_sampler_params(SamplerParams* params_dev, const SamplerParams& v, int B, hipStream_t st);
 // params_dev[b].max_new <- min(max_new, reserved - len_b), len_b = lens[b] (NULL: T) clamped to [1, T], and ctx_cap <- reserved: a row
 // stops where its KV pages end
 int launch_clamp_budgets(SamplerParams* params_dev, const int32_t* lens, int T, int B, int reserved, hipStream_t st);
@@ -388,11 +416,6 @@ constexpr int HB_PITCH = 20;   // head_balanced_kernel: floats per LDS row of a 
 int launch_embed_stats(const int32_t* ids, const int32_t* lens, const int32_t* ctx_len, const float* tok_emb,
                        const float* pos_emb, float* x, float* stats, int B, int T, int C, int vocab, int pos_rows,
                        int absolute_pos, int32_t* err_flag, hipStream_t st);
-int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
-                          int B, hipStream_t st);
-int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
-                                const float* tok_emb, const float* pos_emb, float* x, float* stats, int B, int C, int vocab,
-                                int pos_rows, int absolute_pos, hipStream_t st);
 
 }  // namespace mgea
 

@@ -103,11 +103,11 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, greedy | sampled, plain | penalized | biased, steps).  Everything a step reads besides its
+    // Captured decode-step graphs, one per (batch, StepForm, steps): one per launch sequence.  Everything a step reads besides its
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
-    struct GraphEntry { int batch; bool greedy; bool penalized; bool biased; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
+    struct GraphEntry { int batch; StepForm form; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
     std::vector<GraphEntry> graphs;
     uint64_t use_clock = 0;
     SamplerParams* samp_dev = nullptr;     // [max_batch] records, one per row (common.h)
@@ -444,97 +444,88 @@ int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t
     return MGEA_OK;
 }
 
-// pd != NULL: the EOS id (like the other sampler scalars) is read from that device record -- the captured graph's form
-StepState step_state(mgea_decoder* h, const Bufs& u, int eos, const SamplerParams* pd) {
-    StepState s;
-    s.cur_ids = u.cur_ids;
-    s.ctx_len = u.ctx_len;
-    s.done = u.done;
-    s.row_step = u.row_step;
-    s.n_done = h->n_done;
-    s.ids_out = u.ids_hist;
-    s.n_steps = h->ids_hist_stride;
-    s.eos_id = eos;
-    s.params = pd;
-    return s;
-}
-
-// One fused decode step (T = 1) over the rows of `u`.
-// primed: x already holds the embedding (+ LN statistics) of cur_ids -- generate() keeps that invariant by
+// One decode step (T = 1) of the whole batch.
+// form: the launch sequence of the step's tail (common.h); nothing below looks at a sampler setting to choose a kernel.
+// pd: the rows' device records (generate()), or NULL and pv by value on every row (mgea_decoder_step).
+// primed: x already holds the embedding (+ LN statistics) of cur_ids -- generate() keeps that invariant on the fused path by
 // fusing the next step's embedding into this step's tail, so a replayed step is 32 launches.
-// pd: device-resident sampler scalars (generate()) or NULL (mgea_decoder_step: `sc` by value).  Only sc.top_k == 1
-// (greedy or not) and pen shape the launch sequence.
-// pen: a penalized generate() step (pd holds the penalty, h->presence the rows' bitmaps).  Its greedy steps take the sampled sequence
-// too: the head writes the logits row and the PENALTY sampler keeps top_k = 1 entry of the penalized row (the head's per-tile argmax
-// partials know nothing of the penalty).
-int enqueue_step_fused(mgea_decoder* h, const Bufs& u, int B, const mgea_sampler_config& sc, const SamplerParams* pd,
-                       float* logits_out, hipStream_t st, bool primed, bool pen = false, bool biased = false) {
+struct StepCall {
+    int B; StepForm form;
+    const SamplerParams* pd; SamplerParams pv;
+    float* logits_out;   // optional
+    bool primed;
+    // where the head writes the logits row: the caller's buffer, the engine's `own` for the sampler, nowhere for the argmax tails
+    float* head_out(float* own) const { return logits_out ? logits_out : (form == StepForm::GREEDY ? nullptr : own); }
+};
+
+// The tail of a step over the head's output.  GREEDY: the argmax of the head's n_partials partials per row (0: the ids are already in
+// u.sampled), the bookkeeping and, primed, the next step's embedding.  Otherwise the form's sampler over the logits row lg, with the
+// bookkeeping and the next embedding as its fused tail when primed, followed by the advance kernel when not.
+int enqueue_tail(mgea_decoder* h, const Bufs& u, const StepCall& k, const float* lg, int n_partials, hipStream_t st) {
     const auto& c = h->cfg;
-    const int C = c.d_model, V = c.vocab;
-    const bool greedy = sc.top_k == 1 && !pen;
-    uint32_t* pres = pen ? h->presence : nullptr;
-    const float* bias = biased ? h->bias : nullptr;   // the biased form (always with pen): the BIAS sampler
-    // [embed,] 6 x (qkv, attention, out-proj, fc1, fc2), head (+ per-tile argmax), finalize [+ next embed]
-    const int abs_pos = c.pos_mode == MGEA_POS_ABSOLUTE;
-    if (!primed)
-        PROF(PC_ROWOP, launch_embed_stats(u.cur_ids, nullptr, u.ctx_len, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, 1, C, V,
-                                          c.seq_len, abs_pos, h->err_flag, st));
-    MGEA_TRY(run_blocks_fused(h, u, B, 1, nullptr, true, st));
-    SkinnyArgs a{};
-    a.M = B; a.A = u.x; a.lda = C; a.N = V; a.K = C;
-    a.out = logits_out ? logits_out : (greedy ? nullptr : u.logits);
-    a.ldo = V; a.pmax_val = u.pmax_val; a.pmax_idx = u.pmax_idx;
-    DecodeGemmPlan head;   // its partial count is what the greedy tail merges
-    PROF(PC_GEMM, decode_gemm(h, 0, 4, a, gemv_ok(h, B, 1, nullptr, true) && gemv_shape_ok(B, V, C), st, &head));
-    if (greedy && primed) {
-        PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, head.n_partials, step_state(h, u, sc.eos_id, pd),
-                                                    u.sampled, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, C, V, c.seq_len,
-                                                    abs_pos, st));
-    } else if (greedy) {
-        PROF(PC_SAMPLE, launch_argmax_advance(u.pmax_val, u.pmax_idx, head.n_partials, step_state(h, u, sc.eos_id, pd),
-                                              u.sampled, B, st));
-    } else {
-        if (primed) {   // sampler + loop bookkeeping + next step's embedding in one launch
-            TailArgs t{step_state(h, u, sc.eos_id, pd), h->w(T_TOK), h->w(T_POS), u.x, u.stats, C, V, c.seq_len, abs_pos};
-            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, &t, pres, 1.0f, bias));
-        } else {
-            PROF(PC_SAMPLE, launch_sample(a.out, B, V, sc, pd, u.row_step, 0, u.sampled, nullptr, st, nullptr, pres, 1.0f, bias));
-            PROF(PC_ROWOP, launch_advance(u.sampled, step_state(h, u, sc.eos_id, pd), B, st, pres, V));
-        }
+    const int B = k.B, C = c.d_model, V = c.vocab;
+    // (with records the EOS id, like the other scalars, is read from them -- the captured graph's form)
+    const StepState s{u.cur_ids, u.ctx_len, u.done, u.row_step, h->n_done, u.ids_hist, h->ids_hist_stride, k.pv.eos_id, k.pd};
+    const TailArgs t{s, h->w(T_TOK), h->w(T_POS), u.x, u.stats, C, V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
+    if (k.form == StepForm::GREEDY) {
+        if (k.primed)
+            PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, n_partials, s, u.sampled, t.tok_emb, t.pos_emb, t.x,
+                                                        t.stats, B, C, V, t.pos_rows, t.absolute_pos, st));
+        else if (n_partials > 0)
+            PROF(PC_SAMPLE, launch_argmax_advance(u.pmax_val, u.pmax_idx, n_partials, s, u.sampled, B, st));
+        else
+            PROF(PC_ROWOP, launch_advance(u.sampled, s, B, st, nullptr, V));
+        return MGEA_OK;
     }
+    uint32_t* pres = form_has_presence(k.form) ? h->presence : nullptr;
+    SampleCall sc{};
+    sc.logits = lg; sc.B = B; sc.V = V;
+    sc.params_dev = k.pd; sc.params = k.pv; sc.row_step_dev = u.row_step;
+    sc.ids_out = u.sampled; sc.tail = k.primed ? &t : nullptr;
+    sc.presence = pres; sc.bias = k.form == StepForm::BIASED ? h->bias : nullptr;
+    PROF(PC_SAMPLE, launch_sample(sc, st));
+    if (!k.primed) PROF(PC_ROWOP, launch_advance(u.sampled, s, B, st, pres, V));
     return MGEA_OK;
 }
 
-// one decode step on cur_ids (T = 1) for the whole batch; logits_out optional
-int enqueue_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, const SamplerParams* pd, float* logits_out,
-                 hipStream_t st, bool primed = false, bool pen = false, bool biased = false) {
+// The fused step over the rows of `u`: [embed,] 6 x (qkv, attention, out-proj, fc1, fc2), head (+ per-tile argmax), tail
+int enqueue_step_fused(mgea_decoder* h, const Bufs& u, const StepCall& k, hipStream_t st) {
     const auto& c = h->cfg;
-    const int C = c.d_model, V = c.vocab;
+    const int B = k.B, C = c.d_model, V = c.vocab;
+    if (!k.primed)
+        PROF(PC_ROWOP, launch_embed_stats(u.cur_ids, nullptr, u.ctx_len, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, 1, C, V,
+                                          c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
+    MGEA_TRY(run_blocks_fused(h, u, B, 1, nullptr, true, st));
+    SkinnyArgs a{};
+    a.M = B; a.A = u.x; a.lda = C; a.N = V; a.K = C;
+    a.out = k.head_out(u.logits);
+    a.ldo = V; a.pmax_val = u.pmax_val; a.pmax_idx = u.pmax_idx;
+    DecodeGemmPlan head;   // its partial count is what the greedy tail merges
+    PROF(PC_GEMM, decode_gemm(h, 0, 4, a, gemv_ok(h, B, 1, nullptr, true) && gemv_shape_ok(B, V, C), st, &head));
+    return enqueue_tail(h, u, k, a.out, head.n_partials, st);
+}
+
+// one decode step on cur_ids: the fused path where the geometry has one, else the slab kernels (never primed: they embed cur_ids)
+int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
+    const auto& c = h->cfg;
+    const int B = k.B, C = c.d_model, V = c.vocab;
     const bool post = c.block_mode == MGEA_BLOCK_POSTLN_RELU;
-    const bool greedy = sc.top_k == 1 && !pen;   // (enqueue_step_fused: penalized greedy steps sample with top_k = 1)
-    uint32_t* pres = pen ? h->presence : nullptr;
-    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), B, sc, pd, logits_out, st, primed, pen, biased);
-    const Bufs u = main_bufs(h);
+    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), k, st);
     PROF(PC_ROWOP, launch_embed_ln(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                              post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, 1, C,
                              V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
     MGEA_TRY(run_blocks(h, B, 1, nullptr, true, true, st));
     int S = 1;
     MGEA_TRY(gemm(h, h->x, C, h->head_w(), B, V, C, &S, st));
-    float* lg = logits_out ? logits_out : (greedy ? nullptr : h->logits);
+    float* lg = k.head_out(h->logits);
     PROF(PC_SAMPLE, launch_logits_argmax(h->slabs, S, slab_floats(B, V), (int)slab_ld(V), h->head_b(), lg, B, V,
-                                  greedy ? h->sampled : nullptr, st));
-    if (!greedy)
-        PROF(PC_SAMPLE, launch_sample(lg, B, V, sc, pd, h->row_step, 0, h->sampled, nullptr, st, nullptr, pres, 1.0f,
-                                      biased ? h->bias : nullptr));
-    PROF(PC_ROWOP, launch_advance(h->sampled, step_state(h, u, sc.eos_id, pd), B, st, pres, V));
-    return MGEA_OK;
+                                  k.form == StepForm::GREEDY ? h->sampled : nullptr, st));
+    return enqueue_tail(h, main_bufs(h), k, lg, 0, st);
 }
 
-// The decode step of generate(): x arrives primed on the fused path.
-int enqueue_gen_step(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, bool pen, bool biased) {
-    if (!fused_ok(h, B)) return enqueue_step(h, B, sc, h->samp_dev, nullptr, st, false, pen, biased);
-    return enqueue_step_fused(h, main_bufs(h), B, sc, h->samp_dev, nullptr, st, true, pen, biased);
+// The decode step of generate(): the rows' device records; x arrives primed on the fused path.
+int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, hipStream_t st) {
+    return enqueue_step(h, StepCall{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B)}, st);
 }
 
 // embedding (+ LN statistics) of cur_ids into the buffers the next generate() step will read
@@ -546,16 +537,14 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
-// The captured decode step for (B, greedy, pen): from the cache, or captured + instantiated now (least recently used
+// The captured decode step for (B, form, steps): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond MAX_GRAPHS).
-constexpr size_t MAX_GRAPHS = 16;   // two per (batch, greedy | sampled, plain | penalized | biased): the single step and the 8-step graph
+constexpr size_t MAX_GRAPHS = 16;   // two per (batch, form): the single step and the 8-step graph -- 4 forms x 2 = 8 for one batch size
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_t st, hipGraphExec_t* out, int steps, bool pen,
-               bool biased) {
-    const bool greedy = sc.top_k == 1;
+int step_graph(mgea_decoder* h, int B, StepForm form, hipStream_t st, hipGraphExec_t* out, int steps) {
     for (auto& g : h->graphs)
-        if (g.batch == B && g.greedy == greedy && g.penalized == pen && g.biased == biased && g.steps == steps) {
+        if (g.batch == B && g.form == form && g.steps == steps) {
             g.last_use = ++h->use_clock;
             if (steps == 1) h->counters[0] = g.nodes;
             *out = g.exec;
@@ -572,7 +561,7 @@ int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_
     }
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, sc, st, pen, biased);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, st);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -588,7 +577,7 @@ int step_graph(mgea_decoder* h, int B, const mgea_sampler_config& sc, hipStream_
     }
     size_t nn = 0;
     (void)hipGraphGetNodes(g, nullptr, &nn);
-    h->graphs.push_back({B, greedy, pen, biased, steps, g, ex, (int64_t)nn, ++h->use_clock});
+    h->graphs.push_back({B, form, steps, g, ex, (int64_t)nn, ++h->use_clock});
     if (steps == 1) h->counters[0] = (int64_t)nn;
     h->counters[2] += 1;   // lifetime captures + instantiations
     h->counters[4] = (int64_t)h->graphs.size();
@@ -1043,7 +1032,8 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
     const int B = h->cur_batch;
     if (ids_in_dev)
         MGEA_CHECK_HIP(hipMemcpyAsync(h->cur_ids, ids_in_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    MGEA_TRY(enqueue_step(h, B, *s, nullptr, logits_out_dev, st));   // eager single step: the scalars travel by value
+    // eager single step: the scalars travel by value
+    MGEA_TRY(enqueue_step(h, StepCall{B, step_form(s->top_k == 1, false, false), nullptr, sampler_params(*s), logits_out_dev, false}, st));
     h->host_max_len += 1;
     if (ids_out_dev)
         MGEA_CHECK_HIP(hipMemcpyAsync(ids_out_dev, h->sampled, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -1055,19 +1045,15 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
 namespace {
 // mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
 // (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
-// are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  The generation
-// is "processed" if any row has a penalty != 1, a bias or min_new_tokens > 0: the logits-row + PENALTY sampler sequence; with a bias
-// or min_new_tokens anywhere it is the biased form of that sequence (BIAS sampler, its own graphs), presence bitmaps included.
+// are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  Which of the
+// four launch sequences the steps take: StepForm (common.h).
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
                 const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
                 int32_t* ids_out_dev, hipStream_t st) {
     const auto& c = h->cfg;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
-    // the step graphs' form: greedy only if every row is, penalized if any row is (p = 1 rows are unchanged by it: x * 1, x / 1 exact);
-    // the host poll for early stops when some row can finish before n_steps
-    mgea_sampler_config form{1.0f, 0, 0.0f, -1, 0};
-    bool pen = false, poll = false, biased = false, any_penalty = false;
+    RowRecords rr;   // the step graphs' form; whether to poll for early stops (some row can finish before n_steps)
     int reserve = Tp + n_steps;
     if (rows) {
         MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
@@ -1077,31 +1063,23 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         MGEA_REQUIRE(Tp < c.max_ctx && n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp, n_steps,
                      c.max_ctx);
         reserve = reserve < c.max_ctx ? reserve : c.max_ctx;
-        bool all_greedy = true;
-        for (int b = 0; b < B; ++b) {
-            const bool p1 = rows[b].repetition_penalty == 1.0f;
-            all_greedy = all_greedy && rows[b].top_k == 1 && p1;
-            pen = pen || !p1;
-            biased = biased || (lrows && (lrows[b].bias_dev || lrows[b].min_new_tokens > 0));
-            poll = poll || rows[b].eos_id >= 0 || (rows[b].max_new_tokens > 0 && rows[b].max_new_tokens < n_steps);
-        }
-        poll = poll || reserve < Tp + n_steps;
-        form.top_k = all_greedy ? 1 : 0;
-        any_penalty = pen;
-        pen = pen || biased;   // the biased form keeps the bitmaps: a penalty of 1 leaves a row as it is
+        // the records go to the pinned staging buffer, free once the previous call's copy out of it has run
+        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free));
+        rr = build_row_records(rows, lrows, B, n_steps, h->samp_stage);
+        rr.may_stop_early = rr.may_stop_early || reserve < Tp + n_steps;
     } else {
         MGEA_REQUIRE(Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
         MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
-        form = *s;
-        pen = any_penalty = penalty != 1.0f;
-        poll = s->eos_id >= 0;
+        rr = RowRecords{step_form(s->top_k == 1, penalty != 1.0f, false), penalty != 1.0f, s->eos_id >= 0};
     }
+    const StepForm form = rr.form;
+    const bool biased = form == StepForm::BIASED;
     h->last_penalized = false;
     h->counters[6] = 0;
     h->counters[7] = 0;
     MGEA_TRY(do_reset(h, B, reserve, st));
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
-    if (pen) {   // every row's set starts as its real prompt tokens
+    if (form_has_presence(form)) {   // every row's set starts as its real prompt tokens
         MGEA_TRY(launch_presence_seed(prompt_ids_dev, lens_dev, B, Tp, c.vocab, h->presence, st));
         h->last_penalized = true;
     }
@@ -1110,28 +1088,22 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     // the rows' sampler records -> device memory (stream-ordered, no host sync), then the cached step graph of this batch size:
     // all per-step state lives in device memory, so one graph serves every step of every request
     if (rows) {
-        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free));   // the previous call's copy out of the staging buffer has run
-        for (int b = 0; b < B; ++b) {
-            h->samp_stage[b] = sampler_params(rows[b]);
-            if (!biased) continue;
-            h->samp_stage[b].bias_on = lrows[b].bias_dev ? 1 : 0;
-            h->samp_stage[b].min_new = lrows[b].min_new_tokens;
+        for (int b = 0; biased && b < B; ++b)
             if (lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
                 MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)b * c.vocab, lrows[b].bias_dev, (size_t)c.vocab * sizeof(float),
                                               hipMemcpyDeviceToDevice, st));
-        }
         MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free, st));
         if (reserve < Tp + n_steps) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
     } else {
-        MGEA_TRY(launch_fill_sampler_params(h->samp_dev, *s, B, st, penalty));
+        MGEA_TRY(launch_fill_sampler_params(h->samp_dev, sampler_params(*s, penalty), B, st));
     }
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, st, &gexec, 1, pen, biased));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, st, &gexec, 1));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, st, &gexec_k, K, pen, biased));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, st, &gexec_k, K));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1139,12 +1111,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, st, pen, biased);
+            const int rc = enqueue_gen_step(h, B, form, st);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, st, pen, biased));
+            MGEA_TRY(enqueue_gen_step(h, B, form, st));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1153,7 +1125,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             MGEA_CHECK_HIP(hipGraphLaunch(gexec, st));
             ++launched;
         }
-        if (poll && (launched % 16) == 0) {  // stop once every row has drawn EOS (api_cache.py:181) or spent its budget
+        if (rr.may_stop_early && (launched % 16) == 0) {  // stop once every row has drawn EOS (api_cache.py:181) or spent its budget
             MGEA_CHECK_HIP(hipMemcpyAsync(&host_done, h->n_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             MGEA_CHECK_HIP(hipStreamSynchronize(st));
             if (host_done >= B) break;
@@ -1162,7 +1134,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     if (reserve < Tp + n_steps) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
     h->host_max_len += launched;
     h->counters[1] = launched;
-    h->counters[6] = any_penalty ? launched : 0;
+    h->counters[6] = rr.any_penalty ? launched : 0;
     h->counters[7] = biased ? launched : 0;
     // rows: ids_hist[b, 0:launched]; steps never run are -1
     MGEA_CHECK_HIP(hipMemsetAsync(ids_out_dev, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));

@@ -716,84 +716,4 @@ int launch_embed_stats(const int32_t* ids, const int32_t* lens, const int32_t* c
     return MGEA_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// greedy finalize: argmax over the per-tile partials of each row, then the sampler-loop
-// bookkeeping of api_cache.py:179-181 (append, EOS or budget stop: end_row_step) -- one 64-thread workgroup per row.
-__global__ __launch_bounds__(64) void argmax_advance_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
-                                                           int n_tiles, StepState s, int32_t* __restrict__ sampled) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = lane; i < n_tiles; i += 64) {
-        const float v = pval[(int64_t)b * n_tiles + i];
-        const int ix = pidx[(int64_t)b * n_tiles + i];
-        if (v > best || (v == best && ix < bi)) { best = v; bi = ix; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if (lane == 0) {
-        const int tok = bi == 0x7fffffff ? 0 : bi;
-        sampled[b] = tok;
-        end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], s.done[b]);
-    }
-}
-
-// Same finalize fused with the NEXT step's embedding (generate() keeps x "primed"): one launch less
-// per decode step.  256 threads per row: partial-argmax reduce, bookkeeping by thread 0, then
-// x[row] = tok_emb[token] + pos_emb[pos] (k-tiled) and its LayerNorm partial statistics.
-__global__ __launch_bounds__(256) void argmax_advance_embed_kernel(const float* __restrict__ pval,
-                                                                  const int32_t* __restrict__ pidx, int n_tiles,
-                                                                  TailArgs t, int32_t* __restrict__ sampled) {
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    __shared__ float sh[8];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the row's bookkeeping state is requested together with the partials (one round trip instead of two)
-    int st_step = 0, st_fed = 0, st_len = 0, st_done = 0;
-    if (tid == 0) { st_step = t.s.row_step[b]; st_fed = t.s.cur_ids[b]; st_len = t.s.ctx_len[b]; st_done = t.s.done[b]; }
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < n_tiles; i += 256) {
-        const float v = pval[(int64_t)b * n_tiles + i];
-        const int ix = pidx[(int64_t)b * n_tiles + i];
-        if (v > best || (v == best && ix < bi)) { best = v; bi = ix; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if (lane == 0) { sv[wave] = best; si[wave] = bi; }
-    __syncthreads();
-    int tok = 0;
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        tok = bi == 0x7fffffff ? 0 : bi;
-    }
-    advance_embed_row(b, tok, t, sampled, st_step, st_fed, st_len, st_done, sh);
-}
-
-int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
-                                const float* tok_emb, const float* pos_emb, float* x, float* stats, int B, int C, int vocab,
-                                int pos_rows, int absolute_pos, hipStream_t st) {
-    MGEA_REQUIRE(B <= MGEA_FUSED_MAX_ROWS && C % 4 == 0 && C <= 4096, MGEA_EINVAL, "argmax+embed: bad shape");
-    TailArgs t{s, tok_emb, pos_emb, x, stats, C, vocab, pos_rows, absolute_pos};
-    hipLaunchKernelGGL(argmax_advance_embed_kernel, dim3(B), dim3(256), 0, st, pval, pidx, n_tiles, t, sampled);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
-                          int B, hipStream_t st) {
-    hipLaunchKernelGGL(argmax_advance_kernel, dim3(B), dim3(64), 0, st, pval, pidx, n_tiles, s, sampled);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
 }  // namespace mgea

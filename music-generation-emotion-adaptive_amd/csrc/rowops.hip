@@ -355,55 +355,6 @@ int launch_logits_argmax(const float* P, int S, int64_t ps, int ldp, const float
     return MGEA_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// PENALTY: a row that is not finished also sets its token's bit in its presence bitmap (one thread per row: a plain read-modify-write)
-template <bool PENALTY>
-__global__ void advance_kernel(const int32_t* __restrict__ sampled, StepState s, int B, uint32_t* __restrict__ presence, int V) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int done = s.done[b], tok = sampled[b];
-    end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], done);   // ctx_len + 1: the token fed this step now sits in the cache
-    if constexpr (PENALTY) {
-        if (!done && (unsigned)tok < (unsigned)V) {
-            uint32_t* w = presence + (int64_t)b * presence_words(V) + (tok >> 5);
-            *w = *w | (1u << (tok & 31));
-        }
-    }
-}
-
-int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence, int V) {
-    hipLaunchKernelGGL(presence ? advance_kernel<true> : advance_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, st, sampled, s, B,
-                       presence, V);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// One workgroup per row: the row's bitmap is built in LDS (the prompt may repeat ids, so its bits are OR-ed there), then stored whole --
-// which also clears whatever an earlier generation left in it.
-constexpr int PRESENCE_MAX_WORDS = (MGEA_SAMPLER_MAX_VOCAB + 31) / 32;
-__global__ __launch_bounds__(256) void presence_seed_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, int T, int V,
-                                                            uint32_t* __restrict__ presence) {
-    __shared__ uint32_t bits[PRESENCE_MAX_WORDS];
-    const int b = blockIdx.x, nw = presence_words(V);
-    for (int w = threadIdx.x; w < nw; w += blockDim.x) bits[w] = 0u;
-    __syncthreads();
-    int n = lens ? lens[b] : T;
-    n = n < 0 ? 0 : (n > T ? T : n);
-    for (int t = threadIdx.x; t < n; t += blockDim.x) {
-        const int id = ids[(int64_t)b * T + t];
-        if ((unsigned)id < (unsigned)V) atomicOr(&bits[id >> 5], 1u << (id & 31));
-    }
-    __syncthreads();
-    for (int w = threadIdx.x; w < nw; w += blockDim.x) presence[(int64_t)b * nw + w] = bits[w];
-}
-
-int launch_presence_seed(const int32_t* ids, const int32_t* lens, int B, int T, int V, uint32_t* presence, hipStream_t st) {
-    MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "presence: vocab %d exceeds %d", V, MGEA_SAMPLER_MAX_VOCAB);
-    hipLaunchKernelGGL(presence_seed_kernel, dim3(B), dim3(256), 0, st, ids, lens, T, V, presence);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
 __global__ void add_lens_kernel(int32_t* ctx_len, const int32_t* lens, int T, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) ctx_len[b] += lens ? lens[b] : T;

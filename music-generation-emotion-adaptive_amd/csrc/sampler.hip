@@ -606,97 +606,26 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     else if (tid == 0) ids_out[b] = tok;
 }
 
-int launch_sample(const float* logits, int B, int V, const mgea_sampler_config& s, const SamplerParams* params_dev,
-                  const int32_t* row_step_dev, int64_t step_host, int32_t* ids_out, float* probs_out, hipStream_t st, const TailArgs* tail,
-                  uint32_t* presence, float penalty, const float* bias) {
-    MGEA_REQUIRE(params_dev || s.temperature > 0.f, MGEA_EINVAL, "sampler: temperature must be > 0");
+int launch_sample(const SampleCall& c, hipStream_t st) {
+    const int V = c.V;
+    const TailArgs* tail = c.tail;
+    MGEA_REQUIRE(c.params_dev || c.params.temperature > 0.f, MGEA_EINVAL, "sampler: temperature must be > 0");
     MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "sampler: vocab %d exceeds the register-resident row (%d)", V,
                  MGEA_SAMPLER_MAX_VOCAB);
-    MGEA_REQUIRE(!tail || (ids_out && tail->C % 4 == 0 && tail->C <= 4096), MGEA_EINVAL, "sampler: bad fused-tail arguments");
-    MGEA_REQUIRE(!presence || params_dev || (std::isfinite(penalty) && penalty > 0.f), MGEA_EINVAL,
+    MGEA_REQUIRE(!tail || (c.ids_out && tail->C % 4 == 0 && tail->C <= 4096), MGEA_EINVAL, "sampler: bad fused-tail arguments");
+    MGEA_REQUIRE(!c.presence || c.params_dev || (std::isfinite(c.params.penalty) && c.params.penalty > 0.f), MGEA_EINVAL,
                  "sampler: the repetition penalty must be finite and > 0");
     const TailArgs t = tail ? *tail : TailArgs{};
-    const SamplerParams pv = sampler_params(s, penalty);
     static_assert(SAMP_NT * 56 >= MGEA_SAMPLER_MAX_VOCAB, "the register-resident row must hold the largest vocabulary");
     const bool narrow = V <= SAMP_NT * 36;
-    MGEA_REQUIRE(!bias || params_dev, MGEA_EINVAL, "sampler: a bias needs the rows' device records");
-    auto kern = bias ? (presence ? (narrow ? sample_kernel<36, true, true> : sample_kernel<56, true, true>)
-                                 : (narrow ? sample_kernel<36, false, true> : sample_kernel<56, false, true>))
-                     : (presence ? (narrow ? sample_kernel<36, true, false> : sample_kernel<56, true, false>)
-                                 : (narrow ? sample_kernel<36, false, false> : sample_kernel<56, false, false>));
-    hipLaunchKernelGGL(kern, dim3(B), dim3(SAMP_NT), 0, st, logits, V, pv, params_dev, row_step_dev, step_host, ids_out, probs_out, t,
-                       tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), presence, bias);
+    MGEA_REQUIRE(!c.bias || c.params_dev, MGEA_EINVAL, "sampler: a bias needs the rows' device records");
+    auto kern = c.bias ? (c.presence ? (narrow ? sample_kernel<36, true, true> : sample_kernel<56, true, true>)
+                                     : (narrow ? sample_kernel<36, false, true> : sample_kernel<56, false, true>))
+                       : (c.presence ? (narrow ? sample_kernel<36, true, false> : sample_kernel<56, true, false>)
+                                     : (narrow ? sample_kernel<36, false, false> : sample_kernel<56, false, false>));
+    hipLaunchKernelGGL(kern, dim3(c.B), dim3(SAMP_NT), 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host, c.ids_out,
+                       c.probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), c.presence, c.bias);
     MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// params_dev[0, B) <- v with stream = b, stream-ordered (a kernel argument, so no host buffer has to outlive the call)
-__global__ void fill_sampler_params_kernel(SamplerParams* __restrict__ dst, SamplerParams v, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    v.stream = (uint32_t)b;
-    dst[b] = v;
-}
-
-int launch_fill_sampler_params(SamplerParams* params_dev, const mgea_sampler_config& s, int B, hipStream_t st, float penalty) {
-    hipLaunchKernelGGL(fill_sampler_params_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, params_dev, sampler_params(s, penalty), B);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-__global__ void clamp_budgets_kernel(SamplerParams* __restrict__ p, const int32_t* __restrict__ lens, int T, int B, int reserved) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    int n = lens ? lens[b] : T;
-    n = n < 1 ? 1 : (n > T ? T : n);
-    const int room = reserved - n;   // >= 1: the caller checked T < reserved
-    if (p[b].max_new > room) p[b].max_new = room;
-    p[b].ctx_cap = reserved;
-}
-
-int launch_clamp_budgets(SamplerParams* params_dev, const int32_t* lens, int T, int B, int reserved, hipStream_t st) {
-    MGEA_REQUIRE(T < reserved, MGEA_EINVAL, "budgets: prompt width %d leaves no room in %d tokens", T, reserved);
-    hipLaunchKernelGGL(clamp_budgets_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, params_dev, lens, T, B, reserved);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-__global__ void unpark_rows_kernel(int32_t* __restrict__ done, int32_t* __restrict__ ctx_len, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B && done[b] == 2) {
-        done[b] = 1;
-        ctx_len[b] += 1;
-    }
-}
-
-int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st) {
-    hipLaunchKernelGGL(unpark_rows_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, done, ctx_len, B);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who) {
-    for (int b = 0; b < B; ++b) {
-        const mgea_row_logits& l = lrows[b];
-        MGEA_REQUIRE(l.reserved == 0, MGEA_EINVAL, "%s: row %d: mgea_row_logits.reserved must be 0", who, b);
-        MGEA_REQUIRE(l.min_new_tokens >= 0 && (n_steps < 0 || l.min_new_tokens <= n_steps), MGEA_EINVAL,
-                     "%s: row %d: min_new_tokens %d outside [0, %d]", who, b, l.min_new_tokens, n_steps < 0 ? 0x7fffffff : n_steps);
-    }
-    return MGEA_OK;
-}
-
-int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who) {
-    MGEA_REQUIRE(rows, MGEA_EINVAL, "%s: rows is NULL", who);
-    for (int b = 0; b < B; ++b) {
-        const mgea_row_sampler& r = rows[b];
-        MGEA_REQUIRE(std::isfinite(r.temperature) && r.temperature > 0.f, MGEA_EINVAL, "%s: row %d: temperature must be finite and > 0 (got %g)",
-                     who, b, (double)r.temperature);
-        MGEA_REQUIRE(r.top_k >= 0 && r.top_k <= V, MGEA_EINVAL, "%s: row %d: top_k %d outside [0, %d]", who, b, r.top_k, V);
-        MGEA_REQUIRE(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f, MGEA_EINVAL,
-                     "%s: row %d: repetition_penalty must be finite and > 0 (got %g)", who, b, (double)r.repetition_penalty);
-        MGEA_REQUIRE(n_steps < 0 || (r.max_new_tokens >= 0 && r.max_new_tokens <= n_steps), MGEA_EINVAL,
-                     "%s: row %d: max_new_tokens %d outside [0, %d]", who, b, r.max_new_tokens, n_steps);
-    }
     return MGEA_OK;
 }
 

@@ -1,0 +1,226 @@
+// The end of a decode step, after the LM head: the greedy argmax tails, the bookkeeping kernel behind an unfused sampler launch, the
+// presence bitmaps' seed, and the rows' sampler records (their host checks, the builder, the kernels that fill and clamp them).
+// The sampler itself is sampler.hip; end_row_step / advance_embed_row, which every tail shares, are in common.h.
+#include <cmath>
+
+#include "common.h"
+
+namespace mgea {
+
+// ------------------------------------------------------------------------------------------
+// greedy finalize: argmax over the per-tile partials of each row, then the sampler-loop
+// bookkeeping of api_cache.py:179-181 (append, EOS or budget stop: end_row_step) -- one 64-thread workgroup per row.
+__global__ __launch_bounds__(64) void argmax_advance_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
+                                                           int n_tiles, StepState s, int32_t* __restrict__ sampled) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < n_tiles; i += 64) {
+        const float v = pval[(int64_t)b * n_tiles + i];
+        const int ix = pidx[(int64_t)b * n_tiles + i];
+        if (v > best || (v == best && ix < bi)) { best = v; bi = ix; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) {
+        const int tok = bi == 0x7fffffff ? 0 : bi;
+        sampled[b] = tok;
+        end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], s.done[b]);
+    }
+}
+
+// Same finalize fused with the NEXT step's embedding (generate() keeps x "primed"): one launch less
+// per decode step.  256 threads per row: partial-argmax reduce, bookkeeping by thread 0, then
+// x[row] = tok_emb[token] + pos_emb[pos] (k-tiled) and its LayerNorm partial statistics.
+__global__ __launch_bounds__(256) void argmax_advance_embed_kernel(const float* __restrict__ pval,
+                                                                  const int32_t* __restrict__ pidx, int n_tiles,
+                                                                  TailArgs t, int32_t* __restrict__ sampled) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ float sh[8];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the row's bookkeeping state is requested together with the partials (one round trip instead of two)
+    int st_step = 0, st_fed = 0, st_len = 0, st_done = 0;
+    if (tid == 0) { st_step = t.s.row_step[b]; st_fed = t.s.cur_ids[b]; st_len = t.s.ctx_len[b]; st_done = t.s.done[b]; }
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = tid; i < n_tiles; i += 256) {
+        const float v = pval[(int64_t)b * n_tiles + i];
+        const int ix = pidx[(int64_t)b * n_tiles + i];
+        if (v > best || (v == best && ix < bi)) { best = v; bi = ix; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) { sv[wave] = best; si[wave] = bi; }
+    __syncthreads();
+    int tok = 0;
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+        tok = bi == 0x7fffffff ? 0 : bi;
+    }
+    advance_embed_row(b, tok, t, sampled, st_step, st_fed, st_len, st_done, sh);
+}
+
+int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
+                                const float* tok_emb, const float* pos_emb, float* x, float* stats, int B, int C, int vocab,
+                                int pos_rows, int absolute_pos, hipStream_t st) {
+    MGEA_REQUIRE(B <= MGEA_FUSED_MAX_ROWS && C % 4 == 0 && C <= 4096, MGEA_EINVAL, "argmax+embed: bad shape");
+    TailArgs t{s, tok_emb, pos_emb, x, stats, C, vocab, pos_rows, absolute_pos};
+    hipLaunchKernelGGL(argmax_advance_embed_kernel, dim3(B), dim3(256), 0, st, pval, pidx, n_tiles, t, sampled);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
+                          int B, hipStream_t st) {
+    hipLaunchKernelGGL(argmax_advance_kernel, dim3(B), dim3(64), 0, st, pval, pidx, n_tiles, s, sampled);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// PENALTY: a row that is not finished also sets its token's bit in its presence bitmap (one thread per row: a plain read-modify-write)
+template <bool PENALTY>
+__global__ void advance_kernel(const int32_t* __restrict__ sampled, StepState s, int B, uint32_t* __restrict__ presence, int V) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int done = s.done[b], tok = sampled[b];
+    end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], done);   // ctx_len + 1: the token fed this step now sits in the cache
+    if constexpr (PENALTY) {
+        if (!done && (unsigned)tok < (unsigned)V) {
+            uint32_t* w = presence + (int64_t)b * presence_words(V) + (tok >> 5);
+            *w = *w | (1u << (tok & 31));
+        }
+    }
+}
+
+int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence, int V) {
+    hipLaunchKernelGGL(presence ? advance_kernel<true> : advance_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, st, sampled, s, B,
+                       presence, V);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+// One workgroup per row: the row's bitmap is built in LDS (the prompt may repeat ids, so its bits are OR-ed there), then stored whole --
+// which also clears whatever an earlier generation left in it.
+constexpr int PRESENCE_MAX_WORDS = (MGEA_SAMPLER_MAX_VOCAB + 31) / 32;
+__global__ __launch_bounds__(256) void presence_seed_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, int T, int V,
+                                                            uint32_t* __restrict__ presence) {
+    __shared__ uint32_t bits[PRESENCE_MAX_WORDS];
+    const int b = blockIdx.x, nw = presence_words(V);
+    for (int w = threadIdx.x; w < nw; w += blockDim.x) bits[w] = 0u;
+    __syncthreads();
+    int n = lens ? lens[b] : T;
+    n = n < 0 ? 0 : (n > T ? T : n);
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        const int id = ids[(int64_t)b * T + t];
+        if ((unsigned)id < (unsigned)V) atomicOr(&bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < nw; w += blockDim.x) presence[(int64_t)b * nw + w] = bits[w];
+}
+
+int launch_presence_seed(const int32_t* ids, const int32_t* lens, int B, int T, int V, uint32_t* presence, hipStream_t st) {
+    MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "presence: vocab %d exceeds %d", V, MGEA_SAMPLER_MAX_VOCAB);
+    hipLaunchKernelGGL(presence_seed_kernel, dim3(B), dim3(256), 0, st, ids, lens, T, V, presence);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+// params_dev[0, B) <- v with stream = b, stream-ordered (a kernel argument, so no host buffer has to outlive the call)
+__global__ void fill_sampler_params_kernel(SamplerParams* __restrict__ dst, SamplerParams v, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    v.stream = (uint32_t)b;
+    dst[b] = v;
+}
+
+int launch_fill_sampler_params(SamplerParams* params_dev, const SamplerParams& v, int B, hipStream_t st) {
+    hipLaunchKernelGGL(fill_sampler_params_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, params_dev, v, B);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+__global__ void clamp_budgets_kernel(SamplerParams* __restrict__ p, const int32_t* __restrict__ lens, int T, int B, int reserved) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int n = lens ? lens[b] : T;
+    n = n < 1 ? 1 : (n > T ? T : n);
+    const int room = reserved - n;   // >= 1: the caller checked T < reserved
+    if (p[b].max_new > room) p[b].max_new = room;
+    p[b].ctx_cap = reserved;
+}
+
+int launch_clamp_budgets(SamplerParams* params_dev, const int32_t* lens, int T, int B, int reserved, hipStream_t st) {
+    MGEA_REQUIRE(T < reserved, MGEA_EINVAL, "budgets: prompt width %d leaves no room in %d tokens", T, reserved);
+    hipLaunchKernelGGL(clamp_budgets_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, params_dev, lens, T, B, reserved);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+__global__ void unpark_rows_kernel(int32_t* __restrict__ done, int32_t* __restrict__ ctx_len, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B && done[b] == 2) {
+        done[b] = 1;
+        ctx_len[b] += 1;
+    }
+}
+
+int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st) {
+    hipLaunchKernelGGL(unpark_rows_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, done, ctx_len, B);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who) {
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_logits& l = lrows[b];
+        MGEA_REQUIRE(l.reserved == 0, MGEA_EINVAL, "%s: row %d: mgea_row_logits.reserved must be 0", who, b);
+        MGEA_REQUIRE(l.min_new_tokens >= 0 && (n_steps < 0 || l.min_new_tokens <= n_steps), MGEA_EINVAL,
+                     "%s: row %d: min_new_tokens %d outside [0, %d]", who, b, l.min_new_tokens, n_steps < 0 ? 0x7fffffff : n_steps);
+    }
+    return MGEA_OK;
+}
+
+int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who) {
+    MGEA_REQUIRE(rows, MGEA_EINVAL, "%s: rows is NULL", who);
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_sampler& r = rows[b];
+        MGEA_REQUIRE(std::isfinite(r.temperature) && r.temperature > 0.f, MGEA_EINVAL, "%s: row %d: temperature must be finite and > 0 (got %g)",
+                     who, b, (double)r.temperature);
+        MGEA_REQUIRE(r.top_k >= 0 && r.top_k <= V, MGEA_EINVAL, "%s: row %d: top_k %d outside [0, %d]", who, b, r.top_k, V);
+        MGEA_REQUIRE(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f, MGEA_EINVAL,
+                     "%s: row %d: repetition_penalty must be finite and > 0 (got %g)", who, b, (double)r.repetition_penalty);
+        MGEA_REQUIRE(n_steps < 0 || (r.max_new_tokens >= 0 && r.max_new_tokens <= n_steps), MGEA_EINVAL,
+                     "%s: row %d: max_new_tokens %d outside [0, %d]", who, b, r.max_new_tokens, n_steps);
+    }
+    return MGEA_OK;
+}
+
+// The form: greedy only if every row is, penalized if any row is (p = 1 rows are unchanged by it: x * 1, x / 1 exact), biased if any row
+// has a bias or a min_new_tokens.
+RowRecords build_row_records(const mgea_row_sampler* rows, const mgea_row_logits* lrows, int B, int n_steps, SamplerParams* out) {
+    bool all_greedy = true, pen = false, biased = false, stop = false;
+    for (int b = 0; b < B; ++b) {
+        out[b] = sampler_params(rows[b]);
+        all_greedy = all_greedy && rows[b].top_k == 1;
+        pen = pen || rows[b].repetition_penalty != 1.0f;
+        stop = stop || rows[b].eos_id >= 0 || (rows[b].max_new_tokens > 0 && rows[b].max_new_tokens < n_steps);
+        if (!lrows) continue;
+        out[b].bias_on = lrows[b].bias_dev ? 1 : 0;
+        out[b].min_new = lrows[b].min_new_tokens;
+        biased = biased || lrows[b].bias_dev || lrows[b].min_new_tokens > 0;
+    }
+    return RowRecords{step_form(all_greedy, pen, biased), pen, stop};
+}
+
+}  // namespace mgea
