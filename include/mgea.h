@@ -221,6 +221,33 @@ int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids
                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
                                       int32_t* ids_out_dev, void* stream);
 
+/* mgea_decoder_generate_rows_biased that also says how likely each id was, and may be told ids to take.  Build-defined: the reference
+ * returns no scores (the serving APIs' counterparts are OpenAI's logprobs, HuggingFace's output_scores / compute_transition_scores).
+ * At every decode step of row b, on the raw head logits x of the row:
+ *   0. the raw statistics m = max_i x_i and log sum_i exp(x_i - m), fp32, in a fixed order (deterministic from run to run);
+ *   1.-4. the processing steps of mgea_row_logits: penalty, bias, EOS ban, then / temperature, top-k, top-p, softmax, Philox draw;
+ *   5. f = forced_ids_dev[b * n_steps + t] for the row's step index t (word 1 of its Philox counter): f >= 0 replaces the drawn id
+ *      for everything downstream -- ids_out, EOS and budget bookkeeping, the presence bitmap, the next step's input; -1 leaves the
+ *      draw alone (so does every other negative value).  f >= vocab is clamped to vocab - 1 and sets bit 0 of the sticky error
+ *      flags (mgea_decoder_error_flags);
+ *   6. with id = what the step writes to ids_out:
+ *        logprobs_out[b, t]        = x_id - m - log sum_i exp(x_i - m), natural log, taken over the RAW logits of step 0 -- before
+ *                                    penalty, bias, EOS ban, temperature, top-k and top-p: a function of the model alone;
+ *        choice_logprobs_out[b, t] = log(e_id / total) under the distribution of step 4, the one the draw was made from: -inf for
+ *                                    an id outside the kept set (only a forced id can be), 0 for a greedy row that keeps its argmax.
+ *      A finished row (ids_out -1) has 0.0 in both, as have the steps that never ran.
+ * forced_ids_dev [B, n_steps] int32 (device) or NULL = nothing forced; it is copied into the engine's own buffer in stream order, so
+ * a request with other forced ids replays the cached graph.  choice_logprobs_out_dev may be NULL.  Scoring needs the logits row, so
+ * a scored generation never takes the greedy form: all-greedy rows run as top_k == 1 records of the sampled form (the exact argmax,
+ * ties to the lowest id -- the ids of mgea_decoder_generate_rows).  "Scored" is part of the step-graph key: unscored calls capture
+ * and replay what they always did.  mgea_decoder_stats out[3] counts the scored steps.  Scoring a given continuation under the
+ * model is this call with every step forced (the distribution sample_kvcache draws from exists only inside the step loop: the
+ * prefill is bidirectional, steps add pos_emb[0], the first step re-feeds the last prompt token). */
+int mgea_decoder_generate_rows_scored(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                      const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
+                                      float* choice_logprobs_out_dev, void* stream);
+
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
  * generate applied no penalty (a biased generation keeps the bitmaps too). */
@@ -242,7 +269,8 @@ int mgea_decoder_profile_read(mgea_decoder* h, double* ms_by_class, int64_t* lau
  * captures + instantiations over the handle's lifetime, [4] graphs cached now, [5] forwards that ran on the f16 matrix-core
  * prefill path (MGEA_DTYPE_F16 engines, empty cache, batch * T big enough: csrc/decoder.hip run_prefill16), [6] decode steps
  * of the last generate() that applied a repetition penalty (0 if it applied none), [7] decode steps of the last generate() that
- * applied a logit bias or min_new_tokens (0 if it applied none); others 0. */
+ * applied a logit bias or min_new_tokens (0 if it applied none), [3] decode steps of the last generate() that wrote log-probabilities
+ * (mgea_decoder_generate_rows_scored; 0 otherwise). */
 int mgea_decoder_stats(mgea_decoder* h, int64_t* out /* [8] */);
 
 /* Token ids outside [0, vocab) make nn.Embedding raise IndexError in the reference (api_cache.py:99).
@@ -405,6 +433,15 @@ int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mge
 int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows,
                                const uint32_t* presence_dev, const mgea_row_logits* logits_rows, int64_t step, int32_t* ids_out_dev,
                                float* probs_out_dev, void* stream);
+/* mgea_op_sample_rows_biased as the scored sampler of mgea_decoder_generate_rows_scored runs it (same order of the processing steps,
+ * the two values taken at the same places): forced_ids_dev [B] int32 (device) or NULL -- row b takes forced_ids_dev[b] when it is
+ * >= 0 (any negative value: the draw decides; >= V: clamped to V - 1 SILENTLY -- this call has no error flags to set, unlike the
+ * engine's); logprobs_out_dev [B] = the raw log-probability of ids_out[b], choice_logprobs_out_dev [B] (or NULL)
+ * = its log-probability under the distribution in probs_out.  ids_out_dev and logprobs_out_dev are required. */
+int mgea_op_sample_rows_scored(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows,
+                               const uint32_t* presence_dev, const mgea_row_logits* logits_rows, int64_t step, int32_t* ids_out_dev,
+                               float* probs_out_dev, const int32_t* forced_ids_dev, float* logprobs_out_dev,
+                               float* choice_logprobs_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -45,8 +45,21 @@ def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int
                       constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens)
 
 
+def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                       best_of: int = 4, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
+    """create_constrained_app whose requests draw best_of candidates in one batch and return the most likely one
+    (generate_music.generate.generate_best_of: highest mean raw log-probability per generated token).  best_of is capped by the
+    model's max_batch (ValueError here beyond it).  The response adds X-Best-Of and, when anything was generated, X-Mean-Logprob.  Build-defined: the reference
+    draws one sequence per request."""
+    best_of = int(best_of)
+    if best_of < 1 or best_of > int(model.max_batch):
+        raise ValueError(f"best_of {best_of} outside [1, max_batch={model.max_batch}]")
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, best_of=best_of)
+
+
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
-               out_of_scale_bias=float("-inf"), min_new_tokens=0):
+               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     if constrain not in CONSTRAINTS:
@@ -107,7 +120,14 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
         if constrain is not None:
             extra["X-Constraint"] = constrain
         more = {} if bias is None and not min_new_tokens else dict(logit_bias=bias, min_new_tokens=int(min_new_tokens))
-        if app.state.batcher is not None:   # the same request, served inside whatever batch is forming
+        if best_of:   # best_of candidates of the same request in one batch, the most likely one kept
+            tokens, _, means, best = gen.generate_best_of(model, gen_prompt, best_of, max_len=seq_len, temperature=temperature,
+                                                          top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                                                          logit_bias=bias, min_new_tokens=int(min_new_tokens), return_all=True)
+            extra["X-Best-Of"] = str(best_of)
+            if means[best] > float("-inf"):   # (nothing generated -- seq_len within the prompt -- has no mean)
+                extra["X-Mean-Logprob"] = f"{means[best]:.6f}"
+        elif app.state.batcher is not None:   # the same request, served inside whatever batch is forming
             fut = app.state.batcher.submit(gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                            repetition_penalty=repetition_penalty, **more)
             tokens = fut.result()

@@ -101,6 +101,11 @@ static SampleCall op_sample_call(const float* logits_dev, int B, int V, int64_t 
     return c;
 }
 
+// mgea_op_sample_rows(_biased, _scored): the rows' records and bias vectors to device memory, one sampler launch (defined at the end)
+static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                          const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev, float* probs_out_dev, const ScoreArgs& score,
+                          void* stream);
+
 extern "C" {
 
 const char* mgea_last_error(void) { return get_error(); }
@@ -285,6 +290,24 @@ int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mge
 int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows,
                                const uint32_t* presence_dev, const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev,
                                float* probs_out_dev, void* stream) {
+    return op_sample_rows(logits_dev, B, V, rows, presence_dev, lrows, step, ids_out_dev, probs_out_dev, ScoreArgs{}, stream);
+}
+
+int mgea_op_sample_rows_scored(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows,
+                               const uint32_t* presence_dev, const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev,
+                               float* probs_out_dev, const int32_t* forced_ids_dev, float* logprobs_out_dev,
+                               float* choice_logprobs_out_dev, void* stream) {
+    MGEA_REQUIRE(ids_out_dev && logprobs_out_dev, MGEA_EINVAL, "op_sample_rows_scored: ids_out_dev or logprobs_out_dev is NULL");
+    // forced [B] (stride 0), the values to [B] vectors, no error flag here: a forced id >= V is clamped silently
+    return op_sample_rows(logits_dev, B, V, rows, presence_dev, lrows, step, ids_out_dev, probs_out_dev,
+                          ScoreArgs{forced_ids_dev, 0, logprobs_out_dev, choice_logprobs_out_dev, 0, nullptr}, stream);
+}
+
+}  // extern "C"
+
+static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                          const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev, float* probs_out_dev, const ScoreArgs& score,
+                          void* stream) {
     MGEA_REQUIRE(logits_dev && rows && B > 0, MGEA_EINVAL, "op_sample_rows: NULL argument or empty batch");
     MGEA_TRY(check_row_samplers(rows, B, V, -1, "op_sample_rows"));
     if (lrows) MGEA_TRY(check_row_logits(lrows, B, -1, "op_sample_rows"));
@@ -305,6 +328,7 @@ int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, co
     c.params_dev = rec_dev;   // every scalar comes from the records
     c.presence = rr.any_penalty ? const_cast<uint32_t*>(presence_dev) : nullptr;   // (a bias alone needs no bitmap here: nothing is written)
     c.bias = bias_dev;
+    c.score = score;
     int rc = MGEA_EHIP;
     bool copied = hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st) == hipSuccess;
     for (int b = 0; biased && copied && b < B; ++b)
@@ -322,5 +346,3 @@ int mgea_op_sample_rows_biased(const float* logits_dev, int32_t B, int32_t V, co
     MGEA_CHECK_HIP(e);
     return MGEA_OK;
 }
-
-}  // extern "C"

@@ -258,6 +258,18 @@ struct TailArgs {
     float* x; float* stats;     // k-tiled residual stream and its LayerNorm partials (fused decode path)
     int C, vocab, pos_rows, absolute_pos;
 };
+// What the scored sampler reads and writes besides the draw (sampler.hip, sample_kernel<..., ScoreArgs>).
+// forced: ids the rows must take, -1 = the draw decides -- forced[b] when forced_stride == 0, else forced[b * forced_stride + step] for
+// the row's step index (steps at or beyond the stride are free); NULL: nothing is forced.
+// logprob / choice (choice may be NULL): with a fused tail the histories [B][out_stride], filed at the row's step; without one [B].
+// err_flag (or NULL): bit 0 is set when a forced id >= vocab was clamped.
+struct ScoreArgs {
+    const int32_t* forced; int forced_stride;
+    float* logprob; float* choice; int out_stride;
+    int32_t* err_flag;
+};
+// The unfused path's second half: advance_kernel files the sampler's per-step values at the row's step (0 for a finished row).
+struct ScoreFile { const float* logprob_step; const float* choice_step; float* logprob_hist; float* choice_hist; int stride; };
 // One sampler launch over logits [B, V] (sampler.hip); every optional part is a named field, NULL = absent.
 struct SampleCall {
     const float* logits; int B, V;
@@ -273,6 +285,8 @@ struct SampleCall {
     // x / p; a fused tail then adds the row's new token to the bitmap.  BIAS form (records only): after the penalty, row b adds
     // bias[b * V + i] to logit i if its record has bias_on, and bans its eos_id while its step index is below the record's min_new
     uint32_t* presence; const float* bias;
+    // scored form (score.logprob != NULL): the raw and the choice log-probability of the id the row takes, and forced ids (ScoreArgs)
+    ScoreArgs score;
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
 // ---- the kernels that end a step, and the rows' records (step_tail.hip) ----
@@ -291,7 +305,9 @@ int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st);
 // after ids for this step are in `sampled` [B]: apply EOS/done logic, write ids_out[b, step],
 // cur_ids, ctx_len += 1, row_step += 1; presence != NULL (bitmap of presence_words(V) words per row): also set the bit of the
 // token of every row that was not finished yet
-int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence = nullptr, int V = 0);
+// score != NULL: also file the step's log-probabilities (ScoreFile)
+int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence = nullptr, int V = 0,
+                   const ScoreFile* score = nullptr);
 // presence rows [0, B) <- the set of the real tokens of ids [B, T] (lens: first lens[b] of row b, NULL: all T; ids outside [0, V) skipped)
 int launch_presence_seed(const int32_t* ids, const int32_t* lens, int B, int T, int V, uint32_t* presence, hipStream_t st);
 // ctx_len[b] += (lens ? lens[b] : T)

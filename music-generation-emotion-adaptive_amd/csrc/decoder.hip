@@ -103,11 +103,11 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, StepForm, steps): one per launch sequence.  Everything a step reads besides its
+    // Captured decode-step graphs, one per (batch, StepForm, scored, steps): one per launch sequence.  Everything a step reads besides its
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
-    struct GraphEntry { int batch; StepForm form; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
+    struct GraphEntry { int batch; StepForm form; bool scored; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
     std::vector<GraphEntry> graphs;
     uint64_t use_clock = 0;
     SamplerParams* samp_dev = nullptr;     // [max_batch] records, one per row (common.h)
@@ -120,6 +120,12 @@ struct mgea_decoder {
     // logit bias: [max_batch][vocab] fp32, row b = the vector row b adds to its logits when its record has bias_on.  A biased generate()
     // copies the rows' vectors here in stream order, so the captured graphs hold this pointer whatever the request's values.
     float* bias = nullptr;
+    // scored generations (mgea_decoder_generate_rows_scored): forced [max_batch][ids_hist_stride] holds the ids the rows must take (-1 =
+    // free), copied from the caller's matrix in stream order; lp_hist / ch_hist, next to ids_hist and with its stride, receive the raw and
+    // the choice log-probability of every step; lp_step / ch_step [max_batch] carry one step's values from the sampler to advance_kernel
+    // on the unfused path.  Engine-owned, so the scored graphs hold stable pointers whatever the request forces.
+    int32_t* forced = nullptr;
+    float *lp_hist = nullptr, *ch_hist = nullptr, *lp_step = nullptr, *ch_step = nullptr;
     int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped)
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     int64_t counters[8] = {0};
@@ -454,6 +460,7 @@ struct StepCall {
     const SamplerParams* pd; SamplerParams pv;
     float* logits_out;   // optional
     bool primed;
+    bool scored = false;   // the scored sampler (never with the GREEDY form: scoring needs the logits row)
     // where the head writes the logits row: the caller's buffer, the engine's `own` for the sampler, nowhere for the argmax tails
     float* head_out(float* own) const { return logits_out ? logits_out : (form == StepForm::GREEDY ? nullptr : own); }
 };
@@ -468,6 +475,7 @@ int enqueue_tail(mgea_decoder* h, const Bufs& u, const StepCall& k, const float*
     const StepState s{u.cur_ids, u.ctx_len, u.done, u.row_step, h->n_done, u.ids_hist, h->ids_hist_stride, k.pv.eos_id, k.pd};
     const TailArgs t{s, h->w(T_TOK), h->w(T_POS), u.x, u.stats, C, V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
     if (k.form == StepForm::GREEDY) {
+        MGEA_REQUIRE(!k.scored, MGEA_EINVAL, "internal: a scored step never takes the greedy form");
         if (k.primed)
             PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, n_partials, s, u.sampled, t.tok_emb, t.pos_emb, t.x,
                                                         t.stats, B, C, V, t.pos_rows, t.absolute_pos, st));
@@ -483,8 +491,12 @@ int enqueue_tail(mgea_decoder* h, const Bufs& u, const StepCall& k, const float*
     sc.params_dev = k.pd; sc.params = k.pv; sc.row_step_dev = u.row_step;
     sc.ids_out = u.sampled; sc.tail = k.primed ? &t : nullptr;
     sc.presence = pres; sc.bias = k.form == StepForm::BIASED ? h->bias : nullptr;
+    const int hs = h->ids_hist_stride;
+    if (k.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
+        sc.score = ScoreArgs{h->forced, hs, k.primed ? h->lp_hist : h->lp_step, k.primed ? h->ch_hist : h->ch_step, hs, h->err_flag};
     PROF(PC_SAMPLE, launch_sample(sc, st));
-    if (!k.primed) PROF(PC_ROWOP, launch_advance(u.sampled, s, B, st, pres, V));
+    const ScoreFile sf{h->lp_step, h->ch_step, h->lp_hist, h->ch_hist, hs};
+    if (!k.primed) PROF(PC_ROWOP, launch_advance(u.sampled, s, B, st, pres, V, k.scored ? &sf : nullptr));
     return MGEA_OK;
 }
 
@@ -524,8 +536,8 @@ int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
 }
 
 // The decode step of generate(): the rows' device records; x arrives primed on the fused path.
-int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, hipStream_t st) {
-    return enqueue_step(h, StepCall{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B)}, st);
+int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st) {
+    return enqueue_step(h, StepCall{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored}, st);
 }
 
 // embedding (+ LN statistics) of cur_ids into the buffers the next generate() step will read
@@ -537,14 +549,14 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
-// The captured decode step for (B, form, steps): from the cache, or captured + instantiated now (least recently used
+// The captured decode step for (B, form, scored, steps): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond MAX_GRAPHS).
-constexpr size_t MAX_GRAPHS = 16;   // two per (batch, form): the single step and the 8-step graph -- 4 forms x 2 = 8 for one batch size
+constexpr size_t MAX_GRAPHS = 28;   // two per (batch, form, scored): the single step and the 8-step graph -- (4 forms + 3 scored) x 2 = 14 for one batch size, two batch sizes whole
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, StepForm form, hipStream_t st, hipGraphExec_t* out, int steps) {
+int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps) {
     for (auto& g : h->graphs)
-        if (g.batch == B && g.form == form && g.steps == steps) {
+        if (g.batch == B && g.form == form && g.scored == scored && g.steps == steps) {
             g.last_use = ++h->use_clock;
             if (steps == 1) h->counters[0] = g.nodes;
             *out = g.exec;
@@ -561,7 +573,7 @@ int step_graph(mgea_decoder* h, int B, StepForm form, hipStream_t st, hipGraphEx
     }
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, st);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -577,7 +589,7 @@ int step_graph(mgea_decoder* h, int B, StepForm form, hipStream_t st, hipGraphEx
     }
     size_t nn = 0;
     (void)hipGraphGetNodes(g, nullptr, &nn);
-    h->graphs.push_back({B, form, steps, g, ex, (int64_t)nn, ++h->use_clock});
+    h->graphs.push_back({B, form, scored, steps, g, ex, (int64_t)nn, ++h->use_clock});
     if (steps == 1) h->counters[0] = (int64_t)nn;
     h->counters[2] += 1;   // lifetime captures + instantiations
     h->counters[4] = (int64_t)h->graphs.size();
@@ -958,6 +970,13 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     // (last of the state buffers: the ones above keep the places they had before this buffer existed)
     if (hipMalloc((void**)&h->bias, (size_t)cfg->max_batch * cfg->vocab * sizeof(float)) != hipSuccess)
         return fail(MGEA_ENOMEM, "state allocation failed");
+    const size_t nhist = (size_t)cfg->max_batch * h->ids_hist_stride;
+    if (hipMalloc((void**)&h->forced, nhist * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&h->lp_hist, nhist * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&h->ch_hist, nhist * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&h->lp_step, cfg->max_batch * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&h->ch_step, cfg->max_batch * sizeof(float)) != hipSuccess)
+        return fail(MGEA_ENOMEM, "state allocation failed");
+    (void)hipMemset(h->forced, 0xff, nhist * sizeof(int32_t));
     (void)hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t));
     (void)hipMemset(h->page_table, 0, nb * h->max_pages);
     (void)hipMemset(h->ctx_len, 0, nb);
@@ -998,7 +1017,7 @@ int mgea_decoder_destroy(mgea_decoder* h) {
     free_ws(h);
     free_p16(h);
     void* p[] = {h->kv.base, h->page_table, h->ctx_len, h->cur_ids, h->done, h->row_step, h->n_done, h->sampled, h->ids_hist, h->wt, h->lnv,
-                 h->samp_dev, h->err_flag, h->presence, h->bias, h->arena_own, h->attn_split.part, h->attn_split.count};
+                 h->samp_dev, h->err_flag, h->presence, h->bias, h->forced, h->lp_hist, h->ch_hist, h->lp_step, h->ch_step, h->arena_own, h->attn_split.part, h->attn_split.count};
     for (void* q : p)
         if (q) (void)hipFree(q);
     if (h->samp_stage) (void)hipHostFree(h->samp_stage);
@@ -1047,9 +1066,11 @@ namespace {
 // (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
 // are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  Which of the
 // four launch sequences the steps take: StepForm (common.h).
+// score (with rows only) or NULL: the scored form -- forced ids in, log-probabilities out (mgea_decoder_generate_rows_scored).
+struct ScoreIo { const int32_t* forced_dev; float* logprobs_out; float* choice_out; };
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
                 const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
-                int32_t* ids_out_dev, hipStream_t st) {
+                int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr) {
     const auto& c = h->cfg;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
@@ -1072,9 +1093,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
         rr = RowRecords{step_form(s->top_k == 1, penalty != 1.0f, false), penalty != 1.0f, s->eos_id >= 0};
     }
-    const StepForm form = rr.form;
+    const bool scored = score != nullptr;
+    // scoring needs the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to the lowest id)
+    const StepForm form = scored && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
     const bool biased = form == StepForm::BIASED;
     h->last_penalized = false;
+    h->counters[3] = 0;
     h->counters[6] = 0;
     h->counters[7] = 0;
     MGEA_TRY(do_reset(h, B, reserve, st));
@@ -1098,12 +1122,19 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     } else {
         MGEA_TRY(launch_fill_sampler_params(h->samp_dev, sampler_params(*s, penalty), B, st));
     }
+    if (scored) {   // the engine's forced-id rows: -1 everywhere, then the caller's [B, n_steps] matrix (steps beyond it stay free)
+        const size_t hs = (size_t)h->ids_hist_stride;
+        MGEA_CHECK_HIP(hipMemsetAsync(h->forced, 0xff, (size_t)B * hs * sizeof(int32_t), st));
+        if (score->forced_dev)
+            MGEA_CHECK_HIP(hipMemcpy2DAsync(h->forced, hs * sizeof(int32_t), score->forced_dev, (size_t)n_steps * sizeof(int32_t),
+                                            (size_t)n_steps * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
+    }
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, st, &gexec, 1));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, st, &gexec_k, K));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1111,12 +1142,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, st);
+            const int rc = enqueue_gen_step(h, B, form, scored, st);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, st));
+            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1136,6 +1167,17 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->counters[1] = launched;
     h->counters[6] = rr.any_penalty ? launched : 0;
     h->counters[7] = biased ? launched : 0;
+    h->counters[3] = scored ? launched : 0;
+    if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
+        float* outs[2] = {score->logprobs_out, score->choice_out};
+        const float* hist[2] = {h->lp_hist, h->ch_hist};
+        for (int i = 0; i < 2; ++i) {
+            if (!outs[i]) continue;
+            MGEA_CHECK_HIP(hipMemsetAsync(outs[i], 0, (size_t)B * n_steps * sizeof(float), st));
+            MGEA_CHECK_HIP(hipMemcpy2DAsync(outs[i], (size_t)n_steps * sizeof(float), hist[i], (size_t)h->ids_hist_stride * sizeof(float),
+                                            (size_t)launched * sizeof(float), B, hipMemcpyDeviceToDevice, st));
+        }
+    }
     // rows: ids_hist[b, 0:launched]; steps never run are -1
     MGEA_CHECK_HIP(hipMemsetAsync(ids_out_dev, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));
     MGEA_CHECK_HIP(hipMemcpy2DAsync(ids_out_dev, (size_t)n_steps * sizeof(int32_t), h->ids_hist,
@@ -1185,6 +1227,20 @@ int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids
     MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream);
+}
+
+int mgea_decoder_generate_rows_scored(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                      const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
+                                      float* choice_logprobs_out_dev, void* stream) {
+    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev && logprobs_out_dev, MGEA_EINVAL, "decoder_generate_rows_scored: NULL argument");
+    if (logits_rows) {
+        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_scored: empty batch");
+        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_scored"));
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream, &io);
 }
 
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream) {

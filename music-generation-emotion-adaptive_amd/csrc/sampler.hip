@@ -298,6 +298,14 @@ __device__ __forceinline__ uint32_t wave_mass_boundary(const uint32_t (&key)[R],
     return prefix > floor_key ? prefix : floor_key;
 }
 
+// the scored form's three LDS words: the raw row's maximum, the log of its exp-sum, the final id's mass
+__device__ __forceinline__ float* score_lds() {
+    __shared__ float s[3];
+    return s;
+}
+__device__ __forceinline__ ScoreArgs score_args() { return ScoreArgs{}; }
+__device__ __forceinline__ ScoreArgs score_args(const ScoreArgs& a) { return a; }
+
 __device__ __forceinline__ float funkey(uint32_t k) {   // inverse of fkey
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
@@ -306,13 +314,27 @@ __device__ __forceinline__ float funkey(uint32_t k) {   // inverse of fkey
 // read from memory once, in one batch of loads, and never goes through LDS.
 // PENALTY: presence = the rows' bitmaps (presence_words(V) words per row), updated by the fused tail; unused otherwise.
 // BIAS: bias = the rows' bias vectors (V floats per row, row b at b * V), read by the rows whose record has bias_on; unused otherwise.
-template <int MAXE, bool PENALTY, bool BIAS>
+// SCORED (the instantiations with a ScoreArgs argument; the others are the kernel as it was): the row also reports how likely its id
+// was, and may be told its id (ScoreArgs, common.h).
+//   * raw log-probability: x_id - m - log sum_i exp(x_i - m) over the RAW row, m = its maximum -- reduced right after the load, before
+//     the penalty touches the registers (no second copy of the row); fixed reduction order, fp32; x_id is re-read from the row at the end.
+//   * choice log-probability: log(e_id / total) of the final distribution, -inf for an id outside the kept set (a forced one).
+//   * forced id: requested at kernel start, consumed after the draw; >= 0 replaces the drawn id for everything downstream (>= V: clamped,
+//     bit 0 of the error flag).
+// With a fused tail both values are filed at the row's step in the histories, after the next step's embedding is on its way; a row that
+// was already finished files 0.  Without one they go to [B] vectors (advance_kernel files them).
+template <int MAXE, bool PENALTY, bool BIAS, typename... Score>
 __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict__ logits, int V, SamplerParams pv,
                                                     const SamplerParams* __restrict__ pd,
                                                     const int32_t* __restrict__ row_step, int64_t step_host,
                                                     int32_t* __restrict__ ids_out, float* __restrict__ probs_out,
                                                     TailArgs tail, int fuse_tail, int wave_select, uint32_t* __restrict__ presence,
-                                                    const float* __restrict__ bias) {
+                                                    const float* __restrict__ bias, Score... score) {
+    // the scored form is this kernel with one more argument, a ScoreArgs: with the empty pack the argument list, and with every scored
+    // part under `if constexpr`, the code, are those of the kernel before there was a scored form
+    constexpr bool SCORED = sizeof...(Score) == 1;
+    static_assert(sizeof...(Score) <= 1, "at most one ScoreArgs");
+    [[maybe_unused]] const ScoreArgs sc = score_args(score...);
     constexpr int NT = SAMP_NT, NW = SAMP_NW;
     static_assert(SAMP_KFAST == 64, "wave_publish_ge fills one slot per lane");
     __shared__ unsigned long long red64[2 * NW];
@@ -334,6 +356,14 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     int st_step = 0, st_fed = 0, st_len = 0, st_done = 0;   // the row's loop state, for the fused tail
     if (fuse_tail && tid == 0) {
         st_step = tail.s.row_step[b]; st_fed = tail.s.cur_ids[b]; st_len = tail.s.ctx_len[b]; st_done = tail.s.done[b];
+    }
+    [[maybe_unused]] int forced = -1;   // SCORED: the id this step must take (< 0: the draw decides)
+    if constexpr (SCORED) {
+        if (sc.forced) {
+            const int step = row_step ? row_step[b] : (int32_t)step_host;
+            if (sc.forced_stride == 0) forced = sc.forced[b];
+            else if (step >= 0 && step < sc.forced_stride) forced = sc.forced[(int64_t)b * sc.forced_stride + step];
+        }
     }
     // the whole row is requested at once (a rolled loop pays one ~1 us round trip per pass: the row was just
     // written by the head kernel and sits in another XCD's L2 / the Infinity Cache)
@@ -358,6 +388,30 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
                 bz[j] = i < V ? br[i] : 0.f;
             }
         }
+    }
+    if constexpr (SCORED) {
+        // the raw row's maximum and log-sum-exp, while x still holds what the head wrote; kept in LDS for thread 0's use at the end
+        __shared__ float s_rawm[NW], s_raws[NW];
+        float m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < MAXE; ++j) m = fmaxf(m, x[j]);
+        m = wave_max(m);
+        if ((tid & 63) == 0) s_rawm[tid >> 6] = m;
+        __syncthreads();
+        m = s_rawm[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) m = fmaxf(m, s_rawm[w]);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < MAXE; ++j) s += __expf(x[j] - m);   // the padding beyond V is -inf: exactly 0
+        s = wave_sum(s);
+        if ((tid & 63) == 0) s_raws[tid >> 6] = s;
+        __syncthreads();
+        if (tid == 0) {
+            score_lds()[0] = m;
+            score_lds()[1] = logf((s_raws[0] + s_raws[1]) + (s_raws[2] + s_raws[3]));   // fixed order: deterministic
+        }
+        static_assert(NW == 4, "the log-sum merges four wave sums");
     }
     if constexpr (PENALTY) {
         __shared__ uint32_t s_pres[MAXE * NT / 32];
@@ -602,6 +656,45 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     }
     __syncthreads();
     const int tok = s_choice >= 0 ? s_choice : 0;
+    if constexpr (SCORED) {
+        int tk = tok;
+        float x_id = 0.f;
+        float* s_sc = score_lds();
+        if (forced >= 0) {
+            if (forced >= V) {
+                forced = V - 1;
+                if (tid == 0 && sc.err_flag) atomicOr(sc.err_flag, 1);
+            }
+            tk = forced;
+        }
+        if (tid == (tk & (NT - 1))) {   // the owner of logit tok has its mass in the final distribution (0: not kept)
+            const int jj = tk / NT;
+            float ev = 0.f;
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) ev = j == jj ? e[j] : ev;
+            s_sc[2] = ev;
+        }
+        if (tid == 0) x_id = lg[tk];   // an L2 hit; in flight under the tail
+        if (!fuse_tail) __syncthreads();   // (the fused tail has barriers of its own before thread 0 reads the mass)
+        if (fuse_tail) advance_embed_row<PENALTY>(b, tk, tail, ids_out, st_step, st_fed, st_len, st_done, sh_tail, presence);
+        else if (tid == 0) ids_out[b] = tk;
+        if (tid == 0) {
+            float lp = x_id - s_sc[0] - s_sc[1];
+            float ch = s_sc[2] > 0.f ? logf(s_sc[2] / total) : -INFINITY;
+            int64_t at = b;
+            bool file = true;
+            if (fuse_tail) {
+                if (st_done) lp = ch = 0.f;
+                at = (int64_t)b * sc.out_stride + st_step;
+                file = st_step < sc.out_stride;
+            }
+            if (file) {
+                sc.logprob[at] = lp;
+                if (sc.choice) sc.choice[at] = ch;
+            }
+        }
+        return;
+    }
     if (fuse_tail) advance_embed_row<PENALTY>(b, tok, tail, ids_out, st_step, st_fed, st_len, st_done, sh_tail, presence);   // writes ids_out[b] too
     else if (tid == 0) ids_out[b] = tok;
 }
@@ -623,6 +716,18 @@ int launch_sample(const SampleCall& c, hipStream_t st) {
                                      : (narrow ? sample_kernel<36, false, true> : sample_kernel<56, false, true>))
                        : (c.presence ? (narrow ? sample_kernel<36, true, false> : sample_kernel<56, true, false>)
                                      : (narrow ? sample_kernel<36, false, false> : sample_kernel<56, false, false>));
+    if (c.score.logprob) {
+        MGEA_REQUIRE(c.ids_out, MGEA_EINVAL, "sampler: a scored launch draws ids");
+        auto skern = c.bias ? (c.presence ? (narrow ? sample_kernel<36, true, true, ScoreArgs> : sample_kernel<56, true, true, ScoreArgs>)
+                                          : (narrow ? sample_kernel<36, false, true, ScoreArgs> : sample_kernel<56, false, true, ScoreArgs>))
+                            : (c.presence ? (narrow ? sample_kernel<36, true, false, ScoreArgs> : sample_kernel<56, true, false, ScoreArgs>)
+                                          : (narrow ? sample_kernel<36, false, false, ScoreArgs> : sample_kernel<56, false, false, ScoreArgs>));
+        hipLaunchKernelGGL(skern, dim3(c.B), dim3(SAMP_NT), 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host,
+                           c.ids_out, c.probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), c.presence, c.bias, c.score);
+        MGEA_CHECK_HIP(hipGetLastError());
+        return MGEA_OK;
+    }
+    MGEA_REQUIRE(!c.score.forced, MGEA_EINVAL, "sampler: forced ids need the scored form");
     hipLaunchKernelGGL(kern, dim3(c.B), dim3(SAMP_NT), 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host, c.ids_out,
                        c.probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), c.presence, c.bias);
     MGEA_CHECK_HIP(hipGetLastError());

@@ -90,20 +90,50 @@ int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, c
 // ------------------------------------------------------------------------------------------
 // PENALTY: a row that is not finished also sets its token's bit in its presence bitmap (one thread per row: a plain read-modify-write)
 template <bool PENALTY>
-__global__ void advance_kernel(const int32_t* __restrict__ sampled, StepState s, int B, uint32_t* __restrict__ presence, int V) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int done = s.done[b], tok = sampled[b];
-    end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], done);   // ctx_len + 1: the token fed this step now sits in the cache
+__device__ __forceinline__ void advance_row(int b, const int32_t* __restrict__ sampled, const StepState& s, uint32_t* __restrict__ presence,
+                                            int V, int* step_out, int* done_out) {
+    const int done = s.done[b], tok = sampled[b], step = s.row_step[b];
+    end_row_step(s, b, tok, step, s.cur_ids[b], s.ctx_len[b], done);   // ctx_len + 1: the token fed this step now sits in the cache
     if constexpr (PENALTY) {
         if (!done && (unsigned)tok < (unsigned)V) {
             uint32_t* w = presence + (int64_t)b * presence_words(V) + (tok >> 5);
             *w = *w | (1u << (tok & 31));
         }
     }
+    *step_out = step;
+    *done_out = done;
 }
 
-int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence, int V) {
+template <bool PENALTY>
+__global__ void advance_kernel(const int32_t* __restrict__ sampled, StepState s, int B, uint32_t* __restrict__ presence, int V) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int step, done;
+    advance_row<PENALTY>(b, sampled, s, presence, V, &step, &done);
+}
+
+// the same behind a scored sampler launch: the step's two log-probabilities go to the histories at the row's step, 0 for a row that was
+// already finished (as the fused tail files them)
+template <bool PENALTY>
+__global__ void advance_scored_kernel(const int32_t* __restrict__ sampled, StepState s, int B, uint32_t* __restrict__ presence, int V,
+                                      ScoreFile f) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int step, done;
+    advance_row<PENALTY>(b, sampled, s, presence, V, &step, &done);
+    if (step < f.stride) {
+        f.logprob_hist[(int64_t)b * f.stride + step] = done ? 0.f : f.logprob_step[b];
+        f.choice_hist[(int64_t)b * f.stride + step] = done ? 0.f : f.choice_step[b];
+    }
+}
+
+int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_t st, uint32_t* presence, int V, const ScoreFile* score) {
+    if (score) {
+        hipLaunchKernelGGL(presence ? advance_scored_kernel<true> : advance_scored_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, st,
+                           sampled, s, B, presence, V, *score);
+        MGEA_CHECK_HIP(hipGetLastError());
+        return MGEA_OK;
+    }
     hipLaunchKernelGGL(presence ? advance_kernel<true> : advance_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, st, sampled, s, B,
                        presence, V);
     MGEA_CHECK_HIP(hipGetLastError());

@@ -29,7 +29,8 @@ from mgea.decoder import DecoderEngine, RowSampling, geometry_from_state_dict, r
 __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab", "encode", "decode",
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
            "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
-           "generate_batch_biased", "generate_sequence_biased"]
+           "generate_batch_biased", "generate_sequence_biased", "score_sequence", "generate_best_of", "pick_best",
+           "mean_logprobs"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
 tok2id: Dict[str, int] = {}
@@ -278,6 +279,74 @@ def generate_batch_biased(model, prompts: Sequence[Sequence[str]], max_len=512, 
                            eos_id=eos, seed=_draw_seed() if seed is None else seed,
                            repetition_penalty=repetition_penalty).cpu().tolist()
     return [[id2tok[i] for i in p + [g for g in row if g >= 0]] for p, row in zip(ids, out)]
+
+
+def score_sequence(model, prompt_tokens: Sequence[str], continuation_tokens: Sequence[str]) -> List[float]:
+    """The log-probability (natural log, raw head logits: no temperature, no top-k) of every token of continuation_tokens as
+    sample_kvcache would come to it after prompt_tokens: a teacher-forced run of the decode steps (DecoderEngine.score).
+    Build-defined -- the reference returns no scores.  sum() of the result is the continuation's log-likelihood, exp(-mean) its
+    perplexity."""
+    eng = _as_model(model)._need()
+    ids = [tok2id[t] for t in prompt_tokens]          # KeyError for an unknown token, like api_cache.py:162
+    cont = [tok2id[t] for t in continuation_tokens]
+    if not cont:
+        return []
+    if len(ids) + len(cont) > eng.max_ctx:
+        raise RuntimeError(f"prompt + continuation = {len(ids) + len(cont)} tokens exceed the engine's reserved context {eng.max_ctx}")
+    lp, _ = eng.score([ids], [cont])
+    return [float(v) for v in lp[0].cpu().tolist()]
+
+
+def mean_logprobs(ids, logprobs) -> List[float]:
+    """Per candidate row: the mean raw log-probability over the ids the row produced (ids >= 0); -inf for a row that produced none.
+    ids, logprobs: [n, steps] as nested lists or arrays on the host."""
+    out = []
+    for row_ids, row_lp in zip(ids, logprobs):
+        kept = [float(v) for i, v in zip(row_ids, row_lp) if int(i) >= 0]
+        out.append(sum(kept) / len(kept) if kept else float("-inf"))
+    return out
+
+
+def pick_best(ids, logprobs) -> int:
+    """The candidate generate_best_of keeps: the row with the highest mean_logprobs, ties to the lowest index.  Pure host code."""
+    means = mean_logprobs(ids, logprobs)
+    best = 0
+    for i, m in enumerate(means):
+        if m > means[best]:
+            best = i
+    return best
+
+
+def generate_best_of(model, prompt: Sequence[str], n: int, max_len=512, temperature=1.0, top_k=50, top_p: Optional[float] = None,
+                     seed: Optional[int] = None, repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0,
+                     return_all: bool = False):
+    """sample_kvcache_biased n times in ONE batch, keeping the most likely candidate: the n rows share the prompt, the settings and
+    the seed and draw from Philox streams 0 .. n - 1 (row 0 is the sample_kvcache run of that seed); the one with the highest mean
+    raw log-probability per generated token (pick_best) is returned as prompt + generated tokens.  n is capped by the model's
+    max_batch (ValueError beyond it).  return_all=True returns (tokens, candidates, means, best): every candidate's tokens, their
+    mean log-probabilities and the index kept.  Build-defined: the reference draws one sequence and returns no scores."""
+    m = _as_model(model)
+    n = int(n)
+    if n < 1 or n > m.max_batch:
+        raise ValueError(f"best-of n={n} outside [1, max_batch={m.max_batch}]")
+    eng = m._need()
+    ids = [tok2id[t] for t in prompt]          # KeyError for an unknown token, like api_cache.py:162
+    n_steps = int(max_len) - len(ids)
+    if n_steps <= 0:
+        toks = [id2tok[i] for i in ids]
+        return (toks, [list(toks) for _ in range(n)], [float("-inf")] * n, 0) if return_all else toks
+    if len(ids) + n_steps > eng.max_ctx:
+        raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
+    eos = tok2id.get("[END_SEQUENCE]", -1)
+    seed = _draw_seed() if seed is None else int(seed)
+    rows = [RowSampling(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, eos_id=eos,
+                        seed=seed, stream=b, logit_bias=logit_bias, min_new_tokens=min(int(min_new_tokens), n_steps))
+            for b in range(n)]
+    res = eng.generate_scored([ids] * n, rows, n_steps)
+    out, lps = res.ids.cpu().tolist(), res.logprobs.cpu().tolist()
+    best = pick_best(out, lps)
+    cands = [[id2tok[t] for t in ids + [g for g in row if g >= 0]] for row in out]
+    return (cands[best], cands, mean_logprobs(out, lps), best) if return_all else cands[best]
 
 
 def _per_prompt(value, n: int, name: str) -> list:

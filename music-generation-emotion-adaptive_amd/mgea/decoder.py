@@ -214,6 +214,48 @@ def pack_row_logits(rows: Sequence[RowSampling], vocab: int, device, check: bool
     return recs, keep
 
 
+@dataclasses.dataclass
+class ScoredGeneration:
+    """What DecoderEngine.generate_scored returns, all on the device: ids int32 [B, n] (-1 after a row's EOS or budget), logprobs and
+    choice_logprobs float32 [B, n] -- the raw and the choice log-probability of every id (include/mgea.h,
+    mgea_decoder_generate_rows_scored); 0.0 where ids is -1."""
+    ids: torch.Tensor
+    logprobs: torch.Tensor
+    choice_logprobs: torch.Tensor
+
+
+def pack_force_ids(force_ids, B: int, n_steps: int, vocab: int):
+    """Forced ids as an int32 [B, n_steps] matrix, -1 = the step is free.  force_ids: None (-> None), B id lists (ragged allowed,
+    padded with -1; None or [] = a free row) or an int tensor [B, <= n_steps].  Host data outside [-1, vocab) raises a ValueError
+    naming the row; a DEVICE tensor is not read back (the kernel clamps ids >= vocab and sets the engine's error flag)."""
+    if force_ids is None:
+        return None
+    if isinstance(force_ids, torch.Tensor):
+        if force_ids.dim() != 2 or force_ids.shape[0] != B or force_ids.shape[1] > n_steps or force_ids.is_floating_point():
+            raise ValueError(f"force_ids must be an int tensor [{B}, <= {n_steps}], got {list(force_ids.shape)} {force_ids.dtype}")
+        t = force_ids.to(torch.int32)
+        if not t.is_cuda:
+            bad = ((t < -1) | (t >= vocab)).any(dim=1).nonzero()
+            if bad.numel():
+                b = int(bad[0])
+                raise ValueError(f"row {b}: force_ids outside [-1, {vocab})")
+        if t.shape[1] < n_steps:
+            t = torch.cat([t, torch.full((B, n_steps - t.shape[1]), -1, dtype=torch.int32, device=t.device)], dim=1)
+        return t.contiguous()
+    rows = list(force_ids)
+    if len(rows) != B:
+        raise ValueError(f"{B} prompts but {len(rows)} force_ids rows")
+    out = np.full((B, n_steps), -1, np.int32)
+    for b, r in enumerate(rows):
+        r = np.asarray([] if r is None else list(r), dtype=np.int64).reshape(-1)
+        if r.size > n_steps:
+            raise ValueError(f"row {b}: {r.size} forced ids for {n_steps} steps")
+        if r.size and (r.min() < -1 or r.max() >= vocab):
+            raise ValueError(f"row {b}: force_ids outside [-1, {vocab})")
+        out[b, :r.size] = r
+    return torch.from_numpy(out)
+
+
 def _prompt_ids(prompts):
     """prompts (id lists, ragged ok, or an int tensor [B, Tp]) -> (int32 ids [B, Tp] on the host, lens [B] or None)"""
     if isinstance(prompts, torch.Tensor):
@@ -503,6 +545,68 @@ class DecoderEngine:
             self.id_errors()
         return out[:, :n_steps]
 
+    def generate_scored(self, prompts, rows: Sequence[RowSampling], n_steps: Optional[int] = None, force_ids=None,
+                        check_ids: bool = True, check_bias: bool = True) -> ScoredGeneration:
+        """generate_rows() that also returns how likely every id was (mgea_decoder_generate_rows_scored; build-defined, the
+        reference returns no scores).  logprobs: log-softmax of the RAW head logits at the id -- a function of the model alone;
+        choice_logprobs: the id's log-probability under the distribution the draw was made from (after penalty, bias, temperature,
+        top-k, top-p), -inf for a forced id outside the kept set, 0 for a greedy row.  force_ids (pack_force_ids: id lists, ragged
+        allowed, or an int tensor; -1 = free) replace the drawn ids step by step -- a forced prefix, or teacher forcing (score()).
+        The ids of the free steps are those of generate_rows(); all-greedy rows run as top_k = 1 rows of the sampled form."""
+        rows = list(rows)
+        ids, lens = _prompt_ids(prompts)
+        B, Tp = ids.shape
+        if len(rows) != B:
+            raise ValueError(f"{B} prompts but {len(rows)} sampler rows")
+        if n_steps is None:
+            budgets = [int(r.max_new_tokens) for r in rows]
+            if min(budgets) <= 0:
+                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
+            n_steps = max(budgets)
+        n_steps = int(n_steps)
+        recs = pack_rows(rows, self.vocab, n_steps)
+        forced = pack_force_ids(force_ids, B, n_steps, self.vocab)
+        lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
+        checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
+        with self._on_stream():
+            ids = ids.to(self.device).contiguous()
+            lens = None if lens is None else lens.to(self.device).contiguous()
+            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
+            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
+                forced.record_stream(self.stream)
+            n = max(n_steps, 1)
+            out = torch.empty(B, n, dtype=torch.int32, device=self.device)
+            lp = torch.zeros(B, n, dtype=torch.float32, device=self.device)
+            ch = torch.zeros(B, n, dtype=torch.float32, device=self.device)
+            for t in keep:   # uploaded on the caller's stream, read by the engine's
+                t.record_stream(self.stream)
+            check(self.lib.mgea_decoder_generate_rows_scored(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, ptr(forced),
+                                                             ptr(out), ptr(lp), ptr(ch), self._sp()))
+        self._cur_batch = B
+        self._epoch += 1
+        if check_ids and not checked:
+            self.id_errors()
+        return ScoredGeneration(out[:, :n_steps], lp[:, :n_steps], ch[:, :n_steps])
+
+    def score(self, prompts, continuations, rows: Optional[Sequence[RowSampling]] = None):
+        """Log-probabilities of given continuations under the model, as sample_kvcache would see them: a teacher-forced
+        generate_scored() (prefill, re-feed the last prompt token, then every step takes continuations[b][t] instead of its draw --
+        one prefill cannot do this, it is bidirectional).  continuations: B non-empty id lists (ragged allowed); row b runs
+        len(continuations[b]) steps.  rows: None = greedy records with eos_id = -1 (the raw values do not depend on them); records
+        of your own keep their settings but get that budget.  Returns (logprobs float32 [B, Tc] on the device, 0 past a row's
+        length; their per-row sums [B])."""
+        conts = [list(c) for c in continuations]
+        if not conts or min(len(c) for c in conts) < 1:
+            raise ValueError("empty continuation")
+        if rows is None:
+            rows = [RowSampling(top_k=1, eos_id=-1) for _ in conts]
+        rows = list(rows)
+        if len(rows) != len(conts):
+            raise ValueError(f"{len(conts)} continuations but {len(rows)} sampler rows")
+        rows = [dataclasses.replace(r, max_new_tokens=len(c)) for r, c in zip(rows, conts)]
+        res = self.generate_scored(prompts, rows, max(len(c) for c in conts), force_ids=conts)
+        return res.logprobs, res.logprobs.sum(dim=1)
+
     def presence(self) -> torch.Tensor:
         """bool [B, vocab] on the device: the ids each row of the last (penalized) generate() has seen -- its real prompt
         tokens and the ids it generated, EOS included.  RuntimeError if that generate() applied no penalty."""
@@ -532,4 +636,4 @@ class DecoderEngine:
         out = (C.c_int64 * 8)()
         check(self.lib.mgea_decoder_stats(self.h, out))
         return dict(graph_nodes=out[0], graph_replays=out[1], graph_instantiates=out[2], graphs_cached=out[4], prefill16_forwards=out[5],
-                    penalized_steps=out[6], biased_steps=out[7])
+                    penalized_steps=out[6], biased_steps=out[7], scored_steps=out[3])

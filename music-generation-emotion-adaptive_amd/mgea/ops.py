@@ -222,6 +222,20 @@ def sample_rows(logits: torch.Tensor, rows, step=0, want_probs=False, presence=N
     penalize; none if None.  top_k=1 rows take the exact argmax of their (penalized) row, without the temperature division.
     logit_bias (one vector for all rows or [B, V]) and min_new_tokens (an int or one per row) override the rows' own fields; a row
     with either goes through mgea_op_sample_rows_biased: bias added after the penalty, eos_id banned while step < min_new_tokens."""
+    return _sample_rows(logits, rows, step, want_probs, presence, logit_bias, min_new_tokens, False, None)
+
+
+def sample_rows_scored(logits: torch.Tensor, rows, step=0, want_probs=False, presence=None, logit_bias=None, min_new_tokens=None,
+                       forced=None):
+    """sample_rows() through the scored sampler (mgea_op_sample_rows_scored): returns (ids, logprobs, choice_logprobs[, probs]) --
+    logprobs [B] = log-softmax of the RAW logits row at the id, choice_logprobs [B] = the id's log-probability under the
+    distribution in probs (-inf outside the kept set).  forced: None, or B ints (a list or an int tensor), -1 = draw; a row with a
+    forced id >= 0 takes it instead of its draw."""
+    return _sample_rows(logits, rows, step, want_probs, presence, logit_bias, min_new_tokens, True, forced)
+
+
+def _sample_rows(logits: torch.Tensor, rows, step, want_probs, presence, logit_bias, min_new_tokens, scored, forced):
+    """sample_rows / sample_rows_scored: pack the rows, one native call."""
     import dataclasses
     from .decoder import pack_row_logits, pack_rows
     rows = list(rows)
@@ -249,6 +263,17 @@ def sample_rows(logits: torch.Tensor, rows, step=0, want_probs=False, presence=N
     ids = torch.empty(B, dtype=torch.int32, device=logits.device)
     probs = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_probs else None
     lrecs, keep = pack_row_logits(rows, V, logits.device)
+    if scored:
+        f = None
+        if forced is not None:
+            f = torch.as_tensor(forced).to(device=logits.device, dtype=torch.int32).contiguous()
+            if f.shape != (B,):
+                raise ValueError(f"forced must hold {B} ids, got {list(f.shape)}")
+        lp = torch.empty(B, dtype=torch.float32, device=logits.device)
+        ch = torch.empty(B, dtype=torch.float32, device=logits.device)
+        check(lib.mgea_op_sample_rows_scored(ptr(logits), B, V, recs, ptr(bits), lrecs, int(step), ptr(ids), ptr(probs), ptr(f), ptr(lp),
+                                             ptr(ch), stream_ptr()))
+        return (ids, lp, ch, probs) if want_probs else (ids, lp, ch)
     if lrecs is None:
         check(lib.mgea_op_sample_rows(ptr(logits), B, V, recs, ptr(bits), int(step), ptr(ids), ptr(probs), stream_ptr()))
     else:
