@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devmem.h"
 
 using namespace mgea;
 
@@ -63,6 +64,7 @@ struct mgea_bert {
     const float* arena = nullptr;
     std::vector<int64_t> off;
     std::mutex mu;
+    DevGroup dev;   // owns every device buffer below: allocate a new one at the end of the group (mgea_bert_create)
     float *h = nullptr, *qkv = nullptr, *ctx = nullptr, *ffn = nullptr, *slabs = nullptr, *pooled = nullptr,
           *pooled2 = nullptr;
     void *wb = nullptr, *hb = nullptr, *qkvb = nullptr, *ctxb = nullptr, *ffnb = nullptr, *tmpb = nullptr;  // bf16 mode
@@ -106,10 +108,7 @@ int mgea_bert_arena_layout(const mgea_bert_config* cfg, int64_t* offsets_floats,
 int mgea_bert_destroy(mgea_bert* h) {
     if (!h) return MGEA_OK;
     (void)hipDeviceSynchronize();
-    void* p[] = {h->h, h->qkv, h->ctx, h->ffn, h->slabs, h->pooled, h->pooled2, h->wb, h->hb, h->qkvb, h->ctxb, h->ffnb, h->tmpb, h->wfold, h->fvec, h->stats_part, h->rowstat_sa, h->rowstat_out, h->ident, h->err_flag};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
-    delete h;
+    delete h;   // h->dev frees the buffers
     return MGEA_OK;
 }
 
@@ -133,6 +132,7 @@ int mgea_bert_create(const mgea_bert_config* cfg, const float* arena_dev, mgea_b
     const int64_t head = 32 * (int64_t)(M < 64 ? M : 64) * slab_ld((int)D);
     slab = slab > head ? slab : head;
     h->slab_cap = slab;
+    DevGroup& g = h->dev;   // (alloc() answers MGEA_OK = 0: a chain of || stops at the first failure)
     bool ok;
     if (cfg->dtype == MGEA_DTYPE_BF16) {
         // perf mode: bf16 copy of the whole arena (same offsets), bf16 activations; the classifier head
@@ -141,24 +141,19 @@ int mgea_bert_create(const mgea_bert_config* cfg, const float* arena_dev, mgea_b
         h->slab_cap = small > big ? small : big;
         const int64_t f32_small = 2 * (M < BF16_MIN_TOKENS ? M : BF16_MIN_TOKENS) * slab_ld((int)nmax);   // the exact-fp32 path of small calls (room for a split of K)
         if (f32_small > h->slab_cap) h->slab_cap = f32_small;
-        ok = hipMalloc(&h->wb, total * 2) == hipSuccess && hipMalloc(&h->hb, M * D * 2) == hipSuccess &&
-             hipMalloc(&h->qkvb, M * 3 * D * 2) == hipSuccess && hipMalloc(&h->ctxb, M * D * 2) == hipSuccess &&
-             hipMalloc(&h->ffnb, M * Hd * 2) == hipSuccess && hipMalloc(&h->tmpb, M * D * 2) == hipSuccess &&
-             hipMalloc((void**)&h->slabs, h->slab_cap * 4) == hipSuccess && hipMalloc((void**)&h->pooled, M * D * 4) == hipSuccess &&
-             hipMalloc((void**)&h->pooled2, M * D * 4) == hipSuccess;
+        ok = !(g.alloc(&h->wb, total * 2) || g.alloc(&h->hb, M * D * 2) || g.alloc(&h->qkvb, M * 3 * D * 2) || g.alloc(&h->ctxb, M * D * 2) ||
+               g.alloc(&h->ffnb, M * Hd * 2) || g.alloc(&h->tmpb, M * D * 2) || g.alloc(&h->slabs, h->slab_cap * 4) ||
+               g.alloc(&h->pooled, M * D * 4) || g.alloc(&h->pooled2, M * D * 4));
         // small calls (fewer than BF16_MIN_TOKENS tokens: the endpoint's one text per request) run on the exact-fp32 kernels -- the 16-bit
         // GEMMs need hundreds of rows to fill their tiles -- with fp32 activation buffers of that size
         const int64_t Ms = M < BF16_MIN_TOKENS ? M : BF16_MIN_TOKENS;
-        if (ok) ok = hipMalloc((void**)&h->h, Ms * D * 4) == hipSuccess && hipMalloc((void**)&h->qkv, Ms * 3 * D * 4) == hipSuccess &&
-                     hipMalloc((void**)&h->ctx, Ms * D * 4) == hipSuccess && hipMalloc((void**)&h->ffn, Ms * Hd * 4) == hipSuccess;
+        if (ok) ok = !(g.alloc(&h->h, Ms * D * 4) || g.alloc(&h->qkv, Ms * 3 * D * 4) || g.alloc(&h->ctx, Ms * D * 4) || g.alloc(&h->ffn, Ms * Hd * 4));
         if (ok) ok = launch_f32_to_bf16(arena_dev, h->wb, total, nullptr) == MGEA_OK && hipDeviceSynchronize() == hipSuccess;
         if (ok) {   // folded-LayerNorm pipeline (see mgea_bert_forward): FC1 of every layer, QKV of layers >= 1
             const int64_t L = cfg->n_layers;
             const int64_t wel = (L * Hd + (L - 1) * 3 * D) * D, vel = L * 2 * Hd + (L - 1) * 2 * 3 * D;
-            ok = hipMalloc(&h->wfold, wel * 2) == hipSuccess && hipMalloc((void**)&h->fvec, (vel > 0 ? vel : 1) * 4) == hipSuccess &&
-                 hipMalloc((void**)&h->stats_part, M * ((D + 255) / 256) * 2 * 4) == hipSuccess &&
-                 hipMalloc((void**)&h->rowstat_sa, M * 2 * 4) == hipSuccess && hipMalloc((void**)&h->rowstat_out, M * 2 * 4) == hipSuccess &&
-                 hipMalloc((void**)&h->ident, (M * 2 + 2 * D) * 4) == hipSuccess;
+            ok = !(g.alloc(&h->wfold, wel * 2) || g.alloc(&h->fvec, (vel > 0 ? vel : 1) * 4) || g.alloc(&h->stats_part, M * ((D + 255) / 256) * 2 * 4) ||
+                   g.alloc(&h->rowstat_sa, M * 2 * 4) || g.alloc(&h->rowstat_out, M * 2 * 4) || g.alloc(&h->ident, (M * 2 + 2 * D) * 4));
             if (ok) {
                 std::vector<float> idv((size_t)(M * 2 + 2 * D), 0.f);
                 for (int64_t r = 0; r < M; ++r) idv[(size_t)r * 2 + 1] = 1.f;
@@ -175,12 +170,10 @@ int mgea_bert_create(const mgea_bert_config* cfg, const float* arena_dev, mgea_b
             if (ok) ok = hipDeviceSynchronize() == hipSuccess;
         }
     } else {
-        ok = hipMalloc((void**)&h->h, M * D * 4) == hipSuccess && hipMalloc((void**)&h->qkv, M * 3 * D * 4) == hipSuccess &&
-             hipMalloc((void**)&h->ctx, M * D * 4) == hipSuccess && hipMalloc((void**)&h->ffn, M * Hd * 4) == hipSuccess &&
-             hipMalloc((void**)&h->slabs, slab * 4) == hipSuccess && hipMalloc((void**)&h->pooled, M * D * 4) == hipSuccess &&
-             hipMalloc((void**)&h->pooled2, M * D * 4) == hipSuccess;
+        ok = !(g.alloc(&h->h, M * D * 4) || g.alloc(&h->qkv, M * 3 * D * 4) || g.alloc(&h->ctx, M * D * 4) || g.alloc(&h->ffn, M * Hd * 4) ||
+               g.alloc(&h->slabs, slab * 4) || g.alloc(&h->pooled, M * D * 4) || g.alloc(&h->pooled2, M * D * 4));
     }
-    if (ok) ok = hipMalloc((void**)&h->err_flag, 16) == hipSuccess && hipMemset(h->err_flag, 0, 16) == hipSuccess;
+    if (ok) ok = g.alloc(&h->err_flag, 16) == MGEA_OK && hipMemset(h->err_flag, 0, 16) == hipSuccess;
     if (!ok) {
         set_error("bert_create: out of device memory");
         mgea_bert_destroy(h);

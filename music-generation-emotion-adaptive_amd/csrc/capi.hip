@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devmem.h"
 
 namespace mgea {
 static thread_local char g_err[512] = "";
@@ -20,6 +21,9 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 const char* get_error() { return g_err; }
+
+bool dev_malloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+void dev_free(void* p) { (void)hipFree(p); }
 
 // ---- switches: one table, initialised from the environment when the library is loaded ---------
 namespace {
@@ -317,13 +321,12 @@ static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const m
     MGEA_REQUIRE(!rr.any_penalty || presence_dev, MGEA_EINVAL, "op_sample_rows: a row is penalized but presence_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
     SamplerParams* rec_dev = nullptr;
-    MGEA_CHECK_HIP(hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)));
     float* bias_dev = nullptr;   // the rows' vectors, row b at b * V (rows without one are never read)
-    if (biased && hipMalloc((void**)&bias_dev, (size_t)B * V * sizeof(float)) != hipSuccess) {
-        (void)hipFree(rec_dev);
-        set_error("op_sample_rows: allocation of the bias rows failed");
-        return MGEA_ENOMEM;
-    }
+    DevGroup tmp;   // frees both on return: nothing is enqueued before the allocations, and the stream is synchronised after
+    MGEA_REQUIRE(tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) == MGEA_OK, MGEA_EHIP,
+                 "hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)) failed: %s (%s:%d)", hipGetErrorString(hipGetLastError()), __FILE__, __LINE__);
+    MGEA_REQUIRE(!biased || tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) == MGEA_OK, MGEA_ENOMEM,
+                 "op_sample_rows: allocation of the bias rows failed");
     SampleCall c = op_sample_call(logits_dev, B, V, step, ids_out_dev, probs_out_dev);
     c.params_dev = rec_dev;   // every scalar comes from the records
     c.presence = rr.any_penalty ? const_cast<uint32_t*>(presence_dev) : nullptr;   // (a bias alone needs no bitmap here: nothing is written)
@@ -339,9 +342,7 @@ static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const m
         rc = launch_sample(c, st);
     else
         set_error("op_sample_rows: copy of the records failed");
-    const hipError_t e = hipStreamSynchronize(st);   // rec, rec_dev and bias_dev are freed below
-    (void)hipFree(rec_dev);
-    if (bias_dev) (void)hipFree(bias_dev);
+    const hipError_t e = hipStreamSynchronize(st);   // rec, rec_dev and bias_dev are freed on return
     MGEA_TRY(rc);
     MGEA_CHECK_HIP(e);
     return MGEA_OK;

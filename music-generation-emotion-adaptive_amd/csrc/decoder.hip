@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devmem.h"
 
 using namespace mgea;
 
@@ -81,6 +82,11 @@ struct mgea_decoder {
     std::vector<int64_t> off;
     int dh = 0;
     std::mutex mu;
+    // Every device buffer below belongs to the group of its lifetime (devmem.h); a new one is allocated at the END of its group.
+    DevGroup dev;            // handle state: mgea_decoder_create and build_tiled_weights, until destroy
+    DevGroup dev_ws;         // the workspace: released and regrown by ensure_ws
+    DevGroup dev_p16_rows;   // Prefill16's activations and tables, regrown with its row count (ensure_p16)
+    DevGroup dev_p16_mats;   // Prefill16's matrices p16.w / p16.vec, kept across refresh_weights
 
     // KV pool
     KvPool kv{};
@@ -202,18 +208,6 @@ struct ProfScope {
         MGEA_TRY(call);                \
     } while (0)
 
-void free_ws(mgea_decoder* h) {
-    float** p[] = {&h->x, &h->xn, &h->qkv, &h->att, &h->hbuf, &h->slabs, &h->logits, &h->stats, &h->pmax_val};
-    if (h->pmax_idx) (void)hipFree(h->pmax_idx);
-    h->pmax_idx = nullptr;
-    for (auto q : p) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    h->ws_tokens = 0;
-    h->slab_cap = 0;
-}
-
 void drop_graphs(mgea_decoder* h) {
     for (auto& g : h->graphs) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -240,36 +234,31 @@ int ensure_ws(mgea_decoder* h, int64_t M) {
     M = round_up(M, 64);   // the k-tiled buffers of the fused path are whole 64-row groups
     if (M <= h->ws_tokens) return MGEA_OK;
     MGEA_CHECK_HIP(hipDeviceSynchronize());
-    free_ws(h);
+    DevGroup& g = h->dev_ws;
+    g.release();
+    h->ws_tokens = h->slab_cap = 0;
     drop_graphs(h);  // captured pointers die with the old workspace
     const int C = h->cfg.d_model, F = h->cfg.d_ff;
     int64_t slab = slab_need(h->cfg, (int)M);
     const int64_t s64 = slab_need(h->cfg, 64);
     slab = slab > s64 ? slab : s64;
-#define ALLOC(ptr, n)                                                                                   \
-    if (hipMalloc((void**)&(ptr), (size_t)(n) * sizeof(float)) != hipSuccess) {                        \
-        set_error("decoder workspace: out of device memory (%lld floats)", (long long)(n));            \
-        free_ws(h);                                                                                     \
-        return MGEA_ENOMEM;                                                                             \
-    }
-    ALLOC(h->x, M * C);
-    ALLOC(h->xn, M * C);
-    ALLOC(h->qkv, M * 3 * C);
-    ALLOC(h->att, M * C);
-    ALLOC(h->hbuf, M * F);
-    ALLOC(h->slabs, slab);
-    ALLOC(h->logits, (int64_t)h->cfg.max_batch * h->cfg.vocab);
+    auto floats = [&](float** field, int64_t n) {
+        if (g.alloc(field, (size_t)n * sizeof(float)) == MGEA_OK) return true;
+        set_error("decoder workspace: out of device memory (%lld floats)", (long long)n);
+        return false;
+    };
     const int64_t fr = M < MGEA_FUSED_MAX_ROWS ? M : MGEA_FUSED_MAX_ROWS;   // rows of the fused path
-    ALLOC(h->stats, fr * (C / 16 + 1) * 2);
-    h->pmax_cap = fr * ceil_div(h->cfg.vocab, 16);   // every head plan leaves at most one partial per 16 columns (checked in decode_gemm)
-    ALLOC(h->pmax_val, h->pmax_cap);
-    if (hipMalloc((void**)&h->pmax_idx, (size_t)h->pmax_cap * sizeof(int32_t)) != hipSuccess) {
-        set_error("decoder workspace: out of device memory");
-        free_ws(h);
+    const int64_t pcap = fr * ceil_div(h->cfg.vocab, 16);   // every head plan leaves at most one partial per 16 columns (checked in decode_gemm)
+    const bool ok = floats(&h->x, M * C) && floats(&h->xn, M * C) && floats(&h->qkv, M * 3 * C) && floats(&h->att, M * C) &&
+              floats(&h->hbuf, M * F) && floats(&h->slabs, slab) && floats(&h->logits, (int64_t)h->cfg.max_batch * h->cfg.vocab) &&
+              floats(&h->stats, fr * (C / 16 + 1) * 2) && floats(&h->pmax_val, pcap);
+    if (!ok || g.alloc(&h->pmax_idx, (size_t)pcap * sizeof(int32_t)) != MGEA_OK) {
+        if (ok) set_error("decoder workspace: out of device memory");
+        g.release();
         return MGEA_ENOMEM;
     }
-#undef ALLOC
     h->slab_cap = slab;
+    h->pmax_cap = pcap;
     h->ws_tokens = M;
     return MGEA_OK;
 }
@@ -612,14 +601,6 @@ int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t s
 // accumulation, LayerNorm statistics and the softmax are fp32.  W_in' / W_fc1' round gamma * f16(W) once more (the decode path applies
 // gamma to the activations instead): the two paths serve models that differ by one fp16 rounding of those two matrices -- inside
 // the fp16 mode's tolerance (tests/test_gpu_f16.py compares both with the oracle on the rounded matrices).
-void free_p16(mgea_decoder* h) {
-    auto& p = h->p16;
-    void* q[] = {p.x0, p.x1, p.qkv, p.att, p.hid, p.w, p.rowstat, p.stats_part, p.ident, p.vec, p.mask};
-    for (void* v : q)
-        if (v) (void)hipFree(v);
-    p = mgea_decoder::Prefill16();
-}
-
 bool prefill16_ok(const mgea_decoder* h, int64_t M, bool cache_attn, const float* logits_out) {
     const auto& c = h->cfg;
     if (!h->f16 || cache_attn || c.block_mode != MGEA_BLOCK_PRELN_GELU || !tune(TUNE_DECODER_PREFILL16)) return false;
@@ -637,32 +618,31 @@ int ensure_p16(mgea_decoder* h, int64_t M, hipStream_t st) {
     const int64_t C = c.d_model, F = c.d_ff, V = c.vocab, NL = c.n_layer;
     if (M > p.rows) {
         MGEA_CHECK_HIP(hipDeviceSynchronize());
-        void** bufs[] = {&p.x0, &p.x1, &p.qkv, &p.att, &p.hid};
-        for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-        float** fb[] = {&p.rowstat, &p.stats_part, &p.ident};
-        for (float** b : fb) { if (*b) (void)hipFree(*b); *b = nullptr; }
-        if (p.mask) { (void)hipFree(p.mask); p.mask = nullptr; }
+        DevGroup& g = h->dev_p16_rows;   // (alloc() answers MGEA_OK = 0: a chain of || stops at the first failure)
+        g.release();
+        p.rows = 0;
         const int64_t R = round_up(M, 256);
-        const bool ok = hipMalloc(&p.x0, R * C * 2) == hipSuccess && hipMalloc(&p.x1, R * C * 2) == hipSuccess &&
-                        hipMalloc(&p.qkv, R * 3 * C * 2) == hipSuccess && hipMalloc(&p.att, R * C * 2) == hipSuccess &&
-                        hipMalloc(&p.hid, R * F * 2) == hipSuccess && hipMalloc((void**)&p.rowstat, R * 2 * 4) == hipSuccess &&
-                        hipMalloc((void**)&p.stats_part, R * (C / 256) * 2 * 4) == hipSuccess &&
-                        hipMalloc((void**)&p.ident, (R * 2 + 2 * C) * 4) == hipSuccess && hipMalloc((void**)&p.mask, R * 4) == hipSuccess;
-        if (!ok) {
+        if (g.alloc(&p.x0, R * C * 2) || g.alloc(&p.x1, R * C * 2) || g.alloc(&p.qkv, R * 3 * C * 2) || g.alloc(&p.att, R * C * 2) ||
+            g.alloc(&p.hid, R * F * 2) || g.alloc(&p.rowstat, R * 2 * 4) || g.alloc(&p.stats_part, R * (C / 256) * 2 * 4) ||
+            g.alloc(&p.ident, (R * 2 + 2 * C) * 4) || g.alloc(&p.mask, R * 4)) {
             set_error("decoder: out of device memory for the fp16 prefill workspace (%lld tokens)", (long long)M);
-            free_p16(h);
+            g.release();
+            h->dev_p16_mats.release();
+            p = mgea_decoder::Prefill16();   // (the matrices too: a prefill that ran out of memory keeps nothing)
             return MGEA_ENOMEM;
         }
         std::vector<float> idv((size_t)(R * 2 + 2 * C), 0.f);       // (0, 1) per row, then C ones (gamma), then C zeros (beta)
         for (int64_t r = 0; r < R; ++r) idv[(size_t)r * 2 + 1] = 1.f;
         for (int64_t d = 0; d < C; ++d) idv[(size_t)(R * 2 + d)] = 1.f;
+        struct Guard { DevGroup* g; ~Guard() { if (g) g->release(); } } unless_filled{&g};   // buffers without their table are no workspace: rows stays 0
         MGEA_CHECK_HIP(hipMemcpy(p.ident, idv.data(), idv.size() * 4, hipMemcpyHostToDevice));
+        unless_filled.g = nullptr;
         p.rows = R;
     }
     if (!p.weights_ready) {
         if (!p.w || !p.vec) {
-            if (p.w) { (void)hipFree(p.w); p.w = nullptr; }
-            if (p.vec) { (void)hipFree(p.vec); p.vec = nullptr; }
+            DevGroup& g = h->dev_p16_mats;
+            g.release();
             p.w_off.clear();
             int64_t tot = 0;
             for (int l = 0; l < NL; ++l) {
@@ -672,11 +652,9 @@ int ensure_p16(mgea_decoder* h, int64_t M, hipStream_t st) {
                 p.w_off.push_back(tot); tot += C * F;
             }
             p.w_off.push_back(tot); tot += round_up(V, 256) * C;     // (rows beyond V are never read: the kernel clamps its row index)
-            if (hipMalloc(&p.w, tot * 2) != hipSuccess || hipMalloc((void**)&p.vec, NL * (6 * C + 2 * F) * 4) != hipSuccess) {
-                // no half-built state: with p.w set and p.vec null the next prefill would skip this block and fold into a null table
-                if (p.w) (void)hipFree(p.w);
-                if (p.vec) (void)hipFree(p.vec);
-                p.w = nullptr; p.vec = nullptr; p.w_off.clear();
+            if (g.alloc(&p.w, tot * 2) || g.alloc(&p.vec, NL * (6 * C + 2 * F) * 4)) {
+                g.release();   // both or neither: with p.w set and p.vec null the next prefill would skip this block
+                p.w_off.clear();
                 set_error("decoder: out of device memory for the fp16 prefill matrices");
                 return MGEA_ENOMEM;
             }
@@ -861,14 +839,12 @@ static int build_tiled_weights(mgea_decoder* h, hipStream_t st) {
             h->wt_off.push_back(total); total += wtile_floats(C, F);
         }
         h->wt_off.push_back(total); total += wtile_floats(V, C);
-        if (hipMalloc((void**)&h->wt, (size_t)total * (h->f16 ? 2 : 4)) != hipSuccess ||
-            hipMalloc((void**)&h->lnv, (size_t)c.n_layer * (6 * C + 2 * F) * sizeof(float)) != hipSuccess) {
-            if (h->wt) (void)hipFree(h->wt);
-            h->wt = nullptr;
+        if (h->dev.alloc(&h->wt, (size_t)total * (h->f16 ? 2 : 4)) || h->dev.alloc(&h->lnv, (size_t)c.n_layer * (6 * C + 2 * F) * sizeof(float))) {
             set_error("decoder_create: allocation of the decode-layout weights (%lld MB) failed", (long long)(total * (h->f16 ? 2 : 4) >> 20));
-            return MGEA_ENOMEM;
+            return MGEA_ENOMEM;   // (wt may stay without lnv: create destroys the handle, and the check below stops anyone else)
         }
     }
+    MGEA_REQUIRE(h->lnv, MGEA_EINVAL, "internal: decode-layout weights half built");
     if (h->f16) {
         // private model copy: the caller's arena with the five matrix kinds rounded to fp16 (fp32 storage) ...
         float* own = h->arena_own;
@@ -916,7 +892,8 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         set_error("no HIP device visible: the MI355X path has no CPU fallback");
         return MGEA_ENODEVICE;
     }
-    mgea_decoder* h = new mgea_decoder();
+    { DeviceInfo di; MGEA_TRY(device_info(&di)); }   // cached now: launchers ask for it inside graph capture
+    mgea_decoder* h = new mgea_decoder();   // from here on every failure goes through destroy
     h->cfg = *cfg;
     h->arena = h->arena_src = arena_dev;
     h->f16 = cfg->dtype == MGEA_DTYPE_F16;
@@ -927,7 +904,6 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     h->force_unfused = tune(TUNE_DECODER_UNFUSED) == 1;   // A/B switches (tools/README.md), latched per engine
     h->no_gemv = tune(TUNE_DECODER_NOGEMV) == 1;
     h->no_graph = tune(TUNE_DECODER_NOGRAPH) == 1;
-    { DeviceInfo di; MGEA_TRY(device_info(&di)); }   // cached now: launchers ask for it inside graph capture
     h->pages_per_row_cap = ceil_div(cfg->max_ctx, MGEA_KV_PAGE_TOKENS);
     h->max_pages = h->pages_per_row_cap;
     h->kv.n_pages = cfg->max_batch * h->pages_per_row_cap;
@@ -941,62 +917,48 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         mgea_decoder_destroy(h);
         return code;
     };
+    DevGroup& g = h->dev;   // (alloc() answers MGEA_OK = 0: a chain of || stops at the first failure)
     if (h->f16) {
-        if (hipMalloc((void**)&h->arena_own, (size_t)total * sizeof(float)) != hipSuccess)
+        if (g.alloc(&h->arena_own, (size_t)total * sizeof(float)))
             return fail(MGEA_ENOMEM, "allocation of the fp16-rounded model copy failed");
         h->arena = h->arena_own;   // filled by build_tiled_weights below
     }
     if (cfg->block_mode == MGEA_BLOCK_PRELN_GELU) {
-        if (hipMalloc((void**)&h->kv.base, pool_bytes) != hipSuccess) return fail(MGEA_ENOMEM, "KV pool allocation failed");
+        if (g.alloc(&h->kv.base, pool_bytes)) return fail(MGEA_ENOMEM, "KV pool allocation failed");
         if (hipMemset(h->kv.base, 0, pool_bytes) != hipSuccess) return fail(MGEA_EHIP, "KV pool memset failed");
     }
     const size_t nb = (size_t)cfg->max_batch * sizeof(int32_t);
     h->ids_hist_stride = cfg->max_ctx;
-    if (hipMalloc((void**)&h->page_table, nb * h->max_pages) != hipSuccess || hipMalloc((void**)&h->ctx_len, nb) != hipSuccess ||
-        hipMalloc((void**)&h->cur_ids, nb) != hipSuccess || hipMalloc((void**)&h->done, nb) != hipSuccess ||
-        hipMalloc((void**)&h->row_step, nb) != hipSuccess || hipMalloc((void**)&h->sampled, nb) != hipSuccess ||
-        hipMalloc((void**)&h->n_done, 16) != hipSuccess || hipMalloc((void**)&h->samp_dev, cfg->max_batch * sizeof(SamplerParams)) != hipSuccess ||
+    if (g.alloc(&h->page_table, nb * h->max_pages) || g.alloc(&h->ctx_len, nb) || g.alloc(&h->cur_ids, nb) || g.alloc(&h->done, nb) ||
+        g.alloc(&h->row_step, nb) || g.alloc(&h->sampled, nb) || g.alloc(&h->n_done, 16) ||
+        g.alloc(&h->samp_dev, cfg->max_batch * sizeof(SamplerParams)) ||
         hipHostMalloc((void**)&h->samp_stage, cfg->max_batch * sizeof(SamplerParams), 0) != hipSuccess ||
         hipEventCreateWithFlags(&h->stage_free, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc((void**)&h->err_flag, 16) != hipSuccess ||
-        hipMalloc((void**)&h->presence, (size_t)cfg->max_batch * presence_words(cfg->vocab) * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void**)&h->ids_hist, nb * h->ids_hist_stride) != hipSuccess)
+        g.alloc(&h->err_flag, 16) || g.alloc(&h->presence, (size_t)cfg->max_batch * presence_words(cfg->vocab) * sizeof(uint32_t)) ||
+        g.alloc(&h->ids_hist, nb * h->ids_hist_stride))
         return fail(MGEA_ENOMEM, "state allocation failed");
     h->attn_split.max_split = MGEA_ATTN_MAX_SPLIT;
     h->attn_split.max_items = MGEA_ATTN_SPLIT_ITEMS;   // attn_split_count(): (row, head) pairs, one query each
-    if (hipMalloc((void**)&h->attn_split.part, (size_t)MGEA_ATTN_SPLIT_ITEMS * MGEA_ATTN_MAX_SPLIT * attn_part_floats(h->dh) * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&h->attn_split.count, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess)
-        return fail(MGEA_ENOMEM, "state allocation failed");
-    // (last of the state buffers: the ones above keep the places they had before this buffer existed)
-    if (hipMalloc((void**)&h->bias, (size_t)cfg->max_batch * cfg->vocab * sizeof(float)) != hipSuccess)
-        return fail(MGEA_ENOMEM, "state allocation failed");
     const size_t nhist = (size_t)cfg->max_batch * h->ids_hist_stride;
-    if (hipMalloc((void**)&h->forced, nhist * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&h->lp_hist, nhist * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&h->ch_hist, nhist * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&h->lp_step, cfg->max_batch * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&h->ch_step, cfg->max_batch * sizeof(float)) != hipSuccess)
+    if (g.alloc(&h->attn_split.part, (size_t)MGEA_ATTN_SPLIT_ITEMS * MGEA_ATTN_MAX_SPLIT * attn_part_floats(h->dh) * sizeof(float)) ||
+        g.alloc(&h->attn_split.count, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) ||
+        // (the logit bias came after the state buffers above, which keep the places they had before it existed: DESIGN.md §5)
+        g.alloc(&h->bias, (size_t)cfg->max_batch * cfg->vocab * sizeof(float)) || g.alloc(&h->forced, nhist * sizeof(int32_t)) ||
+        g.alloc(&h->lp_hist, nhist * sizeof(float)) || g.alloc(&h->ch_hist, nhist * sizeof(float)) ||
+        g.alloc(&h->lp_step, cfg->max_batch * sizeof(float)) || g.alloc(&h->ch_step, cfg->max_batch * sizeof(float)))
         return fail(MGEA_ENOMEM, "state allocation failed");
-    (void)hipMemset(h->forced, 0xff, nhist * sizeof(int32_t));
-    (void)hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t));
-    (void)hipMemset(h->page_table, 0, nb * h->max_pages);
-    (void)hipMemset(h->ctx_len, 0, nb);
-    (void)hipMemset(h->done, 0, nb);
-    (void)hipMemset(h->row_step, 0, nb);
-    (void)hipMemset(h->cur_ids, 0, nb);
-    (void)hipMemset(h->n_done, 0, 16);
-    (void)hipMemset(h->samp_dev, 0, cfg->max_batch * sizeof(SamplerParams));
-    (void)hipMemset(h->err_flag, 0, 16);
-    const int rc = ensure_ws(h, cfg->max_batch > 64 ? cfg->max_batch : 64);
+    if (hipMemset(h->forced, 0xff, nhist * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->page_table, 0, nb * h->max_pages) != hipSuccess || hipMemset(h->ctx_len, 0, nb) != hipSuccess ||
+        hipMemset(h->done, 0, nb) != hipSuccess || hipMemset(h->row_step, 0, nb) != hipSuccess ||
+        hipMemset(h->cur_ids, 0, nb) != hipSuccess || hipMemset(h->n_done, 0, 16) != hipSuccess ||
+        hipMemset(h->samp_dev, 0, cfg->max_batch * sizeof(SamplerParams)) != hipSuccess || hipMemset(h->err_flag, 0, 16) != hipSuccess)
+        return fail(MGEA_EHIP, "state memset failed");
+    int rc = ensure_ws(h, cfg->max_batch > 64 ? cfg->max_batch : 64);
+    if (rc == MGEA_OK && fused_geometry(*cfg)) rc = build_tiled_weights(h, nullptr);
     if (rc != MGEA_OK) {
         mgea_decoder_destroy(h);
         return rc;
-    }
-    if (fused_geometry(*cfg)) {
-        const int rc2 = build_tiled_weights(h, nullptr);
-        if (rc2 != MGEA_OK) {
-            mgea_decoder_destroy(h);
-            return rc2;
-        }
     }
     *out = h;
     return MGEA_OK;
@@ -1014,15 +976,9 @@ int mgea_decoder_destroy(mgea_decoder* h) {
     if (!h) return MGEA_OK;
     (void)hipDeviceSynchronize();
     drop_graphs(h);
-    free_ws(h);
-    free_p16(h);
-    void* p[] = {h->kv.base, h->page_table, h->ctx_len, h->cur_ids, h->done, h->row_step, h->n_done, h->sampled, h->ids_hist, h->wt, h->lnv,
-                 h->samp_dev, h->err_flag, h->presence, h->bias, h->forced, h->lp_hist, h->ch_hist, h->lp_step, h->ch_step, h->arena_own, h->attn_split.part, h->attn_split.count};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
     if (h->samp_stage) (void)hipHostFree(h->samp_stage);
     if (h->stage_free) (void)hipEventDestroy(h->stage_free);
-    delete h;
+    delete h;   // its DevGroups free the device buffers
     return MGEA_OK;
 }
 
