@@ -272,6 +272,11 @@ int mgea_decoder_profile_read(mgea_decoder* h, double* ms_by_class, int64_t* lau
  * applied a logit bias or min_new_tokens (0 if it applied none), [3] decode steps of the last generate() that wrote log-probabilities
  * (mgea_decoder_generate_rows_scored; 0 otherwise). */
 int mgea_decoder_stats(mgea_decoder* h, int64_t* out /* [8] */);
+/* Bytes of the engine's layer-0 q | k | v tables (switch decoder_qkv0_table: f32 engines in MGEA_POS_REFERENCE mode, decode steps of at
+ * most 64 rows): vocab * 3 * d_model * 4 per decode path that has generated -- one for 3..64 rows, one for 1..2 rows -- and 0 before
+ * the first such generation, with the switch off, for every other engine, and for a path whose table found no device memory (that
+ * path keeps the layer-0 in-projection launch; nothing fails). */
+int mgea_decoder_qkv0_table_bytes(mgea_decoder* h, int64_t* bytes_out);
 
 /* Token ids outside [0, vocab) make nn.Embedding raise IndexError in the reference (api_cache.py:99).
  * Here they are clamped on the device and recorded in a sticky flag word, so that no call has to

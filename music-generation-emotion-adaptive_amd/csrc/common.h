@@ -60,6 +60,7 @@ enum { TUNE_BF16_GEMM_TILE = 0,   // 0 = the launcher's choice; 1 128x128 / 2 25
        TUNE_ATTN_SPLIT,           // the decode step's attention of at most this many (row, head) pairs spreads each pair's KV pages over several workgroups, the last one to arrive merges their partials (default 64 = 8 rows of 8 heads: measured +3..5 % tokens/s at 1-8 rows, nothing at 16, -3.5 % at 32; 0: always one workgroup per pair)
        TUNE_DECODER_GRAPH_STEPS,  // decode steps per hipGraph launch of mgea_decoder_generate: 1, 2, 4, 8 (default) or 16; the single-step graph serves the remainder (round 4: 289.4 -> 287.6 us per step at B = 64, 168.3 -> 163.4 at B = 1)
        TUNE_ATTN_ARITH_PAGES,     // 1 (default): the decode attention computes physical page ids (j * batch + b, the decoder's own allocation) instead of loading them from the page table -- one dependent scalar load less per page; 0: always the table
+       TUNE_DECODER_QKV0_TABLE,   // 1 (default): f32 engines in the reference's position mode keep layer 0's q | k | v of every token id in a [vocab][3 C] table and the step's tail gathers the row, so the layer-0 in-projection launch leaves the step (decoder.hip, "qkv0 table"; +vocab * 3 C * 4 bytes per engine and decode path); 0: the launch.  Read by mgea_decoder_create()
        TUNE_COUNT };
 int tune(int key);
 
@@ -257,7 +258,16 @@ struct TailArgs {
     const float* tok_emb; const float* pos_emb;
     float* x; float* stats;     // k-tiled residual stream and its LayerNorm partials (fused decode path)
     int C, vocab, pos_rows, absolute_pos;
+    // qkv0 != NULL (decoder.hip, "qkv0 table"): row [id] of the [vocab][3 C] table is layer 0's q | k | v of the embedding, so the tail also
+    // does what the next step's layer-0 in-projection launch would have done -- the row into qkv [B][3 C], its K | V into layer 0's page --
+    // and leaves out the embedding's LayerNorm statistics, which only that launch read.
+    const float* qkv0; float* qkv;
+    KvPool pool; const int32_t* page_table; int max_pages;
 };
+constexpr int QKV0_MAX_C = 1024;   // embed_qkv0_row moves a row with one float4 per thread of 256 (the fused geometry's d_model limit)
+static inline bool tail_qkv0_ok(const TailArgs& t) {
+    return !t.qkv0 || (t.qkv && t.pool.base && !t.pool.f16 && t.C % 4 == 0 && t.C <= QKV0_MAX_C && t.C % t.pool.dh == 0);
+}
 // What the scored sampler reads and writes besides the draw (sampler.hip, sample_kernel<..., ScoreArgs>).
 // forced: ids the rows must take, -1 = the draw decides -- forced[b] when forced_stride == 0, else forced[b * forced_stride + step] for
 // the row's step index (steps at or beyond the stride are free); NULL: nothing is forced.
@@ -292,9 +302,11 @@ int launch_sample(const SampleCall& c, hipStream_t st);
 // ---- the kernels that end a step, and the rows' records (step_tail.hip) ----
 int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
                           int B, hipStream_t st);
-int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
-                                const float* tok_emb, const float* pos_emb, float* x, float* stats, int B, int C, int vocab,
-                                int pos_rows, int absolute_pos, hipStream_t st);
+int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const TailArgs& t, int32_t* sampled, int B,
+                                hipStream_t st);
+// x, qkv and layer 0's K | V of ids[0, B) at the rows' ctx_len through the qkv0 table (t.qkv0 != NULL): what launch_embed_stats and the
+// layer-0 in-projection launch leave, without the statistics; ids outside the vocabulary are clamped and flagged as there
+int launch_embed_qkv0(const int32_t* ids, const int32_t* ctx_len, const TailArgs& t, int B, int32_t* err_flag, hipStream_t st);
 // params_dev[0, B) <- v with stream = b, stream-ordered: the uniform form of the records
 int launch_fill_sampler_params(SamplerParams* params_dev, const SamplerParams& v, int B, hipStream_t st);
 // params_dev[b].max_new <- min(max_new, reserved - len_b), len_b = lens[b] (NULL: T) clamped to [1, T], and ctx_cap <- reserved: a row
@@ -484,21 +496,24 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 // in the barriers: the sampler's workgroup has 1024):
 // the sampler-loop bookkeeping of api_cache.py:179-181 (append, EOS stop) and the NEXT step's embedding
 // x[b] = tok_emb[fed] + pos_emb[pos] (k-tiled) with its LayerNorm statistics (two equal half-row partials).
-// st_* = the row's state as loaded by thread 0 at kernel start.  sh: >= 6 floats of shared scratch.
+// st_* = the row's state as loaded by thread 0 at kernel start.  sh: >= 7 floats of shared scratch.
+// With the qkv0 table (TailArgs::qkv0) the embedding goes through embed_qkv0_row instead and has no statistics.
 // PENALTY: also set the token's bit in the row's presence bitmap (presence_words(vocab) words per row) while the row is not finished:
 // one writer per row, read by a later kernel, so a plain read-modify-write of the word.
 // The end of row b's decode step on every path (fused sampler tail, greedy argmax tails, advance_kernel), so the rule cannot drift between
 // them: a row that is not finished (done = its flag at step start, len = its ctx_len then) appends tok -- ids_out, cur_ids, ctx_len + 1 --
 // and finishes on its EOS id or when this was its last budgeted step (row_step + 1 == max_new): done = 1, n_done + 1.  row_step advances
-// either way.  Returns the token fed to the next step.
+// either way.  Returns the token fed to the next step; *len_out (optional) receives the row's ctx_len as the next step will read it.
 // A finished row still runs every later step of its batch (fed its last token at position ctx_len, attending to ctx_len + 1 keys).  A
 // row that finishes with its pages full (ctx_len = ctx_cap) would read one key past them: it is parked one position short instead --
 // done = 2, ctx_len - 1, where its later steps only rewrite the last key -- and launch_unpark_rows restores both after the loop.
-__device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int tok, int step, int fed, int len, int done) {
-    int out = -1;
+__device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int tok, int step, int fed, int len, int done,
+                                            int* len_out = nullptr) {
+    int out = -1, next_len = len;
     if (!done) {
         out = tok;
         fed = tok;
+        next_len = len + 1;
         s.cur_ids[b] = tok;
         s.ctx_len[b] = len + 1;
         int eos = s.eos_id, max_new = mgea::MGEA_NO_BUDGET, cap = mgea::MGEA_NO_BUDGET;
@@ -506,13 +521,44 @@ __device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int
         if (tok == eos || step + 1 == max_new) {
             const bool park = len + 1 >= cap;
             s.done[b] = park ? 2 : 1;
-            if (park) s.ctx_len[b] = len;
+            if (park) { s.ctx_len[b] = len; next_len = len; }
             atomicAdd(s.n_done, 1);
         }
     }
     if (s.ids_out && step < s.n_steps) s.ids_out[(int64_t)b * s.n_steps + step] = out;
     s.row_step[b] = step + 1;
+    if (len_out) *len_out = next_len;
     return fed;
+}
+
+// The embedding of token `id` for row b with layer 0's in-projection taken from the table (TailArgs::qkv0), by threads 0..255 of a
+// workgroup: x[b] = tok_emb[id] + pos_emb[pos] (k-tiled; the residual the out-projection adds to), qkv[b] = table[id] -- the whole row,
+// as the EPI_QKV epilogue of gemm_skinny.hip stores it -- and its K | V part into layer 0's page at position len = the row's ctx_len as
+// the next step reads it, under that epilogue's `page < max_pages` guard.  The physical page follows the decoder's allocation rule where
+// the pool carries it (KvPool::arith_batch) and the page table otherwise.  Every load -- embedding rows, table row, page id -- is
+// requested before the first store: one memory round trip, as the embedding alone.
+// (The last step of a generation thereby stores one position the launch would not have: in bounds by the guard, beyond every row's
+// length, and overwritten by whatever step comes next.)
+__device__ __forceinline__ void embed_qkv0_row(int b, int id, int pos, int len, const mgea::TailArgs& t) {
+    const int f = threadIdx.x, C = t.C;   // one float4 of x, q, k and v per thread: C <= 1024 (QKV0_MAX_C, checked by the launchers)
+    if (f >= (C >> 2)) return;
+    const int page = len >> 6, slot = len & (MGEA_KV_PAGE_TOKENS - 1);
+    const bool paged = page < t.max_pages;
+    int phys = 0;
+    if (paged) phys = t.pool.arith_batch > 0 ? page * t.pool.arith_batch + b : t.page_table[b * t.max_pages + page];
+    const float* row = t.qkv0 + (int64_t)id * 3 * C + f * 4;
+    const float4 e = add4(ld4(t.tok_emb + (int64_t)id * C + f * 4), ld4(t.pos_emb + (int64_t)pos * C + f * 4));
+    const float4 q = ld4(row), k = ld4(row + C), v = ld4(row + 2 * C);
+    float* out = t.qkv + (int64_t)b * 3 * C + f * 4;
+    st4(t.x + mgea::tiled_off(b, f * 4, C), e);
+    st4(out, q);
+    st4(out + C, k);
+    st4(out + 2 * C, v);
+    if (paged) {
+        const int head = (f * 4) / t.pool.dh, d = (f * 4) % t.pool.dh;
+        kv_store4(t.pool, 0, phys, 0, head, slot, d, k);
+        kv_store4(t.pool, 0, phys, 1, head, slot, d, v);
+    }
 }
 
 template <bool PENALTY = false>
@@ -522,8 +568,10 @@ __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::Ta
     int* shi = reinterpret_cast<int*>(sh);
     if (tid == 0) {
         sampled[b] = tok;
-        const int fed = end_row_step(t.s, b, tok, st_step, st_fed, st_len, st_done);
+        int next_len;
+        const int fed = end_row_step(t.s, b, tok, st_step, st_fed, st_len, st_done, &next_len);
         const int len = st_done ? st_len : st_len + 1;
+        shi[6] = next_len;
         if constexpr (PENALTY) {
             if (!st_done && (unsigned)tok < (unsigned)t.vocab) {
                 uint32_t* w = presence + (int64_t)b * mgea::presence_words(t.vocab) + (tok >> 5);
@@ -536,6 +584,10 @@ __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::Ta
     }
     __syncthreads();
     const int id = shi[4], pos = shi[5];
+    if (t.qkv0) {   // (a kernel argument: the whole workgroup takes this branch or none of it)
+        embed_qkv0_row(b, id, pos, shi[6], t);
+        return;
+    }
     const int C = t.C, nf4 = C >> 2;
     float4 v[4];
     float sum = 0.f;

@@ -134,6 +134,20 @@ struct mgea_decoder {
     float *lp_hist = nullptr, *ch_hist = nullptr, *lp_step = nullptr, *ch_step = nullptr;
     int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped)
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
+    // The qkv0 table.  In MGEA_POS_REFERENCE mode every decode step adds pos_emb[0] (api_cache.py:99), so the input of layer 0's LN1 +
+    // in-projection is tok_emb[id] + pos_emb[0]: its 3 C outputs q | k | v depend on the token id and the weights alone.  An f32 engine
+    // computes them once for every id, with the step's own kernel family, into qkv0_tab [vocab][3 C] (a row's result does not depend on
+    // the row-tile height the plan picks for a batch size: ensure_qkv0); the kernel that ends
+    // a step and gathers the next embedding row gathers the table row too (common.h: embed_qkv0_row), and the layer-0 in-projection
+    // launch leaves the captured step.  The rows of the MFMA kernel and of the <= 2-row dot-product kernel differ in their last bits
+    // (LayerNorm folded / applied directly), so each decode path has a table of its own, [0] MFMA and [1] GEMV, built at the first
+    // generation that takes the path; an engine that serves one path owns one table.
+    bool qkv0_on = false;          // switch decoder_qkv0_table, latched at create
+    float* qkv0_tab[2] = {nullptr, nullptr};
+    bool qkv0_ready[2] = {false, false};   // false again after mgea_decoder_refresh_weights: rebuilt in place by the next generation
+    bool qkv0_no_mem[2] = {false, false};  // the table could not be allocated: the path keeps the launch for the life of the handle (never
+                                           // retried: the graphs of a batch size have one form)
+    int32_t* qkv0_ids = nullptr;   // 0 .. vocab - 1, then 64 zeros: the ids and the ctx_len of the build launches
     int64_t counters[8] = {0};
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline leg)
     int prof_stride = 0;  // 0 = off; n = time every n-th decode step of generate(), run eagerly
@@ -397,8 +411,9 @@ int decode_gemm(mgea_decoder* h, int l, int g, SkinnyArgs a, bool gv, hipStream_
     return launch_decode_gemm(kEpi[g], p, a, st);
 }
 
+// qkv0_primed: u.qkv and layer 0's K | V page already hold this step's in-projection of layer 0 (the qkv0 table): that launch is skipped
 int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t* lens, bool use_cache_attn, hipStream_t st,
-                     bool kv_only_last = false) {
+                     bool kv_only_last = false, bool qkv0_primed = false) {
     const auto& c = h->cfg;
     const int C = c.d_model, F = c.d_ff, M = B * T;
     const bool gv = gemv_ok(h, M, T, lens, use_cache_attn);
@@ -411,7 +426,7 @@ int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t
         a.out = u.qkv; a.ldo = 3 * C;
         a.pool = h->kv; a.layer = l; a.page_table = u.page_table; a.max_pages = h->max_pages; a.ctx_len = u.ctx_len;
         a.lens = lens; a.T = T; a.C = C;
-        PROF(PC_GEMM, decode_gemm(h, l, 0, a, gv, st));
+        if (l > 0 || !qkv0_primed) PROF(PC_GEMM, decode_gemm(h, l, 0, a, gv, st));
         if (kv_only_last && l + 1 == c.n_layer) break;       // (run_blocks: the logits are dropped, the last block's K | V are appended)
         if (use_cache_attn) {
             PROF(PC_ATTN_PAGED, launch_attn_paged(u.qkv, h->kv, l, u.page_table, h->max_pages, u.ctx_len, lens, u.att, B, T, C, 1, st, &h->attn_split));
@@ -450,9 +465,24 @@ struct StepCall {
     float* logits_out;   // optional
     bool primed;
     bool scored = false;   // the scored sampler (never with the GREEDY form: scoring needs the logits row)
+    // primed steps only: the qkv0 table of the step's decode path -- layer 0's q | k | v arrive primed too (no in-projection launch for
+    // layer 0) and the tail gathers them for the next step; NULL: the launch
+    const float* qkv0 = nullptr;
     // where the head writes the logits row: the caller's buffer, the engine's `own` for the sampler, nowhere for the argmax tails
     float* head_out(float* own) const { return logits_out ? logits_out : (form == StepForm::GREEDY ? nullptr : own); }
 };
+
+// What the kernel that embeds the next step's token works on; qkv0: the table of the step's path, or NULL (TailArgs, common.h)
+TailArgs tail_args(const mgea_decoder* h, const Bufs& u, const StepState& s, const float* qkv0) {
+    const auto& c = h->cfg;
+    TailArgs t{s, h->w(T_TOK), h->w(T_POS), u.x, u.stats, c.d_model, c.vocab, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
+    if (qkv0) {
+        t.qkv0 = qkv0; t.qkv = u.qkv;
+        t.pool = h->kv; t.page_table = u.page_table; t.max_pages = h->max_pages;
+        if (!tune(TUNE_ATTN_ARITH_PAGES)) t.pool.arith_batch = 0;   // (as the attention: the switch sends every page id through the table)
+    }
+    return t;
+}
 
 // The tail of a step over the head's output.  GREEDY: the argmax of the head's n_partials partials per row (0: the ids are already in
 // u.sampled), the bookkeeping and, primed, the next step's embedding.  Otherwise the form's sampler over the logits row lg, with the
@@ -462,12 +492,11 @@ int enqueue_tail(mgea_decoder* h, const Bufs& u, const StepCall& k, const float*
     const int B = k.B, C = c.d_model, V = c.vocab;
     // (with records the EOS id, like the other scalars, is read from them -- the captured graph's form)
     const StepState s{u.cur_ids, u.ctx_len, u.done, u.row_step, h->n_done, u.ids_hist, h->ids_hist_stride, k.pv.eos_id, k.pd};
-    const TailArgs t{s, h->w(T_TOK), h->w(T_POS), u.x, u.stats, C, V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
+    const TailArgs t = tail_args(h, u, s, k.primed ? k.qkv0 : nullptr);
     if (k.form == StepForm::GREEDY) {
         MGEA_REQUIRE(!k.scored, MGEA_EINVAL, "internal: a scored step never takes the greedy form");
         if (k.primed)
-            PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, n_partials, s, u.sampled, t.tok_emb, t.pos_emb, t.x,
-                                                        t.stats, B, C, V, t.pos_rows, t.absolute_pos, st));
+            PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, n_partials, t, u.sampled, B, st));
         else if (n_partials > 0)
             PROF(PC_SAMPLE, launch_argmax_advance(u.pmax_val, u.pmax_idx, n_partials, s, u.sampled, B, st));
         else
@@ -496,7 +525,8 @@ int enqueue_step_fused(mgea_decoder* h, const Bufs& u, const StepCall& k, hipStr
     if (!k.primed)
         PROF(PC_ROWOP, launch_embed_stats(u.cur_ids, nullptr, u.ctx_len, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, 1, C, V,
                                           c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
-    MGEA_TRY(run_blocks_fused(h, u, B, 1, nullptr, true, st));
+    MGEA_REQUIRE(!k.qkv0 || k.primed, MGEA_EINVAL, "internal: the qkv0 table serves primed steps only");
+    MGEA_TRY(run_blocks_fused(h, u, B, 1, nullptr, true, st, false, k.qkv0 != nullptr));
     SkinnyArgs a{};
     a.M = B; a.A = u.x; a.lda = C; a.N = V; a.K = C;
     a.out = k.head_out(u.logits);
@@ -524,16 +554,77 @@ int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     return enqueue_tail(h, main_bufs(h), k, lg, 0, st);
 }
 
-// The decode step of generate(): the rows' device records; x arrives primed on the fused path.
-int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st) {
-    return enqueue_step(h, StepCall{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored}, st);
+// Which qkv0 table a primed step of B rows reads: 0 the MFMA kernels', 1 the <= 2-row dot-product kernels', -1 none (the layer-0
+// in-projection launch stays).  A constant of the handle and B, so every graph of a batch size has one form.
+// The 64-row limit is not technical: tests/test_gpu_decoder.py::test_fused_path_beyond_64_rows pins graph_nodes == 32 for a 100-row f32
+// step, and existing tests are this project's yardsticks.  64 rows cover the benchmark and the batched server (RequestBatcher).
+int qkv0_path(const mgea_decoder* h, int B) {
+    if (!h->qkv0_on || h->f16 || h->cfg.pos_mode != MGEA_POS_REFERENCE || !fused_ok(h, B) || B > 64) return -1;
+    return gemv_ok(h, B, 1, nullptr, true) ? 1 : 0;
+}
+const float* qkv0_table(const mgea_decoder* h, int B) {
+    const int p = qkv0_path(h, B);
+    return p >= 0 && h->qkv0_ready[p] ? h->qkv0_tab[p] : nullptr;
 }
 
-// embedding (+ LN statistics) of cur_ids into the buffers the next generate() step will read
+// Builds the table of decode path `path` if it is not there: for the ids in chunks of 64 (MFMA) or 2 (GEMV) rows, the embedding at
+// position 0 with its statistics, then layer 0's in-projection through decode_gemm -- the step's kernel family and its plan for that
+// many rows -- with the chunk's table rows as the output and max_pages = 0, so that the epilogue's page guard keeps it from any KV page.
+// The plan of a step is not always the plan of a chunk: pick_mt gives 16-row tiles (MT = 1) to steps of at most 16 rows and to the last,
+// short chunk, and 32-row tiles (MT = 2) to the 64-row chunks and to steps of 17..64 rows.  A row's result is the same in both: the
+// wave count and the K split do not depend on MT (pick_waves), every 16-row MFMA tile is computed on its own, and the waves' partials are
+// added in the same order.  The dot-product kernel likewise computes row 0 of one row and either row of two with the same instruction
+// sequence.  tests/test_gpu_qkv0_table.py holds both to the bits (3, 16, 24 and 64 rows; 1 and 2 rows).
+// On the call's stream, never inside a capture; x and stats are free between the prefill and the first step.
+// Out of device memory: no error, the path keeps its launch (qkv0_no_mem) and mgea_decoder_qkv0_table_bytes says 0.
+int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
+    if (h->qkv0_ready[path] || h->qkv0_no_mem[path]) return MGEA_OK;
+    const auto& c = h->cfg;
+    const int C = c.d_model, V = c.vocab;
+    if (!h->qkv0_ids) {
+        if (h->dev.alloc(&h->qkv0_ids, ((size_t)V + 64) * sizeof(int32_t))) {
+            h->qkv0_no_mem[0] = h->qkv0_no_mem[1] = true;
+            return MGEA_OK;
+        }
+        std::vector<int32_t> iota((size_t)V + 64, 0);
+        for (int i = 0; i < V; ++i) iota[(size_t)i] = i;
+        MGEA_CHECK_HIP(hipMemcpyAsync(h->qkv0_ids, iota.data(), iota.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        MGEA_CHECK_HIP(hipStreamSynchronize(st));   // iota is a stack-lifetime host buffer (as do_reset's page table)
+    }
+    if (!h->qkv0_tab[path] && h->dev.alloc(&h->qkv0_tab[path], (size_t)V * 3 * C * sizeof(float))) {
+        h->qkv0_no_mem[path] = true;
+        return MGEA_OK;
+    }
+    MGEA_REQUIRE(h->ws_tokens >= 64, MGEA_EINVAL, "internal: qkv0 table build without a 64-row workspace");
+    const int rows = path == 1 ? 2 : 64;
+    for (int v0 = 0; v0 < V; v0 += rows) {
+        const int m = V - v0 < rows ? V - v0 : rows;
+        MGEA_TRY(launch_embed_stats(h->qkv0_ids + v0, nullptr, nullptr, h->w(T_TOK), h->w(T_POS), h->x, h->stats, m, 1, C, V, c.seq_len, 0,
+                                    nullptr, st));
+        SkinnyArgs a{};
+        a.M = m; a.eps = c.ln_eps; a.A = h->x; a.lda = C; a.N = 3 * C; a.K = C;
+        a.stats_in = h->stats; a.n_part = 2; a.part_cnt = C / 2;
+        a.out = h->qkv0_tab[path] + (int64_t)v0 * 3 * C; a.ldo = 3 * C;
+        a.pool = h->kv; a.layer = 0; a.page_table = h->page_table; a.max_pages = 0; a.ctx_len = h->qkv0_ids + V;
+        a.lens = nullptr; a.T = 1; a.C = C;
+        MGEA_TRY(decode_gemm(h, 0, 0, a, path == 1, st));
+    }
+    h->qkv0_ready[path] = true;
+    return MGEA_OK;
+}
+
+// The decode step of generate(): the rows' device records; x arrives primed on the fused path.
+int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st) {
+    return enqueue_step(h, StepCall{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored, qkv0_table(h, B)}, st);
+}
+
+// embedding (+ LN statistics, or through the qkv0 table) of cur_ids into the buffers the next generate() step will read
 int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
     if (!fused_ok(h, B)) return MGEA_OK;
     const auto& c = h->cfg;
     const Bufs u = main_bufs(h);
+    if (const float* tab = qkv0_table(h, B))
+        return launch_embed_qkv0(u.cur_ids, u.ctx_len, tail_args(h, u, StepState{}, tab), B, h->err_flag, st);
     return launch_embed_stats(u.cur_ids, nullptr, u.ctx_len, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, 1, c.d_model, c.vocab,
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
@@ -904,6 +995,7 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     h->force_unfused = tune(TUNE_DECODER_UNFUSED) == 1;   // A/B switches (tools/README.md), latched per engine
     h->no_gemv = tune(TUNE_DECODER_NOGEMV) == 1;
     h->no_graph = tune(TUNE_DECODER_NOGRAPH) == 1;
+    h->qkv0_on = tune(TUNE_DECODER_QKV0_TABLE) == 1;
     h->pages_per_row_cap = ceil_div(cfg->max_ctx, MGEA_KV_PAGE_TOKENS);
     h->max_pages = h->pages_per_row_cap;
     h->kv.n_pages = cfg->max_batch * h->pages_per_row_cap;
@@ -968,6 +1060,7 @@ int mgea_decoder_refresh_weights(mgea_decoder* h, void* stream) {
     MGEA_REQUIRE(h, MGEA_EINVAL, "decoder handle is NULL");
     std::lock_guard<std::mutex> lk(h->mu);
     h->p16.weights_ready = false;   // rebuilt from the refreshed model copy at the next big-batch prefill
+    h->qkv0_ready[0] = h->qkv0_ready[1] = false;   // and the qkv0 tables at the next generation, in place (the graphs keep their pointers)
     if (!fused_geometry(h->cfg)) return MGEA_OK;
     return build_tiled_weights(h, (hipStream_t)stream);
 }
@@ -1085,6 +1178,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             MGEA_CHECK_HIP(hipMemcpy2DAsync(h->forced, hs * sizeof(int32_t), score->forced_dev, (size_t)n_steps * sizeof(int32_t),
                                             (size_t)n_steps * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
     }
+    if (const int path = qkv0_path(h, B); path >= 0) MGEA_TRY(ensure_qkv0(h, path, st));   // before any capture of this batch size
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
     if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
@@ -1250,6 +1344,16 @@ int mgea_decoder_error_flags(mgea_decoder* h, int32_t* flags_out, void* stream) 
     MGEA_CHECK_HIP(hipStreamSynchronize(st));
     if (v) MGEA_CHECK_HIP(hipMemsetAsync(h->err_flag, 0, sizeof(int32_t), st));
     *flags_out = v;
+    return MGEA_OK;
+}
+
+int mgea_decoder_qkv0_table_bytes(mgea_decoder* h, int64_t* bytes_out) {
+    MGEA_REQUIRE(h && bytes_out, MGEA_EINVAL, "decoder_qkv0_table_bytes: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    int64_t n = 0;
+    for (int p = 0; p < 2; ++p)
+        if (h->qkv0_tab[p] && h->qkv0_ready[p]) n += (int64_t)h->cfg.vocab * 3 * h->cfg.d_model * (int64_t)sizeof(float);
+    *bytes_out = n;
     return MGEA_OK;
 }
 

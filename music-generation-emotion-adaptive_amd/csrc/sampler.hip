@@ -705,7 +705,7 @@ int launch_sample(const SampleCall& c, hipStream_t st) {
     MGEA_REQUIRE(c.params_dev || c.params.temperature > 0.f, MGEA_EINVAL, "sampler: temperature must be > 0");
     MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "sampler: vocab %d exceeds the register-resident row (%d)", V,
                  MGEA_SAMPLER_MAX_VOCAB);
-    MGEA_REQUIRE(!tail || (c.ids_out && tail->C % 4 == 0 && tail->C <= 4096), MGEA_EINVAL, "sampler: bad fused-tail arguments");
+    MGEA_REQUIRE(!tail || (c.ids_out && tail->C % 4 == 0 && tail->C <= 4096 && tail_qkv0_ok(*tail)), MGEA_EINVAL, "sampler: bad fused-tail arguments");
     MGEA_REQUIRE(!c.presence || c.params_dev || (std::isfinite(c.params.penalty) && c.params.penalty > 0.f), MGEA_EINVAL,
                  "sampler: the repetition penalty must be finite and > 0");
     const TailArgs t = tail ? *tail : TailArgs{};

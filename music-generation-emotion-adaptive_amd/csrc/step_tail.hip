@@ -70,12 +70,30 @@ __global__ __launch_bounds__(256) void argmax_advance_embed_kernel(const float* 
     advance_embed_row(b, tok, t, sampled, st_step, st_fed, st_len, st_done, sh);
 }
 
-int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
-                                const float* tok_emb, const float* pos_emb, float* x, float* stats, int B, int C, int vocab,
-                                int pos_rows, int absolute_pos, hipStream_t st) {
-    MGEA_REQUIRE(B <= MGEA_FUSED_MAX_ROWS && C % 4 == 0 && C <= 4096, MGEA_EINVAL, "argmax+embed: bad shape");
-    TailArgs t{s, tok_emb, pos_emb, x, stats, C, vocab, pos_rows, absolute_pos};
+int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const TailArgs& t, int32_t* sampled, int B,
+                                hipStream_t st) {
+    MGEA_REQUIRE(B <= MGEA_FUSED_MAX_ROWS && t.C % 4 == 0 && t.C <= 4096 && tail_qkv0_ok(t), MGEA_EINVAL, "argmax+embed: bad shape");
     hipLaunchKernelGGL(argmax_advance_embed_kernel, dim3(B), dim3(256), 0, st, pval, pidx, n_tiles, t, sampled);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+// The embedding of ids[b] through the qkv0 table, for a row whose step is not the tail of another: generate()'s re-fed last prompt token.
+__global__ __launch_bounds__(256) void embed_qkv0_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ ctx_len, TailArgs t,
+                                                        int32_t* __restrict__ err_flag) {
+    const int b = blockIdx.x;
+    int id = ids[b];
+    if ((id < 0 || id >= t.vocab) && err_flag && threadIdx.x == 0) atomicOr(err_flag, 1);   // as embed_stats_kernel
+    id = id < 0 ? 0 : (id >= t.vocab ? t.vocab - 1 : id);
+    const int len = ctx_len[b];
+    int pos = t.absolute_pos ? len : 0;
+    pos = pos < t.pos_rows ? pos : t.pos_rows - 1;
+    embed_qkv0_row(b, id, pos, len, t);
+}
+
+int launch_embed_qkv0(const int32_t* ids, const int32_t* ctx_len, const TailArgs& t, int B, int32_t* err_flag, hipStream_t st) {
+    MGEA_REQUIRE(t.qkv0 && tail_qkv0_ok(t) && B <= MGEA_FUSED_MAX_ROWS, MGEA_EINVAL, "embed (qkv0 table): no table, fp16 KV pages or a bad shape");
+    hipLaunchKernelGGL(embed_qkv0_kernel, dim3(B), dim3(256), 0, st, ids, ctx_len, t, err_flag);
     MGEA_CHECK_HIP(hipGetLastError());
     return MGEA_OK;
 }

@@ -78,6 +78,7 @@ PROTOTYPES = {
     "mgea_decoder_presence": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_context_lengths": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_stats": (C.c_int, [_P, C.POINTER(_I64)]),
+    "mgea_decoder_qkv0_table_bytes": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_error_flags": (C.c_int, [_P, C.POINTER(_I32), _P]),
     "mgea_bert_error_flags": (C.c_int, [_P, C.POINTER(_I32), _P]),
     "mgea_decoder_profile": (C.c_int, [_P, _I32]),

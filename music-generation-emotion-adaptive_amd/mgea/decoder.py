@@ -635,5 +635,7 @@ class DecoderEngine:
     def stats(self):
         out = (C.c_int64 * 8)()
         check(self.lib.mgea_decoder_stats(self.h, out))
+        tab = C.c_int64(0)
+        check(self.lib.mgea_decoder_qkv0_table_bytes(self.h, C.byref(tab)))
         return dict(graph_nodes=out[0], graph_replays=out[1], graph_instantiates=out[2], graphs_cached=out[4], prefill16_forwards=out[5],
-                    penalized_steps=out[6], biased_steps=out[7], scored_steps=out[3])
+                    penalized_steps=out[6], biased_steps=out[7], scored_steps=out[3], qkv0_table_bytes=tab.value)
