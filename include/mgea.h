@@ -387,6 +387,53 @@ int mgea_op_attention_bf16(const void* qkv_dev, const int32_t* mask_dev, void* o
                            int32_t n_head, int32_t head_dim, void* stream);
 int mgea_op_layernorm_bf16(const void* x_dev, const float* w_dev, const float* b_dev, void* y_dev, int32_t M,
                            int32_t C, float eps, void* stream);
+/* The 16-bit kernels of the decoder's fp16 mode (MGEA_DTYPE_F16) and the paged attention, one kernel per call, so that the tests can
+ * hold each against exact references instead of the engine's end-to-end tolerances.  `dtype` is MGEA_DTYPE_BF16 or MGEA_DTYPE_F16
+ * (16-bit storage) or, for the pages of mgea_op_attention_paged, MGEA_DTYPE_F32.
+ * ONE LAYER OF KV PAGES (csrc/common.h KvPool): pages_dev holds n_pages physical pages, page p = [K | V][n_head][64 tokens x head_dim]
+ * elements; inside a (p, K|V, head) block K is [head_dim / G][64 tokens][G] and V is [64 tokens][head_dim], G = the elements of a
+ * 16-byte group (8 fp16, 4 fp32).  page_table_dev [B][max_pages] int32 names the physical page of logical page j of row b; every entry
+ * a call can reach must lie in [0, n_pages) -- checked nowhere, as in the engine, which fills the table itself. */
+/* mgea_op_gemm_bf16_ln on fp16 operands: epi 3 / 4 / 5 (fp16 output) and 6 = a w^T + bias as FP32 [M, N] (N % 4 == 0).  Persistent
+ * kernel only: M >= 512, N >= 256, at least 8 tiles of 256 x 256; epi 3 / 4 / 5 need N % 256 == 0.  Anything else is MGEA_EINVAL. */
+int mgea_op_gemm_f16_ln(const void* a_dev, const void* w_dev, const float* bias_dev, const void* res_dev, void* out_dev,
+                        int32_t M, int32_t N, int32_t K, int32_t epi, const float* rowstat_dev, const float* c1_dev,
+                        const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream);
+/* mgea_op_f32_to_bf16 / mgea_op_fold_ln_bf16 with the 16-bit type as an argument (MGEA_DTYPE_BF16: exactly those calls). */
+int mgea_op_f32_to_16(const float* src_dev, void* dst_dev, int64_t n, int32_t dtype, void* stream);
+int mgea_op_fold_ln_16(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* bias_dev, int32_t N, int32_t K,
+                       int32_t dtype, void* wf_out_dev, float* c1_out_dev, float* c2_out_dev, void* stream);
+/* The 16-bit flash attention (mgea_op_attention_bf16) in either 16-bit type.  mask_dev [B, T] int32 or NULL.  cu_seqlens_dev [B + 1]
+ * int32 or NULL: packed rows (qkv / out [cu[B], 3C / C], T = the longest sequence <= 256, no mask).  pages_dev != NULL (fp16 only,
+ * no cu_seqlens): K | V of every key whose mask bit is set (all keys without a mask) are also written to the pages at position t;
+ * keys of logical pages >= max_pages are not cached. */
+int mgea_op_attention16(const void* qkv_dev, const int32_t* mask_dev, const int32_t* cu_seqlens_dev, void* out_dev, int32_t B, int32_t T,
+                        int32_t n_head, int32_t head_dim, int32_t dtype, void* pages_dev, int32_t n_pages,
+                        const int32_t* page_table_dev, int32_t max_pages, void* stream);
+/* K | V columns of fp16 qkv rows [B * T, 3C] -> fp16 pages: token t < lens[b] (lens_dev NULL: t < T) of row b at position
+ * ctx_len_dev[b] + t; positions in logical pages >= max_pages are not cached. */
+int mgea_op_kv_scatter_f16(const void* qkv_dev, void* pages_dev, int32_t n_pages, const int32_t* page_table_dev, int32_t max_pages,
+                           const int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                           void* stream);
+/* The embedding of the fp16 prefill: x_out_dev [B * T, C] fp16 = f16(tok_emb[id] + pos_emb[pos]), rowstat_out_dev [B * T][2] = (mean,
+ * rstd) of the ROUNDED row, mask_out_dev [B * T] int32 (or NULL) = t < lens[b]; rows past lens[b] are zero rows with (0, 1).
+ * pos = t (+ ctx_len_dev[b] when absolute_pos and ctx_len_dev), clamped to pos_rows - 1; ids are clamped to the vocabulary and bit 0
+ * of *err_flag_dev (or NULL) is set for a clamped REAL token.  C % 4 == 0, C <= 2048. */
+int mgea_op_dec_embed_f16(const int32_t* ids_dev, const int32_t* lens_dev, const int32_t* ctx_len_dev, const float* tok_emb_dev,
+                          const float* pos_emb_dev, void* x_out_dev, float* rowstat_out_dev, int32_t* mask_out_dev, float eps, int32_t B,
+                          int32_t T, int32_t C, int32_t vocab, int32_t pos_rows, int32_t absolute_pos, int32_t* err_flag_dev,
+                          void* stream);
+/* The decode / extend attention over one layer of pages (dtype MGEA_DTYPE_F32 or MGEA_DTYPE_F16): query (b, t) -- q = columns 0..C-1
+ * of row b * T + t of qkv_dev [B * T, 3C] fp32 -- attends to the ctx_len_dev[b] + (lens_dev ? lens_dev[b] : T) cached tokens of row b;
+ * out_dev [B * T, C] fp32 row-major, zero rows for t >= lens[b].  arith_batch > 0: the kernel may compute physical page j * arith_batch + b
+ * instead of loading the table (which must then say the same); 0: only the table says.  no_split != 0: one workgroup per (row, head,
+ * query); otherwise the call brings the split-context scratch (counters zeroed) and the launcher decides as in the engine (switch
+ * attn_split).  info_out [1] (host, or NULL): [0] the workgroups per (row, head, query) of the launch, 1 = the unsplit kernel.
+ * Synchronises `stream` before it returns. */
+int mgea_op_attention_paged(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t dtype, int32_t arith_batch,
+                            const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev, const int32_t* lens_dev,
+                            float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t no_split, int32_t* info_out,
+                            void* stream);
 /* Layouts of the fused decode path.  The skinny GEMM reads both operands in MFMA-fragment order so that
  * every wave load is 1 KB of consecutive bytes (see csrc/common.h):
  *   tile_weights: W [N,K] row-major -> out_dev [mgea_op_tiled_weight_floats(N,K)] (rows padded to 32);

@@ -382,12 +382,14 @@ typedef unsigned long long u64x1;
 template <typename T> struct X16;
 template <> struct X16<__bf16> {
     static constexpr bool is_bf16 = true;
+    static constexpr float attn_rescale_log2 = 16.0f;   // flash attention, deferred rescale: p = 2^((s - m) kexp) <= 2^16 is far inside bf16's range
     typedef bf16x8 v8; typedef bf16x4 v4; typedef bf16x2 v2;
     static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x2 unpack(unsigned u) { return (f32x2){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
 };
 template <> struct X16<_Float16> {
     static constexpr bool is_bf16 = false;
+    static constexpr float attn_rescale_log2 = 15.0f;   // p <= 2^15: fp16 rounds every p from 65520 up to +inf (its largest finite value is 65504)
     typedef h16x8 v8; typedef h16x4 v4; typedef _Float16 v2 __attribute__((ext_vector_type(2)));
     static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x2 unpack(unsigned u) {
@@ -1966,9 +1968,10 @@ void attn_bf16_kernel(const E* __restrict__ qkv, const int32_t* __restrict__ mas
             tmax[1] = quad_max(tmax[1]);
             // Deferred rescale (guide T13): the running maximum is only a scaling reference; P and the accumulators stay exact as long
             // as one reference is used per row.  Keep the old one while no row of this wave outgrows it by more than 2^RESCALE_LOG2
-            // (p <= 2^16: nothing near an fp32 / bf16 range limit) -- the accumulator rescale and its exponential then run on the first
-            // tile of an item and on the rare tile that trips the threshold instead of on every tile.
-            constexpr float RESCALE_LOG2 = 16.0f;
+            // (X16<E>::attn_rescale_log2, a property of the element type: P is stored as E, so 2^RESCALE_LOG2 must stay finite in E --
+            // 2^16 for bf16, 2^15 for fp16, where 2^16 is +inf and made lacc inf and the output row NaN) -- the accumulator rescale and
+            // its exponential then run on the first tile of an item and on the rare tile that trips the threshold instead of on every tile.
+            constexpr float RESCALE_LOG2 = X16<E>::attn_rescale_log2;
             bool grow = first_tile;
             if (!first_tile) {
                 const bool g0 = (tmax[0] - mx[0]) * kexp > RESCALE_LOG2, g1 = (tmax[1] - mx[1]) * kexp > RESCALE_LOG2;   // -inf - -inf = NaN: false

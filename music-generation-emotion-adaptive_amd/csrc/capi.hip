@@ -218,6 +218,105 @@ int mgea_op_layernorm_bf16(const void* x_dev, const float* w_dev, const float* b
     return launch_layernorm_bf16(x_dev, w_dev, b_dev, y_dev, M, C, eps, (hipStream_t)stream);
 }
 
+// ---- the 16-bit kernels of the fp16 decoder and the paged attention, one kernel per call (tests) ----
+// one layer of KV pages on a caller buffer (mgea.h)
+static KvPool op_pool(const void* pages_dev, int n_pages, int H, int dh, int f16, int arith_batch) {
+    KvPool p{};
+    p.base = const_cast<void*>(pages_dev); p.n_pages = n_pages; p.H = H; p.dh = dh;
+    p.layer_stride = (int64_t)n_pages * 2 * H * MGEA_KV_PAGE_TOKENS * dh;
+    p.f16 = f16; p.arith_batch = arith_batch;
+    return p;
+}
+
+int mgea_op_gemm_f16_ln(const void* a_dev, const void* w_dev, const float* bias_dev, const void* res_dev, void* out_dev,
+                        int32_t M, int32_t N, int32_t K, int32_t epi, const float* rowstat_dev, const float* c1_dev,
+                        const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream) {
+    MGEA_REQUIRE(a_dev && w_dev && out_dev, MGEA_EINVAL, "op_gemm_f16_ln: NULL argument");
+    const BfEpiLn ln{rowstat_dev, c1_dev, ln_g_dev, ln_b_dev, stats_out_dev};
+    GemmBf16Info gi{-1, 0, 0};
+    const int rc = launch_gemm_bf16(a_dev, K, w_dev, K, bias_dev, res_dev, out_dev, N, M, N, K, epi, (hipStream_t)stream, &gi, &ln, 1);
+    if (info_out) { info_out[0] = gi.kernel; info_out[1] = gi.half_tiles; }
+    return rc;
+}
+
+int mgea_op_f32_to_16(const float* src_dev, void* dst_dev, int64_t n, int32_t dtype, void* stream) {
+    MGEA_REQUIRE(src_dev && dst_dev && n > 0 && (dtype == MGEA_DTYPE_BF16 || dtype == MGEA_DTYPE_F16), MGEA_EINVAL, "op_f32_to_16: bad argument");
+    return launch_f32_to_bf16(src_dev, dst_dev, n, (hipStream_t)stream, dtype == MGEA_DTYPE_F16);
+}
+
+int mgea_op_fold_ln_16(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* bias_dev, int32_t N, int32_t K,
+                       int32_t dtype, void* wf_out_dev, float* c1_out_dev, float* c2_out_dev, void* stream) {
+    MGEA_REQUIRE(w_dev && gamma_dev && beta_dev && bias_dev && wf_out_dev && c1_out_dev && c2_out_dev && N > 0 && K > 0 &&
+                     (dtype == MGEA_DTYPE_BF16 || dtype == MGEA_DTYPE_F16),
+                 MGEA_EINVAL, "op_fold_ln_16: bad argument");
+    return launch_fold_ln_weights_bf16(w_dev, gamma_dev, beta_dev, bias_dev, wf_out_dev, c1_out_dev, c2_out_dev, N, K, (hipStream_t)stream,
+                                       dtype == MGEA_DTYPE_F16);
+}
+
+int mgea_op_attention16(const void* qkv_dev, const int32_t* mask_dev, const int32_t* cu_seqlens_dev, void* out_dev, int32_t B, int32_t T,
+                        int32_t n_head, int32_t head_dim, int32_t dtype, void* pages_dev, int32_t n_pages,
+                        const int32_t* page_table_dev, int32_t max_pages, void* stream) {
+    MGEA_REQUIRE(qkv_dev && out_dev && n_head > 0 && (dtype == MGEA_DTYPE_BF16 || dtype == MGEA_DTYPE_F16), MGEA_EINVAL,
+                 "op_attention16: NULL argument or dtype %d (bf16, f16)", dtype);
+    if (!pages_dev)
+        return launch_attn_bf16(qkv_dev, mask_dev, out_dev, B, T, n_head, head_dim, (hipStream_t)stream, dtype == MGEA_DTYPE_F16, nullptr,
+                                cu_seqlens_dev);
+    MGEA_REQUIRE(dtype == MGEA_DTYPE_F16 && !cu_seqlens_dev && page_table_dev && n_pages > 0 && max_pages > 0, MGEA_EINVAL,
+                 "op_attention16: pages need fp16, a page table and padded rows");
+    const KvPages pg{op_pool(pages_dev, n_pages, n_head, head_dim, 1, 0), 0, page_table_dev, max_pages};
+    return launch_attn_bf16(qkv_dev, mask_dev, out_dev, B, T, n_head, head_dim, (hipStream_t)stream, 1, &pg, nullptr);
+}
+
+int mgea_op_kv_scatter_f16(const void* qkv_dev, void* pages_dev, int32_t n_pages, const int32_t* page_table_dev, int32_t max_pages,
+                           const int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                           void* stream) {
+    MGEA_REQUIRE(qkv_dev && pages_dev && page_table_dev && ctx_len_dev && n_pages > 0 && max_pages > 0 && B > 0 && T > 0 && n_head > 0 &&
+                     head_dim > 0,
+                 MGEA_EINVAL, "op_kv_scatter_f16: bad argument");
+    return launch_kv_scatter_f16(qkv_dev, op_pool(pages_dev, n_pages, n_head, head_dim, 1, 0), 0, page_table_dev, max_pages, ctx_len_dev,
+                                 lens_dev, B, T, n_head * head_dim, (hipStream_t)stream);
+}
+
+int mgea_op_dec_embed_f16(const int32_t* ids_dev, const int32_t* lens_dev, const int32_t* ctx_len_dev, const float* tok_emb_dev,
+                          const float* pos_emb_dev, void* x_out_dev, float* rowstat_out_dev, int32_t* mask_out_dev, float eps, int32_t B,
+                          int32_t T, int32_t C, int32_t vocab, int32_t pos_rows, int32_t absolute_pos, int32_t* err_flag_dev,
+                          void* stream) {
+    MGEA_REQUIRE(ids_dev && tok_emb_dev && pos_emb_dev && x_out_dev && rowstat_out_dev && B > 0 && T > 0 && vocab > 0 && pos_rows > 0,
+                 MGEA_EINVAL, "op_dec_embed_f16: bad argument");
+    return launch_dec_embed_f16(ids_dev, lens_dev, ctx_len_dev, tok_emb_dev, pos_emb_dev, x_out_dev, rowstat_out_dev, mask_out_dev, eps, B,
+                                T, C, vocab, pos_rows, absolute_pos, err_flag_dev, (hipStream_t)stream);
+}
+
+int mgea_op_attention_paged(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t dtype, int32_t arith_batch,
+                            const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev, const int32_t* lens_dev,
+                            float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t no_split, int32_t* info_out,
+                            void* stream) {
+    MGEA_REQUIRE(qkv_dev && pages_dev && page_table_dev && ctx_len_dev && out_dev && B > 0 && T > 0 && n_head > 0 && n_pages > 0 &&
+                     max_pages > 0 && (dtype == MGEA_DTYPE_F32 || dtype == MGEA_DTYPE_F16),
+                 MGEA_EINVAL, "op_attention_paged: bad argument");
+    MGEA_REQUIRE(arith_batch == 0 || (arith_batch >= B && (int64_t)max_pages * arith_batch <= n_pages), MGEA_EINVAL,
+                 "op_attention_paged: arith_batch %d must be >= B with max_pages * arith_batch <= n_pages", arith_batch);
+    const KvPool pool = op_pool(pages_dev, n_pages, n_head, head_dim, dtype == MGEA_DTYPE_F16, arith_batch);
+    hipStream_t st = (hipStream_t)stream;
+    AttnSplit sp{nullptr, nullptr, MGEA_ATTN_MAX_SPLIT, MGEA_ATTN_SPLIT_ITEMS};
+    DevGroup tmp;   // frees the scratch on return: the stream is synchronised first
+    if (!no_split) {
+        const size_t part_bytes = (size_t)sp.max_items * sp.max_split * attn_part_floats(head_dim) * sizeof(float);
+        MGEA_REQUIRE(tmp.alloc(&sp.part, part_bytes) == MGEA_OK, MGEA_ENOMEM, "op_attention_paged: allocation of the split partials failed");
+        MGEA_REQUIRE(tmp.alloc(&sp.count, (size_t)sp.max_items * sizeof(int32_t)) == MGEA_OK, MGEA_ENOMEM,
+                     "op_attention_paged: allocation of the split counters failed");
+        MGEA_CHECK_HIP(hipMemsetAsync(sp.count, 0, (size_t)sp.max_items * sizeof(int32_t), st));
+    }
+    // what the launcher will decide from the same arguments (attn_paged.hip): workgroups per (row, head, query)
+    if (info_out) info_out[0] = no_split ? 1 : attn_split_count(B, n_head, T, max_pages);
+    const int rc = launch_attn_paged(qkv_dev, pool, 0, page_table_dev, max_pages, ctx_len_dev, lens_dev, out_dev, B, T, n_head * head_dim, 0,
+                                     st, no_split ? nullptr : &sp);
+    const hipError_t e = hipStreamSynchronize(st);
+    MGEA_TRY(rc);
+    MGEA_CHECK_HIP(e);
+    return MGEA_OK;
+}
+
 /* ablation / micro-benchmark hook for the fused skinny GEMM (tools/skinny_bench.py): EPI_ACT or
  * EPI_RES on caller buffers; dbg bits skip A loads (1), W loads (2), MFMAs (4). */
 int64_t mgea_op_tiled_weight_floats(int32_t N, int32_t K) { return wtile_floats(N, K); }

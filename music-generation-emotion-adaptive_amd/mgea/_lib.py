@@ -101,6 +101,13 @@ PROTOTYPES = {
     "mgea_op_fold_ln_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "mgea_op_attention_bf16": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_layernorm_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _P]),
+    "mgea_op_gemm_f16_ln": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32), _P]),
+    "mgea_op_f32_to_16": (C.c_int, [_P, _P, _I64, _I32, _P]),
+    "mgea_op_fold_ln_16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "mgea_op_attention16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P]),
+    "mgea_op_kv_scatter_f16": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_dec_embed_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "mgea_op_attention_paged": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, C.POINTER(_I32), _P]),
     "mgea_op_tiled_weight_floats": (C.c_int64, [_I32, _I32]),
     "mgea_op_tile_weights": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "mgea_op_tile_rows": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),

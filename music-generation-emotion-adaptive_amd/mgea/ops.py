@@ -135,6 +135,232 @@ def layernorm_bf16(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float
     return y
 
 
+# ---- the 16-bit kernels of the fp16 decoder and the paged attention (mgea_op_* of the same names) ----
+_DTYPE16 = {torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def _dtype16(t: torch.Tensor) -> int:
+    if t.dtype not in _DTYPE16:
+        raise RuntimeError(f"a bf16 or fp16 tensor is needed, got {t.dtype}")
+    return _DTYPE16[t.dtype]
+
+
+def gemm_f16_ln(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+                gelu: bool = False, ln: Optional[dict] = None, f32_out: bool = False, info: Optional[list] = None,
+                epi: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """gemm_bf16's folded-LayerNorm epilogues on fp16 operands (persistent kernel only): ln as in gemm_bf16 -> epi 3 / 4 (gelu) / 5,
+    fp16 output; f32_out -> epi 6, a w^T + bias as fp32 [M, N].  epi overrides the choice (the launcher's refusals)."""
+    lib = _lib.load()
+    a, w = _dev(a.half()), _dev(w.half())
+    M, K = a.shape
+    N = w.shape[0]
+    b = None if bias is None else _dev(bias.float())
+    r = None if res is None else _dev(res.half())
+    rowstat = c1 = g = be = stats = None
+    e = 6 if f32_out else -1
+    if ln is not None:
+        rowstat = None if ln.get("rowstat") is None else _dev(ln["rowstat"].float())
+        if "c1" in ln:
+            e, c1 = (4 if gelu else 3), (None if ln["c1"] is None else _dev(ln["c1"].float()))
+        else:
+            e, g, be = 5, _dev(ln["g"].float()), _dev(ln["b"].float())
+            if ln.get("stats"):
+                stats = torch.zeros(M, N // 256, 2, dtype=torch.float32, device=a.device)
+    if epi is not None:
+        e = int(epi)
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if e == 6 else torch.float16, device=a.device)
+    io = (C.c_int32 * 2)(-1, -1)
+    check(lib.mgea_op_gemm_f16_ln(ptr(a), ptr(w), ptr(b), ptr(r), ptr(out), M, N, K, e, ptr(rowstat), ptr(c1), ptr(g), ptr(be),
+                                  ptr(stats), io, stream_ptr()))
+    if info is not None:
+        info[:] = [int(io[0]), int(io[1])]
+    return (out, stats) if stats is not None else out
+
+
+def f32_to_16(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """fp32 -> bf16 / fp16 by the library's convert kernel (round to nearest even)."""
+    lib = _lib.load()
+    x = _dev(x.float())
+    out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    check(lib.mgea_op_f32_to_16(ptr(x), ptr(out), x.numel(), _dtype16(out), stream_ptr()))
+    return out
+
+
+def fold_ln_16(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: torch.Tensor, dtype: torch.dtype):
+    """fold_ln_bf16 with the 16-bit type as an argument -> (dtype(W diag(gamma)) [N,K], c1, c2)."""
+    lib = _lib.load()
+    w, gamma, beta, bias = _dev(w.float()), _dev(gamma.float()), _dev(beta.float()), _dev(bias.float())
+    N, K = w.shape
+    wf = torch.empty(N, K, dtype=dtype, device=w.device)
+    c1 = torch.empty(N, dtype=torch.float32, device=w.device)
+    c2 = torch.empty(N, dtype=torch.float32, device=w.device)
+    check(lib.mgea_op_fold_ln_16(ptr(w), ptr(gamma), ptr(beta), ptr(bias), N, K, _dtype16(wf), ptr(wf), ptr(c1), ptr(c2), stream_ptr()))
+    return wf, c1, c2
+
+
+def kv_page_elems(n_pages: int, n_head: int, head_dim: int) -> int:
+    """elements of one layer of n_pages KV pages (csrc/common.h KvPool)"""
+    return int(n_pages) * 2 * int(n_head) * _lib.KV_PAGE_TOKENS * int(head_dim)
+
+
+def _int_view(t: torch.Tensor) -> torch.Tensor:
+    """the same bits as integers (copies of these are bit copies whatever the floats are)"""
+    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def kv_pages_write(image: torch.Tensor, k: torch.Tensor, v: torch.Tensor, page_table, pos0=None, valid=None) -> torch.Tensor:
+    """Host side of the page layout.  image: a CPU tensor of kv_page_elems(n_pages, H, dh) fp16 or fp32 elements (one layer of pages);
+    k, v [B, T, H, dh] of the same dtype.  Token (b, t) with valid[b, t] (None: all) goes to position pos0[b] + t (None: t) of row b:
+    logical page pos // 64 -> physical page_table[b][page], slot pos % 64; positions in logical pages >= page_table.shape[1] are
+    dropped, as the kernels drop them.  K is [dh / G][64][G], V is [64][dh] per (page, K | V, head), G = 16 bytes of elements.
+    Written in place, bit for bit; returns image."""
+    B, T, H, dh = k.shape
+    G = 16 // image.element_size()
+    P = _lib.KV_PAGE_TOKENS
+    table = np.asarray(page_table, dtype=np.int64).reshape(B, -1)
+    n_pages = image.numel() // (2 * H * P * dh)
+    img = _int_view(image).view(n_pages, 2, H, P * dh)
+    ki, vi = _int_view(k.contiguous()), _int_view(v.contiguous())
+    for b in range(B):
+        t = np.arange(T) if valid is None else np.nonzero(np.asarray(valid[b]).astype(bool))[0]
+        pos = t + (0 if pos0 is None else int(pos0[b]))
+        keep = (pos // P) < table.shape[1]
+        t, pos = t[keep], pos[keep]
+        if t.size == 0:
+            continue
+        phys = torch.from_numpy(table[b][pos // P])
+        slot = torch.from_numpy(pos % P)
+        tt = torch.from_numpy(t)
+        for h in range(H):
+            kimg = img[:, 0, h].view(n_pages, dh // G, P, G)
+            vimg = img[:, 1, h].view(n_pages, P, dh)
+            kimg[phys, :, slot, :] = ki[b, tt, h].view(-1, dh // G, G)
+            vimg[phys, slot, :] = vi[b, tt, h]
+    return image
+
+
+def kv_pages_read(image: torch.Tensor, page_table, b: int, n_tok: int, n_head: int, head_dim: int):
+    """The first n_tok cached tokens of row b out of a page image (CPU tensor) -> (k, v) [n_tok, H, dh] in the image's dtype."""
+    H, dh, P = n_head, head_dim, _lib.KV_PAGE_TOKENS
+    G = 16 // image.element_size()
+    table = np.asarray(page_table, dtype=np.int64).reshape(-1, np.asarray(page_table).shape[-1])
+    n_pages = image.numel() // (2 * H * P * dh)
+    img = image.view(n_pages, 2, H, P * dh)
+    pos = np.arange(n_tok)
+    phys, slot = torch.from_numpy(table[b][pos // P]), torch.from_numpy(pos % P)
+    k = torch.stack([img[:, 0, h].view(n_pages, dh // G, P, G)[phys, :, slot, :].reshape(n_tok, dh) for h in range(H)], 1)
+    v = torch.stack([img[:, 1, h].view(n_pages, P, dh)[phys, slot, :] for h in range(H)], 1)
+    return k, v
+
+
+def attention16(qkv: torch.Tensor, n_head: int, mask: Optional[torch.Tensor] = None, cu: Optional[torch.Tensor] = None,
+                pages: Optional[torch.Tensor] = None, page_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 16-bit flash attention on a bf16 or fp16 qkv (its dtype picks the instantiation): [B, T, 3C] -> [B, T, C], or with cu
+    [B + 1] (packed rows) [cu[B], 3C] -> [cu[B], C].  pages (fp16 only): one layer of device KV pages, written in place at position
+    t for every key whose mask bit is set; page_table [B, max_pages] int32."""
+    lib = _lib.load()
+    if qkv.dtype not in _DTYPE16:
+        raise RuntimeError("attention16 takes a bf16 or fp16 qkv")
+    qkv = _dev(qkv)
+    Cd = qkv.shape[-1] // 3
+    dh = Cd // n_head
+    m32 = None if mask is None else _dev(mask.to(torch.int32))
+    c32 = None
+    if cu is not None:
+        c32 = _dev(cu.to(torch.int32))
+        lens = (cu[1:] - cu[:-1]).cpu()
+        B, T = int(lens.numel()), int(lens.max())
+        if qkv.ndim != 2 or int(cu[-1]) != qkv.shape[0]:
+            raise RuntimeError("packed attention16: qkv must be [cu[B], 3C]")
+    else:
+        B, T = qkv.shape[0], qkv.shape[1]
+    out = torch.empty(*qkv.shape[:-1], Cd, dtype=qkv.dtype, device=qkv.device)
+    n_pages = max_pages = 0
+    pt = None
+    if pages is not None:
+        if pages.dtype != torch.float16 or pages.device != qkv.device or not pages.is_contiguous():
+            raise RuntimeError("attention16: pages must be a contiguous fp16 device tensor")
+        n_pages = pages.numel() // kv_page_elems(1, n_head, dh)
+        pt = _dev(page_table.to(torch.int32))
+        max_pages = pt.shape[1]
+        if pt.shape[0] != B or int(pt.min()) < 0 or int(pt.max()) >= n_pages:
+            raise RuntimeError("attention16: page table must be [B, max_pages] with entries in [0, n_pages)")
+    check(lib.mgea_op_attention16(ptr(qkv), ptr(m32), ptr(c32), ptr(out), B, T, n_head, dh, _dtype16(qkv), ptr(pages), n_pages, ptr(pt),
+                                  max_pages, stream_ptr()))
+    return out
+
+
+def kv_scatter_f16(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_table: torch.Tensor, ctx_len: torch.Tensor,
+                   lens: Optional[torch.Tensor] = None) -> None:
+    """K | V of the fp16 qkv rows [B, T, 3C] into the fp16 device pages (in place) at positions ctx_len[b] + t, t < lens[b]."""
+    lib = _lib.load()
+    if qkv.dtype != torch.float16 or pages.dtype != torch.float16 or not pages.is_contiguous():
+        raise RuntimeError("kv_scatter_f16 takes fp16 qkv rows and contiguous fp16 pages")
+    qkv = _dev(qkv)
+    B, T, C3 = qkv.shape
+    dh = C3 // 3 // n_head
+    n_pages = pages.numel() // kv_page_elems(1, n_head, dh)
+    pt = _dev(page_table.to(torch.int32))
+    if pt.shape[0] != B or int(pt.min()) < 0 or int(pt.max()) >= n_pages:
+        raise RuntimeError("kv_scatter_f16: page table must be [B, max_pages] with entries in [0, n_pages)")
+    cl = _dev(ctx_len.to(torch.int32))
+    l32 = None if lens is None else _dev(lens.to(torch.int32))
+    check(lib.mgea_op_kv_scatter_f16(ptr(qkv), ptr(pages), n_pages, ptr(pt), pt.shape[1], ptr(cl), ptr(l32), B, T, n_head, dh, stream_ptr()))
+
+
+def dec_embed_f16(ids: torch.Tensor, tok_emb: torch.Tensor, pos_emb: torch.Tensor, lens: Optional[torch.Tensor] = None,
+                  ctx_len: Optional[torch.Tensor] = None, absolute_pos: bool = False, eps: float = 1e-5):
+    """The embedding kernel of the fp16 prefill on ids [B, T] -> (x [B, T, C] fp16, rowstat [B, T, 2], mask [B, T] int32, flags int)."""
+    lib = _lib.load()
+    ids = _dev(ids.to(torch.int32))
+    tok_emb, pos_emb = _dev(tok_emb.float()), _dev(pos_emb.float())
+    B, T = ids.shape
+    V, Cd = tok_emb.shape
+    dev = ids.device
+    x = torch.empty(B, T, Cd, dtype=torch.float16, device=dev)
+    rs = torch.empty(B, T, 2, dtype=torch.float32, device=dev)
+    mk = torch.full((B, T), -1, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    l32 = None if lens is None else _dev(lens.to(torch.int32))
+    c32 = None if ctx_len is None else _dev(ctx_len.to(torch.int32))
+    check(lib.mgea_op_dec_embed_f16(ptr(ids), ptr(l32), ptr(c32), ptr(tok_emb), ptr(pos_emb), ptr(x), ptr(rs), ptr(mk), float(eps), B, T, Cd,
+                                    V, pos_emb.shape[0], int(bool(absolute_pos)), ptr(flag), stream_ptr()))
+    return x, rs, mk, int(flag.item())
+
+
+def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_table: torch.Tensor, ctx_len: torch.Tensor,
+                    lens: Optional[torch.Tensor] = None, arith_batch: int = 0, split: bool = True,
+                    info: Optional[list] = None) -> torch.Tensor:
+    """The decode / extend attention over one layer of device KV pages (fp32 or fp16 tensor): the queries are columns 0..C-1 of the
+    fp32 qkv [B, T, 3C]; row b attends to its ctx_len[b] + (lens[b] or T) cached tokens.  split=False: never the split-context form.
+    info: a list that receives [workgroups per (row, head, query)] of the launch (1 = the unsplit kernel)."""
+    lib = _lib.load()
+    qkv = _dev(qkv.float())
+    B, T, C3 = qkv.shape
+    Cd = C3 // 3
+    dh = Cd // n_head
+    if pages.dtype not in (torch.float32, torch.float16) or not pages.is_contiguous() or pages.device != qkv.device:
+        raise RuntimeError("attention_paged: pages must be a contiguous fp32 or fp16 device tensor")
+    n_pages = pages.numel() // kv_page_elems(1, n_head, dh)
+    pt = _dev(page_table.to(torch.int32))
+    if pt.shape[0] != B or int(pt.min()) < 0 or int(pt.max()) >= n_pages:
+        raise RuntimeError("attention_paged: page table must be [B, max_pages] with entries in [0, n_pages)")
+    cl = _dev(ctx_len.to(torch.int32))
+    l32 = None if lens is None else _dev(lens.to(torch.int32))
+    need = int(((cl.cpu() + (T if lens is None else l32.cpu()) + _lib.KV_PAGE_TOKENS - 1) // _lib.KV_PAGE_TOKENS).max())
+    if need > pt.shape[1]:
+        raise RuntimeError(f"attention_paged: a row needs {need} pages, the table has {pt.shape[1]}")
+    out = torch.empty(B, T, Cd, dtype=torch.float32, device=qkv.device)
+    io = (C.c_int32 * 1)(-1)
+    check(lib.mgea_op_attention_paged(ptr(qkv), ptr(pages), n_pages, _lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32,
+                                      int(arith_batch), ptr(pt), pt.shape[1], ptr(cl), ptr(l32), ptr(out), B, T, n_head, dh,
+                                      int(not split), io, stream_ptr()))
+    if info is not None:
+        info[:] = [int(io[0])]
+    return out
+
+
 def check_repetition_penalty(penalty) -> Optional[float]:
     """None -> None (no penalty).  Otherwise the penalty as a float, which must be finite and > 0 also once held as
     fp32 (the kernels' precision): ValueError otherwise, as transformers' RepetitionPenaltyLogitsProcessor raises."""
