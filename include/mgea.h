@@ -194,9 +194,10 @@ int mgea_decoder_generate_rows(mgea_decoder* h, const int32_t* prompt_ids_dev, c
  * sequence_bias / suppress_tokens / min_new_tokens, OpenAI's is logit_bias.  At every decode step of row b, on the raw head logits x:
  *   1. the repetition penalty over seen_b, exactly as in mgea_decoder_generate_penalized;
  *   2. x[i] += bias_dev[i], one fp32 add (-inf bans id i); a row with bias_dev == NULL is not touched (no + 0);
- *   3. if the row's eos_id >= 0 and it has produced fewer than min_new_tokens ids so far (its step index, word 1 of its Philox
+ *   3. the token grammar, for a row that has a state (mgea_decoder_set_grammar): x[i] = -inf wherever next[s_b][class_of[i]] < 0;
+ *   4. if the row's eos_id >= 0 and it has produced fewer than min_new_tokens ids so far (its step index, word 1 of its Philox
  *      counter), x[eos_id] = -inf;
- *   4. the sampler runs unchanged on the result: / temperature, top-k, top-p, softmax, Philox draw.  top_k == 1 is the exact argmax
+ *   5. the sampler runs unchanged on the result: / temperature, top-k, top-p, softmax, Philox draw.  top_k == 1 is the exact argmax
  *      of the processed row (ties to the lowest id, no temperature division).  A banned id has probability exactly 0 and is never
  *      drawn, also where it is among the top_k kept because fewer than top_k ids are admissible.
  * Checked on the host (MGEA_EINVAL naming the row): reserved == 0 and 0 <= min_new_tokens <= n_steps.  The caller guarantees the rest,
@@ -225,15 +226,16 @@ int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids
  * returns no scores (the serving APIs' counterparts are OpenAI's logprobs, HuggingFace's output_scores / compute_transition_scores).
  * At every decode step of row b, on the raw head logits x of the row:
  *   0. the raw statistics m = max_i x_i and log sum_i exp(x_i - m), fp32, in a fixed order (deterministic from run to run);
- *   1.-4. the processing steps of mgea_row_logits: penalty, bias, EOS ban, then / temperature, top-k, top-p, softmax, Philox draw;
- *   5. f = forced_ids_dev[b * n_steps + t] for the row's step index t (word 1 of its Philox counter): f >= 0 replaces the drawn id
+ *   1.-5. the processing steps of mgea_row_logits: penalty, bias, (grammar,) EOS ban, then / temperature, top-k, top-p, softmax,
+ *      Philox draw;
+ *   6. f = forced_ids_dev[b * n_steps + t] for the row's step index t (word 1 of its Philox counter): f >= 0 replaces the drawn id
  *      for everything downstream -- ids_out, EOS and budget bookkeeping, the presence bitmap, the next step's input; -1 leaves the
  *      draw alone (so does every other negative value).  f >= vocab is clamped to vocab - 1 and sets bit 0 of the sticky error
  *      flags (mgea_decoder_error_flags);
- *   6. with id = what the step writes to ids_out:
+ *   7. with id = what the step writes to ids_out:
  *        logprobs_out[b, t]        = x_id - m - log sum_i exp(x_i - m), natural log, taken over the RAW logits of step 0 -- before
  *                                    penalty, bias, EOS ban, temperature, top-k and top-p: a function of the model alone;
- *        choice_logprobs_out[b, t] = log(e_id / total) under the distribution of step 4, the one the draw was made from: -inf for
+ *        choice_logprobs_out[b, t] = log(e_id / total) under the distribution of step 5, the one the draw was made from: -inf for
  *                                    an id outside the kept set (only a forced id can be), 0 for a greedy row that keeps its argmax.
  *      A finished row (ids_out -1) has 0.0 in both, as have the steps that never ran.
  * forced_ids_dev [B, n_steps] int32 (device) or NULL = nothing forced; it is copied into the engine's own buffer in stream order, so
@@ -247,6 +249,44 @@ int mgea_decoder_generate_rows_scored(mgea_decoder* h, const int32_t* prompt_ids
                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
                                       const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
                                       float* choice_logprobs_out_dev, void* stream);
+
+/* Token grammars: a finite automaton over token classes, applied as a mask in the sampler and advanced on the device inside the step
+ * (guided decoding; build-defined, the reference has none).  A grammar is two tables,
+ *   class_of [vocab]           int32: the class 0 <= c < n_class of every id;
+ *   next     [n_state][n_class] int32: the state after drawing an id of class c in state s, -1 = ids of that class are banned in s.
+ * An engine holds one grammar at a time, shared by all rows (several rule sets: one table with disjoint state ranges); every row of a
+ * generation has a start state, -1 = the row is not constrained.  Caps: n_class <= 4096, n_state <= 4096, n_state * n_class <= 1 << 20.
+ * The grammar is step 3 of the per-step order of mgea_row_logits: 1. repetition penalty; 2. bias; 3. x[i] = -inf wherever
+ * next[s_b][class_of[i]] < 0, s_b = the row's current state; 4. the EOS ban of min_new_tokens; 5. the sampler as it is.  After the
+ * step, with id = what the step writes to ids_out (the draw, or a forced id), a row that is not finished moves to
+ * next[s_b][class_of[id]].  A negative transition (only a forced id can cause one) leaves the state where it is and sets bit 1 of the
+ * sticky error flags (mgea_decoder_error_flags); that id's choice log-probability is -inf.  A row whose mask, bias and EOS ban
+ * together leave nothing yields id 0, as a row whose bias bans everything does.  Finished rows and rows with state -1 are not
+ * touched: no masking, no + 0.
+ *
+ * mgea_decoder_set_grammar: host tables, validated on the host before anything is enqueued (MGEA_EINVAL naming the offender): the
+ * caps, every class_of value in [0, n_class), every next value in [-1, n_state), every state admits at least one class that has at
+ * least one id.  The tables are copied in stream order into buffers the handle owns (allocated at create, so the step graphs hold
+ * stable pointers), the call synchronises `stream` before it returns.  n_state == 0 clears the grammar (the tables may be NULL). */
+int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, const int32_t* next_host, int32_t n_state, int32_t n_class,
+                             void* stream);
+/* mgea_decoder_generate_rows_biased / _scored under the grammar: start_states [B] (host, read before the call returns), -1 = none.
+ * With every start state -1, or start_states == NULL, this IS mgea_decoder_generate_rows_biased (logprobs_out_dev == NULL: then
+ * forced_ids_dev and choice_logprobs_out_dev must be NULL too) or mgea_decoder_generate_rows_scored: the same launches and ids.
+ * Otherwise MGEA_EINVAL if no grammar is set or a start state is >= n_state, and the generation takes the grammar form: the biased
+ * form's launch sequence with the grammar sampler (presence bitmaps kept), its own step graphs.  Rows with state -1 keep the ids they
+ * have in a batch of that size without a grammar. */
+int mgea_decoder_generate_rows_grammar(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows /* NULL ok */,
+                                       const int32_t* start_states /* host [B], -1 = none; NULL ok */,
+                                       const int32_t* forced_ids_dev /* NULL ok */, int32_t* ids_out_dev,
+                                       float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                       void* stream);
+/* Every row's state after the last grammar generation -> out_dev [B] int32 (device); -1 for a row without one. */
+int mgea_decoder_grammar_states(mgea_decoder* h, int32_t* out_dev, void* stream);
+/* out[0] n_state and [1] n_class of the grammar set now (0: none), [2] mgea_decoder_set_grammar uploads over the handle's lifetime,
+ * [3] decode steps of the last generate() that ran in the grammar form (0 if it did not). */
+int mgea_decoder_grammar_info(mgea_decoder* h, int64_t* out /* [4] */);
 
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
@@ -281,7 +321,8 @@ int mgea_decoder_qkv0_table_bytes(mgea_decoder* h, int64_t* bytes_out);
 /* Token ids outside [0, vocab) make nn.Embedding raise IndexError in the reference (api_cache.py:99).
  * Here they are clamped on the device and recorded in a sticky flag word, so that no call has to
  * synchronise to validate its input: this call synchronises `stream`, returns the flags (bit 0 = an id
- * was clamped since the last call) in *flags_out (host) and clears them. */
+ * was clamped since the last call; bit 1 = a forced id was banned by the row's grammar state, mgea_decoder_set_grammar) in *flags_out
+ * (host) and clears them. */
 int mgea_decoder_error_flags(mgea_decoder* h, int32_t* flags_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -494,6 +535,14 @@ int mgea_op_sample_rows_scored(const float* logits_dev, int32_t B, int32_t V, co
                                const uint32_t* presence_dev, const mgea_row_logits* logits_rows, int64_t step, int32_t* ids_out_dev,
                                float* probs_out_dev, const int32_t* forced_ids_dev, float* logprobs_out_dev,
                                float* choice_logprobs_out_dev, void* stream);
+/* mgea_op_sample_rows_biased as the grammar sampler of mgea_decoder_generate_rows_grammar runs it: class_of_dev [V] and next_dev
+ * [n_state][n_class] int32 (device, not validated: the caller guarantees mgea_decoder_set_grammar's rules), states_in_dev [B] int32
+ * (-1 = the row has no grammar).  Row b with state s >= 0 loses every id whose class s bans before the EOS ban; states_out_dev [B]
+ * receives next[s][class_of[id]] for the id it draws (states_in[b] for a row at -1).  Synchronises `stream`. */
+int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                                const mgea_row_logits* logits_rows, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
+                                int32_t n_class, const int32_t* states_in_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev,
+                                int32_t* states_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

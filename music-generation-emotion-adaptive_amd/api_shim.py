@@ -12,6 +12,7 @@ from __future__ import annotations
 
 
 CONSTRAINTS = (None, "notes", "scale")
+GRAMMARS = (None, "tracks")
 
 
 def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None):
@@ -30,23 +31,37 @@ def create_constrained_app(model, seq_len: int, temperature: float = 1.0, top_k:
     note, instrument and [END_SEQUENCE] tokens can be drawn (the detokeniser drops everything else); "scale" = also only notes of
     the emotion's key (mapping["key"]; out_of_scale_bias = -inf bans the others, a finite value is added to their logits instead).
     min_new_tokens > 0 keeps [END_SEQUENCE] from being drawn before that many tokens.  The bias vectors (generate_music.constraints)
-    are built once per key and kept on the device; the response carries X-Constraint."""
+    are built once per key and kept on the device; the response carries X-Constraint.  (create_grammar_app: this endpoint under a
+    token grammar.)"""
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
                       out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens)
 
 
+def create_grammar_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                       constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar="tracks"):
+    """create_constrained_app under a token grammar (create_constrained_app keeps its parameter list; create_batched_app and
+    create_best_of_app take the same keyword).  grammar (build-defined, the reference samples the raw vocabulary): None = none, or
+    "tracks" = generate_music.grammar.track_grammar of the vocabulary -- after an instrument only a note may follow, a track's START
+    times never go back, control tokens are not drawn.  Every request starts in the state its prompt leads to (OPEN: the prompt names
+    the instruments); the response carries X-Grammar.  It composes with constrain="scale": the bias bans the out-of-scale notes, the
+    grammar orders the rest."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar)
+
+
 def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                       max_batch=None, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
+                       max_batch=None, grammar=None, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
     """create_app with request batching: concurrent requests are coalesced into batched generations by app.state.batcher
     (mgea.serve.RequestBatcher, up to max_batch rows each -- default the model's max_batch) instead of one sample_kvcache call per
     request.  Each request keeps its own seed and budget; the response also carries X-Batch-Rows, the number of requests its
-    generation served.  app.state.batcher.close() stops the worker."""
+    generation served.  app.state.batcher.close() stops the worker.  grammar: None or "tracks", as in create_grammar_app (the batcher
+    groups requests by their grammar object; the app has one)."""
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=True, max_batch=max_batch,
-                      constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens)
+                      constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar)
 
 
 def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                       best_of: int = 4, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
+                       best_of: int = 4, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None):
     """create_constrained_app whose requests draw best_of candidates in one batch and return the most likely one
     (generate_music.generate.generate_best_of: highest mean raw log-probability per generated token).  best_of is capped by the
     model's max_batch (ValueError here beyond it).  The response adds X-Best-Of and, when anything was generated, X-Mean-Logprob.  Build-defined: the reference
@@ -55,15 +70,17 @@ def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int
     if best_of < 1 or best_of > int(model.max_batch):
         raise ValueError(f"best_of {best_of} outside [1, max_batch={model.max_batch}]")
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
-                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, best_of=best_of)
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, best_of=best_of, grammar=grammar)
 
 
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
-               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0):
+               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     if constrain not in CONSTRAINTS:
         raise ValueError(f"constrain must be one of {CONSTRAINTS}, got {constrain!r}")
+    if grammar not in GRAMMARS:
+        raise ValueError(f"grammar must be one of {GRAMMARS}, got {grammar!r}")
     out_of_scale_bias = float(out_of_scale_bias)
     if out_of_scale_bias != out_of_scale_bias or out_of_scale_bias == float("inf"):
         raise ValueError("out_of_scale_bias must be finite or -inf")
@@ -105,6 +122,16 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             bias_cache[k] = torch.from_numpy(vec).to(model._need().device)
         return bias_cache[k]
 
+    grammar_cache = []   # the vocabulary's track grammar, built at the first request (ONE object: the batcher groups by it)
+
+    def token_grammar():
+        if grammar is None:
+            return None
+        if not grammar_cache:
+            from generate_music.grammar import track_grammar
+            grammar_cache.append(track_grammar(gen.tok2id))
+        return grammar_cache[0]
+
     @app.post("/generate")
     def generate_music(prompt: str = prompt_param):
         label = inference.predict(prompt)                                     # api_cache.py:189
@@ -120,10 +147,15 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
         if constrain is not None:
             extra["X-Constraint"] = constrain
         more = {} if bias is None and not min_new_tokens else dict(logit_bias=bias, min_new_tokens=int(min_new_tokens))
+        tg = token_grammar()
+        if tg is not None:
+            more["grammar"] = tg
+            extra["X-Grammar"] = grammar
         if best_of:   # best_of candidates of the same request in one batch, the most likely one kept
             tokens, _, means, best = gen.generate_best_of(model, gen_prompt, best_of, max_len=seq_len, temperature=temperature,
                                                           top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                                                          logit_bias=bias, min_new_tokens=int(min_new_tokens), return_all=True)
+                                                          logit_bias=bias, min_new_tokens=int(min_new_tokens), return_all=True,
+                                                          grammar=tg)
             extra["X-Best-Of"] = str(best_of)
             if means[best] > float("-inf"):   # (nothing generated -- seq_len within the prompt -- has no mean)
                 extra["X-Mean-Logprob"] = f"{means[best]:.6f}"
@@ -133,7 +165,7 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             tokens = fut.result()
             extra["X-Batch-Rows"] = str(fut.batch_rows)
         else:
-            call = gen.sample_kvcache_biased if more else gen.sample_kvcache
+            call = gen.sample_kvcache_grammar if tg is not None else gen.sample_kvcache_biased if more else gen.sample_kvcache
             tokens = call(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu", top_p=top_p,
                           repetition_penalty=repetition_penalty, **more)   # :204
         if app.state.on_tokens is not None:

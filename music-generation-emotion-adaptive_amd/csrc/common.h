@@ -208,18 +208,21 @@ static inline SamplerParams sampler_params(const mgea_row_sampler& r) {
     return SamplerParams{r.temperature, r.top_k, r.top_p, r.eos_id, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.repetition_penalty,
                          r.stream, r.max_new_tokens > 0 ? r.max_new_tokens : MGEA_NO_BUDGET, MGEA_NO_BUDGET, 0, 0};
 }
-// The tail of a decode step -- everything after the LM head -- has four launch sequences, and a generation runs one of them on every step:
+// The tail of a decode step -- everything after the LM head -- has five launch sequences, and a generation runs one of them on every step:
 //   GREEDY (every row has top_k == 1)  the head leaves per-tile (max, argmax) partials and no logits row; an argmax tail merges them
 //   SAMPLED                            the head writes the logits row; the plain sampler draws from it
 //   PENALIZED (a row's penalty != 1)   as SAMPLED with the PENALTY sampler over the rows' presence bitmaps, which the tail keeps up to
 //                                      date; a greedy row is top_k = 1 of its penalized row (the head's partials know no penalty)
 //   BIASED (a row's bias or min_new)   as PENALIZED with the BIAS sampler and the rows' bias buffer (a penalty of 1 changes nothing)
+//   GRAMMAR (a row's start state >= 0) as BIASED with the GRAMMAR sampler: the row's automaton state masks the classes its table bans
+//                                      and the sampler's bookkeeping thread moves the state on (GrammarArgs below)
 // The form is the key of the captured step graphs: every other setting of a request lives in the rows' device records.
-enum class StepForm { GREEDY = 0, SAMPLED, PENALIZED, BIASED };
+enum class StepForm { GREEDY = 0, SAMPLED, PENALIZED, BIASED, GRAMMAR };
 static inline StepForm step_form(bool all_greedy, bool any_penalized, bool any_biased) {
     return any_biased ? StepForm::BIASED : any_penalized ? StepForm::PENALIZED : all_greedy ? StepForm::GREEDY : StepForm::SAMPLED;
 }
-static inline bool form_has_presence(StepForm f) { return f == StepForm::PENALIZED || f == StepForm::BIASED; }
+static inline bool form_has_presence(StepForm f) { return f == StepForm::PENALIZED || f == StepForm::BIASED || f == StepForm::GRAMMAR; }
+static inline bool form_has_bias(StepForm f) { return f == StepForm::BIASED || f == StepForm::GRAMMAR; }
 
 // host check of rows[0, B) (mgea_decoder_generate_rows, mgea_op_sample_rows): MGEA_EINVAL naming the first bad row; n_steps < 0 skips the
 // budget check
@@ -278,6 +281,27 @@ struct ScoreArgs {
     float* logprob; float* choice; int out_stride;
     int32_t* err_flag;
 };
+// A token grammar (mgea_decoder_set_grammar): a finite automaton over token classes, one per engine, shared by the rows.
+//   class_of [V]                      the class of every id
+//   next     [n_state][n_class]       the state after an id of that class, -1 = the class is banned in the state
+//   allow    [n_state][words]         bit c & 31 of word c >> 5 of row s set iff next[s][c] >= 0 (launch_grammar_allow), words =
+//                                     grammar_words(n_class) <= MGEA_GRAMMAR_MAX_WORDS: what the sampler stages in LDS
+//   state_in / state_out [B]          the rows' states, -1 = the row has no grammar (the engine passes one array as both)
+//   done [B] or NULL                  the rows' finished flags: a finished row is neither masked nor moved
+//   err_flag or NULL                  bit 1 is set when the id a row takes is banned in its state (only a forced id can be); the state stays
+// The GRAMMAR sampler masks x[i] = -inf where the row's state bans class_of[i] -- after the penalty and the bias, before the EOS ban --
+// and its thread 0 stores next[state][class_of[id]] for the id the step commits.
+constexpr int MGEA_GRAMMAR_MAX_CLASSES = 4096, MGEA_GRAMMAR_MAX_STATES = 4096, MGEA_GRAMMAR_MAX_CELLS = 1 << 20;
+constexpr int MGEA_GRAMMAR_MAX_WORDS = MGEA_GRAMMAR_MAX_CLASSES / 32;
+__host__ __device__ static inline int grammar_words(int n_class) { return (n_class + 31) >> 5; }
+struct GrammarArgs {
+    const int32_t* class_of; const int32_t* next; const uint32_t* allow;
+    const int32_t* state_in; int32_t* state_out; const int32_t* done;
+    int32_t n_state, n_class, words;
+    int32_t* err_flag;
+};
+// allow[s][w] from next [n_state][n_class] (step_tail.hip)
+int launch_grammar_allow(const int32_t* next, int n_state, int n_class, uint32_t* allow, hipStream_t st);
 // The unfused path's second half: advance_kernel files the sampler's per-step values at the row's step (0 for a finished row).
 struct ScoreFile { const float* logprob_step; const float* choice_step; float* logprob_hist; float* choice_hist; int stride; };
 // One sampler launch over logits [B, V] (sampler.hip); every optional part is a named field, NULL = absent.
@@ -297,6 +321,8 @@ struct SampleCall {
     uint32_t* presence; const float* bias;
     // scored form (score.logprob != NULL): the raw and the choice log-probability of the id the row takes, and forced ids (ScoreArgs)
     ScoreArgs score;
+    // GRAMMAR form (grammar.class_of != NULL; needs records, presence and bias): the rows' automaton (GrammarArgs)
+    GrammarArgs grammar;
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
 // ---- the kernels that end a step, and the rows' records (step_tail.hip) ----

@@ -132,7 +132,15 @@ struct mgea_decoder {
     // on the unfused path.  Engine-owned, so the scored graphs hold stable pointers whatever the request forces.
     int32_t* forced = nullptr;
     float *lp_hist = nullptr, *ch_hist = nullptr, *lp_step = nullptr, *ch_step = nullptr;
-    int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped)
+    int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped; bit 1: a forced id was banned by the grammar)
+    // token grammar (mgea_decoder_set_grammar; GrammarArgs, common.h): one automaton per engine.  The tables live in buffers of their
+    // largest size, allocated at create behind the other sampler buffers, so the GRAMMAR graphs hold stable pointers whatever table is
+    // uploaded; the shape travels in the graphs' kernel arguments, so an upload of another shape drops those graphs.  gram_state
+    // [max_batch]: the rows' states, filled from the call's start states (through the pinned gram_stage) before the first step.
+    int32_t *gram_class = nullptr, *gram_next = nullptr, *gram_state = nullptr, *gram_stage = nullptr;
+    uint32_t* gram_allow = nullptr;
+    int gram_n_state = 0, gram_n_class = 0;
+    int64_t gram_uploads = 0, gram_steps = 0;
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     // The qkv0 table.  In MGEA_POS_REFERENCE mode every decode step adds pos_emb[0] (api_cache.py:99), so the input of layer 0's LN1 +
     // in-projection is tok_emb[id] + pos_emb[0]: its 3 C outputs q | k | v depend on the token id and the weights alone.  An f32 engine
@@ -508,7 +516,10 @@ int enqueue_tail(mgea_decoder* h, const Bufs& u, const StepCall& k, const float*
     sc.logits = lg; sc.B = B; sc.V = V;
     sc.params_dev = k.pd; sc.params = k.pv; sc.row_step_dev = u.row_step;
     sc.ids_out = u.sampled; sc.tail = k.primed ? &t : nullptr;
-    sc.presence = pres; sc.bias = k.form == StepForm::BIASED ? h->bias : nullptr;
+    sc.presence = pres; sc.bias = form_has_bias(k.form) ? h->bias : nullptr;
+    if (k.form == StepForm::GRAMMAR)
+        sc.grammar = GrammarArgs{h->gram_class, h->gram_next, h->gram_allow, h->gram_state, h->gram_state, u.done,
+                                 h->gram_n_state, h->gram_n_class, grammar_words(h->gram_n_class), h->err_flag};
     const int hs = h->ids_hist_stride;
     if (k.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
         sc.score = ScoreArgs{h->forced, hs, k.primed ? h->lp_hist : h->lp_step, k.primed ? h->ch_hist : h->ch_step, hs, h->err_flag};
@@ -631,7 +642,7 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
 
 // The captured decode step for (B, form, scored, steps): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond MAX_GRAPHS).
-constexpr size_t MAX_GRAPHS = 28;   // two per (batch, form, scored): the single step and the 8-step graph -- (4 forms + 3 scored) x 2 = 14 for one batch size, two batch sizes whole
+constexpr size_t MAX_GRAPHS = 36;   // two per (batch, form, scored): the single step and the 8-step graph -- (5 forms + 4 scored) x 2 = 18 for one batch size, two batch sizes whole
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
 int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps) {
@@ -1037,10 +1048,16 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         // (the logit bias came after the state buffers above, which keep the places they had before it existed: DESIGN.md §5)
         g.alloc(&h->bias, (size_t)cfg->max_batch * cfg->vocab * sizeof(float)) || g.alloc(&h->forced, nhist * sizeof(int32_t)) ||
         g.alloc(&h->lp_hist, nhist * sizeof(float)) || g.alloc(&h->ch_hist, nhist * sizeof(float)) ||
-        g.alloc(&h->lp_step, cfg->max_batch * sizeof(float)) || g.alloc(&h->ch_step, cfg->max_batch * sizeof(float)))
+        g.alloc(&h->lp_step, cfg->max_batch * sizeof(float)) || g.alloc(&h->ch_step, cfg->max_batch * sizeof(float)) ||
+        // (the grammar's buffers came after those, for the same reason)
+        g.alloc(&h->gram_state, nb) || g.alloc(&h->gram_class, (size_t)cfg->vocab * sizeof(int32_t)) ||
+        g.alloc(&h->gram_next, (size_t)MGEA_GRAMMAR_MAX_CELLS * sizeof(int32_t)) ||
+        g.alloc(&h->gram_allow, ((size_t)MGEA_GRAMMAR_MAX_CELLS / 32 + MGEA_GRAMMAR_MAX_STATES) * sizeof(uint32_t)) ||
+        hipHostMalloc((void**)&h->gram_stage, nb, 0) != hipSuccess)
         return fail(MGEA_ENOMEM, "state allocation failed");
     if (hipMemset(h->forced, 0xff, nhist * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->gram_state, 0xff, nb) != hipSuccess ||
         hipMemset(h->page_table, 0, nb * h->max_pages) != hipSuccess || hipMemset(h->ctx_len, 0, nb) != hipSuccess ||
         hipMemset(h->done, 0, nb) != hipSuccess || hipMemset(h->row_step, 0, nb) != hipSuccess ||
         hipMemset(h->cur_ids, 0, nb) != hipSuccess || hipMemset(h->n_done, 0, 16) != hipSuccess ||
@@ -1070,6 +1087,7 @@ int mgea_decoder_destroy(mgea_decoder* h) {
     (void)hipDeviceSynchronize();
     drop_graphs(h);
     if (h->samp_stage) (void)hipHostFree(h->samp_stage);
+    if (h->gram_stage) (void)hipHostFree(h->gram_stage);
     if (h->stage_free) (void)hipEventDestroy(h->stage_free);
     delete h;   // its DevGroups free the device buffers
     return MGEA_OK;
@@ -1114,21 +1132,33 @@ namespace {
 // mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
 // (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
 // are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  Which of the
-// four launch sequences the steps take: StepForm (common.h).
+// five launch sequences the steps take: StepForm (common.h).
 // score (with rows only) or NULL: the scored form -- forced ids in, log-probabilities out (mgea_decoder_generate_rows_scored).
+// start_states (with rows only; host [B]) or NULL: the rows' grammar start states, -1 = none; any >= 0 makes it the GRAMMAR form
+// (mgea_decoder_generate_rows_grammar), none leaves every launch as it is without the argument.
 struct ScoreIo { const int32_t* forced_dev; float* logprobs_out; float* choice_out; };
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
                 const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
-                int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr) {
+                int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr, const int32_t* start_states = nullptr) {
     const auto& c = h->cfg;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
     RowRecords rr;   // the step graphs' form; whether to poll for early stops (some row can finish before n_steps)
+    bool grammar = false;   // some row has a start state
     int reserve = Tp + n_steps;
     if (rows) {
         MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
         MGEA_TRY(check_row_samplers(rows, B, c.vocab, n_steps, "decoder_generate_rows"));
         if (lrows) MGEA_TRY(check_row_logits(lrows, B, n_steps, "decoder_generate_rows"));
+        for (int b = 0; start_states && b < B; ++b) {
+            const int32_t s0 = start_states[b];
+            if (s0 == -1) continue;
+            MGEA_REQUIRE(s0 >= 0, MGEA_EINVAL, "decoder_generate_rows_grammar: row %d: start state %d (-1 = none)", b, s0);
+            MGEA_REQUIRE(h->gram_n_state > 0, MGEA_EINVAL, "decoder_generate_rows_grammar: row %d has start state %d but no grammar is set", b, s0);
+            MGEA_REQUIRE(s0 < h->gram_n_state, MGEA_EINVAL, "decoder_generate_rows_grammar: row %d: start state %d outside [0, %d)", b, s0,
+                         h->gram_n_state);
+            grammar = true;
+        }
         // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
         MGEA_REQUIRE(Tp < c.max_ctx && n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp, n_steps,
                      c.max_ctx);
@@ -1144,9 +1174,10 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     }
     const bool scored = score != nullptr;
     // scoring needs the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to the lowest id)
-    const StepForm form = scored && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
-    const bool biased = form == StepForm::BIASED;
+    const bool biased = rr.form == StepForm::BIASED;
+    const StepForm form = grammar ? StepForm::GRAMMAR : scored && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
     h->last_penalized = false;
+    h->gram_steps = 0;
     h->counters[3] = 0;
     h->counters[6] = 0;
     h->counters[7] = 0;
@@ -1166,6 +1197,10 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
                 MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)b * c.vocab, lrows[b].bias_dev, (size_t)c.vocab * sizeof(float),
                                               hipMemcpyDeviceToDevice, st));
         MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
+        if (grammar) {   // the rows' states, through the pinned staging array (free under the same event as the records')
+            for (int b = 0; b < B; ++b) h->gram_stage[b] = start_states[b];
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        }
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free, st));
         if (reserve < Tp + n_steps) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
     } else {
@@ -1218,6 +1253,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->counters[6] = rr.any_penalty ? launched : 0;
     h->counters[7] = biased ? launched : 0;
     h->counters[3] = scored ? launched : 0;
+    h->gram_steps = grammar ? launched : 0;
     if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
         float* outs[2] = {score->logprobs_out, score->choice_out};
         const float* hist[2] = {h->lp_hist, h->ch_hist};
@@ -1291,6 +1327,95 @@ int mgea_decoder_generate_rows_scored(mgea_decoder* h, const int32_t* prompt_ids
     std::lock_guard<std::mutex> lk(h->mu);
     const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
     return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream, &io);
+}
+
+int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, const int32_t* next_host, int32_t n_state, int32_t n_class,
+                             void* stream) {
+    MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_set_grammar: NULL handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t st = (hipStream_t)stream;
+    auto drop_grammar_graphs = [&]() {   // their kernel arguments carry the table's shape
+        for (size_t i = h->graphs.size(); i-- > 0;)
+            if (h->graphs[i].form == StepForm::GRAMMAR) {
+                (void)hipGraphExecDestroy(h->graphs[i].exec);
+                (void)hipGraphDestroy(h->graphs[i].graph);
+                h->graphs.erase(h->graphs.begin() + (long)i);
+            }
+        h->counters[4] = (int64_t)h->graphs.size();
+    };
+    if (n_state == 0) {   // clear
+        MGEA_CHECK_HIP(hipStreamSynchronize(st));
+        drop_grammar_graphs();
+        h->gram_n_state = h->gram_n_class = 0;
+        return MGEA_OK;
+    }
+    const int V = h->cfg.vocab;
+    MGEA_REQUIRE(class_of_host && next_host, MGEA_EINVAL, "decoder_set_grammar: NULL table");
+    MGEA_REQUIRE(n_class >= 1 && n_class <= MGEA_GRAMMAR_MAX_CLASSES, MGEA_EINVAL, "decoder_set_grammar: n_class %d outside [1, %d]", n_class,
+                 MGEA_GRAMMAR_MAX_CLASSES);
+    MGEA_REQUIRE(n_state >= 1 && n_state <= MGEA_GRAMMAR_MAX_STATES, MGEA_EINVAL, "decoder_set_grammar: n_state %d outside [1, %d]", n_state,
+                 MGEA_GRAMMAR_MAX_STATES);
+    MGEA_REQUIRE((int64_t)n_state * n_class <= MGEA_GRAMMAR_MAX_CELLS, MGEA_EINVAL, "decoder_set_grammar: n_state %d x n_class %d exceeds %d cells",
+                 n_state, n_class, MGEA_GRAMMAR_MAX_CELLS);
+    std::vector<char> populated((size_t)n_class, 0);
+    for (int i = 0; i < V; ++i) {
+        MGEA_REQUIRE(class_of_host[i] >= 0 && class_of_host[i] < n_class, MGEA_EINVAL, "decoder_set_grammar: class_of[%d] = %d outside [0, %d)", i,
+                     class_of_host[i], n_class);
+        populated[(size_t)class_of_host[i]] = 1;
+    }
+    for (int s = 0; s < n_state; ++s) {
+        bool admits = false;
+        for (int c = 0; c < n_class; ++c) {
+            const int32_t v = next_host[(size_t)s * n_class + c];
+            MGEA_REQUIRE(v >= -1 && v < n_state, MGEA_EINVAL, "decoder_set_grammar: next[%d][%d] = %d outside [-1, %d)", s, c, v, n_state);
+            admits = admits || (v >= 0 && populated[(size_t)c]);
+        }
+        MGEA_REQUIRE(admits, MGEA_EINVAL, "decoder_set_grammar: state %d admits no class that has an id", s);
+    }
+    if (n_state != h->gram_n_state || n_class != h->gram_n_class) {
+        MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying
+        drop_grammar_graphs();
+    }
+    MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_class, class_of_host, (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_next, next_host, (size_t)n_state * n_class * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    MGEA_TRY(launch_grammar_allow(h->gram_next, n_state, n_class, h->gram_allow, st));
+    MGEA_CHECK_HIP(hipStreamSynchronize(st));   // the caller's tables are host memory of unknown lifetime
+    h->gram_n_state = n_state;
+    h->gram_n_class = n_class;
+    h->gram_uploads += 1;
+    return MGEA_OK;
+}
+
+int mgea_decoder_generate_rows_grammar(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                       const int32_t* start_states, const int32_t* forced_ids_dev, int32_t* ids_out_dev,
+                                       float* logprobs_out_dev, float* choice_logprobs_out_dev, void* stream) {
+    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows_grammar: NULL argument");
+    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
+                 "decoder_generate_rows_grammar: forced ids and choice log-probabilities need logprobs_out_dev");
+    if (logits_rows) {
+        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_grammar: empty batch");
+        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_grammar"));
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
+                       logprobs_out_dev ? &io : nullptr, start_states);
+}
+
+int mgea_decoder_grammar_states(mgea_decoder* h, int32_t* out_dev, void* stream) {
+    MGEA_REQUIRE(h && out_dev, MGEA_EINVAL, "decoder_grammar_states: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    MGEA_CHECK_HIP(hipMemcpyAsync(out_dev, h->gram_state, (size_t)(h->cur_batch > 0 ? h->cur_batch : 0) * sizeof(int32_t),
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MGEA_OK;
+}
+
+int mgea_decoder_grammar_info(mgea_decoder* h, int64_t* out) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_grammar_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->gram_n_state; out[1] = h->gram_n_class; out[2] = h->gram_uploads; out[3] = h->gram_steps;
+    return MGEA_OK;
 }
 
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream) {

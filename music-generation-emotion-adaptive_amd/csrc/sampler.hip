@@ -37,6 +37,7 @@
 // on: its key is the smallest a real entry can have, exp(-inf - max) is exactly 0, so it carries no mass, is never drawn, and may sit
 // among the top_k kept when fewer than top_k ids are admissible.  A row without a bias is not touched (no + 0).
 #include <cmath>
+#include <type_traits>
 
 #include "common.h"
 
@@ -303,11 +304,28 @@ __device__ __forceinline__ float* score_lds() {
     __shared__ float s[3];
     return s;
 }
-__device__ __forceinline__ ScoreArgs score_args() { return ScoreArgs{}; }
-__device__ __forceinline__ ScoreArgs score_args(const ScoreArgs& a) { return a; }
+// the argument of type T among a kernel's optional trailing arguments (ScoreArgs, GrammarArgs), T{} when it was not passed
+template <typename T>
+__device__ __forceinline__ T extra_arg() { return T{}; }
+template <typename T, typename A, typename... R>
+__device__ __forceinline__ T extra_arg(const A& a, const R&... r) {
+    if constexpr (std::is_same_v<T, A>) return a;
+    else return extra_arg<T>(r...);
+}
 
 __device__ __forceinline__ float funkey(uint32_t k) {   // inverse of fkey
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+// GRAMMAR: the row's bookkeeping thread moves the row's state behind the id `id` the step commits: two dependent scalar loads and one
+// plain store (one writer per row, read by the next step's kernel).  state < 0: the row has no grammar or was finished at step start,
+// nothing is touched.  A banned id (only a forced one can be) leaves the state and sets bit 1 of the error flags.
+__device__ __forceinline__ void grammar_advance_row(const GrammarArgs& gr, int b, int id, int state) {
+    if (threadIdx.x != 0 || state < 0) return;
+    const uint32_t c = (uint32_t)gr.class_of[id];
+    const int ns = c < (uint32_t)gr.n_class ? gr.next[(int64_t)state * gr.n_class + c] : -1;
+    if (ns >= 0) gr.state_out[b] = ns;
+    else if (gr.err_flag) atomicOr(gr.err_flag, 2);
 }
 
 // One SAMP_NT-thread workgroup per row; thread t owns the logits t, t + SAMP_NT, ... in registers (MAXE of them), so the row is
@@ -323,6 +341,14 @@ __device__ __forceinline__ float funkey(uint32_t k) {   // inverse of fkey
 //     bit 0 of the error flag).
 // With a fused tail both values are filed at the row's step in the histories, after the next step's embedding is on its way; a row that
 // was already finished files 0.  Without one they go to [B] vectors (advance_kernel files them).
+// GRAMMAR (the instantiations with a GrammarArgs argument, PENALTY and BIAS ones only; common.h): a row whose state s is >= 0 and which
+// is not finished loses every id whose class s bans, x[i] = -inf, after the bias and before the EOS ban; its thread 0 then stores the
+// state behind the id the step commits.
+//   * the state is one scalar load at kernel start; the classes of the thread's MAXE ids (class_of, shared by all rows, L2-resident)
+//     are requested in the same batch of loads as the logits and the bias -- no dependent round trip;
+//   * the state's row of the allow bitmask (<= 128 words) is staged in LDS next to the presence words, under the penalty's barrier;
+//     every thread folds its ids' verdicts into one 64-bit word (MAXE <= 64), which is all that stays live until the mask is applied.
+// A row with state -1 skips all of it (block-uniform) and computes what the BIAS form computes.
 template <int MAXE, bool PENALTY, bool BIAS, typename... Score>
 __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict__ logits, int V, SamplerParams pv,
                                                     const SamplerParams* __restrict__ pd,
@@ -332,9 +358,13 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
                                                     const float* __restrict__ bias, Score... score) {
     // the scored form is this kernel with one more argument, a ScoreArgs: with the empty pack the argument list, and with every scored
     // part under `if constexpr`, the code, are those of the kernel before there was a scored form
-    constexpr bool SCORED = sizeof...(Score) == 1;
-    static_assert(sizeof...(Score) <= 1, "at most one ScoreArgs");
-    [[maybe_unused]] const ScoreArgs sc = score_args(score...);
+    constexpr bool SCORED = (std::is_same_v<Score, ScoreArgs> || ...);
+    constexpr bool GRAMMAR = (std::is_same_v<Score, GrammarArgs> || ...);
+    static_assert(sizeof...(Score) == (SCORED ? 1 : 0) + (GRAMMAR ? 1 : 0), "at most one ScoreArgs, then at most one GrammarArgs");
+    static_assert(!GRAMMAR || (PENALTY && BIAS), "the GRAMMAR form is built on the BIASED one");
+    static_assert(MAXE <= 64, "the grammar's verdicts of a thread fit one 64-bit word");
+    [[maybe_unused]] const ScoreArgs sc = extra_arg<ScoreArgs>(score...);
+    [[maybe_unused]] const GrammarArgs gr = extra_arg<GrammarArgs>(score...);
     constexpr int NT = SAMP_NT, NW = SAMP_NW;
     static_assert(SAMP_KFAST == 64, "wave_publish_ge fills one slot per lane");
     __shared__ unsigned long long red64[2 * NW];
@@ -344,6 +374,11 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     __shared__ int s_tie[NW], s_fit[NW];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (pd) pv = pd[b];   // the row's device-resident scalars win over the by-value copy
+    [[maybe_unused]] int gstate = -1;   // GRAMMAR: the row's state, -1 = no grammar on this row (or the row is finished)
+    if constexpr (GRAMMAR) {
+        gstate = gr.state_in[b];
+        if (gstate >= gr.n_state || (gr.done && gr.done[b])) gstate = -1;
+    }
     const float temperature = pv.temperature, top_p = pv.top_p;
     const int top_k = pv.top_k;
     const uint64_t seed = ((uint64_t)pv.seed_hi << 32) | pv.seed_lo;
@@ -389,6 +424,22 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
             }
         }
     }
+    // GRAMMAR: so do the classes of the thread's ids; block-uniform
+    [[maybe_unused]] int gcls[GRAMMAR ? MAXE : 1];
+    [[maybe_unused]] unsigned long long gban = 0ull;   // bit j: the row's state bans logit tid + NT * j
+    [[maybe_unused]] uint32_t* s_gram = nullptr;
+    if constexpr (GRAMMAR) {
+        __shared__ uint32_t s_gram_words[MGEA_GRAMMAR_MAX_WORDS];
+        s_gram = s_gram_words;
+        if (gstate >= 0) {
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) {
+                const int i = tid + NT * j;
+                gcls[j] = i < V ? gr.class_of[i] : 0;
+            }
+            if (tid < gr.words) s_gram[tid] = gr.allow[(int64_t)gstate * gr.words + tid];   // words <= 128 < NT; read after the penalty's barrier
+        }
+    }
     if constexpr (SCORED) {
         // the raw row's maximum and log-sum-exp, while x still holds what the head wrote; kept in LDS for thread 0's use at the end
         __shared__ float s_rawm[NW], s_raws[NW];
@@ -418,6 +469,15 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         const int nw = presence_words(V);   // <= MAXE * NT / 32
         for (int w = tid; w < nw; w += NT) s_pres[w] = presence[(int64_t)b * nw + w];
         __syncthreads();
+        if constexpr (GRAMMAR) {
+            if (gstate >= 0) {
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) {
+                    const uint32_t c = (uint32_t)gcls[j] < (uint32_t)gr.n_class ? (uint32_t)gcls[j] : 0u;   // (set_grammar checked the table: never taken)
+                    gban |= (unsigned long long)(((s_gram[c >> 5] >> (c & 31)) & 1u) ^ 1u) << j;
+                }
+            }
+        }
         const float pen = pv.penalty;
 #pragma unroll
         for (int j = 0; j < MAXE; ++j) {
@@ -429,6 +489,13 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         if (biased) {
 #pragma unroll
             for (int j = 0; j < MAXE; ++j) x[j] += bz[j];
+        }
+        if constexpr (GRAMMAR) {
+            if (gstate >= 0) {
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j)
+                    if ((gban >> j) & 1ull) x[j] = -INFINITY;
+            }
         }
         // min_new: no EOS before the row has produced that many ids (its step index, the Philox counter's word 1)
         const int eos = pv.eos_id;
@@ -675,6 +742,7 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
             s_sc[2] = ev;
         }
         if (tid == 0) x_id = lg[tk];   // an L2 hit; in flight under the tail
+        if constexpr (GRAMMAR) grammar_advance_row(gr, b, tk, gstate);
         if (!fuse_tail) __syncthreads();   // (the fused tail has barriers of its own before thread 0 reads the mass)
         if (fuse_tail) advance_embed_row<PENALTY>(b, tk, tail, ids_out, st_step, st_fed, st_len, st_done, sh_tail, presence);
         else if (tid == 0) ids_out[b] = tk;
@@ -695,6 +763,7 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         }
         return;
     }
+    if constexpr (GRAMMAR) grammar_advance_row(gr, b, tok, gstate);
     if (fuse_tail) advance_embed_row<PENALTY>(b, tok, tail, ids_out, st_step, st_fed, st_len, st_done, sh_tail, presence);   // writes ids_out[b] too
     else if (tid == 0) ids_out[b] = tok;
 }
@@ -716,6 +785,25 @@ int launch_sample(const SampleCall& c, hipStream_t st) {
                                      : (narrow ? sample_kernel<36, false, true> : sample_kernel<56, false, true>))
                        : (c.presence ? (narrow ? sample_kernel<36, true, false> : sample_kernel<56, true, false>)
                                      : (narrow ? sample_kernel<36, false, false> : sample_kernel<56, false, false>));
+    if (c.grammar.class_of) {
+        const GrammarArgs& g = c.grammar;
+        MGEA_REQUIRE(c.bias && c.presence && c.params_dev, MGEA_EINVAL, "sampler: the grammar form needs records, presence bitmaps and the bias buffer");
+        MGEA_REQUIRE(g.next && g.allow && g.state_in && g.n_state > 0 && g.n_class > 0 && g.n_class <= MGEA_GRAMMAR_MAX_CLASSES &&
+                         g.words == grammar_words(g.n_class) && (!c.ids_out || g.state_out),
+                     MGEA_EINVAL, "sampler: bad grammar arguments");
+        MGEA_REQUIRE(c.score.logprob || !c.score.forced, MGEA_EINVAL, "sampler: forced ids need the scored form");
+        MGEA_REQUIRE(!c.score.logprob || c.ids_out, MGEA_EINVAL, "sampler: a scored launch draws ids");
+        auto gkern = narrow ? sample_kernel<36, true, true, GrammarArgs> : sample_kernel<56, true, true, GrammarArgs>;
+        auto gskern = narrow ? sample_kernel<36, true, true, ScoreArgs, GrammarArgs> : sample_kernel<56, true, true, ScoreArgs, GrammarArgs>;
+        if (c.score.logprob)
+            hipLaunchKernelGGL(gskern, dim3(c.B), dim3(SAMP_NT), 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host,
+                               c.ids_out, c.probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), c.presence, c.bias, c.score, g);
+        else
+            hipLaunchKernelGGL(gkern, dim3(c.B), dim3(SAMP_NT), 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host,
+                               c.ids_out, c.probs_out, t, tail ? 1 : 0, tune(TUNE_SAMPLER_WAVE_SELECT), c.presence, c.bias, g);
+        MGEA_CHECK_HIP(hipGetLastError());
+        return MGEA_OK;
+    }
     if (c.score.logprob) {
         MGEA_REQUIRE(c.ids_out, MGEA_EINVAL, "sampler: a scored launch draws ids");
         auto skern = c.bias ? (c.presence ? (narrow ? sample_kernel<36, true, true, ScoreArgs> : sample_kernel<56, true, true, ScoreArgs>)

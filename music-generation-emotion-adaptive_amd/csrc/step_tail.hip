@@ -1,5 +1,5 @@
 // The end of a decode step, after the LM head: the greedy argmax tails, the bookkeeping kernel behind an unfused sampler launch, the
-// presence bitmaps' seed, and the rows' sampler records (their host checks, the builder, the kernels that fill and clamp them).
+// presence bitmaps' seed, the grammar's allow bitmask, and the rows' sampler records (their host checks, the builder, the kernels that fill and clamp them).
 // The sampler itself is sampler.hip; end_row_step / advance_embed_row, which every tail shares, are in common.h.
 #include <cmath>
 
@@ -225,6 +225,29 @@ __global__ void unpark_rows_kernel(int32_t* __restrict__ done, int32_t* __restri
 
 int launch_unpark_rows(int32_t* done, int32_t* ctx_len, int B, hipStream_t st) {
     hipLaunchKernelGGL(unpark_rows_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, done, ctx_len, B);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
+// One thread per word of the allow bitmask: bit c & 31 of allow[s][c >> 5] = next[s][c] >= 0
+__global__ void grammar_allow_kernel(const int32_t* __restrict__ next, int n_state, int n_class, int words, uint32_t* __restrict__ allow) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_state * words) return;
+    const int s = i / words, w = i - s * words;
+    uint32_t bits = 0u;
+    for (int k = 0; k < 32; ++k) {
+        const int c = w * 32 + k;
+        if (c < n_class && next[(int64_t)s * n_class + c] >= 0) bits |= 1u << k;
+    }
+    allow[i] = bits;
+}
+
+int launch_grammar_allow(const int32_t* next, int n_state, int n_class, uint32_t* allow, hipStream_t st) {
+    MGEA_REQUIRE(n_state > 0 && n_state <= MGEA_GRAMMAR_MAX_STATES && n_class > 0 && n_class <= MGEA_GRAMMAR_MAX_CLASSES &&
+                     (int64_t)n_state * n_class <= MGEA_GRAMMAR_MAX_CELLS,
+                 MGEA_EINVAL, "grammar: %d states x %d classes exceed the caps", n_state, n_class);
+    const int words = grammar_words(n_class);
+    hipLaunchKernelGGL(grammar_allow_kernel, dim3(ceil_div(n_state * words, 256)), dim3(256), 0, st, next, n_state, n_class, words, allow);
     MGEA_CHECK_HIP(hipGetLastError());
     return MGEA_OK;
 }

@@ -29,7 +29,7 @@ from mgea.decoder import DecoderEngine, RowSampling, geometry_from_state_dict, r
 __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab", "encode", "decode",
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
            "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
-           "generate_batch_biased", "generate_sequence_biased", "score_sequence", "generate_best_of", "pick_best",
+           "generate_batch_biased", "generate_sequence_biased", "sample_kvcache_grammar", "generate_batch_grammar", "score_sequence", "generate_best_of", "pick_best",
            "mean_logprobs"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
@@ -193,8 +193,30 @@ def _as_model(model_or_weights, n_head=8, device=_DEFAULT_DEVICE) -> GPTWithKV:
     raise TypeError("expected a GPTWithKV or a state dict / checkpoint dict")
 
 
-def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, **kw):
-    """eng.generate(), or eng.generate_biased() when a bias or a minimum length is set (capped at the steps there are)"""
+def _use_grammar(eng, grammar) -> None:
+    """Make `grammar` (a TokenGrammar, or None = nothing to do) the engine's: uploaded when it is not the object set there now."""
+    if grammar is not None and eng.grammar is not grammar:
+        eng.set_grammar(grammar)
+
+
+def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, grammar=None, **kw):
+    """eng.generate(), or eng.generate_biased() when a bias or a minimum length is set (capped at the steps there are); with a
+    grammar, generate_rows() with the same record on every row (stream = the row's index: the draws of generate()) and each row's
+    start state walked from its prompt"""
+    if grammar is not None:
+        from .grammar import start_state
+        _use_grammar(eng, grammar)
+        B = len(ids)
+        per_row = [logit_bias] * B
+        if logit_bias is not None and not isinstance(logit_bias, dict) and getattr(logit_bias, "ndim", 1) == 2:
+            if logit_bias.shape[0] != B:
+                raise ValueError(f"logit_bias must be [{eng.vocab}] or [{B}, {eng.vocab}], got {list(logit_bias.shape)}")
+            per_row = [logit_bias[b] for b in range(B)]
+        rows = [RowSampling(temperature=kw.get("temperature", 1.0), top_k=kw.get("top_k", 50), top_p=kw.get("top_p"),
+                            repetition_penalty=kw.get("repetition_penalty"), eos_id=kw.get("eos_id", -1), seed=kw.get("seed", 0),
+                            logit_bias=per_row[b], min_new_tokens=min(int(min_new_tokens), n_steps),
+                            grammar_state=start_state(grammar, ids[b])) for b in range(B)]
+        return eng.generate_rows(ids, rows, n_steps)
     if logit_bias is None and not min_new_tokens:
         return eng.generate(ids, n_steps, **kw)
     return eng.generate_biased(ids, n_steps, logit_bias=logit_bias, min_new_tokens=min(int(min_new_tokens), n_steps), **kw)
@@ -226,7 +248,19 @@ def sample_kvcache_biased(model, prompt: Sequence[str], max_len=512, temperature
     logit_bias (None, a dict id -> bias, a host array or a device tensor [vocab]; -inf bans an id -- generate_music.constraints
     builds the note / scale ones) is added to the penalized logits at every step; min_new_tokens > 0 keeps [END_SEQUENCE] from
     being drawn before that many new tokens (capped at the steps there are).  Both are build-defined (include/mgea.h); with
-    neither this is sample_kvcache, the same engine call."""
+    neither this is sample_kvcache, the same engine call.  (sample_kvcache_grammar: the same with a token grammar.)"""
+    return sample_kvcache_grammar(model, prompt, max_len, temperature, top_k, device, top_p, seed, repetition_penalty, logit_bias,
+                                  min_new_tokens)
+
+
+def sample_kvcache_grammar(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
+                           top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                           logit_bias=None, min_new_tokens: int = 0, grammar=None) -> List[str]:
+    """sample_kvcache_biased under a token grammar (sample_kvcache_biased keeps its parameter list).  grammar (a
+    mgea.decoder.TokenGrammar, e.g. generate_music.grammar.track_grammar; None = none: then this IS sample_kvcache_biased)
+    constrains what may FOLLOW what: the row starts in the state its prompt leads to (generate_music.grammar.start_state), every
+    step is masked by the row's current state, and the state moves on the device.  It composes with logit_bias: the bias bans ids,
+    the grammar orders the rest."""
     m = _as_model(model)
     eng = m._need()
     ids = [tok2id[t] for t in prompt]          # KeyError for an unknown token, like api_cache.py:162
@@ -236,8 +270,9 @@ def sample_kvcache_biased(model, prompt: Sequence[str], max_len=512, temperature
     if len(ids) + n_steps > eng.max_ctx:
         raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
-    out = _engine_generate(eng, [ids], n_steps, logit_bias, min_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
-                           eos_id=eos, seed=_draw_seed() if seed is None else seed, repetition_penalty=repetition_penalty)
+    out = _engine_generate(eng, [ids], n_steps, logit_bias, min_new_tokens, grammar, temperature=temperature, top_k=top_k,
+                           top_p=top_p, eos_id=eos, seed=_draw_seed() if seed is None else seed,
+                           repetition_penalty=repetition_penalty)
     gen = [int(i) for i in out[0].cpu().tolist() if i >= 0]
     return [id2tok[i] for i in ids + gen]
 
@@ -270,13 +305,22 @@ def generate_batch_biased(model, prompts: Sequence[Sequence[str]], max_len=512, 
                           top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
                           logit_bias=None, min_new_tokens: int = 0) -> List[List[str]]:
     """generate_batch with a logit bias (one vector for every row, or [B, vocab]) and min_new_tokens, as in sample_kvcache_biased."""
+    return generate_batch_grammar(model, prompts, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias,
+                                  min_new_tokens)
+
+
+def generate_batch_grammar(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
+                           top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                           logit_bias=None, min_new_tokens: int = 0, grammar=None) -> List[List[str]]:
+    """generate_batch_biased under a token grammar (None = none), as in sample_kvcache_grammar: every row starts in the state of its
+    own prompt."""
     m = _as_model(model)
     eng = m._need()
     ids = [[tok2id[t] for t in p] for p in prompts]
     n_steps = int(max_len) - max(len(p) for p in ids)
     eos = tok2id.get("[END_SEQUENCE]", -1)
-    out = _engine_generate(eng, ids, max(n_steps, 0), logit_bias, min_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
-                           eos_id=eos, seed=_draw_seed() if seed is None else seed,
+    out = _engine_generate(eng, ids, max(n_steps, 0), logit_bias, min_new_tokens, grammar, temperature=temperature, top_k=top_k,
+                           top_p=top_p, eos_id=eos, seed=_draw_seed() if seed is None else seed,
                            repetition_penalty=repetition_penalty).cpu().tolist()
     return [[id2tok[i] for i in p + [g for g in row if g >= 0]] for p, row in zip(ids, out)]
 
@@ -319,12 +363,13 @@ def pick_best(ids, logprobs) -> int:
 
 def generate_best_of(model, prompt: Sequence[str], n: int, max_len=512, temperature=1.0, top_k=50, top_p: Optional[float] = None,
                      seed: Optional[int] = None, repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0,
-                     return_all: bool = False):
+                     return_all: bool = False, grammar=None):
     """sample_kvcache_biased n times in ONE batch, keeping the most likely candidate: the n rows share the prompt, the settings and
     the seed and draw from Philox streams 0 .. n - 1 (row 0 is the sample_kvcache run of that seed); the one with the highest mean
     raw log-probability per generated token (pick_best) is returned as prompt + generated tokens.  n is capped by the model's
     max_batch (ValueError beyond it).  return_all=True returns (tokens, candidates, means, best): every candidate's tokens, their
-    mean log-probabilities and the index kept.  Build-defined: the reference draws one sequence and returns no scores."""
+    mean log-probabilities and the index kept.  grammar (a TokenGrammar or None): every candidate starts in the state of the prompt.
+    Build-defined: the reference draws one sequence and returns no scores."""
     m = _as_model(model)
     n = int(n)
     if n < 1 or n > m.max_batch:
@@ -339,8 +384,14 @@ def generate_best_of(model, prompt: Sequence[str], n: int, max_len=512, temperat
         raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
     seed = _draw_seed() if seed is None else int(seed)
+    gstate = None
+    if grammar is not None:
+        from .grammar import start_state
+        _use_grammar(eng, grammar)
+        gstate = start_state(grammar, ids)
     rows = [RowSampling(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, eos_id=eos,
-                        seed=seed, stream=b, logit_bias=logit_bias, min_new_tokens=min(int(min_new_tokens), n_steps))
+                        seed=seed, stream=b, logit_bias=logit_bias, min_new_tokens=min(int(min_new_tokens), n_steps),
+                        grammar_state=gstate)
             for b in range(n)]
     res = eng.generate_scored([ids] * n, rows, n_steps)
     out, lps = res.ids.cpu().tolist(), res.logprobs.cpu().tolist()
@@ -360,7 +411,7 @@ def _per_prompt(value, n: int, name: str) -> list:
 
 def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
                       top_p: Optional[float] = None, seed=None, repetition_penalty=None, logit_bias=None,
-                      min_new_tokens=0) -> List[List[str]]:
+                      min_new_tokens=0, grammar=None) -> List[List[str]]:
     """Independent sample_kvcache requests served by one batched generation (up to the engine's max_batch rows per
     generation; more prompts take several).  Every argument may be a scalar or a list with one value per prompt.  Prompt i
     gets max_len_i - len(prompt_i) new tokens and stops after [END_SEQUENCE], like sample_kvcache; a seed of None is drawn
@@ -369,7 +420,8 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     Greedy rows (top_k=1) equal the reference run of their prompt alone; sampled rows depend on their own settings and on
     the batch size (kernel choice), not on the other requests.  logit_bias (one vector -- a dict, a host array or a device
     tensor [vocab] -- for every prompt, or a list with one per prompt, None = none) and min_new_tokens (capped at the prompt's
-    budget) travel in the rows' records."""
+    budget) travel in the rows' records.  grammar (ONE TokenGrammar for all the prompts, or None) makes every row start in the state
+    of its own prompt."""
     m = _as_model(model)
     eng = m._need()
     n = len(prompts)
@@ -391,9 +443,14 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     for i in range(n):
         if mins[i] < 0:
             raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
+    gstates = [None] * n
+    if grammar is not None:
+        from .grammar import start_state
+        _use_grammar(eng, grammar)
+        gstates = [start_state(grammar, p) for p in ids]
     rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
                            max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]))
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i])
             for i in live}
     gen: Dict[int, List[int]] = {}
     for c0 in range(0, len(live), eng.max_batch):

@@ -124,6 +124,89 @@ def check_logit_bias(vec, row: int, eos_id: int = -1, min_new_tokens: int = 0, c
         raise ValueError(f"row {row}: logit_bias admits only eos_id {eos_id}, which min_new_tokens {min_new_tokens} bans")
 
 
+GRAMMAR_MAX_CLASSES, GRAMMAR_MAX_STATES, GRAMMAR_MAX_CELLS = 4096, 4096, 1 << 20
+ERR_ID_CLAMPED, ERR_GRAMMAR_BANNED = 1, 2   # bits of the engine's sticky error flags (include/mgea.h, mgea_decoder_error_flags)
+
+
+@dataclasses.dataclass(eq=False)
+class TokenGrammar:
+    """A token grammar (include/mgea.h, mgea_decoder_set_grammar): a finite automaton over token classes.  class_of int32 [vocab] is
+    the class of every id, next int32 [n_state, n_class] the state after an id of class c in state s, -1 = the class is banned in s.
+    The engine masks a row's logits with allowed(state) at every step and moves the state with step(); the methods here are the
+    host model of exactly that."""
+    class_of: np.ndarray
+    next: np.ndarray
+
+    def __post_init__(self):
+        self.class_of = np.ascontiguousarray(np.asarray(self.class_of), dtype=np.int32).reshape(-1)
+        nx = np.asarray(self.next)
+        if nx.ndim != 2:
+            raise ValueError(f"TokenGrammar.next must be [n_state, n_class], got {list(nx.shape)}")
+        self.next = np.ascontiguousarray(nx, dtype=np.int32)
+
+    @property
+    def n_state(self) -> int:
+        return int(self.next.shape[0])
+
+    @property
+    def n_class(self) -> int:
+        return int(self.next.shape[1])
+
+    def check(self, vocab: int) -> None:
+        """The rules of mgea_decoder_set_grammar as ValueErrors naming the offender."""
+        S, K = self.n_state, self.n_class
+        if not 1 <= K <= GRAMMAR_MAX_CLASSES:
+            raise ValueError(f"grammar: n_class {K} outside [1, {GRAMMAR_MAX_CLASSES}]")
+        if not 1 <= S <= GRAMMAR_MAX_STATES:
+            raise ValueError(f"grammar: n_state {S} outside [1, {GRAMMAR_MAX_STATES}]")
+        if S * K > GRAMMAR_MAX_CELLS:
+            raise ValueError(f"grammar: n_state {S} x n_class {K} exceeds {GRAMMAR_MAX_CELLS} cells")
+        if self.class_of.shape != (vocab,):
+            raise ValueError(f"grammar: class_of must be [{vocab}], got {list(self.class_of.shape)}")
+        bad = np.flatnonzero((self.class_of < 0) | (self.class_of >= K))
+        if bad.size:
+            raise ValueError(f"grammar: class_of[{int(bad[0])}] = {int(self.class_of[bad[0]])} outside [0, {K})")
+        bad = np.argwhere((self.next < -1) | (self.next >= S))
+        if bad.size:
+            s, c = (int(v) for v in bad[0])
+            raise ValueError(f"grammar: next[{s}][{c}] = {int(self.next[s, c])} outside [-1, {S})")
+        populated = np.zeros(K, bool)
+        populated[self.class_of] = True
+        dead = np.flatnonzero(~((self.next >= 0) & populated[None, :]).any(axis=1))
+        if dead.size:
+            raise ValueError(f"grammar: state {int(dead[0])} admits no class that has an id")
+
+    def allowed(self, state: int) -> np.ndarray:
+        """bool [vocab]: the ids the state admits."""
+        return self.next[int(state)][self.class_of] >= 0
+
+    def step(self, state: int, id: int) -> int:
+        """The state after `id` in `state`; -1 if the state bans it."""
+        return int(self.next[int(state), self.class_of[int(id)]])
+
+    def run(self, ids, state: int = 0, strict: bool = True) -> int:
+        """The state after the ids.  strict: a banned id raises a ValueError; otherwise it leaves the state alone (what walking a
+        prompt needs: its control tokens are not part of the generated language)."""
+        state = int(state)
+        for t, i in enumerate(ids):
+            n = self.step(state, i)
+            if n < 0:
+                if strict:
+                    raise ValueError(f"grammar: id {int(i)} at position {t} is banned in state {state}")
+                continue
+            state = n
+        return state
+
+    def accepts(self, ids, state: int = 0) -> bool:
+        """True iff the grammar admits every id in turn, starting from `state`."""
+        state = int(state)
+        for i in ids:
+            state = self.step(state, i)
+            if state < 0:
+                return False
+        return True
+
+
 @dataclasses.dataclass
 class RowSampling:
     """One batch row's sampler settings (mgea_row_sampler, include/mgea.h) for DecoderEngine.generate_rows / ops.sample_rows.
@@ -131,7 +214,8 @@ class RowSampling:
     repetition_penalty None = 1 = none; max_new_tokens 0 = the call's n_steps; stream None = the row's index in the batch (what
     generate() uses).  The row draws its step-t number from Philox counter (stream, t) under key seed.
     logit_bias (None, a dict id -> bias, a host array or a device tensor [vocab]; -inf bans an id) is added to the row's penalized
-    logits at every step; min_new_tokens > 0 bans eos_id until the row has produced that many ids (mgea_row_logits)."""
+    logits at every step; min_new_tokens > 0 bans eos_id until the row has produced that many ids (mgea_row_logits).
+    grammar_state (None = the row is not constrained): the row's start state in the engine's TokenGrammar (DecoderEngine.set_grammar)."""
     temperature: float = 1.0
     top_k: Optional[int] = 50
     top_p: Optional[float] = None
@@ -142,6 +226,12 @@ class RowSampling:
     stream: Optional[int] = None
     logit_bias: object = None
     min_new_tokens: int = 0
+    # the eleventh constructor argument, after min_new_tokens, and an ordinary attribute afterwards (dataclasses.replace keeps it).  An
+    # InitVar rather than a field: dataclasses.fields() stays the ten sampler and logits settings the native records are packed from
+    grammar_state: dataclasses.InitVar[Optional[int]] = None
+
+    def __post_init__(self, grammar_state):
+        self.grammar_state = grammar_state
 
     def check(self, row: int, vocab: int, n_steps: Optional[int] = None) -> None:
         """ValueError naming the row for what the native call would refuse (MGEA_EINVAL)."""
@@ -319,6 +409,7 @@ class DecoderEngine:
         h = C.c_void_p(0)
         check(self.lib.mgea_decoder_create(C.byref(self.cfg), ptr(self.arena), C.byref(h)))
         self.h = h
+        self.grammar: Optional[TokenGrammar] = None
         self._cur_batch = 0
         self._epoch = 0  # bumps whenever the native cache is reset (guards stale `presents`)
         self._len = 0
@@ -390,8 +481,9 @@ class DecoderEngine:
         return True
 
     def id_errors(self, raise_error: bool = True) -> int:
-        """Read and clear the engine's sticky device flags (ONE stream sync): bit 0 = some token id handed over as a
-        device tensor since the last call was outside the vocabulary (and was clamped)."""
+        """Read and clear the engine's sticky device flags (ONE stream sync): bit 0 (ERR_ID_CLAMPED) = some token id handed over as a
+        device tensor since the last call was outside the vocabulary (and was clamped) -- the IndexError; bit 1 (ERR_GRAMMAR_BANNED) =
+        a forced id was banned by its row's grammar state (the state stayed where it was) -- reported in the return value only."""
         flags = C.c_int32(0)
         with self._on_stream():
             check(self.lib.mgea_decoder_error_flags(self.h, C.byref(flags), self._sp()))
@@ -404,6 +496,49 @@ class DecoderEngine:
                 seed: int = 0) -> SamplerConfig:
         return SamplerConfig(temperature=float(temperature), top_k=int(top_k) if top_k else 0,
                              top_p=float(top_p) if top_p else 0.0, eos_id=int(eos_id), seed=int(seed) & (2 ** 64 - 1))
+
+    # ------------------------------------------------------------------ token grammar
+    def set_grammar(self, grammar: Optional[TokenGrammar]) -> None:
+        """Upload a TokenGrammar (checked here: ValueError naming the offender), or None to clear it.  One grammar per engine, shared
+        by the rows; a row takes part through RowSampling.grammar_state.  An upload of the same shape keeps the captured graphs."""
+        if grammar is None:
+            with self._on_stream():
+                check(self.lib.mgea_decoder_set_grammar(self.h, None, None, 0, 0, self._sp()))
+            self.grammar = None
+            return
+        grammar.check(self.vocab)
+        with self._on_stream():
+            check(self.lib.mgea_decoder_set_grammar(self.h, grammar.class_of.ctypes.data_as(C.c_void_p), grammar.next.ctypes.data_as(C.c_void_p),
+                                                    grammar.n_state, grammar.n_class, self._sp()))
+        self.grammar = grammar
+
+    def grammar_states(self) -> torch.Tensor:
+        """int32 [B] on the device: every row's state after the last grammar generation (-1: the row had none)."""
+        with self._on_stream():
+            out = torch.empty(self._cur_batch, dtype=torch.int32, device=self.device)
+            check(self.lib.mgea_decoder_grammar_states(self.h, ptr(out), self._sp()))
+        return out
+
+    def grammar_info(self):
+        out = (C.c_int64 * 4)()
+        check(self.lib.mgea_decoder_grammar_info(self.h, out))
+        return dict(n_state=out[0], n_class=out[1], uploads=out[2], grammar_steps=out[3])
+
+    def _start_states(self, rows):
+        """The rows' grammar start states as a C int32 [B] array, or None when no row has one (the caller then makes the call it
+        always made).  ValueError naming the row for what mgea_decoder_generate_rows_grammar would refuse."""
+        if all(r.grammar_state is None for r in rows):
+            return None
+        g = getattr(self, "grammar", None)
+        out = (C.c_int32 * len(rows))()
+        for b, r in enumerate(rows):
+            st = -1 if r.grammar_state is None else int(r.grammar_state)
+            if st != -1 and g is None:
+                raise ValueError(f"row {b}: grammar_state {st} but no grammar is set (DecoderEngine.set_grammar)")
+            if st != -1 and not 0 <= st < g.n_state:
+                raise ValueError(f"row {b}: grammar_state {st} outside [0, {g.n_state})")
+            out[b] = st
+        return out
 
     # ------------------------------------------------------------------ model(idx, past) surface
     def reset(self, batch: int, max_len: Optional[int] = None):
@@ -527,12 +662,18 @@ class DecoderEngine:
         n_steps = int(n_steps)
         recs = pack_rows(rows, self.vocab, n_steps)
         lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
+        starts = self._start_states(rows)
         checked = self._check_ids(ids)
         with self._on_stream():
             ids = ids.to(self.device).contiguous()
             lens = None if lens is None else lens.to(self.device).contiguous()
             out = torch.empty(B, max(n_steps, 1), dtype=torch.int32, device=self.device)
-            if lrecs is None:
+            if starts is not None:
+                for t in keep:
+                    t.record_stream(self.stream)
+                check(self.lib.mgea_decoder_generate_rows_grammar(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, None,
+                                                                  ptr(out), None, None, self._sp()))
+            elif lrecs is None:
                 check(self.lib.mgea_decoder_generate_rows(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, ptr(out), self._sp()))
             else:
                 for t in keep:   # uploaded on the caller's stream, read by the engine's
@@ -567,6 +708,7 @@ class DecoderEngine:
         recs = pack_rows(rows, self.vocab, n_steps)
         forced = pack_force_ids(force_ids, B, n_steps, self.vocab)
         lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
+        starts = self._start_states(rows)
         checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
         with self._on_stream():
             ids = ids.to(self.device).contiguous()
@@ -580,8 +722,12 @@ class DecoderEngine:
             ch = torch.zeros(B, n, dtype=torch.float32, device=self.device)
             for t in keep:   # uploaded on the caller's stream, read by the engine's
                 t.record_stream(self.stream)
-            check(self.lib.mgea_decoder_generate_rows_scored(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, ptr(forced),
-                                                             ptr(out), ptr(lp), ptr(ch), self._sp()))
+            if starts is not None:
+                check(self.lib.mgea_decoder_generate_rows_grammar(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts,
+                                                                  ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
+            else:
+                check(self.lib.mgea_decoder_generate_rows_scored(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, ptr(forced),
+                                                                 ptr(out), ptr(lp), ptr(ch), self._sp()))
         self._cur_batch = B
         self._epoch += 1
         if check_ids and not checked:

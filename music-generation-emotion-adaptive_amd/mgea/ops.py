@@ -507,6 +507,39 @@ def _sample_rows(logits: torch.Tensor, rows, step, want_probs, presence, logit_b
     return (ids, probs) if want_probs else ids
 
 
+def sample_rows_grammar(logits: torch.Tensor, rows, grammar, states, step=0, want_probs=False, presence=None):
+    """sample_rows() under a mgea.decoder.TokenGrammar (mgea_op_sample_rows_grammar): row b in state states[b] (-1 = no grammar on
+    the row) loses every id its state bans -- after its penalty and bias, before the EOS ban -- and moves to
+    grammar.step(states[b], id).  The rows' own logit_bias / min_new_tokens apply.  Returns (ids, states_out[, probs])."""
+    from .decoder import pack_row_logits, pack_rows
+    rows = list(rows)
+    lib = _lib.load()
+    logits = _dev(logits.float())
+    B, V = logits.shape
+    grammar.check(V)
+    recs = pack_rows(rows, V)
+    if len(recs) != B:
+        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
+    st = np.asarray(list(states), dtype=np.int64).reshape(-1)
+    if st.shape != (B,) or st.min() < -1 or st.max() >= grammar.n_state:
+        raise ValueError(f"states must be {B} values in [-1, {grammar.n_state})")
+    bits = None
+    if presence is not None or any(r.repetition_penalty != 1.0 for r in recs):
+        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
+        bits = torch.from_numpy(words.view(np.int32)).to(logits.device)
+    lrecs, keep = pack_row_logits(rows, V, logits.device)
+    dev = logits.device
+    cls = torch.from_numpy(grammar.class_of).to(dev)
+    nxt = torch.from_numpy(grammar.next).to(dev)
+    s_in = torch.from_numpy(st.astype(np.int32)).to(dev)
+    s_out = torch.empty(B, dtype=torch.int32, device=dev)
+    ids = torch.empty(B, dtype=torch.int32, device=dev)
+    probs = torch.empty(B, V, dtype=torch.float32, device=dev) if want_probs else None
+    check(lib.mgea_op_sample_rows_grammar(ptr(logits), B, V, recs, ptr(bits), lrecs, ptr(cls), ptr(nxt), grammar.n_state, grammar.n_class,
+                                          ptr(s_in), int(step), ptr(ids), ptr(probs), ptr(s_out), stream_ptr()))
+    return (ids, s_out, probs) if want_probs else (ids, s_out)
+
+
 def tile_weights(w: torch.Tensor) -> torch.Tensor:
     """W [N,K] row-major -> the fragment-ordered layout the skinny GEMM reads (rows padded to 32)."""
     lib = _lib.load()

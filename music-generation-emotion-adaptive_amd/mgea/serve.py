@@ -14,10 +14,10 @@ from typing import List, Optional, Sequence
 
 
 class _Request:
-    __slots__ = ("tokens", "kwargs", "future")
+    __slots__ = ("tokens", "kwargs", "future", "grammar")
 
-    def __init__(self, tokens, kwargs, future):
-        self.tokens, self.kwargs, self.future = tokens, kwargs, future
+    def __init__(self, tokens, kwargs, future, grammar=None):
+        self.tokens, self.kwargs, self.future, self.grammar = tokens, kwargs, future, grammar
 
 
 class RequestBatcher:
@@ -46,11 +46,14 @@ class RequestBatcher:
                 self._thread.start()
 
     def submit(self, prompt_tokens: Sequence[str], max_len=512, temperature=1.0, top_k=50, top_p=None,
-               repetition_penalty=None, seed: Optional[int] = None, logit_bias=None, min_new_tokens: int = 0) -> "Future[List[str]]":
+               repetition_penalty=None, seed: Optional[int] = None, logit_bias=None, min_new_tokens: int = 0,
+               grammar=None) -> "Future[List[str]]":
         """Queue one sample_kvcache request; the future's result is its prompt + generated tokens.  Unknown tokens raise KeyError
         and a bad repetition penalty, logit_bias (a dict id -> bias, a host array or a device tensor [vocab]; a host one is checked
         in full, a device one for its shape) or min_new_tokens ValueError here, in the caller's thread.  A seed of None is drawn here too, so
-        torch.manual_seed in the caller makes it reproducible whatever the batch it lands in."""
+        torch.manual_seed in the caller makes it reproducible whatever the batch it lands in.  grammar (a mgea.decoder.TokenGrammar or
+        None, checked here): the engine holds one grammar at a time, so a batch serves requests that share the grammar object (or have
+        none); a request with another one goes into the next batch."""
         import generate_music.generate as gen
         from .ops import check_repetition_penalty
         tokens = list(prompt_tokens)
@@ -65,6 +68,8 @@ class RequestBatcher:
             eos = gen.tok2id.get("[END_SEQUENCE]", -1)
             logit_bias = dense_logit_bias(logit_bias, self.model._need().vocab)   # packed once, here, at the engine's vocabulary
             check_logit_bias(logit_bias, 0, eos, int(min_new_tokens), check=False)
+        if grammar is not None:
+            grammar.check(self.model._need().vocab)
         kwargs = dict(max_len=int(max_len), temperature=temperature, top_k=top_k, top_p=top_p,
                       repetition_penalty=repetition_penalty, seed=gen._draw_seed() if seed is None else int(seed),
                       logit_bias=logit_bias, min_new_tokens=int(min_new_tokens))
@@ -72,7 +77,7 @@ class RequestBatcher:
         with self._cv:
             if self._closed:
                 raise RuntimeError("RequestBatcher is closed")
-            self._queue.append(_Request(tokens, kwargs, fut))
+            self._queue.append(_Request(tokens, kwargs, fut, grammar))
             self._cv.notify()
         return fut
 
@@ -105,7 +110,9 @@ class RequestBatcher:
                     self._cv.wait()
                 if not self._queue:
                     return
-                batch = [self._queue.popleft() for _ in range(min(len(self._queue), self.max_batch))]
+                batch = [self._queue.popleft()]   # up to max_batch requests from the front, as long as they share the grammar object
+                while self._queue and len(batch) < self.max_batch and self._queue[0].grammar is batch[0].grammar:
+                    batch.append(self._queue.popleft())
             self._run(batch)
 
     def _run(self, batch: List[_Request]) -> None:
@@ -115,7 +122,7 @@ class RequestBatcher:
             return
         kw = {k: [r.kwargs[k] for r in batch] for k in batch[0].kwargs}
         try:
-            outs = gen.generate_requests(self.model, [r.tokens for r in batch], **kw)
+            outs = gen.generate_requests(self.model, [r.tokens for r in batch], grammar=batch[0].grammar, **kw)
         except BaseException as e:   # this batch's requests fail; the worker serves the next one
             with self._cv:
                 self._rows.append(len(batch))
