@@ -503,6 +503,66 @@ int mgea_op_skinny(int32_t epi, const float* a_dev, const float* w_dev, const fl
  * csrc/head_gemm.hip, P = the CU count -- and on the generic skinny kernel otherwise; switch head_balanced.)  epi = 3 takes no
  * ln_c1_dev. */
 int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K);
+/* TEST ONLY: any plan of the decode-step GEMMs (csrc/common.h plan_decode_gemm) on caller buffers, one launch per call, so that the
+ * tests can hold each kernel family, instantiation and epilogue against exact references.  The call fills the launcher's argument
+ * block from *args, plans, launches exactly that plan and synchronises `stream` before it returns; a shape or combination the plan
+ * refuses is MGEA_EINVAL and nothing is launched.  No pointer is range-checked: the caller sizes every buffer as documented here.
+ *   family    rowmajor = 1: w_dev is the ROW-MAJOR [N, K] fp32 matrix for the dot-product kernel (csrc/gemv_small.hip: M <= 2,
+ *             K % 256 == 0), LayerNorm applied directly from ln_g_dev / ln_b_dev [K] (both or neither; K <= 1024);
+ *             rowmajor = 0: w_dev is the tiled copy (mgea_op_tile_weights / mgea_op_fold_ln), LayerNorm folded: ln_c1_dev [N] and
+ *             bias_dev = c2, stats_in_dev [M][n_part][2] partial (mean, M2) over part_cnt columns each;
+ *   weights   w_f16 = 1 (rowmajor = 0 only): w_dev holds mgea_op_tile_weights_f16's fp16 fragments; with a LayerNorm ln_g_dev [K]
+ *             comes next to ln_c1_dev / bias_dev = mgea_op_ln_vectors' c1 / c2 (gamma is applied to the activations);
+ *   a_dev     k-tiled activations (mgea_op_tile_rows), whole 64-row groups;
+ *   epi       0 QKV:    out_dev [M, N] row-major = q | k | v, N = 3 * n_head * head_dim; K | V of row m = b * T + t (t < lens[b], or
+ *                       every t if lens_dev == NULL) are appended at position ctx_len_dev[b] + t of layer `layer` of the page image
+ *                       pages_dev: (layer + 1) layers of n_pages pages in the layout above (page_dtype MGEA_DTYPE_F32 / _F16);
+ *                       positions in logical pages >= max_pages are not cached; rows past lens[b] are zero rows.  page_table_dev
+ *                       [M / T][max_pages].  Needs a LayerNorm;
+ *             1 RES:    out_dev = the k-tiled residual stream [M, N], updated in place; stats_out_dev [M][N / 16][2] or NULL (tiled
+ *                       family only);
+ *             2 ACT:    out_dev k-tiled [M, N] = act(...), act 0 none, 1 GELU, 2 ReLU;
+ *             3 LOGITS: out_dev [M, N] row-major or NULL; partials_dev = the (max, argmax) partials in the layout of
+ *                       mgea_op_skinny_logits_partials, P = plan_out[10]: the caller brings 2 * max(64, M) * ceil(N / 16) floats, or
+ *                       2 * max(64, M) * 512 if that is more (no plan has more partials).
+ *   plan_out  [MGEA_DECODE_GEMM_PLAN_INTS] (host) what ran: [0] kind (0 gemm_skinny_kernel, 1 head_balanced_kernel, 2
+ *             gemv_rows_kernel), [1] mt, [2] nt, [3] nw, [4] nch, [5] cw, [6] mr, [7] base, [8] grid.x, [9] grid.y, [10] n_partials;
+ *             all -1 when the plan was refused. */
+#define MGEA_DECODE_GEMM_PLAN_INTS 11
+typedef struct mgea_decode_gemm_args {
+    int32_t epi, rowmajor, w_f16;
+    int32_t M, N, K;
+    int32_t act;
+    float   eps;
+    const float* a_dev;
+    const void*  w_dev;
+    const float* bias_dev;        /* [N] or NULL */
+    const float* ln_c1_dev;
+    const float* ln_g_dev;
+    const float* ln_b_dev;
+    const float* stats_in_dev;
+    int32_t n_part, part_cnt;
+    float* out_dev;
+    float* stats_out_dev;
+    /* QKV */
+    void*  pages_dev;
+    const int32_t* page_table_dev;
+    const int32_t* ctx_len_dev;   /* [M / T] */
+    const int32_t* lens_dev;      /* [M / T] or NULL */
+    int32_t n_pages, page_dtype, n_head, head_dim, layer, max_pages, T;
+    int32_t reserved;             /* 0 */
+    /* LOGITS */
+    float* partials_dev;
+} mgea_decode_gemm_args;
+int mgea_op_decode_gemm(const mgea_decode_gemm_args* args, int32_t* plan_out, void* stream);
+/* W [N, K] row-major fp32 -> out_dev: mgea_op_tiled_weight_floats(N, K) fp16 fragments of v_mfma_f32_16x16x32_f16 (rows padded to 32
+ * with zeros): per (16-row tile, 32-wide k-chunk) one 1 KB block [lane = 16 g + c][8] holding W[tile * 16 + c][chunk * 32 + 8 g + 0..7],
+ * rounded to nearest even. */
+int mgea_op_tile_weights_f16(const float* w_dev, int32_t N, int32_t K, void* out_dev, void* stream);
+/* The folded-LayerNorm vectors when gamma is applied on the activation side (fp16 tiles): c1[n] = sum_k gamma[k] W[n,k],
+ * c2[n] = sum_k beta[k] W[n,k] + bias[n] (bias_dev NULL: + 0), fp64 sums of exact products, rounded once. */
+int mgea_op_ln_vectors(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* bias_dev, int32_t N, int32_t K,
+                       float* c1_out_dev, float* c2_out_dev, void* stream);
 /* Sampler on a logits matrix [B,V]; step selects the Philox counter.  probs_out_dev [B,V] or NULL
  * receives the pre-multinomial distribution. */
 int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s,

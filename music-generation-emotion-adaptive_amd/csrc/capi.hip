@@ -359,6 +359,60 @@ int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K) {
     return plan_decode_gemm(EPI_LOGITS, a, false, &p) == MGEA_OK ? p.n_partials : 0;
 }
 
+// test-only: any decode-GEMM plan on caller buffers (mgea.h).  Fills the argument block, plans, launches that plan, synchronises.
+int mgea_op_decode_gemm(const mgea_decode_gemm_args* g, int32_t* plan_out, void* stream) {
+    for (int i = 0; plan_out && i < MGEA_DECODE_GEMM_PLAN_INTS; ++i) plan_out[i] = -1;
+    MGEA_REQUIRE(g && g->a_dev && g->w_dev && g->M > 0 && g->N > 0 && g->K > 0 && !g->reserved, MGEA_EINVAL, "op_decode_gemm: bad argument");
+    const int epi = g->epi;
+    MGEA_REQUIRE(epi >= EPI_QKV && epi <= EPI_LOGITS, MGEA_EINVAL, "op_decode_gemm: bad epilogue %d", epi);
+    MGEA_REQUIRE(epi == EPI_LOGITS ? g->partials_dev != nullptr : g->out_dev != nullptr, MGEA_EINVAL,
+                 "op_decode_gemm: the epilogue's output buffer is NULL");
+    MGEA_REQUIRE(!g->ln_c1_dev || (g->stats_in_dev && g->n_part > 0 && g->part_cnt > 0), MGEA_EINVAL,
+                 "op_decode_gemm: the folded LayerNorm needs stats_in_dev, n_part and part_cnt");
+    SkinnyArgs a{};
+    a.A = g->a_dev; a.lda = g->K; a.W = static_cast<const float*>(g->w_dev); a.w_f16 = g->w_f16 != 0; a.bias = g->bias_dev;
+    a.M = g->M; a.N = g->N; a.K = g->K;
+    a.ln_c1 = g->ln_c1_dev; a.eps = g->eps; a.ln_g = g->ln_g_dev; a.ln_b = g->ln_b_dev;
+    a.stats_in = g->stats_in_dev; a.n_part = g->n_part; a.part_cnt = g->part_cnt;
+    a.out = g->out_dev; a.ldo = g->N; a.stats_out = g->stats_out_dev; a.act = g->act;
+    if (epi == EPI_QKV) {
+        MGEA_REQUIRE(g->pages_dev && g->page_table_dev && g->ctx_len_dev && g->n_pages > 0 && g->max_pages > 0 && g->n_head > 0 &&
+                         g->head_dim > 0 && g->head_dim % 8 == 0 && g->layer >= 0 && g->T >= 1 && g->M % g->T == 0 &&
+                         g->N == 3 * g->n_head * g->head_dim && (g->page_dtype == MGEA_DTYPE_F32 || g->page_dtype == MGEA_DTYPE_F16),
+                     MGEA_EINVAL, "op_decode_gemm: bad QKV argument (N = 3 * n_head * head_dim, M a multiple of T, fp32 or fp16 pages)");
+        a.pool = op_pool(g->pages_dev, g->n_pages, g->n_head, g->head_dim, g->page_dtype == MGEA_DTYPE_F16, 0);
+        a.layer = g->layer; a.page_table = g->page_table_dev; a.max_pages = g->max_pages; a.ctx_len = g->ctx_len_dev;
+        a.lens = g->lens_dev; a.T = g->T; a.C = g->n_head * g->head_dim;
+    }
+    DecodeGemmPlan p;
+    MGEA_TRY(plan_decode_gemm(epi, a, g->rowmajor != 0, &p));
+    if (epi == EPI_LOGITS) {   // the partials layout of mgea_op_skinny_logits_partials
+        a.pmax_val = g->partials_dev;
+        a.pmax_idx = reinterpret_cast<int32_t*>(g->partials_dev + (int64_t)(g->M > 64 ? g->M : 64) * p.n_partials);
+    }
+    if (plan_out) {
+        const int v[MGEA_DECODE_GEMM_PLAN_INTS] = {p.kind, p.mt, p.nt, p.nw, p.nch, p.cw, p.mr, p.base, (int)p.grid.x, (int)p.grid.y,
+                                                   p.n_partials};
+        for (int i = 0; i < MGEA_DECODE_GEMM_PLAN_INTS; ++i) plan_out[i] = v[i];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = launch_decode_gemm(epi, p, a, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    MGEA_TRY(rc);
+    MGEA_CHECK_HIP(e);
+    return MGEA_OK;
+}
+
+int mgea_op_tile_weights_f16(const float* w_dev, int32_t N, int32_t K, void* out_dev, void* stream) {
+    return launch_tile_weights_f16(w_dev, N, K, out_dev, (hipStream_t)stream);
+}
+
+int mgea_op_ln_vectors(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* bias_dev, int32_t N, int32_t K,
+                       float* c1_out_dev, float* c2_out_dev, void* stream) {
+    MGEA_REQUIRE(N > 0 && K > 0, MGEA_EINVAL, "op_ln_vectors: N=%d K=%d", N, K);
+    return launch_ln_vectors(w_dev, gamma_dev, beta_dev, bias_dev, N, K, c1_out_dev, c2_out_dev, (hipStream_t)stream);
+}
+
 int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s, int64_t step,
                    int32_t* ids_out_dev, float* probs_out_dev, void* stream) {
     MGEA_REQUIRE(logits_dev && s, MGEA_EINVAL, "op_sample: NULL argument");

@@ -164,6 +164,12 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
                     const float4 g0 = gf[buf][0], g1 = gf[buf][1];
                     x0 = make_float4(x0.x * g0.x, x0.y * g0.y, x0.z * g0.z, x0.w * g0.w);
                     x1 = make_float4(x1.x * g1.x, x1.y * g1.y, x1.z * g1.z, x1.w * g1.w);
+                    // The products are fp32 values BEFORE they are rounded to fp16, as the model above says.  In the generic stream the
+                    // compiler otherwise fuses part of them with their conversion (v_fma_mix*_f16: ONE rounding of the exact product),
+                    // which differs from the NCH > 0 streams where the fp32 product lands on an fp16 tie.  (No instruction: the
+                    // empty statement only makes the eight fp32 products visible.)
+                    if (NCH == 0)
+                        asm("" : "+v"(x0.x), "+v"(x0.y), "+v"(x0.z), "+v"(x0.w), "+v"(x1.x), "+v"(x1.y), "+v"(x1.z), "+v"(x1.w));
                 }
                 const h16x8 x8 = to_h8(x0, x1);
 #pragma unroll

@@ -55,6 +55,21 @@ class BertConfig(C.Structure):
 _P = C.c_void_p
 _I32, _I64, _F = C.c_int32, C.c_int64, C.c_float
 
+
+class DecodeGemmArgs(C.Structure):
+    """mgea_decode_gemm_args: one decode-step GEMM on caller buffers (mgea_op_decode_gemm, test only)."""
+    _fields_ = [("epi", _I32), ("rowmajor", _I32), ("w_f16", _I32), ("M", _I32), ("N", _I32), ("K", _I32), ("act", _I32), ("eps", _F),
+                ("a_dev", _P), ("w_dev", _P), ("bias_dev", _P), ("ln_c1_dev", _P), ("ln_g_dev", _P), ("ln_b_dev", _P),
+                ("stats_in_dev", _P), ("n_part", _I32), ("part_cnt", _I32), ("out_dev", _P), ("stats_out_dev", _P),
+                ("pages_dev", _P), ("page_table_dev", _P), ("ctx_len_dev", _P), ("lens_dev", _P),
+                ("n_pages", _I32), ("page_dtype", _I32), ("n_head", _I32), ("head_dim", _I32), ("layer", _I32), ("max_pages", _I32),
+                ("T", _I32), ("reserved", _I32), ("partials_dev", _P)]
+
+
+DECODE_GEMM_PLAN_INTS = 11
+EPI_QKV, EPI_RES, EPI_ACT, EPI_LOGITS = 0, 1, 2, 3
+DG_SKINNY, DG_HEAD, DG_GEMV = 0, 1, 2
+
 # name -> (restype, argtypes); every symbol include/mgea.h declares
 PROTOTYPES = {
     "mgea_last_error": (C.c_char_p, []),
@@ -119,6 +134,9 @@ PROTOTYPES = {
     "mgea_op_fold_ln": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "mgea_op_skinny": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_skinny_logits_partials": (C.c_int, [_I32, _I32, _I32]),
+    "mgea_op_decode_gemm": (C.c_int, [C.POINTER(DecodeGemmArgs), C.POINTER(_I32), _P]),
+    "mgea_op_tile_weights_f16": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "mgea_op_ln_vectors": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "mgea_op_sample": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _I64, _P, _P, _P]),
     "mgea_op_sample_penalized": (C.c_int, [_P, _I32, _I32, C.POINTER(SamplerConfig), _F, _P, _I64, _P, _P, _P]),
     "mgea_op_sample_rows": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, _I64, _P, _P, _P]),

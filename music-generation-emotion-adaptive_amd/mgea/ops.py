@@ -626,3 +626,142 @@ def head(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, want_logits: bool
     best = val.max(1, keepdim=True).values
     cand = torch.where(val == best, idx, torch.full_like(idx, 2 ** 31 - 1))
     return out, cand.min(1).values, P
+
+
+# ---- the decode-step GEMMs one plan at a time (mgea_op_decode_gemm: tests only) ----
+POISON_BITS = 0x7FC5A5A5   # a quiet NaN no kernel produces: buffers pre-filled with it show, compared as int32, what was written
+PLAN_KEYS = ("kind", "mt", "nt", "nw", "nch", "cw", "mr", "base", "grid_x", "grid_y", "n_partials")
+
+
+def poison(n, dtype=torch.float32, device="cpu") -> torch.Tensor:
+    """n elements of `dtype` (fp32 or fp16) whose bits are POISON_BITS (fp16: its upper half, also a NaN)"""
+    if dtype == torch.float16:
+        return torch.full((int(n),), POISON_BITS >> 16, dtype=torch.int16, device=device).view(torch.float16)
+    return torch.full((int(n),), POISON_BITS, dtype=torch.int32, device=device).view(torch.float32)
+
+
+def tile_weights_f16(w: torch.Tensor) -> torch.Tensor:
+    """W [N,K] row-major fp32 -> the fp16 fragments the fp16-weight decode GEMMs read (rows padded to 32 with zeros)."""
+    lib = _lib.load()
+    w = _dev(w.float())
+    N, K = w.shape
+    out = torch.empty(lib.mgea_op_tiled_weight_floats(N, K), dtype=torch.float16, device=w.device)
+    check(lib.mgea_op_tile_weights_f16(ptr(w), N, K, ptr(out), stream_ptr()))
+    return out
+
+
+def ln_vectors(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Optional[torch.Tensor] = None):
+    """(c1 [N] = sum_k gamma[k] w[n,k], c2 [N] = sum_k beta[k] w[n,k] + bias[n]) of the folded LayerNorm with gamma on the
+    activation side (fp16 weights): w is the matrix the kernel multiplies with, i.e. already rounded to fp16 values."""
+    lib = _lib.load()
+    w, gamma, beta = _dev(w.float()), _dev(gamma.float()), _dev(beta.float())
+    b = None if bias is None else _dev(bias.float())
+    N, K = w.shape
+    c1 = torch.empty(N, dtype=torch.float32, device=w.device)
+    c2 = torch.empty(N, dtype=torch.float32, device=w.device)
+    check(lib.mgea_op_ln_vectors(ptr(w), ptr(gamma), ptr(beta), ptr(b), N, K, ptr(c1), ptr(c2), stream_ptr()))
+    return c1, c2
+
+
+def decode_gemm(epi: int, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], M: int, N: int, K: int, *,
+                rowmajor: bool = False, w_f16: bool = False, act: int = 0, eps: float = 1e-5, ln_c1=None, ln_g=None, ln_b=None,
+                stats_in=None, part_cnt: int = 16, out=None, stats_out=None, kv: Optional[dict] = None, partials=None,
+                want_out: bool = True):
+    """One decode-step GEMM through mgea_op_decode_gemm on prepared device buffers: a = k-tiled activations (tile_rows), w = the
+    row-major matrix (rowmajor), the tiled copy (tile_weights / fold_ln) or fp16 fragments (w_f16, tile_weights_f16).  epi 0 QKV
+    (kv = dict(pages, n_pages, n_head, head_dim, layer, page_table [B, max_pages], ctx_len [B], lens=None, T=1); pages: the device
+    image of >= layer + 1 layers, written in place), 1 RES (out = the k-tiled residual, updated in place), 2 ACT, 3 LOGITS.
+    Buffers not passed are allocated: out (QKV / LOGITS row-major [M, N] filled with NaN, ACT k-tiled zeros), stats_out for RES,
+    the LOGITS partials pre-filled with POISON_BITS.  Returns (out, extras, plan): extras holds stats_out [M, N / 16, 2] (RES) or
+    partials = the raw buffer with R = max(64, M) and P = plan['n_partials'] (LOGITS: values [R][P] then indices [R][P], mgea.h);
+    plan maps PLAN_KEYS to what ran.  A refused plan raises RuntimeError and launches nothing."""
+    lib = _lib.load()
+    dev = a.device
+    g = _lib.DecodeGemmArgs()
+    keep = [_dev(a), _dev(w)]
+    if keep[0].dtype != torch.float32 or keep[1].dtype != (torch.float16 if w_f16 else torch.float32):
+        raise RuntimeError("decode_gemm: a is fp32; w is fp32, or fp16 fragments with w_f16")
+    if keep[0].numel() < (M + 63) // 64 * 64 * K or keep[1].numel() < (N * K if rowmajor else lib.mgea_op_tiled_weight_floats(N, K)):
+        raise RuntimeError("decode_gemm: a or w is smaller than its layout needs")
+
+    def f32(t, n=None):
+        if t is None:
+            return None
+        t = _dev(t)
+        if t.dtype != torch.float32 or (n is not None and t.numel() < n):
+            raise RuntimeError("decode_gemm: an fp32 vector is too short or of another dtype")
+        keep.append(t)
+        return t
+
+    g.epi, g.rowmajor, g.w_f16, g.M, g.N, g.K, g.act, g.eps = int(epi), int(bool(rowmajor)), int(bool(w_f16)), M, N, K, int(act), float(eps)
+    g.a_dev, g.w_dev, g.bias_dev = ptr(keep[0]), ptr(keep[1]), ptr(f32(bias, N))
+    g.ln_c1_dev, g.ln_g_dev, g.ln_b_dev = ptr(f32(ln_c1, N)), ptr(f32(ln_g, K)), ptr(f32(ln_b, K))
+    if stats_in is not None:
+        stats_in = f32(stats_in)
+        if stats_in.ndim != 3 or stats_in.shape[0] < M or stats_in.shape[2] != 2:
+            raise RuntimeError("decode_gemm: stats_in must be [M, n_part, 2]")
+        g.stats_in_dev, g.n_part, g.part_cnt = ptr(stats_in), stats_in.shape[1], int(part_cnt)
+    tiled = (M + 63) // 64 * 64 * N
+    extras = {}
+    if epi == _lib.EPI_RES:
+        if out is None or out.numel() < tiled:
+            raise RuntimeError("decode_gemm: RES updates the k-tiled residual `out` in place")
+        if stats_out is None and not rowmajor:
+            stats_out = torch.zeros(max(64, M) * (N // 16) * 2, dtype=torch.float32, device=dev)
+    elif epi == _lib.EPI_ACT:
+        if out is None:
+            out = torch.zeros(tiled, dtype=torch.float32, device=dev)
+        if out.numel() < tiled:
+            raise RuntimeError("decode_gemm: ACT writes a k-tiled buffer of whole 64-row groups")
+    elif out is None and (want_out or epi == _lib.EPI_QKV):
+        out = torch.full((M, N), float("nan"), dtype=torch.float32, device=dev)
+    if out is not None and (out.dtype != torch.float32 or out.numel() < M * N or not out.is_contiguous()):
+        raise RuntimeError("decode_gemm: out must be a contiguous fp32 tensor of at least M * N elements")
+    g.out_dev = ptr(out)
+    if stats_out is not None:
+        if stats_out.numel() < M * (N // 16) * 2:
+            raise RuntimeError("decode_gemm: stats_out holds [M, N / 16, 2]")
+        g.stats_out_dev = ptr(f32(stats_out))
+        extras["stats_out"] = stats_out[: M * (N // 16) * 2].view(M, N // 16, 2)
+    if epi == _lib.EPI_QKV:
+        pages, H, dh, layer, T = kv["pages"], int(kv["n_head"]), int(kv["head_dim"]), int(kv["layer"]), int(kv.get("T", 1))
+        n_pages = int(kv["n_pages"])
+        if pages.dtype not in (torch.float32, torch.float16) or not pages.is_contiguous() or pages.device != dev:
+            raise RuntimeError("decode_gemm: pages must be a contiguous fp32 or fp16 device tensor")
+        if layer < 0 or pages.numel() < (layer + 1) * kv_page_elems(n_pages, H, dh):
+            raise RuntimeError("decode_gemm: the page image must hold layer + 1 layers of n_pages pages")
+        pt = _dev(kv["page_table"].to(torch.int32))
+        cl = _dev(kv["ctx_len"].to(torch.int32))
+        l32 = None if kv.get("lens") is None else _dev(kv["lens"].to(torch.int32))
+        if T < 1 or M % T or pt.ndim != 2 or pt.shape[0] != M // T or cl.shape != (M // T,) or (l32 is not None and l32.shape != cl.shape):
+            raise RuntimeError("decode_gemm: page_table [M / T, max_pages], ctx_len and lens [M / T]")
+        if int(pt.min()) < 0 or int(pt.max()) >= n_pages or int(cl.min()) < 0:
+            raise RuntimeError("decode_gemm: page table entries must lie in [0, n_pages), context lengths must not be negative")
+        keep += [pt, cl, l32]
+        g.pages_dev, g.page_table_dev, g.ctx_len_dev, g.lens_dev = ptr(pages), ptr(pt), ptr(cl), ptr(l32)
+        g.n_pages, g.page_dtype = n_pages, (_lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32)
+        g.n_head, g.head_dim, g.layer, g.max_pages, g.T = H, dh, layer, pt.shape[1], T
+    if epi == _lib.EPI_LOGITS:
+        R = max(64, M)
+        need = 2 * R * max((N + 15) // 16, 512)
+        if partials is None:
+            partials = poison(need + 64, device=dev)
+        if partials.dtype != torch.float32 or partials.numel() < need:
+            raise RuntimeError(f"decode_gemm: the partials buffer needs {need} floats")
+        g.partials_dev = ptr(partials)
+        extras.update(partials=partials, R=R)
+    po = (C.c_int32 * _lib.DECODE_GEMM_PLAN_INTS)()
+    check(lib.mgea_op_decode_gemm(C.byref(g), po, stream_ptr()))
+    plan = dict(zip(PLAN_KEYS, (int(v) for v in po)))
+    if epi == _lib.EPI_LOGITS:
+        extras["P"] = plan["n_partials"]
+    return out, extras, plan
+
+
+def merge_partials(partials: torch.Tensor, M: int, R: int, P: int) -> torch.Tensor:
+    """the greedy tail's merge of the (max, argmax) partials of rows < M: the lowest index among the partials that hold the row maximum"""
+    p = partials.cpu()
+    val = p[: R * P].view(R, P)[:M]
+    idx = p[R * P: 2 * R * P].view(torch.int32).view(R, P)[:M].long()
+    best = val.max(1, keepdim=True).values
+    return torch.where(val == best, idx, torch.full_like(idx, 2 ** 31 - 1)).min(1).values
