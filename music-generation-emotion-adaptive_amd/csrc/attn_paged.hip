@@ -7,8 +7,10 @@
 // pages w, w+4, ... (one page = 64 tokens = one wave tile) and are merged through LDS with the
 // usual (max, sum, acc) rescale.  B*H = 512 workgroups at the benchmark shape -> 8 waves per CU.
 //   QK^T : lane = token.  The K page is stored [dh/4][64 tokens][4], so each of the dh/4 loads
-//          of a wave is one fully coalesced 1 KiB global_load_dwordx4; q is wave-uniform (scalar
-//          loads -> SGPR operands of the FMAs); no cross-lane reduction for the dot product.
+//          of a wave is one fully coalesced 1 KiB global_load_dwordx4; q is wave-uniform and lives in
+//          dh VGPRs: every wave fetches it with ONE vector load per 64 dimensions (lane = dimension),
+//          scales it and spreads it with v_readlane + v_mov (see "q:" in the kernel); no cross-lane
+//          reduction for the dot product.
 //   softmax: online, one wave-wide max per 64-token tile (shuffle reduction), per-lane partial
 //          sums reduced once at the end.
 //   PV   : lane = (token group g, 16-byte d-chunk c).  V page is [64 tokens][dh]: a wave
@@ -56,7 +58,13 @@ __global__ __launch_bounds__(256) void attn_paged_kernel(const float* __restrict
     __shared__ float s_m[4], s_l[4];
     __shared__ float s_acc[4][DH];
 
-    const int bh = blockIdx.x;
+    // The argument block in ONE batch of scalar loads and one wait: the zero below is "computed from" every argument, so all of them
+    // are fetched in front of the first index that needs one (the compiler otherwise leaves the page fields for a second batch behind
+    // the first wait).
+    int zero;
+    asm("s_mov_b32 %0, 0" : "=s"(zero) : "s"(qkv), "s"(pool.base), "s"(pool.H), "s"(pool.dh), "s"(pool.layer_stride), "s"(pool.arith_batch),
+        "s"(layer), "s"(page_table), "s"(max_pages), "s"(ctx_len), "s"(lens), "s"(out), "s"(H), "s"(T), "s"(C), "s"(scale), "s"(tiled_out));
+    const int bh = blockIdx.x + zero;
     const int b = bh / H, h = bh % H;
     const int arith_b = pool.arith_batch;   // > 0: physical page = logical page * arith_b + row (no table load in front of the K | V loads)
     const int t = blockIdx.y;
@@ -72,21 +80,22 @@ __global__ __launch_bounds__(256) void attn_paged_kernel(const float* __restrict
     // flight, and while PV consumes V(page) the K(next page) loads are -- each wave keeps 16 KiB
     // (one operand tile) streaming at all times.  K/V are read once per step: non-temporal loads.
     f32x4 kk[NCH], vv[NVI];   // raw 16-byte groups: 4 floats or 8 halves
-    auto page_base = [&](int pg, int isv) {
-        const int phys = arith_b > 0 ? pg * arith_b + b : page_table[b * max_pages + pg];
-        return lbase + ((int64_t)(phys * 2 + isv) * H + h) * pf * EB;
-    };
+    // physical page of logical page pg: computed, or one scalar load from the table -- looked up ONCE per page, for its K and its V
+    auto phys_of = [&](int pg) { return arith_b > 0 ? pg * arith_b + b : page_table[b * max_pages + pg]; };
+    auto page_base = [&](int phys, int isv) { return lbase + ((int64_t)(phys * 2 + isv) * H + h) * pf * EB; };
     auto ldraw = [](const char* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); };
     // n_tok = tokens of the page that are in the cache: lanes (= tokens) past the end of the last, partial page
     // re-read the last cached token instead of their own slot -- a wave instruction is 1 KiB of consecutive bytes,
     // so the tail of the page is never fetched from HBM (whole-page reads cost 8 % extra traffic on the benchmark
     // run).  Clamped addresses rather than predication: a load inside a branch makes the compiler drain vmcnt to 0
     // at the next use and the K/V pipelining below is lost.
+    int phys = 0;   // of the page whose K was requested last
     auto load_k = [&](int pg, int n_tok) {
-        const char* kpage = page_base(pg, 0);
+        phys = phys_of(pg);
+        const char* kpage = page_base(phys, 0);
         const int tok = lane < n_tok ? lane : n_tok - 1;
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) kk[i] = ldraw(kpage + (i * 64 + tok) * 16);
+        for (int i = 0; i < NCH; ++i) kk[i] = ldraw(kpage + (unsigned)(i * 64 + tok) * 16u);   // (unsigned: uniform base + 32-bit lane offset)
     };
     // Wave 0's first K tile (page 0 always holds a token) is requested before anything else is known, so that the page-table -> K
     // round trips overlap the ctx_len / q fetches; the length is not known yet: the whole page.  Waves 1..3 wait for the length
@@ -98,36 +107,66 @@ __global__ __launch_bounds__(256) void attn_paged_kernel(const float* __restrict
     const int zsplit = SPLIT ? (int)blockIdx.z : 0, nsplit = SPLIT ? (int)gridDim.z : 1;
     if (wave == 0 && zsplit == 0) load_k(0, 64);
 
-    const int n_new = lens ? lens[b] : T;
+    // q: ONE vector load per 64 dimensions -- lane l takes q[64 i + l] -- requested here, beside the lengths, and spread over the wave
+    // (readlane: wave-uniform values, as the FMAs want them) only once the first page's K and V are on their way.  Through the
+    // scalar path the compiler fetched it as DH / 16 loads of 64 bytes, each awaited before the next was issued and the first one
+    // behind the wait for the length: four more dependent round trips at head_dim 64, on lines the QKV launch has just written
+    // from other CUs.  (Sixteen 16-byte loads of the same addresses by every lane would also do; they cost each wave 16 KiB of L1
+    // returns where this costs 256 bytes, in a kernel whose L1 is busy streaming pages.)  The load is a relaxed wave-scope atomic
+    // only because the compiler may not sink one of those to its first use, behind the lengths' wait; the instruction is a plain
+    // global_load_dword.  A padded query row asks too: its address lies inside the qkv buffer, and nothing waits for the answer.
+    constexpr int NQ = (DH + 63) / 64;
+    const float* qp = qkv + m * 3 * C + h * DH;
+    float qraw[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i)
+        qraw[i] = __hip_atomic_load(qp + min(64 * i + lane, DH - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+
+    // the row's two lengths in one round trip (without `lens` the second load repeats the first)
+    int c_len = ctx_len[b];
+    int l_new = (lens ? lens : ctx_len)[b];
+    asm("" : "+s"(c_len), "+s"(l_new));   // (both are there before either is looked at: one wait, not two)
+    const int n_new = lens ? l_new : T;
     auto optr = [&](int d) { return tiled_out ? out + tiled_off((int)m, h * DH + d, C) : out + m * C + h * DH + d; };
     if (t >= n_new) {  // padded query row: defined output, never used
         if (threadIdx.x < DH && zsplit == 0) *optr(threadIdx.x) = 0.f;
         return;
     }
-    const int len = ctx_len[b] + n_new;  // tokens visible to this query (whole cache, no mask)
+    const int len = c_len + n_new;  // tokens visible to this query (whole cache, no mask)
     const int npages = (len + 63) >> 6;
     const int active = SPLIT ? min(nsplit, (npages + 3) >> 2) : 1;   // splits that have a page
     if (SPLIT && zsplit >= active) return;
     const int pg0 = zsplit * 4 + wave, pg_step = 4 * nsplit;
     if ((wave != 0 || zsplit != 0) && pg0 < npages) load_k(pg0, len - pg0 * 64);
 
-    const float* qp = qkv + m * 3 * C + h * DH;
-    float q[DH];
-#pragma unroll
-    for (int d = 0; d < DH; ++d) q[d] = qp[d] * scale;  // 1/sqrt(64) etc.: power-of-two scales are exact
-
+    float q[DH];   // set on the wave's first page, below
     float mx = -INFINITY, lsum = 0.f;
     float acc[G];
 #pragma unroll
     for (int e = 0; e < G; ++e) acc[e] = 0.f;
 
     for (int pg = pg0; pg < npages; pg += pg_step) {
-        const char* vpage = page_base(pg, 1);
+        const char* vpage = page_base(phys, 1);   // its K was the last one requested
         const int n_tok = len - pg * 64;   // >= 1; > 64 for a full page
 #pragma unroll
         for (int j = 0; j < NVI; ++j) {   // rows beyond the cache end: the last cached row instead (their p is 0)
-            const int row = v_lane ? j * TPI + g : 0;
-            vv[j] = ldraw(vpage + ((row < n_tok ? row : n_tok - 1) * DH + c * G) * EB);
+            // row = min(j * TPI + g, n_tok - 1), written so that the sixteen j * TPI + g are not kept in a register each all kernel long
+            const int row = min(n_tok - 1 - j * TPI, v_lane ? g : 0) + j * TPI;
+            vv[j] = ldraw(vpage + (unsigned)(row * DH + c * G) * (unsigned)EB);
+        }
+        if (pg == pg0) {   // q arrives: behind it in the queue are this page's V and, on waves 1..3, its K -- which the first FMA needs as well
+            __builtin_amdgcn_sched_barrier(0);   // the V loads above are issued before the wait for q below
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                float qr = qraw[i];
+                asm("" : "+v"(qr));   // (keeps the scaling, and with it the wait, inside this block)
+                const int qs = __builtin_bit_cast(int, qr * scale);  // 1/sqrt(64) etc.: power-of-two scales are exact
+#pragma unroll
+                for (int d = 64 * i; d < DH && d < 64 * i + 64; ++d) {
+                    q[d] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(qs, d - 64 * i));
+                    asm("" : "+v"(q[d]));   // a VGPR each, as before: left in SGPRs they exceed the scalar file and are spilled into the loop
+                }
+            }
         }
 
         float s0 = 0.f, s1 = 0.f;   // two chains; fp32: the same order as before (groups alternate between them)

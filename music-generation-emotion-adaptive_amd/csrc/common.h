@@ -144,6 +144,7 @@ struct KvPool {
     void* base;
     int32_t n_pages;      // physical pages per layer
     int32_t H, dh;
+    int32_t spare;        // (the word the alignment of layer_stride leaves free, named so that a kernel can list it with the rest: SkinnyArgs)
     int64_t layer_stride; // elements
     int32_t f16;          // 0: float elements, 1: _Float16 elements
     int32_t arith_batch;  // > 0: the page table holds logical page j of row b -> physical j * arith_batch + b (what mgea_decoder_reset
@@ -408,31 +409,46 @@ int launch_kv_scatter_f16(const void* qkv, const KvPool& pool, int layer, const 
 enum { EPI_QKV = 0, EPI_RES = 1, EPI_ACT = 2, EPI_LOGITS = 3 };
 
 struct SkinnyArgs {
-    const float* A; int lda;
+    // Field order is part of the kernels' prologue: what a decode launch reads comes first, without a hole, in the order of the
+    // 64-byte lines of the kernel-argument block -- lines 0 and 1 for every epilogue, lines 2 and 3 for the QKV scatter.  The kernels
+    // name every one of these fields in front of their first instruction, so the compiler fetches the lines with one batch of scalar
+    // loads and one wait; a field it does not need, or a padding word, inside a wide load is a register it reuses at once, and the
+    // load that reuses it has to wait for the first batch to land (tools/prologue_chain.py shows the batches of the compiled kernels).
+    // ---- line 0
+    const float* A;
     const float* W;            // [N, K] in the tiled weight layout (launch_tile_weights); fp16 tiles (launch_tile_weights_f16) if w_f16
-    int w_f16;                 // MGEA_DTYPE_F16 engines: W holds _Float16 fragments, A is rounded to fp16 on load, f16 MFMA, fp32 accumulate
     const float* bias;         // [N] or NULL
-    int M, N, K;
+    float* out;                // QKV: qkv_out [M, N]; RES: x [M, N] (in place); ACT: out [M, ldo]; LOGITS: logits or NULL
+    int M, N, K; int ldo;
     // folded LayerNorm (ln_c1 != NULL): W holds gamma * W, ln_c1 [N] = its row sums, bias = beta @ W^T + bias
     // (launch_ln_fold); per-row partial stats [64][n_part][2], each over `part_cnt` elements
-    const float* ln_c1; float eps;
-    const float* ln_g; const float* ln_b;   // gemv: LayerNorm gamma / beta applied directly (W row-major, unfolded);
-                                            // w_f16 with ln_c1: gamma is applied to A on load (W stays the plain rounded matrix,
-                                            // ln_c1 = sum_k gamma_k W[n,k], bias = sum_k beta_k W[n,k] + b[n])
-    const float* stats_in; int n_part; int part_cnt;
+    const float* ln_c1; const float* stats_in;
+    // ---- line 1
+    float eps; int n_part; int part_cnt;
     float inv_n_part, inv_k;   // 1 / n_part and 1 / (n_part * part_cnt), filled by the launcher (no division in the kernel)
-    // outputs
-    float* out; int ldo;       // QKV: qkv_out [M, N]; RES: x [M, N] (in place); ACT: out [M, ldo]; LOGITS: logits or NULL
-    float* stats_out;          // RES: [64][N/16][2]
     int act;
-    // QKV scatter
-    KvPool pool; int layer; const int32_t* page_table; int max_pages; const int32_t* ctx_len;
-    const int32_t* lens; int T; int C;
-    // LOGITS
-    float* pmax_val; int32_t* pmax_idx;   // [M][n_partials] (DecodeGemmPlan)
     int dbg;                   // ablation bits for tools/skinny_bench.py (0 in production)
     int nw;                    // waves per workgroup (set by the launcher)
+    float* stats_out;          // RES: [64][N/16][2]
+    const float* ln_g;         // gemv: LayerNorm gamma applied directly (W row-major, unfolded); w_f16 with ln_c1: gamma is applied
+                               // to A on load (W stays the plain rounded matrix, ln_c1 = sum_k gamma_k W[n,k], bias = sum_k beta_k W[n,k] + b[n])
+    float* pmax_val; int32_t* pmax_idx;   // LOGITS: [M][n_partials] (DecodeGemmPlan)
+    // ---- lines 2 and 3: QKV scatter
+    KvPool pool; int layer; int max_pages; const int32_t* page_table; const int32_t* ctx_len;
+    const int32_t* lens; int T; int C;
+    // ---- what no decode GEMM kernel reads from the block
+    int lda;
+    int w_f16;                 // MGEA_DTYPE_F16 engines: W holds _Float16 fragments, A is rounded to fp16 on load, f16 MFMA, fp32 accumulate
+    const float* ln_b;         // gemv: LayerNorm beta applied directly
 };
+
+// lines 0 and 1 / lines 2 and 3 of the block as operands of an empty asm statement: every field is then in a scalar register in front of it
+#define MGEA_SKINNY_ARGS_01(a) "s"((a).A), "s"((a).W), "s"((a).bias), "s"((a).out), "s"((a).M), "s"((a).N), "s"((a).K), "s"((a).ldo), \
+    "s"((a).ln_c1), "s"((a).stats_in), "s"((a).eps), "s"((a).n_part), "s"((a).part_cnt), "s"((a).inv_n_part), "s"((a).inv_k), "s"((a).act), \
+    "s"((a).dbg), "s"((a).nw), "s"((a).stats_out), "s"((a).ln_g), "s"((a).pmax_val), "s"((a).pmax_idx)
+#define MGEA_SKINNY_ARGS_23(a) "s"((a).pool.base), "s"((a).pool.n_pages), "s"((a).pool.H), "s"((a).pool.dh), "s"((a).pool.spare), "s"((a).pool.layer_stride), \
+    "s"((a).pool.f16), "s"((a).pool.arith_batch), "s"((a).layer), "s"((a).max_pages), "s"((a).page_table), "s"((a).ctx_len), "s"((a).lens), \
+    "s"((a).T), "s"((a).C)
 
 // ---- decode GEMMs: one launch plan per call (gemm_skinny.hip) ----------------------------------------------------
 // Three kernel families serve them: gemm_skinny_kernel (tiled, LayerNorm-folded operands), head_balanced_kernel (head_gemm.hip:

@@ -70,16 +70,14 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
 
     // grid.x is padded to a multiple of 8 so that the workgroups sharing a W tile (same blockIdx.x, different
     // blockIdx.y) are a multiple of 8 apart in dispatch order = same XCD / same L2 (speed only)
-    // The kernel-argument block (4 x 64-B lines) is read with scalar loads the compiler otherwise sinks to
-    // their first use, block by block: each is a cold scalar-cache miss of several hundred ns on the critical
-    // path of a ~6 us kernel.  Asking for every field here makes them ONE batch of loads and one wait.
-    asm volatile("" :: "s"(a.A), "s"(a.W), "s"(a.bias), "s"(a.M), "s"(a.N), "s"(a.K), "s"(a.ln_c1), "s"(a.eps),
-                       "s"(a.stats_in), "s"(a.n_part), "s"(a.part_cnt), "s"(a.out), "s"(a.ldo), "s"(a.stats_out), "s"(a.act), "s"(a.dbg), "s"(a.nw));
-    if (F16 && LN) asm volatile("" :: "s"(a.ln_g));
-    if (EPI == EPI_QKV)
-        asm volatile("" :: "s"(a.pool.base), "s"(a.pool.H), "s"(a.pool.dh), "s"(a.pool.layer_stride), "s"(a.pool.f16), "s"(a.layer), "s"(a.page_table),
-                           "s"(a.max_pages), "s"(a.ctx_len), "s"(a.lens), "s"(a.T), "s"(a.C));
-    if (EPI == EPI_LOGITS) asm volatile("" :: "s"(a.pmax_val), "s"(a.pmax_idx));
+    // The kernel-argument block is read with scalar loads the compiler otherwise sinks to their first use, block by block: each is
+    // a cold scalar-cache miss of several hundred ns on the critical path of a ~6 us kernel.  Naming every field here puts the loads
+    // in front of this point; that they are ONE batch with one wait behind it also needs every register of every load to stay in
+    // use up to here -- a field left out, or a padding word inside a wide load, is a register the compiler hands to the next load,
+    // which then waits for the first batch to land (that was the second batch of six the decode instantiations had).  So
+    // SkinnyArgs keeps what a kernel reads in whole lines without holes (common.h) and the lists name all of it.
+    if (EPI == EPI_QKV) asm volatile("" :: MGEA_SKINNY_ARGS_23(a));
+    asm volatile("" :: MGEA_SKINNY_ARGS_01(a));
     const int n_tiles = (a.N + COLS - 1) / COLS;
     if ((int)blockIdx.x >= n_tiles) return;
     const int tid = threadIdx.x, lane = tid & 63;

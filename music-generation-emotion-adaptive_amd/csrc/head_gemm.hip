@@ -37,7 +37,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     extern __shared__ __attribute__((aligned(16))) float red[];   // [8 waves][NU][16][HB_PITCH], then pb_val[64][NS], pb_idx[64][NS]
     float* pb_val = red + 8 * NU * 16 * HB_PITCH;
     int* pb_idx = reinterpret_cast<int*>(pb_val + 64 * NS);
-    asm volatile("" :: "s"(a.A), "s"(a.W), "s"(a.bias), "s"(a.M), "s"(a.N), "s"(a.K), "s"(a.out), "s"(a.ldo), "s"(a.pmax_val), "s"(a.pmax_idx));
+    // the argument block in one batch of scalar loads and one wait (gemm_skinny.hip says how): lines 0 and 1 whole, and the two words
+    // behind the struct
+    asm volatile("" :: MGEA_SKINNY_ARGS_01(a), "s"(n_extra), "s"(gridDim.x));
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, g = lane >> 4;

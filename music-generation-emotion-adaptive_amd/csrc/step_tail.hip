@@ -42,10 +42,20 @@ __global__ __launch_bounds__(256) void argmax_advance_embed_kernel(const float* 
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ float sh[8];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the row's bookkeeping state is requested together with the partials (one round trip instead of two)
-    int st_step = 0, st_fed = 0, st_len = 0, st_done = 0;
-    if (tid == 0) { st_step = t.s.row_step[b]; st_fed = t.s.cur_ids[b]; st_len = t.s.ctx_len[b]; st_done = t.s.done[b]; }
+    // The argument block in ONE batch of scalar loads and one wait: the row index below is "computed from" every field (two empty
+    // statements, 30 operands each at most), so all of them are fetched in front of the first address that needs one -- the compiler
+    // otherwise fetches them where they are first used, in four batches with a wait each (tools/prologue_chain.py).
+    int zero;
+    asm("s_mov_b32 %0, 0" : "=s"(zero) : "s"(pval), "s"(pidx), "s"(n_tiles), "s"(sampled), "s"(t.s.cur_ids), "s"(t.s.ctx_len), "s"(t.s.done),
+        "s"(t.s.row_step), "s"(t.s.n_done), "s"(t.s.ids_out), "s"(t.s.n_steps), "s"(t.s.eos_id), "s"(t.s.params), "s"(t.tok_emb), "s"(t.pos_emb),
+        "s"(t.x), "s"(t.stats), "s"(t.C), "s"(t.vocab), "s"(t.pos_rows), "s"(t.absolute_pos));
+    asm("" : "+s"(zero) : "s"(t.qkv0), "s"(t.qkv), "s"(t.pool.base), "s"(t.pool.n_pages), "s"(t.pool.H), "s"(t.pool.dh), "s"(t.pool.spare),
+        "s"(t.pool.layer_stride),
+        "s"(t.pool.f16), "s"(t.pool.arith_batch), "s"(t.page_table), "s"(t.max_pages));
+    const int b = blockIdx.x + zero, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the row's bookkeeping state is requested together with the partials (one round trip instead of two): four scalar loads by every
+    // wave -- only thread 0 uses them, but loaded by it alone they were awaited, as that thread's values, in front of the partials' loads
+    const int st_step = t.s.row_step[b], st_fed = t.s.cur_ids[b], st_len = t.s.ctx_len[b], st_done = t.s.done[b];
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = tid; i < n_tiles; i += 256) {
