@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "devmem.h"
+#include "hipres.h"
 
 namespace mgea {
 static thread_local char g_err[512] = "";
@@ -24,6 +25,13 @@ const char* get_error() { return g_err; }
 
 bool dev_malloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
 void dev_free(void* p) { (void)hipFree(p); }
+bool pinned_malloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, 0) == hipSuccess; }
+void pinned_free(void* p) { (void)hipHostFree(p); }
+void event_destroy(hipEvent_t ev) { (void)hipEventDestroy(ev); }
+void graph_destroy(hipGraph_t graph, hipGraphExec_t exec) {
+    if (exec) (void)hipGraphExecDestroy(exec);   // (NULL: a graph whose capture or instantiation failed)
+    if (graph) (void)hipGraphDestroy(graph);
+}
 
 // ---- switches: one table, initialised from the environment when the library is loaded ---------
 namespace {

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "devmem.h"
+#include "hipres.h"
 
 using namespace mgea;
 
@@ -87,6 +88,10 @@ struct mgea_decoder {
     DevGroup dev_ws;         // the workspace: released and regrown by ensure_ws
     DevGroup dev_p16_rows;   // Prefill16's activations and tables, regrown with its row count (ensure_p16)
     DevGroup dev_p16_mats;   // Prefill16's matrices p16.w / p16.vec, kept across refresh_weights
+    // The handle's other HIP resources, declared behind the device groups, so that they go first (members die in reverse order):
+    // the graphs, the pinned staging arrays and the events, then the device memory.
+    Event stage_free;        // recorded after the copy out of samp_stage / gram_stage: they may be rewritten once it has completed
+    PinnedGroup pinned;      // samp_stage, gram_stage
 
     // KV pool
     KvPool kv{};
@@ -113,12 +118,9 @@ struct mgea_decoder {
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
-    struct GraphEntry { int batch; StepForm form; bool scored; int steps; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
-    std::vector<GraphEntry> graphs;
-    uint64_t use_clock = 0;
+    StepGraphs graphs;
     SamplerParams* samp_dev = nullptr;     // [max_batch] records, one per row (common.h)
     SamplerParams* samp_stage = nullptr;   // [max_batch] pinned host records of mgea_decoder_generate_rows, copied to samp_dev in stream order
-    hipEvent_t stage_free = nullptr;       // recorded after that copy: the staging buffer may be rewritten once it has completed
     // repetition penalty: per row the set of ids it has seen (prompt + generated), [max_batch][presence_words(vocab)] (common.h);
     // seeded by a penalized generate() after its prefill, then updated by the kernel that commits each row's token
     uint32_t* presence = nullptr;
@@ -156,12 +158,13 @@ struct mgea_decoder {
     bool qkv0_no_mem[2] = {false, false};  // the table could not be allocated: the path keeps the launch for the life of the handle (never
                                            // retried: the graphs of a batch size have one form)
     int32_t* qkv0_ids = nullptr;   // 0 .. vocab - 1, then 64 zeros: the ids and the ctx_len of the build launches
-    int64_t counters[8] = {0};
+    // what mgea_decoder_stats reports besides the graph cache's own two figures; the *_steps and graph_replays are of the last generation
+    struct Counters { int64_t graph_nodes = 0, graph_replays = 0, scored_steps = 0, prefill16_forwards = 0, penalized_steps = 0, biased_steps = 0; } n;
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline leg)
     int prof_stride = 0;  // 0 = off; n = time every n-th decode step of generate(), run eagerly
     bool prof_now = false;
-    struct ProfRec { hipEvent_t a, b; int cls; };
-    std::vector<ProfRec> prof;
+    struct ProfRec { Event a, b; int cls; };
+    std::vector<ProfRec> prof;   // unread records go with the handle
 
     const float* w(int idx) const { return arena + off[idx]; }
     const float* lw(int layer, int j) const { return arena + off[2 + layer * L_COUNT + j]; }
@@ -209,18 +212,18 @@ struct ProfScope {
     mgea_decoder* h;
     hipStream_t st;
     bool on;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;   // (half a pair, where the second create fails, goes with the scope)
     int cls;
     ProfScope(mgea_decoder* h_, int cls_, hipStream_t st_) : h(h_), st(st_), on(h_->prof_now), cls(cls_) {
         if (on) {
-            on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-            if (on) (void)hipEventRecord(a, st);
+            on = hipEventCreate(&a.ev) == hipSuccess && hipEventCreate(&b.ev) == hipSuccess;
+            if (on) (void)hipEventRecord(a.ev, st);
         }
     }
     ~ProfScope() {
         if (on) {
-            (void)hipEventRecord(b, st);
-            h->prof.push_back({a, b, cls});
+            (void)hipEventRecord(b.ev, st);
+            h->prof.push_back({std::move(a), std::move(b), cls});
         }
     }
 };
@@ -229,15 +232,6 @@ struct ProfScope {
         ProfScope _ps(h, cls, st);     \
         MGEA_TRY(call);                \
     } while (0)
-
-void drop_graphs(mgea_decoder* h) {
-    for (auto& g : h->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    h->graphs.clear();
-    h->counters[4] = 0;
-}
 
 int64_t slab_need(const mgea_decoder_config& c, int M) {
     const int C = c.d_model, F = c.d_ff, V = c.vocab;
@@ -259,7 +253,7 @@ int ensure_ws(mgea_decoder* h, int64_t M) {
     DevGroup& g = h->dev_ws;
     g.release();
     h->ws_tokens = h->slab_cap = 0;
-    drop_graphs(h);  // captured pointers die with the old workspace
+    h->graphs.drop_all();  // captured pointers die with the old workspace
     const int C = h->cfg.d_model, F = h->cfg.d_ff;
     int64_t slab = slab_need(h->cfg, (int)M);
     const int64_t s64 = slab_need(h->cfg, 64);
@@ -364,18 +358,6 @@ int run_blocks(mgea_decoder* h, int B, int T, const int32_t* lens, bool use_cach
     return MGEA_OK;
 }
 
-// Everything one fused decode pass touches besides the weights.
-struct Bufs {
-    float *x, *qkv, *att, *hbuf, *stats, *pmax_val;
-    int32_t *pmax_idx, *page_table, *ctx_len, *cur_ids, *done, *row_step, *sampled, *ids_hist;
-    float* logits;
-};
-
-Bufs main_bufs(mgea_decoder* h) {
-    return Bufs{h->x, h->qkv, h->att, h->hbuf, h->stats, h->pmax_val, h->pmax_idx, h->page_table, h->ctx_len, h->cur_ids,
-                h->done, h->row_step, h->sampled, h->ids_hist, h->logits};
-}
-
 // Fused path for M = B*T <= MGEA_FUSED_MAX_ROWS rows in the KV-cache block mode: 5 launches per layer
 // (gemm_skinny.hip); x carries per-row LayerNorm partial statistics between kernels.
 bool fused_geometry(const mgea_decoder_config& c) {
@@ -419,8 +401,8 @@ int decode_gemm(mgea_decoder* h, int l, int g, SkinnyArgs a, bool gv, hipStream_
     return launch_decode_gemm(kEpi[g], p, a, st);
 }
 
-// qkv0_primed: u.qkv and layer 0's K | V page already hold this step's in-projection of layer 0 (the qkv0 table): that launch is skipped
-int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t* lens, bool use_cache_attn, hipStream_t st,
+// qkv0_primed: h->qkv and layer 0's K | V page already hold this step's in-projection of layer 0 (the qkv0 table): that launch is skipped
+int run_blocks_fused(mgea_decoder* h, int B, int T, const int32_t* lens, bool use_cache_attn, hipStream_t st,
                      bool kv_only_last = false, bool qkv0_primed = false) {
     const auto& c = h->cfg;
     const int C = c.d_model, F = c.d_ff, M = B * T;
@@ -429,34 +411,34 @@ int run_blocks_fused(mgea_decoder* h, const Bufs& u, int B, int T, const int32_t
     for (int l = 0; l < c.n_layer; ++l) {
         // ln1 + in_proj + KV append
         SkinnyArgs a{};
-        a.M = M; a.eps = c.ln_eps; a.A = u.x; a.lda = C; a.N = 3 * C; a.K = C;
-        a.stats_in = u.stats; a.n_part = n_part; a.part_cnt = part_cnt;
-        a.out = u.qkv; a.ldo = 3 * C;
-        a.pool = h->kv; a.layer = l; a.page_table = u.page_table; a.max_pages = h->max_pages; a.ctx_len = u.ctx_len;
+        a.M = M; a.eps = c.ln_eps; a.A = h->x; a.lda = C; a.N = 3 * C; a.K = C;
+        a.stats_in = h->stats; a.n_part = n_part; a.part_cnt = part_cnt;
+        a.out = h->qkv; a.ldo = 3 * C;
+        a.pool = h->kv; a.layer = l; a.page_table = h->page_table; a.max_pages = h->max_pages; a.ctx_len = h->ctx_len;
         a.lens = lens; a.T = T; a.C = C;
         if (l > 0 || !qkv0_primed) PROF(PC_GEMM, decode_gemm(h, l, 0, a, gv, st));
         if (kv_only_last && l + 1 == c.n_layer) break;       // (run_blocks: the logits are dropped, the last block's K | V are appended)
         if (use_cache_attn) {
-            PROF(PC_ATTN_PAGED, launch_attn_paged(u.qkv, h->kv, l, u.page_table, h->max_pages, u.ctx_len, lens, u.att, B, T, C, 1, st, &h->attn_split));
+            PROF(PC_ATTN_PAGED, launch_attn_paged(h->qkv, h->kv, l, h->page_table, h->max_pages, h->ctx_len, lens, h->att, B, T, C, 1, st, &h->attn_split));
         } else {
-            PROF(PC_ATTN_DENSE, launch_attn_dense(u.qkv, lens, nullptr, u.att, B, T, c.n_head, h->dh, 1, st));
+            PROF(PC_ATTN_DENSE, launch_attn_dense(h->qkv, lens, nullptr, h->att, B, T, c.n_head, h->dh, 1, st));
         }
         // out_proj + residual (+ stats for ln2)
         SkinnyArgs o{};
-        o.M = M; o.eps = c.ln_eps; o.A = u.att; o.lda = C; o.N = C; o.K = C;
-        o.out = u.x; o.ldo = C; o.stats_out = u.stats;
+        o.M = M; o.eps = c.ln_eps; o.A = h->att; o.lda = C; o.N = C; o.K = C;
+        o.out = h->x; o.ldo = C; o.stats_out = h->stats;
         PROF(PC_GEMM, decode_gemm(h, l, 1, o, gv, st));
         n_part = C / 16; part_cnt = 16;
         // ln2 + mlp.0 + GELU
         SkinnyArgs f{};
-        f.M = M; f.eps = c.ln_eps; f.A = u.x; f.lda = C; f.N = F; f.K = C;
-        f.stats_in = u.stats; f.n_part = n_part; f.part_cnt = part_cnt;
-        f.out = u.hbuf; f.ldo = F; f.act = ACT_GELU;
+        f.M = M; f.eps = c.ln_eps; f.A = h->x; f.lda = C; f.N = F; f.K = C;
+        f.stats_in = h->stats; f.n_part = n_part; f.part_cnt = part_cnt;
+        f.out = h->hbuf; f.ldo = F; f.act = ACT_GELU;
         PROF(PC_GEMM, decode_gemm(h, l, 2, f, gv, st));
         // mlp.2 + residual (+ stats for the next ln1)
         SkinnyArgs r{};
-        r.M = M; r.eps = c.ln_eps; r.A = u.hbuf; r.lda = F; r.N = C; r.K = F;
-        r.out = u.x; r.ldo = C; r.stats_out = u.stats;
+        r.M = M; r.eps = c.ln_eps; r.A = h->hbuf; r.lda = F; r.N = C; r.K = F;
+        r.out = h->x; r.ldo = C; r.stats_out = h->stats;
         PROF(PC_GEMM, decode_gemm(h, l, 3, r, gv, st));
     }
     return MGEA_OK;
@@ -481,70 +463,70 @@ struct StepCall {
 };
 
 // What the kernel that embeds the next step's token works on; qkv0: the table of the step's path, or NULL (TailArgs, common.h)
-TailArgs tail_args(const mgea_decoder* h, const Bufs& u, const StepState& s, const float* qkv0) {
+TailArgs tail_args(const mgea_decoder* h, const StepState& s, const float* qkv0) {
     const auto& c = h->cfg;
-    TailArgs t{s, h->w(T_TOK), h->w(T_POS), u.x, u.stats, c.d_model, c.vocab, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
+    TailArgs t{s, h->w(T_TOK), h->w(T_POS), h->x, h->stats, c.d_model, c.vocab, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
     if (qkv0) {
-        t.qkv0 = qkv0; t.qkv = u.qkv;
-        t.pool = h->kv; t.page_table = u.page_table; t.max_pages = h->max_pages;
+        t.qkv0 = qkv0; t.qkv = h->qkv;
+        t.pool = h->kv; t.page_table = h->page_table; t.max_pages = h->max_pages;
         if (!tune(TUNE_ATTN_ARITH_PAGES)) t.pool.arith_batch = 0;   // (as the attention: the switch sends every page id through the table)
     }
     return t;
 }
 
 // The tail of a step over the head's output.  GREEDY: the argmax of the head's n_partials partials per row (0: the ids are already in
-// u.sampled), the bookkeeping and, primed, the next step's embedding.  Otherwise the form's sampler over the logits row lg, with the
+// h->sampled), the bookkeeping and, primed, the next step's embedding.  Otherwise the form's sampler over the logits row lg, with the
 // bookkeeping and the next embedding as its fused tail when primed, followed by the advance kernel when not.
-int enqueue_tail(mgea_decoder* h, const Bufs& u, const StepCall& k, const float* lg, int n_partials, hipStream_t st) {
+int enqueue_tail(mgea_decoder* h, const StepCall& k, const float* lg, int n_partials, hipStream_t st) {
     const auto& c = h->cfg;
     const int B = k.B, C = c.d_model, V = c.vocab;
     // (with records the EOS id, like the other scalars, is read from them -- the captured graph's form)
-    const StepState s{u.cur_ids, u.ctx_len, u.done, u.row_step, h->n_done, u.ids_hist, h->ids_hist_stride, k.pv.eos_id, k.pd};
-    const TailArgs t = tail_args(h, u, s, k.primed ? k.qkv0 : nullptr);
+    const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, h->ids_hist, h->ids_hist_stride, k.pv.eos_id, k.pd};
+    const TailArgs t = tail_args(h, s, k.primed ? k.qkv0 : nullptr);
     if (k.form == StepForm::GREEDY) {
         MGEA_REQUIRE(!k.scored, MGEA_EINVAL, "internal: a scored step never takes the greedy form");
         if (k.primed)
-            PROF(PC_SAMPLE, launch_argmax_advance_embed(u.pmax_val, u.pmax_idx, n_partials, t, u.sampled, B, st));
+            PROF(PC_SAMPLE, launch_argmax_advance_embed(h->pmax_val, h->pmax_idx, n_partials, t, h->sampled, B, st));
         else if (n_partials > 0)
-            PROF(PC_SAMPLE, launch_argmax_advance(u.pmax_val, u.pmax_idx, n_partials, s, u.sampled, B, st));
+            PROF(PC_SAMPLE, launch_argmax_advance(h->pmax_val, h->pmax_idx, n_partials, s, h->sampled, B, st));
         else
-            PROF(PC_ROWOP, launch_advance(u.sampled, s, B, st, nullptr, V));
+            PROF(PC_ROWOP, launch_advance(h->sampled, s, B, st, nullptr, V));
         return MGEA_OK;
     }
     uint32_t* pres = form_has_presence(k.form) ? h->presence : nullptr;
     SampleCall sc{};
     sc.logits = lg; sc.B = B; sc.V = V;
-    sc.params_dev = k.pd; sc.params = k.pv; sc.row_step_dev = u.row_step;
-    sc.ids_out = u.sampled; sc.tail = k.primed ? &t : nullptr;
+    sc.params_dev = k.pd; sc.params = k.pv; sc.row_step_dev = h->row_step;
+    sc.ids_out = h->sampled; sc.tail = k.primed ? &t : nullptr;
     sc.presence = pres; sc.bias = form_has_bias(k.form) ? h->bias : nullptr;
     if (k.form == StepForm::GRAMMAR)
-        sc.grammar = GrammarArgs{h->gram_class, h->gram_next, h->gram_allow, h->gram_state, h->gram_state, u.done,
+        sc.grammar = GrammarArgs{h->gram_class, h->gram_next, h->gram_allow, h->gram_state, h->gram_state, h->done,
                                  h->gram_n_state, h->gram_n_class, grammar_words(h->gram_n_class), h->err_flag};
     const int hs = h->ids_hist_stride;
     if (k.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
         sc.score = ScoreArgs{h->forced, hs, k.primed ? h->lp_hist : h->lp_step, k.primed ? h->ch_hist : h->ch_step, hs, h->err_flag};
     PROF(PC_SAMPLE, launch_sample(sc, st));
     const ScoreFile sf{h->lp_step, h->ch_step, h->lp_hist, h->ch_hist, hs};
-    if (!k.primed) PROF(PC_ROWOP, launch_advance(u.sampled, s, B, st, pres, V, k.scored ? &sf : nullptr));
+    if (!k.primed) PROF(PC_ROWOP, launch_advance(h->sampled, s, B, st, pres, V, k.scored ? &sf : nullptr));
     return MGEA_OK;
 }
 
-// The fused step over the rows of `u`: [embed,] 6 x (qkv, attention, out-proj, fc1, fc2), head (+ per-tile argmax), tail
-int enqueue_step_fused(mgea_decoder* h, const Bufs& u, const StepCall& k, hipStream_t st) {
+// The fused step: [embed,] 6 x (qkv, attention, out-proj, fc1, fc2), head (+ per-tile argmax), tail
+int enqueue_step_fused(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     const auto& c = h->cfg;
     const int B = k.B, C = c.d_model, V = c.vocab;
     if (!k.primed)
-        PROF(PC_ROWOP, launch_embed_stats(u.cur_ids, nullptr, u.ctx_len, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, 1, C, V,
+        PROF(PC_ROWOP, launch_embed_stats(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->stats, B, 1, C, V,
                                           c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
     MGEA_REQUIRE(!k.qkv0 || k.primed, MGEA_EINVAL, "internal: the qkv0 table serves primed steps only");
-    MGEA_TRY(run_blocks_fused(h, u, B, 1, nullptr, true, st, false, k.qkv0 != nullptr));
+    MGEA_TRY(run_blocks_fused(h, B, 1, nullptr, true, st, false, k.qkv0 != nullptr));
     SkinnyArgs a{};
-    a.M = B; a.A = u.x; a.lda = C; a.N = V; a.K = C;
-    a.out = k.head_out(u.logits);
-    a.ldo = V; a.pmax_val = u.pmax_val; a.pmax_idx = u.pmax_idx;
+    a.M = B; a.A = h->x; a.lda = C; a.N = V; a.K = C;
+    a.out = k.head_out(h->logits);
+    a.ldo = V; a.pmax_val = h->pmax_val; a.pmax_idx = h->pmax_idx;
     DecodeGemmPlan head;   // its partial count is what the greedy tail merges
     PROF(PC_GEMM, decode_gemm(h, 0, 4, a, gemv_ok(h, B, 1, nullptr, true) && gemv_shape_ok(B, V, C), st, &head));
-    return enqueue_tail(h, u, k, a.out, head.n_partials, st);
+    return enqueue_tail(h, k, a.out, head.n_partials, st);
 }
 
 // one decode step on cur_ids: the fused path where the geometry has one, else the slab kernels (never primed: they embed cur_ids)
@@ -552,7 +534,7 @@ int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     const auto& c = h->cfg;
     const int B = k.B, C = c.d_model, V = c.vocab;
     const bool post = c.block_mode == MGEA_BLOCK_POSTLN_RELU;
-    if (fused_ok(h, B)) return enqueue_step_fused(h, main_bufs(h), k, st);
+    if (fused_ok(h, B)) return enqueue_step_fused(h, k, st);
     PROF(PC_ROWOP, launch_embed_ln(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                              post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, 1, C,
                              V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
@@ -562,7 +544,7 @@ int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     float* lg = k.head_out(h->logits);
     PROF(PC_SAMPLE, launch_logits_argmax(h->slabs, S, slab_floats(B, V), (int)slab_ld(V), h->head_b(), lg, B, V,
                                   k.form == StepForm::GREEDY ? h->sampled : nullptr, st));
-    return enqueue_tail(h, main_bufs(h), k, lg, 0, st);
+    return enqueue_tail(h, k, lg, 0, st);
 }
 
 // Which qkv0 table a primed step of B rows reads: 0 the MFMA kernels', 1 the <= 2-row dot-product kernels', -1 none (the layer-0
@@ -633,57 +615,45 @@ int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStre
 int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
     if (!fused_ok(h, B)) return MGEA_OK;
     const auto& c = h->cfg;
-    const Bufs u = main_bufs(h);
     if (const float* tab = qkv0_table(h, B))
-        return launch_embed_qkv0(u.cur_ids, u.ctx_len, tail_args(h, u, StepState{}, tab), B, h->err_flag, st);
-    return launch_embed_stats(u.cur_ids, nullptr, u.ctx_len, h->w(T_TOK), h->w(T_POS), u.x, u.stats, B, 1, c.d_model, c.vocab,
+        return launch_embed_qkv0(h->cur_ids, h->ctx_len, tail_args(h, StepState{}, tab), B, h->err_flag, st);
+    return launch_embed_stats(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->stats, B, 1, c.d_model, c.vocab,
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
 // The captured decode step for (B, form, scored, steps): from the cache, or captured + instantiated now (least recently used
-// entry evicted beyond MAX_GRAPHS).
-constexpr size_t MAX_GRAPHS = 36;   // two per (batch, form, scored): the single step and the 8-step graph -- (5 forms + 4 scored) x 2 = 18 for one batch size, two batch sizes whole
+// entry evicted beyond StepGraphs::CAP, hipres.h).
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
 int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps) {
-    for (auto& g : h->graphs)
-        if (g.batch == B && g.form == form && g.scored == scored && g.steps == steps) {
-            g.last_use = ++h->use_clock;
-            if (steps == 1) h->counters[0] = g.nodes;
-            *out = g.exec;
-            return MGEA_OK;
-        }
-    if (h->graphs.size() >= MAX_GRAPHS) {
-        size_t lru = 0;
-        for (size_t i = 1; i < h->graphs.size(); ++i)
-            if (h->graphs[i].last_use < h->graphs[lru].last_use) lru = i;
-        MGEA_CHECK_HIP(hipStreamSynchronize(st));   // an evicted exec may still be replaying
-        (void)hipGraphExecDestroy(h->graphs[lru].exec);
-        (void)hipGraphDestroy(h->graphs[lru].graph);
-        h->graphs.erase(h->graphs.begin() + (long)lru);
+    const StepGraphs::Key key{B, form, scored, steps};
+    if (const StepGraphs::Entry* e = h->graphs.find(key)) {
+        if (steps == 1) h->n.graph_nodes = e->nodes;
+        *out = e->exec;
+        return MGEA_OK;
     }
+    // the insert below then evicts, and an evicted exec may still be replaying (nothing is launched in between: a capture enqueues no work)
+    if (h->graphs.full()) MGEA_CHECK_HIP(hipStreamSynchronize(st));
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
     for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
-        if (g) (void)hipGraphDestroy(g);
+        graph_destroy(g, nullptr);
         return rc;
     }
     MGEA_CHECK_HIP(e);
     hipGraphExec_t ex = nullptr;
     const hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
     if (ei != hipSuccess) {
-        (void)hipGraphDestroy(g);
+        graph_destroy(g, nullptr);
         MGEA_CHECK_HIP(ei);
     }
     size_t nn = 0;
     (void)hipGraphGetNodes(g, nullptr, &nn);
-    h->graphs.push_back({B, form, scored, steps, g, ex, (int64_t)nn, ++h->use_clock});
-    if (steps == 1) h->counters[0] = (int64_t)nn;
-    h->counters[2] += 1;   // lifetime captures + instantiations
-    h->counters[4] = (int64_t)h->graphs.size();
+    h->graphs.insert(key, g, ex, (int64_t)nn);
+    if (steps == 1) h->n.graph_nodes = (int64_t)nn;
     *out = ex;
     return MGEA_OK;
 }
@@ -818,7 +788,7 @@ int run_prefill16(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int 
     }
     if (logits_out)
         PROF(PC_GEMM, launch_gemm_bf16(xc, C, h->p16_w(4 * c.n_layer), C, h->head_b(), nullptr, logits_out, V, M, V, C, 6, st, nullptr, nullptr, 1));
-    h->counters[5] += 1;
+    h->n.prefill16_forwards += 1;
     return MGEA_OK;
 }
 
@@ -874,7 +844,7 @@ int do_forward(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int B, 
     } else if (fused_ok(h, (int)M)) {
         MGEA_TRY(launch_embed_stats(ids, lens, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->stats, B, T, C, V,
                                     c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
-        MGEA_TRY(run_blocks_fused(h, main_bufs(h), B, T, lens, cache_attn, st, kv_only_last));
+        MGEA_TRY(run_blocks_fused(h, B, T, lens, cache_attn, st, kv_only_last));
     } else {
         MGEA_TRY(launch_embed_ln(ids, lens, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                                  post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, T, C,
@@ -1035,8 +1005,8 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
     if (g.alloc(&h->page_table, nb * h->max_pages) || g.alloc(&h->ctx_len, nb) || g.alloc(&h->cur_ids, nb) || g.alloc(&h->done, nb) ||
         g.alloc(&h->row_step, nb) || g.alloc(&h->sampled, nb) || g.alloc(&h->n_done, 16) ||
         g.alloc(&h->samp_dev, cfg->max_batch * sizeof(SamplerParams)) ||
-        hipHostMalloc((void**)&h->samp_stage, cfg->max_batch * sizeof(SamplerParams), 0) != hipSuccess ||
-        hipEventCreateWithFlags(&h->stage_free, hipEventDisableTiming) != hipSuccess ||
+        h->pinned.alloc(&h->samp_stage, cfg->max_batch * sizeof(SamplerParams)) ||
+        hipEventCreateWithFlags(&h->stage_free.ev, hipEventDisableTiming) != hipSuccess ||
         g.alloc(&h->err_flag, 16) || g.alloc(&h->presence, (size_t)cfg->max_batch * presence_words(cfg->vocab) * sizeof(uint32_t)) ||
         g.alloc(&h->ids_hist, nb * h->ids_hist_stride))
         return fail(MGEA_ENOMEM, "state allocation failed");
@@ -1053,7 +1023,7 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         g.alloc(&h->gram_state, nb) || g.alloc(&h->gram_class, (size_t)cfg->vocab * sizeof(int32_t)) ||
         g.alloc(&h->gram_next, (size_t)MGEA_GRAMMAR_MAX_CELLS * sizeof(int32_t)) ||
         g.alloc(&h->gram_allow, ((size_t)MGEA_GRAMMAR_MAX_CELLS / 32 + MGEA_GRAMMAR_MAX_STATES) * sizeof(uint32_t)) ||
-        hipHostMalloc((void**)&h->gram_stage, nb, 0) != hipSuccess)
+        h->pinned.alloc(&h->gram_stage, nb))
         return fail(MGEA_ENOMEM, "state allocation failed");
     if (hipMemset(h->forced, 0xff, nhist * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess ||
@@ -1085,11 +1055,7 @@ int mgea_decoder_refresh_weights(mgea_decoder* h, void* stream) {
 int mgea_decoder_destroy(mgea_decoder* h) {
     if (!h) return MGEA_OK;
     (void)hipDeviceSynchronize();
-    drop_graphs(h);
-    if (h->samp_stage) (void)hipHostFree(h->samp_stage);
-    if (h->gram_stage) (void)hipHostFree(h->gram_stage);
-    if (h->stage_free) (void)hipEventDestroy(h->stage_free);
-    delete h;   // its DevGroups free the device buffers
+    delete h;   // every resource goes with its owner (devmem.h, hipres.h)
     return MGEA_OK;
 }
 
@@ -1164,7 +1130,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
                      c.max_ctx);
         reserve = reserve < c.max_ctx ? reserve : c.max_ctx;
         // the records go to the pinned staging buffer, free once the previous call's copy out of it has run
-        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free));
+        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free.ev));
         rr = build_row_records(rows, lrows, B, n_steps, h->samp_stage);
         rr.may_stop_early = rr.may_stop_early || reserve < Tp + n_steps;
     } else {
@@ -1178,9 +1144,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     const StepForm form = grammar ? StepForm::GRAMMAR : scored && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
     h->last_penalized = false;
     h->gram_steps = 0;
-    h->counters[3] = 0;
-    h->counters[6] = 0;
-    h->counters[7] = 0;
+    h->n.scored_steps = h->n.penalized_steps = h->n.biased_steps = 0;
     MGEA_TRY(do_reset(h, B, reserve, st));
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
     if (form_has_presence(form)) {   // every row's set starts as its real prompt tokens
@@ -1201,7 +1165,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             for (int b = 0; b < B; ++b) h->gram_stage[b] = start_states[b];
             MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
         }
-        MGEA_CHECK_HIP(hipEventRecord(h->stage_free, st));
+        MGEA_CHECK_HIP(hipEventRecord(h->stage_free.ev, st));
         if (reserve < Tp + n_steps) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
     } else {
         MGEA_TRY(launch_fill_sampler_params(h->samp_dev, sampler_params(*s, penalty), B, st));
@@ -1249,10 +1213,10 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     }
     if (reserve < Tp + n_steps) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
     h->host_max_len += launched;
-    h->counters[1] = launched;
-    h->counters[6] = rr.any_penalty ? launched : 0;
-    h->counters[7] = biased ? launched : 0;
-    h->counters[3] = scored ? launched : 0;
+    h->n.graph_replays = launched;
+    h->n.penalized_steps = rr.any_penalty ? launched : 0;
+    h->n.biased_steps = biased ? launched : 0;
+    h->n.scored_steps = scored ? launched : 0;
     h->gram_steps = grammar ? launched : 0;
     if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
         float* outs[2] = {score->logprobs_out, score->choice_out};
@@ -1334,18 +1298,9 @@ int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, cons
     MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_set_grammar: NULL handle");
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t st = (hipStream_t)stream;
-    auto drop_grammar_graphs = [&]() {   // their kernel arguments carry the table's shape
-        for (size_t i = h->graphs.size(); i-- > 0;)
-            if (h->graphs[i].form == StepForm::GRAMMAR) {
-                (void)hipGraphExecDestroy(h->graphs[i].exec);
-                (void)hipGraphDestroy(h->graphs[i].graph);
-                h->graphs.erase(h->graphs.begin() + (long)i);
-            }
-        h->counters[4] = (int64_t)h->graphs.size();
-    };
     if (n_state == 0) {   // clear
         MGEA_CHECK_HIP(hipStreamSynchronize(st));
-        drop_grammar_graphs();
+        h->graphs.drop_form(StepForm::GRAMMAR);
         h->gram_n_state = h->gram_n_class = 0;
         return MGEA_OK;
     }
@@ -1374,7 +1329,7 @@ int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, cons
     }
     if (n_state != h->gram_n_state || n_class != h->gram_n_class) {
         MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying
-        drop_grammar_graphs();
+        h->graphs.drop_form(StepForm::GRAMMAR);   // their kernel arguments carry the table's shape
     }
     MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_class, class_of_host, (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, st));
     MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_next, next_host, (size_t)n_state * n_class * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -1449,12 +1404,10 @@ int mgea_decoder_profile_read(mgea_decoder* h, double* ms_by_class, int64_t* lau
     for (int i = 0; i < n_classes; ++i) { ms_by_class[i] = 0.0; launches_by_class[i] = 0; }
     for (auto& r : h->prof) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, r.a.ev, r.b.ev) == hipSuccess) {
             ms_by_class[r.cls] += ms;
             launches_by_class[r.cls] += 1;
         }
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
     }
     h->prof.clear();
     return MGEA_OK;
@@ -1484,7 +1437,16 @@ int mgea_decoder_qkv0_table_bytes(mgea_decoder* h, int64_t* bytes_out) {
 
 int mgea_decoder_stats(mgea_decoder* h, int64_t* out) {
     MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_stats: NULL argument");
-    for (int i = 0; i < 8; ++i) out[i] = h->counters[i];
+    std::lock_guard<std::mutex> lk(h->mu);
+    // the ABI's order (include/mgea.h), written down here and nowhere else
+    out[0] = h->n.graph_nodes;
+    out[1] = h->n.graph_replays;
+    out[2] = h->graphs.inserted();        // graph_instantiates: lifetime captures + instantiations
+    out[3] = h->n.scored_steps;
+    out[4] = (int64_t)h->graphs.size();   // graphs_cached
+    out[5] = h->n.prefill16_forwards;
+    out[6] = h->n.penalized_steps;
+    out[7] = h->n.biased_steps;
     return MGEA_OK;
 }
 

@@ -1,5 +1,6 @@
-// DevGroup (csrc/devmem.h) on the CPU: dev_malloc / dev_free over malloc / free with a "fail the k-th call" counter and a count of
-// live allocations.  Built with -fsanitize=address,undefined and run by tests/test_devmem_host.py; exit status 0 = every check held.
+// DevGroup and PinnedGroup (csrc/devmem.h) on the CPU: each group's malloc / free pair over malloc / free with a "fail the k-th call"
+// counter and a count of live allocations of its own (a buffer freed through the other group's seam shows in both counts).  Built with
+// -fsanitize=address,undefined and run by tests/test_devmem_host.py; exit status 0 = every check held.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -7,24 +8,29 @@
 #include "../../music-generation-emotion-adaptive_amd/csrc/devmem.h"
 
 namespace {
-int g_calls = 0, g_fail_at = -1, g_live = 0, g_failures = 0;
-}
+int g_failures = 0;
+struct Fake {
+    int calls = 0, fail_at = -1, live = 0;
+    bool get(void** p, size_t bytes) {
+        if (calls++ == fail_at) return false;
+        *p = malloc(bytes ? bytes : 1);
+        if (!*p) return false;
+        ++live;
+        return true;
+    }
+    void put(void* p) {
+        --live;
+        free(p);
+    }
+} g_dev, g_pinned;
+}  // namespace
 
 namespace mgea {
-bool dev_malloc(void** p, size_t bytes) {
-    if (g_calls++ == g_fail_at) return false;
-    *p = malloc(bytes ? bytes : 1);
-    if (!*p) return false;
-    ++g_live;
-    return true;
-}
-void dev_free(void* p) {
-    --g_live;
-    free(p);
-}
+bool dev_malloc(void** p, size_t bytes) { return g_dev.get(p, bytes); }
+void dev_free(void* p) { g_dev.put(p); }
+bool pinned_malloc(void** p, size_t bytes) { return g_pinned.get(p, bytes); }
+void pinned_free(void* p) { g_pinned.put(p); }
 }  // namespace mgea
-
-using mgea::DevGroup;
 
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -35,8 +41,9 @@ using mgea::DevGroup;
     } while (0)
 
 // a handle in the engines' style: raw fields of several types, one group
+template <class Group>
 struct Handle {
-    DevGroup dev;
+    Group dev;
     float* a = nullptr;
     void* b = nullptr;
     int32_t* c = nullptr;
@@ -53,12 +60,16 @@ struct Handle {
     bool all_set() const { return a && b && c && in.d && e; }
 };
 
-void arm(int fail_at) {
-    g_calls = 0;
-    g_fail_at = fail_at;
-}
-
-int main() {
+// every check on one group type, whose seam is the fake `f`
+template <class Group>
+void group_checks(Fake& f) {
+    using Handle = ::Handle<Group>;
+    int& g_calls = f.calls;
+    int& g_live = f.live;
+    auto arm = [&f](int fail_at) {
+        f.calls = 0;
+        f.fail_at = fail_at;
+    };
     // every k-th allocation of a group of n failing: after the caller's release() nothing is live and every field reads null
     for (int k = 0; k < Handle::N; ++k) {
         Handle h;
@@ -73,7 +84,7 @@ int main() {
     // a failed alloc() answers MGEA_ENOMEM with the field null and the group as it was
     {
         float *x = nullptr, *y = reinterpret_cast<float*>(&g_live);
-        DevGroup g;
+        Group g;
         arm(1);
         CHECK(g.alloc(&x, 32) == MGEA_OK && x);
         CHECK(g.alloc(&y, 32) == MGEA_ENOMEM && !y);
@@ -105,7 +116,7 @@ int main() {
     // a zero-byte allocation is a success (hipMalloc answers NULL for it) and costs nothing to release
     {
         float* z = nullptr;
-        DevGroup g;   // (after the field: the group writes to it when it goes)
+        Group g;   // (after the field: the group writes to it when it goes)
         arm(-1);
         CHECK(g.alloc(&z, 0) == MGEA_OK);
     }
@@ -114,10 +125,10 @@ int main() {
     {
         float *x = nullptr, *y = nullptr;
         arm(-1);
-        DevGroup a;
+        Group a;
         CHECK(a.alloc(&x, 8) == MGEA_OK);
         {
-            DevGroup b(std::move(a));
+            Group b(std::move(a));
             a.release();
             CHECK(x && g_live == 1);
             CHECK(a.alloc(&y, 8) == MGEA_OK && g_live == 2);
@@ -126,6 +137,13 @@ int main() {
         a.release();
         CHECK(!y && g_live == 0);
     }
+}
+
+int main() {
+    group_checks<mgea::DevGroup>(g_dev);
+    CHECK(g_pinned.calls == 0);   // (each group reaches its own pair)
+    group_checks<mgea::PinnedGroup>(g_pinned);
+    CHECK(g_dev.live == 0 && g_pinned.live == 0);
     if (g_failures) return 1;
     puts("devmem ok");
     return 0;

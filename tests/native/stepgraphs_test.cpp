@@ -1,0 +1,187 @@
+// StepGraphs and Event (csrc/hipres.h) on the CPU: graph_destroy / event_destroy over free, with counts of live pairs and live events
+// and a log of the pairs destroyed.  A fake handle is a one-byte allocation, so a pair destroyed twice or never is the sanitizer's
+// finding too.  Built with -fsanitize=address,undefined and run by tests/test_devmem_host.py; exit status 0 = every check held.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <utility>
+#include <vector>
+
+#include "../../music-generation-emotion-adaptive_amd/csrc/hipres.h"
+
+namespace {
+int g_live_pairs = 0, g_live_events = 0, g_failures = 0;
+std::vector<hipGraph_t> g_destroyed;   // in the order of the calls
+}  // namespace
+
+namespace mgea {
+void graph_destroy(hipGraph_t graph, hipGraphExec_t exec) {
+    --g_live_pairs;
+    g_destroyed.push_back(graph);
+    free(graph);
+    free(exec);
+}
+void event_destroy(hipEvent_t ev) {
+    --g_live_events;
+    free(ev);
+}
+}  // namespace mgea
+
+using mgea::Event;
+using mgea::StepForm;
+using mgea::StepGraphs;
+
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
+            ++g_failures;                                               \
+        }                                                               \
+    } while (0)
+
+// the cache never looks inside a form: two values of the enumeration common.h defines
+const StepForm FORM_A = static_cast<StepForm>(1), FORM_B = static_cast<StepForm>(4);
+
+struct Pair { hipGraph_t graph; hipGraphExec_t exec; };
+Pair capture() {
+    ++g_live_pairs;
+    return {static_cast<hipGraph_t>(malloc(1)), static_cast<hipGraphExec_t>(malloc(1))};
+}
+hipEvent_t create_event() {
+    ++g_live_events;
+    return static_cast<hipEvent_t>(malloc(1));
+}
+// inserts a new pair under `k` and returns its graph, the name the destroy log knows it by
+hipGraph_t put(StepGraphs& c, const StepGraphs::Key& k, int64_t nodes = 31) {
+    const Pair p = capture();
+    c.insert(k, p.graph, p.exec, nodes);
+    return p.graph;
+}
+StepGraphs::Key key(int batch, StepForm form = FORM_A, bool scored = false, int steps = 1) { return {batch, form, scored, steps}; }
+
+int main() {
+    const size_t CAP = StepGraphs::CAP;
+    CHECK(CAP == 36);
+    // a hit returns the stored pair and makes it the most recently used; every part of the key tells entries apart
+    {
+        StepGraphs c;
+        CHECK(c.size() == 0 && c.inserted() == 0 && !c.full() && !c.find(key(1)));
+        const Pair p = capture();
+        c.insert(key(1), p.graph, p.exec, 62);
+        CHECK(c.size() == 1 && c.inserted() == 1);
+        const StepGraphs::Entry* e = c.find(key(1));
+        CHECK(e && e->graph == p.graph && e->exec == p.exec && e->nodes == 62);
+        const uint64_t stamp = e ? e->last_use : 0;
+        e = c.find(key(1));
+        CHECK(e && e->last_use > stamp && e->exec == p.exec);
+        CHECK(!c.find(key(2)) && !c.find(key(1, FORM_B)) && !c.find(key(1, FORM_A, true)) && !c.find(key(1, FORM_A, false, 8)));
+        CHECK(c.size() == 1 && c.inserted() == 1 && g_live_pairs == 1);   // (a lookup inserts and destroys nothing)
+        const hipGraph_t g8 = put(c, key(1, FORM_A, false, 8), 248);
+        e = c.find(key(1, FORM_A, false, 8));
+        CHECK(e && e->graph == g8 && e->nodes == 248 && c.size() == 2 && c.inserted() == 2);
+    }   // the destructor destroys what is left
+    CHECK(g_live_pairs == 0 && g_destroyed.size() == 2);
+
+    // the 37th distinct key evicts exactly the least recently used entry; one touched after its insertion outlives an older,
+    // untouched one
+    {
+        StepGraphs c;
+        std::vector<hipGraph_t> g;
+        g_destroyed.clear();
+        for (int b = 0; b < (int)CAP; ++b) {
+            CHECK(!c.full());
+            g.push_back(put(c, key(b)));
+            CHECK(c.size() == (size_t)b + 1 && c.inserted() == b + 1 && g_live_pairs == b + 1);
+        }
+        CHECK(c.full() && g_destroyed.empty());
+        CHECK(c.find(key(0)));   // the oldest entry becomes the newest
+        put(c, key(100));
+        CHECK(g_destroyed.size() == 1 && g_destroyed[0] == g[1]);   // key 1: the oldest stamp once key 0 was touched
+        CHECK(c.size() == CAP && c.inserted() == (int64_t)CAP + 1 && g_live_pairs == (int)CAP);
+        CHECK(c.find(key(0)) && !c.find(key(1)) && c.find(key(2)) && c.find(key(100)));
+        // those lookups touched 0, 2 and 100: key 3 holds the oldest stamp now, then 4
+        put(c, key(101));
+        put(c, key(102));
+        CHECK(g_destroyed.size() == 3 && g_destroyed[1] == g[3] && g_destroyed[2] == g[4]);
+        CHECK(c.size() == CAP && c.inserted() == (int64_t)CAP + 3 && g_live_pairs == (int)CAP);
+        // an evicted key comes back as a new entry
+        const hipGraph_t again = put(c, key(1));
+        CHECK(g_destroyed.size() == 4 && g_destroyed[3] == g[5]);
+        const StepGraphs::Entry* e = c.find(key(1));
+        CHECK(e && e->graph == again && c.inserted() == (int64_t)CAP + 4);
+        c.drop_all();
+        CHECK(c.size() == 0 && g_live_pairs == 0 && !c.full() && !c.find(key(0)));
+        CHECK(c.inserted() == (int64_t)CAP + 4);   // a lifetime count
+        c.drop_all();                              // idempotent
+        CHECK(g_live_pairs == 0);
+        put(c, key(0));                            // and the cache works on
+        CHECK(c.size() == 1 && c.inserted() == (int64_t)CAP + 5 && g_live_pairs == 1);
+    }
+    CHECK(g_live_pairs == 0);
+
+    // dropping a form removes that form's entries only, and leaves the others' stamps alone: the evictions that follow take them
+    // in the order they were inserted in
+    {
+        StepGraphs c;
+        std::vector<hipGraph_t> ga, gb;
+        for (int b = 0; b < 12; ++b) {   // A0 B0 B0' A1 B1 B1' ...
+            ga.push_back(put(c, key(b, FORM_A)));
+            gb.push_back(put(c, key(b, FORM_B)));
+            gb.push_back(put(c, key(b, FORM_B, true, 8)));
+        }
+        CHECK(c.size() == CAP && c.full());
+        g_destroyed.clear();
+        c.drop_form(FORM_B);
+        CHECK(c.size() == 12 && g_destroyed.size() == 24 && g_live_pairs == 12 && c.inserted() == 36);
+        for (hipGraph_t d : g_destroyed) {
+            bool is_b = false;
+            for (hipGraph_t x : gb) is_b = is_b || x == d;
+            CHECK(is_b);
+        }
+        c.drop_form(FORM_B);   // none left: nothing happens
+        CHECK(c.size() == 12 && g_destroyed.size() == 24);
+        g_destroyed.clear();
+        for (int b = 0; b < 24; ++b) put(c, key(200 + b));   // refill: no eviction yet
+        CHECK(c.size() == CAP && g_destroyed.empty());
+        for (int b = 0; b < 12; ++b) put(c, key(300 + b));
+        CHECK(g_destroyed.size() == 12);
+        for (size_t i = 0; i < g_destroyed.size() && i < ga.size(); ++i) CHECK(g_destroyed[i] == ga[i]);
+        CHECK(c.size() == CAP && c.inserted() == 72 && g_live_pairs == (int)CAP);
+    }
+    CHECK(g_live_pairs == 0);
+
+    // Event: null until created, destroyed with its owner, moved with a record; half a pair goes with its scope
+    {
+        Event none;
+        CHECK(!none.ev);
+    }
+    CHECK(g_live_events == 0);
+    {
+        struct Rec { Event a, b; int cls; };
+        std::vector<Rec> recs;
+        for (int i = 0; i < 5; ++i) {   // (the vector regrows: records move)
+            Event a, b;
+            a.ev = create_event();
+            b.ev = create_event();
+            recs.push_back({std::move(a), std::move(b), i});
+            CHECK(!a.ev && !b.ev);
+        }
+        CHECK(g_live_events == 10 && recs[4].cls == 4 && recs[0].a.ev && recs[0].b.ev);
+        {
+            Event a, b;
+            a.ev = create_event();   // the second create failed: the scope ends without a record
+            CHECK(g_live_events == 11);
+        }
+        CHECK(g_live_events == 10);
+        recs.clear();   // read: the records go
+        CHECK(g_live_events == 0);
+        Event a;
+        a.ev = create_event();
+        recs.push_back({std::move(a), Event(), 0});
+    }   // unread records go with their owner
+    CHECK(g_live_events == 0);
+
+    if (g_failures) return 1;
+    puts("stepgraphs ok");
+    return 0;
+}

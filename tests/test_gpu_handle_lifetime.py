@@ -1,6 +1,7 @@
-"""Lifetimes of the native handles' device buffers: handles that are created and destroyed in a row, the decoder's workspace and
-its fp16-prefill buffers regrowing under a live handle, and device memory coming back at destroy.  The failure paths of the
-allocations are covered on the CPU (test_devmem_host.py); nothing here provokes one."""
+"""Lifetimes of the native handles' resources: handles that are created and destroyed in a row, the decoder's workspace and
+its fp16-prefill buffers regrowing under a live handle, device memory coming back at destroy, the step-graph cache filled past its
+capacity, and an engine closed with unread profile records.  The failure paths of the allocations and the cache's rules one by one
+are covered on the CPU (test_devmem_host.py); nothing here provokes a failure."""
 import pytest
 import torch
 
@@ -120,3 +121,62 @@ def test_destroy_returns_device_memory():
     free1, _ = torch.cuda.mem_get_info()
     print(f"free device memory before {free0} after {free1}: dropped by {free0 - free1} bytes (bound {pool})")
     assert free0 - free1 <= pool
+
+
+def tiny_engine():
+    """d_model 256: the smallest geometry that takes the fused, graph-replayed path"""
+    from mgea.decoder import DecoderEngine
+    return DecoderEngine(synth.decoder_state_dict(78, 128, 64, 256, 1, d_ff=512), n_head=4, max_batch=10, max_ctx=64, device=DEV)
+
+
+def test_step_graph_cache_evicts_the_least_recently_used(tune):
+    """20 configurations x (1-step, 8-step graph) = 40 keys against the cache's 36: the first two configurations' graphs are evicted,
+    a configuration that comes back is captured again at the cost of the oldest one left, and the ids never change."""
+    tune("decoder_graph_steps", 8)
+    eng = tiny_engine()
+    configs = [(B, top_k) for B in range(1, 11) for top_k in (1, 50)]   # greedy, then sampled: two step forms per batch size
+
+    def run(i):
+        B, top_k = configs[i]
+        prompts = [[1 + b, 5 + 2 * b, 14 + 3 * b] for b in range(B)]
+        return eng.generate(prompts, 8, temperature=1.0, top_k=top_k, seed=79).cpu().tolist()
+
+    def counts():
+        st = eng.stats()
+        return st["graph_instantiates"], st["graphs_cached"]
+
+    first = []
+    for i in range(20):
+        first.append(run(i))
+        inst, cached = counts()
+        assert inst == 2 * (i + 1) and cached == min(2 * (i + 1), 36), f"after configuration {i + 1}: {inst} instantiated, {cached} cached"
+    assert counts() == (40, 36)
+    assert run(19) == first[19] and counts() == (40, 36)   # the last one: cached
+    assert run(0) == first[0] and counts() == (42, 36)     # the first one was evicted: captured again, in the place of the third's graphs
+    assert run(3) == first[3] and counts() == (42, 36)     # the fourth: never touched by an eviction
+    assert run(2) == first[2] and counts() == (44, 36)     # the third: evicted a moment ago
+    eng.close()
+
+
+def test_unread_profile_records_go_with_the_engine():
+    prompts = [[1, 5, 14], [2, 9, 4]]
+
+    def ids(eng):
+        return eng.generate(prompts, 4, temperature=1.0, top_k=1).cpu().tolist()
+    plain = tiny_engine()
+    want = ids(plain)
+    plain.close()
+    eng = tiny_engine()
+    eng.profile(1)           # every step eagerly, an event pair around each launch
+    assert ids(eng) == want
+    eng.close()              # ... and nobody reads them
+    eng = tiny_engine()
+    assert ids(eng) == want
+    eng.profile(1)
+    assert ids(eng) == want
+    eng.profile(0)
+    rec = eng.profile_read()
+    assert sum(r["launches"] for r in rec.values()) > 0 and all(r["ms"] >= 0.0 for r in rec.values())
+    assert sum(r["launches"] for r in eng.profile_read().values()) == 0   # one read takes every record
+    assert ids(eng) == want
+    eng.close()
