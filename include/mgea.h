@@ -293,7 +293,48 @@ int mgea_decoder_grammar_info(mgea_decoder* h, int64_t* out /* [4] */);
  * generate applied no penalty (a biased generation keeps the bitmaps too). */
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream);
 
-/* Current cached length of each row -> lens_out_dev [B] (device int32). */
+/* The KV window: a generation may run longer than max_ctx (build-defined; the reference's cache simply grows, api_cache.py:159-184).
+ * Two of the reference's quirks make it clean: a decode step carries no position information (it adds pos_emb[0]) and no mask, and
+ * attention over a set of cached keys does not depend on their order.
+ *
+ * With a window set, every row of every generation keeps P = sink_pages + ring_pages pages of MGEA_KV_PAGE_TOKENS (64) tokens.  Logical
+ * pages 0 .. S-1 are the SINK and are never evicted -- they hold the prompt, the conditioning tokens; pages S .. P-1 are a RING.  A
+ * row's ctx_len is then the number of tokens CACHED, no longer the tokens so far; everything else a step records still counts every
+ * token: row_step, budgets, min_new_tokens, the Philox counter, the id / log-probability histories and the presence bitmaps (a
+ * repetition penalty keeps whole-history semantics).
+ *
+ * Row b has Lp real prompt tokens; step i (0-based) caches the token it feeds at absolute position Lp + i (step 0 feeds the last
+ * prompt token again, as always).
+ *   Eviction rule: at the start of a step, a row that is not finished and whose ctx_len == 64 P - 1 evicts its oldest ring page
+ *   whole: page_table[b][S .. P-1] rotates left by one (the freed physical page becomes logical page P-1), ctx_len drops by 64 and
+ *   the row's eviction counter goes up by one.
+ * In closed form, with i0 = 64 P - 1 - Lp: the evictions before step i attends are e(i) = 0 for i < i0 and 1 + (i - i0) div 64
+ * otherwise, and step i attends the absolute positions {0 .. 64 S - 1} u {64 (S + e) .. Lp + i}: Lp + i + 1 - 64 e keys, between
+ * 64 P - 64 and 64 P - 1 of them once eviction has begun.  Finished rows are left alone: one that finishes at ctx_len = 64 P - 1 reads
+ * exactly its P full pages on the later steps of its batch.  (Why 64 P - 1: with the qkv0 table the previous step's tail has already
+ * written layer 0's K | V of the fed token at position ctx_len; the rule keeps that write in bounds and alive across the rotation.)
+ * The sampled ids of a windowed row depend on (S, R) as well as on what an unwindowed row's depend on.
+ *
+ * Requirements (MGEA_EINVAL naming the offending value): sink_pages >= 1; ring_pages >= 2 (one ring page would be evicted with the
+ * current token's layer-0 K | V in it) and <= 256; sink_pages + ring_pages <= max_ctx / 64; 1 <= max_steps <= MGEA_WINDOW_MAX_STEPS;
+ * the KV-cache block mode and MGEA_POS_REFERENCE (an absolute position would be the cached length).  f32 and fp16 engines alike.
+ * A windowed generation needs prompt width Tp + 1 <= 64 S (the prompt and its duplicate stay in the sink) and n_steps <= max_steps
+ * (MGEA_ECAPACITY otherwise) -- whatever max_ctx is: no budget is clamped and no row is stopped at the end of its pages.  Its
+ * histories are a second set with stride max_steps, allocated HERE with the eviction counters (max_batch * max_steps * 16 bytes);
+ * mgea_decoder_create allocates nothing for a window.  "Windowed" is part of the step-graph key: every windowed step is the
+ * unwindowed launch sequence behind ONE more launch, the eviction, and every page id comes from the page table.  Changing or
+ * clearing the window synchronises `stream` and drops the windowed graphs, nothing else.  sink_pages == 0 clears the window: the
+ * engine is then exactly the engine without one.
+ * After a windowed generation mgea_decoder_step and an extending mgea_decoder_forward are refused (MGEA_EINVAL) until the next
+ * mgea_decoder_reset or generate: the host's length tracking no longer holds. */
+#define MGEA_WINDOW_MAX_STEPS (1 << 24)
+int mgea_decoder_set_window(mgea_decoder* h, int32_t sink_pages, int32_t ring_pages, int32_t max_steps, void* stream);
+/* out[0] sink_pages, [1] ring_pages, [2] max_steps of the window set now (all 0: none).  evictions_out (HOST int32 [B], or NULL): the
+ * rows' eviction counts of the last generation; synchronises `stream`; MGEA_EINVAL without a window. */
+int mgea_decoder_window_info(mgea_decoder* h, int32_t* out /* [3] */, int32_t* evictions_out /* NULL ok */, void* stream);
+
+/* Current cached length of each row -> lens_out_dev [B] (device int32).  Under a KV window (mgea_decoder_set_window) that is the
+ * tokens the row's pages hold after its evictions, not the tokens it has seen. */
 int mgea_decoder_context_lengths(mgea_decoder* h, int32_t* lens_out_dev, void* stream);
 
 /* Per-kernel-class timing for bench.py's roofline leg: with stride n > 0 every n-th decode step of
@@ -603,6 +644,12 @@ int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, c
                                 const mgea_row_logits* logits_rows, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
                                 int32_t n_class, const int32_t* states_in_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev,
                                 int32_t* states_out_dev, void* stream);
+/* The kernel that opens a windowed decode step (mgea_decoder_set_window, the eviction rule), alone on caller buffers: page_table_dev
+ * [B][max_pages], ctx_len_dev / done_dev / evictions_dev [B] int32 (device).  A row with done == 0 and ctx_len == 64 (S + R) - 1
+ * rotates its entries [S, S + R) left by one, ctx_len - 64, evictions + 1; every other row is left as it is.  MGEA_EINVAL for
+ * sink_pages < 1, ring_pages outside [2, 256] or sink_pages + ring_pages > max_pages. */
+int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sink_pages, int32_t ring_pages, int32_t* ctx_len_dev,
+                         const int32_t* done_dev, int32_t* evictions_dev, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }

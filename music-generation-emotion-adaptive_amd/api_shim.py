@@ -19,8 +19,18 @@ def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, t
     """top_p / repetition_penalty (None = none) reach sample_kvcache; the paper's decoding setting (§10.3) is
     create_app(model, seq_len, top_k=0, top_p=0.92, repetition_penalty=1.1).  One sample_kvcache call per request (they queue
     behind the engine's lock); create_batched_app serves concurrent requests as batches; create_constrained_app is this
-    endpoint with a constraint on what may be drawn."""
+    endpoint with a constraint on what may be drawn; create_windowed_app is it for pieces longer than the engine's context."""
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False)
+
+
+def create_windowed_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                        window=(1, None)):
+    """create_app with a KV window (create_app keeps its parameter list; create_batched_app takes the same keyword).
+    window = (sink_pages, ring_pages), ring_pages None = all the remaining pages: the model gets that window (GPTWithKV.set_window,
+    max_steps = seq_len) and seq_len may exceed the engine's context -- a piece of more than max_ctx tokens, the prompt's
+    conditioning tokens pinned in the sink while the oldest generated tokens leave (build-defined mechanics; the reference's loop
+    has no context limit either, api_cache.py:159-184)."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, window=window)
 
 
 def create_constrained_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
@@ -50,14 +60,17 @@ def create_grammar_app(model, seq_len: int, temperature: float = 1.0, top_k: int
 
 
 def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                       max_batch=None, grammar=None, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0):
+                       max_batch=None, grammar=None, window=None, constrain=None, out_of_scale_bias=float("-inf"),
+                       min_new_tokens: int = 0):
     """create_app with request batching: concurrent requests are coalesced into batched generations by app.state.batcher
     (mgea.serve.RequestBatcher, up to max_batch rows each -- default the model's max_batch) instead of one sample_kvcache call per
     request.  Each request keeps its own seed and budget; the response also carries X-Batch-Rows, the number of requests its
     generation served.  app.state.batcher.close() stops the worker.  grammar: None or "tracks", as in create_grammar_app (the batcher
-    groups requests by their grammar object; the app has one)."""
+    groups requests by their grammar object; the app has one).  window: as in create_windowed_app (the requests' budgets are then not
+    clamped at the engine's context)."""
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=True, max_batch=max_batch,
-                      constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar)
+                      constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar,
+                      window=window)
 
 
 def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
@@ -74,7 +87,7 @@ def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int
 
 
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
-               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None):
+               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     if constrain not in CONSTRAINTS:
@@ -86,6 +99,9 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
         raise ValueError("out_of_scale_bias must be finite or -inf")
     if int(min_new_tokens) < 0:
         raise ValueError(f"min_new_tokens {min_new_tokens} is negative")
+    if window is not None:   # (sink_pages, ring_pages); max_steps = what seq_len asks for
+        sink_pages, ring_pages = window
+        model.set_window(int(sink_pages), None if ring_pages is None else int(ring_pages), max_steps=max(int(seq_len), 1))
     from fastapi import FastAPI, Form
     from fastapi.middleware.cors import CORSMiddleware
     from fastapi.responses import Response

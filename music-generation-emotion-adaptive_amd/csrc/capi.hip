@@ -469,6 +469,12 @@ int mgea_op_sample_rows_scored(const float* logits_dev, int32_t B, int32_t V, co
                           ScoreArgs{forced_ids_dev, 0, logprobs_out_dev, choice_logprobs_out_dev, 0, nullptr}, stream);
 }
 
+int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sink_pages, int32_t ring_pages, int32_t* ctx_len_dev,
+                         const int32_t* done_dev, int32_t* evictions_dev, int32_t B, void* stream) {
+    return launch_window_evict(page_table_dev, max_pages, sink_pages, ring_pages, ctx_len_dev, done_dev, evictions_dev, B,
+                               (hipStream_t)stream);
+}
+
 int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                                 const mgea_row_logits* lrows, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
                                 int32_t n_class, const int32_t* states_in_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev,

@@ -349,6 +349,11 @@ int launch_advance(const int32_t* sampled, const StepState& s, int B, hipStream_
                    const ScoreFile* score = nullptr);
 // presence rows [0, B) <- the set of the real tokens of ids [B, T] (lens: first lens[b] of row b, NULL: all T; ids outside [0, V) skipped)
 int launch_presence_seed(const int32_t* ids, const int32_t* lens, int B, int T, int V, uint32_t* presence, hipStream_t st);
+// The first launch of a windowed decode step (kv_window.hip; the contract: include/mgea.h, mgea_decoder_set_window): a row that is not
+// finished and has ctx_len == 64 (S + R) - 1 rotates page_table[b][S .. S+R-1] left by one, ctx_len - 64, evictions + 1.
+constexpr int WINDOW_MAX_RING = 256;   // the ring of a row is held in registers: 4 entries per lane of one wave
+int launch_window_evict(int32_t* page_table, int max_pages, int S, int R, int32_t* ctx_len, const int32_t* done, int32_t* evictions,
+                        int B, hipStream_t st);
 // ctx_len[b] += (lens ? lens[b] : T)
 int launch_add_lens(int32_t* ctx_len, const int32_t* lens, int T, int B, hipStream_t st);
 // cur_ids[b] = ids[b, (lens ? lens[b] : T) - 1]

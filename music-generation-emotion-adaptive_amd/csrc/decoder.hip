@@ -88,6 +88,7 @@ struct mgea_decoder {
     DevGroup dev_ws;         // the workspace: released and regrown by ensure_ws
     DevGroup dev_p16_rows;   // Prefill16's activations and tables, regrown with its row count (ensure_p16)
     DevGroup dev_p16_mats;   // Prefill16's matrices p16.w / p16.vec, kept across refresh_weights
+    DevGroup dev_win;        // the KV window's histories and eviction counters: mgea_decoder_set_window, until the window changes
     // The handle's other HIP resources, declared behind the device groups, so that they go first (members die in reverse order):
     // the graphs, the pinned staging arrays and the events, then the device memory.
     Event stage_free;        // recorded after the copy out of samp_stage / gram_stage: they may be rewritten once it has completed
@@ -134,6 +135,19 @@ struct mgea_decoder {
     // on the unfused path.  Engine-owned, so the scored graphs hold stable pointers whatever the request forces.
     int32_t* forced = nullptr;
     float *lp_hist = nullptr, *ch_hist = nullptr, *lp_step = nullptr, *ch_step = nullptr;
+    // The KV window (mgea_decoder_set_window; the contract: include/mgea.h).  win_S > 0: every generation keeps P = win_S + win_R pages
+    // per row -- the sink and a ring -- and each of its steps opens with the evict launch (kv_window.hip), so it may run win_max_steps
+    // steps whatever max_ctx is.  Its id, forced-id and log-probability histories are therefore a second set, whist, with stride
+    // win_max_steps, next to the rows' eviction counters win_evict [max_batch] in dev_win: allocated by set_window and by nothing else, so
+    // an engine without a window allocates what it always did.  "Windowed" is part of the step-graph key; changing the window drops
+    // those graphs alone.  win_dirty: a windowed generation has run since the last reset -- ctx_len counts cached tokens, the host
+    // mirror (host_max_len) no longer says what the rows hold, and mgea_decoder_step / an extending forward are refused.
+    int win_S = 0, win_R = 0, win_max_steps = 0;
+    bool win_dirty = false;
+    int32_t* win_evict = nullptr;
+    struct Hist { int32_t* ids; int32_t* forced; float* lp; float* ch; int stride; };
+    Hist whist{nullptr, nullptr, nullptr, nullptr, 0};
+    Hist hist(bool windowed) const { return windowed ? whist : Hist{ids_hist, forced, lp_hist, ch_hist, ids_hist_stride}; }
     int32_t* err_flag = nullptr;   // sticky device flags (bit 0: a token id outside the vocabulary was clamped; bit 1: a forced id was banned by the grammar)
     // token grammar (mgea_decoder_set_grammar; GrammarArgs, common.h): one automaton per engine.  The tables live in buffers of their
     // largest size, allocated at create behind the other sampler buffers, so the GRAMMAR graphs hold stable pointers whatever table is
@@ -458,6 +472,7 @@ struct StepCall {
     // primed steps only: the qkv0 table of the step's decode path -- layer 0's q | k | v arrive primed too (no in-projection launch for
     // layer 0) and the tail gathers them for the next step; NULL: the launch
     const float* qkv0 = nullptr;
+    bool windowed = false;   // a step of a windowed generation: it files into the windowed histories (mgea_decoder::hist)
     // where the head writes the logits row: the caller's buffer, the engine's `own` for the sampler, nowhere for the argmax tails
     float* head_out(float* own) const { return logits_out ? logits_out : (form == StepForm::GREEDY ? nullptr : own); }
 };
@@ -481,7 +496,8 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, const float* lg, int n_part
     const auto& c = h->cfg;
     const int B = k.B, C = c.d_model, V = c.vocab;
     // (with records the EOS id, like the other scalars, is read from them -- the captured graph's form)
-    const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, h->ids_hist, h->ids_hist_stride, k.pv.eos_id, k.pd};
+    const mgea_decoder::Hist hi = h->hist(k.windowed);
+    const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, hi.ids, hi.stride, k.pv.eos_id, k.pd};
     const TailArgs t = tail_args(h, s, k.primed ? k.qkv0 : nullptr);
     if (k.form == StepForm::GREEDY) {
         MGEA_REQUIRE(!k.scored, MGEA_EINVAL, "internal: a scored step never takes the greedy form");
@@ -502,11 +518,11 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, const float* lg, int n_part
     if (k.form == StepForm::GRAMMAR)
         sc.grammar = GrammarArgs{h->gram_class, h->gram_next, h->gram_allow, h->gram_state, h->gram_state, h->done,
                                  h->gram_n_state, h->gram_n_class, grammar_words(h->gram_n_class), h->err_flag};
-    const int hs = h->ids_hist_stride;
+    const int hs = hi.stride;
     if (k.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
-        sc.score = ScoreArgs{h->forced, hs, k.primed ? h->lp_hist : h->lp_step, k.primed ? h->ch_hist : h->ch_step, hs, h->err_flag};
+        sc.score = ScoreArgs{hi.forced, hs, k.primed ? hi.lp : h->lp_step, k.primed ? hi.ch : h->ch_step, hs, h->err_flag};
     PROF(PC_SAMPLE, launch_sample(sc, st));
-    const ScoreFile sf{h->lp_step, h->ch_step, h->lp_hist, h->ch_hist, hs};
+    const ScoreFile sf{h->lp_step, h->ch_step, hi.lp, hi.ch, hs};
     if (!k.primed) PROF(PC_ROWOP, launch_advance(h->sampled, s, B, st, pres, V, k.scored ? &sf : nullptr));
     return MGEA_OK;
 }
@@ -607,8 +623,14 @@ int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
 }
 
 // The decode step of generate(): the rows' device records; x arrives primed on the fused path.
-int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st) {
-    return enqueue_step(h, StepCall{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored, qkv0_table(h, B)}, st);
+// windowed: the step opens with the KV window's evict launch, in front of every append of the step (the rule and why it keeps the
+// previous tail's layer-0 K | V alive: kv_window.hip); the node does not depend on the step's form.
+int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, bool windowed) {
+    if (windowed)
+        PROF(PC_ROWOP, launch_window_evict(h->page_table, h->max_pages, h->win_S, h->win_R, h->ctx_len, h->done, h->win_evict, B, st));
+    StepCall k{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored, qkv0_table(h, B)};
+    k.windowed = windowed;
+    return enqueue_step(h, k, st);
 }
 
 // embedding (+ LN statistics, or through the qkv0 table) of cur_ids into the buffers the next generate() step will read
@@ -625,8 +647,8 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
 // entry evicted beyond StepGraphs::CAP, hipres.h).
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps) {
-    const StepGraphs::Key key{B, form, scored, steps};
+int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps, bool windowed) {
+    const StepGraphs::Key key{B, form, scored, steps, windowed};
     if (const StepGraphs::Entry* e = h->graphs.find(key)) {
         if (steps == 1) h->n.graph_nodes = e->nodes;
         *out = e->exec;
@@ -636,7 +658,7 @@ int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t s
     if (h->graphs.full()) MGEA_CHECK_HIP(hipStreamSynchronize(st));
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st, windowed);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -816,6 +838,7 @@ int do_reset(mgea_decoder* h, int B, int max_len, hipStream_t st) {
     h->reserved_len = ppr * MGEA_KV_PAGE_TOKENS < c.max_ctx ? ppr * MGEA_KV_PAGE_TOKENS : c.max_ctx;
     h->host_max_len = 0;
     h->host_min_len = 0;
+    h->win_dirty = false;
     return MGEA_OK;
 }
 
@@ -825,6 +848,7 @@ int do_forward(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int B, 
     MGEA_REQUIRE(ids, MGEA_EINVAL, "forward: ids is NULL");
     MGEA_REQUIRE(h->cur_batch > 0, MGEA_EINVAL, "forward: call mgea_decoder_reset first");
     MGEA_REQUIRE(B == h->cur_batch, MGEA_EINVAL, "forward: batch %d differs from the reset batch %d", B, h->cur_batch);
+    MGEA_REQUIRE(!h->win_dirty, MGEA_EINVAL, "forward: the cache holds a windowed generation; call mgea_decoder_reset first");
     MGEA_REQUIRE(T > 0, MGEA_EINVAL, "forward: T must be positive");
     // the reference fails with a broadcast RuntimeError when T exceeds the position table (api_cache.py:99)
     MGEA_REQUIRE(T <= c.seq_len, MGEA_EINVAL, "T=%d exceeds the position table (%d rows)", T, c.seq_len);
@@ -1079,6 +1103,7 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
     hipStream_t st = (hipStream_t)stream;
     MGEA_REQUIRE(h->cfg.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_step needs the KV-cache block mode");
     MGEA_REQUIRE(h->cur_batch > 0, MGEA_EINVAL, "decoder_step: call reset/forward first");
+    MGEA_REQUIRE(!h->win_dirty, MGEA_EINVAL, "decoder_step: the cache holds a windowed generation; call mgea_decoder_reset first");
     MGEA_REQUIRE(h->host_max_len + 1 <= h->reserved_len, MGEA_ECAPACITY, "context %d + 1 exceeds the reserved %d",
                  h->host_max_len, h->reserved_len);
     const int B = h->cur_batch;
@@ -1112,6 +1137,16 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     RowRecords rr;   // the step graphs' form; whether to poll for early stops (some row can finish before n_steps)
     bool grammar = false;   // some row has a start state
     int reserve = Tp + n_steps;
+    // With a window set every generation is windowed: P pages per row, no budget clamp, no parking, every page id through the table.
+    const bool windowed = h->win_S > 0;
+    const int win_tokens = (h->win_S + h->win_R) * MGEA_KV_PAGE_TOKENS;
+    if (windowed) {
+        MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
+        MGEA_REQUIRE(Tp + 1 <= h->win_S * MGEA_KV_PAGE_TOKENS, MGEA_ECAPACITY,
+                     "prompt width %d + 1 exceeds the window's sink of %d pages (%d tokens)", Tp, h->win_S, h->win_S * MGEA_KV_PAGE_TOKENS);
+        MGEA_REQUIRE(n_steps <= h->win_max_steps, MGEA_ECAPACITY, "%d steps exceed the window's max_steps %d", n_steps, h->win_max_steps);
+        reserve = win_tokens;
+    }
     if (rows) {
         MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
         MGEA_TRY(check_row_samplers(rows, B, c.vocab, n_steps, "decoder_generate_rows"));
@@ -1126,15 +1161,16 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             grammar = true;
         }
         // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
-        MGEA_REQUIRE(Tp < c.max_ctx && n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp, n_steps,
-                     c.max_ctx);
-        reserve = reserve < c.max_ctx ? reserve : c.max_ctx;
+        // (a window holds every row for as long as it runs: nothing to stop)
+        MGEA_REQUIRE(windowed || (Tp < c.max_ctx && n_steps <= c.max_ctx), MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp,
+                     n_steps, c.max_ctx);
+        if (!windowed) reserve = reserve < c.max_ctx ? reserve : c.max_ctx;
         // the records go to the pinned staging buffer, free once the previous call's copy out of it has run
         MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free.ev));
         rr = build_row_records(rows, lrows, B, n_steps, h->samp_stage);
-        rr.may_stop_early = rr.may_stop_early || reserve < Tp + n_steps;
+        rr.may_stop_early = rr.may_stop_early || (!windowed && reserve < Tp + n_steps);
     } else {
-        MGEA_REQUIRE(Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
+        MGEA_REQUIRE(windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
         MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
         rr = RowRecords{step_form(s->top_k == 1, penalty != 1.0f, false), penalty != 1.0f, s->eos_id >= 0};
     }
@@ -1146,7 +1182,14 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->gram_steps = 0;
     h->n.scored_steps = h->n.penalized_steps = h->n.biased_steps = 0;
     MGEA_TRY(do_reset(h, B, reserve, st));
+    if (windowed) {   // the rotation breaks the allocation rule: every page id of the call comes from the table, the prefill's included
+        h->kv.arith_batch = 0;
+        MGEA_CHECK_HIP(hipMemsetAsync(h->win_evict, 0, (size_t)c.max_batch * sizeof(int32_t), st));
+    }
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
+    h->win_dirty = windowed;
+    const bool capped = !windowed && reserve < Tp + n_steps;   // rows stop where their pages end (launch_clamp_budgets, parking)
+    const mgea_decoder::Hist hi = h->hist(windowed);
     if (form_has_presence(form)) {   // every row's set starts as its real prompt tokens
         MGEA_TRY(launch_presence_seed(prompt_ids_dev, lens_dev, B, Tp, c.vocab, h->presence, st));
         h->last_penalized = true;
@@ -1166,24 +1209,24 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
         }
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free.ev, st));
-        if (reserve < Tp + n_steps) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
+        if (capped) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
     } else {
         MGEA_TRY(launch_fill_sampler_params(h->samp_dev, sampler_params(*s, penalty), B, st));
     }
     if (scored) {   // the engine's forced-id rows: -1 everywhere, then the caller's [B, n_steps] matrix (steps beyond it stay free)
-        const size_t hs = (size_t)h->ids_hist_stride;
-        MGEA_CHECK_HIP(hipMemsetAsync(h->forced, 0xff, (size_t)B * hs * sizeof(int32_t), st));
+        const size_t hs = (size_t)hi.stride;
+        MGEA_CHECK_HIP(hipMemsetAsync(hi.forced, 0xff, (size_t)B * hs * sizeof(int32_t), st));
         if (score->forced_dev)
-            MGEA_CHECK_HIP(hipMemcpy2DAsync(h->forced, hs * sizeof(int32_t), score->forced_dev, (size_t)n_steps * sizeof(int32_t),
+            MGEA_CHECK_HIP(hipMemcpy2DAsync(hi.forced, hs * sizeof(int32_t), score->forced_dev, (size_t)n_steps * sizeof(int32_t),
                                             (size_t)n_steps * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
     }
     if (const int path = qkv0_path(h, B); path >= 0) MGEA_TRY(ensure_qkv0(h, path, st));   // before any capture of this batch size
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1, windowed));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K, windowed));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1191,12 +1234,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, scored, st);
+            const int rc = enqueue_gen_step(h, B, form, scored, st, windowed);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st));
+            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st, windowed));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1211,7 +1254,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             if (host_done >= B) break;
         }
     }
-    if (reserve < Tp + n_steps) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
+    if (capped) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
     h->host_max_len += launched;
     h->n.graph_replays = launched;
     h->n.penalized_steps = rr.any_penalty ? launched : 0;
@@ -1220,18 +1263,18 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->gram_steps = grammar ? launched : 0;
     if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
         float* outs[2] = {score->logprobs_out, score->choice_out};
-        const float* hist[2] = {h->lp_hist, h->ch_hist};
+        const float* hist[2] = {hi.lp, hi.ch};
         for (int i = 0; i < 2; ++i) {
             if (!outs[i]) continue;
             MGEA_CHECK_HIP(hipMemsetAsync(outs[i], 0, (size_t)B * n_steps * sizeof(float), st));
-            MGEA_CHECK_HIP(hipMemcpy2DAsync(outs[i], (size_t)n_steps * sizeof(float), hist[i], (size_t)h->ids_hist_stride * sizeof(float),
+            MGEA_CHECK_HIP(hipMemcpy2DAsync(outs[i], (size_t)n_steps * sizeof(float), hist[i], (size_t)hi.stride * sizeof(float),
                                             (size_t)launched * sizeof(float), B, hipMemcpyDeviceToDevice, st));
         }
     }
     // rows: ids_hist[b, 0:launched]; steps never run are -1
     MGEA_CHECK_HIP(hipMemsetAsync(ids_out_dev, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));
-    MGEA_CHECK_HIP(hipMemcpy2DAsync(ids_out_dev, (size_t)n_steps * sizeof(int32_t), h->ids_hist,
-                                    (size_t)h->ids_hist_stride * sizeof(int32_t), (size_t)launched * sizeof(int32_t), B,
+    MGEA_CHECK_HIP(hipMemcpy2DAsync(ids_out_dev, (size_t)n_steps * sizeof(int32_t), hi.ids,
+                                    (size_t)hi.stride * sizeof(int32_t), (size_t)launched * sizeof(int32_t), B,
                                     hipMemcpyDeviceToDevice, st));
     return MGEA_OK;
 }
@@ -1356,6 +1399,67 @@ int mgea_decoder_generate_rows_grammar(mgea_decoder* h, const int32_t* prompt_id
     const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
     return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
                        logprobs_out_dev ? &io : nullptr, start_states);
+}
+
+int mgea_decoder_set_window(mgea_decoder* h, int32_t sink_pages, int32_t ring_pages, int32_t max_steps, void* stream) {
+    MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_set_window: NULL handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const auto& c = h->cfg;
+    auto clear = [&]() {
+        h->graphs.drop_windowed();
+        h->dev_win.release();
+        h->whist = mgea_decoder::Hist{nullptr, nullptr, nullptr, nullptr, 0};
+        h->win_S = h->win_R = h->win_max_steps = 0;
+    };
+    if (sink_pages == 0) {
+        if (h->win_S == 0) return MGEA_OK;
+        MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying, a freed history still be written
+        clear();
+        return MGEA_OK;
+    }
+    MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_set_window needs the KV-cache block mode");
+    MGEA_REQUIRE(c.pos_mode == MGEA_POS_REFERENCE, MGEA_EINVAL,
+                 "decoder_set_window: MGEA_POS_ABSOLUTE engines have no window (a step's position would be its cached length)");
+    MGEA_REQUIRE(sink_pages >= 1, MGEA_EINVAL, "decoder_set_window: sink_pages %d must be >= 1 (0 clears the window)", sink_pages);
+    MGEA_REQUIRE(ring_pages >= 2, MGEA_EINVAL,
+                 "decoder_set_window: ring_pages %d must be >= 2 (one page would be evicted with the current token in it)", ring_pages);
+    MGEA_REQUIRE(ring_pages <= WINDOW_MAX_RING, MGEA_EINVAL, "decoder_set_window: ring_pages %d exceeds %d", ring_pages, WINDOW_MAX_RING);
+    MGEA_REQUIRE((int64_t)sink_pages + ring_pages <= c.max_ctx / MGEA_KV_PAGE_TOKENS, MGEA_EINVAL,
+                 "decoder_set_window: sink_pages %d + ring_pages %d exceed the %d whole pages of max_ctx %d", sink_pages, ring_pages,
+                 c.max_ctx / MGEA_KV_PAGE_TOKENS, c.max_ctx);
+    MGEA_REQUIRE(max_steps >= 1 && max_steps <= MGEA_WINDOW_MAX_STEPS, MGEA_EINVAL, "decoder_set_window: max_steps %d outside [1, %d]",
+                 max_steps, MGEA_WINDOW_MAX_STEPS);
+    if (sink_pages == h->win_S && ring_pages == h->win_R && max_steps == h->win_max_steps) return MGEA_OK;
+    MGEA_CHECK_HIP(hipStreamSynchronize(st));
+    clear();   // the windowed graphs carry S, P and the histories' pointers
+    const size_t nhist = (size_t)c.max_batch * (size_t)max_steps;
+    DevGroup& g = h->dev_win;
+    if (g.alloc(&h->whist.ids, nhist * sizeof(int32_t)) || g.alloc(&h->whist.forced, nhist * sizeof(int32_t)) ||
+        g.alloc(&h->whist.lp, nhist * sizeof(float)) || g.alloc(&h->whist.ch, nhist * sizeof(float)) ||
+        g.alloc(&h->win_evict, (size_t)c.max_batch * sizeof(int32_t))) {
+        clear();
+        set_error("decoder_set_window: allocation of the histories for max_steps %d failed", max_steps);
+        return MGEA_ENOMEM;
+    }
+    MGEA_CHECK_HIP(hipMemsetAsync(h->win_evict, 0, (size_t)c.max_batch * sizeof(int32_t), st));
+    h->whist.stride = max_steps;
+    h->win_S = sink_pages; h->win_R = ring_pages; h->win_max_steps = max_steps;
+    return MGEA_OK;
+}
+
+int mgea_decoder_window_info(mgea_decoder* h, int32_t* out, int32_t* evictions_out, void* stream) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_window_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->win_S; out[1] = h->win_R; out[2] = h->win_max_steps;
+    if (evictions_out) {
+        MGEA_REQUIRE(h->win_S > 0, MGEA_EINVAL, "decoder_window_info: no window is set");
+        hipStream_t st = (hipStream_t)stream;
+        const int B = h->cur_batch > 0 ? h->cur_batch : 0;
+        MGEA_CHECK_HIP(hipMemcpyAsync(evictions_out, h->win_evict, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        MGEA_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    return MGEA_OK;
 }
 
 int mgea_decoder_grammar_states(mgea_decoder* h, int32_t* out_dev, void* stream) {

@@ -101,6 +101,7 @@ class GPTWithKV:
         self.dtype = dtype   # "f32" = the reference's arithmetic (parity mode); "f16" = fp16 matrices + KV (mgea.decoder)
         self.engine: Optional[DecoderEngine] = None
         self._epoch = -1
+        self._window = None   # set_window's arguments, applied to every engine load_state_dict builds
 
     # -- nn.Module look-alikes ----------------------------------------------------------------
     def load_state_dict(self, sd: Dict, strict: bool = True):
@@ -115,7 +116,19 @@ class GPTWithKV:
         max_ctx = self.max_ctx if self.max_ctx is not None else max(self.seq_len, 1)
         self.engine = DecoderEngine(sd, n_head=self.n_head, max_batch=self.max_batch, max_ctx=max_ctx,
                                     device=self.device, block_mode=self.block_mode, dtype=self.dtype)
+        if self._window is not None:
+            self.engine.set_window(*self._window)
         return "<All keys matched successfully>"
+
+    def set_window(self, sink_pages: int = 1, ring_pages: Optional[int] = None, max_steps: Optional[int] = None):
+        """Give the model a KV window (DecoderEngine.set_window): sample_kvcache and the other generation calls then take a max_len
+        beyond the engine's context -- the prompt stays cached, the oldest generated tokens leave a 64-token page at a time, as
+        the reference's own loop has no context limit (api_cache.py:159-184).  sink_pages 0 clears it.  Kept across
+        load_state_dict."""
+        self._window = None if int(sink_pages) == 0 else (int(sink_pages), ring_pages, max_steps)
+        if self.engine is not None:
+            self.engine.set_window(sink_pages, ring_pages, max_steps)
+        return self
 
     def eval(self):
         return self
@@ -164,15 +177,17 @@ class GPT(GPTWithKV):
 
 
 def load_checkpoint(path, n_head: int = 8, device: str = _DEFAULT_DEVICE, max_batch: int = 8,
-                    max_ctx: Optional[int] = None):
+                    max_ctx: Optional[int] = None, window=None):
     """api_cache.py:26-37,108-138 in one call: torch.load(weights_only=True), geometry from tensor
     shapes, GPTWithKV + remapped weights.  Returns (model, tok2id, id2tok, SEQ_LEN, D_MODEL) and
-    installs the vocabulary in this module."""
+    installs the vocabulary in this module.  window (None, or (sink_pages, ring_pages[, max_steps])): GPTWithKV.set_window."""
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     geo = geometry_from_state_dict(ckpt["model"])
     set_vocab(ckpt["vocab"])
     m = GPTWithKV(vocab_size=len(tok2id), seq_len=geo["seq_len"], d_model=geo["d_model"], n_head=n_head,
                   n_layer=geo["n_layer"], max_batch=max_batch, max_ctx=max_ctx, device=device)
+    if window is not None:
+        m.set_window(*window)
     m.load_state_dict(remap_state_dict(ckpt["model"]))
     global model
     model = m
@@ -191,6 +206,11 @@ def _as_model(model_or_weights, n_head=8, device=_DEFAULT_DEVICE) -> GPTWithKV:
         m.load_state_dict(sd)
         return m
     raise TypeError("expected a GPTWithKV or a state dict / checkpoint dict")
+
+
+def _no_window(eng) -> bool:
+    """True when the engine stops a generation at its reserved context (no KV window: DecoderEngine.set_window)."""
+    return getattr(eng, "window", None) is None
 
 
 def _use_grammar(eng, grammar) -> None:
@@ -267,7 +287,7 @@ def sample_kvcache_grammar(model, prompt: Sequence[str], max_len=512, temperatur
     n_steps = int(max_len) - len(ids)
     if n_steps <= 0:
         return [id2tok[i] for i in ids]
-    if len(ids) + n_steps > eng.max_ctx:
+    if _no_window(eng) and len(ids) + n_steps > eng.max_ctx:
         raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
     out = _engine_generate(eng, [ids], n_steps, logit_bias, min_new_tokens, grammar, temperature=temperature, top_k=top_k,
@@ -335,7 +355,7 @@ def score_sequence(model, prompt_tokens: Sequence[str], continuation_tokens: Seq
     cont = [tok2id[t] for t in continuation_tokens]
     if not cont:
         return []
-    if len(ids) + len(cont) > eng.max_ctx:
+    if _no_window(eng) and len(ids) + len(cont) > eng.max_ctx:
         raise RuntimeError(f"prompt + continuation = {len(ids) + len(cont)} tokens exceed the engine's reserved context {eng.max_ctx}")
     lp, _ = eng.score([ids], [cont])
     return [float(v) for v in lp[0].cpu().tolist()]
@@ -380,7 +400,7 @@ def generate_best_of(model, prompt: Sequence[str], n: int, max_len=512, temperat
     if n_steps <= 0:
         toks = [id2tok[i] for i in ids]
         return (toks, [list(toks) for _ in range(n)], [float("-inf")] * n, 0) if return_all else toks
-    if len(ids) + n_steps > eng.max_ctx:
+    if _no_window(eng) and len(ids) + n_steps > eng.max_ctx:
         raise RuntimeError(f"max_len={max_len} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
     seed = _draw_seed() if seed is None else int(seed)
@@ -436,7 +456,7 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
     budgets = [L - len(p) for L, p in zip(max_lens, ids)]
     for L, p in zip(max_lens, ids):
-        if L > len(p) and L > eng.max_ctx:
+        if _no_window(eng) and L > len(p) and L > eng.max_ctx:
             raise RuntimeError(f"max_len={L} exceeds the engine's reserved context {eng.max_ctx}")
     eos = tok2id.get("[END_SEQUENCE]", -1)
     live = [i for i in range(n) if budgets[i] > 0]

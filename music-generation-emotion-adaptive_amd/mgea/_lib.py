@@ -93,6 +93,8 @@ PROTOTYPES = {
     "mgea_decoder_set_grammar": (C.c_int, [_P, _P, _P, _I32, _I32, _P]),
     "mgea_decoder_generate_rows_grammar": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P, _P, _P,
                                                     _P, _P, _P]),
+    "mgea_decoder_set_window": (C.c_int, [_P, _I32, _I32, _I32, _P]),
+    "mgea_decoder_window_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "mgea_decoder_grammar_states": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_grammar_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_presence": (C.c_int, [_P, _P, _P]),
@@ -142,6 +144,7 @@ PROTOTYPES = {
     "mgea_op_sample_rows": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, _I64, _P, _P, _P]),
     "mgea_op_sample_rows_biased": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P]),
     "mgea_op_sample_rows_scored": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P, _P, _P, _P]),
+    "mgea_op_window_evict": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,
                                               _P, _P, _P]),
 }

@@ -207,6 +207,104 @@ class TokenGrammar:
         return True
 
 
+KV_PAGE_TOKENS = _lib.KV_PAGE_TOKENS
+WINDOW_MAX_RING, WINDOW_MAX_STEPS = 256, 1 << 24
+
+
+@dataclasses.dataclass(frozen=True)
+class KVWindow:
+    """The host model of the engine's KV window (include/mgea.h, mgea_decoder_set_window): pure Python, no device.  Every row keeps
+    P = sink_pages + ring_pages pages of 64 tokens; logical pages 0 .. S-1, the sink, are never evicted, pages S .. P-1 are a ring.
+    At the start of a step a row that is not finished and caches exactly 64 P - 1 tokens evicts its oldest ring page whole.  A row
+    has Lp real prompt tokens, and step i (0-based) caches the token it feeds at absolute position Lp + i."""
+    sink_pages: int
+    ring_pages: int
+    max_steps: int
+
+    @property
+    def pages(self) -> int:
+        return self.sink_pages + self.ring_pages
+
+    @property
+    def tokens(self) -> int:
+        return self.pages * KV_PAGE_TOKENS
+
+    def check(self, max_ctx: int) -> None:
+        """The rules of mgea_decoder_set_window as ValueErrors naming the offending value."""
+        S, R = int(self.sink_pages), int(self.ring_pages)
+        if S < 1:
+            raise ValueError(f"window: sink_pages {S} must be >= 1")
+        if R < 2:
+            raise ValueError(f"window: ring_pages {R} must be >= 2 (one page would be evicted with the current token in it)")
+        if R > WINDOW_MAX_RING:
+            raise ValueError(f"window: ring_pages {R} exceeds {WINDOW_MAX_RING}")
+        if S + R > int(max_ctx) // KV_PAGE_TOKENS:
+            raise ValueError(f"window: sink_pages {S} + ring_pages {R} exceed the {int(max_ctx) // KV_PAGE_TOKENS} whole pages of "
+                             f"max_ctx {max_ctx}")
+        if not 1 <= int(self.max_steps) <= WINDOW_MAX_STEPS:
+            raise ValueError(f"window: max_steps {self.max_steps} outside [1, {WINDOW_MAX_STEPS}]")
+
+    def check_call(self, prompt_width: int, n_steps: int) -> None:
+        """What a windowed generation needs: the prompt and its duplicate inside the sink, n_steps <= max_steps."""
+        if int(prompt_width) + 1 > self.sink_pages * KV_PAGE_TOKENS:
+            raise ValueError(f"prompt width {prompt_width} + 1 exceeds the window's sink of {self.sink_pages} pages "
+                             f"({self.sink_pages * KV_PAGE_TOKENS} tokens)")
+        if int(n_steps) > int(self.max_steps):
+            raise ValueError(f"{n_steps} steps exceed the window's max_steps {self.max_steps}")
+
+    def first_eviction_step(self, prompt_len: int) -> int:
+        """i0: the first step that opens with an eviction."""
+        return self.tokens - 1 - int(prompt_len)
+
+    def evictions(self, prompt_len: int, step: int) -> int:
+        """e(i): the evictions of a row of prompt_len real tokens before step `step` attends (after n steps that all ran:
+        evictions(prompt_len, n - 1))."""
+        i0 = self.first_eviction_step(prompt_len)
+        return 0 if step < i0 else 1 + (int(step) - i0) // KV_PAGE_TOKENS
+
+    def attended(self, prompt_len: int, step: int):
+        """The absolute positions step `step` attends, as two ranges: the sink side and the ring side (one of them may be empty
+        before the first eviction, when the ranges meet)."""
+        e = self.evictions(prompt_len, step)
+        last = int(prompt_len) + int(step)
+        if e == 0:
+            return range(0, last + 1), range(0)
+        return range(0, self.sink_pages * KV_PAGE_TOKENS), range((self.sink_pages + e) * KV_PAGE_TOKENS, last + 1)
+
+    def attended_count(self, prompt_len: int, step: int) -> int:
+        a, b = self.attended(prompt_len, step)
+        return len(a) + len(b)
+
+    def simulate(self, prompt_len: int, n_steps: int, steps=None):
+        """The rule, step by step (what the device does, on the host).  Returns (counts, sets): the number of positions every step
+        attends, and {step: the set of absolute positions attended} for the steps in `steps` (None: all).  The eviction drops ring
+        page S whole."""
+        S, P = self.sink_pages, self.pages
+        cached = list(range(int(prompt_len)))            # absolute positions in logical order
+        counts, sets = [], {}
+        for i in range(int(n_steps)):
+            if len(cached) == KV_PAGE_TOKENS * P - 1:
+                del cached[S * KV_PAGE_TOKENS:(S + 1) * KV_PAGE_TOKENS]
+            cached.append(int(prompt_len) + i)
+            counts.append(len(cached))
+            if steps is None or i in steps:
+                sets[i] = set(cached)
+        return counts, sets
+
+    @staticmethod
+    def evict_rows(page_table, sink_pages: int, ring_pages: int, ctx_len, done, evictions):
+        """The evict kernel on host arrays (numpy int32; copies are returned): rows with done == 0 and ctx_len == 64 P - 1 rotate
+        page_table[b, S:P] left by one, ctx_len - 64, evictions + 1; the others stay."""
+        pt, cl, ev = (np.array(a, dtype=np.int32, copy=True) for a in (page_table, ctx_len, evictions))
+        S, P = int(sink_pages), int(sink_pages) + int(ring_pages)
+        for b in range(pt.shape[0]):
+            if int(np.asarray(done)[b]) == 0 and int(cl[b]) == KV_PAGE_TOKENS * P - 1:
+                pt[b, S:P] = np.roll(pt[b, S:P], -1)
+                cl[b] -= KV_PAGE_TOKENS
+                ev[b] += 1
+        return pt, cl, ev
+
+
 @dataclasses.dataclass
 class RowSampling:
     """One batch row's sampler settings (mgea_row_sampler, include/mgea.h) for DecoderEngine.generate_rows / ops.sample_rows.
@@ -410,6 +508,7 @@ class DecoderEngine:
         check(self.lib.mgea_decoder_create(C.byref(self.cfg), ptr(self.arena), C.byref(h)))
         self.h = h
         self.grammar: Optional[TokenGrammar] = None
+        self.window: Optional[KVWindow] = None
         self._cur_batch = 0
         self._epoch = 0  # bumps whenever the native cache is reset (guards stale `presents`)
         self._len = 0
@@ -523,6 +622,42 @@ class DecoderEngine:
         out = (C.c_int64 * 4)()
         check(self.lib.mgea_decoder_grammar_info(self.h, out))
         return dict(n_state=out[0], n_class=out[1], uploads=out[2], grammar_steps=out[3])
+
+    # ------------------------------------------------------------------ KV window
+    def set_window(self, sink_pages: int = 1, ring_pages: Optional[int] = None, max_steps: Optional[int] = None) -> None:
+        """Set the engine's KV window (KVWindow; include/mgea.h, mgea_decoder_set_window): generate*, generate_rows, generate_scored
+        and score then accept n_steps up to max_steps whatever max_ctx is -- the prompt (width + 1 <= 64 * sink_pages) stays pinned
+        in the sink while the oldest generated tokens leave the ring a page at a time.  ring_pages None = all the remaining pages of
+        max_ctx; max_steps None = 16 * max_ctx (the histories cost max_batch * max_steps * 16 bytes).  sink_pages 0 clears the
+        window: the engine then behaves exactly as one that never had it.  ValueError naming the offending value."""
+        if int(sink_pages) == 0:
+            with self._on_stream():
+                check(self.lib.mgea_decoder_set_window(self.h, 0, 0, 0, self._sp()))
+            self.window = None
+            return
+        if ring_pages is None:
+            ring_pages = min(self.max_ctx // KV_PAGE_TOKENS - int(sink_pages), WINDOW_MAX_RING)
+        w = KVWindow(int(sink_pages), int(ring_pages), int(16 * self.max_ctx if max_steps is None else max_steps))
+        w.check(self.max_ctx)
+        if self.cfg.block_mode != _lib.BLOCK_PRELN_GELU or self.cfg.pos_mode != _lib.POS_REFERENCE:
+            raise ValueError("window: needs the KV-cache block mode and the reference's position mode")
+        with self._on_stream():
+            check(self.lib.mgea_decoder_set_window(self.h, w.sink_pages, w.ring_pages, w.max_steps, self._sp()))
+        self.window = w
+
+    def window_info(self) -> Optional[KVWindow]:
+        """The window the native engine holds now (None: none)."""
+        out = (C.c_int32 * 3)()
+        check(self.lib.mgea_decoder_window_info(self.h, out, None, self._sp()))
+        return KVWindow(out[0], out[1], out[2]) if out[0] > 0 else None
+
+    def window_evictions(self) -> List[int]:
+        """The rows' eviction counts of the last generation (one stream sync); KVWindow.evictions is their closed form."""
+        out = (C.c_int32 * 3)()
+        ev = (C.c_int32 * max(self._cur_batch, 1))()
+        with self._on_stream():
+            check(self.lib.mgea_decoder_window_info(self.h, out, ev, self._sp()))
+        return list(ev)[:self._cur_batch]
 
     def _start_states(self, rows):
         """The rows' grammar start states as a C int32 [B] array, or None when no row has one (the caller then makes the call it

@@ -361,6 +361,20 @@ def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_ta
     return out
 
 
+def window_evict(page_table: torch.Tensor, sink_pages: int, ring_pages: int, ctx_len: torch.Tensor, done: torch.Tensor,
+                 evictions: torch.Tensor):
+    """The kernel that opens a windowed decode step (mgea_op_window_evict), alone: int32 copies of page_table [B, max_pages], ctx_len,
+    done and evictions [B] (host or device tensors) on the device; returns the (page_table, ctx_len, evictions) it leaves there.  The
+    host model of it: mgea.decoder.KVWindow.evict_rows."""
+    lib = _lib.load()
+    pt, cl, dn, ev = (t.to(device="cuda", dtype=torch.int32).contiguous().clone() for t in (page_table, ctx_len, done, evictions))
+    if pt.dim() != 2 or any(t.shape != (pt.shape[0],) for t in (cl, dn, ev)):
+        raise RuntimeError("window_evict: page_table must be [B, max_pages] and ctx_len / done / evictions [B]")
+    check(lib.mgea_op_window_evict(ptr(pt), pt.shape[1], int(sink_pages), int(ring_pages), ptr(cl), ptr(dn), ptr(ev), pt.shape[0],
+                                   stream_ptr()))
+    return pt, cl, ev
+
+
 def check_repetition_penalty(penalty) -> Optional[float]:
     """None -> None (no penalty).  Otherwise the penalty as a float, which must be finite and > 0 also once held as
     fp32 (the kernels' precision): ValueError otherwise, as transformers' RepetitionPenaltyLogitsProcessor raises."""
