@@ -257,8 +257,9 @@ static int bert_forward_impl(mgea_bert* h, const int32_t* ids_dev, const int32_t
         for (int64_t& e : h->last_epi) e = 0;
         auto bgemm = [&](const void* A, int lda, const void* W, int ldw, const float* bias, const void* res, void* C, int ldc, int m, int n,
                          int k, int epi, const BfEpiLn* ln = nullptr) -> int {
-            GemmBf16Info gi{0, 0, k > n ? 1 : 0};   // the FFN down-projection (K = hidden > N) reads the up-projection's big output: walk it backwards
-            MGEA_TRY(launch_gemm_bf16(A, lda, W, ldw, bias, res, C, ldc, m, n, k, epi, st, &gi, ln));
+            GemmBf16Info gi{0, 0};
+            // reverse: the FFN down-projection (K = hidden > N) reads the up-projection's big output: walk it backwards
+            MGEA_TRY(launch_gemm_bf16(A, lda, W, ldw, bias, res, C, ldc, m, n, k, epi, st, &gi, ln, 0, k > n ? 1 : 0));
             (gi.kernel == 2 ? h->last_persistent : gi.kernel == 1 ? h->last_ring : h->last_small) += 1;
             h->last_half_tiles += gi.half_tiles;
             h->last_epi[epi] += 1;
@@ -288,33 +289,33 @@ static int bert_forward_impl(mgea_bert* h, const int32_t* ids_dev, const int32_t
                 if (cls_last && l == last) {                // K | V of every position, the rest of the layer on the [CLS] rows
                     if (first) {
                         MGEA_TRY(bgemm(h->hb, D, (const char*)wb(l, BL_QKVW) + kv_off, D, h->lw(l, BL_QKVB) + D, nullptr, (char*)h->qkvb + D * 2, 3 * D, M,
-                                       2 * D, D, 0));
+                                       2 * D, D, BEPI_BIAS));
                         MGEA_TRY(launch_gather_cls_bf16(h->hb, h->pooled, B, S, D, st, cu));
                     } else {
                         BfEpiLn q{h->rowstat_out, h->qkvc(l, 0) + D, nullptr, nullptr, nullptr};
-                        MGEA_TRY(bgemm(h->hb, D, h->qkvf(l) + kv_off, D, h->qkvc(l, 1) + D, nullptr, (char*)h->qkvb + D * 2, 3 * D, M, 2 * D, D, 3, &q));
+                        MGEA_TRY(bgemm(h->hb, D, h->qkvf(l) + kv_off, D, h->qkvc(l, 1) + D, nullptr, (char*)h->qkvb + D * 2, 3 * D, M, 2 * D, D, BEPI_LNFOLD, &q));
                         MGEA_TRY(launch_gather_cls_ln_bf16(h->hb, h->rowstat_out, h->lw(l - 1, BL_OLNW), h->lw(l - 1, BL_OLNB), h->pooled, B, S, D, st, cu));
                     }
                     MGEA_TRY(cls_tail(l, h->qkvb, 1));
                     break;
                 }
                 if (first) {
-                    MGEA_TRY(bgemm(h->hb, D, wb(l, BL_QKVW), D, h->lw(l, BL_QKVB), nullptr, h->qkvb, 3 * D, M, 3 * D, D, 0));
+                    MGEA_TRY(bgemm(h->hb, D, wb(l, BL_QKVW), D, h->lw(l, BL_QKVB), nullptr, h->qkvb, 3 * D, M, 3 * D, D, BEPI_BIAS));
                 } else {
                     BfEpiLn q{h->rowstat_out, h->qkvc(l, 0), nullptr, nullptr, nullptr};
-                    MGEA_TRY(bgemm(h->hb, D, h->qkvf(l), D, h->qkvc(l, 1), nullptr, h->qkvb, 3 * D, M, 3 * D, D, 3, &q));
+                    MGEA_TRY(bgemm(h->hb, D, h->qkvf(l), D, h->qkvc(l, 1), nullptr, h->qkvb, 3 * D, M, 3 * D, D, BEPI_LNFOLD, &q));
                 }
                 MGEA_TRY(launch_attn_bf16(h->qkvb, mask_dev, h->ctxb, B, S, c.n_heads, dh, st, 0, nullptr, cu));
                 // out-proj + LayerNorm_out(l-1)(raw hb) as the residual (layer 0: hb is already normalised) -> raw tmpb + row sums
                 BfEpiLn o{first ? h->ident : h->rowstat_out, nullptr, first ? id_g : h->lw(l - 1, BL_OLNW), first ? id_b : h->lw(l - 1, BL_OLNB),
                           h->stats_part};
-                MGEA_TRY(bgemm(h->ctxb, D, wb(l, BL_OUTW), D, h->lw(l, BL_OUTB), h->hb, h->tmpb, D, M, D, D, 5, &o));
+                MGEA_TRY(bgemm(h->ctxb, D, wb(l, BL_OUTW), D, h->lw(l, BL_OUTB), h->hb, h->tmpb, D, M, D, D, BEPI_RES_LN, &o));
                 MGEA_TRY(launch_ln_rowstat(h->stats_part, h->rowstat_sa, M, npart, D, c.ln_eps, st));
                 BfEpiLn f1{h->rowstat_sa, h->fc1c(l, 0), nullptr, nullptr, nullptr};
-                MGEA_TRY(bgemm(h->tmpb, D, h->fc1f(l), D, h->fc1c(l, 1), nullptr, h->ffnb, Hd, M, Hd, D, 4, &f1));
+                MGEA_TRY(bgemm(h->tmpb, D, h->fc1f(l), D, h->fc1c(l, 1), nullptr, h->ffnb, Hd, M, Hd, D, BEPI_LNFOLD_GELU, &f1));
                 // FC2 + LayerNorm_sa(l)(raw tmpb) as the residual -> raw hb + row sums
                 BfEpiLn f2{h->rowstat_sa, nullptr, h->lw(l, BL_SALNW), h->lw(l, BL_SALNB), h->stats_part};
-                MGEA_TRY(bgemm(h->ffnb, Hd, wb(l, BL_L2W), Hd, h->lw(l, BL_L2B), h->tmpb, h->hb, D, M, D, Hd, 5, &f2));
+                MGEA_TRY(bgemm(h->ffnb, Hd, wb(l, BL_L2W), Hd, h->lw(l, BL_L2B), h->tmpb, h->hb, D, M, D, Hd, BEPI_RES_LN, &f2));
                 MGEA_TRY(launch_ln_rowstat(h->stats_part, h->rowstat_out, M, npart, D, c.ln_eps, st));
             }
             if (!cls_last)
@@ -324,18 +325,18 @@ static int bert_forward_impl(mgea_bert* h, const int32_t* ids_dev, const int32_t
         for (int l = 0; l < c.n_layers; ++l) {
             if (cls_last && l == last) {
                 MGEA_TRY(bgemm(h->hb, D, (const char*)wb(l, BL_QKVW) + kv_off, D, h->lw(l, BL_QKVB) + D, nullptr, (char*)h->qkvb + D * 2, 3 * D, M, 2 * D,
-                               D, 0));
+                               D, BEPI_BIAS));
                 MGEA_TRY(launch_gather_cls_bf16(h->hb, h->pooled, B, S, D, st, cu));
                 MGEA_TRY(cls_tail(l, h->qkvb, 1));
                 break;
             }
-            MGEA_TRY(bgemm(h->hb, D, wb(l, BL_QKVW), D, h->lw(l, BL_QKVB), nullptr, h->qkvb, 3 * D, M, 3 * D, D, 0));
+            MGEA_TRY(bgemm(h->hb, D, wb(l, BL_QKVW), D, h->lw(l, BL_QKVB), nullptr, h->qkvb, 3 * D, M, 3 * D, D, BEPI_BIAS));
             MGEA_TRY(launch_attn_bf16(h->qkvb, mask_dev, h->ctxb, B, S, c.n_heads, dh, st, 0, nullptr, cu));
-            MGEA_TRY(bgemm(h->ctxb, D, wb(l, BL_OUTW), D, h->lw(l, BL_OUTB), h->hb, h->tmpb, D, M, D, D, 2));
+            MGEA_TRY(bgemm(h->ctxb, D, wb(l, BL_OUTW), D, h->lw(l, BL_OUTB), h->hb, h->tmpb, D, M, D, D, BEPI_BIAS_RES));
             MGEA_TRY(launch_layernorm_bf16(h->tmpb, h->lw(l, BL_SALNW), h->lw(l, BL_SALNB), h->hb, M, D, c.ln_eps, st));
             h->last_ln_kernels += 2;
-            MGEA_TRY(bgemm(h->hb, D, wb(l, BL_L1W), D, h->lw(l, BL_L1B), nullptr, h->ffnb, Hd, M, Hd, D, 1));
-            MGEA_TRY(bgemm(h->ffnb, Hd, wb(l, BL_L2W), Hd, h->lw(l, BL_L2B), h->hb, h->tmpb, D, M, D, Hd, 2));
+            MGEA_TRY(bgemm(h->hb, D, wb(l, BL_L1W), D, h->lw(l, BL_L1B), nullptr, h->ffnb, Hd, M, Hd, D, BEPI_BIAS_GELU));
+            MGEA_TRY(bgemm(h->ffnb, Hd, wb(l, BL_L2W), Hd, h->lw(l, BL_L2B), h->hb, h->tmpb, D, M, D, Hd, BEPI_BIAS_RES));
             MGEA_TRY(launch_layernorm_bf16(h->tmpb, h->lw(l, BL_OLNW), h->lw(l, BL_OLNB), h->hb, M, D, c.ln_eps, st));
         }
         if (!cls_last) MGEA_TRY(launch_gather_cls_bf16(h->hb, h->pooled, B, S, D, st, cu));

@@ -195,9 +195,9 @@ int mgea_op_gemm_bf16_ln(const void* a_dev, const void* w_dev, const float* bias
                          const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream) {
     MGEA_REQUIRE(a_dev && w_dev && out_dev, MGEA_EINVAL, "op_gemm_bf16_ln: NULL argument");
     const BfEpiLn ln{rowstat_dev, c1_dev, ln_g_dev, ln_b_dev, stats_out_dev};
-    GemmBf16Info gi{-1, 0, 0};
+    GemmBf16Info gi{-1, 0};
     const int rc = launch_gemm_bf16(a_dev, K, w_dev, K, bias_dev, res_dev, out_dev, N, M, N, K, epi, (hipStream_t)stream, &gi,
-                                    epi >= 3 ? &ln : nullptr);
+                                    epi >= BEPI_LNFOLD ? &ln : nullptr);
     if (info_out) { info_out[0] = gi.kernel; info_out[1] = gi.half_tiles; }
     return rc;
 }
@@ -241,7 +241,7 @@ int mgea_op_gemm_f16_ln(const void* a_dev, const void* w_dev, const float* bias_
                         const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream) {
     MGEA_REQUIRE(a_dev && w_dev && out_dev, MGEA_EINVAL, "op_gemm_f16_ln: NULL argument");
     const BfEpiLn ln{rowstat_dev, c1_dev, ln_g_dev, ln_b_dev, stats_out_dev};
-    GemmBf16Info gi{-1, 0, 0};
+    GemmBf16Info gi{-1, 0};
     const int rc = launch_gemm_bf16(a_dev, K, w_dev, K, bias_dev, res_dev, out_dev, N, M, N, K, epi, (hipStream_t)stream, &gi, &ln, 1);
     if (info_out) { info_out[0] = gi.kernel; info_out[1] = gi.half_tiles; }
     return rc;

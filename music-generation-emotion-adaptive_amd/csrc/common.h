@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/mgea.h"
+#include "gemm16_plan.h"
 
 namespace mgea {
 
@@ -363,10 +364,10 @@ int launch_gather_rows(const float* src, int ld_src, float* dst, int ld_dst, int
 int launch_lora_merge(float* w, const float* a, const float* b, int out_dim, int in_dim, int r, float scale,
                       hipStream_t st);
 
-// ---- bf16 perf-mode kernels (bf16.hip); bf16 buffers travel as void* ---------------------------
+// ---- 16-bit perf-mode kernels (gemm16.hip, attn16.hip, rows16.hip); bf16 / fp16 buffers travel as void* ------
 int launch_f32_to_bf16(const float* src, void* dst, int64_t n, hipStream_t st, int f16 = 0);   // f16: _Float16 instead of bf16
-// C = epi(A @ W^T + bias): epi 0 bias, 1 bias + GELU, 2 bias + residual(res, ld = ldc)
-// LayerNorm folded around the bf16 GEMMs (bf16.hip, epilogues 3-5 of launch_gemm_bf16; persistent 256 x 256 kernel only).
+// C = epi(A @ W^T + bias), epi = a BEPI_* of gemm16_plan.h: 0 bias, 1 bias + GELU, 2 bias + residual(res, ld = ldc)
+// LayerNorm folded around the 16-bit GEMMs (gemm16.hip, epilogues 3-5 of launch_gemm_bf16; persistent 256 x 256 kernel only).
 //   epi 3 / 4 (LNFOLD / +GELU): A = RAW rows, W = W diag(gamma) in bf16, c1[n] = sum_k W'[n, k], bias slot = c2 = b + W beta;
 //                               rowstat = (mean, rstd) of the A rows, [M][2]; out = rstd (A W'^T - mean c1) + c2
 //   epi 5 (RES_LN): out = A W^T + bias + LayerNorm(res row) with the residual's rowstat / ln_g / ln_b (an already normalised
@@ -374,16 +375,17 @@ int launch_f32_to_bf16(const float* src, void* dst, int64_t n, hipStream_t st, i
 //                   sum of squared deviations from the tile's own mean) of every output row per 256-column tile, [M][N / 256][2],
 //                   from which launch_ln_rowstat makes the next (mean, rstd).
 struct BfEpiLn { const float* rowstat; const float* c1; const float* ln_g; const float* ln_b; float* stats_out; };
-// What a launch_gemm_bf16 call ran (optional out-parameter; the engines count these for mgea_bert_stats): kernel 0 = the
-// register-staged 128 x 128 kernel, 1 = a ring kernel, 2 = the persistent phase-interleaved 256 x 256 kernel, 3 = the two-workgroups-per-CU
-// 256 x 128 kernel (switch bf16_gemm_tile = 5 only); half_tiles = 1 when the persistent
-// kernel cuts the tiles left over after its full rounds into two 128-row halves (bf16.hip, "HALF-TILE TAIL").
-// reverse (IN): ask the persistent kernel to walk its tiles from the end of every XCD's run (switch bf16_gemm_reverse; for a GEMM whose A
-// operand is the previous kernel's large output: see the kernel).
-struct GemmBf16Info { int kernel; int half_tiles; int reverse; };
+// What a launch_gemm_bf16 call ran, from its plan (optional out-parameter; the engines count these for mgea_bert_stats): kernel = the
+// G16_* family (0 the register-staged 128 x 128 kernel, 1 a ring kernel, 2 the persistent phase-interleaved 256 x 256 kernel, 3 the
+// two-workgroups-per-CU 256 x 128 kernel, switch bf16_gemm_tile = 5 only); half_tiles = 1 when the persistent kernel cuts the tiles
+// left over after its full rounds into two 128-row halves (gemm16.hip, "HALF-TILE TAIL").
+struct GemmBf16Info { int kernel; int half_tiles; };
+// f16 != 0: _Float16 operands / outputs (persistent kernel, epilogues 3 / 4 / 5, and 6 = fp32 output).  reverse != 0: ask the persistent
+// kernel to walk its tiles from the end of every XCD's run (switch bf16_gemm_reverse; for a GEMM whose A operand is the previous
+// kernel's large output: see the kernel).
 int launch_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res, void* C,
                      int ldc, int M, int N, int K, int epi, hipStream_t st, GemmBf16Info* info = nullptr, const BfEpiLn* ln = nullptr,
-                     int f16 = 0);   // f16 != 0: _Float16 operands / outputs (persistent kernel, epilogues 3 / 4 / 5, and 6 = fp32 output)
+                     int f16 = 0, int reverse = 0);
 // true when launch_gemm_bf16 would run this shape on the persistent 256 x 256 kernel (the only one with epilogues 3-5)
 bool gemm_bf16_is_persistent(int M, int N, int K);
 int launch_ln_rowstat(const float* part, float* rowstat, int M, int n_part, int C, float eps, hipStream_t st);
@@ -403,7 +405,7 @@ struct KvPages { KvPool pool; int layer; const int32_t* page_table; int max_page
 int launch_attn_bf16(const void* qkv, const int32_t* mask, void* out, int B, int T, int H, int dh, hipStream_t st, int f16 = 0,
                      const KvPages* pages = nullptr, const int32_t* cu = nullptr);
 
-// fp16 big-batch prefill of the decoder (bf16.hip): embedding rows as fp16 + their (mean, rstd); K | V of fp16 qkv rows -> fp16 KV pages
+// fp16 big-batch prefill of the decoder (rows16.hip): embedding rows as fp16 + their (mean, rstd); K | V of fp16 qkv rows -> fp16 KV pages
 int launch_dec_embed_f16(const int32_t* ids, const int32_t* lens, const int32_t* ctx_len, const float* tok_emb, const float* pos_emb,
                          void* x, float* rowstat, int32_t* mask_out, float eps, int B, int T, int C, int vocab, int pos_rows,
                          int absolute_pos, int32_t* err_flag, hipStream_t st);

@@ -776,7 +776,7 @@ int run_prefill16(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int 
     const float *id_g = p.ident + p.rows * 2, *id_b = id_g + C;
     PROF(PC_ROWOP, launch_dec_embed_f16(ids, lens, h->ctx_len, h->w(T_TOK), h->w(T_POS), xc, p.rowstat, lens ? p.mask : nullptr, c.ln_eps, B, T,
                                         C, V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
-    // K | V of the real tokens reach the fp16 KV pages from inside the attention kernel of their layer (bf16.hip: it has those rows in LDS
+    // K | V of the real tokens reach the fp16 KV pages from inside the attention kernel of their layer (attn16.hip: it has those rows in LDS
     // anyway; round 3 ran a scatter kernel per layer that re-read them from the qkv buffer, on a side stream under the attention).  Only a
     // last block that stops at its K | V (kv_only_last: no attention runs) still uses the scatter kernel.
     for (int l = 0; l < c.n_layer; ++l) {
@@ -785,12 +785,12 @@ int run_prefill16(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int 
             // the logits are dropped (run_blocks): of the last block only K | V -- rows C.. of the stacked projection -- then its scatter
             const BfEpiLn qk{p.rowstat, h->p16_vec(l, 0) + C, nullptr, nullptr, nullptr};
             PROF(PC_GEMM, launch_gemm_bf16(xc, C, (const char*)h->p16_w(4 * l + 0) + (int64_t)C * C * 2, C, h->p16_vec(l, 1) + C, nullptr,
-                                           (char*)p.qkv + (int64_t)C * 2, 3 * C, M, 2 * C, C, 3, st, nullptr, &qk, 1));
+                                           (char*)p.qkv + (int64_t)C * 2, 3 * C, M, 2 * C, C, BEPI_LNFOLD, st, nullptr, &qk, 1));
             PROF(PC_ROWOP, launch_kv_scatter_f16(p.qkv, h->kv, l, h->page_table, h->max_pages, h->ctx_len, lens, B, T, C, st));
             break;
         }
         const BfEpiLn q{p.rowstat, h->p16_vec(l, 0), nullptr, nullptr, nullptr};
-        PROF(PC_GEMM, launch_gemm_bf16(xc, C, h->p16_w(4 * l + 0), C, h->p16_vec(l, 1), nullptr, p.qkv, 3 * C, M, 3 * C, C, 3, st, nullptr, &q, 1));
+        PROF(PC_GEMM, launch_gemm_bf16(xc, C, h->p16_w(4 * l + 0), C, h->p16_vec(l, 1), nullptr, p.qkv, 3 * C, M, 3 * C, C, BEPI_LNFOLD, st, nullptr, &q, 1));
         const KvPages pages{h->kv, l, h->page_table, h->max_pages};
         if (tune(TUNE_DECODER_PREFILL16_PAGES)) {
             PROF(PC_ATTN_DENSE, launch_attn_bf16(p.qkv, lens ? p.mask : nullptr, p.att, B, T, c.n_head, h->dh, st, 1, &pages));
@@ -799,17 +799,17 @@ int run_prefill16(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int 
             PROF(PC_ATTN_DENSE, launch_attn_bf16(p.qkv, lens ? p.mask : nullptr, p.att, B, T, c.n_head, h->dh, st, 1));
         }
         const BfEpiLn o{p.ident, nullptr, id_g, id_b, p.stats_part};
-        PROF(PC_GEMM, launch_gemm_bf16(p.att, C, h->p16_w(4 * l + 1), C, h->lw(l, L_OUTB), xc, xo, C, M, C, C, 5, st, nullptr, &o, 1));
+        PROF(PC_GEMM, launch_gemm_bf16(p.att, C, h->p16_w(4 * l + 1), C, h->lw(l, L_OUTB), xc, xo, C, M, C, C, BEPI_RES_LN, st, nullptr, &o, 1));
         PROF(PC_ROWOP, launch_ln_rowstat(p.stats_part, p.rowstat, M, npart, C, c.ln_eps, st));
         const BfEpiLn f1{p.rowstat, h->p16_vec(l, 2), nullptr, nullptr, nullptr};
-        PROF(PC_GEMM, launch_gemm_bf16(xo, C, h->p16_w(4 * l + 2), C, h->p16_vec(l, 3), nullptr, p.hid, F, M, F, C, 4, st, nullptr, &f1, 1));
+        PROF(PC_GEMM, launch_gemm_bf16(xo, C, h->p16_w(4 * l + 2), C, h->p16_vec(l, 3), nullptr, p.hid, F, M, F, C, BEPI_LNFOLD_GELU, st, nullptr, &f1, 1));
         const BfEpiLn f2{p.ident, nullptr, id_g, id_b, last ? nullptr : p.stats_part};
-        GemmBf16Info rv{0, 0, 1};                            // reads FC1's big output: walk the tiles backwards (bf16.hip)
-        PROF(PC_GEMM, launch_gemm_bf16(p.hid, F, h->p16_w(4 * l + 3), F, h->lw(l, L_FC2B), xo, xc, C, M, C, F, 5, st, &rv, &f2, 1));
+        // reads FC1's big output: walk the tiles backwards (reverse = 1; gemm16.hip)
+        PROF(PC_GEMM, launch_gemm_bf16(p.hid, F, h->p16_w(4 * l + 3), F, h->lw(l, L_FC2B), xo, xc, C, M, C, F, BEPI_RES_LN, st, nullptr, &f2, 1, 1));
         if (!last) PROF(PC_ROWOP, launch_ln_rowstat(p.stats_part, p.rowstat, M, npart, C, c.ln_eps, st));
     }
     if (logits_out)
-        PROF(PC_GEMM, launch_gemm_bf16(xc, C, h->p16_w(4 * c.n_layer), C, h->head_b(), nullptr, logits_out, V, M, V, C, 6, st, nullptr, nullptr, 1));
+        PROF(PC_GEMM, launch_gemm_bf16(xc, C, h->p16_w(4 * c.n_layer), C, h->head_b(), nullptr, logits_out, V, M, V, C, BEPI_BIAS_F32, st, nullptr, nullptr, 1));
     h->n.prefill16_forwards += 1;
     return MGEA_OK;
 }

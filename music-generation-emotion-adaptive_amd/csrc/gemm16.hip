@@ -1,93 +1,20 @@
-// bf16 "perf mode" kernels for the prefill-only DistilBERT path (BASELINE.json configs[1]: bf16,
-// B=256, S=128): bf16 storage for weights and activations, fp32 accumulation in the MFMAs, fp32
-// LayerNorm / softmax / GELU math.  Parity mode stays fp32 (gemm_f32.hip, attn_dense.hip); these
-// kernels are validated against the oracle run on bf16-rounded weights (tests/test_gpu_bf16.py).
-//
-// * gemm_bf16_nt_kernel: C[M,N] = epi(A[M,K] @ W[N,K]^T + bias), v_mfma_f32_16x16x32_bf16,
-//   128x128x64 tiles, 4 waves (2x2, 64x64 per wave), LDS tiles [row][8 x 16 B] with the 16-B chunk
-//   XOR-swizzled by row&7 (conflict-free ds_write_b128 staging and ds_read_b128 fragments),
-//   register-staged double buffering (next tile's global loads fly under this tile's MFMAs), XCD-aware
-//   tile order, "swapped" MFMA so a lane owns 4 consecutive output columns (8-byte bf16 stores).
-// * attn_bf16_kernel: persistent, LDS-DMA double-buffered flash attention over a packed bf16 qkv buffer with an optional key
-//   mask; S^T = K Q^T keeps the query on lane&15, so the softmax is in-lane + two permlane swaps and the fp32 accumulators,
-//   converted to bf16, ARE the B operand of O^T = V^T P^T (k-permutation shared by V^T, which is read with ds_read_b64_tr_b16).
-// * layernorm / embedding kernels: bf16 in/out, fp32 statistics.
+// The 16-bit GEMMs C[M, N] = epi(A[M, K] @ W[N, K]^T + bias) of the perf modes: bf16 for DistilBERT (BASELINE.json configs[1]: B = 256,
+// S = 128), fp16 for the decoder's big-batch prefill.  16-bit storage, fp32 accumulation in the MFMAs, fp32 epilogue math; validated
+// against the oracle on rounded weights (tests/test_gpu_bf16.py, tests/test_gpu_f16.py) and family by family on exact integer operands
+// (tests/test_gpu_gemm16_plan.py).  Four kernel families, chosen by plan_gemm16 (gemm16_plan.h) and launched at the end of this file:
+// * gemm_bf16_nt_kernel (G16_SMALL): v_mfma_f32_16x16x32_bf16, 128x128x64 tiles, 4 waves (2x2, 64x64 per wave), LDS tiles
+//   [row][8 x 16 B] with the 16-B chunk XOR-swizzled by row&7 (conflict-free ds_write_b128 staging and ds_read_b128 fragments),
+//   register-staged double buffering (next tile's global loads fly under this tile's MFMAs), XCD-aware tile order, "swapped" MFMA so
+//   a lane owns 4 consecutive output columns (8-byte bf16 stores).
+// * gemm_bf16_glds_kernel (G16_RING): operands HBM/L2 -> LDS by LDS-DMA, 128 x 128 / 256 x 128 / 256 x 256 tiles.
+// * gemm_bf16_ph_kernel (G16_PERSISTENT): one workgroup per CU, phase-interleaved 256 x 256 tiles, the only one with the
+//   folded-LayerNorm epilogues and fp16 operands; with the stamp / ablation macros of the tools build (tools/build_stamps.sh).
+// * gemm16_duo_kernel (G16_DUO): two independent 256 x 128 workgroups per CU (switch bf16_gemm_tile = 5).
 #include <stdlib.h>
 
-#include "common.h"
+#include "x16.h"
 
 namespace mgea {
-
-typedef __bf16 bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void f32_to_bf16_kernel(const float* __restrict__ src, T* __restrict__ dst, int64_t n) {
-    typedef T t4 __attribute__((ext_vector_type(4)));
-    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i + 3 < n) {
-        const float4 v = ld4(src + i);
-        t4 o = {(T)v.x, (T)v.y, (T)v.z, (T)v.w};
-        *reinterpret_cast<t4*>(dst + i) = o;
-    } else {
-        for (int64_t j = i; j < n; ++j) dst[j] = (T)src[j];
-    }
-}
-int launch_f32_to_bf16(const float* src, void* dst, int64_t n, hipStream_t st, int f16) {
-    if (f16) hipLaunchKernelGGL(f32_to_bf16_kernel<_Float16>, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, st, src, (_Float16*)dst, n);
-    else     hipLaunchKernelGGL(f32_to_bf16_kernel<bf16_t>, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, st, src, (bf16_t*)dst, n);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-enum { BEPI_BIAS = 0, BEPI_BIAS_GELU = 1, BEPI_BIAS_RES = 2,
-       // LayerNorm folded around the GEMMs (persistent 256 x 256 kernel only; see BfEpiLn in common.h):
-       BEPI_LNFOLD = 3,        // out = rstd_row (A W'^T - mean_row c1) + c2         (A = raw rows, W' = W diag(gamma), c2 in the bias slot)
-       BEPI_LNFOLD_GELU = 4,   // ... then GELU
-       BEPI_RES_LN = 5,        // out = A W^T + bias + LN(res rows) (LayerNorm of the residual applied on the way in), + row statistics of out
-       BEPI_BIAS_F32 = 6 };    // out = A W^T + bias written as fp32 [M, ldc floats] (the decoder's LM head: N = vocab need only be a multiple of 4)
-
-// erf-GELU for bf16 outputs with ONE transcendental.  With a = |x|: gelu(x) = max(x, 0) - 0.5 a erfc(a / sqrt 2), and
-// erfc(a / sqrt 2) = 2^q(a) where q = log2(erfcx) - (a^2 / 2) log2 e is smooth: a degree-5 polynomial (weighted least squares on
-// [0, 6.5], fitted and checked in fp32 against scipy's erf: |gelu error| < 1.5e-5 on [-12, 12], far below the 2^-9 rounding of the
-// bf16 result; beyond 6.5 the clamped tail is < 2^-30).  11 instructions per element, v_exp_f32 the only quarter-rate one.  History:
-// A&S 7.1.26 with a full-precision division and libm-style exp cost ~40 (14 us of a 40 us FC1 tile round); A&S 7.1.25 on
-// v_rcp_f32 + v_exp_f32 12 with two transcendentals, still 28 of FC1's 169 us (measured by switching GELU off).
-#define MGEA_GELU_D0 -1.585257735e-05f
-#define MGEA_GELU_D1 -1.150631181e+00f
-#define MGEA_GELU_D2 -4.612153958e-01f
-#define MGEA_GELU_D3 -4.992833406e-02f
-#define MGEA_GELU_D4 6.105210696e-03f
-#define MGEA_GELU_D5 -3.249367875e-04f
-#define MGEA_GELU_AMAX 6.505382387f
-__device__ __forceinline__ float gelu_fast(float x) {
-    const float a = fminf(fabsf(x), MGEA_GELU_AMAX);
-    float q = fmaf(MGEA_GELU_D5, a, MGEA_GELU_D4);
-    q = fmaf(q, a, MGEA_GELU_D3);
-    q = fmaf(q, a, MGEA_GELU_D2);
-    q = fmaf(q, a, MGEA_GELU_D1);
-    q = fmaf(q, a, MGEA_GELU_D0);
-    return fmaf(-0.5f * a, __builtin_amdgcn_exp2f(q), fmaxf(x, 0.f));
-}
-// Two elements with packed fp32 arithmetic (v_pk_fma_f32 / v_pk_mul_f32: two results per instruction).  For epilogues only --
-// beside MFMAs packed fp32 is slower than scalar (MI355X_MICROARCH.md).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
-    const f32x2 a = {fminf(fabsf(x[0]), MGEA_GELU_AMAX), fminf(fabsf(x[1]), MGEA_GELU_AMAX)};
-    f32x2 q = __builtin_elementwise_fma((f32x2){MGEA_GELU_D5, MGEA_GELU_D5}, a, (f32x2){MGEA_GELU_D4, MGEA_GELU_D4});
-    q = __builtin_elementwise_fma(q, a, (f32x2){MGEA_GELU_D3, MGEA_GELU_D3});
-    q = __builtin_elementwise_fma(q, a, (f32x2){MGEA_GELU_D2, MGEA_GELU_D2});
-    q = __builtin_elementwise_fma(q, a, (f32x2){MGEA_GELU_D1, MGEA_GELU_D1});
-    q = __builtin_elementwise_fma(q, a, (f32x2){MGEA_GELU_D0, MGEA_GELU_D0});
-    const f32x2 e = {__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])};
-    const f32x2 pos = {fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)};
-    return __builtin_elementwise_fma(a * -0.5f, e, pos);
-}
 
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(const bf16_t* __restrict__ A, int lda,
@@ -356,57 +283,6 @@ __global__ __launch_bounds__(256 * WMW) void gemm_bf16_glds_kernel(const bf16_t*
 //            waits until ITS DMAs of tile u+1 have landed -- vmcnt(6): only the three half-tiles issued in phases 4u+2, 4u+3
 //            may still be in flight -- at the end of interval 8u+7 (waves 0-3: end of C(4u+3); waves 4-7: end of L(4u+3)),
 //            and the barrier that ends that interval publishes them to every wave.
-// One 1 KiB LDS-DMA piece (64 lanes x 16 B, LDS destination = wave-uniform byte address + 16 * lane) issued from inline
-// asm, so that hipcc does not see it: seen through the builtin, ROCm 7.2 puts an s_waitcnt vmcnt(0) in front of the next
-// ds_read of every phase (it cannot tell which LDS bytes a pending DMA writes) and the pipeline drains.  Hidden, none of the
-// compiler's waits refer to it; every wait for these pieces is one of the hand-counted vmcnt below (this kernel has no other
-// vector-memory instruction between its prologue and its epilogue).  M0 is compiler-reserved: saved and restored in the same
-// statement (cdna_hip_programming.md section 5.7).
-__device__ __forceinline__ void glds16_hidden(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr) : "memory");
-}
-
-// Same, with a wave-uniform 64-bit base in SGPRs and a 32-bit byte offset per lane (no 64-bit vector address arithmetic).
-__device__ __forceinline__ void glds16_hidden_s(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
-
-typedef unsigned long long u64x1;
-
-// The two 16-bit storage types of the perf modes (bf16: DistilBERT, MGEA_DTYPE_BF16; fp16: the decoder's big-batch prefill,
-// MGEA_DTYPE_F16) behind one set of kernels: vector types, the 16 x 16 x 32 MFMA, and a packed pair (one dword) <-> two fp32.
-template <typename T> struct X16;
-template <> struct X16<__bf16> {
-    static constexpr bool is_bf16 = true;
-    static constexpr float attn_rescale_log2 = 16.0f;   // flash attention, deferred rescale: p = 2^((s - m) kexp) <= 2^16 is far inside bf16's range
-    typedef bf16x8 v8; typedef bf16x4 v4; typedef bf16x2 v2;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x2 unpack(unsigned u) { return (f32x2){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
-};
-template <> struct X16<_Float16> {
-    static constexpr bool is_bf16 = false;
-    static constexpr float attn_rescale_log2 = 15.0f;   // p <= 2^15: fp16 rounds every p from 65520 up to +inf (its largest finite value is 65504)
-    typedef h16x8 v8; typedef h16x4 v4; typedef _Float16 v2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x2 unpack(unsigned u) {
-        const v2 h = __builtin_bit_cast(v2, u);
-        return (f32x2){(float)h[0], (float)h[1]};
-    }
-};
-
-// Sum over the 32 lanes of a half wave (lanes 32 h .. 32 h + 31), result in all of them: four DPP row rotations (VALU speed) give
-// the 16-lane sums, one ds_bpermute adds the neighbouring row.  (Five __shfl_xor steps = five trips through the LDS pipeline per
-// value: 160 of them per tile made the statistics cost more than the LayerNorm kernel they replace.)
-__device__ __forceinline__ float half_wave_sum(float v) {
-#define MGEA_ROR_ADD(n) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + (n), 0xf, 0xf, false))
-    MGEA_ROR_ADD(1); MGEA_ROR_ADD(2); MGEA_ROR_ADD(4); MGEA_ROR_ADD(8);
-#undef MGEA_ROR_ADD
-    return v + __shfl_xor(v, 16, 64);
-}
 
 // In-kernel time stamps of the persistent GEMM (cdna_hip_programming.md section 7), compiled ONLY into the tools build
 // (tools/build_stamps.sh: -DMGEA_PH_STAMPS, a separate .so that tools/gemm_bf16_stamps.py loads); the product library has none of it.
@@ -1162,29 +1038,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(const T* __restrict__
     }
 }
 
-template <int EPI, typename T, int PH>
-static int launch_ph2(const T* a, int lda, const T* w, int ldw, const float* bias, const T* r, T* c, int ldc, int M,
-                      int N, int K, hipStream_t st, GemmBf16Info* info, const BfEpiLn* lnp) {
-    const int shmem = 2 * (256 + 256) * 128 + 32768;   // two operand stages + the C stage: all 160 KB of the CU's LDS
-    DeviceInfo di;
-    MGEA_TRY(device_info(&di));
-    static uint64_t attr_done = 0;                      // per instantiation, one bit per device
-    MGEA_TRY(set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_bf16_ph_kernel<EPI, T, PH>), shmem, di.dev, &attr_done));
-    const int tm = ceil_div(M, 256), tn = ceil_div(N, 256), n_tiles = tm * tn;
-    const int n_cu = di.n_cu / 8 * 8;
-    const int grid = (int)round_up(n_tiles < n_cu ? n_tiles : n_cu, 8);   // one persistent workgroup per CU (160 KB of LDS each)
-    const int tail = (tune(TUNE_BF16_GEMM_TAIL) & 3) | ((info && info->reverse && tune(TUNE_BF16_GEMM_REVERSE)) ? 4 : 0);
-    if (info) {   // what the kernel will do with the tiles left after the full rounds (the same arithmetic as in the kernel, XCD run 0)
-        const int wg_x = grid / 8, per_x = (n_tiles + 7) / 8 < n_tiles ? (n_tiles + 7) / 8 : n_tiles;
-        const int rem = per_x - per_x / wg_x * wg_x;
-        info->kernel = 2;
-        info->half_tiles = ((tail & 3) != 0 && rem > 0 && 2 * rem <= wg_x) ? 1 : 0;
-    }
-    hipLaunchKernelGGL((gemm_bf16_ph_kernel<EPI, T, PH>), dim3(grid), dim3(512), shmem, st, a, lda, w, ldw, bias, r, c, ldc, M, N, K, tn, n_tiles,
-                       tail, lnp ? *lnp : BfEpiLn{nullptr, nullptr, nullptr, nullptr, nullptr});
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
 // ------------------------------------------------------------------------------------------
 // TWO WORKGROUPS PER CU ("duo"): 256 x 128 of C per workgroup of 4 waves (2 x 2, the same 128 x 64 per wave and the same fragment
 // layout as the 256 x 256 kernel), 80 KB of LDS each, so that a CU holds two of them and they run INDEPENDENTLY: while one is in
@@ -1329,916 +1182,73 @@ __global__ __launch_bounds__(256, 2) void gemm16_duo_kernel(const T* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// the instantiation a plan names ({nullptr, nullptr}: none)
 template <int EPI, typename T>
-static int launch_duo(const T* a, int lda, const T* w, int ldw, const float* bias, const T* r, T* c, int ldc, int M,
-                      int N, int K, hipStream_t st) {
-    const int shmem = 2 * 256 * 128 + 128 * 128;        // 80 KB: two workgroups per CU
-    DeviceInfo di;
-    MGEA_TRY(device_info(&di));
-    static uint64_t attr_done = 0;
-    MGEA_TRY(set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm16_duo_kernel<EPI, T>), shmem, di.dev, &attr_done));
-    const int tm = ceil_div(M, 256), tn = ceil_div(N, 128), n_tiles = tm * tn;
-    const int slots = 2 * (di.n_cu / 8 * 8);
-    const int grid = (int)round_up(n_tiles < slots ? n_tiles : slots, 8);
-    hipLaunchKernelGGL((gemm16_duo_kernel<EPI, T>), dim3(grid), dim3(256), shmem, st, a, lda, w, ldw, bias, r, c, ldc, M, N, K, tn, n_tiles);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
+static KernelRef gemm16_ph(int phases) {
+    if (phases == 1) return kernel_ref<&gemm_bf16_ph_kernel<EPI, T, 1>>();
+    if (phases == 2) return kernel_ref<&gemm_bf16_ph_kernel<EPI, T, 2>>();
+    return kernel_ref<&gemm_bf16_ph_kernel<EPI, T, 4>>();
 }
-
-template <int EPI, typename T = bf16_t>
-static int launch_ph(const T* a, int lda, const T* w, int ldw, const float* bias, const T* r, T* c, int ldc, int M,
-                     int N, int K, hipStream_t st, GemmBf16Info* info, const BfEpiLn* lnp = nullptr) {
-    const int ph = tune(TUNE_BF16_GEMM_PHASES);
-    if (ph == 1) return launch_ph2<EPI, T, 1>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-    if (ph == 2) return launch_ph2<EPI, T, 2>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-    return launch_ph2<EPI, T, 4>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-}
-
-template <int EPI, int NT, int WMW>
-static int launch_glds(const bf16_t* a, int lda, const bf16_t* w, int ldw, const float* bias, const bf16_t* r, bf16_t* c,
-                       int ldc, int M, int N, int K, hipStream_t st) {
-    constexpr int BM = 128 * WMW, BN = 64 * NT;
-    constexpr int NS = (NT == 2 && WMW == 2) ? 3 : 2;
-    constexpr size_t ring = (size_t)NS * (BM + BN) * 128, stage_c = (size_t)BM * (BN * 2 + 16);
-    const int shmem = (int)(ring > stage_c ? ring : stage_c);      // 64 KB .. 144 KB of the 160 KB LDS
-    DeviceInfo di;
-    MGEA_TRY(device_info(&di));
-    static uint64_t attr_done = 0;   // one per instantiation
-    MGEA_TRY(set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_bf16_glds_kernel<EPI, NT, WMW>), shmem, di.dev, &attr_done));
-    const int tm = ceil_div(M, BM), tn = ceil_div(N, BN);
-    hipLaunchKernelGGL((gemm_bf16_glds_kernel<EPI, NT, WMW>), dim3(tm * tn), dim3(256 * WMW), shmem, st, a, lda, w, ldw, bias,
-                       r, c, ldc, M, N, K, tn);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// which kernel runs a shape: 0 the register-staged 128 x 128 kernel, 1 a ring kernel, 2 the persistent phase-interleaved 256 x 256 kernel
-static int pick_bf16_kernel(int M, int N, int K, int ldc) {
-    if (!(M >= 512 && N >= 128 && N % 8 == 0 && ldc % 8 == 0 && K % 64 == 0) || tune(TUNE_BF16_GEMM_SMALL)) return 0;
-    const int force = tune(TUNE_BF16_GEMM_TILE);
-    const int64_t blocks256 = (int64_t)ceil_div(M, 256) * ceil_div(N, 256);
-    // 256-wide N tiles unless that leaves too few workgroups for 256 CUs.  (From 192 tiles on, round 4: the packed DistilBERT batch -- 18.8 k
-    // real tokens of [256, 128] -- is 74 x 3 = 222 tiles at N = 768, and only the persistent kernel has the folded-LayerNorm epilogues.)
-    return (force == 4 || (force == 0 && N % 256 == 0 && blocks256 >= 192)) ? 2 : 1;
-}
-
 template <int EPI>
-static int launch_glds_pick(const bf16_t* a, int lda, const bf16_t* w, int ldw, const float* bias, const bf16_t* r, bf16_t* c,
-                            int ldc, int M, int N, int K, hipStream_t st, GemmBf16Info* info) {
-    const int force = tune(TUNE_BF16_GEMM_TILE);   // 1: 128x128 / 2: 256x128 / 3: 256x256 ring kernels (tools/gemm_bf16_bench.py)
-    if (force == 5 && EPI != BEPI_BIAS_RES && K % 64 == 0 && N % 8 == 0) {   // (prototype switch: the two-workgroups-per-CU kernel)
-        if (info) { info->kernel = 3; info->half_tiles = 0; }
-        return launch_duo<EPI, bf16_t>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st);
+static KernelRef gemm16_epi(const Gemm16Plan& p) {
+    if constexpr (EPI == BEPI_BIAS_F32) return p.f16 ? gemm16_ph<EPI, _Float16>(p.phases) : KernelRef{};
+    else if constexpr (EPI >= BEPI_LNFOLD) return p.f16 ? gemm16_ph<EPI, _Float16>(p.phases) : gemm16_ph<EPI, bf16_t>(p.phases);
+    else {
+        if (p.f16) return KernelRef{};
+        switch (p.family) {
+            case G16_SMALL: return kernel_ref<&gemm_bf16_nt_kernel<EPI>>();
+            case G16_PERSISTENT: return gemm16_ph<EPI, bf16_t>(p.phases);
+            case G16_DUO: return kernel_ref<&gemm16_duo_kernel<EPI, bf16_t>>();   // (never planned with BEPI_BIAS_RES)
+        }
+        if (p.nt == 4) return kernel_ref<&gemm_bf16_glds_kernel<EPI, 4, 2>>();
+        return p.wmw == 1 ? kernel_ref<&gemm_bf16_glds_kernel<EPI, 2, 1>>() : kernel_ref<&gemm_bf16_glds_kernel<EPI, 2, 2>>();
     }
-    if (pick_bf16_kernel(M, N, K, ldc) == 2) return launch_ph<EPI>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info);
-    if (info) { info->kernel = 1; info->half_tiles = 0; }
-    if (force == 1) return launch_glds<EPI, 2, 1>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st);
-    if (force == 2) return launch_glds<EPI, 2, 2>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st);
-    if (force == 3) return launch_glds<EPI, 4, 2>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st);
-    const int64_t blocks256 = (int64_t)ceil_div(M, 256) * ceil_div(N, 256);
-    if (N % 256 == 0 && blocks256 >= 512) return launch_glds<EPI, 4, 2>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st);
-    return launch_glds<EPI, 2, 2>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st);
+}
+static KernelRef gemm16_kernel(const Gemm16Plan& p) {
+    switch (p.epi) {
+        case BEPI_BIAS: return gemm16_epi<BEPI_BIAS>(p);
+        case BEPI_BIAS_GELU: return gemm16_epi<BEPI_BIAS_GELU>(p);
+        case BEPI_BIAS_RES: return gemm16_epi<BEPI_BIAS_RES>(p);
+        case BEPI_LNFOLD: return gemm16_epi<BEPI_LNFOLD>(p);
+        case BEPI_LNFOLD_GELU: return gemm16_epi<BEPI_LNFOLD_GELU>(p);
+        case BEPI_RES_LN: return gemm16_epi<BEPI_RES_LN>(p);
+        case BEPI_BIAS_F32: return gemm16_epi<BEPI_BIAS_F32>(p);
+    }
+    return KernelRef{};
 }
 
-bool gemm_bf16_is_persistent(int M, int N, int K) { return pick_bf16_kernel(M, N, K, 8) == 2; }
+static Gemm16Switches gemm16_switches() {
+    return Gemm16Switches{tune(TUNE_BF16_GEMM_TILE), tune(TUNE_BF16_GEMM_SMALL), tune(TUNE_BF16_GEMM_TAIL), tune(TUNE_BF16_GEMM_PHASES),
+                          tune(TUNE_BF16_GEMM_REVERSE)};
+}
 
-// fp16 operands (the decoder's big-batch prefill): the persistent kernel only, epilogues 3 / 4 / 5 and the fp32-output head (6)
-static int launch_gemm_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res, void* C, int ldc, int M, int N,
-                           int K, int epi, hipStream_t st, GemmBf16Info* info, const BfEpiLn* lnp) {
-    typedef _Float16 H;
-    const H *a = (const H*)A, *w = (const H*)W, *r = (const H*)res;
-    H* c = (H*)C;
-    MGEA_REQUIRE(M >= 512 && N >= 256 && (int64_t)ceil_div(M, 256) * ceil_div(N, 256) >= 8, MGEA_EINVAL,
-                 "fp16 gemm: M=%d N=%d below what the persistent kernel takes", M, N);
-    if (epi == BEPI_BIAS_F32) {
-        MGEA_REQUIRE(bias && N % 4 == 0 && ldc % 4 == 0, MGEA_EINVAL, "fp16 gemm: fp32-output epilogue needs a bias and N, ldc multiples of 4");
-        return launch_ph<BEPI_BIAS_F32, H>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-    }
-    MGEA_REQUIRE(epi >= BEPI_LNFOLD && epi <= BEPI_RES_LN && lnp && bias && N % 256 == 0 && ldc % 8 == 0, MGEA_EINVAL,
-                 "fp16 gemm: epilogue %d / shape not built (3, 4, 5 with N %% 256 == 0, or 6)", epi);
-    if (epi == BEPI_RES_LN) {
-        MGEA_REQUIRE(res && lnp->rowstat && lnp->ln_g && lnp->ln_b, MGEA_EINVAL, "fp16 gemm: RES_LN without residual / row statistics / gamma / beta");
-        return launch_ph<BEPI_RES_LN, H>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-    }
-    MGEA_REQUIRE(lnp->rowstat && lnp->c1, MGEA_EINVAL, "fp16 gemm: LNFOLD without row statistics / c1");
-    if (epi == BEPI_LNFOLD) return launch_ph<BEPI_LNFOLD, H>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-    return launch_ph<BEPI_LNFOLD_GELU, H>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
+bool gemm_bf16_is_persistent(int M, int N, int K) {
+    DeviceInfo di;
+    if (device_info(&di) != MGEA_OK) return false;
+    const Gemm16Call c{M, N, K, 8, 8, 8, BEPI_BIAS};
+    Gemm16Plan p;
+    return plan_gemm16(c, gemm16_switches(), di.n_cu, &p, nullptr) == 0 && p.family == G16_PERSISTENT;
 }
 
 int launch_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res, void* C,
-                     int ldc, int M, int N, int K, int epi, hipStream_t st, GemmBf16Info* info, const BfEpiLn* lnp, int f16) {
-    MGEA_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 4 == 0 && lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0,
-                 MGEA_EINVAL, "bf16 gemm: bad shape M=%d N=%d K=%d (K %% 64, N %% 4)", M, N, K);
-    if (f16) return launch_gemm_f16(A, lda, W, ldw, bias, res, C, ldc, M, N, K, epi, st, info, lnp);
-    if (epi >= BEPI_LNFOLD) {   // LayerNorm folded around the GEMM: the persistent kernel only
-        MGEA_REQUIRE(epi <= BEPI_RES_LN && lnp && bias, MGEA_EINVAL, "bf16 gemm: epilogue %d needs its LayerNorm operands and a bias / c2 vector", epi);
-        MGEA_REQUIRE(gemm_bf16_is_persistent(M, N, K) && ldc % 8 == 0 && N % 256 == 0, MGEA_EINVAL,
-                     "bf16 gemm: epilogue %d exists on the persistent 256 x 256 kernel only (M=%d N=%d K=%d)", epi, M, N, K);
-        const bf16_t *a = (const bf16_t*)A, *w = (const bf16_t*)W, *r = (const bf16_t*)res;
-        bf16_t* c = (bf16_t*)C;
-        if (epi == BEPI_RES_LN) {
-            MGEA_REQUIRE(res && lnp->rowstat && lnp->ln_g && lnp->ln_b, MGEA_EINVAL,
-                         "bf16 gemm: RES_LN without residual / row statistics / gamma / beta (identity tables for a normalised residual)");
-            return launch_ph<BEPI_RES_LN>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-        }
-        MGEA_REQUIRE(lnp->rowstat && lnp->c1, MGEA_EINVAL, "bf16 gemm: LNFOLD without row statistics / c1");
-        if (epi == BEPI_LNFOLD) return launch_ph<BEPI_LNFOLD>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-        return launch_ph<BEPI_LNFOLD_GELU>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info, lnp);
-    }
-    if (pick_bf16_kernel(M, N, K, ldc) != 0) {
-        const bf16_t *a = (const bf16_t*)A, *w = (const bf16_t*)W, *r = (const bf16_t*)res;
-        bf16_t* c = (bf16_t*)C;
-        if (epi == BEPI_BIAS) return launch_glds_pick<BEPI_BIAS>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info);
-        if (epi == BEPI_BIAS_GELU) return launch_glds_pick<BEPI_BIAS_GELU>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info);
-        if (epi == BEPI_BIAS_RES && res) return launch_glds_pick<BEPI_BIAS_RES>(a, lda, w, ldw, bias, r, c, ldc, M, N, K, st, info);
-    }
-    if (info) { info->kernel = 0; info->half_tiles = 0; }
-    const int tm = ceil_div(M, 128), tn = ceil_div(N, 128);
-    dim3 grid(tm * tn), block(256);
-    const bf16_t *a = (const bf16_t*)A, *w = (const bf16_t*)W, *r = (const bf16_t*)res;
-    bf16_t* c = (bf16_t*)C;
-    switch (epi) {
-        case BEPI_BIAS: hipLaunchKernelGGL(gemm_bf16_nt_kernel<BEPI_BIAS>, grid, block, 0, st, a, lda, w, ldw, bias, r, c, ldc, M, N, K, tn); break;
-        case BEPI_BIAS_GELU: hipLaunchKernelGGL(gemm_bf16_nt_kernel<BEPI_BIAS_GELU>, grid, block, 0, st, a, lda, w, ldw, bias, r, c, ldc, M, N, K, tn); break;
-        case BEPI_BIAS_RES:
-            MGEA_REQUIRE(res, MGEA_EINVAL, "bf16 gemm: residual epilogue without residual");
-            hipLaunchKernelGGL(gemm_bf16_nt_kernel<BEPI_BIAS_RES>, grid, block, 0, st, a, lda, w, ldw, bias, r, c, ldc, M, N, K, tn);
-            break;
-        default: MGEA_REQUIRE(false, MGEA_EINVAL, "bf16 gemm: bad epilogue %d", epi);
-    }
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Helpers of the folded-LayerNorm pipeline (BfEpiLn).
-// (mean, rstd) per row from the per-tile (sum, M2 about the tile's own mean) pairs the RES_LN epilogue left, each over C / n_part
-// columns: mean = sum of sums / C, M2 = sum_i M2_i + cnt sum_i (mean_i - mean)^2 (the exact pairwise merge), in double.
-// A launch of its own (5 us): deriving the statistics inside the consumers instead (8-16 more loaded values live per lane in their
-// epilogues) pushed 20-50 registers of the persistent kernel to scratch and cost 0.45 ms per forward.
-__global__ void ln_rowstat_kernel(const float* __restrict__ part, float* __restrict__ rowstat, int M, int n_part, int C, float eps) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= M) return;
-    const double cnt = (double)C / n_part;
-    double s1 = 0.0;
-    for (int i = 0; i < n_part; ++i) s1 += part[((int64_t)row * n_part + i) * 2];
-    const double mean = s1 / C;
-    double m2 = 0.0;
-    for (int i = 0; i < n_part; ++i) {
-        const double d = part[((int64_t)row * n_part + i) * 2] / cnt - mean;
-        m2 += part[((int64_t)row * n_part + i) * 2 + 1] + cnt * d * d;
-    }
-    rowstat[(int64_t)row * 2] = (float)mean;
-    rowstat[(int64_t)row * 2 + 1] = (float)(1.0 / sqrt(m2 / C + (double)eps));
-}
-int launch_ln_rowstat(const float* part, float* rowstat, int M, int n_part, int C, float eps, hipStream_t st) {
-    hipLaunchKernelGGL(ln_rowstat_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, st, part, rowstat, M, n_part, C, eps);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// W' = bf16(W diag(gamma)), c1[n] = sum_k W'[n, k] (of the ROUNDED folded weights: the epilogue subtracts exactly what the MFMAs
-// added), c2[n] = b[n] + sum_k W[n, k] beta[k].  One workgroup per output row n.
-template <typename T>
-__global__ __launch_bounds__(256) void fold_ln_weights_bf16_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
-                                                                  const float* __restrict__ beta, const float* __restrict__ b,
-                                                                  T* __restrict__ Wf, float* __restrict__ c1,
-                                                                  float* __restrict__ c2, int K) {
-    const int64_t n = blockIdx.x;
-    float s1 = 0.f, s2 = 0.f;
-    for (int k = threadIdx.x; k < K; k += 256) {
-        const float w = W[n * K + k];
-        const T wf = (T)(w * gamma[k]);
-        Wf[n * K + k] = wf;
-        s1 += (float)wf;
-        s2 = fmaf(w, beta[k], s2);
-    }
-    __shared__ float r1[4], r2[4];
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        c1[n] = (r1[0] + r1[1]) + (r1[2] + r1[3]);
-        c2[n] = b[n] + ((r2[0] + r2[1]) + (r2[2] + r2[3]));
-    }
-}
-int launch_fold_ln_weights_bf16(const float* W, const float* gamma, const float* beta, const float* b, void* Wf, float* c1, float* c2,
-                                int N, int K, hipStream_t st, int f16) {
-    if (f16) hipLaunchKernelGGL(fold_ln_weights_bf16_kernel<_Float16>, dim3(N), dim3(256), 0, st, W, gamma, beta, b, (_Float16*)Wf, c1, c2, K);
-    else     hipLaunchKernelGGL(fold_ln_weights_bf16_kernel<bf16_t>, dim3(N), dim3(256), 0, st, W, gamma, beta, b, (bf16_t*)Wf, c1, c2, K);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// CLS rows (row b * S) of the RAW last-layer output -> LayerNorm with the row's (mean, rstd) -> fp32 [B, D]
-__global__ void gather_cls_ln_bf16_kernel(const bf16_t* __restrict__ h, const float* __restrict__ rowstat, const float* __restrict__ g,
-                                          const float* __restrict__ be, float* __restrict__ out, int S, int D, const int32_t* __restrict__ cu) {
-    const int64_t row = cu ? (int64_t)cu[blockIdx.x] : (int64_t)blockIdx.x * S;      // the [CLS] row of sequence b (packed input: its first row)
-    const float mean = rowstat[row * 2], rstd = rowstat[row * 2 + 1];
-    for (int d = threadIdx.x; d < D; d += blockDim.x) out[(int64_t)blockIdx.x * D + d] = fmaf(((float)h[row * D + d] - mean) * rstd, g[d], be[d]);
-}
-int launch_gather_cls_ln_bf16(const void* h, const float* rowstat, const float* g, const float* be, float* out, int B, int S, int D,
-                              hipStream_t st, const int32_t* cu) {
-    hipLaunchKernelGGL(gather_cls_ln_bf16_kernel, dim3(B), dim3(256), 0, st, (const bf16_t*)h, rowstat, g, be, out, S, D, cu);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// LayerNorm over bf16 rows (fp32 statistics), in place allowed.  A wave owns 4 rows and requests all of them (and the affine
-// vectors) before the first reduction: 8-16 loads of 16 bytes in flight per lane instead of 2, four independent reduction chains.
-// (One row per wave ran at 4.2 TB/s of read + write on [32768, 768]: every wave sat through a load, two dependent wave reductions
-// and a second round trip for w / b before its only stores.)
-template <int NCHL>   // 16-byte chunks per lane and row: C <= 512 * NCHL
-__global__ __launch_bounds__(256) void layernorm_bf16_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ b, bf16_t* __restrict__ y, int M,
-                                                            int C, float eps) {
-    constexpr int RW = 4;
-    const int lane = threadIdx.x & 63;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RW;
-    if (row0 >= M) return;
-    const int nch = C >> 3;  // 16-byte chunks per row
-    bf16x8 t[RW][NCHL];
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        const int64_t row = row0 + r < M ? row0 + r : M - 1;     // clamped: loaded, never stored
-#pragma unroll
-        for (int i = 0; i < NCHL; ++i) {
-            const int ch = lane + i * 64;
-            t[r][i] = *reinterpret_cast<const bf16x8*>(x + row * C + (ch < nch ? ch : 0) * 8);
-        }
-    }
-    float4 wv[NCHL][2], bv[NCHL][2];
-#pragma unroll
-    for (int i = 0; i < NCHL; ++i) {
-        const int ch = lane + i * 64 < nch ? lane + i * 64 : 0;
-        wv[i][0] = ld4(w + ch * 8); wv[i][1] = ld4(w + ch * 8 + 4);
-        bv[i][0] = ld4(b + ch * 8); bv[i][1] = ld4(b + ch * 8 + 4);
-    }
-    const float inv_c = 1.0f / (float)C;
-    float mean[RW], rstd[RW];
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCHL; ++i)
-            if (lane + i * 64 < nch)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) s += (float)t[r][i][j];
-        mean[r] = s;
-    }
-#pragma unroll
-    for (int r = 0; r < RW; ++r) mean[r] = wave_sum(mean[r]) * inv_c;
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCHL; ++i)
-            if (lane + i * 64 < nch)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float d = (float)t[r][i][j] - mean[r]; q += d * d; }
-        rstd[r] = q;
-    }
-#pragma unroll
-    for (int r = 0; r < RW; ++r) rstd[r] = 1.0f / sqrtf(wave_sum(rstd[r]) * inv_c + eps);
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        if (row0 + r >= M) break;
-#pragma unroll
-        for (int i = 0; i < NCHL; ++i) {
-            const int ch = lane + i * 64;
-            if (ch < nch) {
-                const float ww[8] = {wv[i][0].x, wv[i][0].y, wv[i][0].z, wv[i][0].w, wv[i][1].x, wv[i][1].y, wv[i][1].z, wv[i][1].w};
-                const float bb[8] = {bv[i][0].x, bv[i][0].y, bv[i][0].z, bv[i][0].w, bv[i][1].x, bv[i][1].y, bv[i][1].z, bv[i][1].w};
-                bf16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (bf16_t)(((float)t[r][i][j] - mean[r]) * rstd[r] * ww[j] + bb[j]);
-                *reinterpret_cast<bf16x8*>(y + (row0 + r) * C + ch * 8) = o;
-            }
-        }
-    }
-}
-int launch_layernorm_bf16(const void* x, const float* w, const float* b, void* y, int M, int C, float eps, hipStream_t st) {
-    MGEA_REQUIRE(C % 8 == 0 && C <= 2048, MGEA_EINVAL, "bf16 layernorm: C=%d must be a multiple of 8 and <= 2048", C);
-    const dim3 grid(ceil_div(M, 16));
-    if (C <= 1024) hipLaunchKernelGGL(layernorm_bf16_kernel<2>, grid, dim3(256), 0, st, (const bf16_t*)x, w, b, (bf16_t*)y, M, C, eps);
-    else           hipLaunchKernelGGL(layernorm_bf16_kernel<4>, grid, dim3(256), 0, st, (const bf16_t*)x, w, b, (bf16_t*)y, M, C, eps);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// h[m] = LN(word[ids[m]] + pos[t]) -> bf16 (fp32 tables)
-__global__ __launch_bounds__(256) void bert_embed_ln_bf16_kernel(const int32_t* __restrict__ ids, const float* __restrict__ word,
-                                                                const float* __restrict__ pos, const float* __restrict__ lnw,
-                                                                const float* __restrict__ lnb, float eps,
-                                                                bf16_t* __restrict__ h, int M, int S, int D, int vocab,
-                                                                int32_t* __restrict__ err_flag, const int32_t* __restrict__ pos_ids) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const int t = pos_ids ? pos_ids[row] : (int)(row % S);      // packed input carries each row's position in its sequence
-    int id = ids[row];
-    if ((id < 0 || id >= vocab) && err_flag && lane == 0) atomicOr(err_flag, 1);   // clamped + reported (mgea_bert_error_flags)
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    const int nf4 = D >> 2;
-    float4 v[8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int f = lane + i * 64;
-        if (f < nf4) {
-            v[i] = add4(ld4(word + (int64_t)id * D + f * 4), ld4(pos + (int64_t)t * D + f * 4));
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-        if (lane + i * 64 < nf4) {
-            const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int f = lane + i * 64;
-        if (f < nf4) {
-            const float4 ww = ld4(lnw + f * 4), bb = ld4(lnb + f * 4);
-            bf16x4 o = {(bf16_t)((v[i].x - mean) * rstd * ww.x + bb.x), (bf16_t)((v[i].y - mean) * rstd * ww.y + bb.y),
-                        (bf16_t)((v[i].z - mean) * rstd * ww.z + bb.z), (bf16_t)((v[i].w - mean) * rstd * ww.w + bb.w)};
-            *reinterpret_cast<bf16x4*>(h + row * D + f * 4) = o;
-        }
-    }
-}
-int launch_bert_embed_ln_bf16(const int32_t* ids, const float* word, const float* pos, const float* lnw, const float* lnb,
-                              float eps, void* h, int B, int S, int D, int vocab, hipStream_t st, int32_t* err_flag, const int32_t* pos_ids) {
-    MGEA_REQUIRE(D % 4 == 0 && D <= 2048, MGEA_EINVAL, "bf16 embed: dim=%d must be a multiple of 4 and <= 2048", D);
-    // (packed input: B = the number of rows, S = 1)
-    hipLaunchKernelGGL(bert_embed_ln_bf16_kernel, dim3(ceil_div(B * S, 4)), dim3(256), 0, st, ids, word, pos, lnw, lnb, eps,
-                       (bf16_t*)h, B * S, S, D, vocab, err_flag, pos_ids);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// CLS rows (row b*S) of a bf16 [B*S, D] matrix -> fp32 [B, D] for the small fp32 classifier head
-__global__ void gather_cls_bf16_kernel(const bf16_t* __restrict__ h, float* __restrict__ out, int S, int D, const int32_t* __restrict__ cu) {
-    const int64_t b = blockIdx.x, row = cu ? (int64_t)cu[b] : b * S;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) out[b * D + d] = (float)h[row * D + d];
-}
-int launch_gather_cls_bf16(const void* h, float* out, int B, int S, int D, hipStream_t st, const int32_t* cu) {
-    hipLaunchKernelGGL(gather_cls_bf16_kernel, dim3(B), dim3(256), 0, st, (const bf16_t*)h, out, S, D, cu);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Reductions over the four lanes c, c + 16, c + 32, c + 48 (the lanes that share a query in the K Q^T accumulator) with gfx950's
-// v_permlane32_swap / v_permlane16_swap: VALU instructions, no trip through the LDS pipeline like ds_bpermute (__shfl_xor), which
-// matters at 2 waves per SIMD where nothing hides that latency.  swap(x, x) leaves [lo, lo] / [hi, hi] (32) or [r0 r0 r2 r2] / [r1 r1
-// r3 r3] (16) in the two results, so one max of the pair is the xor-32 / xor-16 butterfly step.
-// max(a, b) as the median of (a, b, +inf): ONE v_med3_f32.  fmaxf() on values that come out of an MFMA or a lane swap costs two extra
-// instructions each -- hipcc canonicalises both inputs first (v_max_f32 x, x, x: IEEE maxNum semantics for signalling NaNs), 16 + 8 of them
-// per 64-key tile of the flash attention.  No score is a NaN here; -inf (masked keys) orders as usual.
-__device__ __forceinline__ float max_nc(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, INFINITY); }
-__device__ __forceinline__ float quad_max(float x) {
-    const auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    const float m = max_nc(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-    return max_nc(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
-// ------------------------------------------------------------------------------------------
-// Flash attention, bf16 in/out, head_dim 64.  PERSISTENT and software-pipelined: 2 workgroups per CU walk the work items
-// (b, h, block of 128 queries); 4 waves x 32 queries (two 16-query MFMA column blocks per wave, every V fragment read from LDS feeds
-// two MFMAs).  Keys are staged 128 at a time -- for the DistilBERT shape (T = 128) K and V of a (b, h) leave HBM exactly once --
-// by LDS-DMA into one of two 32 KB stages: the DMA of unit u + 1 is issued right after the barrier that opens unit u and flies under
-// u's MFMAs, softmax and output stores.  (Without it every workgroup of a round loads, computes and stores in step with all the
-// others: 54 us = 27 load + 16 + 11, the phases add up.)  The DMA is issued from inline asm (glds16_hidden) so that hipcc does not
-// drain vmcnt in front of every LDS read; the only wait for it is the explicit vmcnt(0) at the top of a unit, where nothing younger
-// is in flight.
-//   K image [key][8 x 16 B], chunk ^= key & 7            : row reads (ds_read_b128) for the A operand of K Q^T, conflict-free
-//   V image [key][8 x 16 B], chunk ^= ((key >> 1) & 3) * 2: read with ds_read_b64_tr_b16, the hardware transpose (guide T10): lanes
-//      16g..16g+15 fetch a block of 4 keys x 16 d and lane c gets column d = 16 dt + c of the 4 keys -- the V^T A-operand of the
-//      P V product without a transposing write pass.  The 8 rows a 32-lane half touches land on 8 different 8-bank groups.
-//   Both swizzles are applied on the GLOBAL side of the DMA (a lane picks which 16 bytes of its key's row it fetches); the LDS side
-//   of a DMA is lane-linear.  EXEC is all ones at every transposed read (uniform control flow only).
-// S^T = K Q^T keeps a query's scores lane-local (lane = query, registers = keys 16 kt + 4 g + r); the k index of the P V product is
-// permuted to match (k = 8 g + j  <->  key 32 p + 16 (j >> 2) + 4 g + (j & 3)), so P goes from accumulator to operand in registers.
-// The output tile goes through the (then free) K image so that every store instruction writes complete 128-byte rows.
-// NW waves x 32 queries per workgroup, keys staged KB = 32 NW at a time: <4, 128> (two workgroups per CU) for short sequences -- DistilBERT: K and V
-// of a (batch, head) leave HBM exactly once --, <8, 256> (one workgroup per CU, 2 x 64 KB stages) for long ones, where the per-unit costs (the
-// wait for the DMA, the barrier, 8 LDS-DMA pieces per wave: 1.7 of 4.3 us per unit by in-kernel stamps at 1024 keys) are spread over four
-// 64-key tiles instead of two.
-template <typename E, int NW, int PIPE>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void attn_bf16_kernel(const E* __restrict__ qkv, const int32_t* __restrict__ mask, E* __restrict__ out, int T, int H,
-                      int n_items, int nqb, float scale, KvPages pg, const int32_t* __restrict__ cu) {
-    typedef typename X16<E>::v8 bf16x8;   // (the names below were written for bf16; E may be _Float16)
-    typedef typename X16<E>::v4 bf16x4;
-    typedef E bf16_t;
-    constexpr int DH = 64, KB = 32 * NW, QPB = 32 * NW;           // keys per stage, queries per workgroup
-    constexpr int STAGE = KB * 16;                                // 16-byte chunks: K image [KB][8], then V image [KB][8]
-    constexpr int VW = KB / 64;                                   // 64-bit validity words per stage
-    extern __shared__ __attribute__((aligned(16))) float4 lds[];  // [2][STAGE], then [2][VW] 64-bit validity words
-    unsigned long long* sValid = reinterpret_cast<unsigned long long*>(lds + 2 * STAGE);
-    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) float4*)lds;
-
-    const int C = H * DH;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 15, g = lane >> 4;
-    const int nkb = (T + KB - 1) / KB;
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-    // DMA of one unit (item, key block) into a stage: wave w moves keys 32 w .. 32 w + 31 of K and of V (8 instructions of 1 KB)
-    const int d_key = lane >> 3, d_ch = lane & 7;                 // this lane's slot inside an 8-key piece
-    const unsigned dk_off = 2u * C + 16u * (d_ch ^ d_key);                              // K: chunk ^ (key & 7), key & 7 == d_key
-    const unsigned dv_off = 4u * C + 16u * (d_ch ^ (((d_key >> 1) & 3) << 1));          // V: chunk ^ 2 ((key >> 1) & 3)
-    // PACKED ("varlen") INPUT, cu != NULL (round 4, DistilBERT on unpadded batches): the rows of sequence b are cu[b] .. cu[b + 1] - 1 of one
-    // [sum of lengths, 3 C] buffer, no padding rows and no key mask; every sequence fits one query block and one key stage (host check:
-    // max length <= KB, so nqb == nkb == 1 and an item is a (sequence, head)).  T then only sizes the grid; a sequence's own length
-    // bounds its key tiles, so a 20-token prompt computes one 64-key tile where the padded form computes the batch's maximum.
-    auto seq_rows = [&](int bb, int& row0, int& Tb) {            // wave-uniform (scalar loads)
-        if (cu) { row0 = cu[bb]; Tb = cu[bb + 1] - row0; } else { row0 = bb * T; Tb = T; }
-    };
-    struct ItemBase { const bf16_t* p; int Tb; };
-    auto item_base = [&](int it) {                                // first qkv row of the item's (batch, head): wave-uniform, stays in SGPRs
-        const int bh = it / nqb, bb = bh / H, hh = bh - bb * H;
-        int row0, Tb;
-        seq_rows(bb, row0, Tb);
-        return ItemBase{qkv + (int64_t)row0 * 3 * C + hh * DH, Tb};
-    };
-    auto issue_part = [&](const ItemBase& ib, int kbi, int st, int i0, int i1) {   // pieces i0 .. i1 - 1 of this wave's four (K and V of 8 keys each)
-        const bf16_t* base = ib.p;
-#pragma unroll
-        for (int i = i0; i < i1; ++i) {
-            const int piece = wave * 4 + i, key = piece * 8 + d_key;
-            int kr = kbi * KB + key; kr = kr < ib.Tb ? kr : ib.Tb - 1;
-            const unsigned row = (unsigned)kr * (unsigned)(6 * C);    // bytes; a sequence's rows span < 4 GB (checked on the host)
-            const unsigned dst = lds_base + (unsigned)(st * STAGE + piece * 64) * 16u;
-            glds16_hidden_s(base, row + dk_off, dst);
-            glds16_hidden_s(base, row + dv_off, dst + (unsigned)(KB * 8) * 16u);
-        }
-    };
-    auto issue = [&](int it, int kbi, int st) { issue_part(item_base(it), kbi, st, 0, 4); };
-    auto mask_of = [&](int it, int kbi) -> int {                  // validity of key kbi * KB + tid (the first KB / 64 waves)
-        const int bh = it / nqb, bb = bh / H;
-        const int kidx = kbi * KB + tid;
-        int row0, Tb;
-        seq_rows(bb, row0, Tb);
-        int ok = (tid < KB && kidx < Tb) ? 1 : 0;
-        if (ok && mask) ok = mask[(int64_t)bb * T + kidx];        // (packed input has no mask: host check)
-        return ok;
-    };
-    bf16x8 qn[2][2];                                              // next item's raw Q fragments
-    auto load_q = [&](int it) {
-        const int bh = it / nqb, qb = it - bh * nqb, bb = bh / H, hh = bh - bb * H;
-        int row0, Tb;
-        seq_rows(bb, row0, Tb);
-#pragma unroll
-        for (int mq = 0; mq < 2; ++mq) {
-            int qr = qb * QPB + wave * 32 + mq * 16 + c; qr = qr < Tb ? qr : Tb - 1;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                qn[mq][ks] = *reinterpret_cast<const bf16x8*>(qkv + ((int64_t)row0 + qr) * 3 * C + hh * DH + ks * 32 + 8 * g);
-        }
-    };
-    // transposed-read offsets (bf16 elements) of this lane inside a 16-key group of the V image, one per 16-d block:
-    // row 4 g + (c >> 2) of the group, 16-byte chunk (2 dt + ((c & 3) >> 1)) ^ swizzle(row), half (c & 1)
-    int v_off[4];
-    {
-        const int vrow = 4 * g + (c >> 2), sw = ((vrow >> 1) & 3) << 1;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) v_off[dt] = vrow * 64 + (((2 * dt + ((c & 3) >> 1)) ^ sw) * 8) + 4 * (c & 1);
-    }
-
-    // The output rows of an item are held in registers and stored one unit later, behind the next DMA issue: a store issued at the
-    // end of a unit would be waited for (vmcnt(0), loads and stores share the counter) at the top of the next one with nothing to hide
-    // its latency behind -- 2-3 us per item.
-    float4 ov0, ov1, ov2, ov3;                                    // (scalars, not an array: an array captured by a lambda went to scratch)
-    bf16_t* optr = nullptr;                                       // row of ov0; ov<i> is 8 i rows further; nullptr: nothing held
-    int orow = 0, oT = 0;                                         // query index of ov0 within the sequence, and that sequence's length
-#define MGEA_FLUSH_OUT()                                                                               \
-    if (optr) {                                                                                        \
-        if (orow < oT)      *reinterpret_cast<float4*>(optr) = ov0;                                    \
-        if (orow + 8 < oT)  *reinterpret_cast<float4*>(optr + (int64_t)8 * C) = ov1;                   \
-        if (orow + 16 < oT) *reinterpret_cast<float4*>(optr + (int64_t)16 * C) = ov2;                  \
-        if (orow + 24 < oT) *reinterpret_cast<float4*>(optr + (int64_t)24 * C) = ov3;                  \
-    }
-    int item = blockIdx.x, kb = 0, stage = 0, mk = 0;
-    if (item < n_items) { issue(item, 0, 0); mk = mask_of(item, 0); load_q(item); }
-    bf16x8 qf[2][2];
-    f32x4 oacc[2][4], lacc[2];                                    // lacc: row sums of P, from an all-ones A operand (every row equal)
-    float mx[2];                                                  // running maximum of the RAW scores q . k
-    const float kexp = scale * 1.4426950408889634f;               // exp(scale * (s - m)) = 2^((s - m) * kexp)
-    bf16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = (bf16_t)1.0f;
-    [[maybe_unused]] int un = 0;                                   // (tools-only stamps: unit counter)
-    while (item < n_items) {
-        PH_STAMP(un * 8 + 0);
-        // unit (item, kb) has landed: nothing younger than its DMA, its mask word and (kb == 0) its Q rows is in flight here
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PH_STAMP(un * 8 + 1);
-        // Tell hipcc that the prefetched registers are complete on every path.  It does not read the wait above, and a load it still
-        // believes pending makes it wait (by ITS count, which does not include the hidden DMAs: in effect vmcnt(0)) before those
-        // registers are written again -- right after the next unit's DMA was issued, which would serialise the pipeline.
-        asm volatile("" : "+v"(qn[0][0]), "+v"(qn[0][1]), "+v"(qn[1][0]), "+v"(qn[1][1]), "+v"(mk));
-        int row0cur, Tcur;                                        // the current item's sequence: first row, length
-        seq_rows((item / nqb) / H, row0cur, Tcur);
-        if (tid < KB) {
-            const unsigned long long bal = __ballot(mk != 0);
-            if (lane == 0) sValid[stage * VW + wave] = bal;
-        }
-        __syncthreads();
-        PH_STAMP(un * 8 + 2);
-        if (kb == 0) {
-#pragma unroll
-            for (int mq = 0; mq < 2; ++mq) {
-                mx[mq] = -INFINITY;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) oacc[mq][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                lacc[mq] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                qf[mq][0] = qn[mq][0];                               // unscaled: 1/sqrt(dh) is folded into the exponent's constant
-                qf[mq][1] = qn[mq][1];
-            }
-        }
-        // K | V OF THE REAL TOKENS -> fp16 KV PAGES (decoder prefill, round 4; replaces kv_scatter_f16_kernel, which re-read the K | V columns
-        // of the qkv buffer from HBM -- 134 MB in, 134 MB out per layer at [64, 1024]).  The stage that has just landed holds exactly
-        // those rows: ONE of the (batch, head)'s items writes them out (below), each wave the 32 keys it moved in -- K as
-        // [d-group][token][8 halves] (lane = token: 512 contiguous bytes per d-group and instruction), V as whole 128-byte rows.
-        // Only keys with their validity bit set (t < lens[b], t < T) are cached, at position t (the cache is empty: run_prefill16).
-        if constexpr (sizeof(E) == 2 && !X16<E>::is_bf16) {
-            if (pg.pool.base) {
-                const int bh_u = item / nqb, qb_u = item - bh_u * nqb;
-                if (qb_u == kb) {     // (nqb == nkb: queries per item = keys per stage.  The item of query block kb writes key block kb -- every
-                                      //  workgroup a quarter of the stages; with query block 0 writing all of them a quarter of the workgroups
-                                      //  did all the writing and the launch waited for them: 4.64 ms per cache fill against 4.37 with the scatter kernel)
-                    const int bb = bh_u / H, hh = bh_u - bb * H;
-                    const int tok0 = kb * KB + wave * 32;                                   // 32-aligned: one page
-                    const unsigned long long vw = sValid[stage * VW + (wave >> 1)];
-                    const unsigned vbits = (unsigned)(vw >> (32 * (wave & 1)));             // validity of this wave's 32 keys
-                    if (tok0 < Tcur && (tok0 >> 6) < pg.max_pages) {
-                        const int phys = pg.page_table[bb * pg.max_pages + (tok0 >> 6)];
-                        const int64_t pe = pg.pool.page_elems();
-                        _Float16* kpage = static_cast<_Float16*>(pg.pool.base) + pg.layer * pg.pool.layer_stride + ((int64_t)(phys * 2) * H + hh) * pe;
-                        _Float16* vpage = kpage + (int64_t)H * pe;
-                        const int slot0 = tok0 & 63;
-                        const float4* sKs = lds + stage * STAGE;
-                        const float4* sVs = sKs + KB * 8;
-                        {   // K: lane -> (token lane & 31, d-group 2 i + (lane >> 5))
-                            const int tk = lane & 31, key = wave * 32 + tk;
-                            const bool ok = (vbits >> tk) & 1u;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int j = 2 * i + (lane >> 5);
-                                const float4 v = sKs[key * 8 + (j ^ (key & 7))];
-                                if (ok) *reinterpret_cast<float4*>(kpage + ((int64_t)j * 64 + slot0 + tk) * 8) = v;
-                            }
-                        }
-                        {   // V: lane -> (token 8 i + (lane >> 3), 16-byte chunk lane & 7): 1 KB of consecutive bytes per instruction
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int tk = 8 * i + (lane >> 3), key = wave * 32 + tk, ch = lane & 7;
-                                const float4 v = sVs[key * 8 + (ch ^ (((key >> 1) & 3) << 1))];
-                                if ((vbits >> tk) & 1u) *reinterpret_cast<float4*>(vpage + ((int64_t)(slot0 + tk) * 64 + ch * 8)) = v;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        int nitem = item, nkbi = kb + 1;
-        if (nkbi == nkb) { nitem = item + gridDim.x; nkbi = 0; }
-        // PIPE, full stage: the next unit's 8 LDS-DMA pieces are issued inside the tile loop below, a quarter per tile, instead of as a
-        // burst here (stamps, round 3: 0.85 us per unit during which all 8 waves only issue and the matrix pipe idles)
-        const bool dma_in_loop = PIPE && NW == 8 && (kb + 1) * KB <= Tcur;
-        const ItemBase nbase = item_base(nitem < n_items ? nitem : item);   // (two integer divisions: once per unit, not once per piece)
-        if (nitem < n_items) {                                    // the other stage was last read before the barrier above
-            if (!dma_in_loop) issue(nitem, nkbi, stage ^ 1);
-            mk = mask_of(nitem, nkbi);
-            if (nkbi == 0) load_q(nitem);
-        }
-        MGEA_FLUSH_OUT();
-        optr = nullptr;
-        PH_STAMP(un * 8 + 3);
-
-        const float4* sK = lds + stage * STAGE;
-        const bf16_t* sV = reinterpret_cast<const bf16_t*>(lds + stage * STAGE + KB * 8);
-        // ---- one 64-key tile in three pieces (lambdas, so that the two loop forms below share them) ----
-        // S^T = K Q^T of keys t0 .. t0 + 63 against the wave's 32 queries: two independent chains per key tile (both query blocks)
-        auto qk_tile = [&](int t0, f32x4 (&sc)[2][4]) {
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) { sc[0][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; sc[1][kt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    const int key = t0 + kt * 16 + c;
-                    const float4 kv = sK[key * 8 + ((ks * 4 + g) ^ (key & 7))];
-                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(&kv);
-                    sc[0][kt] = X16<E>::mfma(kf, qf[0][ks], sc[0][kt]);
-                    sc[1][kt] = X16<E>::mfma(kf, qf[1][ks], sc[1][kt]);
-                }
-        };
-        // key mask, tile maximum, and the (rare) move of the scaling reference with its accumulator rescale
-        auto tile_max = [&](int t0, f32x4 (&sc)[2][4], bool first_tile) {
-            const unsigned long long vm = sValid[stage * VW + (t0 >> 6)];
-            const unsigned vm_lo = __builtin_amdgcn_readfirstlane((unsigned)vm), vm_hi = __builtin_amdgcn_readfirstlane((unsigned)(vm >> 32));
-            const bool all_valid = (vm_lo & vm_hi) == 0xffffffffu;                         // wave-uniform
-            const unsigned vb_lo = vm_lo >> (4 * g), vb_hi = vm_hi >> (4 * g);              // bit 16 (kt & 1) + r of word kt >> 1
-            float tmax[2];
-#pragma unroll
-            for (int mq = 0; mq < 2; ++mq) {
-                tmax[mq] = -INFINITY;
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    if (!all_valid) {
-                        const unsigned w = (kt >> 1) ? vb_hi : vb_lo;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) sc[mq][kt][r] = ((w >> (16 * (kt & 1) + r)) & 1u) ? sc[mq][kt][r] : -INFINITY;
-                    }
-                    const float m4 = max_nc(max_nc(sc[mq][kt][0], sc[mq][kt][1]), max_nc(sc[mq][kt][2], sc[mq][kt][3]));
-                    tmax[mq] = kt == 0 ? m4 : max_nc(tmax[mq], m4);
-                }
-            }
-            tmax[0] = quad_max(tmax[0]);
-            tmax[1] = quad_max(tmax[1]);
-            // Deferred rescale (guide T13): the running maximum is only a scaling reference; P and the accumulators stay exact as long
-            // as one reference is used per row.  Keep the old one while no row of this wave outgrows it by more than 2^RESCALE_LOG2
-            // (X16<E>::attn_rescale_log2, a property of the element type: P is stored as E, so 2^RESCALE_LOG2 must stay finite in E --
-            // 2^16 for bf16, 2^15 for fp16, where 2^16 is +inf and made lacc inf and the output row NaN) -- the accumulator rescale and
-            // its exponential then run on the first tile of an item and on the rare tile that trips the threshold instead of on every tile.
-            constexpr float RESCALE_LOG2 = X16<E>::attn_rescale_log2;
-            bool grow = first_tile;
-            if (!first_tile) {
-                const bool g0 = (tmax[0] - mx[0]) * kexp > RESCALE_LOG2, g1 = (tmax[1] - mx[1]) * kexp > RESCALE_LOG2;   // -inf - -inf = NaN: false
-                grow = __any((g0 || g1) ? 1 : 0) != 0;                                                                  // wave-uniform
-            }
-            if (grow) {
-#pragma unroll
-                for (int mq = 0; mq < 2; ++mq) {
-                    const float mnew = fmaxf(mx[mq], tmax[mq]);
-                    if (!first_tile) {
-                        // alpha = 2^((m_old - m_new) kexp); rows that had no valid key so far carry zeros: any finite alpha will do
-                        const float alpha = (mx[mq] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mx[mq] - mnew) * kexp);
-#pragma unroll
-                        for (int dt = 0; dt < 4; ++dt) {
-                            oacc[mq][dt][0] *= alpha; oacc[mq][dt][1] *= alpha; oacc[mq][dt][2] *= alpha; oacc[mq][dt][3] *= alpha;
-                        }
-                        lacc[mq][0] *= alpha; lacc[mq][1] *= alpha; lacc[mq][2] *= alpha; lacc[mq][3] *= alpha;
-                    }
-                    mx[mq] = mnew;
-                }
-            }
-        };
-        // P = 2^((s - m) kexp) as the 16-bit operand (straight from the accumulator registers), its row sums, and O += P V
-        auto exp_half = [&](f32x4 (&sc)[2][4], bf16x8 (&pf)[2][2], int p) {
-#pragma unroll
-            for (int mq = 0; mq < 2; ++mq) {
-                const float nml = (mx[mq] == -INFINITY) ? 0.f : -mx[mq] * kexp;   // a row without a valid key yet: p = 2^(-inf) = 0
-#pragma unroll
-                for (int kt = 2 * p; kt < 2 * p + 2; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        pf[mq][p][(kt & 1) * 4 + r] = (bf16_t)__builtin_amdgcn_exp2f(fmaf(sc[mq][kt][r], kexp, nml));
-            }
-        };
-        auto pv_half = [&](int t0, bf16x8 (&pf)[2][2], int p) {
-            lacc[0] = X16<E>::mfma(ones, pf[0][p], lacc[0]);      // row sums of the 16-bit P the P V product actually uses
-            lacc[1] = X16<E>::mfma(ones, pf[1][p], lacc[1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const bf16_t* vb = sV + (t0 + 32 * p) * 64 + v_off[dt];
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vb));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vb + 16 * 64));
-                union { s16x4 s[2]; bf16x8 v; } u;
-                u.s[0] = lo; u.s[1] = hi;
-                oacc[0][dt] = X16<E>::mfma(u.v, pf[0][p], oacc[0][dt]);
-                oacc[1][dt] = X16<E>::mfma(u.v, pf[1][p], oacc[1][dt]);
-            }
-        };
-        if (PIPE && (kb + 1) * KB <= Tcur) {
-            // SOFTWARE-PIPELINED form for a full stage (round 4).  In the rolled loop below a tile is Q K^T (16 MFMAs), then ~190 vector
-            // instructions of softmax, then P V (20 MFMAs): matrix pipe and vector ALU take turns -- 576 + ~770 cycles per wave and
-            // tile, and the two waves of a SIMD, which run the same program between the same barriers, do it in lockstep (2,600 cycles
-            // per pair of tiles by in-kernel stamps, round 3: the SUM).  Here the stage's tiles are unrolled and the NEXT tile's
-            // Q K^T is issued between this tile's maximum and its exponentials (scores double-buffered, +32 registers), and P V of the
-            // first 32 keys runs under the exponentials of the other 32: the MFMAs of one tile sit in the shadow of the vector work of
-            // its neighbours, inside ONE wave's instruction stream (hipcc interleaves what is independent within a basic block).
-            constexpr int NT = KB / 64;
-            f32x4 sc[2][2][4];
-            qk_tile(0, sc[0]);
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                tile_max(64 * i, sc[i & 1], kb == 0 && i == 0);
-                if (dma_in_loop && nitem < n_items) issue_part(nbase, nkbi, stage ^ 1, i * 4 / NT, (i + 1) * 4 / NT);
-                bf16x8 pf[2][2];
-                if (i + 1 < NT) qk_tile(64 * (i + 1), sc[(i + 1) & 1]);
-                exp_half(sc[i & 1], pf, 0);
-                exp_half(sc[i & 1], pf, 1);
-                pv_half(64 * i, pf, 0);
-                pv_half(64 * i, pf, 1);
-            }
-        } else {
-#pragma unroll 1
-            for (int t0 = 0; t0 < KB && kb * KB + t0 < Tcur; t0 += 64) {   // workgroup-uniform bounds (packed input: this sequence's length)
-                f32x4 sc[2][4];                                   // both query blocks side by side: two independent dependency chains per wave
-                bf16x8 pf[2][2];                                  // [query block][32-key half]
-                qk_tile(t0, sc);
-                tile_max(t0, sc, kb == 0 && t0 == 0);
-                exp_half(sc, pf, 0);
-                exp_half(sc, pf, 1);
-                pv_half(t0, pf, 0);
-                pv_half(t0, pf, 1);
-            }
-        }
-
-        PH_STAMP(un * 8 + 4);
-        if (kb == nkb - 1) {
-            const int bh = item / nqb, qb = item - bh * nqb, bb = bh / H, hh = bh - bb * H;
-            __syncthreads();                                      // every wave is done with this stage's K image
-            bf16_t* so = reinterpret_cast<bf16_t*>(lds + stage * STAGE) + wave * (32 * 64);   // [32 queries][64 d], chunk ^= query & 7
-#pragma unroll
-            for (int mq = 0; mq < 2; ++mq) {
-                // 1 ulp, far below the bf16 output rounding; a row without ANY valid key (all-zero mask) has lacc == 0 and oacc == 0:
-                // it gets zeros, not rcp(0) * 0 = NaN (the reference's finfo.min mask would attend uniformly to padding there --
-                // an input the tokenizer never produces: [CLS] is always valid)
-                const float inv = lacc[mq][0] > 0.f ? __builtin_amdgcn_rcpf(lacc[mq][0]) : 0.f;
-                const int ql = mq * 16 + c;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    bf16x4 o = {(bf16_t)(oacc[mq][dt][0] * inv), (bf16_t)(oacc[mq][dt][1] * inv), (bf16_t)(oacc[mq][dt][2] * inv),
-                                (bf16_t)(oacc[mq][dt][3] * inv)};
-                    const int ch = (dt * 2 + (g >> 1)) ^ (ql & 7);
-                    *reinterpret_cast<bf16x4*>(so + ql * 64 + ch * 8 + 4 * (g & 1)) = o;
-                }
-            }
-            // a wave reads back only what it wrote itself: lane -> row (lane >> 3) + 8 i, 16-byte chunk lane & 7
-            {
-                const int ql = lane >> 3, ch = lane & 7;             // (8 i + ql) & 7 == ql
-                const bf16_t* sp = so + ql * 64 + ((ch ^ ql) * 8);
-                ov0 = *reinterpret_cast<const float4*>(sp);
-                ov1 = *reinterpret_cast<const float4*>(sp + 8 * 64);
-                ov2 = *reinterpret_cast<const float4*>(sp + 16 * 64);
-                ov3 = *reinterpret_cast<const float4*>(sp + 24 * 64);
-            }
-            orow = qb * QPB + wave * 32 + (lane >> 3);
-            oT = Tcur;
-            optr = out + ((int64_t)row0cur + orow) * C + hh * DH + (lane & 7) * 8;
-        }
-        item = nitem; kb = nkbi; stage ^= 1;
-        PH_STAMP(un * 8 + 5);
-        ++un;
-    }
-    MGEA_FLUSH_OUT();
-#undef MGEA_FLUSH_OUT
-}
-
-template <typename E, int NW, int PIPE>
-static int launch_attn16(const void* qkv, const int32_t* mask, void* out, int B, int T, int H, hipStream_t st, const KvPages& pg, const int32_t* cu) {
-    constexpr int QPB = 32 * NW, KB = 32 * NW;
-    const int nqb = ceil_div(T, QPB);
-    const int64_t n_items = (int64_t)B * H * nqb;
-    MGEA_REQUIRE(n_items < (1 << 30), MGEA_EINVAL, "16-bit attention: too many (batch, head, query block) items");
+                     int ldc, int M, int N, int K, int epi, hipStream_t st, GemmBf16Info* info, const BfEpiLn* lnp, int f16, int reverse) {
+    BfEpiLn ln = lnp ? *lnp : BfEpiLn{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const Gemm16Call c{M, N, K, lda, ldw, ldc, epi, f16 != 0, bias != nullptr, res != nullptr, ln.rowstat != nullptr, ln.c1 != nullptr,
+                       ln.ln_g != nullptr, ln.ln_b != nullptr, ln.stats_out != nullptr, reverse != 0};
     DeviceInfo di;
     MGEA_TRY(device_info(&di));
-    const int shmem = 2 * KB * 16 * 16 + 64;
-    static uint64_t attr_done = 0;                     // per instantiation
-    MGEA_TRY(set_max_dynamic_lds((const void*)attn_bf16_kernel<E, NW, PIPE>, shmem, di.dev, &attr_done));
-    const int per_cu = NW == 4 ? 2 : 1;
-    const int grid = (int)(n_items < per_cu * di.n_cu ? n_items : per_cu * di.n_cu);
-    hipLaunchKernelGGL((attn_bf16_kernel<E, NW, PIPE>), dim3(grid), dim3(64 * NW), shmem, st, (const E*)qkv, mask, (E*)out, T, H, (int)n_items, nqb,
-                       0.125f, pg, cu);
-    MGEA_CHECK_HIP(hipGetLastError());
+    Gemm16Plan p;
+    const char* why = "";
+    MGEA_REQUIRE(plan_gemm16(c, gemm16_switches(), di.n_cu, &p, &why) == 0, MGEA_EINVAL, "16-bit gemm M=%d N=%d K=%d ldc=%d epilogue %d%s: %s",
+                 M, N, K, ldc, epi, f16 ? " (fp16)" : "", why);
+    if (info) { info->kernel = p.family; info->half_tiles = p.half_tiles; }
+    const KernelRef k = gemm16_kernel(p);
+    MGEA_REQUIRE(k.fn, MGEA_EINVAL, "16-bit gemm: no kernel for plan family %d, epilogue %d", p.family, epi);
+    if (p.shmem) MGEA_TRY(set_max_dynamic_lds(k.fn, p.shmem, di.dev, k.lds_raised));
+    // one argument list for the four families: each kernel takes a prefix of it (small, ring: up to tiles_n; duo: n_tiles; persistent: all)
+    void* args[] = {&A, &lda, &W, &ldw, &bias, &res, &C, &ldc, &M, &N, &K, &p.tiles_n, &p.n_tiles, &p.tail_mode, &ln};
+    MGEA_CHECK_HIP(hipLaunchKernel(k.fn, dim3(p.grid), dim3(p.block), args, p.shmem, st));
     return MGEA_OK;
 }
-
-int launch_attn_bf16(const void* qkv, const int32_t* mask, void* out, int B, int T, int H, int dh, hipStream_t st, int f16, const KvPages* pages,
-                     const int32_t* cu) {
-    MGEA_REQUIRE(dh == 64, MGEA_EINVAL, "bf16 attention: head_dim %d not supported (64)", dh);
-    MGEA_REQUIRE(B > 0 && T > 0 && B <= 65535 && H <= 65535, MGEA_EINVAL, "bf16 attention: bad shape");
-    MGEA_REQUIRE((int64_t)T * 6 * H * dh < ((int64_t)1 << 32), MGEA_EINVAL, "bf16 attention: one sequence of qkv rows must span < 4 GB");
-    // long sequences: 256 queries / 256 keys per unit (switch attn16_wide: 0 never, 1 from 512 tokens (default), 2 always)
-    const int wide = tune(TUNE_ATTN16_WIDE);
-    bool w8 = wide == 2 || (wide == 1 && T >= 512);
-    if (cu) {   // packed input: T = the longest sequence, which must fit one query block / key stage of the form that runs it
-        MGEA_REQUIRE(!mask && T <= 256, MGEA_EINVAL, "16-bit attention over packed rows: no key mask, sequences of at most 256 tokens (got %d)", T);
-        w8 = T > 128;
-    }
-    // the wide form runs its full stages software-pipelined (round 4; switch attn16_pipe = 0: the rolled tile loop).  The 4-wave form keeps
-    // the rolled loop: at 128 keys it is memory-bound and the pipelined body spilled 31 registers (44 -> 54 us on [256, 128, 12 x 64])
-    const bool pipe = tune(TUNE_ATTN16_PIPE) != 0;
-    // (a static priority for waves 4..7 -- guide T5, static form -- on top of the pipelined body: 224.9 vs 227.0 us, nothing; not kept)
-    const KvPages none{};
-    const KvPages& pg = pages ? *pages : none;
-    if (f16) {
-        if (w8) return pipe ? launch_attn16<_Float16, 8, 1>(qkv, mask, out, B, T, H, st, pg, cu) : launch_attn16<_Float16, 8, 0>(qkv, mask, out, B, T, H, st, pg, cu);
-        return launch_attn16<_Float16, 4, 0>(qkv, mask, out, B, T, H, st, pg, cu);
-    }
-    MGEA_REQUIRE(!pg.pool.base, MGEA_EINVAL, "16-bit attention: KV pages are written by the fp16 instantiation only");
-    if (w8) return pipe ? launch_attn16<bf16_t, 8, 1>(qkv, mask, out, B, T, H, st, pg, cu) : launch_attn16<bf16_t, 8, 0>(qkv, mask, out, B, T, H, st, pg, cu);
-    return launch_attn16<bf16_t, 4, 0>(qkv, mask, out, B, T, H, st, pg, cu);
-}
-
-// ------------------------------------------------------------------------------------------
-// fp16 big-batch prefill of the decoder (MGEA_DTYPE_F16, decoder.hip: run_prefill16): the pre-LN GPT block on the kernels above with
-// _Float16 operands.  Three small kernels around them:
-// x[m] = f16(tok_emb[ids[m]] + pos_emb[pos]) and the (mean, rstd) of the ROUNDED row (what the folded-LayerNorm GEMM consumes);
-// rows with t >= lens[b] are zero rows with the identity statistics (0, 1).  One wave per row.
-__global__ __launch_bounds__(256) void dec_embed_f16_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens,
-                                                           const int32_t* __restrict__ ctx_len, const float* __restrict__ tok_emb,
-                                                           const float* __restrict__ pos_emb, _Float16* __restrict__ x,
-                                                           float* __restrict__ rowstat, int32_t* __restrict__ mask_out, float eps, int M,
-                                                           int T, int C, int vocab, int pos_rows, int absolute_pos,
-                                                           int32_t* __restrict__ err_flag) {
-    const int lane = threadIdx.x & 63;
-    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= M) return;
-    const int b = (int)(m / T), t = (int)(m % T);
-    const bool real = lens ? (t < lens[b]) : true;
-    int id = ids[m];
-    if (real && (id < 0 || id >= vocab) && err_flag && lane == 0) atomicOr(err_flag, 1);
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    int pos = t + ((absolute_pos && ctx_len) ? ctx_len[b] : 0);
-    pos = pos < pos_rows ? pos : pos_rows - 1;
-    const int nf4 = C >> 2;
-    float4 v[8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int f = lane + i * 64;
-        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (f < nf4 && real) {
-            const float4 e = add4(ld4(tok_emb + (int64_t)id * C + f * 4), ld4(pos_emb + (int64_t)pos * C + f * 4));
-            const h16x4 o = {(_Float16)e.x, (_Float16)e.y, (_Float16)e.z, (_Float16)e.w};
-            v[i] = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
-        }
-        if (f < nf4) {
-            const h16x4 o = {(_Float16)v[i].x, (_Float16)v[i].y, (_Float16)v[i].z, (_Float16)v[i].w};
-            *reinterpret_cast<h16x4*>(x + m * C + f * 4) = o;
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-        if (lane + i * 64 < nf4) {
-            const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-    const float var = wave_sum(q) / (float)C;
-    if (lane == 0) {
-        *reinterpret_cast<float2*>(rowstat + m * 2) = real ? make_float2(mean, 1.0f / sqrtf(var + eps)) : make_float2(0.f, 1.f);
-        if (mask_out) mask_out[m] = real ? 1 : 0;           // the key validity the dense attention wants for ragged prompts
-    }
-}
-int launch_dec_embed_f16(const int32_t* ids, const int32_t* lens, const int32_t* ctx_len, const float* tok_emb, const float* pos_emb,
-                         void* x, float* rowstat, int32_t* mask_out, float eps, int B, int T, int C, int vocab, int pos_rows, int absolute_pos,
-                         int32_t* err_flag, hipStream_t st) {
-    MGEA_REQUIRE(C % 4 == 0 && C <= 2048, MGEA_EINVAL, "fp16 embed: d_model=%d must be a multiple of 4 and <= 2048", C);
-    hipLaunchKernelGGL(dec_embed_f16_kernel, dim3(ceil_div(B * T, 4)), dim3(256), 0, st, ids, lens, ctx_len, tok_emb, pos_emb,
-                       (_Float16*)x, rowstat, mask_out, eps, B * T, T, C, vocab, pos_rows, absolute_pos, err_flag);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
-// K | V columns of the fp16 qkv rows [M, 3C] -> the fp16 KV pages of `layer` (common.h: K [dh/8][64 tokens][8], V [64 tokens][dh]):
-// one thread per 16-byte group, real tokens only, position ctx_len[b] + t.
-__global__ __launch_bounds__(256) void kv_scatter_f16_kernel(const _Float16* __restrict__ qkv, KvPool pool, int layer,
-                                                            const int32_t* __restrict__ page_table, int max_pages,
-                                                            const int32_t* __restrict__ ctx_len, const int32_t* __restrict__ lens,
-                                                            int64_t n_groups, int T, int C) {
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= n_groups) return;
-    const int gpr = (2 * C) >> 3;                       // 16-byte groups of K | V per row
-    const int64_t m = gid / gpr;
-    const int gi = (int)(gid - m * gpr);
-    const int b = (int)(m / T), t = (int)(m % T);
-    const bool real = lens ? (t < lens[b]) : true;
-    if (!real) return;
-    const int pos = ctx_len[b] + t;
-    const int page = pos >> 6, slot = pos & 63;
-    if (page >= max_pages) return;
-    const int phys = page_table[b * max_pages + page];
-    const int n = gi * 8;                                // column inside K | V
-    const int isv = n >= C, nn = n - (isv ? C : 0), head = nn / pool.dh, d = nn % pool.dh;
-    const float4 raw = *reinterpret_cast<const float4*>(qkv + m * 3 * C + C + n);
-    const int64_t pe = pool.page_elems();
-    _Float16* pg = static_cast<_Float16*>(pool.base) + layer * pool.layer_stride + ((int64_t)(phys * 2 + isv) * pool.H + head) * pe;
-    *reinterpret_cast<float4*>(pg + (isv ? slot * pool.dh + d : ((d >> 3) * MGEA_KV_PAGE_TOKENS + slot) * 8)) = raw;
-}
-int launch_kv_scatter_f16(const void* qkv, const KvPool& pool, int layer, const int32_t* page_table, int max_pages, const int32_t* ctx_len,
-                          const int32_t* lens, int B, int T, int C, hipStream_t st) {
-    MGEA_REQUIRE(pool.f16 && pool.dh % 8 == 0 && C % 8 == 0, MGEA_EINVAL, "fp16 KV scatter needs fp16 pages and head_dim %% 8 == 0");
-    const int64_t n_groups = (int64_t)B * T * ((2 * C) >> 3);
-    hipLaunchKernelGGL(kv_scatter_f16_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, st, (const _Float16*)qkv, pool, layer,
-                       page_table, max_pages, ctx_len, lens, n_groups, T, C);
-    MGEA_CHECK_HIP(hipGetLastError());
-    return MGEA_OK;
-}
-
 }  // namespace mgea

@@ -59,12 +59,14 @@ def attention(qkv: torch.Tensor, n_head: int, lens: Optional[torch.Tensor] = Non
 
 
 def gemm_bf16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
-              gelu: bool = False, ln: Optional[dict] = None, info: Optional[list] = None, out: Optional[torch.Tensor] = None):
+              gelu: bool = False, ln: Optional[dict] = None, info: Optional[list] = None, out: Optional[torch.Tensor] = None,
+              epi: Optional[int] = None):
     """bf16 perf-mode GEMM: (a [M,K] bf16) @ (w [N,K] bf16)^T + bias (fp32) [+GELU | +res (bf16)] -> bf16.
     ln (persistent 256 x 256 kernel only) selects a LayerNorm-folding epilogue of the big-batch DistilBERT pipeline (mgea.h):
       dict(rowstat=[M,2], c1=[N])                      -> epi 3 / 4 (gelu): rstd (a w'^T - mean c1) + bias, bias = c2
       dict(rowstat=[M,2], g=[N], b=[N], stats=True)    -> epi 5: a w^T + bias + LN(res); returns (out, per-tile (sum, M2) [M, N/256, 2])
-    info: a list that receives [kernel, half_tiles] of the launch."""
+    info: a list that receives [kernel, half_tiles] of the launch.  epi overrides the choice, and an ln entry may be None (the
+    launcher's refusals)."""
     lib = _lib.load()
     a, w = _dev(a.to(torch.bfloat16)), _dev(w.to(torch.bfloat16))
     M, K = a.shape
@@ -73,20 +75,23 @@ def gemm_bf16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = N
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
     b = None if bias is None else _dev(bias.float())
     r = None if res is None else _dev(res.to(torch.bfloat16))
-    epi = 2 if res is not None else (1 if gelu else 0)
+    e = 2 if res is not None else (1 if gelu else 0)
     rowstat = c1 = g = be = stats = None
+    opt = lambda t: None if t is None else _dev(t.float())
     if ln is not None:
-        rowstat = _dev(ln["rowstat"].float())
+        rowstat = opt(ln["rowstat"])
         if "c1" in ln:
-            epi, c1 = (4 if gelu else 3), _dev(ln["c1"].float())
+            e, c1 = (4 if gelu else 3), opt(ln["c1"])
         else:
-            epi, g, be = 5, _dev(ln["g"].float()), _dev(ln["b"].float())
+            e, g, be = 5, opt(ln["g"]), opt(ln["b"])
             if isinstance(ln.get("stats"), torch.Tensor):
                 stats = ln["stats"]                                   # caller's [M, N/256, 2] fp32 buffer (benchmarks: no allocation per call)
             elif ln.get("stats"):
                 stats = torch.zeros(M, N // 256, 2, dtype=torch.float32, device=a.device)
+    if epi is not None:
+        e = int(epi)
     io = (C.c_int32 * 2)(-1, -1)
-    check(lib.mgea_op_gemm_bf16_ln(ptr(a), ptr(w), ptr(b), ptr(r), ptr(out), M, N, K, epi, ptr(rowstat), ptr(c1), ptr(g), ptr(be),
+    check(lib.mgea_op_gemm_bf16_ln(ptr(a), ptr(w), ptr(b), ptr(r), ptr(out), M, N, K, e, ptr(rowstat), ptr(c1), ptr(g), ptr(be),
                                    ptr(stats), io, stream_ptr()))
     if info is not None:
         info[:] = [int(io[0]), int(io[1])]

@@ -27,6 +27,9 @@ FEW_WAVE_K = {96: 3, 160: 5, 288: 3, 352: 1, 704: 2}          # K -> waves per w
 FEW_WAVE_MN = [(200, 512), (16, 512), (200, 1024)]
 FEW_WAVE_LOGITS = (48, 4100)
 
+# tests/test_gpu_gemm16_plan.py: the 16-bit GEMM families (bf16 / fp16 operands AND outputs) on the same operands
+GEMM16_SHAPES = [(128, 128, 64), (512, 256, 64), (1000, 512, 128), (8192, 4096, 64), (2048, 256, 64)]
+
 
 def exact_shapes():
     s = [(m, n, k) for m in (1, 2) for n, k in GEMV_RES + GEMV_ACT + GEMV_LOGITS]

@@ -29,6 +29,22 @@ def test_integer_operands_stay_below_2_pow_24_at_every_shape_used():
         assert torch.equal(out.float().long(), out)
 
 
+def test_integer_operands_give_16_bit_outputs_without_rounding_at_the_gemm16_shapes():
+    """tests/test_gpu_gemm16_plan.py: operands exact in bf16 and fp16 (float -> bfloat16 -> float is the identity), every partial sum in
+    ANY order an integer below 2^24, and every OUTPUT (+ bias + residual) an integer of magnitude <= 256 -- exact in bf16's 8
+    significant bits and in fp16: the expected output, "the int64 product rounded once", involves no rounding at all, whichever
+    intermediate a kernel's epilogue stages in 16 bits."""
+    for M, N, K in U.GEMM16_SHAPES:
+        a, w, b, r = U.int_a(M, K), U.int_w(N, K), U.int_bias(N), U.int_res(M, N)
+        for t in (a, w, r):
+            assert torch.equal(t.float().bfloat16().float().long(), t) and torch.equal(t.float().half().float().long(), t)
+        worst = int((a[:7].abs().double() @ w[:17].abs().double().t()).max())          # (both operands are periodic: 7 rows, 17 columns)
+        assert worst + int(b.abs().max()) + int(r.abs().max()) < 2 ** 24
+        for out in (U.int_product(a, w), U.int_product(a, w, b), U.int_product(a, w, b, r)):
+            assert int(out.abs().max()) <= 256
+            assert torch.equal(out.float().bfloat16().float().long(), out) and torch.equal(out.float().half().float().long(), out)
+
+
 @pytest.mark.parametrize("K", sorted({k for _, _, k in U.exact_shapes()}))
 def test_integer_operands_give_the_same_fp32_bits_in_three_summation_orders(K):
     """Both operands are periodic (A in m with period 7, W in n with period 17): 8 rows x 18 columns hold every (row, column) pattern

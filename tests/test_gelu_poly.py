@@ -1,4 +1,4 @@
-"""CPU check of the constants of the bf16 mode's one-transcendental erf-GELU (csrc/bf16.hip): gelu(x) = max(x, 0) - 0.5 a 2^q(a),
+"""CPU check of the constants of the bf16 mode's one-transcendental erf-GELU (csrc/x16.h): gelu(x) = max(x, 0) - 0.5 a 2^q(a),
 a = min(|x|, AMAX), q a degree-5 polynomial.  The coefficients are read from the source and evaluated in fp32 the way the kernel
 does (Horner with fused multiply-adds) against the erf-GELU of the reference model (torch.nn.functional.gelu, approximate='none')."""
 import os
@@ -7,7 +7,7 @@ import re
 import numpy as np
 import torch
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "music-generation-emotion-adaptive_amd", "csrc", "bf16.hip")
+SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "music-generation-emotion-adaptive_amd", "csrc", "x16.h")
 
 
 def test_gelu_polynomial_matches_erf_gelu():

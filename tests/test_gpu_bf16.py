@@ -103,7 +103,7 @@ def _ln_tables(M, K, seed):
 
 def _gemm_case(M, N, K, epi, seed=21):
     """Inputs and the fp32 reference (torch matmul of the same bf16 inputs ON THE GPU: fp64 on the host would take minutes at
-    M = 32768) of one epilogue of the persistent kernel, in the arithmetic of csrc/bf16.hip."""
+    M = 32768) of one epilogue of the persistent kernel, in the arithmetic of csrc/gemm16.hip."""
     dev = "cuda"
     a = rnd(M, K, seed=seed).bfloat16().to(dev)
     w = rnd(N, K, seed=seed + 1, scale=K ** -0.5).bfloat16().to(dev)

@@ -11,11 +11,11 @@ import numpy as np
 import torch
 from mgea import _lib, ops
 lib = _lib.load()
-lib.mgea_dbg_set_ph_stamps.restype = C.c_int
-lib.mgea_dbg_set_ph_stamps.argtypes = [C.c_void_p]
+lib.mgea_dbg_set_attn_stamps.restype = C.c_int
+lib.mgea_dbg_set_attn_stamps.argtypes = [C.c_void_p]
 B, T, H = (int(x) for x in sys.argv[1:4]) if len(sys.argv) > 3 else (64, 1024, 8)
 stamps = torch.zeros(512, 64, dtype=torch.int64, device="cuda")
-assert lib.mgea_dbg_set_ph_stamps(C.c_void_p(stamps.data_ptr())) == 0
+assert lib.mgea_dbg_set_attn_stamps(C.c_void_p(stamps.data_ptr())) == 0
 qkv = (torch.randn(B, T, 3 * H * 64, device="cuda") * 1.0).bfloat16()
 for _ in range(3): ops.attention_bf16(qkv, H, None)
 torch.cuda.synchronize(); stamps.zero_()

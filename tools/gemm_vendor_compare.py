@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How far is the hand-written 16-bit GEMM (csrc/bf16.hip) from the vendor library on the shapes the engines run?  torch.matmul
+"""How far is the hand-written 16-bit GEMM (csrc/gemm16.hip) from the vendor library on the shapes the engines run?  torch.matmul
 (hipBLASLt / rocBLAS) against ops.gemm_bf16 with the PLAIN bias epilogue, bf16, medians of interleaved rounds (GPU box).  A measurement
 only: nothing in the product calls the vendor GEMM."""
 import os, sys
