@@ -651,6 +651,61 @@ int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, c
 int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sink_pages, int32_t ring_pages, int32_t* ctx_len_dev,
                          const int32_t* done_dev, int32_t* evictions_dev, int32_t B, void* stream);
 
+/* The DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call on caller buffers (tests/test_gpu_bert_kernels.py,
+ * tests/test_gpu_attention_exact.py).  No pointer is range-checked: the caller sizes every buffer as documented here. */
+/* The [CLS] attention of the last DistilBERT layer (csrc/attn_cls.hip): ONE query per sequence and head against all keys of its
+ * sequence.  q_dev [B, D] fp32 (D = n_head * head_dim), qkv_dev [rows, 3 D] (q | k | v; only K | V are read) in kv_dtype MGEA_DTYPE_F32
+ * or MGEA_DTYPE_BF16, out_dev [B, D] fp32.  Padded form: sequence b = rows b S .. b S + S - 1, mask_dev [B, S] int32 (0 = key not
+ * counted) or NULL.  Packed form: cu_seqlens_dev [B + 1] int32, sequence b = rows cu[b] .. cu[b + 1] - 1, no mask (S is ignored).  A
+ * sequence without any valid key gives a zero row.  MGEA_EINVAL: a mask together with cu_seqlens, bf16 with head_dim != 64, head_dim
+ * not 32 / 64, any other kv_dtype. */
+int mgea_op_attention_cls(const float* q_dev, const void* qkv_dev, int32_t kv_dtype, const int32_t* mask_dev,
+                          const int32_t* cu_seqlens_dev, float* out_dev, int32_t B, int32_t S, int32_t n_head, int32_t head_dim,
+                          void* stream);
+/* out[m] = LayerNorm(word[ids[m]] + pos[t]; ln_w, ln_b, eps) for the B * S rows m, as fp32 or bf16 (out_dtype MGEA_DTYPE_F32 /
+ * MGEA_DTYPE_BF16) [B * S, D].  t = m mod S, or pos_ids_dev[m] when pos_ids_dev != NULL (the packed form passes B = rows, S = 1).
+ * word_dev [vocab, D], pos_dev [>= every t + 1, D] fp32.  An id outside [0, vocab) is clamped to the nearest row and sets bit 0 of
+ * *err_flag_dev (device int32, or NULL: clamped silently).  D % 4 == 0 and D <= 4096 (fp32) / 2048 (bf16), else MGEA_EINVAL. */
+int mgea_op_bert_embed(const int32_t* ids_dev, const int32_t* pos_ids_dev, const float* word_dev, const float* pos_dev,
+                       const float* ln_w_dev, const float* ln_b_dev, float eps, void* out_dev, int32_t out_dtype, int32_t B, int32_t S,
+                       int32_t D, int32_t vocab, int32_t* err_flag_dev, void* stream);
+/* The [CLS] rows of h_dev [rows, D] -> out_dev [B, D] fp32: row b S of the padded form, row cu_dev[b] of the packed one (cu_dev
+ * [B + 1] int32 or NULL).  dtype MGEA_DTYPE_F32: a copy (D % 4 == 0).  MGEA_DTYPE_BF16 without rowstat_dev: the converted row.
+ * MGEA_DTYPE_BF16 with rowstat_dev [rows][2] = (mean, rstd): ((h - mean) rstd) ln_g + ln_b, the folded LayerNorm of the bf16
+ * pipeline (ln_g_dev, ln_b_dev [D] required).  rowstat_dev with MGEA_DTYPE_F32 is MGEA_EINVAL. */
+int mgea_op_gather_cls(const void* h_dev, int32_t dtype, const float* rowstat_dev, const float* ln_g_dev, const float* ln_b_dev,
+                       const int32_t* cu_dev, float* out_dev, int32_t B, int32_t S, int32_t D, void* stream);
+/* The fp32 GEMM with the bias / activation epilogue inside the kernel (no split-K, 128 x 128 tiles):
+ * out[m, n] = act(sum_k a[m, k] w[n, k] + bias[n]) for n < N, row strides lda / ldw / ldo floats; columns N .. ldo - 1 of out are
+ * not written.  act 0 none, 1 GELU, 2 ReLU.  M > 64, N % 4 == 0, K % 32 == 0, lda, ldw >= K, ldo >= N, all three strides multiples
+ * of 4, bias_dev required; anything else is MGEA_EINVAL. */
+int mgea_op_gemm_f32_direct(const float* a_dev, int32_t lda, const float* w_dev, int32_t ldw, const float* bias_dev, float* out_dev,
+                            int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+/* The row epilogues of the split-K GEMM on caller-provided slabs: p_dev holds S slabs [M][ldp] fp32, slab s at p_dev + s * ps
+ * floats; v[m, n] = sum_s P[s][m][n] (slab order) + bias[n] (bias_dev NULL: + 0).  The kernels load 16 bytes at a time: ldp % 4 == 0,
+ * ps % 4 == 0, ldp >= the row length rounded up to 4 (logits_argmax reads scalars: ldp >= V).
+ *   bias_act:       out[m, n] = act(v) for n < N, row stride ldo >= N (any value); act 0 none, 1 GELU, 2 ReLU.
+ *   bias_res_ln:    post_ln = 0: x[m] += v, and xn[m] = LayerNorm(x[m]) when ln_w_dev != NULL (xn_dev then required);
+ *                   post_ln = 1: x[m] = LayerNorm(x[m] + v), ln_w_dev required.  x, xn [M, C]; C % 4 == 0, C <= 4096.
+ *   logits_argmax:  logits_dev [M, V] = v (or NULL) and argmax_dev [M] int32 = the LOWEST index of the row maximum (or NULL); a row
+ *                   without any value above -inf gives 0.
+ *   qkv_scatter:    rows m = b T + t of [B T, 3 C], C = n_head * head_dim (head_dim % 8 == 0).  qkv_out_dev != NULL:
+ *                   qkv_out[m] = v for t < lens[b] (lens_dev NULL: every t), zero rows past it, and K | V of those tokens go to
+ *                   position ctx_len_dev[b] + t of ONE layer of pages (layout and page table: above; page_dtype MGEA_DTYPE_F32 /
+ *                   MGEA_DTYPE_F16).  qkv_out_dev == NULL: scatter only, p_dev is the finished [B T, ldp] buffer (S, ps and bias
+ *                   are ignored).  Positions in logical pages >= max_pages are not cached. */
+int mgea_op_slab_bias_act(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* out_dev, int32_t ldo,
+                          int32_t M, int32_t N, int32_t act, void* stream);
+int mgea_op_slab_bias_res_ln(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* x_dev, float* xn_dev,
+                             const float* ln_w_dev, const float* ln_b_dev, float eps, int32_t M, int32_t C, int32_t post_ln,
+                             void* stream);
+int mgea_op_slab_logits_argmax(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* logits_dev,
+                               int32_t M, int32_t V, int32_t* argmax_dev, void* stream);
+int mgea_op_slab_qkv_scatter(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* qkv_out_dev,
+                             void* pages_dev, int32_t n_pages, int32_t page_dtype, const int32_t* page_table_dev, int32_t max_pages,
+                             const int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t n_head,
+                             int32_t head_dim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

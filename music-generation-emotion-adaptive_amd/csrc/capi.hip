@@ -492,6 +492,95 @@ int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, c
     return op_sample_rows(logits_dev, B, V, rows, presence_dev, lrows, step, ids_out_dev, probs_out_dev, ScoreArgs{}, stream, &g);
 }
 
+// ---- the DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call (tests) ----
+int mgea_op_attention_cls(const float* q_dev, const void* qkv_dev, int32_t kv_dtype, const int32_t* mask_dev,
+                          const int32_t* cu_seqlens_dev, float* out_dev, int32_t B, int32_t S, int32_t n_head, int32_t head_dim,
+                          void* stream) {
+    MGEA_REQUIRE(q_dev && qkv_dev && out_dev && B > 0 && n_head > 0 && (cu_seqlens_dev || S > 0), MGEA_EINVAL, "op_attention_cls: bad argument");
+    MGEA_REQUIRE(kv_dtype == MGEA_DTYPE_F32 || kv_dtype == MGEA_DTYPE_BF16, MGEA_EINVAL, "op_attention_cls: K | V dtype %d (f32, bf16)", kv_dtype);
+    return launch_attn_cls(q_dev, qkv_dev, kv_dtype == MGEA_DTYPE_BF16, mask_dev, out_dev, B, S, n_head, head_dim, (hipStream_t)stream,
+                           cu_seqlens_dev);
+}
+
+int mgea_op_bert_embed(const int32_t* ids_dev, const int32_t* pos_ids_dev, const float* word_dev, const float* pos_dev,
+                       const float* ln_w_dev, const float* ln_b_dev, float eps, void* out_dev, int32_t out_dtype, int32_t B, int32_t S,
+                       int32_t D, int32_t vocab, int32_t* err_flag_dev, void* stream) {
+    MGEA_REQUIRE(ids_dev && word_dev && pos_dev && ln_w_dev && ln_b_dev && out_dev && B > 0 && S > 0 && D > 0 && vocab > 0, MGEA_EINVAL,
+                 "op_bert_embed: bad argument");
+    MGEA_REQUIRE(out_dtype == MGEA_DTYPE_F32 || out_dtype == MGEA_DTYPE_BF16, MGEA_EINVAL, "op_bert_embed: output dtype %d (f32, bf16)", out_dtype);
+    if (out_dtype == MGEA_DTYPE_BF16)
+        return launch_bert_embed_ln_bf16(ids_dev, word_dev, pos_dev, ln_w_dev, ln_b_dev, eps, out_dev, B, S, D, vocab, (hipStream_t)stream,
+                                         err_flag_dev, pos_ids_dev);
+    return launch_bert_embed_ln(ids_dev, word_dev, pos_dev, ln_w_dev, ln_b_dev, eps, static_cast<float*>(out_dev), B, S, D, vocab,
+                                (hipStream_t)stream, err_flag_dev, pos_ids_dev);
+}
+
+int mgea_op_gather_cls(const void* h_dev, int32_t dtype, const float* rowstat_dev, const float* ln_g_dev, const float* ln_b_dev,
+                       const int32_t* cu_dev, float* out_dev, int32_t B, int32_t S, int32_t D, void* stream) {
+    MGEA_REQUIRE(h_dev && out_dev && B > 0 && D > 0 && (cu_dev || S > 0), MGEA_EINVAL, "op_gather_cls: bad argument");
+    MGEA_REQUIRE(dtype == MGEA_DTYPE_F32 || dtype == MGEA_DTYPE_BF16, MGEA_EINVAL, "op_gather_cls: dtype %d (f32, bf16)", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MGEA_DTYPE_F32) {
+        MGEA_REQUIRE(!rowstat_dev && D % 4 == 0, MGEA_EINVAL, "op_gather_cls: fp32 rows are copied (no rowstat, D %% 4 == 0)");
+        return launch_gather_rows(static_cast<const float*>(h_dev), D, out_dev, D, B, S, D, st, cu_dev);
+    }
+    if (!rowstat_dev) return launch_gather_cls_bf16(h_dev, out_dev, B, S, D, st, cu_dev);
+    MGEA_REQUIRE(ln_g_dev && ln_b_dev, MGEA_EINVAL, "op_gather_cls: the LayerNorm form needs ln_g_dev and ln_b_dev");
+    return launch_gather_cls_ln_bf16(h_dev, rowstat_dev, ln_g_dev, ln_b_dev, out_dev, B, S, D, st, cu_dev);
+}
+
+int mgea_op_gemm_f32_direct(const float* a_dev, int32_t lda, const float* w_dev, int32_t ldw, const float* bias_dev, float* out_dev,
+                            int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    MGEA_REQUIRE(a_dev && w_dev && out_dev && N > 0 && K > 0 && lda >= K && ldw >= K && lda % 4 == 0 && ldw % 4 == 0, MGEA_EINVAL,
+                 "op_gemm_f32_direct: bad argument (lda, ldw >= K and multiples of 4)");
+    MGEA_REQUIRE(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU, MGEA_EINVAL, "op_gemm_f32_direct: act %d", act);
+    return launch_gemm_f32_bias_act(a_dev, lda, w_dev, ldw, bias_dev, out_dev, ldo, M, N, K, act, (hipStream_t)stream);
+}
+
+// the slab geometry every epilogue kernel relies on: 16-byte loads of whole groups of `row` columns
+static int check_slabs(const char* who, const float* p_dev, int32_t S, int64_t ps, int32_t ldp, int32_t M, int32_t row) {
+    MGEA_REQUIRE(p_dev && S >= 1 && M > 0 && row > 0 && ldp % 4 == 0 && ldp >= round_up(row, 4) && (S == 1 || (ps % 4 == 0 && ps >= (int64_t)M * ldp)),
+                 MGEA_EINVAL, "%s: bad slabs (S=%d ps=%lld ldp=%d for %d rows of %d columns)", who, S, (long long)ps, ldp, M, row);
+    return MGEA_OK;
+}
+
+int mgea_op_slab_bias_act(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* out_dev, int32_t ldo,
+                          int32_t M, int32_t N, int32_t act, void* stream) {
+    MGEA_TRY(check_slabs("op_slab_bias_act", p_dev, S, ps, ldp, M, N));
+    MGEA_REQUIRE(out_dev && ldo >= N && (act == ACT_NONE || act == ACT_GELU || act == ACT_RELU), MGEA_EINVAL,
+                 "op_slab_bias_act: bad argument (ldo=%d N=%d act=%d)", ldo, N, act);
+    return launch_bias_act(p_dev, S, ps, ldp, bias_dev, out_dev, ldo, M, N, act, (hipStream_t)stream);
+}
+
+int mgea_op_slab_bias_res_ln(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* x_dev, float* xn_dev,
+                             const float* ln_w_dev, const float* ln_b_dev, float eps, int32_t M, int32_t C, int32_t post_ln,
+                             void* stream) {
+    MGEA_TRY(check_slabs("op_slab_bias_res_ln", p_dev, S, ps, ldp, M, C));
+    MGEA_REQUIRE(x_dev && (!ln_w_dev || (ln_b_dev && (post_ln || xn_dev))), MGEA_EINVAL,
+                 "op_slab_bias_res_ln: x_dev is NULL, or LayerNorm weights without ln_b_dev / xn_dev");
+    return launch_bias_res_ln(p_dev, S, ps, ldp, bias_dev, x_dev, xn_dev, ln_w_dev, ln_b_dev, eps, M, C, post_ln, (hipStream_t)stream);
+}
+
+int mgea_op_slab_logits_argmax(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* logits_dev,
+                               int32_t M, int32_t V, int32_t* argmax_dev, void* stream) {
+    MGEA_REQUIRE(p_dev && S >= 1 && M > 0 && V > 0 && ldp >= V && (S == 1 || ps >= (int64_t)M * ldp), MGEA_EINVAL,
+                 "op_slab_logits_argmax: bad slabs (S=%d ps=%lld ldp=%d for %d rows of %d columns)", S, (long long)ps, ldp, M, V);
+    return launch_logits_argmax(p_dev, S, ps, ldp, bias_dev, logits_dev, M, V, argmax_dev, (hipStream_t)stream);
+}
+
+int mgea_op_slab_qkv_scatter(const float* p_dev, int32_t S, int64_t ps, int32_t ldp, const float* bias_dev, float* qkv_out_dev,
+                             void* pages_dev, int32_t n_pages, int32_t page_dtype, const int32_t* page_table_dev, int32_t max_pages,
+                             const int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t n_head,
+                             int32_t head_dim, void* stream) {
+    MGEA_REQUIRE(pages_dev && page_table_dev && ctx_len_dev && n_pages > 0 && max_pages > 0 && B > 0 && T > 0 && n_head > 0 && head_dim > 0 &&
+                     head_dim % 8 == 0 && (page_dtype == MGEA_DTYPE_F32 || page_dtype == MGEA_DTYPE_F16),
+                 MGEA_EINVAL, "op_slab_qkv_scatter: bad argument (head_dim %% 8 == 0, fp32 or fp16 pages)");
+    const int C = n_head * head_dim;
+    MGEA_TRY(check_slabs("op_slab_qkv_scatter", p_dev, qkv_out_dev ? S : 1, ps, ldp, B * T, 3 * C));
+    return launch_qkv_scatter(p_dev, S, ps, ldp, bias_dev, qkv_out_dev, op_pool(pages_dev, n_pages, n_head, head_dim, page_dtype == MGEA_DTYPE_F16, 0),
+                              0, page_table_dev, max_pages, ctx_len_dev, lens_dev, B, T, C, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,

@@ -147,6 +147,14 @@ PROTOTYPES = {
     "mgea_op_window_evict": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,
                                               _P, _P, _P]),
+    "mgea_op_attention_cls": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_bert_embed": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "mgea_op_gather_cls": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "mgea_op_gemm_f32_direct": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_slab_bias_act": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_slab_bias_res_ln": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _F, _I32, _I32, _I32, _P]),
+    "mgea_op_slab_logits_argmax": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P]),
+    "mgea_op_slab_qkv_scatter": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
 }
 
 _lib = None

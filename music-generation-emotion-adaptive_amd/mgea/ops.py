@@ -380,6 +380,220 @@ def window_evict(page_table: torch.Tensor, sink_pages: int, ring_pages: int, ctx
     return pt, cl, ev
 
 
+# ---- the DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call (mgea_op_* of the same names: tests only) ----
+_DTYPE_ROWS = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+def _i32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else _dev(t.to(torch.int32))
+
+
+def _rows2d(t: torch.Tensor, what: str) -> torch.Tensor:
+    """a device fp32 [rows, cols] view whose columns are contiguous (the row stride is the leading dimension the kernel gets)"""
+    if t.device.type != "cuda" or t.dtype != torch.float32 or t.ndim != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RuntimeError(f"{what}: an fp32 device matrix with contiguous columns is needed")
+    return t
+
+
+def attention_cls(q: torch.Tensor, qkv: torch.Tensor, n_head: int, mask: Optional[torch.Tensor] = None,
+                  cu: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The [CLS] attention (mgea_op_attention_cls): q [B, D] fp32, one query per sequence; qkv [B, S, 3 D] (padded; mask [B, S] or
+    None) or [cu[B], 3 D] with cu [B + 1] (packed), fp32 or bf16 (only its K | V columns are read) -> [B, D] fp32."""
+    lib = _lib.load()
+    if qkv.dtype not in _DTYPE_ROWS:
+        raise RuntimeError("attention_cls takes an fp32 or bf16 qkv")
+    q, qkv = _dev(q.float()), _dev(qkv)
+    B, D = q.shape
+    if qkv.shape[-1] != 3 * D or D % n_head:
+        raise RuntimeError("attention_cls: qkv rows hold 3 D columns, D = n_head * head_dim")
+    c32 = _i32(cu)
+    if cu is not None:
+        if qkv.ndim != 2 or cu.numel() != B + 1 or int(cu[-1]) != qkv.shape[0] or int(cu[0]) != 0 or bool((cu[1:] < cu[:-1]).any()):
+            raise RuntimeError("packed attention_cls: qkv must be [cu[B], 3 D] and cu [B + 1] non-decreasing from 0")
+        S = 0
+    else:
+        if qkv.ndim != 3 or qkv.shape[0] != B:
+            raise RuntimeError("attention_cls: qkv must be [B, S, 3 D]")
+        S = qkv.shape[1]
+    m32 = _i32(mask)
+    if m32 is not None and cu is None and tuple(m32.shape) != (B, S):
+        raise RuntimeError("attention_cls: mask must be [B, S]")
+    out = torch.full((B, D), float("nan"), dtype=torch.float32, device=q.device)
+    check(lib.mgea_op_attention_cls(ptr(q), ptr(qkv), _DTYPE_ROWS[qkv.dtype], ptr(m32), ptr(c32), ptr(out), B, S, n_head, D // n_head,
+                                    stream_ptr()))
+    return out
+
+
+def bert_embed(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float,
+               out_dtype: torch.dtype = torch.float32, pos_ids: Optional[torch.Tensor] = None, want_flag: bool = True,
+               out: Optional[torch.Tensor] = None):
+    """LayerNorm(word[ids] + pos[t]) by the DistilBERT embedding kernel (mgea_op_bert_embed): ids [B, S] (t = the column), or [rows]
+    with pos_ids [rows] (packed).  -> (out [rows, D] fp32 or bf16, flag): flag = the error word after the call (1: an id was clamped), None
+    with want_flag=False (the kernel then gets no flag word).  out: the caller's buffer (left as it is when the call is refused)."""
+    lib = _lib.load()
+    word, pos, ln_w, ln_b = (_dev(t.float()) for t in (word, pos, ln_w, ln_b))
+    ids = _i32(ids)
+    p32 = _i32(pos_ids)
+    if p32 is not None:
+        if ids.ndim != 1 or p32.shape != ids.shape:
+            raise RuntimeError("packed bert_embed: ids and pos_ids are [rows]")
+        B, S, tmax = ids.numel(), 1, int(p32.max())
+        if int(p32.min()) < 0:
+            raise RuntimeError("bert_embed: negative position")
+    else:
+        B, S = ids.shape
+        tmax = S - 1
+    V, D = word.shape
+    if pos.shape[1] != D or pos.shape[0] <= tmax or ln_w.numel() != D or ln_b.numel() != D:
+        raise RuntimeError("bert_embed: pos must be [> every position, D], ln_w and ln_b [D]")
+    if out is None:
+        out = torch.empty(B * S, D, dtype=out_dtype, device=ids.device)
+    if out.dtype != out_dtype or out.numel() < B * S * D or not out.is_contiguous() or out_dtype not in _DTYPE_ROWS:
+        raise RuntimeError("bert_embed: out must be a contiguous fp32 or bf16 tensor of rows * D elements")
+    flag = torch.zeros(1, dtype=torch.int32, device=ids.device) if want_flag else None
+    check(lib.mgea_op_bert_embed(ptr(ids), ptr(p32), ptr(word), ptr(pos), ptr(ln_w), ptr(ln_b), float(eps), ptr(out), _DTYPE_ROWS[out_dtype],
+                                 B, S, D, V, ptr(flag), stream_ptr()))
+    return out, (int(flag.item()) if want_flag else None)
+
+
+def gather_cls(h: torch.Tensor, B: int, S: int, cu: Optional[torch.Tensor] = None, rowstat: Optional[torch.Tensor] = None,
+               ln_g: Optional[torch.Tensor] = None, ln_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The [CLS] rows of h [rows, D] (fp32 or bf16) -> [B, D] fp32 (mgea_op_gather_cls): row b S, or row cu[b] with cu [B + 1].  bf16
+    with rowstat [rows, 2] = (mean, rstd): the folded LayerNorm ((h - mean) rstd) ln_g + ln_b of those rows."""
+    lib = _lib.load()
+    if h.dtype not in _DTYPE_ROWS or h.ndim != 2:
+        raise RuntimeError("gather_cls takes an fp32 or bf16 [rows, D] matrix")
+    h = _dev(h)
+    rows, D = h.shape
+    c32 = _i32(cu)
+    first = [int(c) for c in cu[:B]] if cu is not None else [b * S for b in range(B)]
+    if (cu is not None and cu.numel() != B + 1) or min(first) < 0 or max(first) >= rows:
+        raise RuntimeError("gather_cls: a [CLS] row lies outside h")
+    rs = None if rowstat is None else _dev(rowstat.float())
+    if rs is not None and rs.numel() != rows * 2:
+        raise RuntimeError("gather_cls: rowstat must be [rows, 2]")
+    g = None if ln_g is None else _dev(ln_g.float())
+    be = None if ln_b is None else _dev(ln_b.float())
+    out = torch.full((B, D), float("nan"), dtype=torch.float32, device=h.device)
+    check(lib.mgea_op_gather_cls(ptr(h), _DTYPE_ROWS[h.dtype], ptr(rs), ptr(g), ptr(be), ptr(c32), ptr(out), B, S, D, stream_ptr()))
+    return out
+
+
+def gemm_direct(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, act: int = 0) -> torch.Tensor:
+    """The fp32 GEMM with its bias / activation epilogue inside the kernel (mgea_op_gemm_f32_direct): out[:, :] = act(a w^T + bias),
+    written in place.  a [M, K], w [N, K] and out [M, N] are device VIEWS with contiguous columns: their row strides go to the kernel as
+    lda / ldw / ldo, so a column slice of a wider matrix is read or written in place."""
+    lib = _lib.load()
+    a, w, out = _rows2d(a, "gemm_direct a"), _rows2d(w, "gemm_direct w"), _rows2d(out, "gemm_direct out")
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K or tuple(out.shape) != (M, N):
+        raise RuntimeError("gemm_direct: a [M, K], w [N, K], out [M, N]")
+    b = None if bias is None else _dev(bias.float())
+    if b is not None and b.numel() != N:
+        raise RuntimeError("gemm_direct: bias [N]")
+    check(lib.mgea_op_gemm_f32_direct(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(b), ptr(out), out.stride(0), M, N, K, int(act),
+                                      stream_ptr()))
+    return out
+
+
+def _slabs(P: torch.Tensor, what: str):
+    """P [S, M, ldp] fp32 on the device, rows contiguous -> (S, slab stride, ldp, M)"""
+    if P.device.type != "cuda" or P.dtype != torch.float32 or P.ndim != 3 or P.stride(2) != 1 or P.stride(1) != P.shape[2]:
+        raise RuntimeError(f"{what}: the slabs are an fp32 device tensor [S, M, ldp] with contiguous rows")
+    return P.shape[0], (P.stride(0) if P.shape[0] > 1 else 0), P.shape[2], P.shape[1]
+
+
+def slab_bias_act(P: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, act: int = 0) -> torch.Tensor:
+    """out[m, n] = act(sum_s P[s, m, n] + bias[n]) (mgea_op_slab_bias_act), in place: out is a device view [M, N] with contiguous
+    columns whose row stride is the kernel's ldo."""
+    lib = _lib.load()
+    S, ps, ldp, M = _slabs(P, "slab_bias_act")
+    out = _rows2d(out, "slab_bias_act out")
+    N = out.shape[1]
+    b = None if bias is None else _dev(bias.float())
+    if out.shape[0] != M or (b is not None and b.numel() < N):
+        raise RuntimeError("slab_bias_act: out [M, N], bias [N]")
+    check(lib.mgea_op_slab_bias_act(ptr(P), S, ps, ldp, ptr(b), ptr(out), out.stride(0), M, N, int(act), stream_ptr()))
+    return out
+
+
+def slab_bias_res_ln(P: torch.Tensor, bias: Optional[torch.Tensor], x: torch.Tensor, ln_w: Optional[torch.Tensor] = None,
+                     ln_b: Optional[torch.Tensor] = None, eps: float = 1e-5, post_ln: bool = False):
+    """The residual / LayerNorm epilogue (mgea_op_slab_bias_res_ln) on x [M, C] (contiguous fp32 device tensor, updated in place):
+    pre-LN x += v and xn = LN(x) when ln_w is given; post-LN x = LN(x + v).  Returns (x, xn or None)."""
+    lib = _lib.load()
+    S, ps, ldp, M = _slabs(P, "slab_bias_res_ln")
+    if x.device.type != "cuda" or x.dtype != torch.float32 or x.ndim != 2 or not x.is_contiguous() or x.shape[0] != M:
+        raise RuntimeError("slab_bias_res_ln: x is a contiguous fp32 device tensor [M, C]")
+    Cd = x.shape[1]
+    b = None if bias is None else _dev(bias.float())
+    w = None if ln_w is None else _dev(ln_w.float())
+    be = None if ln_b is None else _dev(ln_b.float())
+    if any(t is not None and t.numel() < Cd for t in (b, w, be)):
+        raise RuntimeError("slab_bias_res_ln: bias, ln_w and ln_b are [C]")
+    xn = torch.full_like(x, float("nan")) if (w is not None and not post_ln) else None
+    check(lib.mgea_op_slab_bias_res_ln(ptr(P), S, ps, ldp, ptr(b), ptr(x), ptr(xn), ptr(w), ptr(be), float(eps), M, Cd, int(bool(post_ln)),
+                                       stream_ptr()))
+    return x, xn
+
+
+def slab_logits_argmax(P: torch.Tensor, bias: Optional[torch.Tensor], V: int, logits: Optional[torch.Tensor] = None,
+                       argmax: Optional[torch.Tensor] = None):
+    """logits [M, V] = sum_s P[s] + bias and argmax [M] int32 = the lowest index of each row's maximum (mgea_op_slab_logits_argmax);
+    each output is written only if its (contiguous device) buffer is passed.  Returns (logits, argmax) as passed."""
+    lib = _lib.load()
+    S, ps, ldp, M = _slabs(P, "slab_logits_argmax")
+    b = None if bias is None else _dev(bias.float())
+    if ldp < V or (b is not None and b.numel() < V):
+        raise RuntimeError("slab_logits_argmax: ldp >= V, bias [V]")
+    if logits is not None and (logits.dtype != torch.float32 or logits.numel() < M * V or not logits.is_contiguous() or logits.device != P.device):
+        raise RuntimeError("slab_logits_argmax: logits must be a contiguous fp32 device tensor [M, V]")
+    if argmax is not None and (argmax.dtype != torch.int32 or argmax.numel() < M or not argmax.is_contiguous() or argmax.device != P.device):
+        raise RuntimeError("slab_logits_argmax: argmax must be a contiguous int32 device tensor [M]")
+    check(lib.mgea_op_slab_logits_argmax(ptr(P), S, ps, ldp, ptr(b), ptr(logits), M, int(V), ptr(argmax), stream_ptr()))
+    return logits, argmax
+
+
+def slab_qkv_scatter(P: torch.Tensor, bias: Optional[torch.Tensor], n_head: int, head_dim: int, pages: torch.Tensor,
+                     page_table: torch.Tensor, ctx_len: torch.Tensor, lens: Optional[torch.Tensor], T: int, want_qkv: bool = True):
+    """The qkv epilogue with its KV-page scatter (mgea_op_slab_qkv_scatter).  P [S, B T, ldp]; pages: one layer of device KV pages (fp32
+    or fp16), written in place at positions ctx_len[b] + t, t < lens[b].  want_qkv: qkv_out [B T, 3 C] = the slab sum + bias (zero rows
+    past lens) is returned; False: scatter only, P[0] is the finished buffer and nothing else is written."""
+    lib = _lib.load()
+    S, ps, ldp, M = _slabs(P, "slab_qkv_scatter")
+    Cd = n_head * head_dim
+    if pages.dtype not in (torch.float32, torch.float16) or not pages.is_contiguous() or pages.device != P.device:
+        raise RuntimeError("slab_qkv_scatter: pages must be a contiguous fp32 or fp16 device tensor")
+    n_pages = pages.numel() // kv_page_elems(1, n_head, head_dim)
+    pt, cl, l32 = _i32(page_table), _i32(ctx_len), _i32(lens)
+    B = M // T
+    if M % T or pt.ndim != 2 or pt.shape[0] != B or cl.shape != (B,) or (l32 is not None and l32.shape != (B,)) or ldp < 3 * Cd:
+        raise RuntimeError("slab_qkv_scatter: P [S, B T, >= 3 C], page_table [B, max_pages], ctx_len and lens [B]")
+    if n_pages < 1 or int(pt.min()) < 0 or int(pt.max()) >= n_pages or int(cl.min()) < 0:
+        raise RuntimeError("slab_qkv_scatter: page table entries must lie in [0, n_pages), context lengths must not be negative")
+    b = None if bias is None else _dev(bias.float())
+    if b is not None and b.numel() < 3 * Cd:
+        raise RuntimeError("slab_qkv_scatter: bias [3 C]")
+    out = torch.full((M, 3 * Cd), float("nan"), dtype=torch.float32, device=P.device) if want_qkv else None
+    check(lib.mgea_op_slab_qkv_scatter(ptr(P), S, ps, ldp, ptr(b), ptr(out), ptr(pages), n_pages,
+                                       _lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32, ptr(pt), pt.shape[1], ptr(cl),
+                                       ptr(l32), B, T, n_head, head_dim, stream_ptr()))
+    return out
+
+
+def lora_merge(w: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float) -> torch.Tensor:
+    """W [out, in] + scale * B [out, r] @ A [r, in] by the LoRA fold kernel (mgea_lora_merge) -> a new [out, in] fp32 tensor."""
+    lib = _lib.load()
+    w, a, b = _dev(w.float()).clone(), _dev(a.float()), _dev(b.float())
+    out_dim, in_dim = w.shape
+    r = a.shape[0]
+    if tuple(a.shape) != (r, in_dim) or tuple(b.shape) != (out_dim, r):
+        raise RuntimeError("lora_merge: W [out, in], A [r, in], B [out, r]")
+    check(lib.mgea_lora_merge(ptr(w), ptr(a), ptr(b), out_dim, in_dim, r, float(scale), stream_ptr()))
+    return w
+
+
 def check_repetition_penalty(penalty) -> Optional[float]:
     """None -> None (no penalty).  Otherwise the penalty as a float, which must be finite and > 0 also once held as
     fp32 (the kernels' precision): ValueError otherwise, as transformers' RepetitionPenaltyLogitsProcessor raises."""

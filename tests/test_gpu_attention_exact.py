@@ -418,6 +418,170 @@ def test_attention_paged_ragged_extend(pdtype, dh):
             assert float(out[1, 1:].abs().max()) == 0.0
 
 
+# ---- the [CLS] attention of the last DistilBERT layer (csrc/attn_cls.hip) ---------------------------------------------------
+# One query per (sequence, head); a wave walks its keys in blocks of 16 iterations x G key groups: G = 8 / blk = 128 keys at head_dim 64,
+# G = 16 / blk = 256 at head_dim 32.  Three instantiations: <float, 64>, <__bf16, 64>, <float, 32>; all write fp32, and the 16-bit-exact
+# inputs make the bf16 K | V lossless, so every one is held to ULP[fp32].
+CLS_B, CLS_H = 4, 4
+CLS_BLK = {64: 128, 32: 256}
+CLS_S = {64: [1, 7, 8, 9, 127, 128, 129, 257, 300], 32: [1, 15, 16, 17, 255, 256, 257, 513]}
+CLS_KINDS = ["none", "prefix", "random"]
+CLS_FORMS = [(torch.float32, 64), (torch.bfloat16, 64), (torch.float32, 32)]
+CLS_PACKED = (1, 20, 128, 129, 257)
+CLS_PACKED_32 = (1, 20, 256, 257)       # head_dim 32: the poison family has 8 dims per sequence, and the block is 256 keys
+
+
+def _cls_valid(kind, S, dh):
+    """[CLS_B, S] bool.  prefix: lens [S, 1, min(blk, S), S - 1] (at least 1).  random, S > blk: row 0 has the kernel's whole first
+    block masked and its first valid key at blk (the `mn == -inf -> continue` path, then alpha = exp(-inf)), row 1 has key 0 -- the
+    [CLS] key itself -- masked, row 2 has a single valid key (the last: every earlier block is skipped), row 3 is plain random; S <= blk
+    has no second block: key 0 valid in every row, row 2 keeps its single key."""
+    blk = CLS_BLK[dh]
+    if kind == "none":
+        return np.ones((CLS_B, S), dtype=bool)
+    if kind == "prefix":
+        lens = [S, 1, min(blk, S), max(1, S - 1)]
+        return np.arange(S)[None, :] < np.asarray(lens)[:, None]
+    assert kind == "random"
+    m = np.random.RandomState(2000 + 8 * S + dh).rand(CLS_B, S) > 0.3
+    if S > blk:
+        m[0, :blk] = False
+        m[0, blk] = True
+        m[1, 0] = False
+        m[1, 1] = True
+        m[2, :] = False
+        m[2, S - 1] = True
+        m[3, 0] = True
+    else:
+        m[:, 0] = True
+        m[2, 1:] = False
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def _cls_cases(family, kind, S, dh):
+    """the launches of one family: a launch has only B * H queries, so the pointer family takes as many rounds as the pointer targets
+    of the longest row need (as _paged_cases does)"""
+    valid = _cls_valid(kind, S, dh)
+    if family != "pointer":
+        return [Case(family, valid, CLS_H, dh, Tq=1)]
+    per_row = [_targets(valid[b], extra=[7, 8, 15, 16, 127, 128, 255, 256, S - 2]) for b in range(CLS_B)]
+    rounds = max((len(t) + CLS_H - 1) // CLS_H for t in per_row)
+    return [Case(family, valid, CLS_H, dh, Tq=1, q_targets=[[[t[(r * CLS_H + h) % len(t)]] for h in range(CLS_H)] for t in per_row])
+            for r in range(rounds)]
+
+
+def cls_case_list():
+    """every (family, kind, S, head_dim) of the [CLS] tests (tests/test_bert_kernels_host.py builds them all on the CPU)"""
+    return [(f, kind, S, dh) for dh in (64, 32) for S in CLS_S[dh] for kind in CLS_KINDS for f in FAMILIES]
+
+
+def _cls_run(case, kv_dtype, mask):
+    """q [B, D] fp32 and a qkv buffer whose q columns are NaN: the kernel reads K | V only"""
+    from mgea import ops
+    B, S = case.valid.shape
+    D = case.H * case.dh
+    qkv = torch.from_numpy(np.concatenate([np.full((B, S, D), np.nan)] + [x.reshape(B, S, D) for x in (case.k, case.v)], -1)).to(kv_dtype)
+    q = torch.from_numpy(case.q.reshape(B, D)).float()
+    return ops.attention_cls(q.cuda(), qkv.cuda(), case.H, mask=mask).view(B, 1, D)
+
+
+@pytest.mark.parametrize("kind", CLS_KINDS)
+@pytest.mark.parametrize("kv_dtype,dh", CLS_FORMS, ids=lambda x: _ID.get(x, str(x)))
+def test_attention_cls_counts_every_valid_key_exactly_once(kv_dtype, dh, kind):
+    for S in CLS_S[dh]:
+        for family in FAMILIES:
+            for case in _cls_cases(family, kind, S, dh):
+                mask = None if kind == "none" else torch.from_numpy(case.valid).to(torch.int32).cuda()
+                case.check(_cls_run(case, kv_dtype, mask), torch.float32, what=f"attn_cls {_ID[kv_dtype]} dh={dh} S={S} {kind} mask")
+
+
+@pytest.mark.parametrize("kv_dtype,dh,seqs", [(torch.float32, 64, CLS_PACKED), (torch.bfloat16, 64, CLS_PACKED), (torch.float32, 32, CLS_PACKED_32)],
+                         ids=lambda x: _ID.get(x, str(x) if isinstance(x, int) else "seqs"))
+def test_attention_cls_packed_rows_stay_inside_their_sequence(kv_dtype, dh, seqs):
+    """cu_seqlens input: the query of sequence s is the query of one of its own tokens in _packed_case (pointer: the code of that
+    token's target, round r takes token r of every sequence so that all targets of the longest are visited); poison: the keys of the
+    other sequences are loud and V is 2^s."""
+    from mgea import ops
+    H, C = 2, 2 * dh
+    cu = np.concatenate([[0], np.cumsum(seqs)])
+    for family in FAMILIES:
+        qkv, exp = _packed_case(family, seqs, H, dh)
+        kv = qkv.clone()
+        kv[:, :C] = float("nan")
+        kv = kv.to(kv_dtype).cuda()
+        for r in range(16 if family == "pointer" else 1):
+            tok = np.asarray([cu[s] + r % n for s, n in enumerate(seqs)])
+            got = ops.attention_cls(qkv[tok, :C].cuda(), kv, H, cu=torch.from_numpy(cu).to(torch.int32).cuda()).double().cpu().numpy()
+            want = exp[0, tok].reshape(len(seqs), C)
+            tol = ULP[torch.float32] * (np.abs(want) if family != "pointer" else 1.0)
+            bad = ~(np.abs(got - want) <= tol)
+            assert not bad.any(), f"{family} round {r}: {int(bad.sum())} wrong outputs, first in sequence {int(np.nonzero(bad)[0][0])}"
+
+
+@pytest.mark.parametrize("kv_dtype,dh", CLS_FORMS, ids=lambda x: _ID.get(x, str(x)))
+def test_attention_cls_sequence_without_a_valid_key_gives_zeros(kv_dtype, dh):
+    """The kernel's contract (_ref64 cannot express it): a sequence whose every key is masked, or a packed sequence of no rows, gives an
+    all-zero, finite output row; its neighbours are untouched by it."""
+    from mgea import ops
+    for S in (1, CLS_BLK[dh] + 1, 300):
+        case = Case("poison", np.ones((CLS_B, S), dtype=bool), CLS_H, dh, Tq=1)
+        mask = torch.ones(CLS_B, S, dtype=torch.int32)
+        mask[1] = 0
+        out = _cls_run(case, kv_dtype, mask.cuda()).cpu()
+        assert torch.equal(out[1], torch.zeros_like(out[1])), f"S={S}: the row without a valid key is not zero"
+        rows = np.ones((CLS_B, 1), dtype=bool)
+        rows[1] = False
+        case.check(out, torch.float32, rows=rows, what=f"S={S}, row 1 fully masked")
+    seqs = (20, 0, 129)
+    H, C = 2, 2 * dh
+    qkv, exp = _packed_case("poison", (20, 129), H, dh)
+    cu = torch.tensor([0, 20, 20, 149], dtype=torch.int32)
+    q = torch.stack([qkv[0, :C], qkv[0, :C], qkv[20, :C]])
+    got = ops.attention_cls(q.cuda(), qkv.to(kv_dtype).cuda(), H, cu=cu.cuda()).cpu()
+    assert torch.equal(got[1], torch.zeros(C)), f"packed {seqs}: the empty sequence's row is not zero"
+    assert float((got[0] - 1.0).abs().max()) <= ULP[torch.float32] and float((got[2] - 2.0).abs().max()) <= 2 * ULP[torch.float32]
+
+
+def test_attention_cls_refusals():
+    from mgea import ops
+    q, qkv = torch.zeros(2, 128).cuda(), torch.zeros(2, 4, 384).cuda()
+    out = ops.attention_cls(q, qkv, 2)                      # the shape itself is fine
+    assert out.shape == (2, 128)
+    with pytest.raises(RuntimeError, match="no key mask"):
+        ops.attention_cls(q, qkv.view(8, 384), 2, mask=torch.ones(2, 4, dtype=torch.int32).cuda(), cu=torch.tensor([0, 4, 8]).cuda())
+    with pytest.raises(RuntimeError, match="head_dim 64"):
+        ops.attention_cls(q, qkv.bfloat16(), 4)             # bf16 with head_dim 32
+    with pytest.raises(RuntimeError, match="not built"):
+        ops.attention_cls(q, qkv, 1)                        # head_dim 128
+    with pytest.raises(RuntimeError):
+        ops.attention_cls(q, qkv.half(), 2)                 # fp16 K | V
+
+
+# Diffuse softmax: uniform +-1.5 inputs (what test_attention_dense uses), rounded to bf16 first for the bf16 form, ragged prefix mask,
+# against fp64.  The bound is the project's bound for the fp32 dense attention on this distribution.
+CLS_DIFFUSE_BOUND = 2e-5
+
+
+@pytest.mark.parametrize("kv_dtype,dh,S", [(torch.float32, 64, 300), (torch.bfloat16, 64, 300), (torch.float32, 32, 600)],
+                         ids=lambda x: _ID.get(x, str(x)))
+def test_attention_cls_diffuse_softmax_against_fp64(kv_dtype, dh, S):
+    """Observed on MI355X: 4.9e-8 (f32, head_dim 64), 4.8e-8 (bf16 K | V), 3.0e-8 (head_dim 32)"""
+    from mgea import ops
+    B, H = CLS_B, CLS_H
+    D = H * dh
+    g = torch.Generator().manual_seed(11 + dh)
+    qkv = ((torch.rand(B, S, 3 * D, generator=g) * 2 - 1) * 1.5).to(kv_dtype)
+    qrow = ((torch.rand(B, D, generator=g) * 2 - 1) * 1.5).float()
+    valid = _cls_valid("prefix", S, dh)
+    k, v = (qkv[..., i * D:(i + 1) * D].reshape(B, S, H, dh).double().numpy() for i in (1, 2))
+    want = _ref64(qrow.reshape(B, 1, H, dh).double().numpy(), k, v, valid).reshape(B, D)
+    got = ops.attention_cls(qrow.cuda(), qkv.cuda(), H, mask=torch.from_numpy(valid).to(torch.int32).cuda()).double().cpu().numpy()
+    err = float(np.abs(got - want).max())
+    print(f"[attention_cls diffuse] {_ID[kv_dtype]} dh={dh} S={S}: max |out - fp64| = {err:.3e} (bound {CLS_DIFFUSE_BOUND:.1e})")
+    assert err < CLS_DIFFUSE_BOUND
+
+
 # ---- the exact-fp32 dense attention ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("T", [65, 129, 1000])
 def test_attention_f32_counts_every_valid_key_exactly_once(T):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Is the device code of two builds of csrc/ the same?  Needs no GPU.
-  python3 tools/kernel_diff.py PARENT_BUILD_DIR CHANGE_BUILD_DIR [--moved bf16=gemm16,attn16,rows16] [--out FILE]
+  python3 tools/kernel_diff.py PARENT_BUILD_DIR CHANGE_BUILD_DIR [--moved OLD=NEW1,NEW2] [--out FILE]
 For every *.o of both directories the gfx950 code object is taken out of the fat binary (llvm-objcopy --dump-section .hip_fatbin,
 clang-offload-bundler --unbundle).  Objects present under one name on both sides are compared by sha256.  For --moved OLD=NEW,...
 the kernels of OLD.o are looked up in the NEW objects and compared symbol by symbol: the disassembled instruction text (addresses
@@ -58,10 +58,10 @@ def kernels(co):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent"); ap.add_argument("change")
-    ap.add_argument("--moved", default="bf16=gemm16,attn16,rows16")
+    ap.add_argument("--moved", default="")
     ap.add_argument("--out")
     a = ap.parse_args()
-    old_name, new_names = a.moved.split("=")[0], a.moved.split("=")[1].split(",")
+    old_name, new_names = (a.moved.split("=")[0], a.moved.split("=")[1].split(",")) if a.moved else (None, [])
     lines, bad = [], 0
     with tempfile.TemporaryDirectory() as tmp:
         names = lambda d: sorted(f[:-2] for f in os.listdir(d) if f.endswith(".o"))
@@ -80,13 +80,14 @@ def main():
         extra = [n for n in names(a.change) if n not in names(a.parent) and n not in new_names]
         bad += len(extra)
         lines += [f"{n}.o  only in the change" for n in extra]
-        old = kernels(code_object(os.path.join(a.parent, old_name + ".o"), tmp))
+        old = kernels(code_object(os.path.join(a.parent, old_name + ".o"), tmp)) if old_name else {}
         new, where = {}, {}
         for n in new_names:
             for k, v in kernels(code_object(os.path.join(a.change, n + ".o"), tmp)).items():
                 new[k], where[k] = v, n
-        lines.append(f"# kernels of {old_name}.o ({len(old)}) against {', '.join(x + '.o' for x in new_names)} ({len(new)}): "
-                     "symbol, file, instructions, instruction text and resource record identical")
+        if old_name:
+            lines.append(f"# kernels of {old_name}.o ({len(old)}) against {', '.join(x + '.o' for x in new_names)} ({len(new)}): "
+                         "symbol, file, instructions, instruction text and resource record identical")
         for k in sorted(set(old) | set(new)):
             if k not in old or k not in new:
                 bad += 1
