@@ -706,6 +706,119 @@ int mgea_op_slab_qkv_scatter(const float* p_dev, int32_t S, int64_t ps, int32_t 
                              const int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t n_head,
                              int32_t head_dim, void* stream);
 
+/* TEST ONLY: the kernels that END a decode step (csrc/step_tail.hip, the fused tail of csrc/sampler.hip) and the row kernels around the
+ * decoder's prefill, one launch per call on caller buffers (tests/test_gpu_step_tail.py; the rule they are held to is written out in
+ * tests/step_tail_util.py).  Every call synchronises `stream` before it returns; a shape a launcher refuses is MGEA_EINVAL and nothing is
+ * launched.  No pointer is range-checked: the caller sizes every buffer as documented here.
+ *
+ * mgea_op_step_tail: one end-of-step launch over B rows (1 <= B <= 512), chosen by `kind`:
+ *   0  argmax_advance_kernel          (max, argmax) partials -> sampled, the rows' bookkeeping
+ *   1  argmax_advance_embed_kernel    the same + the NEXT step's embedding: x (k-tiled) and stats [B][4] = (mean, M2 / 2) x 2, or with
+ *                                     qkv0_dev != NULL the table form: x, qkv [B][3 C] = row [fed id] of qkv0 [vocab][3 C], its K | V at
+ *                                     position ctx_len (as the next step reads it) of the one-layer page image, no statistics
+ *   2  advance_kernel / advance_scored_kernel   sampled_dev is read; presence_dev != NULL: the PENALTY instantiation (bitmaps of
+ *                                     ceil(V / 32) words per row); logprob_hist_dev != NULL: the scored kernel files logprob_step_dev /
+ *                                     choice_step_dev [B] in logprob_hist_dev / choice_hist_dev [B][hist_stride] (all four required)
+ *   3  embed_qkv0_kernel              the table form of kind 1 for ids = cur_ids_dev at ctx_len_dev, no bookkeeping; an id outside
+ *                                     [0, vocab) is clamped and sets bit 0 of *err_flag_dev (or NULL)
+ *   4  sample_kernel with its fused tail   logits_dev [B][V] (V == vocab), rows required; the instantiation follows the optional parts:
+ *                                     presence_dev (PENALTY), logits_rows (BIAS: the rows' vectors are gathered into a temporary [B][V]
+ *                                     buffer as in mgea_op_sample_rows_biased), logprob_hist_dev (scored: forced_dev [B] with
+ *                                     forced_stride 0 or [B][forced_stride], the histories [B][hist_stride], choice_hist_dev may be
+ *                                     NULL, bit 0 of *err_flag_dev for a clamped forced id), class_of_dev (GRAMMAR: next_dev
+ *                                     [n_state][n_class], states_dev [B] read and written, done_dev is the rows' finished flags; the
+ *                                     allow bitmask is built first by its own kernel, as in mgea_op_sample_rows_grammar; bit 1 of
+ *                                     *err_flag_dev for a banned id).  The step index of the draw is row_step_dev[b].
+ * The rows' state: cur_ids_dev, ctx_len_dev, done_dev, row_step_dev [B] and n_done_dev [1] int32, ids_out_dev [B][n_steps] or NULL.
+ * rows [B] (host) or NULL: with records every row reads its own eos_id and max_new_tokens (0 = no budget; the records are not held to
+ * n_steps here) and ctx_cap[b] (host [B] or NULL = no cap) from a temporary device copy of the records the call builds; with NULL the
+ * by-value eos_id holds and no row has a budget or a cap.  The embedding (kinds 1, 3, 4): tok_emb_dev [vocab][C], pos_emb_dev
+ * [pos_rows][C], x_dev = the k-tiled layout: ceil(B / 64) * 64 * C floats when C % 32 == 0; a width that is no multiple of 32 leaves its
+ * last 32-wide k-chunk partly used, so x_dev then needs 64 * round_up(C, 32) floats and holds ONE row group: C % 32 != 0 with B > 64 is
+ * MGEA_EINVAL.  C % 4 == 0, C <= 4096, and C <= 1024 with C % head_dim == 0 and
+ * fp32 pages (page_dtype MGEA_DTYPE_F32) for the table form, whose page image is ONE layer of n_pages pages with page_table_dev
+ * [B][max_pages]; arith_batch > 0 (>= B, max_pages * arith_batch <= n_pages): physical page = j * arith_batch + b, the table is not
+ * read.  reserved must be 0. */
+typedef struct mgea_step_tail_args {
+    int32_t kind, B, n_steps, eos_id;
+    int32_t* cur_ids_dev;
+    int32_t* ctx_len_dev;
+    int32_t* done_dev;
+    int32_t* row_step_dev;
+    int32_t* n_done_dev;
+    int32_t* ids_out_dev;              /* [B][n_steps] or NULL */
+    const mgea_row_sampler* rows;      /* host [B] or NULL */
+    const int32_t* ctx_cap;            /* host [B] or NULL */
+    const mgea_row_logits* logits_rows;/* host [B] or NULL (kind 4) */
+    /* partials (kinds 0, 1) */
+    const float* pval_dev;             /* [B][n_tiles] */
+    const int32_t* pidx_dev;
+    int32_t n_tiles;
+    int32_t reserved;                  /* 0 */
+    int32_t* sampled_dev;              /* [B]: written by kinds 0, 1, 4, read by kind 2 */
+    /* the next step's embedding (kinds 1, 3, 4) */
+    const float* tok_emb_dev;
+    const float* pos_emb_dev;
+    float* x_dev;
+    float* stats_dev;
+    int32_t C, vocab, pos_rows, absolute_pos;
+    /* the qkv0 table form */
+    const float* qkv0_dev;
+    float* qkv_dev;
+    void* pages_dev;
+    const int32_t* page_table_dev;
+    int32_t n_pages, page_dtype, n_head, head_dim, arith_batch, max_pages;
+    /* presence and scores (kinds 2, 4) */
+    uint32_t* presence_dev;
+    int32_t V, hist_stride;
+    const float* logprob_step_dev;
+    const float* choice_step_dev;
+    float* logprob_hist_dev;
+    float* choice_hist_dev;
+    int32_t* err_flag_dev;
+    /* the sampler (kind 4) */
+    const float* logits_dev;
+    const int32_t* forced_dev;
+    int32_t forced_stride, n_state, n_class, reserved2;   /* reserved2: 0 */
+    const int32_t* class_of_dev;
+    const int32_t* next_dev;
+    int32_t* states_dev;
+} mgea_step_tail_args;
+int mgea_op_step_tail(const mgea_step_tail_args* args, void* stream);
+/* The decoder's fp32 prefill embedding of rows m = b T + t: x[m] = tok_emb[ids[m]] + pos_emb[pos], pos = t (+ ctx_len_dev[b] when
+ * absolute_pos != 0 and ctx_len_dev != NULL), clamped to pos_rows - 1; rows with t >= lens_dev[b] (NULL: none) are zero rows.  An id
+ * outside [0, vocab) is clamped and, for a real row, sets bit 0 of *err_flag_dev (or NULL).  C % 4 == 0, C <= 4096.
+ *   form 0 (embed_stats_kernel):  x_out_dev k-tiled, B T <= 512: ceil(B T / 64) * 64 * C floats when C % 32 == 0, else 64 * round_up(C, 32)
+ *                                 floats and B T <= 64 (more rows: MGEA_EINVAL, as for mgea_op_step_tail); aux_out_dev = stats [B T][4] = (mean, M2 / 2,
+ *                                 mean, M2 / 2) of the row; ln_w_dev / ln_b_dev / eps are ignored;
+ *   form 1 (embed_ln_kernel):     x_out_dev [B T][C] row-major, aux_out_dev = xn = LayerNorm(x; ln_w, ln_b, eps) [B T][C]; ln_w_dev ==
+ *                                 NULL: x only, aux_out_dev is not touched. */
+int mgea_op_dec_embed(int32_t form, const int32_t* ids_dev, const int32_t* lens_dev, const int32_t* ctx_len_dev, const float* tok_emb_dev,
+                      const float* pos_emb_dev, float* x_out_dev, float* aux_out_dev, const float* ln_w_dev, const float* ln_b_dev,
+                      float eps, int32_t B, int32_t T, int32_t C, int32_t vocab, int32_t pos_rows, int32_t absolute_pos,
+                      int32_t* err_flag_dev, void* stream);
+/* The bookkeeping launches around a generation, each alone (all arrays int32 / uint32 in device memory):
+ *   take_last:      cur_ids[b] = ids[b][n - 1], n = lens[b] (lens_dev NULL: T) clamped to [1, T];
+ *   add_lens:       ctx_len[b] += lens[b] (lens_dev NULL: T), unclamped;
+ *   presence_seed:  presence[b] (ceil(V / 32) words) = the set of the first n ids of ids[b] (n = lens[b] clamped to [0, T], NULL: T)
+ *                   that lie in [0, V); the row is stored whole, so older bits are cleared.  V > 14336 is MGEA_EINVAL;
+ *   unpark_rows:    done 2 -> 1 with ctx_len + 1; every other row untouched;
+ *   grammar_allow:  allow[s][w] bit k = next[s][32 w + k] >= 0 for 32 w + k < n_class, words = ceil(n_class / 32) per state;
+ *                   MGEA_EINVAL unless 1 <= n_state, n_class <= 4096 and n_state * n_class <= 2^20. */
+int mgea_op_take_last(const int32_t* ids_dev, const int32_t* lens_dev, int32_t* cur_ids_dev, int32_t B, int32_t T, void* stream);
+int mgea_op_add_lens(int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t T, int32_t B, void* stream);
+int mgea_op_presence_seed(const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t V, uint32_t* presence_dev,
+                          void* stream);
+int mgea_op_unpark_rows(int32_t* done_dev, int32_t* ctx_len_dev, int32_t B, void* stream);
+int mgea_op_grammar_allow(const int32_t* next_dev, int32_t n_state, int32_t n_class, uint32_t* allow_dev, void* stream);
+/* The rows' device records as a generation builds them, read back: rows == NULL: fill_sampler_params_kernel writes B records from *s
+ * with stream = b; otherwise the records built from rows [B] (host) are copied.  reserved > 0: clamp_budgets_kernel then sets
+ * max_new = min(max_new, reserved - n) with n = lens_dev[b] (NULL: T) clamped to [1, T], and ctx_cap = reserved (T >= reserved is
+ * MGEA_EINVAL); reserved == 0: no clamp.  rows_out [B] (host) receives every record in the public form (max_new_tokens = max_new,
+ * INT32_MAX = none; repetition_penalty = the record's penalty), ctx_cap_out [B] (host) its ctx_cap (INT32_MAX = none). */
+int mgea_op_row_budgets(const mgea_sampler_config* s, const mgea_row_sampler* rows, int32_t B, const int32_t* lens_dev, int32_t T,
+                        int32_t reserved, mgea_row_sampler* rows_out, int32_t* ctx_cap_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -581,6 +581,192 @@ int mgea_op_slab_qkv_scatter(const float* p_dev, int32_t S, int64_t ps, int32_t 
                               0, page_table_dev, max_pages, ctx_len_dev, lens_dev, B, T, C, (hipStream_t)stream);
 }
 
+// ---- the kernels that end a decode step and the decoder's prefill row kernels, one launch per call (tests) ----
+// the launch's status and the stream's, in that order
+static int op_finish(int rc, hipStream_t st) {
+    const hipError_t e = hipStreamSynchronize(st);
+    MGEA_TRY(rc);
+    MGEA_CHECK_HIP(e);
+    return MGEA_OK;
+}
+
+int mgea_op_step_tail(const mgea_step_tail_args* a, void* stream) {
+    MGEA_REQUIRE(a && !a->reserved && !a->reserved2 && a->kind >= 0 && a->kind <= 4, MGEA_EINVAL, "op_step_tail: NULL block, reserved != 0 or bad kind");
+    const int kind = a->kind, B = a->B;
+    MGEA_REQUIRE(B >= 1 && B <= MGEA_FUSED_MAX_ROWS, MGEA_EINVAL, "op_step_tail: %d rows (1..%d)", B, MGEA_FUSED_MAX_ROWS);
+    MGEA_REQUIRE(a->cur_ids_dev && a->ctx_len_dev && (kind == 3 || (a->done_dev && a->row_step_dev && a->n_done_dev && a->sampled_dev)) &&
+                     a->n_steps >= 0,
+                 MGEA_EINVAL, "op_step_tail: the rows' state is incomplete");
+    hipStream_t st = (hipStream_t)stream;
+    const bool embeds = kind == 1 || kind == 3 || kind == 4, table = a->qkv0_dev != nullptr;
+    TailArgs t{};
+    t.s = StepState{a->cur_ids_dev, a->ctx_len_dev, a->done_dev, a->row_step_dev, a->n_done_dev, a->ids_out_dev, a->n_steps, a->eos_id, nullptr};
+    if (embeds) {
+        MGEA_REQUIRE(a->tok_emb_dev && a->pos_emb_dev && a->x_dev && (table || kind == 3 || a->stats_dev) && a->C > 0 && a->vocab > 0 &&
+                         a->pos_rows > 0,
+                     MGEA_EINVAL, "op_step_tail: the embedding's arguments are incomplete");
+        // k-tiled x: a width that is no multiple of 32 leaves its last k-chunk partly used, and the next 64-row group would start inside it
+        MGEA_REQUIRE(a->C % 32 == 0 || B <= 64, MGEA_EINVAL, "op_step_tail: a k-tiled x of width %d (no multiple of 32) holds at most 64 rows", a->C);
+        t.tok_emb = a->tok_emb_dev; t.pos_emb = a->pos_emb_dev; t.x = a->x_dev; t.stats = a->stats_dev;
+        t.C = a->C; t.vocab = a->vocab; t.pos_rows = a->pos_rows; t.absolute_pos = a->absolute_pos;
+        if (table) {
+            MGEA_REQUIRE(a->n_pages > 0 && a->max_pages > 0 && a->n_head > 0 && a->head_dim > 0 && a->head_dim % 4 == 0 &&
+                             (a->page_dtype == MGEA_DTYPE_F32 || a->page_dtype == MGEA_DTYPE_F16) &&
+                             (a->arith_batch > 0 ? a->arith_batch >= B && (int64_t)a->max_pages * a->arith_batch <= a->n_pages
+                                                 : a->arith_batch == 0 && a->page_table_dev != nullptr),
+                         MGEA_EINVAL, "op_step_tail: bad page image (a page table, or arith_batch >= B with max_pages * arith_batch <= n_pages)");
+            t.qkv0 = a->qkv0_dev; t.qkv = a->qkv_dev;
+            t.pool = op_pool(a->pages_dev, a->n_pages, a->n_head, a->head_dim, a->page_dtype == MGEA_DTYPE_F16, a->arith_batch);
+            t.page_table = a->page_table_dev; t.max_pages = a->max_pages;
+        }
+    }
+    const bool scored = a->logprob_hist_dev != nullptr, grammar = kind == 4 && a->class_of_dev != nullptr;
+    const int V = kind == 4 ? a->vocab : a->V;
+    if (kind == 0 || kind == 1) MGEA_REQUIRE(a->pval_dev && a->pidx_dev && a->n_tiles >= 1, MGEA_EINVAL, "op_step_tail: no partials");
+    if (kind == 2)
+        MGEA_REQUIRE((!a->presence_dev || V > 0) && (!scored || (a->logprob_step_dev && a->choice_step_dev && a->choice_hist_dev && a->hist_stride >= 0)),
+                     MGEA_EINVAL, "op_step_tail: advance: a bitmap without V, or an incomplete score file");
+    if (kind == 4) {
+        MGEA_REQUIRE(a->logits_dev && a->rows && a->V == a->vocab && (!scored || a->hist_stride >= 0) && (scored || !a->forced_dev) &&
+                         a->forced_stride >= 0,
+                     MGEA_EINVAL, "op_step_tail: sampler: logits, records, V == vocab; forced ids need the histories");
+        MGEA_REQUIRE(!grammar || (a->next_dev && a->states_dev && a->n_class >= 1 && a->n_class <= MGEA_GRAMMAR_MAX_CLASSES && a->n_state >= 1 &&
+                                  a->n_state <= MGEA_GRAMMAR_MAX_STATES && (int64_t)a->n_state * a->n_class <= MGEA_GRAMMAR_MAX_CELLS),
+                     MGEA_EINVAL, "op_step_tail: sampler: bad grammar arguments");
+    }
+    if (kind == 4)   // launch_sample's own refusals, taken before anything is enqueued
+        MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB && t.C % 4 == 0 && t.C <= 4096 && tail_qkv0_ok(t), MGEA_EINVAL,
+                     "op_step_tail: sampler: vocab %d or the fused tail's shape is refused", V);
+    // the rows' records -> a temporary device buffer (freed on return: the stream is synchronised first)
+    std::vector<SamplerParams> rec;
+    SamplerParams* rec_dev = nullptr;
+    float* bias_dev = nullptr;
+    uint32_t *allow_dev = nullptr, *pres_tmp = nullptr;
+    DevGroup tmp;
+    const mgea_row_logits* lrows = kind == 4 ? a->logits_rows : nullptr;
+    if (a->rows) {
+        MGEA_TRY(check_row_samplers(a->rows, B, kind == 4 ? V : MGEA_SAMPLER_MAX_VOCAB, -1, "op_step_tail"));
+        if (lrows) MGEA_TRY(check_row_logits(lrows, B, -1, "op_step_tail"));
+        rec.resize((size_t)B);
+        build_row_records(a->rows, lrows, B, -1, rec.data());
+        for (int b = 0; a->ctx_cap && b < B; ++b) rec[b].ctx_cap = a->ctx_cap[b];
+        MGEA_REQUIRE(tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) == MGEA_OK, MGEA_ENOMEM, "op_step_tail: allocation of the records failed");
+        MGEA_CHECK_HIP(hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
+        t.s.params = rec_dev;
+    }
+    if (kind == 0) return op_finish(launch_argmax_advance(a->pval_dev, a->pidx_dev, a->n_tiles, t.s, a->sampled_dev, B, st), st);
+    if (kind == 1) return op_finish(launch_argmax_advance_embed(a->pval_dev, a->pidx_dev, a->n_tiles, t, a->sampled_dev, B, st), st);
+    if (kind == 2) {
+        const ScoreFile f{a->logprob_step_dev, a->choice_step_dev, a->logprob_hist_dev, a->choice_hist_dev, a->hist_stride};
+        return op_finish(launch_advance(a->sampled_dev, t.s, B, st, a->presence_dev, V, scored ? &f : nullptr), st);
+    }
+    if (kind == 3) return op_finish(launch_embed_qkv0(a->cur_ids_dev, a->ctx_len_dev, t, B, a->err_flag_dev, st), st);
+    // kind 4: the sampler with its fused tail
+    SampleCall c{};
+    c.logits = a->logits_dev; c.B = B; c.V = V; c.ids_out = a->sampled_dev; c.params_dev = rec_dev; c.row_step_dev = a->row_step_dev;
+    c.tail = &t;
+    c.presence = a->presence_dev;
+    if (lrows || grammar) {
+        MGEA_REQUIRE(tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) == MGEA_OK, MGEA_ENOMEM, "op_step_tail: allocation of the bias rows failed");
+        for (int b = 0; lrows && b < B; ++b)
+            if (lrows[b].bias_dev)
+                MGEA_CHECK_HIP(hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st));
+        c.bias = bias_dev;
+    }
+    if (scored) c.score = ScoreArgs{a->forced_dev, a->forced_stride, a->logprob_hist_dev, a->choice_hist_dev, a->hist_stride, a->err_flag_dev};
+    if (grammar) {   // as mgea_op_sample_rows_grammar builds it: the allow bitmask by its own kernel, empty bitmaps where none came
+        const size_t nw = (size_t)a->n_state * grammar_words(a->n_class), np = (size_t)B * presence_words(V);
+        MGEA_REQUIRE(tmp.alloc(&allow_dev, nw * sizeof(uint32_t)) == MGEA_OK && (c.presence || tmp.alloc(&pres_tmp, np * sizeof(uint32_t)) == MGEA_OK),
+                     MGEA_ENOMEM, "op_step_tail: allocation of the grammar's bitmask failed");
+        if (pres_tmp) {
+            MGEA_CHECK_HIP(hipMemsetAsync(pres_tmp, 0, np * sizeof(uint32_t), st));
+            c.presence = pres_tmp;
+        }
+        c.grammar = GrammarArgs{a->class_of_dev, a->next_dev, allow_dev, a->states_dev, a->states_dev, a->done_dev,
+                                a->n_state, a->n_class, grammar_words(a->n_class), a->err_flag_dev};
+        const int rc = launch_grammar_allow(a->next_dev, a->n_state, a->n_class, allow_dev, st);
+        if (rc != MGEA_OK) return op_finish(rc, st);
+    }
+    return op_finish(launch_sample(c, st), st);
+}
+
+int mgea_op_dec_embed(int32_t form, const int32_t* ids_dev, const int32_t* lens_dev, const int32_t* ctx_len_dev, const float* tok_emb_dev,
+                      const float* pos_emb_dev, float* x_out_dev, float* aux_out_dev, const float* ln_w_dev, const float* ln_b_dev,
+                      float eps, int32_t B, int32_t T, int32_t C, int32_t vocab, int32_t pos_rows, int32_t absolute_pos,
+                      int32_t* err_flag_dev, void* stream) {
+    MGEA_REQUIRE((form == 0 || form == 1) && ids_dev && tok_emb_dev && pos_emb_dev && x_out_dev && B > 0 && T > 0 && C > 0 && vocab > 0 &&
+                     pos_rows > 0,
+                 MGEA_EINVAL, "op_dec_embed: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (form == 0) {
+        MGEA_REQUIRE(aux_out_dev, MGEA_EINVAL, "op_dec_embed: form 0 writes the statistics to aux_out_dev");
+        MGEA_REQUIRE(C % 32 == 0 || (int64_t)B * T <= 64, MGEA_EINVAL, "op_dec_embed: a k-tiled x of width %d (no multiple of 32) holds at most 64 rows", C);
+        return op_finish(launch_embed_stats(ids_dev, lens_dev, ctx_len_dev, tok_emb_dev, pos_emb_dev, x_out_dev, aux_out_dev, B, T, C, vocab,
+                                            pos_rows, absolute_pos, err_flag_dev, st), st);
+    }
+    MGEA_REQUIRE(!ln_w_dev || (ln_b_dev && aux_out_dev), MGEA_EINVAL, "op_dec_embed: LayerNorm weights without ln_b_dev / aux_out_dev");
+    return op_finish(launch_embed_ln(ids_dev, lens_dev, ctx_len_dev, tok_emb_dev, pos_emb_dev, x_out_dev, aux_out_dev, ln_w_dev, ln_b_dev, eps,
+                                     B, T, C, vocab, pos_rows, absolute_pos, err_flag_dev, st), st);
+}
+
+int mgea_op_take_last(const int32_t* ids_dev, const int32_t* lens_dev, int32_t* cur_ids_dev, int32_t B, int32_t T, void* stream) {
+    MGEA_REQUIRE(ids_dev && cur_ids_dev && B > 0 && T > 0, MGEA_EINVAL, "op_take_last: bad argument");
+    return op_finish(launch_take_last(ids_dev, lens_dev, cur_ids_dev, B, T, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int mgea_op_add_lens(int32_t* ctx_len_dev, const int32_t* lens_dev, int32_t T, int32_t B, void* stream) {
+    MGEA_REQUIRE(ctx_len_dev && B > 0, MGEA_EINVAL, "op_add_lens: bad argument");
+    return op_finish(launch_add_lens(ctx_len_dev, lens_dev, T, B, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int mgea_op_presence_seed(const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t V, uint32_t* presence_dev,
+                          void* stream) {
+    MGEA_REQUIRE(ids_dev && presence_dev && B > 0 && T > 0, MGEA_EINVAL, "op_presence_seed: bad argument");
+    return op_finish(launch_presence_seed(ids_dev, lens_dev, B, T, V, presence_dev, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int mgea_op_unpark_rows(int32_t* done_dev, int32_t* ctx_len_dev, int32_t B, void* stream) {
+    MGEA_REQUIRE(done_dev && ctx_len_dev && B > 0, MGEA_EINVAL, "op_unpark_rows: bad argument");
+    return op_finish(launch_unpark_rows(done_dev, ctx_len_dev, B, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int mgea_op_grammar_allow(const int32_t* next_dev, int32_t n_state, int32_t n_class, uint32_t* allow_dev, void* stream) {
+    MGEA_REQUIRE(next_dev && allow_dev, MGEA_EINVAL, "op_grammar_allow: NULL argument");
+    return op_finish(launch_grammar_allow(next_dev, n_state, n_class, allow_dev, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int mgea_op_row_budgets(const mgea_sampler_config* s, const mgea_row_sampler* rows, int32_t B, const int32_t* lens_dev, int32_t T,
+                        int32_t reserved, mgea_row_sampler* rows_out, int32_t* ctx_cap_out, void* stream) {
+    MGEA_REQUIRE((s || rows) && B > 0 && T > 0 && reserved >= 0 && rows_out && ctx_cap_out, MGEA_EINVAL, "op_row_budgets: bad argument");
+    MGEA_REQUIRE(reserved == 0 || T < reserved, MGEA_EINVAL, "op_row_budgets: prompt width %d leaves no room in %d tokens", T, reserved);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<SamplerParams> rec((size_t)B);
+    SamplerParams* rec_dev = nullptr;
+    DevGroup tmp;
+    MGEA_REQUIRE(tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) == MGEA_OK, MGEA_ENOMEM, "op_row_budgets: allocation of the records failed");
+    int rc = MGEA_OK;
+    if (rows) {
+        MGEA_TRY(check_row_samplers(rows, B, MGEA_SAMPLER_MAX_VOCAB, -1, "op_row_budgets"));
+        build_row_records(rows, nullptr, B, -1, rec.data());
+        MGEA_CHECK_HIP(hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
+    } else {
+        rc = launch_fill_sampler_params(rec_dev, sampler_params(*s), B, st);
+    }
+    if (rc == MGEA_OK && reserved > 0) rc = launch_clamp_budgets(rec_dev, lens_dev, T, B, reserved, st);
+    if (rc == MGEA_OK && hipMemcpyAsync(rec.data(), rec_dev, (size_t)B * sizeof(SamplerParams), hipMemcpyDeviceToHost, st) != hipSuccess) {
+        set_error("op_row_budgets: copy of the records failed");
+        rc = MGEA_EHIP;
+    }
+    MGEA_TRY(op_finish(rc, st));
+    for (int b = 0; b < B; ++b) {
+        const SamplerParams& p = rec[b];
+        rows_out[b] = mgea_row_sampler{p.temperature, p.top_k, p.top_p, p.penalty, p.eos_id, p.max_new,
+                                       ((uint64_t)p.seed_hi << 32) | p.seed_lo, p.stream, 0u};
+        ctx_cap_out[b] = p.ctx_cap;
+    }
+    return MGEA_OK;
+}
+
 }  // extern "C"
 
 static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,

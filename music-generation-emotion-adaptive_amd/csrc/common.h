@@ -542,7 +542,7 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 }
 
 // End of a decode step for row b, by one workgroup of >= 256 threads whose thread 0 holds the new token `tok` (threads >= 256 only take part
-// in the barriers: the sampler's workgroup has 1024):
+// in the barriers; the sampler's workgroup has SAMP_NT = 256):
 // the sampler-loop bookkeeping of api_cache.py:179-181 (append, EOS stop) and the NEXT step's embedding
 // x[b] = tok_emb[fed] + pos_emb[pos] (k-tiled) with its LayerNorm statistics (two equal half-row partials).
 // st_* = the row's state as loaded by thread 0 at kernel start.  sh: >= 7 floats of shared scratch.
@@ -556,6 +556,12 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 // A finished row still runs every later step of its batch (fed its last token at position ctx_len, attending to ctx_len + 1 keys).  A
 // row that finishes with its pages full (ctx_len = ctx_cap) would read one key past them: it is parked one position short instead --
 // done = 2, ctx_len - 1, where its later steps only rewrite the last key -- and launch_unpark_rows restores both after the loop.
+// (Each later step of a parked row stores the K | V of its re-fed last token at position ctx_len, over the key of the token fed before
+// it: after unpark the row's ctx_len counts all its tokens, but its last cache position holds its final token, not the one before it
+// as a fresh prefill of its ids would.  Nobody attends from a finished row again; a caller that continued one would have to prefill it anew.)
+// Every row's NEXT position is therefore *len_out, the parked row's too: advance_embed_row embeds at it and embed_qkv0_row caches at it,
+// as the unfused pair (advance_kernel, then an embedding kernel that reads ctx_len) does.  The rule is written out, and every caller
+// held to it, in tests/step_tail_util.py and tests/test_gpu_step_tail.py.
 __device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int tok, int step, int fed, int len, int done,
                                             int* len_out = nullptr) {
     int out = -1, next_len = len;
@@ -619,7 +625,7 @@ __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::Ta
         sampled[b] = tok;
         int next_len;
         const int fed = end_row_step(t.s, b, tok, st_step, st_fed, st_len, st_done, &next_len);
-        const int len = st_done ? st_len : st_len + 1;
+        const int len = next_len;   // the position the row is fed at = its ctx_len as the next step reads it (a row parked in this step: st_len)
         shi[6] = next_len;
         if constexpr (PENALTY) {
             if (!st_done && (unsigned)tok < (unsigned)t.vocab) {

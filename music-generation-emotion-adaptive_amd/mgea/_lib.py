@@ -66,6 +66,23 @@ class DecodeGemmArgs(C.Structure):
                 ("T", _I32), ("reserved", _I32), ("partials_dev", _P)]
 
 
+class StepTailArgs(C.Structure):
+    """mgea_step_tail_args: one end-of-step launch on caller buffers (mgea_op_step_tail, test only)."""
+    _fields_ = [("kind", _I32), ("B", _I32), ("n_steps", _I32), ("eos_id", _I32),
+                ("cur_ids_dev", _P), ("ctx_len_dev", _P), ("done_dev", _P), ("row_step_dev", _P), ("n_done_dev", _P), ("ids_out_dev", _P),
+                ("rows", C.POINTER(RowSampler)), ("ctx_cap", C.POINTER(_I32)), ("logits_rows", C.POINTER(RowLogits)),
+                ("pval_dev", _P), ("pidx_dev", _P), ("n_tiles", _I32), ("reserved", _I32), ("sampled_dev", _P),
+                ("tok_emb_dev", _P), ("pos_emb_dev", _P), ("x_dev", _P), ("stats_dev", _P),
+                ("C", _I32), ("vocab", _I32), ("pos_rows", _I32), ("absolute_pos", _I32),
+                ("qkv0_dev", _P), ("qkv_dev", _P), ("pages_dev", _P), ("page_table_dev", _P),
+                ("n_pages", _I32), ("page_dtype", _I32), ("n_head", _I32), ("head_dim", _I32), ("arith_batch", _I32), ("max_pages", _I32),
+                ("presence_dev", _P), ("V", _I32), ("hist_stride", _I32),
+                ("logprob_step_dev", _P), ("choice_step_dev", _P), ("logprob_hist_dev", _P), ("choice_hist_dev", _P), ("err_flag_dev", _P),
+                ("logits_dev", _P), ("forced_dev", _P), ("forced_stride", _I32), ("n_state", _I32), ("n_class", _I32), ("reserved2", _I32),
+                ("class_of_dev", _P), ("next_dev", _P), ("states_dev", _P)]
+
+
+TAIL_ARGMAX, TAIL_ARGMAX_EMBED, TAIL_ADVANCE, TAIL_EMBED_QKV0, TAIL_SAMPLE = 0, 1, 2, 3, 4
 DECODE_GEMM_PLAN_INTS = 11
 EPI_QKV, EPI_RES, EPI_ACT, EPI_LOGITS = 0, 1, 2, 3
 DG_SKINNY, DG_HEAD, DG_GEMV = 0, 1, 2
@@ -155,6 +172,15 @@ PROTOTYPES = {
     "mgea_op_slab_bias_res_ln": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _F, _I32, _I32, _I32, _P]),
     "mgea_op_slab_logits_argmax": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P]),
     "mgea_op_slab_qkv_scatter": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_step_tail": (C.c_int, [C.POINTER(StepTailArgs), _P]),
+    "mgea_op_dec_embed": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "mgea_op_take_last": (C.c_int, [_P, _P, _P, _I32, _I32, _P]),
+    "mgea_op_add_lens": (C.c_int, [_P, _P, _I32, _I32, _P]),
+    "mgea_op_presence_seed": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "mgea_op_unpark_rows": (C.c_int, [_P, _P, _I32, _P]),
+    "mgea_op_grammar_allow": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "mgea_op_row_budgets": (C.c_int, [C.POINTER(SamplerConfig), C.POINTER(RowSampler), _I32, _P, _I32, _I32, C.POINTER(RowSampler),
+                                      C.POINTER(_I32), _P]),
 }
 
 _lib = None

@@ -998,3 +998,196 @@ def merge_partials(partials: torch.Tensor, M: int, R: int, P: int) -> torch.Tens
     idx = p[R * P: 2 * R * P].view(torch.int32).view(R, P)[:M].long()
     best = val.max(1, keepdim=True).values
     return torch.where(val == best, idx, torch.full_like(idx, 2 ** 31 - 1)).min(1).values
+
+
+# ---- the kernels that end a decode step and the decoder's prefill row kernels, one launch per call (tests only) ----
+def _buf(t: Optional[torch.Tensor], n: int, dtype, what: str) -> Optional[torch.Tensor]:
+    """a caller buffer of an op_* call: on the device, contiguous, of `dtype`, at least n elements (None passes)"""
+    if t is None:
+        return None
+    if not t.is_cuda or not t.is_contiguous() or t.dtype != dtype or t.numel() < int(n):
+        raise RuntimeError(f"{what}: needs a contiguous {dtype} device tensor of at least {int(n)} elements")
+    return t
+
+
+def tiled_floats(M: int, N: int) -> int:
+    """floats of a k-tiled [M, N] buffer: whole 64-row groups; a width that is no multiple of 32 leaves its last 32-wide k-chunk
+    partly used, and such a buffer holds one row group only (the next group would start inside that chunk)"""
+    if N % 32 == 0:
+        return (M + 63) // 64 * 64 * N
+    if M > 64:
+        raise RuntimeError(f"a k-tiled buffer of width {N} (no multiple of 32) holds at most 64 rows")
+    return 64 * ((N + 31) // 32 * 32)
+
+
+def step_tail(kind: int, B: int, state: dict, *, rows=None, ctx_cap=None, eos_id: int = -1, partials=None, sampled=None, embed=None,
+              table=None, presence=None, V: int = 0, scores=None, sampler=None, grammar=None, err_flag=None):
+    """One end-of-step launch through mgea_op_step_tail (include/mgea.h) on caller buffers, all written in place.
+    kind: _lib.TAIL_ARGMAX / TAIL_ARGMAX_EMBED / TAIL_ADVANCE / TAIL_EMBED_QKV0 / TAIL_SAMPLE.
+    state   dict(cur_ids, ctx_len, done, row_step [>= B] int32, n_done [1], ids_out [B * n_steps] or None, n_steps)
+    rows    None (the by-value eos_id, no budgets) or B mgea.decoder.RowSampling (max_new_tokens is not held to n_steps here);
+            ctx_cap: None or B ints
+    partials (pval fp32, pidx int32 [B * n_tiles], n_tiles); sampled int32 [B]
+    embed   dict(tok_emb [vocab * C], pos_emb [pos_rows * C], x k-tiled, stats [4 B] or None, C, vocab, pos_rows, absolute_pos)
+    table   dict(qkv0 [vocab * 3 C], qkv [B * 3 C], pages (one layer, fp32 or fp16), n_pages, n_head, head_dim, page_table int32
+            [B, max_pages], arith_batch=0)
+    presence int32 words [B * ceil(V / 32)] (kind 2 with V; kind 4: V = the embedding's vocab)
+    scores  kind 2: dict(logprob_step, choice_step [B], logprob_hist, choice_hist [B * stride], stride); kind 4: dict(logprob_hist,
+            choice_hist or None, stride, forced=None, forced_stride=0)
+    sampler dict(logits [B * V]); rows' logit_bias / min_new_tokens apply (the BIAS form) when any row sets one
+    grammar dict(class_of [V], next [n_state * n_class], n_state, n_class, states [B])
+    The buffers' sizes and the indices the kernels follow unguarded (ctx_len, row_step >= 0, page table entries) are checked here;
+    what the native call refuses raises RuntimeError and launches nothing."""
+    from .decoder import pack_row_logits, pack_rows
+    lib = _lib.load()
+    a = _lib.StepTailArgs()
+    keep = []
+    i32, f32 = torch.int32, torch.float32
+    a.kind, a.B, a.n_steps, a.eos_id = int(kind), int(B), int(state["n_steps"]), int(eos_id)
+    nb = max(int(B), 0)
+    for k in ("cur_ids", "ctx_len", "done", "row_step"):
+        t = _buf(state.get(k), nb, i32, f"step_tail: {k}")
+        setattr(a, k + "_dev", None if t is None else t.data_ptr())
+        if t is not None and k in ("ctx_len", "row_step") and nb and int(t[:nb].min()) < 0:
+            raise RuntimeError(f"step_tail: {k} must not be negative")
+    a.n_done_dev = ptr(_buf(state.get("n_done"), 1, i32, "step_tail: n_done"))
+    a.ids_out_dev = ptr(_buf(state.get("ids_out"), nb * a.n_steps, i32, "step_tail: ids_out"))
+    vocab = int(embed["vocab"]) if embed else 0
+    if rows is not None:
+        rows = list(rows)
+        if len(rows) != nb:
+            raise RuntimeError(f"step_tail: {nb} rows but {len(rows)} records")
+        recs = pack_rows(rows, vocab if kind == _lib.TAIL_SAMPLE else 14336)
+        keep.append(recs)
+        a.rows = recs
+        if kind == _lib.TAIL_SAMPLE:
+            lrecs, kp = pack_row_logits(rows, vocab, state["cur_ids"].device)
+            keep += [lrecs, kp]
+            if lrecs is not None:
+                a.logits_rows = lrecs
+    if ctx_cap is not None:
+        caps = (C.c_int32 * nb)(*[int(c) for c in ctx_cap])
+        keep.append(caps)
+        a.ctx_cap = caps
+    if partials is not None:
+        pval, pidx, n_tiles = partials
+        a.n_tiles = int(n_tiles)
+        a.pval_dev = ptr(_buf(pval, nb * a.n_tiles, f32, "step_tail: pval"))
+        a.pidx_dev = ptr(_buf(pidx, nb * a.n_tiles, i32, "step_tail: pidx"))
+    a.sampled_dev = ptr(_buf(sampled, nb, i32, "step_tail: sampled"))
+    if embed is not None:
+        Cm, pr = int(embed["C"]), int(embed["pos_rows"])
+        a.C, a.vocab, a.pos_rows, a.absolute_pos = Cm, vocab, pr, int(embed.get("absolute_pos", 0))
+        a.tok_emb_dev = ptr(_buf(embed["tok_emb"], vocab * Cm, f32, "step_tail: tok_emb"))
+        a.pos_emb_dev = ptr(_buf(embed["pos_emb"], pr * Cm, f32, "step_tail: pos_emb"))
+        a.x_dev = ptr(_buf(embed["x"], tiled_floats(nb, Cm) if Cm % 32 == 0 or nb <= 64 else 0, f32, "step_tail: x"))   # (else: the native call refuses)
+        a.stats_dev = ptr(_buf(embed.get("stats"), 4 * nb, f32, "step_tail: stats"))
+    if table is not None:
+        if embed is None:
+            raise RuntimeError("step_tail: the table form needs the embedding")
+        H, dh, n_pages = int(table["n_head"]), int(table["head_dim"]), int(table["n_pages"])
+        pages = table["pages"]
+        if pages.dtype not in (f32, torch.float16):
+            raise RuntimeError("step_tail: pages are fp32 or fp16")
+        _buf(pages, kv_page_elems(n_pages, H, dh), pages.dtype, "step_tail: pages")
+        pt = table["page_table"]
+        if pt.ndim != 2 or pt.shape[0] != nb or _buf(pt, 0, i32, "step_tail: page_table") is None or int(pt.min()) < 0 or int(pt.max()) >= n_pages:
+            raise RuntimeError("step_tail: page_table is int32 [B, max_pages] with entries in [0, n_pages)")
+        a.qkv0_dev = ptr(_buf(table["qkv0"], vocab * 3 * a.C, f32, "step_tail: qkv0"))
+        a.qkv_dev = ptr(_buf(table.get("qkv"), nb * 3 * a.C, f32, "step_tail: qkv"))
+        a.pages_dev, a.page_table_dev = ptr(pages), ptr(pt)
+        a.n_pages, a.page_dtype = n_pages, (_lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32)
+        a.n_head, a.head_dim, a.arith_batch, a.max_pages = H, dh, int(table.get("arith_batch", 0)), int(pt.shape[1])
+    a.V = vocab if kind == _lib.TAIL_SAMPLE else int(V)
+    a.presence_dev = ptr(_buf(presence, nb * presence_words(a.V), i32, "step_tail: presence"))
+    if scores is not None:
+        st = int(scores["stride"])
+        a.hist_stride = st
+        a.logprob_hist_dev = ptr(_buf(scores["logprob_hist"], nb * st, f32, "step_tail: logprob_hist"))
+        a.choice_hist_dev = ptr(_buf(scores.get("choice_hist"), nb * st, f32, "step_tail: choice_hist"))
+        a.logprob_step_dev = ptr(_buf(scores.get("logprob_step"), nb, f32, "step_tail: logprob_step"))
+        a.choice_step_dev = ptr(_buf(scores.get("choice_step"), nb, f32, "step_tail: choice_step"))
+        a.forced_stride = int(scores.get("forced_stride", 0))
+        a.forced_dev = ptr(_buf(scores.get("forced"), nb * max(a.forced_stride, 1), i32, "step_tail: forced"))
+    if sampler is not None:
+        a.logits_dev = ptr(_buf(sampler["logits"], nb * a.V, f32, "step_tail: logits"))
+    if grammar is not None:
+        ns, nc = int(grammar["n_state"]), int(grammar["n_class"])
+        cls = _buf(grammar["class_of"], a.V, i32, "step_tail: class_of")
+        nxt = _buf(grammar["next"], ns * nc, i32, "step_tail: next")
+        sts = _buf(grammar["states"], nb, i32, "step_tail: states")
+        if int(cls.min()) < 0 or int(cls.max()) >= nc or int(nxt.max()) >= ns or int(sts.max()) >= ns:
+            raise RuntimeError("step_tail: grammar tables out of range")
+        a.class_of_dev, a.next_dev, a.states_dev, a.n_state, a.n_class = ptr(cls), ptr(nxt), ptr(sts), ns, nc
+    a.err_flag_dev = ptr(_buf(err_flag, 1, i32, "step_tail: err_flag"))
+    check(lib.mgea_op_step_tail(C.byref(a), stream_ptr()))
+    del keep
+
+
+def dec_embed(form: int, ids: torch.Tensor, tok_emb: torch.Tensor, pos_emb: torch.Tensor, x_out: torch.Tensor, aux_out=None, *,
+              lens=None, ctx_len=None, ln_w=None, ln_b=None, eps: float = 1e-5, absolute_pos: int = 0, err_flag=None) -> None:
+    """The fp32 prefill embedding through mgea_op_dec_embed: ids int32 [B, T]; form 0 = embed_stats_kernel (x_out k-tiled, aux_out =
+    stats [B T, 4]), form 1 = embed_ln_kernel (x_out [B T, C] row-major, aux_out = xn, written when ln_w is given).  In place."""
+    lib = _lib.load()
+    B, T = ids.shape
+    vocab, Cm = tok_emb.shape
+    i32, f32 = torch.int32, torch.float32
+    M = B * T
+    _buf(ids, M, i32, "dec_embed: ids"), _buf(tok_emb, 0, f32, "dec_embed: tok_emb"), _buf(pos_emb, Cm, f32, "dec_embed: pos_emb")
+    _buf(x_out, (tiled_floats(M, Cm) if Cm % 32 == 0 or M <= 64 else 0) if form == 0 else M * Cm, f32, "dec_embed: x_out")
+    _buf(aux_out, 4 * M if form == 0 else M * Cm, f32, "dec_embed: aux_out")
+    _buf(lens, B, i32, "dec_embed: lens"), _buf(ctx_len, B, i32, "dec_embed: ctx_len")
+    if ctx_len is not None and int(ctx_len.min()) < 0:
+        raise RuntimeError("dec_embed: ctx_len must not be negative")
+    _buf(ln_w, Cm, f32, "dec_embed: ln_w"), _buf(ln_b, Cm, f32, "dec_embed: ln_b"), _buf(err_flag, 1, i32, "dec_embed: err_flag")
+    check(lib.mgea_op_dec_embed(int(form), ptr(ids), ptr(lens), ptr(ctx_len), ptr(tok_emb), ptr(pos_emb), ptr(x_out), ptr(aux_out), ptr(ln_w),
+                                ptr(ln_b), float(eps), B, T, Cm, vocab, pos_emb.shape[0], int(absolute_pos), ptr(err_flag), stream_ptr()))
+
+
+def take_last(ids: torch.Tensor, lens: Optional[torch.Tensor], cur_ids: torch.Tensor) -> None:
+    """cur_ids[b] = ids[b, n - 1], n = lens[b] (None: T) clamped to [1, T] (mgea_op_take_last); in place"""
+    B, T = ids.shape
+    _buf(ids, B * T, torch.int32, "take_last: ids"), _buf(lens, B, torch.int32, "take_last: lens"), _buf(cur_ids, B, torch.int32, "take_last: cur_ids")
+    check(_lib.load().mgea_op_take_last(ptr(ids), ptr(lens), ptr(cur_ids), B, T, stream_ptr()))
+
+
+def add_lens(ctx_len: torch.Tensor, lens: Optional[torch.Tensor], T: int, B: int) -> None:
+    """ctx_len[b] += lens[b] (None: T) for b < B (mgea_op_add_lens); in place"""
+    _buf(ctx_len, B, torch.int32, "add_lens: ctx_len"), _buf(lens, B, torch.int32, "add_lens: lens")
+    check(_lib.load().mgea_op_add_lens(ptr(ctx_len), ptr(lens), int(T), int(B), stream_ptr()))
+
+
+def presence_seed(ids: torch.Tensor, lens: Optional[torch.Tensor], V: int, presence: torch.Tensor) -> None:
+    """presence rows [B, ceil(V / 32)] (int32 words) <- the sets of the rows' first lens[b] ids (mgea_op_presence_seed); in place"""
+    B, T = ids.shape
+    _buf(ids, B * T, torch.int32, "presence_seed: ids"), _buf(lens, B, torch.int32, "presence_seed: lens")
+    _buf(presence, B * presence_words(min(max(int(V), 0), 14336)), torch.int32, "presence_seed: presence")
+    check(_lib.load().mgea_op_presence_seed(ptr(ids), ptr(lens), B, T, int(V), ptr(presence), stream_ptr()))
+
+
+def unpark_rows(done: torch.Tensor, ctx_len: torch.Tensor, B: int) -> None:
+    """done 2 -> 1 with ctx_len + 1 for b < B (mgea_op_unpark_rows); in place"""
+    _buf(done, B, torch.int32, "unpark_rows: done"), _buf(ctx_len, B, torch.int32, "unpark_rows: ctx_len")
+    check(_lib.load().mgea_op_unpark_rows(ptr(done), ptr(ctx_len), int(B), stream_ptr()))
+
+
+def grammar_allow(nxt: torch.Tensor, allow: torch.Tensor) -> None:
+    """allow [n_state, ceil(n_class / 32)] int32 words <- next [n_state, n_class] >= 0 (mgea_op_grammar_allow); in place"""
+    ns, nc = nxt.shape
+    taken = 1 <= ns <= 4096 and 1 <= nc <= 4096 and ns * nc <= 1 << 20    # (a shape the call refuses needs no room)
+    _buf(nxt, ns * nc, torch.int32, "grammar_allow: next"), _buf(allow, ns * ((nc + 31) // 32) if taken else 0, torch.int32, "grammar_allow: allow")
+    check(_lib.load().mgea_op_grammar_allow(ptr(nxt), ns, nc, ptr(allow), stream_ptr()))
+
+
+def row_budgets(B: int, T: int, *, config=None, rows=None, lens: Optional[torch.Tensor] = None, reserved: int = 0):
+    """The rows' device records as a generation builds them (mgea_op_row_budgets), read back as a list of dicts (temperature, top_k,
+    top_p, penalty, eos_id, max_new, seed, stream, ctx_cap).  config = dict(temperature, top_k, top_p, eos_id, seed): the uniform
+    form, stream = b; or rows = B mgea.decoder.RowSampling.  reserved > 0: the budgets are clamped to the reservation."""
+    from .decoder import pack_rows
+    s = None if config is None else C.byref(SamplerConfig(**config))
+    recs = None if rows is None else pack_rows(list(rows), 14336)
+    _buf(lens, B, torch.int32, "row_budgets: lens")
+    out, caps = (_lib.RowSampler * B)(), (C.c_int32 * B)()
+    check(_lib.load().mgea_op_row_budgets(s, recs, int(B), ptr(lens), int(T), int(reserved), out, caps, stream_ptr()))
+    return [dict(temperature=r.temperature, top_k=r.top_k, top_p=r.top_p, penalty=r.repetition_penalty, eos_id=r.eos_id,
+                 max_new=r.max_new_tokens, seed=r.seed, stream=r.stream, ctx_cap=int(c)) for r, c in zip(out, caps)]

@@ -14,8 +14,10 @@ LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 def code_object(obj, tmp):
     """path of the gfx950 code object of a host object file, or None if it has no device code"""
-    fat = os.path.join(tmp, os.path.basename(obj) + ".fatbin")
-    co = os.path.join(tmp, os.path.basename(os.path.dirname(os.path.abspath(obj))) + "_" + os.path.basename(obj) + ".co")
+    # named after the whole path: two build directories of the same name (parent/build, change/build) must not share a file
+    tag = hashlib.sha256(os.path.abspath(obj).encode()).hexdigest()[:12]
+    fat = os.path.join(tmp, tag + "_" + os.path.basename(obj) + ".fatbin")
+    co = os.path.join(tmp, tag + "_" + os.path.basename(obj) + ".co")
     r = subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj, os.devnull], capture_output=True)
     if r.returncode != 0 or not os.path.exists(fat) or os.path.getsize(fat) == 0:
         return None
@@ -98,7 +100,11 @@ def main():
             lines.append(f"{k}  {where[k]}.o  {len(new[k][0])}  {'yes' if same else 'NO'}")
             if not same:
                 import difflib
-                for d in list(difflib.unified_diff(old[k][0] + old[k][1], new[k][0] + new[k][1], "parent", "change", lineterm="", n=1))[:60]:
+                # the resource record first and whole (a cut-off instruction diff must not hide it), then the instructions, cut at 60 lines
+                rec = [d for d in difflib.unified_diff(old[k][1], new[k][1], "parent", "change", lineterm="", n=0) if d[:1] in "+-" and d[:3] not in ("+++", "---")]
+                lines.append(f"    resource record: {'identical' if not rec else 'DIFFERENT'}; instructions: {len(old[k][0])} -> {len(new[k][0])}")
+                lines += ["    " + d for d in rec]
+                for d in list(difflib.unified_diff(old[k][0], new[k][0], "parent", "change", lineterm="", n=1))[:60]:
                     lines.append("    " + d)
         lines.append(f"# {'all identical' if not bad else str(bad) + ' DIFFERENT'}")
     text = "\n".join(lines) + "\n"
