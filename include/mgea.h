@@ -225,7 +225,9 @@ int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids
 /* mgea_decoder_generate_rows_biased that also says how likely each id was, and may be told ids to take.  Build-defined: the reference
  * returns no scores (the serving APIs' counterparts are OpenAI's logprobs, HuggingFace's output_scores / compute_transition_scores).
  * At every decode step of row b, on the raw head logits x of the row:
- *   0. the raw statistics m = max_i x_i and log sum_i exp(x_i - m), fp32, in a fixed order (deterministic from run to run);
+ *   0. the raw statistics m = max_i x_i and log sum_i exp(x_i - m), fp32, in a fixed order (deterministic from run to run).  In a
+ *      guided generation (mgea_decoder_generate_rows_guided) the row of a pair is the guided row g by now: guidance comes before
+ *      everything here, and the scored outputs of a guided row are taken over g;
  *   1.-5. the processing steps of mgea_row_logits: penalty, bias, (grammar,) EOS ban, then / temperature, top-k, top-p, softmax,
  *      Philox draw;
  *   6. f = forced_ids_dev[b * n_steps + t] for the row's step index t (word 1 of its Philox counter): f >= 0 replaces the drawn id
@@ -287,6 +289,48 @@ int mgea_decoder_grammar_states(mgea_decoder* h, int32_t* out_dev, void* stream)
 /* out[0] n_state and [1] n_class of the grammar set now (0: none), [2] mgea_decoder_set_grammar uploads over the handle's lifetime,
  * [3] decode steps of the last generate() that ran in the grammar form (0 if it did not). */
 int mgea_decoder_grammar_info(mgea_decoder* h, int64_t* out /* [4] */);
+
+/* Classifier-free guidance between paired rows (build-defined, the reference has none; HuggingFace's counterpart is guidance_scale /
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor).  A CONDITIONAL row c names a SHADOW row u = shadow_row: the same generation from
+ * a prompt without the conditioning tokens.  At every decode step, on the raw head logits of the two rows,
+ *   0. (guidance) g = scale * log_softmax(x_c) + (1 - scale) * log_softmax(x_u), fp32, each row's maximum and log-sum-exp reduced in
+ *      a fixed order (deterministic from run to run); g replaces BOTH rows' logits;
+ *   1.-5. the per-step order of mgea_row_logits runs on g: penalty, bias, grammar, EOS ban, then / temperature, top-k, top-p, softmax,
+ *      Philox draw -- guidance comes before the penalty, as in HuggingFace;
+ *   6.-7. forced ids and the scored outputs as in mgea_decoder_generate_rows_scored, with x := g: logprobs_out of a guided row is
+ *      log_softmax(g) at the id -- the guided distribution, renormalised --, no longer a function of one prompt alone.
+ * One id is drawn per pair and fed to both rows.  There is no hand-off between the rows: before the first step the engine overwrites
+ * the shadow row's sampler record (seed, Philox stream and budget included), bias vector, grammar start state, forced ids and --
+ * after the prompts have seeded them -- presence bitmap with the conditional row's, so both rows' samplers compute the same function
+ * of identical inputs.  A pair's repetition-penalty set is therefore the CONDITIONAL prompt plus the generated ids, and what the
+ * caller passes in the shadow row's own records is validated and then ignored.  Everything else stays the row's own: its prompt, KV
+ * pages, ctx_len and window evictions.  scale == 1 still mixes (the result is log_softmax(x_c)); scale > 1 extrapolates away from the
+ * shadow; scale == 0 is the shadow's distribution. */
+typedef struct mgea_row_guidance {
+    int32_t shadow_row;   /* the row's shadow row in [0, B), or -1 = the row is not conditional */
+    float   scale;        /* finite, >= 0; read only where shadow_row >= 0 */
+} mgea_row_guidance;
+
+/* mgea_decoder_generate_rows_grammar with one mgea_row_guidance per row, guide [B] (host memory, read before the call returns).
+ * guide == NULL, or every shadow_row == -1, IS mgea_decoder_generate_rows_grammar: the same launches and the same ids.  Checked on
+ * the host before anything is enqueued (MGEA_EINVAL naming the row): shadow_row in [-1, B) and not the row itself; a shadow row is
+ * not conditional itself; no row is the shadow of two rows; a conditional row's scale is finite and >= 0.  Otherwise the generation
+ * is guided: every step is the unguided launch sequence with ONE more launch, the mix, between the head GEMM and the sampler;
+ * "guided" is part of the step-graph key (unguided calls capture and replay what they always did), and the pairs and scales live in
+ * device vectors the handle owns, so a request with other pairs or scales replays the cached graphs.  A guided generation never
+ * takes the greedy form: all-greedy rows run as top_k == 1 records of the sampled form.  ids_out_dev holds every row; a shadow row's
+ * line equals its conditional row's.  Rows outside every pair keep the ids they get in an unguided batch of that size and form.
+ * A guided call that would be capped -- Tp + n_steps > max_ctx without a KV window -- is refused with MGEA_ECAPACITY: the rows of a
+ * pair would be stopped after different numbers of steps.  Under a window nothing is capped and each row evicts on its own schedule. */
+int mgea_decoder_generate_rows_guided(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows /* NULL ok */,
+                                      const int32_t* start_states /* host [B], -1 = none; NULL ok */,
+                                      const mgea_row_guidance* guide /* host [B]; NULL ok */,
+                                      const int32_t* forced_ids_dev /* NULL ok */, int32_t* ids_out_dev,
+                                      float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                      void* stream);
+/* out[0] the guidance pairs and [1] the guided decode steps of the last generation (both 0 if it was not guided). */
+int mgea_decoder_guidance_info(mgea_decoder* h, int64_t* out /* [2] */);
 
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
@@ -650,6 +694,11 @@ int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, c
  * sink_pages < 1, ring_pages outside [2, 256] or sink_pages + ring_pages > max_pages. */
 int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sink_pages, int32_t ring_pages, int32_t* ctx_len_dev,
                          const int32_t* done_dev, int32_t* evictions_dev, int32_t B, void* stream);
+/* The guidance mix of a guided decode step (mgea_row_guidance, step 0), alone and IN PLACE on logits_dev [B, V] fp32: for every row c
+ * with u = partner_dev[c] in [0, B), g = scale_dev[c] * log_softmax(row c) + (1 - scale_dev[c]) * log_softmax(row u) is written into
+ * both rows; every other row is left as it is.  partner_dev int32 [B], scale_dev fp32 [B] (device).  The caller guarantees the pair
+ * rules of mgea_decoder_generate_rows_guided and finite logits; V <= 14336, else MGEA_EINVAL. */
+int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* partner_dev, const float* scale_dev, void* stream);
 
 /* The DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call on caller buffers (tests/test_gpu_bert_kernels.py,
  * tests/test_gpu_attention_exact.py).  No pointer is range-checked: the caller sizes every buffer as documented here. */

@@ -86,8 +86,27 @@ def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int
                       out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, best_of=best_of, grammar=grammar)
 
 
+def create_guided_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                      constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None, guidance_scale: float = 1.5):
+    """create_grammar_app under classifier-free guidance (create_grammar_app keeps its parameter list; grammar defaults to None here).
+    Every request runs as a pair of rows -- its prompt, and the prompt without the emotion's [BPM] and [KEY_SIGNATURE] tokens
+    (generate_music.guidance.unconditional_prompt) -- and draws each id from guidance_scale * logp(prompt) + (1 - guidance_scale) *
+    logp(the other): above 1 the piece follows the emotion's tempo and key more strongly than the model alone would, 1 is the
+    conditional distribution, 0 ignores the emotion tokens (generate_music.generate.sample_kvcache_guided; build-defined, the
+    reference has no guidance).  guidance_scale must be finite and >= 0 and the model needs max_batch >= 2 (ValueError here).  The
+    response carries X-Guidance-Scale."""
+    import math
+    guidance_scale = float(guidance_scale)
+    if not (math.isfinite(guidance_scale) and guidance_scale >= 0):
+        raise ValueError(f"guidance_scale {guidance_scale} must be finite and >= 0")
+    if int(model.max_batch) < 2:
+        raise ValueError(f"a guided request is a pair of rows: max_batch={model.max_batch} is too small")
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale)
+
+
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
-               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None):
+               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None, guidance_scale=None):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     if constrain not in CONSTRAINTS:
@@ -175,6 +194,11 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             extra["X-Best-Of"] = str(best_of)
             if means[best] > float("-inf"):   # (nothing generated -- seq_len within the prompt -- has no mean)
                 extra["X-Mean-Logprob"] = f"{means[best]:.6f}"
+        elif guidance_scale is not None:   # the request and its unconditional twin as one pair of rows
+            tokens = gen.sample_kvcache_guided(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu",
+                                               top_p=top_p, repetition_penalty=repetition_penalty, logit_bias=bias,
+                                               min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale)
+            extra["X-Guidance-Scale"] = f"{guidance_scale:g}"
         elif app.state.batcher is not None:   # the same request, served inside whatever batch is forming
             fut = app.state.batcher.submit(gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                            repetition_penalty=repetition_penalty, **more)

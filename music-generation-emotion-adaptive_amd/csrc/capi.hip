@@ -475,6 +475,10 @@ int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sin
                                (hipStream_t)stream);
 }
 
+int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* partner_dev, const float* scale_dev, void* stream) {
+    return launch_guidance_mix(logits_dev, B, V, partner_dev, scale_dev, (hipStream_t)stream);
+}
+
 int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                                 const mgea_row_logits* lrows, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
                                 int32_t n_class, const int32_t* states_in_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev,

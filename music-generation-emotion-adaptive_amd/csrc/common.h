@@ -327,6 +327,11 @@ struct SampleCall {
     GrammarArgs grammar;
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
+// Classifier-free guidance between paired rows of logits [B, V], in place (guidance.hip): for every row c with u = partner[c] in [0, B),
+// g = scale[c] * log_softmax(row c) + (1 - scale[c]) * log_softmax(row u) goes into BOTH rows; rows with partner < 0 that are nobody's
+// partner stay as they are.  partner / scale: device [B].  The caller guarantees that no row is the partner of two rows and that a
+// partner has no partner itself (one workgroup per pair is then the only one that touches its two rows).
+int launch_guidance_mix(float* logits, int B, int V, const int32_t* partner, const float* scale, hipStream_t st);
 // ---- the kernels that end a step, and the rows' records (step_tail.hip) ----
 int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
                           int B, hipStream_t st);

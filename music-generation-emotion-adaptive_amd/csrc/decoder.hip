@@ -115,7 +115,7 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, StepForm, scored, steps): one per launch sequence.  Everything a step reads besides its
+    // Captured decode-step graphs, one per (batch, StepForm, scored, steps, windowed, guided): one per launch sequence.  Everything a step reads besides its
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
@@ -157,6 +157,14 @@ struct mgea_decoder {
     uint32_t* gram_allow = nullptr;
     int gram_n_state = 0, gram_n_class = 0;
     int64_t gram_uploads = 0, gram_steps = 0;
+    // Classifier-free guidance (mgea_decoder_generate_rows_guided; guidance.hip): guide_partner [max_batch] holds the shadow row of every
+    // conditional row (-1 elsewhere), guide_scale [max_batch] its scale.  Allocated at create behind the grammar's buffers and filled per
+    // call through the pinned guide_stage ([max_batch] partners, then [max_batch] scales; free under stage_free like the records), so
+    // the guided graphs hold stable pointers and a request with other pairs or scales replays them.
+    int32_t* guide_partner = nullptr;
+    float* guide_scale = nullptr;
+    int32_t* guide_stage = nullptr;
+    int64_t guide_pairs = 0, guide_steps = 0;   // of the last generation (mgea_decoder_guidance_info)
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     // The qkv0 table.  In MGEA_POS_REFERENCE mode every decode step adds pos_emb[0] (api_cache.py:99), so the input of layer 0's LN1 +
     // in-projection is tok_emb[id] + pos_emb[0]: its 3 C outputs q | k | v depend on the token id and the weights alone.  An f32 engine
@@ -473,6 +481,7 @@ struct StepCall {
     // layer 0) and the tail gathers them for the next step; NULL: the launch
     const float* qkv0 = nullptr;
     bool windowed = false;   // a step of a windowed generation: it files into the windowed histories (mgea_decoder::hist)
+    bool guided = false;     // the guidance-mix launch over the engine's logits, between the head and the sampler (never GREEDY)
     // where the head writes the logits row: the caller's buffer, the engine's `own` for the sampler, nowhere for the argmax tails
     float* head_out(float* own) const { return logits_out ? logits_out : (form == StepForm::GREEDY ? nullptr : own); }
 };
@@ -492,7 +501,7 @@ TailArgs tail_args(const mgea_decoder* h, const StepState& s, const float* qkv0)
 // The tail of a step over the head's output.  GREEDY: the argmax of the head's n_partials partials per row (0: the ids are already in
 // h->sampled), the bookkeeping and, primed, the next step's embedding.  Otherwise the form's sampler over the logits row lg, with the
 // bookkeeping and the next embedding as its fused tail when primed, followed by the advance kernel when not.
-int enqueue_tail(mgea_decoder* h, const StepCall& k, const float* lg, int n_partials, hipStream_t st) {
+int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, hipStream_t st) {
     const auto& c = h->cfg;
     const int B = k.B, C = c.d_model, V = c.vocab;
     // (with records the EOS id, like the other scalars, is read from them -- the captured graph's form)
@@ -500,7 +509,7 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, const float* lg, int n_part
     const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, hi.ids, hi.stride, k.pv.eos_id, k.pd};
     const TailArgs t = tail_args(h, s, k.primed ? k.qkv0 : nullptr);
     if (k.form == StepForm::GREEDY) {
-        MGEA_REQUIRE(!k.scored, MGEA_EINVAL, "internal: a scored step never takes the greedy form");
+        MGEA_REQUIRE(!k.scored && !k.guided, MGEA_EINVAL, "internal: a scored or guided step never takes the greedy form");
         if (k.primed)
             PROF(PC_SAMPLE, launch_argmax_advance_embed(h->pmax_val, h->pmax_idx, n_partials, t, h->sampled, B, st));
         else if (n_partials > 0)
@@ -509,6 +518,8 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, const float* lg, int n_part
             PROF(PC_ROWOP, launch_advance(h->sampled, s, B, st, nullptr, V));
         return MGEA_OK;
     }
+    // guided: every pair's two logits rows become the pair's mixed row, in place, before the sampler reads them
+    if (k.guided) PROF(PC_SAMPLE, launch_guidance_mix(lg, B, V, h->guide_partner, h->guide_scale, st));
     uint32_t* pres = form_has_presence(k.form) ? h->presence : nullptr;
     SampleCall sc{};
     sc.logits = lg; sc.B = B; sc.V = V;
@@ -625,11 +636,13 @@ int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
 // The decode step of generate(): the rows' device records; x arrives primed on the fused path.
 // windowed: the step opens with the KV window's evict launch, in front of every append of the step (the rule and why it keeps the
 // previous tail's layer-0 K | V alive: kv_window.hip); the node does not depend on the step's form.
-int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, bool windowed) {
+// guided: the step mixes the pairs' logits rows between the head and the sampler (enqueue_tail); one more node, whatever the pairs are.
+int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, bool windowed, bool guided) {
     if (windowed)
         PROF(PC_ROWOP, launch_window_evict(h->page_table, h->max_pages, h->win_S, h->win_R, h->ctx_len, h->done, h->win_evict, B, st));
     StepCall k{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored, qkv0_table(h, B)};
     k.windowed = windowed;
+    k.guided = guided;
     return enqueue_step(h, k, st);
 }
 
@@ -643,12 +656,13 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
-// The captured decode step for (B, form, scored, steps): from the cache, or captured + instantiated now (least recently used
+// The captured decode step for (B, form, scored, steps, windowed, guided): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond StepGraphs::CAP, hipres.h).
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps, bool windowed) {
-    const StepGraphs::Key key{B, form, scored, steps, windowed};
+int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps, bool windowed,
+               bool guided) {
+    const StepGraphs::Key key{B, form, scored, steps, windowed, guided};
     if (const StepGraphs::Entry* e = h->graphs.find(key)) {
         if (steps == 1) h->n.graph_nodes = e->nodes;
         *out = e->exec;
@@ -658,7 +672,7 @@ int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t s
     if (h->graphs.full()) MGEA_CHECK_HIP(hipStreamSynchronize(st));
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st, windowed);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -1047,9 +1061,13 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         g.alloc(&h->gram_state, nb) || g.alloc(&h->gram_class, (size_t)cfg->vocab * sizeof(int32_t)) ||
         g.alloc(&h->gram_next, (size_t)MGEA_GRAMMAR_MAX_CELLS * sizeof(int32_t)) ||
         g.alloc(&h->gram_allow, ((size_t)MGEA_GRAMMAR_MAX_CELLS / 32 + MGEA_GRAMMAR_MAX_STATES) * sizeof(uint32_t)) ||
-        h->pinned.alloc(&h->gram_stage, nb))
+        h->pinned.alloc(&h->gram_stage, nb) ||
+        // (and the guidance pairs after the grammar's)
+        g.alloc(&h->guide_partner, nb) || g.alloc(&h->guide_scale, cfg->max_batch * sizeof(float)) ||
+        h->pinned.alloc(&h->guide_stage, 2 * nb))
         return fail(MGEA_ENOMEM, "state allocation failed");
     if (hipMemset(h->forced, 0xff, nhist * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->guide_partner, 0xff, nb) != hipSuccess || hipMemset(h->guide_scale, 0, cfg->max_batch * sizeof(float)) != hipSuccess ||
         hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->gram_state, 0xff, nb) != hipSuccess ||
         hipMemset(h->page_table, 0, nb * h->max_pages) != hipSuccess || hipMemset(h->ctx_len, 0, nb) != hipSuccess ||
@@ -1120,6 +1138,31 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
 }  // extern "C"
 
 namespace {
+// host check of guide[0, B) (mgea_decoder_generate_rows_guided): MGEA_EINVAL naming the first bad row; *n_pairs = the conditional rows
+int check_row_guidance(const mgea_row_guidance* guide, int B, int* n_pairs) {
+    const char* who = "decoder_generate_rows_guided";
+    *n_pairs = 0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t u = guide[b].shadow_row;
+        MGEA_REQUIRE(u >= -1 && u < B, MGEA_EINVAL, "%s: row %d: shadow_row %d outside [-1, %d)", who, b, u, B);
+        MGEA_REQUIRE(u != b, MGEA_EINVAL, "%s: row %d: a row cannot be its own shadow", who, b);
+        if (u < 0) continue;
+        MGEA_REQUIRE(std::isfinite(guide[b].scale) && guide[b].scale >= 0.f, MGEA_EINVAL, "%s: row %d: scale %g must be finite and >= 0", who, b,
+                     (double)guide[b].scale);
+    }
+    std::vector<int> owner((size_t)B, -1);   // the conditional row of every shadow
+    for (int b = 0; b < B; ++b) {
+        const int32_t u = guide[b].shadow_row;
+        if (u < 0) continue;
+        MGEA_REQUIRE(guide[u].shadow_row < 0, MGEA_EINVAL, "%s: row %d: its shadow row %d is conditional itself (shadow_row %d)", who, b, u,
+                     guide[u].shadow_row);
+        MGEA_REQUIRE(owner[(size_t)u] < 0, MGEA_EINVAL, "%s: row %d: row %d is already the shadow of row %d", who, b, u, owner[(size_t)u]);
+        owner[(size_t)u] = b;
+        *n_pairs += 1;
+    }
+    return MGEA_OK;
+}
+
 // mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
 // (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
 // are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  Which of the
@@ -1127,15 +1170,20 @@ namespace {
 // score (with rows only) or NULL: the scored form -- forced ids in, log-probabilities out (mgea_decoder_generate_rows_scored).
 // start_states (with rows only; host [B]) or NULL: the rows' grammar start states, -1 = none; any >= 0 makes it the GRAMMAR form
 // (mgea_decoder_generate_rows_grammar), none leaves every launch as it is without the argument.
+// guide (with rows only; host [B]) or NULL: the rows' guidance pairs (mgea_decoder_generate_rows_guided); any shadow_row >= 0 makes the
+// generation guided -- the mix launch in every step, the shadow rows' inputs overwritten with their conditional rows' --, none leaves
+// every launch as it is without the argument.
 struct ScoreIo { const int32_t* forced_dev; float* logprobs_out; float* choice_out; };
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
                 const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
-                int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr, const int32_t* start_states = nullptr) {
+                int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr, const int32_t* start_states = nullptr,
+                const mgea_row_guidance* guide = nullptr) {
     const auto& c = h->cfg;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
     RowRecords rr;   // the step graphs' form; whether to poll for early stops (some row can finish before n_steps)
     bool grammar = false;   // some row has a start state
+    int n_pairs = 0;        // guidance pairs: conditional rows with a shadow row
     int reserve = Tp + n_steps;
     // With a window set every generation is windowed: P pages per row, no budget clamp, no parking, every page id through the table.
     const bool windowed = h->win_S > 0;
@@ -1160,6 +1208,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
                          h->gram_n_state);
             grammar = true;
         }
+        if (guide) MGEA_TRY(check_row_guidance(guide, B, &n_pairs));
+        // A guided pair must run the same steps: rows stopped where their pages end (launch_clamp_budgets) would get budgets of their own
+        // prompt lengths.  Under a window nothing is clamped, and each row of a pair evicts on its own schedule.
+        MGEA_REQUIRE(n_pairs == 0 || windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY,
+                     "decoder_generate_rows_guided: prompt width %d + %d steps exceed max_ctx %d (a guided generation is never capped; set a window)",
+                     Tp, n_steps, c.max_ctx);
         // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
         // (a window holds every row for as long as it runs: nothing to stop)
         MGEA_REQUIRE(windowed || (Tp < c.max_ctx && n_steps <= c.max_ctx), MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp,
@@ -1168,6 +1222,9 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         // the records go to the pinned staging buffer, free once the previous call's copy out of it has run
         MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free.ev));
         rr = build_row_records(rows, lrows, B, n_steps, h->samp_stage);
+        // a shadow row samples with its conditional row's record -- seed, Philox stream, budget and all: same inputs, same id
+        for (int b = 0; n_pairs > 0 && b < B; ++b)
+            if (guide[b].shadow_row >= 0) h->samp_stage[guide[b].shadow_row] = h->samp_stage[b];
         rr.may_stop_early = rr.may_stop_early || (!windowed && reserve < Tp + n_steps);
     } else {
         MGEA_REQUIRE(windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
@@ -1175,11 +1232,14 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         rr = RowRecords{step_form(s->top_k == 1, penalty != 1.0f, false), penalty != 1.0f, s->eos_id >= 0};
     }
     const bool scored = score != nullptr;
-    // scoring needs the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to the lowest id)
+    const bool guided = n_pairs > 0;
+    // scoring and guidance need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
+    // the lowest id)
     const bool biased = rr.form == StepForm::BIASED;
-    const StepForm form = grammar ? StepForm::GRAMMAR : scored && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
+    const StepForm form = grammar ? StepForm::GRAMMAR : (scored || guided) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
     h->last_penalized = false;
     h->gram_steps = 0;
+    h->guide_pairs = h->guide_steps = 0;
     h->n.scored_steps = h->n.penalized_steps = h->n.biased_steps = 0;
     MGEA_TRY(do_reset(h, B, reserve, st));
     if (windowed) {   // the rotation breaks the allocation rule: every page id of the call comes from the table, the prefill's included
@@ -1192,6 +1252,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     const mgea_decoder::Hist hi = h->hist(windowed);
     if (form_has_presence(form)) {   // every row's set starts as its real prompt tokens
         MGEA_TRY(launch_presence_seed(prompt_ids_dev, lens_dev, B, Tp, c.vocab, h->presence, st));
+        // a pair's set is the conditional prompt plus the generated ids: the shadow's bitmap starts as a copy, and both tails add the same ids
+        const size_t pw = (size_t)presence_words(c.vocab);
+        for (int b = 0; guided && b < B; ++b)
+            if (guide[b].shadow_row >= 0)
+                MGEA_CHECK_HIP(hipMemcpyAsync(h->presence + (size_t)guide[b].shadow_row * pw, h->presence + (size_t)b * pw, pw * sizeof(uint32_t),
+                                              hipMemcpyDeviceToDevice, st));
         h->last_penalized = true;
     }
     if (n_steps == 0) return MGEA_OK;
@@ -1203,10 +1269,25 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             if (lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
                 MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)b * c.vocab, lrows[b].bias_dev, (size_t)c.vocab * sizeof(float),
                                               hipMemcpyDeviceToDevice, st));
+        for (int b = 0; guided && biased && b < B; ++b)   // a shadow row adds its conditional row's vector (its record says bias_on as that one's does)
+            if (guide[b].shadow_row >= 0 && h->samp_stage[b].bias_on)
+                MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)guide[b].shadow_row * c.vocab, h->bias + (size_t)b * c.vocab,
+                                              (size_t)c.vocab * sizeof(float), hipMemcpyDeviceToDevice, st));
         MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
         if (grammar) {   // the rows' states, through the pinned staging array (free under the same event as the records')
             for (int b = 0; b < B; ++b) h->gram_stage[b] = start_states[b];
+            for (int b = 0; guided && b < B; ++b)   // a shadow row starts in its conditional row's state
+                if (guide[b].shadow_row >= 0) h->gram_stage[guide[b].shadow_row] = start_states[b];
             MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        }
+        if (guided) {   // the pairs and their scales, through the pinned staging array: the guided graphs read the engine's two vectors
+            float* scale_stage = reinterpret_cast<float*>(h->guide_stage + c.max_batch);
+            for (int b = 0; b < B; ++b) {
+                h->guide_stage[b] = guide[b].shadow_row;
+                scale_stage[b] = guide[b].shadow_row >= 0 ? guide[b].scale : 0.f;
+            }
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_partner, h->guide_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_scale, scale_stage, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
         }
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free.ev, st));
         if (capped) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
@@ -1219,14 +1300,18 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         if (score->forced_dev)
             MGEA_CHECK_HIP(hipMemcpy2DAsync(hi.forced, hs * sizeof(int32_t), score->forced_dev, (size_t)n_steps * sizeof(int32_t),
                                             (size_t)n_steps * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
+        for (int b = 0; guided && b < B; ++b)   // a shadow row is told the ids its conditional row is told
+            if (guide[b].shadow_row >= 0)
+                MGEA_CHECK_HIP(hipMemcpyAsync(hi.forced + (size_t)guide[b].shadow_row * hs, hi.forced + (size_t)b * hs,
+                                              (size_t)n_steps * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     }
     if (const int path = qkv0_path(h, B); path >= 0) MGEA_TRY(ensure_qkv0(h, path, st));   // before any capture of this batch size
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1, windowed));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1, windowed, guided));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K, windowed));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K, windowed, guided));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1234,12 +1319,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, scored, st, windowed);
+            const int rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st, windowed));
+            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st, windowed, guided));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1261,6 +1346,8 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->n.biased_steps = biased ? launched : 0;
     h->n.scored_steps = scored ? launched : 0;
     h->gram_steps = grammar ? launched : 0;
+    h->guide_pairs = n_pairs;
+    h->guide_steps = guided ? launched : 0;
     if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
         float* outs[2] = {score->logprobs_out, score->choice_out};
         const float* hist[2] = {hi.lp, hi.ch};
@@ -1399,6 +1486,30 @@ int mgea_decoder_generate_rows_grammar(mgea_decoder* h, const int32_t* prompt_id
     const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
     return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
                        logprobs_out_dev ? &io : nullptr, start_states);
+}
+
+int mgea_decoder_generate_rows_guided(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                      const int32_t* start_states, const mgea_row_guidance* guide, const int32_t* forced_ids_dev,
+                                      int32_t* ids_out_dev, float* logprobs_out_dev, float* choice_logprobs_out_dev, void* stream) {
+    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows_guided: NULL argument");
+    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
+                 "decoder_generate_rows_guided: forced ids and choice log-probabilities need logprobs_out_dev");
+    if (logits_rows) {
+        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_guided: empty batch");
+        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_guided"));
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
+                       logprobs_out_dev ? &io : nullptr, start_states, guide);
+}
+
+int mgea_decoder_guidance_info(mgea_decoder* h, int64_t* out) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_guidance_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->guide_pairs; out[1] = h->guide_steps;
+    return MGEA_OK;
 }
 
 int mgea_decoder_set_window(mgea_decoder* h, int32_t sink_pages, int32_t ring_pages, int32_t max_steps, void* stream) {

@@ -30,7 +30,7 @@ __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
            "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
            "generate_batch_biased", "generate_sequence_biased", "sample_kvcache_grammar", "generate_batch_grammar", "score_sequence", "generate_best_of", "pick_best",
-           "mean_logprobs"]
+           "mean_logprobs", "sample_kvcache_guided", "generate_requests_guided"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
 tok2id: Dict[str, int] = {}
@@ -476,6 +476,81 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     for c0 in range(0, len(live), eng.max_batch):
         part = live[c0:c0 + eng.max_batch]
         out = eng.generate_rows([ids[i] for i in part], [rows[i] for i in part], max(budgets[i] for i in part)).cpu().tolist()
+        for i, row in zip(part, out):
+            gen[i] = [g for g in row if g >= 0]
+    return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]
+
+
+def sample_kvcache_guided(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
+                          top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                          logit_bias=None, min_new_tokens: int = 0, grammar=None, guidance_scale: float = 1.5,
+                          negative_prompt: Optional[Sequence[str]] = None) -> List[str]:
+    """sample_kvcache_grammar under classifier-free guidance (sample_kvcache_grammar keeps its parameter list): the request runs as a
+    pair of rows, the prompt and negative_prompt -- None = the prompt without its [BPM] and [KEY_SIGNATURE] tokens
+    (generate_music.guidance.unconditional_prompt) -- and every id is drawn from guidance_scale * logp(prompt) +
+    (1 - guidance_scale) * logp(negative_prompt): 1 = the conditional distribution (not the same draws as sample_kvcache: a batch of
+    two takes other kernels), above 1 the emotion tokens weigh more, 0 = the negative prompt alone.  Everything else -- penalty, bias,
+    minimum length, grammar, the seed's Philox stream -- is the request's, applied to the mixed distribution.  Build-defined
+    (DecoderEngine.generate_guided); the model needs max_batch >= 2."""
+    return generate_requests_guided(model, [prompt], max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias,
+                                    min_new_tokens, grammar, guidance_scale,
+                                    None if negative_prompt is None else [list(negative_prompt)])[0]
+
+
+def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
+                             top_p: Optional[float] = None, seed=None, repetition_penalty=None, logit_bias=None, min_new_tokens=0,
+                             grammar=None, guidance_scale=1.5, negative_prompts=None) -> List[List[str]]:
+    """generate_requests under classifier-free guidance: every request is a pair of rows (sample_kvcache_guided), so one generation
+    serves up to max_batch // 2 of them.  guidance_scale: one value or one per prompt; negative_prompts: None = every prompt without
+    its [BPM] / [KEY_SIGNATURE] tokens, else one token list per prompt (a None entry = that one's default).  Unlike generate_requests
+    a request that would run past the engine's context is refused (RuntimeError) also where only its budget would be cut: a guided
+    generation is never capped (a KV window lifts the limit)."""
+    from .guidance import unconditional_prompt
+    m = _as_model(model)
+    eng = m._need()
+    n = len(prompts)
+    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
+    temps = _per_prompt(temperature, n, "temperature")
+    ks = _per_prompt(top_k, n, "top_k")
+    ps = _per_prompt(top_p, n, "top_p")
+    seeds = _per_prompt(seed, n, "seed")
+    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
+    biases = _per_prompt(logit_bias, n, "logit_bias")
+    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
+    scales = [float(v) for v in _per_prompt(guidance_scale, n, "guidance_scale")]
+    negs = [None] * n if negative_prompts is None else list(negative_prompts)
+    if len(negs) != n:
+        raise ValueError(f"negative_prompts: {len(negs)} values for {n} prompts")
+    negs = [unconditional_prompt(p) if q is None else list(q) for p, q in zip(prompts, negs)]
+    ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
+    neg_ids = [[tok2id[t] for t in q] for q in negs]
+    budgets = [L - len(p) for L, p in zip(max_lens, ids)]
+    if eng.max_batch < 2:
+        raise ValueError("guided generation needs a model with max_batch >= 2 (a request is a pair of rows)")
+    for i in range(n):
+        if mins[i] < 0:
+            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
+    eos = tok2id.get("[END_SEQUENCE]", -1)
+    live = [i for i in range(n) if budgets[i] > 0]
+    gstates = [None] * n
+    if grammar is not None:
+        from .grammar import start_state
+        _use_grammar(eng, grammar)
+        gstates = [start_state(grammar, p) for p in ids]
+    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
+                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i])
+            for i in live}
+    gen: Dict[int, List[int]] = {}
+    per = eng.max_batch // 2
+    for c0 in range(0, len(live), per):
+        part = live[c0:c0 + per]
+        steps = max(budgets[i] for i in part)
+        width = max(max(len(ids[i]), len(neg_ids[i])) for i in part)
+        if _no_window(eng) and width + steps > eng.max_ctx:
+            raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
+        out = eng.generate_guided([ids[i] for i in part], [neg_ids[i] for i in part], [rows[i] for i in part],
+                                  [scales[i] for i in part], steps).cpu().tolist()
         for i, row in zip(part, out):
             gen[i] = [g for g in row if g >= 0]
     return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]

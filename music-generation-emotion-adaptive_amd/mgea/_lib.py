@@ -46,6 +46,11 @@ class RowLogits(C.Structure):
     _fields_ = [("bias_dev", C.c_void_p), ("min_new_tokens", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RowGuidance(C.Structure):
+    """mgea_row_guidance: one batch row's classifier-free-guidance pair (mgea_decoder_generate_rows_guided)."""
+    _fields_ = [("shadow_row", C.c_int32), ("scale", C.c_float)]
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -110,6 +115,9 @@ PROTOTYPES = {
     "mgea_decoder_set_grammar": (C.c_int, [_P, _P, _P, _I32, _I32, _P]),
     "mgea_decoder_generate_rows_grammar": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P, _P, _P,
                                                     _P, _P, _P]),
+    "mgea_decoder_generate_rows_guided": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
+                                                   C.POINTER(RowGuidance), _P, _P, _P, _P, _P]),
+    "mgea_decoder_guidance_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_set_window": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "mgea_decoder_window_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "mgea_decoder_grammar_states": (C.c_int, [_P, _P, _P]),
@@ -162,6 +170,7 @@ PROTOTYPES = {
     "mgea_op_sample_rows_biased": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P]),
     "mgea_op_sample_rows_scored": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P, _P, _P, _P]),
     "mgea_op_window_evict": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
+    "mgea_op_guidance_mix": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,
                                               _P, _P, _P]),
     "mgea_op_attention_cls": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),

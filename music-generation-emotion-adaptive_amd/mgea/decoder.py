@@ -444,6 +444,89 @@ def pack_force_ids(force_ids, B: int, n_steps: int, vocab: int):
     return torch.from_numpy(out)
 
 
+def check_guidance(shadow_rows, scales, B: int) -> None:
+    """The pair rules of mgea_decoder_generate_rows_guided (include/mgea.h, mgea_row_guidance) as ValueErrors naming the row:
+    shadow_row in [-1, B) and not the row itself, a shadow row is not conditional itself, no row is the shadow of two rows, a
+    conditional row's scale is finite and >= 0.  Pure host code."""
+    shadow_rows = [int(u) for u in shadow_rows]
+    if len(shadow_rows) != B or len(scales) != B:
+        raise ValueError(f"guidance: {len(shadow_rows)} shadow rows and {len(scales)} scales for {B} rows")
+    for b, u in enumerate(shadow_rows):
+        if not -1 <= u < B:
+            raise ValueError(f"row {b}: shadow_row {u} outside [-1, {B})")
+        if u == b:
+            raise ValueError(f"row {b}: a row cannot be its own shadow")
+        if u < 0:
+            continue
+        s = float(scales[b])
+        if not (math.isfinite(s) and 0 <= s <= float(np.finfo(np.float32).max)):   # (finite as the float32 the record holds)
+            raise ValueError(f"row {b}: guidance scale {scales[b]} must be finite and >= 0")
+    owner = {}
+    for b, u in enumerate(shadow_rows):
+        if u < 0:
+            continue
+        if shadow_rows[u] >= 0:
+            raise ValueError(f"row {b}: its shadow row {u} is conditional itself (shadow_row {shadow_rows[u]})")
+        if u in owner:
+            raise ValueError(f"row {b}: row {u} is already the shadow of row {owner[u]}")
+        owner[u] = b
+
+
+def pack_guided(prompts, negative_prompts, rows, guidance_scale, max_batch: int, force_ids=None):
+    """The host half of DecoderEngine.generate_guided (no device): n prompts, of which those with a negative prompt are conditional,
+    become one batch -- the callers' rows 0 .. n-1, then one shadow row per pair in the order of their conditional rows, each with its
+    negative prompt and its conditional row's RowSampling (the engine samples a shadow row with its conditional row's record anyway).
+    negative_prompts[i] None = row i is not guided; guidance_scale: one value, or one per prompt (read only for the guided ones).
+    force_ids (None, or n id lists as in pack_force_ids; an int tensor [n, steps] gets free rows behind it): the shadow rows take
+    their conditional rows' ids inside the engine.  Returns (prompts, rows, shadow_rows, scales, force_ids) of the whole batch.
+    ValueError naming the row: a bad scale, an empty negative prompt, a shadow row that would not fit into max_batch."""
+    prompts = prompts.tolist() if isinstance(prompts, torch.Tensor) else [list(p) for p in prompts]
+    rows = list(rows)
+    n = len(prompts)
+    negative_prompts = [None] * n if negative_prompts is None else list(negative_prompts)
+    if len(rows) != n:
+        raise ValueError(f"{n} prompts but {len(rows)} sampler rows")
+    if len(negative_prompts) != n:
+        raise ValueError(f"{n} prompts but {len(negative_prompts)} negative prompts")
+    if isinstance(guidance_scale, (list, tuple, np.ndarray, torch.Tensor)):
+        per = [float(v) for v in guidance_scale]
+        if len(per) != n:
+            raise ValueError(f"guidance_scale: {len(per)} values for {n} prompts")
+    else:
+        per = [float(guidance_scale)] * n
+    all_prompts, all_rows = list(prompts), list(rows)
+    shadow, scales = [-1] * n, [0.0] * n
+    for i, neg in enumerate(negative_prompts):
+        if neg is None:
+            continue
+        neg = neg.tolist() if isinstance(neg, torch.Tensor) else list(neg)
+        if len(neg) < 1:
+            raise ValueError(f"row {i}: empty negative prompt")
+        if not (math.isfinite(per[i]) and per[i] >= 0):
+            raise ValueError(f"row {i}: guidance scale {per[i]} must be finite and >= 0")
+        u = len(all_prompts)
+        if u >= int(max_batch):
+            n_pairs = sum(p is not None for p in negative_prompts)
+            raise ValueError(f"row {i}: its shadow row {u} does not fit: {n} prompts + {n_pairs} negative prompts exceed max_batch {max_batch}")
+        shadow[i], scales[i] = u, per[i]
+        all_prompts.append(neg)
+        all_rows.append(rows[i])
+        shadow.append(-1)
+        scales.append(0.0)
+    extra = len(all_prompts) - n
+    if isinstance(force_ids, torch.Tensor):
+        if force_ids.dim() == 2 and extra:
+            pad = torch.full((extra, force_ids.shape[1]), -1, dtype=force_ids.dtype, device=force_ids.device)
+            force_ids = torch.cat([force_ids, pad], dim=0)
+    elif force_ids is not None:
+        force_ids = list(force_ids)
+        if len(force_ids) != n:
+            raise ValueError(f"{n} prompts but {len(force_ids)} force_ids rows")
+        force_ids = force_ids + [None] * extra
+    check_guidance(shadow, scales, len(all_prompts))
+    return all_prompts, all_rows, shadow, scales, force_ids
+
+
 def _prompt_ids(prompts):
     """prompts (id lists, ragged ok, or an int tensor [B, Tp]) -> (int32 ids [B, Tp] on the host, lens [B] or None)"""
     if isinstance(prompts, torch.Tensor):
@@ -868,6 +951,76 @@ class DecoderEngine:
         if check_ids and not checked:
             self.id_errors()
         return ScoredGeneration(out[:, :n_steps], lp[:, :n_steps], ch[:, :n_steps])
+
+    def generate_guided(self, prompts, negative_prompts, rows: Sequence[RowSampling], guidance_scale=1.5,
+                        n_steps: Optional[int] = None, force_ids=None, scored: bool = False, check_ids: bool = True,
+                        check_bias: bool = True, all_rows: bool = False):
+        """generate_rows() under classifier-free guidance (mgea_decoder_generate_rows_guided; build-defined, HuggingFace's
+        guidance_scale).  negative_prompts[i] (id list, or None = row i is not guided) is prompt i without its conditioning tokens;
+        the engine runs it as a shadow row behind the callers' rows, and at every step the pair draws ONE id from
+        scale * logp(prompt) + (1 - scale) * logp(negative prompt): scale 1 = the conditional distribution, > 1 follows the
+        conditioning more strongly, 0 = the negative prompt's.  guidance_scale: one value or one per prompt.  The mix comes before
+        the repetition penalty (over the CONDITIONAL prompt and the generated ids), the bias and the grammar, which are row i's.
+        A pair costs two rows of max_batch and one more launch per step; a call without any negative prompt is generate_rows /
+        generate_scored itself.  Returns the callers' rows only: int32 [n, n_steps], or with scored=True a ScoredGeneration whose
+        logprobs of a guided row are those of the guided distribution; all_rows=True returns the shadow rows too, behind the callers'
+        rows in the order of their conditional rows (pack_guided).  force_ids as in generate_scored (scored=True only).
+        ValueError naming the row for what the native call would refuse, a batch beyond max_batch and a capped generation
+        (prompt width + n_steps > max_ctx without a window) included."""
+        n = prompts.shape[0] if isinstance(prompts, torch.Tensor) else len(prompts)
+        if force_ids is not None and not scored:
+            raise ValueError("force_ids need scored=True")
+        all_prompts, rows_all, shadow, scales, forced_in = pack_guided(prompts, negative_prompts, rows, guidance_scale, self.max_batch,
+                                                                       force_ids)
+        if all(u < 0 for u in shadow):   # nothing is guided: the calls there always were
+            if scored:
+                return self.generate_scored(prompts, rows, n_steps, force_ids, check_ids, check_bias)
+            return self.generate_rows(prompts, rows, n_steps, check_ids, check_bias)
+        ids, lens = _prompt_ids(all_prompts)
+        B, Tp = ids.shape
+        if n_steps is None:
+            budgets = [int(r.max_new_tokens) for r in rows_all]
+            if min(budgets) <= 0:
+                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
+            n_steps = max(budgets)
+        n_steps = int(n_steps)
+        if self.window is None and Tp + n_steps > self.max_ctx:
+            raise ValueError(f"prompt width {Tp} + {n_steps} steps exceed max_ctx {self.max_ctx}: a guided generation is never capped "
+                             "(set a window)")
+        recs = pack_rows(rows_all, self.vocab, n_steps)
+        forced = pack_force_ids(forced_in, B, n_steps, self.vocab)
+        lrecs, keep = pack_row_logits(rows_all, self.vocab, self.device, check_bias)
+        starts = self._start_states(rows_all)
+        guide = (_lib.RowGuidance * B)(*[_lib.RowGuidance(shadow_row=u, scale=s) for u, s in zip(shadow, scales)])
+        checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
+        with self._on_stream():
+            ids = ids.to(self.device).contiguous()
+            lens = None if lens is None else lens.to(self.device).contiguous()
+            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
+            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
+                forced.record_stream(self.stream)
+            w = max(n_steps, 1)
+            out = torch.empty(B, w, dtype=torch.int32, device=self.device)
+            lp = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
+            ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
+            for t in keep:   # uploaded on the caller's stream, read by the engine's
+                t.record_stream(self.stream)
+            check(self.lib.mgea_decoder_generate_rows_guided(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
+                                                             ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
+        self._cur_batch = B
+        self._epoch += 1
+        if check_ids and not checked:
+            self.id_errors()
+        n = B if all_rows else n
+        if scored:
+            return ScoredGeneration(out[:n, :n_steps], lp[:n, :n_steps], ch[:n, :n_steps])
+        return out[:n, :n_steps]
+
+    def guidance_info(self):
+        """The guidance pairs and the guided decode steps of the last generation (both 0 if it was not guided)."""
+        out = (C.c_int64 * 2)()
+        check(self.lib.mgea_decoder_guidance_info(self.h, out))
+        return dict(pairs=out[0], guided_steps=out[1])
 
     def score(self, prompts, continuations, rows: Optional[Sequence[RowSampling]] = None):
         """Log-probabilities of given continuations under the model, as sample_kvcache would see them: a teacher-forced

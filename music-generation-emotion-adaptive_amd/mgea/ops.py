@@ -380,6 +380,26 @@ def window_evict(page_table: torch.Tensor, sink_pages: int, ring_pages: int, ctx
     return pt, cl, ev
 
 
+def guidance_mix(logits: torch.Tensor, partner, scale) -> torch.Tensor:
+    """The mix launch of a guided decode step (mgea_op_guidance_mix), alone, on a COPY of logits [>= B, V] (B = len(partner); rows
+    behind B are guard rows the kernel must not touch): for every row c with u = partner[c] >= 0, both rows become
+    scale[c] * log_softmax(row c) + (1 - scale[c]) * log_softmax(row u).  partner / scale: B ints (-1 = not conditional) and B floats,
+    checked on the host like a guided call's pairs (mgea.decoder.check_guidance: ValueError naming the row).  Returns the copy."""
+    from .decoder import check_guidance
+    lib = _lib.load()
+    partner = [int(v) for v in (partner.tolist() if hasattr(partner, "tolist") else partner)]
+    scale = [float(v) for v in (scale.tolist() if hasattr(scale, "tolist") else scale)]
+    B = len(partner)
+    if logits.dim() != 2 or logits.shape[0] < B or len(scale) != B or B < 1:
+        raise RuntimeError("guidance_mix: logits must be [>= B, V] with B = len(partner) = len(scale) >= 1")
+    check_guidance(partner, scale, B)
+    out = logits.to(device="cuda", dtype=torch.float32).contiguous().clone()
+    p = torch.tensor(partner, dtype=torch.int32, device="cuda")
+    s = torch.tensor(scale, dtype=torch.float32, device="cuda")
+    check(lib.mgea_op_guidance_mix(ptr(out), B, out.shape[1], ptr(p), ptr(s), stream_ptr()))
+    return out
+
+
 # ---- the DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call (mgea_op_* of the same names: tests only) ----
 _DTYPE_ROWS = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
 
