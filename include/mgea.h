@@ -332,6 +332,62 @@ int mgea_decoder_generate_rows_guided(mgea_decoder* h, const int32_t* prompt_ids
 /* out[0] the guidance pairs and [1] the guided decode steps of the last generation (both 0 if it was not guided). */
 int mgea_decoder_guidance_info(mgea_decoder* h, int64_t* out /* [2] */);
 
+/* Emotion transitions: a row's prompt K | V swapped in the middle of a generation (build-defined; the reference labels a text's
+ * sentences in analyze_emotion_transitions and has nothing downstream that uses them).  The emotion reaches the decoder only through
+ * the prompt's [BPM] and [KEY_SIGNATURE] tokens; decode steps use position row 0 and the attention is mask-free over the cache, so
+ * "the model now sees prompt B instead of prompt A" is exactly "the K | V of cache positions [0, len_b) of every layer are those a
+ * prefill of B caches".
+ * A SCHEDULED row has n_segments prompt variants, 1 .. MGEA_SCHEDULE_MAX_SEGMENTS (1 = a plain row), all of the row's prompt length
+ * len_b = lens[b].  The call has one lens vector and prompt ids [n_seg_max][B][Tp] with Tp <= 64, so the variants lie in the row's
+ * logical page 0; a row with fewer segments than n_seg_max repeats its last variant in the matrix (its later variants are prefilled
+ * and never used).  Every row starts in segment 0.  The rule runs at the START of every decode step, for a row that is not finished:
+ *   k   = key == 0 ? the row's step index (0 at its first decode step) : its grammar state (the start state at its first step);
+ *   seg = #{ s in [0, n_segments - 1) : threshold[s] <= k };
+ *   if seg != cur_seg[b]: the K | V of positions [0, len_b) in every layer of the row's pages become the K | V that a prefill of
+ *   variant seg caches -- the prefill of the B variant-seg prompts with this call's B, Tp and lens --, bit for bit in the page's
+ *   element type; then cur_seg[b] = seg.
+ * Nothing else changes: not positions >= len_b (the re-fed duplicate of the last prompt token included), not ctx_len, cur_ids, the
+ * histories or the Philox counters, not the presence bitmap (the penalty set stays the FIRST variant plus the generated ids), bias or
+ * grammar state.  A finished or parked row never switches.  With key == 1 thresholds are grammar states: under an automaton whose
+ * states ascend with musical time (generate_music.grammar.track_grammar: 2 + k ascends with START) the segment follows the START of
+ * the row's last note and falls back to segment 0 when a new track opens; key == 0 counts steps. */
+#define MGEA_SCHEDULE_MAX_SEGMENTS 8
+typedef struct mgea_row_schedule {
+    int32_t n_segments;     /* 1 .. 8 prompt variants; 1 = the row never switches */
+    int32_t key;            /* 0: the row's step index, 1: its grammar state */
+    int32_t threshold[7];   /* ascending (equal values allowed) over [0, n_segments - 1); the rest is not read */
+    int32_t reserved;       /* 0 */
+} mgea_row_schedule;
+
+/* mgea_decoder_generate_rows_guided with one mgea_row_schedule per row, sched [B] (host memory, read before the call returns), and
+ * prompt_ids_dev [n_seg_max][B][Tp].  sched == NULL or n_seg_max == 1 with every n_segments == 1 IS
+ * mgea_decoder_generate_rows_guided on variant 0: the same launches and the same ids.  Checked on the host before anything is
+ * enqueued: MGEA_EINVAL naming the row for n_segments outside [1, min(8, n_seg_max)], key outside {0, 1}, thresholds that descend or
+ * are negative, a non-zero reserved, key == 1 on a row without a start state or with no grammar set, and a guidance shadow row with
+ * more than one segment (its prompt has no emotion tokens); MGEA_EINVAL for n_seg_max outside [1, 8] and for a block mode other than
+ * the KV-cache one; MGEA_ECAPACITY for Tp > 64.
+ * A scheduled call prefills variants n_seg_max - 1 .. 1 and then variant 0 -- each a reset and a prefill of the B prompts, so every
+ * variant takes the kernels the generation's own prefill takes --, and copies positions [0, len_b) of every row, layer and head out of
+ * the pages into a conditioning store the handle owns after each (n_seg_max * n_layer * B * 2 * d_model * Tp elements; allocated and
+ * regrown by scheduled calls only, a regrow synchronises and drops the scheduled graphs).  Every step is then the unscheduled launch
+ * sequence of its form behind ONE more launch that applies the rule (after the window's evict launch when windowed); "scheduled" is
+ * part of the step-graph key (unscheduled calls capture and replay what they always did), and records, segments and store live in
+ * device memory, so other thresholds replay the cached graphs.  It composes with every form, the greedy one included. */
+int mgea_decoder_generate_rows_scheduled(mgea_decoder* h, const int32_t* prompt_ids_dev /* [n_seg_max][B][Tp] */, const int32_t* lens_dev,
+                                         int32_t B, int32_t Tp, int32_t n_steps, const mgea_row_sampler* rows,
+                                         const mgea_row_logits* logits_rows /* NULL ok */,
+                                         const int32_t* start_states /* host [B], -1 = none; NULL ok */,
+                                         const mgea_row_guidance* guide /* host [B]; NULL ok */,
+                                         const mgea_row_schedule* sched /* host [B]; NULL ok */, int32_t n_seg_max,
+                                         const int32_t* forced_ids_dev /* NULL ok */, int32_t* ids_out_dev,
+                                         float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                         void* stream);
+/* out[0] the scheduled decode steps and [1] the switches (rows x times the rule rewrote a row's pages) of the last generation, both
+ * 0 if it was not scheduled.  Synchronises `stream`. */
+int mgea_decoder_schedule_info(mgea_decoder* h, int64_t* out /* [2] */, void* stream);
+/* The rows' current segments cur_seg -> out_dev [B] (device int32).  MGEA_EINVAL if the last generation was not scheduled. */
+int mgea_decoder_segments(mgea_decoder* h, int32_t* out_dev, void* stream);
+
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
  * generate applied no penalty (a biased generation keeps the bitmaps too). */
@@ -699,6 +755,24 @@ int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sin
  * both rows; every other row is left as it is.  partner_dev int32 [B], scale_dev fp32 [B] (device).  The caller guarantees the pair
  * rules of mgea_decoder_generate_rows_guided and finite logits; V <= 14336, else MGEA_EINVAL. */
 int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* partner_dev, const float* scale_dev, void* stream);
+/* The two kernels of a scheduled generation (mgea_row_schedule), alone on caller buffers.  pool_dev: a KV pool
+ * [n_layer][n_pages][K | V][H][64 x dh] of fp32 (f16 == 0) or fp16 (f16 == 1) elements in the page layouts of csrc/common.h; row b's
+ * logical page 0 is physical page b when arith_batch > 0 and page_table_dev[b * max_pages] otherwise.  store_dev: the conditioning
+ * store, n_seg_max * n_layer * B * 2 * H * dh * slot_tokens elements; a row of length len fills the first 2 * H * dh * len elements
+ * of its slot (seg, layer, b) in 16-byte groups: first K, group (h * D + dg) * len + t = elements dg * G .. dg * G + G - 1 of token t,
+ * head h (G = 4 floats / 8 halves, D = dh / G), then V, group (h * len + t) * D + dg.  meta_dev int32 [4] and len_dev int32 [B] are
+ * the layout words {slot_tokens, B, n_seg_max, 0} and the rows' lengths: written by the gather, read by the apply.
+ *   gather_seg >= 0: positions [0, lens_dev[b]) (lens_dev NULL: slot_tokens) of every row's page -> the slots of segment gather_seg;
+ *   sched_dev != NULL: then the rule of one scheduled step over device vectors: sched_dev [B] records, done_dev, row_step_dev,
+ *   gram_state_dev, cur_seg_dev [B] and the counter switches_dev [1].
+ * MGEA_EINVAL (nothing launched) for what the launchers refuse: a NULL buffer, head_dim not 32 / 64 / 96, slot_tokens outside
+ * [1, 64], n_seg_max outside [1, 8], gather_seg >= n_seg_max, B beyond arith_batch, neither arith_batch nor a table.  The records'
+ * values, the page ids and the buffers' sizes are the caller's (the kernels skip a row whose page id or segment is out of range). */
+int mgea_op_recondition(void* pool_dev, int32_t n_layer, int32_t n_pages, int32_t H, int32_t dh, int32_t f16, int32_t arith_batch,
+                        const int32_t* page_table_dev, int32_t max_pages, void* store_dev, int32_t n_seg_max, int32_t slot_tokens,
+                        int32_t* meta_dev, int32_t* len_dev, int32_t B, int32_t gather_seg, const int32_t* lens_dev,
+                        const mgea_row_schedule* sched_dev, const int32_t* done_dev, const int32_t* row_step_dev,
+                        const int32_t* gram_state_dev, int32_t* cur_seg_dev, int32_t* switches_dev, void* stream);
 
 /* The DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call on caller buffers (tests/test_gpu_bert_kernels.py,
  * tests/test_gpu_attention_exact.py).  No pointer is range-checked: the caller sizes every buffer as documented here. */

@@ -105,8 +105,33 @@ def create_guided_app(model, seq_len: int, temperature: float = 1.0, top_k: int 
                       out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale)
 
 
+def create_transition_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                          constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar="tracks",
+                          guidance_scale=None):
+    """create_guided_app for a piece that follows the emotions of its text (create_guided_app keeps its parameter list; grammar
+    defaults to "tracks" and guidance_scale to None = no guidance here).  The text goes through
+    emotion_analysis.inference.analyze_emotion_transitions: one emotion, one EATS parameter set and one prompt variant per sentence
+    (at most 8; generate_music.transitions.transition_prompts: the first sentence's prompt -- its instruments -- with each
+    sentence's [BPM] and [KEY_SIGNATURE] tokens), the segments' shares the sentences' lengths.  Under the track grammar a segment is
+    a range of note START classes, so every track walks through the emotions in musical time
+    (generate_music.generate.sample_kvcache_transitions; build-defined, the reference labels the sentences and stops there); with
+    grammar=None the segments are ranges of steps.  constrain="scale" keeps the FIRST sentence's key.  The response carries X-Emotions
+    (the sentences' labels, comma-separated; X-Emotion is the first) and X-Segments."""
+    if guidance_scale is not None:
+        import math
+        guidance_scale = float(guidance_scale)
+        if not (math.isfinite(guidance_scale) and guidance_scale >= 0):
+            raise ValueError(f"guidance_scale {guidance_scale} must be finite and >= 0")
+        if int(model.max_batch) < 2:
+            raise ValueError(f"a guided request is a pair of rows: max_batch={model.max_batch} is too small")
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale,
+                      transitions=True)
+
+
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
-               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None, guidance_scale=None):
+               out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None, guidance_scale=None,
+               transitions=False):
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
     if constrain not in CONSTRAINTS:
@@ -169,7 +194,11 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
 
     @app.post("/generate")
     def generate_music(prompt: str = prompt_param):
-        label = inference.predict(prompt)                                     # api_cache.py:189
+        sentences = []
+        if transitions:   # one emotion per sentence; the first one's is the request's as far as the reference's steps go
+            from generate_music.transitions import MAX_SEGMENTS
+            sentences = inference.analyze_emotion_transitions(prompt)[:MAX_SEGMENTS]
+        label = sentences[0][1] if sentences else inference.predict(prompt)   # api_cache.py:189
         mapping = EATS.get_music_params(label)                                # :190
         bpm_tok = gen.closest_bpm_token(mapping["bpm"])                       # :194
         key = gen.normalize_key_signature(mapping["key"])                     # :195
@@ -194,6 +223,19 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             extra["X-Best-Of"] = str(best_of)
             if means[best] > float("-inf"):   # (nothing generated -- seq_len within the prompt -- has no mean)
                 extra["X-Mean-Logprob"] = f"{means[best]:.6f}"
+        elif transitions:   # one prompt variant per sentence, switched at the segments' boundaries
+            from generate_music.transitions import transition_prompts
+            sentences = sentences or [(prompt, label)]
+            # (the first sentence's parameters are the request's own: get_music_params may draw, and variant 0 is gen_prompt itself)
+            variants = transition_prompts(gen_prompt, [mapping] + [EATS.get_music_params(lb) for _, lb in sentences[1:]])
+            tokens = gen.sample_kvcache_transitions(model, variants, [max(len(seg), 1) for seg, _ in sentences], max_len=seq_len,
+                                                    temperature=temperature, top_k=top_k, device="cpu", top_p=top_p,
+                                                    repetition_penalty=repetition_penalty, logit_bias=bias,
+                                                    min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale)
+            extra["X-Emotions"] = ",".join(lb for _, lb in sentences)
+            extra["X-Segments"] = str(len(sentences))
+            if guidance_scale is not None:
+                extra["X-Guidance-Scale"] = f"{guidance_scale:g}"
         elif guidance_scale is not None:   # the request and its unconditional twin as one pair of rows
             tokens = gen.sample_kvcache_guided(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu",
                                                top_p=top_p, repetition_penalty=repetition_penalty, logit_bias=bias,

@@ -479,6 +479,31 @@ int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t*
     return launch_guidance_mix(logits_dev, B, V, partner_dev, scale_dev, (hipStream_t)stream);
 }
 
+int mgea_op_recondition(void* pool_dev, int32_t n_layer, int32_t n_pages, int32_t H, int32_t dh, int32_t f16, int32_t arith_batch,
+                        const int32_t* page_table_dev, int32_t max_pages, void* store_dev, int32_t n_seg_max, int32_t slot_tokens,
+                        int32_t* meta_dev, int32_t* len_dev, int32_t B, int32_t gather_seg, const int32_t* lens_dev,
+                        const mgea_row_schedule* sched_dev, const int32_t* done_dev, const int32_t* row_step_dev,
+                        const int32_t* gram_state_dev, int32_t* cur_seg_dev, int32_t* switches_dev, void* stream) {
+    MGEA_REQUIRE(n_seg_max >= 1 && n_seg_max <= MGEA_SCHEDULE_MAX_SEGMENTS, MGEA_EINVAL, "op_recondition: n_seg_max %d outside [1, %d]", n_seg_max,
+                 MGEA_SCHEDULE_MAX_SEGMENTS);
+    MGEA_REQUIRE(slot_tokens >= 1 && slot_tokens <= MGEA_KV_PAGE_TOKENS, MGEA_EINVAL, "op_recondition: slot_tokens %d outside [1, %d]", slot_tokens,
+                 MGEA_KV_PAGE_TOKENS);
+    MGEA_REQUIRE(gather_seg < n_seg_max, MGEA_EINVAL, "op_recondition: gather_seg %d of %d segments", gather_seg, n_seg_max);
+    MGEA_REQUIRE(gather_seg >= 0 || sched_dev, MGEA_EINVAL, "op_recondition: neither a gather nor an apply");
+    MGEA_REQUIRE(!sched_dev || (done_dev && row_step_dev && gram_state_dev && cur_seg_dev && switches_dev), MGEA_EINVAL,
+                 "op_recondition: an apply needs done, row_step, gram_state, cur_seg and switches");
+    KvPool pool{};
+    pool.base = pool_dev; pool.n_pages = n_pages; pool.H = H; pool.dh = dh; pool.f16 = f16; pool.arith_batch = arith_batch;
+    pool.layer_stride = (int64_t)n_pages * 2 * H * pool.page_elems();
+    if (gather_seg >= 0)
+        MGEA_TRY(launch_cond_gather(pool, n_layer, page_table_dev, max_pages, lens_dev, slot_tokens, store_dev, gather_seg, n_seg_max, slot_tokens,
+                                    meta_dev, len_dev, B, (hipStream_t)stream));
+    if (sched_dev)
+        MGEA_TRY(launch_cond_apply(pool, n_layer, page_table_dev, max_pages, store_dev, meta_dev, len_dev, sched_dev, done_dev, row_step_dev,
+                                   gram_state_dev, cur_seg_dev, switches_dev, B, (hipStream_t)stream));
+    return MGEA_OK;
+}
+
 int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                                 const mgea_row_logits* lrows, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
                                 int32_t n_class, const int32_t* states_in_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev,

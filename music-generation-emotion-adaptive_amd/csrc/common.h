@@ -332,6 +332,16 @@ int launch_sample(const SampleCall& c, hipStream_t st);
 // partner stay as they are.  partner / scale: device [B].  The caller guarantees that no row is the partner of two rows and that a
 // partner has no partner itself (one workgroup per pair is then the only one that touches its two rows).
 int launch_guidance_mix(float* logits, int B, int V, const int32_t* partner, const float* scale, hipStream_t st);
+// Emotion transitions (recondition.hip; the rule and the store's layout: include/mgea.h, mgea_row_schedule / mgea_op_recondition).
+// gather: positions [0, lens[b]) (lens NULL: Tp) of logical page 0 of every row, layer and head -> the slots of segment `seg` of the
+// conditioning store, and the layout words / the rows' lengths -> meta [4] / cond_len [B].  apply: the launch that opens a scheduled
+// decode step; rows whose segment changes get the new variant's positions back over their pages.  cond_store_bytes: the store's size.
+int64_t cond_store_bytes(const KvPool& pool, int n_layer, int n_seg_max, int B, int slot_tokens);
+int launch_cond_gather(const KvPool& pool, int n_layer, const int32_t* page_table, int max_pages, const int32_t* lens, int Tp, void* store,
+                       int seg, int n_seg_max, int slot_tokens, int32_t* meta, int32_t* cond_len, int B, hipStream_t st);
+int launch_cond_apply(const KvPool& pool, int n_layer, const int32_t* page_table, int max_pages, const void* store, const int32_t* meta,
+                      const int32_t* cond_len, const mgea_row_schedule* sched, const int32_t* done, const int32_t* row_step,
+                      const int32_t* gram_state, int32_t* cur_seg, int32_t* switches, int B, hipStream_t st);
 // ---- the kernels that end a step, and the rows' records (step_tail.hip) ----
 int launch_argmax_advance(const float* pval, const int32_t* pidx, int n_tiles, const StepState& s, int32_t* sampled,
                           int B, hipStream_t st);

@@ -89,10 +89,11 @@ struct mgea_decoder {
     DevGroup dev_p16_rows;   // Prefill16's activations and tables, regrown with its row count (ensure_p16)
     DevGroup dev_p16_mats;   // Prefill16's matrices p16.w / p16.vec, kept across refresh_weights
     DevGroup dev_win;        // the KV window's histories and eviction counters: mgea_decoder_set_window, until the window changes
+    DevGroup dev_cond;       // the conditioning store, the rows' schedules and segments: scheduled generations only (ensure_cond)
     // The handle's other HIP resources, declared behind the device groups, so that they go first (members die in reverse order):
     // the graphs, the pinned staging arrays and the events, then the device memory.
     Event stage_free;        // recorded after the copy out of samp_stage / gram_stage: they may be rewritten once it has completed
-    PinnedGroup pinned;      // samp_stage, gram_stage
+    PinnedGroup pinned;      // samp_stage, gram_stage, guide_stage, cond_stage
 
     // KV pool
     KvPool kv{};
@@ -115,7 +116,7 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, StepForm, scored, steps, windowed, guided): one per launch sequence.  Everything a step reads besides its
+    // Captured decode-step graphs, one per (batch, StepForm, scored, steps, windowed, guided, scheduled): one per launch sequence.  Everything a step reads besides its
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
@@ -165,6 +166,18 @@ struct mgea_decoder {
     float* guide_scale = nullptr;
     int32_t* guide_stage = nullptr;
     int64_t guide_pairs = 0, guide_steps = 0;   // of the last generation (mgea_decoder_guidance_info)
+    // Emotion transitions (mgea_decoder_generate_rows_scheduled; recondition.hip).  Everything here belongs to dev_cond and is allocated by
+    // the first scheduled call, never by create: cond_store holds the K | V of positions [0, len_b) of every prompt variant (cond_bytes
+    // of it; a call that needs more synchronises, drops the scheduled graphs and regrows the whole group), cond_sched [max_batch] the
+    // rows' records, cond_cur_seg [max_batch] their segments, cond_switches [1] the call's switch count, cond_meta [4] / cond_len
+    // [max_batch] the store's layout words and the rows' prompt lengths (written by the gather kernel).  Records reach the device
+    // through the pinned cond_stage, free under stage_free like the sampler records.
+    void* cond_store = nullptr;
+    int64_t cond_bytes = 0;
+    mgea_row_schedule *cond_sched = nullptr, *cond_stage = nullptr;
+    int32_t *cond_cur_seg = nullptr, *cond_switches = nullptr, *cond_meta = nullptr, *cond_len = nullptr;
+    int64_t sched_steps = 0;          // of the last generation (mgea_decoder_schedule_info)
+    bool last_scheduled = false;
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     // The qkv0 table.  In MGEA_POS_REFERENCE mode every decode step adds pos_emb[0] (api_cache.py:99), so the input of layer 0's LN1 +
     // in-projection is tok_emb[id] + pos_emb[0]: its 3 C outputs q | k | v depend on the token id and the weights alone.  An f32 engine
@@ -637,9 +650,18 @@ int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
 // windowed: the step opens with the KV window's evict launch, in front of every append of the step (the rule and why it keeps the
 // previous tail's layer-0 K | V alive: kv_window.hip); the node does not depend on the step's form.
 // guided: the step mixes the pairs' logits rows between the head and the sampler (enqueue_tail); one more node, whatever the pairs are.
-int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, bool windowed, bool guided) {
+// scheduled: behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip): a row whose segment changes
+// gets the new variant's K | V over positions [0, len_b) of its pages before anything of the step reads them; one more node, whatever
+// the records say.  (The previous tail's layer-0 K | V of the fed token sits at position ctx_len >= len_b: never in its way.)
+int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, bool windowed, bool guided, bool scheduled) {
     if (windowed)
         PROF(PC_ROWOP, launch_window_evict(h->page_table, h->max_pages, h->win_S, h->win_R, h->ctx_len, h->done, h->win_evict, B, st));
+    if (scheduled) {
+        KvPool pool = h->kv;
+        if (!tune(TUNE_ATTN_ARITH_PAGES)) pool.arith_batch = 0;   // (as the attention: the switch sends every page id through the table)
+        PROF(PC_ROWOP, launch_cond_apply(pool, h->cfg.n_layer, h->page_table, h->max_pages, h->cond_store, h->cond_meta, h->cond_len,
+                                         h->cond_sched, h->done, h->row_step, h->gram_state, h->cond_cur_seg, h->cond_switches, B, st));
+    }
     StepCall k{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored, qkv0_table(h, B)};
     k.windowed = windowed;
     k.guided = guided;
@@ -656,13 +678,13 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
-// The captured decode step for (B, form, scored, steps, windowed, guided): from the cache, or captured + instantiated now (least recently used
+// The captured decode step for (B, form, scored, steps, windowed, guided, scheduled): from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond StepGraphs::CAP, hipres.h).
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
 int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps, bool windowed,
-               bool guided) {
-    const StepGraphs::Key key{B, form, scored, steps, windowed, guided};
+               bool guided, bool scheduled) {
+    const StepGraphs::Key key{B, form, scored, steps, windowed, guided, scheduled};
     if (const StepGraphs::Entry* e = h->graphs.find(key)) {
         if (steps == 1) h->n.graph_nodes = e->nodes;
         *out = e->exec;
@@ -672,7 +694,7 @@ int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t s
     if (h->graphs.full()) MGEA_CHECK_HIP(hipStreamSynchronize(st));
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided, scheduled);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -1163,6 +1185,59 @@ int check_row_guidance(const mgea_row_guidance* guide, int B, int* n_pairs) {
     return MGEA_OK;
 }
 
+// host check of sched[0, B) (mgea_decoder_generate_rows_scheduled): MGEA_EINVAL naming the first bad row; *n_sched = the rows with
+// more than one segment
+int check_row_schedules(const mgea_row_schedule* sched, int B, int n_seg_max, const int32_t* start_states, int gram_n_state,
+                        const mgea_row_guidance* guide, int* n_sched) {
+    const char* who = "decoder_generate_rows_scheduled";
+    *n_sched = 0;
+    std::vector<char> shadow((size_t)B, 0);
+    for (int b = 0; guide && b < B; ++b)
+        if (guide[b].shadow_row >= 0 && guide[b].shadow_row < B) shadow[(size_t)guide[b].shadow_row] = 1;
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_schedule& r = sched[b];
+        MGEA_REQUIRE(r.n_segments >= 1 && r.n_segments <= MGEA_SCHEDULE_MAX_SEGMENTS, MGEA_EINVAL, "%s: row %d: n_segments %d outside [1, %d]", who, b,
+                     r.n_segments, MGEA_SCHEDULE_MAX_SEGMENTS);
+        MGEA_REQUIRE(r.n_segments <= n_seg_max, MGEA_EINVAL, "%s: row %d: n_segments %d exceeds n_seg_max %d", who, b, r.n_segments, n_seg_max);
+        MGEA_REQUIRE(r.key == 0 || r.key == 1, MGEA_EINVAL, "%s: row %d: key %d (0 = step index, 1 = grammar state)", who, b, r.key);
+        MGEA_REQUIRE(r.reserved == 0, MGEA_EINVAL, "%s: row %d: reserved must be 0", who, b);
+        for (int s = 0; s + 1 < r.n_segments; ++s) {
+            MGEA_REQUIRE(r.threshold[s] >= 0, MGEA_EINVAL, "%s: row %d: threshold[%d] = %d is negative", who, b, s, r.threshold[s]);
+            MGEA_REQUIRE(s == 0 || r.threshold[s] >= r.threshold[s - 1], MGEA_EINVAL, "%s: row %d: thresholds not ascending (%d after %d)", who, b,
+                         r.threshold[s], r.threshold[s - 1]);
+        }
+        if (r.n_segments == 1) continue;
+        MGEA_REQUIRE(!shadow[(size_t)b], MGEA_EINVAL, "%s: row %d is a guidance shadow row: it has one segment (its prompt has no emotion tokens)", who, b);
+        if (r.key == 1) {
+            MGEA_REQUIRE(gram_n_state > 0, MGEA_EINVAL, "%s: row %d: key 1 (grammar state) but no grammar is set", who, b);
+            MGEA_REQUIRE(start_states && start_states[b] >= 0, MGEA_EINVAL, "%s: row %d: key 1 (grammar state) on a row without a start state", who, b);
+        }
+        *n_sched += 1;
+    }
+    return MGEA_OK;
+}
+
+// The buffers of a scheduled generation (dev_cond), big enough for `bytes` of store.  They are allocated, and regrown, by scheduled
+// calls only; a regrow frees pointers the scheduled graphs hold, so it synchronises and drops those.
+int ensure_cond(mgea_decoder* h, int64_t bytes, hipStream_t st) {
+    if (h->cond_store && bytes <= h->cond_bytes) return MGEA_OK;
+    MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying, a freed store still be read
+    h->graphs.drop_scheduled();
+    DevGroup& g = h->dev_cond;
+    g.release();
+    h->cond_bytes = 0;
+    const size_t mb = (size_t)h->cfg.max_batch;
+    if ((!h->cond_stage && h->pinned.alloc(&h->cond_stage, mb * sizeof(mgea_row_schedule))) || g.alloc(&h->cond_store, (size_t)bytes) ||
+        g.alloc(&h->cond_sched, mb * sizeof(mgea_row_schedule)) || g.alloc(&h->cond_cur_seg, mb * sizeof(int32_t)) ||
+        g.alloc(&h->cond_switches, 16) || g.alloc(&h->cond_meta, 16) || g.alloc(&h->cond_len, mb * sizeof(int32_t))) {
+        g.release();
+        set_error("decoder_generate_rows_scheduled: allocation of the conditioning store (%lld MB) failed", (long long)(bytes >> 20));
+        return MGEA_ENOMEM;
+    }
+    h->cond_bytes = bytes;
+    return MGEA_OK;
+}
+
 // mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
 // (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
 // are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  Which of the
@@ -1173,17 +1248,21 @@ int check_row_guidance(const mgea_row_guidance* guide, int B, int* n_pairs) {
 // guide (with rows only; host [B]) or NULL: the rows' guidance pairs (mgea_decoder_generate_rows_guided); any shadow_row >= 0 makes the
 // generation guided -- the mix launch in every step, the shadow rows' inputs overwritten with their conditional rows' --, none leaves
 // every launch as it is without the argument.
+// sched (with rows only; host [B]) or NULL, n_seg_max: the rows' prompt schedules (mgea_decoder_generate_rows_scheduled); prompt_ids_dev
+// is then [n_seg_max][B][Tp].  Any n_segments > 1 makes the generation scheduled -- the variants' prefills and gathers in front of the
+// generation's own, the apply launch in every step --, none leaves every launch as it is without the argument (variant 0 is the prompt).
 struct ScoreIo { const int32_t* forced_dev; float* logprobs_out; float* choice_out; };
 int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
                 const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
                 int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr, const int32_t* start_states = nullptr,
-                const mgea_row_guidance* guide = nullptr) {
+                const mgea_row_guidance* guide = nullptr, const mgea_row_schedule* sched = nullptr, int32_t n_seg_max = 1) {
     const auto& c = h->cfg;
     MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
     MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
     RowRecords rr;   // the step graphs' form; whether to poll for early stops (some row can finish before n_steps)
     bool grammar = false;   // some row has a start state
     int n_pairs = 0;        // guidance pairs: conditional rows with a shadow row
+    int n_sched = 0;        // scheduled rows: more than one prompt variant
     int reserve = Tp + n_steps;
     // With a window set every generation is windowed: P pages per row, no budget clamp, no parking, every page id through the table.
     const bool windowed = h->win_S > 0;
@@ -1209,6 +1288,11 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             grammar = true;
         }
         if (guide) MGEA_TRY(check_row_guidance(guide, B, &n_pairs));
+        if (sched) {   // (n_seg_max itself: checked by the entry point)
+            MGEA_TRY(check_row_schedules(sched, B, n_seg_max, start_states, h->gram_n_state, guide, &n_sched));
+            MGEA_REQUIRE(n_sched == 0 || Tp <= MGEA_KV_PAGE_TOKENS, MGEA_ECAPACITY,
+                         "decoder_generate_rows_scheduled: prompt width %d exceeds one page of %d tokens", Tp, MGEA_KV_PAGE_TOKENS);
+        }
         // A guided pair must run the same steps: rows stopped where their pages end (launch_clamp_budgets) would get budgets of their own
         // prompt lengths.  Under a window nothing is clamped, and each row of a pair evicts on its own schedule.
         MGEA_REQUIRE(n_pairs == 0 || windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY,
@@ -1233,6 +1317,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     }
     const bool scored = score != nullptr;
     const bool guided = n_pairs > 0;
+    const bool scheduled = n_sched > 0;
     // scoring and guidance need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
     // the lowest id)
     const bool biased = rr.form == StepForm::BIASED;
@@ -1240,13 +1325,40 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->last_penalized = false;
     h->gram_steps = 0;
     h->guide_pairs = h->guide_steps = 0;
+    h->sched_steps = 0;
+    h->last_scheduled = false;
     h->n.scored_steps = h->n.penalized_steps = h->n.biased_steps = 0;
+    // positions [0, lens) of the prefill that has just finished -> segment sg of the conditioning store (the pool as the attention sees
+    // it: the allocation rule where the prefill's pages follow it, the table otherwise)
+    auto gather = [&](int sg) {
+        KvPool pool = h->kv;
+        if (!tune(TUNE_ATTN_ARITH_PAGES)) pool.arith_batch = 0;
+        return launch_cond_gather(pool, c.n_layer, h->page_table, h->max_pages, lens_dev, Tp, h->cond_store, sg, n_seg_max, Tp, h->cond_meta,
+                                  h->cond_len, B, st);
+    };
+    if (scheduled) {
+        // The variants behind the first, last to first: each a reset and a prefill of the B prompts with the call's own B, Tp and lens --
+        // the kernels the generation's own prefill takes, so the gathered K | V are bit for bit what a generation from that variant caches.
+        MGEA_TRY(ensure_cond(h, cond_store_bytes(h->kv, c.n_layer, n_seg_max, B, Tp), st));
+        for (int sg = n_seg_max - 1; sg >= 1; --sg) {
+            MGEA_TRY(do_reset(h, B, reserve, st));
+            if (windowed) h->kv.arith_batch = 0;
+            MGEA_TRY(do_forward(h, prompt_ids_dev + (size_t)sg * B * Tp, lens_dev, B, Tp, nullptr, st));
+            MGEA_TRY(gather(sg));
+        }
+    }
     MGEA_TRY(do_reset(h, B, reserve, st));
     if (windowed) {   // the rotation breaks the allocation rule: every page id of the call comes from the table, the prefill's included
         h->kv.arith_batch = 0;
         MGEA_CHECK_HIP(hipMemsetAsync(h->win_evict, 0, (size_t)c.max_batch * sizeof(int32_t), st));
     }
     MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
+    if (scheduled) {   // the generation's own prefill is segment 0; every row starts there
+        MGEA_TRY(gather(0));
+        MGEA_CHECK_HIP(hipMemsetAsync(h->cond_cur_seg, 0, (size_t)c.max_batch * sizeof(int32_t), st));
+        MGEA_CHECK_HIP(hipMemsetAsync(h->cond_switches, 0, 16, st));
+        h->last_scheduled = true;
+    }
     h->win_dirty = windowed;
     const bool capped = !windowed && reserve < Tp + n_steps;   // rows stop where their pages end (launch_clamp_budgets, parking)
     const mgea_decoder::Hist hi = h->hist(windowed);
@@ -1289,6 +1401,10 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_partner, h->guide_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
             MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_scale, scale_stage, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
         }
+        if (scheduled) {   // the rows' schedules, through the pinned staging array (free under the same event as the records')
+            for (int b = 0; b < B; ++b) h->cond_stage[b] = sched[b];
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->cond_sched, h->cond_stage, (size_t)B * sizeof(mgea_row_schedule), hipMemcpyHostToDevice, st));
+        }
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free.ev, st));
         if (capped) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
     } else {
@@ -1307,11 +1423,11 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     }
     if (const int path = qkv0_path(h, B); path >= 0) MGEA_TRY(ensure_qkv0(h, path, st));   // before any capture of this batch size
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1, windowed, guided));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1, windowed, guided, scheduled));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K, windowed, guided));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K, windowed, guided, scheduled));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1319,12 +1435,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided);
+            const int rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided, scheduled);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st, windowed, guided));
+            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st, windowed, guided, scheduled));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1348,6 +1464,7 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
     h->gram_steps = grammar ? launched : 0;
     h->guide_pairs = n_pairs;
     h->guide_steps = guided ? launched : 0;
+    h->sched_steps = scheduled ? launched : 0;
     if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
         float* outs[2] = {score->logprobs_out, score->choice_out};
         const float* hist[2] = {hi.lp, hi.ch};
@@ -1503,6 +1620,48 @@ int mgea_decoder_generate_rows_guided(mgea_decoder* h, const int32_t* prompt_ids
     const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
     return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
                        logprobs_out_dev ? &io : nullptr, start_states, guide);
+}
+
+int mgea_decoder_generate_rows_scheduled(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                         int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                         const int32_t* start_states, const mgea_row_guidance* guide, const mgea_row_schedule* sched,
+                                         int32_t n_seg_max, const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
+                                         float* choice_logprobs_out_dev, void* stream) {
+    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows_scheduled: NULL argument");
+    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
+                 "decoder_generate_rows_scheduled: forced ids and choice log-probabilities need logprobs_out_dev");
+    MGEA_REQUIRE(n_seg_max >= 1 && n_seg_max <= MGEA_SCHEDULE_MAX_SEGMENTS, MGEA_EINVAL, "decoder_generate_rows_scheduled: n_seg_max %d outside [1, %d]",
+                 n_seg_max, MGEA_SCHEDULE_MAX_SEGMENTS);
+    MGEA_REQUIRE(sched || n_seg_max == 1, MGEA_EINVAL, "decoder_generate_rows_scheduled: %d prompt variants but no schedules", n_seg_max);
+    if (logits_rows) {
+        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_scheduled: empty batch");
+        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_scheduled"));
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
+    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
+                       logprobs_out_dev ? &io : nullptr, start_states, guide, sched, n_seg_max);
+}
+
+int mgea_decoder_schedule_info(mgea_decoder* h, int64_t* out, void* stream) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_schedule_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = out[1] = 0;
+    if (!h->last_scheduled) return MGEA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t n = 0;
+    MGEA_CHECK_HIP(hipMemcpyAsync(&n, h->cond_switches, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MGEA_CHECK_HIP(hipStreamSynchronize(st));
+    out[0] = h->sched_steps; out[1] = n;
+    return MGEA_OK;
+}
+
+int mgea_decoder_segments(mgea_decoder* h, int32_t* out_dev, void* stream) {
+    MGEA_REQUIRE(h && out_dev, MGEA_EINVAL, "decoder_segments: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    MGEA_REQUIRE(h->last_scheduled && h->cur_batch > 0, MGEA_EINVAL, "decoder_segments: the last generate() was not scheduled");
+    MGEA_CHECK_HIP(hipMemcpyAsync(out_dev, h->cond_cur_seg, (size_t)h->cur_batch * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MGEA_OK;
 }
 
 int mgea_decoder_guidance_info(mgea_decoder* h, int64_t* out) {

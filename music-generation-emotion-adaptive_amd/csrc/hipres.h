@@ -33,15 +33,16 @@ struct Event {
 // The captured decode steps of a handle, one (graph, exec) pair per key, at most CAP of them.
 struct StepGraphs {
     // two per (batch, form, scored): the single step and the 8-step graph -- (5 forms + 4 scored) x 2 = 18 for one batch size, two batch sizes whole
-    // (the graphs of a windowed engine and of guided generations share the cache and its LRU)
+    // (the graphs of a windowed engine and of guided and scheduled generations share the cache and its LRU)
     static constexpr size_t CAP = 36;
     struct Key {
         int batch; StepForm form; bool scored; int steps;
         bool windowed = false;   // the steps open with the KV window's evict launch and file into the windowed histories (decoder.hip)
         bool guided = false;     // the steps run the guidance-mix launch between the head and the sampler (guidance.hip)
+        bool scheduled = false;  // the steps open with the launch that applies the rows' prompt schedules (recondition.hip)
         bool operator==(const Key& o) const {
             return batch == o.batch && form == o.form && scored == o.scored && steps == o.steps && windowed == o.windowed &&
-                   guided == o.guided;
+                   guided == o.guided && scheduled == o.scheduled;
         }
     };
     struct Entry { Key key; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
@@ -88,6 +89,13 @@ struct StepGraphs {
     void drop_windowed() {
         for (size_t i = entries.size(); i-- > 0;)
             if (entries[i].key.windowed) {
+                graph_destroy(entries[i].graph, entries[i].exec);
+                entries.erase(entries.begin() + (long)i);
+            }
+    }
+    void drop_scheduled() {
+        for (size_t i = entries.size(); i-- > 0;)
+            if (entries[i].key.scheduled) {
                 graph_destroy(entries[i].graph, entries[i].exec);
                 entries.erase(entries.begin() + (long)i);
             }

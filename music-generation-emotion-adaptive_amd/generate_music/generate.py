@@ -556,6 +556,101 @@ def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=51
     return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]
 
 
+def sample_kvcache_transitions(model, prompts: Sequence[Sequence[str]], shares=None, max_len=512, temperature=1.0, top_k=50,
+                               device="cpu", top_p: Optional[float] = None, seed: Optional[int] = None,
+                               repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                               guidance_scale: Optional[float] = None, negative_prompt: Optional[Sequence[str]] = None) -> List[str]:
+    """sample_kvcache_guided for a piece whose conditioning changes on the way (sample_kvcache_guided keeps its parameter list).
+    prompts: 1 to 8 variants of ONE prompt, equal in length (generate_music.transitions.transition_prompts: the first with other
+    [BPM] / [KEY_SIGNATURE] tokens); shares: the segments' relative lengths (None = equal).  The generation starts from prompts[0];
+    when it enters segment s the cached keys and values of its prompt become those of prompts[s].  With a grammar
+    (generate_music.grammar.track_grammar) the segments are ranges of note START classes (transitions.start_thresholds), so every
+    track passes through all the emotions in musical time; without one they are ranges of steps (transitions.step_thresholds).
+    guidance_scale None = no guidance; a number pairs the request with negative_prompt as sample_kvcache_guided does (the shadow row
+    does not switch: it has no emotion tokens).  Returns prompts[0] + the generated tokens.  Build-defined
+    (DecoderEngine.generate_scheduled)."""
+    return generate_requests_transitions(model, [prompts], None if shares is None else [shares], max_len, temperature, top_k, top_p,
+                                         seed, repetition_penalty, logit_bias, min_new_tokens, grammar, guidance_scale,
+                                         None if negative_prompt is None else [list(negative_prompt)])[0]
+
+
+def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequence[str]]], shares=None, max_len=512,
+                                  temperature=1.0, top_k=50, top_p: Optional[float] = None, seed=None, repetition_penalty=None,
+                                  logit_bias=None, min_new_tokens=0, grammar=None, guidance_scale=None,
+                                  negative_prompts=None) -> List[List[str]]:
+    """generate_requests_guided whose requests each bring the variants of their prompt (sample_kvcache_transitions) and, in shares, one
+    list of relative segment lengths per request (None = equal).  guidance_scale None: no request is guided and a generation serves
+    max_batch of them; otherwise every request is a pair and the limits of generate_requests_guided hold."""
+    from mgea.decoder import RowSchedule
+    from .guidance import unconditional_prompt
+    from .transitions import start_thresholds, step_thresholds
+    m = _as_model(model)
+    eng = m._need()
+    n = len(prompt_segments)
+    segs = [[list(v) for v in ps] for ps in prompt_segments]
+    for i, ps in enumerate(segs):
+        if not ps or any(len(v) != len(ps[0]) for v in ps):
+            raise ValueError(f"request {i}: the variants of a prompt must be of one length, got {[len(v) for v in ps]}")
+    shares = [None] * n if shares is None else list(shares)
+    if len(shares) != n:
+        raise ValueError(f"shares: {len(shares)} values for {n} requests")
+    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
+    temps = _per_prompt(temperature, n, "temperature")
+    ks = _per_prompt(top_k, n, "top_k")
+    ps_ = _per_prompt(top_p, n, "top_p")
+    seeds = _per_prompt(seed, n, "seed")
+    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
+    biases = _per_prompt(logit_bias, n, "logit_bias")
+    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
+    guided = guidance_scale is not None
+    scales = [float(v) for v in _per_prompt(guidance_scale if guided else 0.0, n, "guidance_scale")]
+    negs = [None] * n if negative_prompts is None else list(negative_prompts)
+    if len(negs) != n:
+        raise ValueError(f"negative_prompts: {len(negs)} values for {n} requests")
+    ids = [[[tok2id[t] for t in v] for v in ps] for ps in segs]   # KeyError for an unknown token, like api_cache.py:162
+    neg_ids = [None] * n
+    if guided:
+        if eng.max_batch < 2:
+            raise ValueError("guided generation needs a model with max_batch >= 2 (a request is a pair of rows)")
+        neg_ids = [[tok2id[t] for t in (unconditional_prompt(ps[0]) if q is None else list(q))] for ps, q in zip(segs, negs)]
+    budgets = [L - len(p[0]) for L, p in zip(max_lens, ids)]
+    for i in range(n):
+        if mins[i] < 0:
+            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
+    eos = tok2id.get("[END_SEQUENCE]", -1)
+    live = [i for i in range(n) if budgets[i] > 0]
+    gstates = [None] * n
+    if grammar is not None:
+        from .grammar import start_state
+        _use_grammar(eng, grammar)
+        gstates = [start_state(grammar, p[0]) for p in ids]
+    scheds = {}
+    for i in live:
+        sh = [1.0] * len(ids[i]) if shares[i] is None else list(shares[i])
+        if len(sh) != len(ids[i]):
+            raise ValueError(f"request {i}: {len(sh)} shares for {len(ids[i])} prompt variants")
+        scheds[i] = RowSchedule(tuple(start_thresholds(grammar, sh)), 1) if grammar is not None else \
+            RowSchedule(tuple(step_thresholds(budgets[i], sh)), 0)
+    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps_[i], repetition_penalty=pens[i], eos_id=eos,
+                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i])
+            for i in live}
+    gen: Dict[int, List[int]] = {}
+    per = eng.max_batch // 2 if guided else eng.max_batch
+    for c0 in range(0, len(live), per):
+        part = live[c0:c0 + per]
+        steps = max(budgets[i] for i in part)
+        width = max(max(len(ids[i][0]), len(neg_ids[i] or [])) for i in part)
+        if _no_window(eng) and width + steps > eng.max_ctx:
+            raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
+        out = eng.generate_scheduled([ids[i] for i in part], [rows[i] for i in part], [scheds[i] for i in part], steps,
+                                     negative_prompts=[neg_ids[i] for i in part] if guided else None,
+                                     guidance_scale=[scales[i] for i in part]).cpu().tolist()
+        for i, row in zip(part, out):
+            gen[i] = [g for g in row if g >= 0]
+    return [[id2tok[t] for t in ids[i][0] + gen.get(i, [])] for i in range(n)]
+
+
 def sample(prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu") -> List[str]:
     """generate_music/generate.py:46-61: same sampler over the module-level `model`.  With a
     GPTWithKV model this is sample_kvcache; with the post-LN twin `GPT` it recomputes the whole

@@ -51,6 +51,11 @@ class RowGuidance(C.Structure):
     _fields_ = [("shadow_row", C.c_int32), ("scale", C.c_float)]
 
 
+class RowSchedule(C.Structure):
+    """mgea_row_schedule: one batch row's prompt schedule (mgea_decoder_generate_rows_scheduled)."""
+    _fields_ = [("n_segments", C.c_int32), ("key", C.c_int32), ("threshold", C.c_int32 * 7), ("reserved", C.c_int32)]
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -118,6 +123,10 @@ PROTOTYPES = {
     "mgea_decoder_generate_rows_guided": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
                                                    C.POINTER(RowGuidance), _P, _P, _P, _P, _P]),
     "mgea_decoder_guidance_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "mgea_decoder_generate_rows_scheduled": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
+                                                      C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P, _P]),
+    "mgea_decoder_schedule_info": (C.c_int, [_P, C.POINTER(_I64), _P]),
+    "mgea_decoder_segments": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_set_window": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "mgea_decoder_window_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "mgea_decoder_grammar_states": (C.c_int, [_P, _P, _P]),
@@ -171,6 +180,8 @@ PROTOTYPES = {
     "mgea_op_sample_rows_scored": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P, _P, _P, _P]),
     "mgea_op_window_evict": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "mgea_op_guidance_mix": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "mgea_op_recondition": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
+                                      _P, _P, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,
                                               _P, _P, _P]),
     "mgea_op_attention_cls": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),

@@ -527,6 +527,81 @@ def pack_guided(prompts, negative_prompts, rows, guidance_scale, max_batch: int,
     return all_prompts, all_rows, shadow, scales, force_ids
 
 
+SCHEDULE_MAX_SEGMENTS = 8
+
+
+@dataclasses.dataclass(frozen=True)
+class RowSchedule:
+    """One batch row's prompt schedule (mgea_row_schedule, include/mgea.h) and the host model of its rule: the row has
+    len(thresholds) + 1 prompt variants and, at the start of every decode step, is in segment #{s : thresholds[s] <= k}, where k is
+    its step index (key 0) or its grammar state (key 1).  RowSchedule() is a plain row: one segment, never switched."""
+    thresholds: Sequence[int] = ()
+    key: int = 0
+
+    @property
+    def n_segments(self) -> int:
+        return len(self.thresholds) + 1
+
+    def check(self, row: int = 0) -> None:
+        """ValueError naming the row for what the native call would refuse by the record alone."""
+        if not 1 <= self.n_segments <= SCHEDULE_MAX_SEGMENTS:
+            raise ValueError(f"row {row}: n_segments {self.n_segments} outside [1, {SCHEDULE_MAX_SEGMENTS}]")
+        if self.key not in (0, 1):
+            raise ValueError(f"row {row}: key {self.key} (0 = step index, 1 = grammar state)")
+        th = [int(t) for t in self.thresholds]
+        for s, t in enumerate(th):
+            if not 0 <= t < 2 ** 31:
+                raise ValueError(f"row {row}: threshold[{s}] = {t} outside [0, 2^31)")
+            if s and t < th[s - 1]:
+                raise ValueError(f"row {row}: thresholds not ascending ({t} after {th[s - 1]})")
+
+    def record(self) -> "_lib.RowSchedule":
+        rec = _lib.RowSchedule(n_segments=self.n_segments, key=int(self.key), reserved=0)
+        for s, t in enumerate(self.thresholds):
+            rec.threshold[s] = int(t)
+        return rec
+
+    def segment_at(self, key: int) -> int:
+        """The segment a row that is not finished is in at the start of a step whose key value is `key`."""
+        seg = 0
+        for t in self.thresholds:
+            seg += 1 if int(t) <= int(key) else 0
+        return seg
+
+
+def pack_scheduled(prompt_segments, schedules, rows, max_batch: int):
+    """The host half of DecoderEngine.generate_scheduled (no device): per row its prompt variants (a list of id lists, all of one
+    length; a bare id list = one variant) and its RowSchedule (None = plain).  Returns (variants, schedules, n_seg_max): variants[s] =
+    the B prompts of segment s, a row with fewer segments repeating its last one.  ValueError naming the row: a variant count that
+    differs from the schedule's n_segments, variants of different lengths, a prompt wider than a page, key 1 without grammar_state."""
+    rows = list(rows)
+    segs = []
+    for p in prompt_segments:
+        p = p.tolist() if isinstance(p, torch.Tensor) else list(p)
+        segs.append([list(v) for v in p] if p and isinstance(p[0], (list, tuple)) else [list(p)])
+    n = len(segs)
+    schedules = [RowSchedule() if s is None else s for s in ([None] * n if schedules is None else list(schedules))]
+    if len(schedules) != n or len(rows) != n:
+        raise ValueError(f"{n} prompts but {len(schedules)} schedules and {len(rows)} sampler rows")
+    if n > int(max_batch):
+        raise ValueError(f"{n} prompts exceed max_batch {max_batch}")
+    for b, (vs, sc) in enumerate(zip(segs, schedules)):
+        sc.check(b)
+        if len(vs) != sc.n_segments:
+            raise ValueError(f"row {b}: {len(vs)} prompt variants for a schedule of {sc.n_segments} segments")
+        if len(vs[0]) < 1:
+            raise ValueError(f"row {b}: empty prompt")
+        if any(len(v) != len(vs[0]) for v in vs):
+            raise ValueError(f"row {b}: prompt variants of different lengths {[len(v) for v in vs]}")
+        if sc.n_segments > 1 and len(vs[0]) > KV_PAGE_TOKENS:
+            raise ValueError(f"row {b}: a scheduled prompt of {len(vs[0])} tokens exceeds one page of {KV_PAGE_TOKENS}")
+        if sc.n_segments > 1 and sc.key == 1 and rows[b].grammar_state is None:
+            raise ValueError(f"row {b}: key 1 (grammar state) on a row without a grammar_state")
+    n_seg_max = max(sc.n_segments for sc in schedules)
+    variants = [[vs[min(s, len(vs) - 1)] for vs in segs] for s in range(n_seg_max)]
+    return variants, schedules, n_seg_max
+
+
 def _prompt_ids(prompts):
     """prompts (id lists, ragged ok, or an int tensor [B, Tp]) -> (int32 ids [B, Tp] on the host, lens [B] or None)"""
     if isinstance(prompts, torch.Tensor):
@@ -1021,6 +1096,97 @@ class DecoderEngine:
         out = (C.c_int64 * 2)()
         check(self.lib.mgea_decoder_guidance_info(self.h, out))
         return dict(pairs=out[0], guided_steps=out[1])
+
+    def generate_scheduled(self, prompt_segments, rows: Sequence[RowSampling], schedules, n_steps: Optional[int] = None,
+                           scored: bool = False, force_ids=None, negative_prompts=None, guidance_scale=1.5, check_ids: bool = True,
+                           check_bias: bool = True):
+        """generate_rows() whose rows change their prompt in the middle of the generation (mgea_decoder_generate_rows_scheduled;
+        build-defined, the contract: include/mgea.h at mgea_row_schedule).  prompt_segments[b]: row b's prompt variants, id lists of
+        one length (a bare id list = one variant); schedules[b]: its RowSchedule (None = a plain row).  At the start of every step a
+        row whose segment (RowSchedule.segment_at of its step index or grammar state) has changed gets the K | V of the new variant
+        over its prompt's cache positions; everything else of the row stays.  negative_prompts / guidance_scale as in
+        generate_guided: the shadow rows are plain rows.  A call in which no row has more than one segment is generate_guided /
+        generate_scored / generate_rows itself.  Returns the callers' rows: int32 [n, n_steps] or, scored, a ScoredGeneration.
+        ValueError naming the row for what the native call would refuse."""
+        rows = list(rows)
+        n = len(rows)
+        if force_ids is not None and not scored:
+            raise ValueError("force_ids need scored=True")
+        variants, scheds, n_seg_max = pack_scheduled(prompt_segments, schedules, rows, self.max_batch)
+        if n_seg_max == 1:   # nothing is scheduled: the calls there always were
+            return self.generate_guided(variants[0], negative_prompts, rows, guidance_scale, n_steps, force_ids, scored, check_ids,
+                                        check_bias)
+        all_prompts, rows_all, shadow, scales, forced_in = pack_guided(variants[0], negative_prompts, rows, guidance_scale,
+                                                                       self.max_batch, force_ids)
+        B = len(all_prompts)
+        for u in range(n, B):   # a shadow row has one variant: its negative prompt in every segment
+            if len(all_prompts[u]) > KV_PAGE_TOKENS:
+                raise ValueError(f"row {u}: a negative prompt of {len(all_prompts[u])} tokens exceeds one page of {KV_PAGE_TOKENS}")
+        scheds = scheds + [RowSchedule()] * (B - n)
+        segs = []
+        lens = None
+        for s in range(n_seg_max):
+            ids_s, lens = _prompt_ids(variants[s] + all_prompts[n:])
+            segs.append(ids_s)
+        ids = torch.stack(segs, dim=0).contiguous()   # [n_seg_max, B, Tp]: the variants of a row have one length, so one lens vector
+        Tp = ids.shape[2]
+        if Tp > KV_PAGE_TOKENS:
+            raise ValueError(f"prompt width {Tp} exceeds one page of {KV_PAGE_TOKENS} tokens")
+        if n_steps is None:
+            budgets = [int(r.max_new_tokens) for r in rows_all]
+            if min(budgets) <= 0:
+                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
+            n_steps = max(budgets)
+        n_steps = int(n_steps)
+        guided = any(u >= 0 for u in shadow)
+        if self.window is not None:
+            self.window.check_call(Tp, n_steps)
+        elif guided and Tp + n_steps > self.max_ctx:
+            raise ValueError(f"prompt width {Tp} + {n_steps} steps exceed max_ctx {self.max_ctx}: a guided generation is never capped "
+                             "(set a window)")
+        recs = pack_rows(rows_all, self.vocab, n_steps)
+        forced = pack_force_ids(forced_in, B, n_steps, self.vocab)
+        lrecs, keep = pack_row_logits(rows_all, self.vocab, self.device, check_bias)
+        starts = self._start_states(rows_all)
+        guide = (_lib.RowGuidance * B)(*[_lib.RowGuidance(shadow_row=u, scale=s) for u, s in zip(shadow, scales)]) if guided else None
+        srecs = (_lib.RowSchedule * B)(*[s.record() for s in scheds])
+        checked = self._check_ids(ids.reshape(-1, Tp)) and (forced is None or not forced.is_cuda)
+        with self._on_stream():
+            ids = ids.to(self.device).contiguous()
+            lens = None if lens is None else lens.to(self.device).contiguous()
+            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
+            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
+                forced.record_stream(self.stream)
+            w = max(n_steps, 1)
+            out = torch.empty(B, w, dtype=torch.int32, device=self.device)
+            lp = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
+            ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
+            for t in keep:   # uploaded on the caller's stream, read by the engine's
+                t.record_stream(self.stream)
+            check(self.lib.mgea_decoder_generate_rows_scheduled(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
+                                                                srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
+        self._cur_batch = B
+        self._epoch += 1
+        if check_ids and not checked:
+            self.id_errors()
+        if scored:
+            return ScoredGeneration(out[:n, :n_steps], lp[:n, :n_steps], ch[:n, :n_steps])
+        return out[:n, :n_steps]
+
+    def schedule_info(self):
+        """The scheduled decode steps and the switches (rows x times a row's prompt K | V was replaced) of the last generation, both 0
+        if it was not scheduled (one stream sync)."""
+        out = (C.c_int64 * 2)()
+        with self._on_stream():
+            check(self.lib.mgea_decoder_schedule_info(self.h, out, self._sp()))
+        return dict(scheduled_steps=out[0], switches=out[1])
+
+    def segments(self) -> torch.Tensor:
+        """int32 [B] on the device: every row's segment after the last scheduled generation (shadow rows behind the callers' rows)."""
+        with self._on_stream():
+            out = torch.empty(self._cur_batch, dtype=torch.int32, device=self.device)
+            check(self.lib.mgea_decoder_segments(self.h, ptr(out), self._sp()))
+        return out
 
     def score(self, prompts, continuations, rows: Optional[Sequence[RowSampling]] = None):
         """Log-probabilities of given continuations under the model, as sample_kvcache would see them: a teacher-forced

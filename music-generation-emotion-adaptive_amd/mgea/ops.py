@@ -380,6 +380,62 @@ def window_evict(page_table: torch.Tensor, sink_pages: int, ring_pages: int, ctx
     return pt, cl, ev
 
 
+def recondition(pool: torch.Tensor, store: torch.Tensor, lens, page_table=None, gather_seg: int = -1, schedules=None, done=None,
+                row_step=None, gram_state=None, cur_seg=None):
+    """The two kernels of a scheduled generation (mgea_op_recondition), alone, on COPIES of a KV pool [n_layer, n_pages, 2, H, 64 * dh]
+    (fp32 or fp16, the page layouts of csrc/common.h) and of a conditioning store [n_seg_max, n_layer, B, 2 * H * dh * slot_tokens] of
+    the pool's dtype.  lens: the B rows' prompt lengths (1 .. slot_tokens).  page_table None: row b's page is physical page b (the
+    decoder's allocation rule); else int32 [B, max_pages], column 0 = the rows' pages.  gather_seg >= 0: the rows' positions
+    [0, len) -> the slots of that segment.  schedules (B mgea.decoder.RowSchedule, or None = no apply): then one scheduled step's rule
+    over done / row_step / gram_state / cur_seg (B ints each; default 0, gram_state -1).  Returns (pool, store, cur_seg, switches)
+    as the launches leave them.  Sizes are checked here (the kernels trust them): RuntimeError."""
+    lib = _lib.load()
+    if pool.dim() != 5 or pool.shape[2] != 2 or pool.dtype not in (torch.float32, torch.float16) or store.dim() != 4 or store.dtype != pool.dtype:
+        raise RuntimeError("recondition: pool must be [n_layer, n_pages, 2, H, 64 * dh] and store [n_seg_max, n_layer, B, slot] of one dtype (f32 / f16)")
+    L, n_pages, _, H, pe = pool.shape
+    dh = pe // _lib.KV_PAGE_TOKENS
+    lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+    B = len(lens)
+    n_seg_max = store.shape[0]
+    slot_tokens = store.shape[3] // (2 * H * dh) if dh else 0
+    if pe != dh * _lib.KV_PAGE_TOKENS or store.shape[1] != L or store.shape[2] != B or B < 1 or store.shape[3] != 2 * H * dh * slot_tokens:
+        raise RuntimeError(f"recondition: store {list(store.shape)} does not fit pool {list(pool.shape)} and {B} rows")
+    if any(not 1 <= v <= min(slot_tokens, _lib.KV_PAGE_TOKENS) for v in lens):
+        raise RuntimeError(f"recondition: lens {lens} outside [1, {slot_tokens}]")
+    pl = pool.to("cuda").contiguous().clone()
+    stc = store.to("cuda").contiguous().clone()
+    pt = None
+    if page_table is not None:
+        pt = torch.as_tensor(page_table).to(device="cuda", dtype=torch.int32).contiguous()
+        if pt.dim() != 2 or pt.shape[0] != B or int(pt[:, 0].min()) < 0 or int(pt[:, 0].max()) >= n_pages:
+            raise RuntimeError("recondition: page_table must be [B, max_pages] with column 0 inside the pool")
+    elif B > n_pages:
+        raise RuntimeError(f"recondition: {B} rows but {n_pages} pages")
+
+    def vec(v, default):
+        v = [default] * B if v is None else [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+        if len(v) != B:
+            raise RuntimeError(f"recondition: a vector of {len(v)} values for {B} rows")
+        return torch.tensor(v, dtype=torch.int32, device="cuda")
+    dn, rs, gs, cs = vec(done, 0), vec(row_step, 0), vec(gram_state, -1), vec(cur_seg, 0)
+    ln = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    ln_out = ln.clone()   # (the gather files the lengths it read here; the apply reads them)
+    meta = torch.tensor([slot_tokens, B, n_seg_max, 0], dtype=torch.int32, device="cuda")
+    sw = torch.zeros(4, dtype=torch.int32, device="cuda")
+    sched = None
+    if schedules is not None:
+        schedules = list(schedules)
+        if len(schedules) != B:
+            raise RuntimeError(f"recondition: {len(schedules)} schedules for {B} rows")
+        recs = (_lib.RowSchedule * B)(*[s.record() for s in schedules])
+        sched = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.int32).to("cuda")
+    check(lib.mgea_op_recondition(ptr(pl), L, n_pages, H, dh, int(pool.dtype == torch.float16), 0 if pt is not None else n_pages, ptr(pt),
+                                  1 if pt is None else pt.shape[1], ptr(stc), n_seg_max, slot_tokens, ptr(meta), ptr(ln_out), B,
+                                  int(gather_seg), ptr(ln), ptr(sched), ptr(dn), ptr(rs), ptr(gs), ptr(cs), ptr(sw), stream_ptr()))
+    torch.cuda.synchronize()
+    return pl, stc, cs, int(sw[0])
+
+
 def guidance_mix(logits: torch.Tensor, partner, scale) -> torch.Tensor:
     """The mix launch of a guided decode step (mgea_op_guidance_mix), alone, on a COPY of logits [>= B, V] (B = len(partner); rows
     behind B are guard rows the kernel must not touch): for every row c with u = partner[c] >= 0, both rows become
