@@ -7,6 +7,7 @@
 
 #include "../../include/mgea.h"
 #include "gemm16_plan.h"
+#include "gen_plan.h"   // GenRequest / StepKind / GenPlan, the rows' host checks, MGEA_REQUIRE / MGEA_TRY
 
 namespace mgea {
 
@@ -22,20 +23,6 @@ const char* get_error();
                               __FILE__, __LINE__);                                    \
             return MGEA_EHIP;                                                         \
         }                                                                             \
-    } while (0)
-
-#define MGEA_REQUIRE(cond, code, ...)            \
-    do {                                         \
-        if (!(cond)) {                           \
-            ::mgea::set_error(__VA_ARGS__);      \
-            return (code);                       \
-        }                                        \
-    } while (0)
-
-#define MGEA_TRY(expr)               \
-    do {                             \
-        int _rc = (expr);            \
-        if (_rc != MGEA_OK) return _rc; \
     } while (0)
 
 // ---- A/B and test switches (tools/README.md) ------------------------------------------------
@@ -210,29 +197,7 @@ static inline SamplerParams sampler_params(const mgea_row_sampler& r) {
     return SamplerParams{r.temperature, r.top_k, r.top_p, r.eos_id, (uint32_t)r.seed, (uint32_t)(r.seed >> 32), r.repetition_penalty,
                          r.stream, r.max_new_tokens > 0 ? r.max_new_tokens : MGEA_NO_BUDGET, MGEA_NO_BUDGET, 0, 0};
 }
-// The tail of a decode step -- everything after the LM head -- has five launch sequences, and a generation runs one of them on every step:
-//   GREEDY (every row has top_k == 1)  the head leaves per-tile (max, argmax) partials and no logits row; an argmax tail merges them
-//   SAMPLED                            the head writes the logits row; the plain sampler draws from it
-//   PENALIZED (a row's penalty != 1)   as SAMPLED with the PENALTY sampler over the rows' presence bitmaps, which the tail keeps up to
-//                                      date; a greedy row is top_k = 1 of its penalized row (the head's partials know no penalty)
-//   BIASED (a row's bias or min_new)   as PENALIZED with the BIAS sampler and the rows' bias buffer (a penalty of 1 changes nothing)
-//   GRAMMAR (a row's start state >= 0) as BIASED with the GRAMMAR sampler: the row's automaton state masks the classes its table bans
-//                                      and the sampler's bookkeeping thread moves the state on (GrammarArgs below)
-// The form is the key of the captured step graphs: every other setting of a request lives in the rows' device records.
-enum class StepForm { GREEDY = 0, SAMPLED, PENALIZED, BIASED, GRAMMAR };
-static inline StepForm step_form(bool all_greedy, bool any_penalized, bool any_biased) {
-    return any_biased ? StepForm::BIASED : any_penalized ? StepForm::PENALIZED : all_greedy ? StepForm::GREEDY : StepForm::SAMPLED;
-}
-static inline bool form_has_presence(StepForm f) { return f == StepForm::PENALIZED || f == StepForm::BIASED || f == StepForm::GRAMMAR; }
-static inline bool form_has_bias(StepForm f) { return f == StepForm::BIASED || f == StepForm::GRAMMAR; }
-
-// host check of rows[0, B) (mgea_decoder_generate_rows, mgea_op_sample_rows): MGEA_EINVAL naming the first bad row; n_steps < 0 skips the
-// budget check
-int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who);
-// host check of the rows' mgea_row_logits records: reserved == 0, 0 <= min_new_tokens <= n_steps (n_steps < 0: no upper bound)
-int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who);
-// checked rows [B] (+ lrows [B] or NULL) -> out[B] and the batch's form; may_stop_early: some row has an EOS id or a budget below n_steps
-struct RowRecords { StepForm form; bool any_penalty; bool may_stop_early; };
+// checked rows [B] (+ lrows [B] or NULL) -> out[B]; the batch's form and flags are row_records' (gen_plan.h, with the rows' host checks)
 RowRecords build_row_records(const mgea_row_sampler* rows, const mgea_row_logits* lrows, int B, int n_steps, SamplerParams* out);
 constexpr int MGEA_SAMPLER_MAX_VOCAB = 14336;   // the sampler keeps a row in registers: 256 threads x 56 logits
 // Repetition penalty (mgea_decoder_generate_penalized): per row a presence bitmap of ceil(V / 32) words, bit id & 31 of word id >> 5

@@ -116,7 +116,7 @@ struct mgea_decoder {
     bool no_gemv = false;        // MGEA_DECODER_NOGEMV=1: keep the MFMA skinny GEMMs for batches of <= 2 rows too (A/B)
     bool force_unfused = false;  // MGEA_DECODER_UNFUSED=1: keep the 9-launch-per-layer path (A/B and fallback)
     int64_t slab_cap = 0;
-    // Captured decode-step graphs, one per (batch, StepForm, scored, steps, windowed, guided, scheduled): one per launch sequence.  Everything a step reads besides its
+    // Captured decode-step graphs, one per (batch, steps, StepKind): one per launch sequence.  Everything a step reads besides its
     // structure lives in device memory (per-row state, page table, presence bitmaps, and the rows' sampler records in samp_dev), so a
     // request with a new seed / temperature / top-k / top-p / EOS id / repetition penalty / budget -- or a batch whose rows differ in
     // them -- replays an existing graph: no capture, no instantiate.
@@ -126,7 +126,6 @@ struct mgea_decoder {
     // repetition penalty: per row the set of ids it has seen (prompt + generated), [max_batch][presence_words(vocab)] (common.h);
     // seeded by a penalized generate() after its prefill, then updated by the kernel that commits each row's token
     uint32_t* presence = nullptr;
-    bool last_penalized = false;   // the last generate() applied a penalty (or a bias): presence holds its rows
     // logit bias: [max_batch][vocab] fp32, row b = the vector row b adds to its logits when its record has bias_on.  A biased generate()
     // copies the rows' vectors here in stream order, so the captured graphs hold this pointer whatever the request's values.
     float* bias = nullptr;
@@ -157,7 +156,7 @@ struct mgea_decoder {
     int32_t *gram_class = nullptr, *gram_next = nullptr, *gram_state = nullptr, *gram_stage = nullptr;
     uint32_t* gram_allow = nullptr;
     int gram_n_state = 0, gram_n_class = 0;
-    int64_t gram_uploads = 0, gram_steps = 0;
+    int64_t gram_uploads = 0;
     // Classifier-free guidance (mgea_decoder_generate_rows_guided; guidance.hip): guide_partner [max_batch] holds the shadow row of every
     // conditional row (-1 elsewhere), guide_scale [max_batch] its scale.  Allocated at create behind the grammar's buffers and filled per
     // call through the pinned guide_stage ([max_batch] partners, then [max_batch] scales; free under stage_free like the records), so
@@ -165,7 +164,6 @@ struct mgea_decoder {
     int32_t* guide_partner = nullptr;
     float* guide_scale = nullptr;
     int32_t* guide_stage = nullptr;
-    int64_t guide_pairs = 0, guide_steps = 0;   // of the last generation (mgea_decoder_guidance_info)
     // Emotion transitions (mgea_decoder_generate_rows_scheduled; recondition.hip).  Everything here belongs to dev_cond and is allocated by
     // the first scheduled call, never by create: cond_store holds the K | V of positions [0, len_b) of every prompt variant (cond_bytes
     // of it; a call that needs more synchronises, drops the scheduled graphs and regrows the whole group), cond_sched [max_batch] the
@@ -176,8 +174,6 @@ struct mgea_decoder {
     int64_t cond_bytes = 0;
     mgea_row_schedule *cond_sched = nullptr, *cond_stage = nullptr;
     int32_t *cond_cur_seg = nullptr, *cond_switches = nullptr, *cond_meta = nullptr, *cond_len = nullptr;
-    int64_t sched_steps = 0;          // of the last generation (mgea_decoder_schedule_info)
-    bool last_scheduled = false;
     AttnSplit attn_split{};        // scratch of the split-context decode attention (small batches; attn_paged.hip)
     // The qkv0 table.  In MGEA_POS_REFERENCE mode every decode step adds pos_emb[0] (api_cache.py:99), so the input of layer 0's LN1 +
     // in-projection is tok_emb[id] + pos_emb[0]: its 3 C outputs q | k | v depend on the token id and the weights alone.  An f32 engine
@@ -193,8 +189,16 @@ struct mgea_decoder {
     bool qkv0_no_mem[2] = {false, false};  // the table could not be allocated: the path keeps the launch for the life of the handle (never
                                            // retried: the graphs of a batch size have one form)
     int32_t* qkv0_ids = nullptr;   // 0 .. vocab - 1, then 64 zeros: the ids and the ctx_len of the build launches
-    // what mgea_decoder_stats reports besides the graph cache's own two figures; the *_steps and graph_replays are of the last generation
-    struct Counters { int64_t graph_nodes = 0, graph_replays = 0, scored_steps = 0, prefill16_forwards = 0, penalized_steps = 0, biased_steps = 0; } n;
+    // What the last generate() did, for the _info and stats entry points.  do_generate assigns it whole: zeroed once the call is
+    // planned, with the two flags once its prefill is through, with the step counts once its steps have run.
+    struct LastGen {
+        bool penalized = false;   // it applied a penalty (or a bias): presence holds its rows
+        bool scheduled = false;   // it was scheduled: cond_cur_seg / cond_switches hold its rows
+        int64_t graph_replays = 0, scored_steps = 0, penalized_steps = 0, biased_steps = 0, gram_steps = 0, guide_pairs = 0, guide_steps = 0,
+                sched_steps = 0;
+    } last;
+    // what mgea_decoder_stats reports of the handle's lifetime, besides the graph cache's own two figures
+    struct Counters { int64_t graph_nodes = 0, prefill16_forwards = 0; } n;
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline leg)
     int prof_stride = 0;  // 0 = off; n = time every n-th decode step of generate(), run eagerly
     bool prof_now = false;
@@ -480,23 +484,20 @@ int run_blocks_fused(mgea_decoder* h, int B, int T, const int32_t* lens, bool us
 }
 
 // One decode step (T = 1) of the whole batch.
-// form: the launch sequence of the step's tail (common.h); nothing below looks at a sampler setting to choose a kernel.
+// kind: the step's launch sequence (StepKind, gen_plan.h); nothing below looks at a sampler setting to choose a kernel.
 // pd: the rows' device records (generate()), or NULL and pv by value on every row (mgea_decoder_step).
 // primed: x already holds the embedding (+ LN statistics) of cur_ids -- generate() keeps that invariant on the fused path by
 // fusing the next step's embedding into this step's tail, so a replayed step is 32 launches.
 struct StepCall {
-    int B; StepForm form;
+    int B; StepKind kind;
     const SamplerParams* pd; SamplerParams pv;
     float* logits_out;   // optional
     bool primed;
-    bool scored = false;   // the scored sampler (never with the GREEDY form: scoring needs the logits row)
     // primed steps only: the qkv0 table of the step's decode path -- layer 0's q | k | v arrive primed too (no in-projection launch for
     // layer 0) and the tail gathers them for the next step; NULL: the launch
     const float* qkv0 = nullptr;
-    bool windowed = false;   // a step of a windowed generation: it files into the windowed histories (mgea_decoder::hist)
-    bool guided = false;     // the guidance-mix launch over the engine's logits, between the head and the sampler (never GREEDY)
     // where the head writes the logits row: the caller's buffer, the engine's `own` for the sampler, nowhere for the argmax tails
-    float* head_out(float* own) const { return logits_out ? logits_out : (form == StepForm::GREEDY ? nullptr : own); }
+    float* head_out(float* own) const { return logits_out ? logits_out : (kind.form == StepForm::GREEDY ? nullptr : own); }
 };
 
 // What the kernel that embeds the next step's token works on; qkv0: the table of the step's path, or NULL (TailArgs, common.h)
@@ -518,11 +519,11 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
     const auto& c = h->cfg;
     const int B = k.B, C = c.d_model, V = c.vocab;
     // (with records the EOS id, like the other scalars, is read from them -- the captured graph's form)
-    const mgea_decoder::Hist hi = h->hist(k.windowed);
+    const mgea_decoder::Hist hi = h->hist(k.kind.windowed);
     const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, hi.ids, hi.stride, k.pv.eos_id, k.pd};
     const TailArgs t = tail_args(h, s, k.primed ? k.qkv0 : nullptr);
-    if (k.form == StepForm::GREEDY) {
-        MGEA_REQUIRE(!k.scored && !k.guided, MGEA_EINVAL, "internal: a scored or guided step never takes the greedy form");
+    if (k.kind.form == StepForm::GREEDY) {
+        MGEA_REQUIRE(!k.kind.scored && !k.kind.guided, MGEA_EINVAL, "internal: a scored or guided step never takes the greedy form");
         if (k.primed)
             PROF(PC_SAMPLE, launch_argmax_advance_embed(h->pmax_val, h->pmax_idx, n_partials, t, h->sampled, B, st));
         else if (n_partials > 0)
@@ -532,22 +533,22 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
         return MGEA_OK;
     }
     // guided: every pair's two logits rows become the pair's mixed row, in place, before the sampler reads them
-    if (k.guided) PROF(PC_SAMPLE, launch_guidance_mix(lg, B, V, h->guide_partner, h->guide_scale, st));
-    uint32_t* pres = form_has_presence(k.form) ? h->presence : nullptr;
+    if (k.kind.guided) PROF(PC_SAMPLE, launch_guidance_mix(lg, B, V, h->guide_partner, h->guide_scale, st));
+    uint32_t* pres = form_has_presence(k.kind.form) ? h->presence : nullptr;
     SampleCall sc{};
     sc.logits = lg; sc.B = B; sc.V = V;
     sc.params_dev = k.pd; sc.params = k.pv; sc.row_step_dev = h->row_step;
     sc.ids_out = h->sampled; sc.tail = k.primed ? &t : nullptr;
-    sc.presence = pres; sc.bias = form_has_bias(k.form) ? h->bias : nullptr;
-    if (k.form == StepForm::GRAMMAR)
+    sc.presence = pres; sc.bias = form_has_bias(k.kind.form) ? h->bias : nullptr;
+    if (k.kind.form == StepForm::GRAMMAR)
         sc.grammar = GrammarArgs{h->gram_class, h->gram_next, h->gram_allow, h->gram_state, h->gram_state, h->done,
                                  h->gram_n_state, h->gram_n_class, grammar_words(h->gram_n_class), h->err_flag};
     const int hs = hi.stride;
-    if (k.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
+    if (k.kind.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
         sc.score = ScoreArgs{hi.forced, hs, k.primed ? hi.lp : h->lp_step, k.primed ? hi.ch : h->ch_step, hs, h->err_flag};
     PROF(PC_SAMPLE, launch_sample(sc, st));
     const ScoreFile sf{h->lp_step, h->ch_step, hi.lp, hi.ch, hs};
-    if (!k.primed) PROF(PC_ROWOP, launch_advance(h->sampled, s, B, st, pres, V, k.scored ? &sf : nullptr));
+    if (!k.primed) PROF(PC_ROWOP, launch_advance(h->sampled, s, B, st, pres, V, k.kind.scored ? &sf : nullptr));
     return MGEA_OK;
 }
 
@@ -583,7 +584,7 @@ int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     MGEA_TRY(gemm(h, h->x, C, h->head_w(), B, V, C, &S, st));
     float* lg = k.head_out(h->logits);
     PROF(PC_SAMPLE, launch_logits_argmax(h->slabs, S, slab_floats(B, V), (int)slab_ld(V), h->head_b(), lg, B, V,
-                                  k.form == StepForm::GREEDY ? h->sampled : nullptr, st));
+                                  k.kind.form == StepForm::GREEDY ? h->sampled : nullptr, st));
     return enqueue_tail(h, k, lg, 0, st);
 }
 
@@ -653,19 +654,16 @@ int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
 // scheduled: behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip): a row whose segment changes
 // gets the new variant's K | V over positions [0, len_b) of its pages before anything of the step reads them; one more node, whatever
 // the records say.  (The previous tail's layer-0 K | V of the fed token sits at position ctx_len >= len_b: never in its way.)
-int enqueue_gen_step(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, bool windowed, bool guided, bool scheduled) {
-    if (windowed)
+int enqueue_gen_step(mgea_decoder* h, int B, const StepKind& kind, hipStream_t st) {
+    if (kind.windowed)
         PROF(PC_ROWOP, launch_window_evict(h->page_table, h->max_pages, h->win_S, h->win_R, h->ctx_len, h->done, h->win_evict, B, st));
-    if (scheduled) {
+    if (kind.scheduled) {
         KvPool pool = h->kv;
         if (!tune(TUNE_ATTN_ARITH_PAGES)) pool.arith_batch = 0;   // (as the attention: the switch sends every page id through the table)
         PROF(PC_ROWOP, launch_cond_apply(pool, h->cfg.n_layer, h->page_table, h->max_pages, h->cond_store, h->cond_meta, h->cond_len,
                                          h->cond_sched, h->done, h->row_step, h->gram_state, h->cond_cur_seg, h->cond_switches, B, st));
     }
-    StepCall k{B, form, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), scored, qkv0_table(h, B)};
-    k.windowed = windowed;
-    k.guided = guided;
-    return enqueue_step(h, k, st);
+    return enqueue_step(h, StepCall{B, kind, h->samp_dev, SamplerParams{}, nullptr, fused_ok(h, B), qkv0_table(h, B)}, st);
 }
 
 // embedding (+ LN statistics, or through the qkv0 table) of cur_ids into the buffers the next generate() step will read
@@ -678,13 +676,12 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
                               c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
 }
 
-// The captured decode step for (B, form, scored, steps, windowed, guided, scheduled): from the cache, or captured + instantiated now (least recently used
+// The captured graph of `steps` decode steps of `kind` over B rows: from the cache, or captured + instantiated now (least recently used
 // entry evicted beyond StepGraphs::CAP, hipres.h).
 // steps > 1: that many consecutive decode steps in one graph (switch decoder_graph_steps; the per-step state is in device memory, so the
 // steps of a graph are as independent of the host as the graphs are of each other)
-int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t st, hipGraphExec_t* out, int steps, bool windowed,
-               bool guided, bool scheduled) {
-    const StepGraphs::Key key{B, form, scored, steps, windowed, guided, scheduled};
+int step_graph(mgea_decoder* h, int B, const StepKind& kind, int steps, hipStream_t st, hipGraphExec_t* out) {
+    const StepGraphs::Key key{B, steps, kind};
     if (const StepGraphs::Entry* e = h->graphs.find(key)) {
         if (steps == 1) h->n.graph_nodes = e->nodes;
         *out = e->exec;
@@ -694,7 +691,7 @@ int step_graph(mgea_decoder* h, int B, StepForm form, bool scored, hipStream_t s
     if (h->graphs.full()) MGEA_CHECK_HIP(hipStreamSynchronize(st));
     MGEA_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = MGEA_OK;
-    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided, scheduled);
+    for (int k = 0; k < steps && rc == MGEA_OK; ++k) rc = enqueue_gen_step(h, B, kind, st);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(st, &g);
     if (rc != MGEA_OK) {
@@ -1150,7 +1147,7 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
     if (ids_in_dev)
         MGEA_CHECK_HIP(hipMemcpyAsync(h->cur_ids, ids_in_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     // eager single step: the scalars travel by value
-    MGEA_TRY(enqueue_step(h, StepCall{B, step_form(s->top_k == 1, false, false), nullptr, sampler_params(*s), logits_out_dev, false}, st));
+    MGEA_TRY(enqueue_step(h, StepCall{B, StepKind{step_form(s->top_k == 1, false, false)}, nullptr, sampler_params(*s), logits_out_dev, false}, st));
     h->host_max_len += 1;
     if (ids_out_dev)
         MGEA_CHECK_HIP(hipMemcpyAsync(ids_out_dev, h->sampled, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -1160,69 +1157,12 @@ int mgea_decoder_step(mgea_decoder* h, const int32_t* ids_in_dev, const mgea_sam
 }  // extern "C"
 
 namespace {
-// host check of guide[0, B) (mgea_decoder_generate_rows_guided): MGEA_EINVAL naming the first bad row; *n_pairs = the conditional rows
-int check_row_guidance(const mgea_row_guidance* guide, int B, int* n_pairs) {
-    const char* who = "decoder_generate_rows_guided";
-    *n_pairs = 0;
-    for (int b = 0; b < B; ++b) {
-        const int32_t u = guide[b].shadow_row;
-        MGEA_REQUIRE(u >= -1 && u < B, MGEA_EINVAL, "%s: row %d: shadow_row %d outside [-1, %d)", who, b, u, B);
-        MGEA_REQUIRE(u != b, MGEA_EINVAL, "%s: row %d: a row cannot be its own shadow", who, b);
-        if (u < 0) continue;
-        MGEA_REQUIRE(std::isfinite(guide[b].scale) && guide[b].scale >= 0.f, MGEA_EINVAL, "%s: row %d: scale %g must be finite and >= 0", who, b,
-                     (double)guide[b].scale);
-    }
-    std::vector<int> owner((size_t)B, -1);   // the conditional row of every shadow
-    for (int b = 0; b < B; ++b) {
-        const int32_t u = guide[b].shadow_row;
-        if (u < 0) continue;
-        MGEA_REQUIRE(guide[u].shadow_row < 0, MGEA_EINVAL, "%s: row %d: its shadow row %d is conditional itself (shadow_row %d)", who, b, u,
-                     guide[u].shadow_row);
-        MGEA_REQUIRE(owner[(size_t)u] < 0, MGEA_EINVAL, "%s: row %d: row %d is already the shadow of row %d", who, b, u, owner[(size_t)u]);
-        owner[(size_t)u] = b;
-        *n_pairs += 1;
-    }
-    return MGEA_OK;
-}
-
-// host check of sched[0, B) (mgea_decoder_generate_rows_scheduled): MGEA_EINVAL naming the first bad row; *n_sched = the rows with
-// more than one segment
-int check_row_schedules(const mgea_row_schedule* sched, int B, int n_seg_max, const int32_t* start_states, int gram_n_state,
-                        const mgea_row_guidance* guide, int* n_sched) {
-    const char* who = "decoder_generate_rows_scheduled";
-    *n_sched = 0;
-    std::vector<char> shadow((size_t)B, 0);
-    for (int b = 0; guide && b < B; ++b)
-        if (guide[b].shadow_row >= 0 && guide[b].shadow_row < B) shadow[(size_t)guide[b].shadow_row] = 1;
-    for (int b = 0; b < B; ++b) {
-        const mgea_row_schedule& r = sched[b];
-        MGEA_REQUIRE(r.n_segments >= 1 && r.n_segments <= MGEA_SCHEDULE_MAX_SEGMENTS, MGEA_EINVAL, "%s: row %d: n_segments %d outside [1, %d]", who, b,
-                     r.n_segments, MGEA_SCHEDULE_MAX_SEGMENTS);
-        MGEA_REQUIRE(r.n_segments <= n_seg_max, MGEA_EINVAL, "%s: row %d: n_segments %d exceeds n_seg_max %d", who, b, r.n_segments, n_seg_max);
-        MGEA_REQUIRE(r.key == 0 || r.key == 1, MGEA_EINVAL, "%s: row %d: key %d (0 = step index, 1 = grammar state)", who, b, r.key);
-        MGEA_REQUIRE(r.reserved == 0, MGEA_EINVAL, "%s: row %d: reserved must be 0", who, b);
-        for (int s = 0; s + 1 < r.n_segments; ++s) {
-            MGEA_REQUIRE(r.threshold[s] >= 0, MGEA_EINVAL, "%s: row %d: threshold[%d] = %d is negative", who, b, s, r.threshold[s]);
-            MGEA_REQUIRE(s == 0 || r.threshold[s] >= r.threshold[s - 1], MGEA_EINVAL, "%s: row %d: thresholds not ascending (%d after %d)", who, b,
-                         r.threshold[s], r.threshold[s - 1]);
-        }
-        if (r.n_segments == 1) continue;
-        MGEA_REQUIRE(!shadow[(size_t)b], MGEA_EINVAL, "%s: row %d is a guidance shadow row: it has one segment (its prompt has no emotion tokens)", who, b);
-        if (r.key == 1) {
-            MGEA_REQUIRE(gram_n_state > 0, MGEA_EINVAL, "%s: row %d: key 1 (grammar state) but no grammar is set", who, b);
-            MGEA_REQUIRE(start_states && start_states[b] >= 0, MGEA_EINVAL, "%s: row %d: key 1 (grammar state) on a row without a start state", who, b);
-        }
-        *n_sched += 1;
-    }
-    return MGEA_OK;
-}
-
 // The buffers of a scheduled generation (dev_cond), big enough for `bytes` of store.  They are allocated, and regrown, by scheduled
 // calls only; a regrow frees pointers the scheduled graphs hold, so it synchronises and drops those.
 int ensure_cond(mgea_decoder* h, int64_t bytes, hipStream_t st) {
     if (h->cond_store && bytes <= h->cond_bytes) return MGEA_OK;
     MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying, a freed store still be read
-    h->graphs.drop_scheduled();
+    h->graphs.drop_if([](const StepGraphs::Key& k) { return k.kind.scheduled; });
     DevGroup& g = h->dev_cond;
     g.release();
     h->cond_bytes = 0;
@@ -1238,196 +1178,155 @@ int ensure_cond(mgea_decoder* h, int64_t bytes, hipStream_t st) {
     return MGEA_OK;
 }
 
-// mgea_decoder_generate(_penalized, _rows); the caller holds h->mu.  rows == NULL: the uniform form, `s` and `penalty` on every row
-// (penalty == 1: no penalty, exactly the unpenalized launch sequence).  rows [B] (host, checked): one record per row; `s` and `penalty`
-// are then ignored.  lrows [B] (host, with rows only) or NULL: the rows' logit bias and min_new_tokens (mgea_row_logits).  Which of the
-// five launch sequences the steps take: StepForm (common.h).
-// score (with rows only) or NULL: the scored form -- forced ids in, log-probabilities out (mgea_decoder_generate_rows_scored).
-// start_states (with rows only; host [B]) or NULL: the rows' grammar start states, -1 = none; any >= 0 makes it the GRAMMAR form
-// (mgea_decoder_generate_rows_grammar), none leaves every launch as it is without the argument.
-// guide (with rows only; host [B]) or NULL: the rows' guidance pairs (mgea_decoder_generate_rows_guided); any shadow_row >= 0 makes the
-// generation guided -- the mix launch in every step, the shadow rows' inputs overwritten with their conditional rows' --, none leaves
-// every launch as it is without the argument.
-// sched (with rows only; host [B]) or NULL, n_seg_max: the rows' prompt schedules (mgea_decoder_generate_rows_scheduled); prompt_ids_dev
-// is then [n_seg_max][B][Tp].  Any n_segments > 1 makes the generation scheduled -- the variants' prefills and gathers in front of the
-// generation's own, the apply launch in every step --, none leaves every launch as it is without the argument (variant 0 is the prompt).
-struct ScoreIo { const int32_t* forced_dev; float* logprobs_out; float* choice_out; };
-int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
-                const mgea_sampler_config* s, float penalty, const mgea_row_sampler* rows, const mgea_row_logits* lrows,
-                int32_t* ids_out_dev, hipStream_t st, const ScoreIo* score = nullptr, const int32_t* start_states = nullptr,
-                const mgea_row_guidance* guide = nullptr, const mgea_row_schedule* sched = nullptr, int32_t n_seg_max = 1) {
+// ---- generate(): plan, prefill, stage, run, finish ------------------------------------------------------------------------------
+// do_generate runs a GenRequest (gen_plan.h) in five phases, each a function of the request and its plan; the caller holds h->mu.
+GenLimits gen_limits(const mgea_decoder* h) {
     const auto& c = h->cfg;
-    MGEA_REQUIRE(c.block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "decoder_generate needs the KV-cache block mode");
-    MGEA_REQUIRE(n_steps >= 0 && Tp > 0, MGEA_EINVAL, "decoder_generate: bad n_steps / Tp");
-    RowRecords rr;   // the step graphs' form; whether to poll for early stops (some row can finish before n_steps)
-    bool grammar = false;   // some row has a start state
-    int n_pairs = 0;        // guidance pairs: conditional rows with a shadow row
-    int n_sched = 0;        // scheduled rows: more than one prompt variant
-    int reserve = Tp + n_steps;
-    // With a window set every generation is windowed: P pages per row, no budget clamp, no parking, every page id through the table.
-    const bool windowed = h->win_S > 0;
-    const int win_tokens = (h->win_S + h->win_R) * MGEA_KV_PAGE_TOKENS;
-    if (windowed) {
-        MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
-        MGEA_REQUIRE(Tp + 1 <= h->win_S * MGEA_KV_PAGE_TOKENS, MGEA_ECAPACITY,
-                     "prompt width %d + 1 exceeds the window's sink of %d pages (%d tokens)", Tp, h->win_S, h->win_S * MGEA_KV_PAGE_TOKENS);
-        MGEA_REQUIRE(n_steps <= h->win_max_steps, MGEA_ECAPACITY, "%d steps exceed the window's max_steps %d", n_steps, h->win_max_steps);
-        reserve = win_tokens;
-    }
-    if (rows) {
-        MGEA_REQUIRE(B > 0 && B <= c.max_batch, MGEA_ECAPACITY, "batch %d exceeds max_batch %d", B, c.max_batch);
-        MGEA_TRY(check_row_samplers(rows, B, c.vocab, n_steps, "decoder_generate_rows"));
-        if (lrows) MGEA_TRY(check_row_logits(lrows, B, n_steps, "decoder_generate_rows"));
-        for (int b = 0; start_states && b < B; ++b) {
-            const int32_t s0 = start_states[b];
-            if (s0 == -1) continue;
-            MGEA_REQUIRE(s0 >= 0, MGEA_EINVAL, "decoder_generate_rows_grammar: row %d: start state %d (-1 = none)", b, s0);
-            MGEA_REQUIRE(h->gram_n_state > 0, MGEA_EINVAL, "decoder_generate_rows_grammar: row %d has start state %d but no grammar is set", b, s0);
-            MGEA_REQUIRE(s0 < h->gram_n_state, MGEA_EINVAL, "decoder_generate_rows_grammar: row %d: start state %d outside [0, %d)", b, s0,
-                         h->gram_n_state);
-            grammar = true;
+    return GenLimits{c.vocab, c.max_batch, c.max_ctx, c.block_mode, h->win_S, h->win_R, h->win_max_steps, h->gram_n_state};
+}
+
+// A guidance shadow row runs on its conditional row's inputs -- same inputs, same id -- and this is the one place that hands them over.
+// `part` names what the caller has just filled for the callers' rows:
+//   PRESENCE  the seeded bitmaps: a pair's set is the conditional prompt plus the generated ids, and both tails add the same ids
+//   RECORDS   the pinned staging arrays: the sampler record -- seed, Philox stream, budget and all -- and the grammar start state
+//   BIAS      the engine's bias rows: the shadow adds its conditional row's vector (its record says bias_on as that one's does)
+//   FORCED    the engine's forced-id rows: the shadow is told the ids its conditional row is told
+enum class Mirror { PRESENCE, RECORDS, BIAS, FORCED };
+int mirror_shadow_rows(mgea_decoder* h, const GenRequest& q, const GenPlan& p, Mirror part, hipStream_t st) {
+    if (!p.kind.guided) return MGEA_OK;
+    const size_t V = (size_t)h->cfg.vocab, pw = (size_t)presence_words(h->cfg.vocab);
+    const mgea_decoder::Hist hi = h->hist(p.kind.windowed);
+    const size_t hs = (size_t)hi.stride;
+    for (int b = 0; b < q.B; ++b) {
+        const int32_t u = q.guide[b].shadow_row;
+        if (u < 0) continue;
+        switch (part) {
+        case Mirror::PRESENCE:
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->presence + (size_t)u * pw, h->presence + (size_t)b * pw, pw * sizeof(uint32_t),
+                                          hipMemcpyDeviceToDevice, st));
+            break;
+        case Mirror::RECORDS:
+            h->samp_stage[u] = h->samp_stage[b];
+            if (p.grammar) h->gram_stage[u] = q.start_states[b];
+            break;
+        case Mirror::BIAS:
+            if (h->samp_stage[b].bias_on)
+                MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)u * V, h->bias + (size_t)b * V, V * sizeof(float), hipMemcpyDeviceToDevice, st));
+            break;
+        case Mirror::FORCED:
+            MGEA_CHECK_HIP(hipMemcpyAsync(hi.forced + (size_t)u * hs, hi.forced + (size_t)b * hs, (size_t)q.n_steps * sizeof(int32_t),
+                                          hipMemcpyDeviceToDevice, st));
+            break;
         }
-        if (guide) MGEA_TRY(check_row_guidance(guide, B, &n_pairs));
-        if (sched) {   // (n_seg_max itself: checked by the entry point)
-            MGEA_TRY(check_row_schedules(sched, B, n_seg_max, start_states, h->gram_n_state, guide, &n_sched));
-            MGEA_REQUIRE(n_sched == 0 || Tp <= MGEA_KV_PAGE_TOKENS, MGEA_ECAPACITY,
-                         "decoder_generate_rows_scheduled: prompt width %d exceeds one page of %d tokens", Tp, MGEA_KV_PAGE_TOKENS);
-        }
-        // A guided pair must run the same steps: rows stopped where their pages end (launch_clamp_budgets) would get budgets of their own
-        // prompt lengths.  Under a window nothing is clamped, and each row of a pair evicts on its own schedule.
-        MGEA_REQUIRE(n_pairs == 0 || windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY,
-                     "decoder_generate_rows_guided: prompt width %d + %d steps exceed max_ctx %d (a guided generation is never capped; set a window)",
-                     Tp, n_steps, c.max_ctx);
-        // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
-        // (a window holds every row for as long as it runs: nothing to stop)
-        MGEA_REQUIRE(windowed || (Tp < c.max_ctx && n_steps <= c.max_ctx), MGEA_ECAPACITY, "prompt width %d / %d steps exceed max_ctx %d", Tp,
-                     n_steps, c.max_ctx);
-        if (!windowed) reserve = reserve < c.max_ctx ? reserve : c.max_ctx;
-        // the records go to the pinned staging buffer, free once the previous call's copy out of it has run
-        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free.ev));
-        rr = build_row_records(rows, lrows, B, n_steps, h->samp_stage);
-        // a shadow row samples with its conditional row's record -- seed, Philox stream, budget and all: same inputs, same id
-        for (int b = 0; n_pairs > 0 && b < B; ++b)
-            if (guide[b].shadow_row >= 0) h->samp_stage[guide[b].shadow_row] = h->samp_stage[b];
-        rr.may_stop_early = rr.may_stop_early || (!windowed && reserve < Tp + n_steps);
-    } else {
-        MGEA_REQUIRE(windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY, "prompt %d + %d steps exceeds max_ctx %d", Tp, n_steps, c.max_ctx);
-        MGEA_REQUIRE(s->temperature > 0.f, MGEA_EINVAL, "temperature must be > 0");
-        rr = RowRecords{step_form(s->top_k == 1, penalty != 1.0f, false), penalty != 1.0f, s->eos_id >= 0};
     }
-    const bool scored = score != nullptr;
-    const bool guided = n_pairs > 0;
-    const bool scheduled = n_sched > 0;
-    // scoring and guidance need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
-    // the lowest id)
-    const bool biased = rr.form == StepForm::BIASED;
-    const StepForm form = grammar ? StepForm::GRAMMAR : (scored || guided) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
-    h->last_penalized = false;
-    h->gram_steps = 0;
-    h->guide_pairs = h->guide_steps = 0;
-    h->sched_steps = 0;
-    h->last_scheduled = false;
-    h->n.scored_steps = h->n.penalized_steps = h->n.biased_steps = 0;
+    return MGEA_OK;
+}
+
+// Prefill: for a scheduled call the variants' prefills and gathers, then the generation's own reset and prefill (logits dropped,
+// api_cache.py:163) and the presence seed.  Leaves the cache, cur_ids and the host mirror as the first step reads them.
+int gen_prefill(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_t st) {
+    const auto& c = h->cfg;
+    const int B = q.B, Tp = q.Tp;
+    const bool windowed = p.kind.windowed;
     // positions [0, lens) of the prefill that has just finished -> segment sg of the conditioning store (the pool as the attention sees
     // it: the allocation rule where the prefill's pages follow it, the table otherwise)
     auto gather = [&](int sg) {
         KvPool pool = h->kv;
         if (!tune(TUNE_ATTN_ARITH_PAGES)) pool.arith_batch = 0;
-        return launch_cond_gather(pool, c.n_layer, h->page_table, h->max_pages, lens_dev, Tp, h->cond_store, sg, n_seg_max, Tp, h->cond_meta,
+        return launch_cond_gather(pool, c.n_layer, h->page_table, h->max_pages, q.lens, Tp, h->cond_store, sg, q.n_seg_max, Tp, h->cond_meta,
                                   h->cond_len, B, st);
     };
-    if (scheduled) {
+    if (p.kind.scheduled) {
         // The variants behind the first, last to first: each a reset and a prefill of the B prompts with the call's own B, Tp and lens --
         // the kernels the generation's own prefill takes, so the gathered K | V are bit for bit what a generation from that variant caches.
-        MGEA_TRY(ensure_cond(h, cond_store_bytes(h->kv, c.n_layer, n_seg_max, B, Tp), st));
-        for (int sg = n_seg_max - 1; sg >= 1; --sg) {
-            MGEA_TRY(do_reset(h, B, reserve, st));
+        MGEA_TRY(ensure_cond(h, cond_store_bytes(h->kv, c.n_layer, q.n_seg_max, B, Tp), st));
+        for (int sg = q.n_seg_max - 1; sg >= 1; --sg) {
+            MGEA_TRY(do_reset(h, B, p.reserve, st));
             if (windowed) h->kv.arith_batch = 0;
-            MGEA_TRY(do_forward(h, prompt_ids_dev + (size_t)sg * B * Tp, lens_dev, B, Tp, nullptr, st));
+            MGEA_TRY(do_forward(h, q.prompt_ids + (size_t)sg * B * Tp, q.lens, B, Tp, nullptr, st));
             MGEA_TRY(gather(sg));
         }
     }
-    MGEA_TRY(do_reset(h, B, reserve, st));
+    MGEA_TRY(do_reset(h, B, p.reserve, st));
     if (windowed) {   // the rotation breaks the allocation rule: every page id of the call comes from the table, the prefill's included
         h->kv.arith_batch = 0;
         MGEA_CHECK_HIP(hipMemsetAsync(h->win_evict, 0, (size_t)c.max_batch * sizeof(int32_t), st));
     }
-    MGEA_TRY(do_forward(h, prompt_ids_dev, lens_dev, B, Tp, nullptr, st));  // prefill, logits dropped (api_cache.py:163)
-    if (scheduled) {   // the generation's own prefill is segment 0; every row starts there
+    MGEA_TRY(do_forward(h, q.prompt_ids, q.lens, B, Tp, nullptr, st));
+    if (p.kind.scheduled) {   // the generation's own prefill is segment 0; every row starts there
         MGEA_TRY(gather(0));
         MGEA_CHECK_HIP(hipMemsetAsync(h->cond_cur_seg, 0, (size_t)c.max_batch * sizeof(int32_t), st));
         MGEA_CHECK_HIP(hipMemsetAsync(h->cond_switches, 0, 16, st));
-        h->last_scheduled = true;
     }
     h->win_dirty = windowed;
-    const bool capped = !windowed && reserve < Tp + n_steps;   // rows stop where their pages end (launch_clamp_budgets, parking)
-    const mgea_decoder::Hist hi = h->hist(windowed);
-    if (form_has_presence(form)) {   // every row's set starts as its real prompt tokens
-        MGEA_TRY(launch_presence_seed(prompt_ids_dev, lens_dev, B, Tp, c.vocab, h->presence, st));
-        // a pair's set is the conditional prompt plus the generated ids: the shadow's bitmap starts as a copy, and both tails add the same ids
-        const size_t pw = (size_t)presence_words(c.vocab);
-        for (int b = 0; guided && b < B; ++b)
-            if (guide[b].shadow_row >= 0)
-                MGEA_CHECK_HIP(hipMemcpyAsync(h->presence + (size_t)guide[b].shadow_row * pw, h->presence + (size_t)b * pw, pw * sizeof(uint32_t),
-                                              hipMemcpyDeviceToDevice, st));
-        h->last_penalized = true;
+    if (form_has_presence(p.kind.form)) {   // every row's set starts as its real prompt tokens
+        MGEA_TRY(launch_presence_seed(q.prompt_ids, q.lens, B, Tp, c.vocab, h->presence, st));
+        MGEA_TRY(mirror_shadow_rows(h, q, p, Mirror::PRESENCE, st));
     }
-    if (n_steps == 0) return MGEA_OK;
+    return MGEA_OK;
+}
 
-    // the rows' sampler records -> device memory (stream-ordered, no host sync), then the cached step graph of this batch size:
-    // all per-step state lives in device memory, so one graph serves every step of every request
-    if (rows) {
-        for (int b = 0; biased && b < B; ++b)
-            if (lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
-                MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)b * c.vocab, lrows[b].bias_dev, (size_t)c.vocab * sizeof(float),
+// Stage: everything the steps read besides the cache goes into engine memory, stream-ordered and without a host sync -- the rows'
+// records, bias vectors, grammar states, pairs, schedules and forced ids.  The captured graphs point at the engine's buffers, so one
+// graph serves every step of every request.
+int gen_stage(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_t st) {
+    const auto& c = h->cfg;
+    const int B = q.B;
+    if (q.rows) {
+        // the pinned staging arrays are free once the previous call's copies out of them have run
+        MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free.ev));
+        build_row_records(q.rows, q.lrows, B, q.n_steps, h->samp_stage);
+        for (int b = 0; p.grammar && b < B; ++b) h->gram_stage[b] = q.start_states[b];
+        MGEA_TRY(mirror_shadow_rows(h, q, p, Mirror::RECORDS, st));
+        for (int b = 0; p.biased && b < B; ++b)
+            if (q.lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
+                MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)b * c.vocab, q.lrows[b].bias_dev, (size_t)c.vocab * sizeof(float),
                                               hipMemcpyDeviceToDevice, st));
-        for (int b = 0; guided && biased && b < B; ++b)   // a shadow row adds its conditional row's vector (its record says bias_on as that one's does)
-            if (guide[b].shadow_row >= 0 && h->samp_stage[b].bias_on)
-                MGEA_CHECK_HIP(hipMemcpyAsync(h->bias + (size_t)guide[b].shadow_row * c.vocab, h->bias + (size_t)b * c.vocab,
-                                              (size_t)c.vocab * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (p.biased) MGEA_TRY(mirror_shadow_rows(h, q, p, Mirror::BIAS, st));
         MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
-        if (grammar) {   // the rows' states, through the pinned staging array (free under the same event as the records')
-            for (int b = 0; b < B; ++b) h->gram_stage[b] = start_states[b];
-            for (int b = 0; guided && b < B; ++b)   // a shadow row starts in its conditional row's state
-                if (guide[b].shadow_row >= 0) h->gram_stage[guide[b].shadow_row] = start_states[b];
+        if (p.grammar)
             MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        }
-        if (guided) {   // the pairs and their scales, through the pinned staging array: the guided graphs read the engine's two vectors
+        if (p.kind.guided) {   // the pairs and their scales: the guided graphs read the engine's two vectors
             float* scale_stage = reinterpret_cast<float*>(h->guide_stage + c.max_batch);
             for (int b = 0; b < B; ++b) {
-                h->guide_stage[b] = guide[b].shadow_row;
-                scale_stage[b] = guide[b].shadow_row >= 0 ? guide[b].scale : 0.f;
+                h->guide_stage[b] = q.guide[b].shadow_row;
+                scale_stage[b] = q.guide[b].shadow_row >= 0 ? q.guide[b].scale : 0.f;
             }
             MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_partner, h->guide_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
             MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_scale, scale_stage, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
         }
-        if (scheduled) {   // the rows' schedules, through the pinned staging array (free under the same event as the records')
-            for (int b = 0; b < B; ++b) h->cond_stage[b] = sched[b];
+        if (p.kind.scheduled) {
+            for (int b = 0; b < B; ++b) h->cond_stage[b] = q.sched[b];
             MGEA_CHECK_HIP(hipMemcpyAsync(h->cond_sched, h->cond_stage, (size_t)B * sizeof(mgea_row_schedule), hipMemcpyHostToDevice, st));
         }
         MGEA_CHECK_HIP(hipEventRecord(h->stage_free.ev, st));
-        if (capped) MGEA_TRY(launch_clamp_budgets(h->samp_dev, lens_dev, Tp, B, reserve, st));
+        if (p.capped) MGEA_TRY(launch_clamp_budgets(h->samp_dev, q.lens, q.Tp, B, p.reserve, st));
     } else {
-        MGEA_TRY(launch_fill_sampler_params(h->samp_dev, sampler_params(*s, penalty), B, st));
+        MGEA_TRY(launch_fill_sampler_params(h->samp_dev, sampler_params(*q.sampler, q.penalty), B, st));
     }
-    if (scored) {   // the engine's forced-id rows: -1 everywhere, then the caller's [B, n_steps] matrix (steps beyond it stay free)
+    if (p.kind.scored) {   // the engine's forced-id rows: -1 everywhere, then the caller's [B, n_steps] matrix (steps beyond it stay free)
+        const mgea_decoder::Hist hi = h->hist(p.kind.windowed);
         const size_t hs = (size_t)hi.stride;
         MGEA_CHECK_HIP(hipMemsetAsync(hi.forced, 0xff, (size_t)B * hs * sizeof(int32_t), st));
-        if (score->forced_dev)
-            MGEA_CHECK_HIP(hipMemcpy2DAsync(hi.forced, hs * sizeof(int32_t), score->forced_dev, (size_t)n_steps * sizeof(int32_t),
-                                            (size_t)n_steps * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
-        for (int b = 0; guided && b < B; ++b)   // a shadow row is told the ids its conditional row is told
-            if (guide[b].shadow_row >= 0)
-                MGEA_CHECK_HIP(hipMemcpyAsync(hi.forced + (size_t)guide[b].shadow_row * hs, hi.forced + (size_t)b * hs,
-                                              (size_t)n_steps * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (q.forced)
+            MGEA_CHECK_HIP(hipMemcpy2DAsync(hi.forced, hs * sizeof(int32_t), q.forced, (size_t)q.n_steps * sizeof(int32_t),
+                                            (size_t)q.n_steps * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
+        MGEA_TRY(mirror_shadow_rows(h, q, p, Mirror::FORCED, st));
     }
+    return MGEA_OK;
+}
+
+// Run: the qkv0 table and the step graphs of this batch size and kind, the first step's embedding, then the launches -- with a poll
+// every 16 steps where some row can finish early.  *launched = the steps that ran.
+int gen_run(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_t st, int* launched_out) {
+    const int B = q.B, n_steps = q.n_steps;
     if (const int path = qkv0_path(h, B); path >= 0) MGEA_TRY(ensure_qkv0(h, path, st));   // before any capture of this batch size
     hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
-    if (!h->no_graph) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec, 1, windowed, guided, scheduled));
+    if (!h->no_graph) MGEA_TRY(step_graph(h, B, p.kind, 1, st, &gexec));
     // several steps per graph launch (switch decoder_graph_steps, a divisor of 16 so that the EOS poll below keeps its rhythm)
     int K = h->no_graph || h->prof_stride > 0 ? 1 : tune(TUNE_DECODER_GRAPH_STEPS);
     if (K != 2 && K != 4 && K != 8 && K != 16) K = 1;
-    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, form, scored, st, &gexec_k, K, windowed, guided, scheduled));
+    if (K > 1 && n_steps >= K) MGEA_TRY(step_graph(h, B, p.kind, K, st, &gexec_k));
     MGEA_TRY(prime_gen(h, B, st));   // x <- embedding of the re-fed last prompt token (api_cache.py:167)
     int launched = 0;
     int32_t host_done = 0;
@@ -1435,12 +1334,12 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
         const int i = launched;
         if (h->prof_stride > 0 && (i % h->prof_stride) == h->prof_stride / 2) {
             h->prof_now = true;  // this step runs eagerly with HIP events around every launch
-            const int rc = enqueue_gen_step(h, B, form, scored, st, windowed, guided, scheduled);
+            const int rc = enqueue_gen_step(h, B, p.kind, st);
             h->prof_now = false;
             MGEA_TRY(rc);
             ++launched;
         } else if (h->no_graph) {
-            MGEA_TRY(enqueue_gen_step(h, B, form, scored, st, windowed, guided, scheduled));
+            MGEA_TRY(enqueue_gen_step(h, B, p.kind, st));
             ++launched;
         } else if (gexec_k && i % K == 0 && i + K <= n_steps) {
             MGEA_CHECK_HIP(hipGraphLaunch(gexec_k, st));
@@ -1449,24 +1348,24 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
             MGEA_CHECK_HIP(hipGraphLaunch(gexec, st));
             ++launched;
         }
-        if (rr.may_stop_early && (launched % 16) == 0) {  // stop once every row has drawn EOS (api_cache.py:181) or spent its budget
+        if (p.may_stop_early && (launched % 16) == 0) {  // stop once every row has drawn EOS (api_cache.py:181) or spent its budget
             MGEA_CHECK_HIP(hipMemcpyAsync(&host_done, h->n_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             MGEA_CHECK_HIP(hipStreamSynchronize(st));
             if (host_done >= B) break;
         }
     }
-    if (capped) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
+    if (p.capped) MGEA_TRY(launch_unpark_rows(h->done, h->ctx_len, B, st));
     h->host_max_len += launched;
-    h->n.graph_replays = launched;
-    h->n.penalized_steps = rr.any_penalty ? launched : 0;
-    h->n.biased_steps = biased ? launched : 0;
-    h->n.scored_steps = scored ? launched : 0;
-    h->gram_steps = grammar ? launched : 0;
-    h->guide_pairs = n_pairs;
-    h->guide_steps = guided ? launched : 0;
-    h->sched_steps = scheduled ? launched : 0;
-    if (scored) {   // as the ids below: the steps that ran from the histories, 0 for the steps that never did
-        float* outs[2] = {score->logprobs_out, score->choice_out};
+    *launched_out = launched;
+    return MGEA_OK;
+}
+
+// Finish: the steps that ran, from the histories into the caller's matrices; steps that never ran are 0 (log-probabilities) and -1 (ids)
+int gen_finish(mgea_decoder* h, const GenRequest& q, const GenPlan& p, int launched, hipStream_t st) {
+    const int B = q.B, n_steps = q.n_steps;
+    const mgea_decoder::Hist hi = h->hist(p.kind.windowed);
+    if (p.kind.scored) {
+        float* outs[2] = {q.logprobs_out, q.choice_out};
         const float* hist[2] = {hi.lp, hi.ch};
         for (int i = 0; i < 2; ++i) {
             if (!outs[i]) continue;
@@ -1475,12 +1374,74 @@ int do_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* l
                                             (size_t)launched * sizeof(float), B, hipMemcpyDeviceToDevice, st));
         }
     }
-    // rows: ids_hist[b, 0:launched]; steps never run are -1
-    MGEA_CHECK_HIP(hipMemsetAsync(ids_out_dev, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));
-    MGEA_CHECK_HIP(hipMemcpy2DAsync(ids_out_dev, (size_t)n_steps * sizeof(int32_t), hi.ids,
-                                    (size_t)hi.stride * sizeof(int32_t), (size_t)launched * sizeof(int32_t), B,
-                                    hipMemcpyDeviceToDevice, st));
+    MGEA_CHECK_HIP(hipMemsetAsync(q.ids_out, 0xff, (size_t)B * n_steps * sizeof(int32_t), st));
+    MGEA_CHECK_HIP(hipMemcpy2DAsync(q.ids_out, (size_t)n_steps * sizeof(int32_t), hi.ids, (size_t)hi.stride * sizeof(int32_t),
+                                    (size_t)launched * sizeof(int32_t), B, hipMemcpyDeviceToDevice, st));
     return MGEA_OK;
+}
+
+int do_generate(mgea_decoder* h, const GenRequest& q, hipStream_t st) {
+    GenPlan p;
+    MGEA_TRY(plan_generation(q, gen_limits(h), &p));
+    mgea_decoder::LastGen last;
+    h->last = last;   // a call that fails from here on reports nothing
+    MGEA_TRY(gen_prefill(h, q, p, st));
+    last.penalized = form_has_presence(p.kind.form);
+    last.scheduled = p.kind.scheduled;
+    h->last = last;
+    if (q.n_steps == 0) return MGEA_OK;
+    MGEA_TRY(gen_stage(h, q, p, st));
+    int launched = 0;
+    MGEA_TRY(gen_run(h, q, p, st, &launched));
+    last.graph_replays = launched;
+    last.penalized_steps = p.any_penalty ? launched : 0;
+    last.biased_steps = p.biased ? launched : 0;
+    last.scored_steps = p.kind.scored ? launched : 0;
+    last.gram_steps = p.grammar ? launched : 0;
+    last.guide_pairs = p.n_pairs;
+    last.guide_steps = p.kind.guided ? launched : 0;
+    last.sched_steps = p.kind.scheduled ? launched : 0;
+    h->last = last;
+    return gen_finish(h, q, p, launched, st);
+}
+
+// mgea_decoder_generate and _penalized: the uniform form
+int generate_uniform(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
+                     const mgea_sampler_config* s, float penalty, int32_t* ids_out_dev, void* stream) {
+    MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
+    MGEA_REQUIRE(std::isfinite(penalty) && penalty > 0.f, MGEA_EINVAL, "decoder_generate: repetition_penalty must be finite and > 0 (got %g)",
+                 (double)penalty);
+    GenRequest q;
+    q.prompt_ids = prompt_ids_dev; q.lens = lens_dev; q.B = B; q.Tp = Tp; q.n_steps = n_steps;
+    q.sampler = s; q.penalty = penalty; q.ids_out = ids_out_dev;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return do_generate(h, q, (hipStream_t)stream);
+}
+
+// The six mgea_decoder_generate_rows* entry points: what all of them take, then their one prologue.  What the records alone decide
+// is checked before the handle is looked at (plan_generation checks it again, with the sampler records).
+GenRequest rows_request(const char* who, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
+                        const mgea_row_sampler* rows, const mgea_row_logits* lrows, int32_t* ids_out_dev) {
+    GenRequest q;
+    q.who = who;
+    q.prompt_ids = prompt_ids_dev; q.lens = lens_dev; q.B = B; q.Tp = Tp; q.n_steps = n_steps;
+    q.rows = rows; q.lrows = lrows; q.ids_out = ids_out_dev;
+    return q;
+}
+int generate_rows(mgea_decoder* h, const GenRequest& q, void* stream, bool needs_logprobs = false) {
+    MGEA_REQUIRE(q.rows && q.prompt_ids && q.ids_out && (q.logprobs_out || !needs_logprobs), MGEA_EINVAL, "%s: NULL argument", q.who);
+    if (q.lrows) {
+        MGEA_REQUIRE(q.B > 0, MGEA_EINVAL, "%s: empty batch", q.who);
+        MGEA_TRY(check_row_logits(q.lrows, q.B, q.n_steps, q.who));
+    }
+    MGEA_REQUIRE(h, MGEA_EINVAL, "%s: NULL argument", q.who);
+    MGEA_REQUIRE(q.logprobs_out || (!q.forced && !q.choice_out), MGEA_EINVAL,
+                 "%s: forced ids and choice log-probabilities need logprobs_out_dev", q.who);
+    MGEA_REQUIRE(q.n_seg_max >= 1 && q.n_seg_max <= MGEA_SCHEDULE_MAX_SEGMENTS, MGEA_EINVAL, "%s: n_seg_max %d outside [1, %d]", q.who,
+                 q.n_seg_max, MGEA_SCHEDULE_MAX_SEGMENTS);
+    MGEA_REQUIRE(q.sched || q.n_seg_max == 1, MGEA_EINVAL, "%s: %d prompt variants but no schedules", q.who, q.n_seg_max);
+    std::lock_guard<std::mutex> lk(h->mu);
+    return do_generate(h, q, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -1489,55 +1450,64 @@ extern "C" {
 int mgea_decoder_generate(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
                           int32_t Tp, int32_t n_steps, const mgea_sampler_config* s, int32_t* ids_out_dev,
                           void* stream) {
-    MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
-    std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, nullptr, nullptr, ids_out_dev, (hipStream_t)stream);
+    return generate_uniform(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, 1.0f, ids_out_dev, stream);
 }
 
 int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B,
                                     int32_t Tp, int32_t n_steps, const mgea_sampler_config* s, float repetition_penalty,
                                     int32_t* ids_out_dev, void* stream) {
-    MGEA_REQUIRE(h && s && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate: NULL argument");
-    MGEA_REQUIRE(std::isfinite(repetition_penalty) && repetition_penalty > 0.f, MGEA_EINVAL,
-                 "decoder_generate: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
-    std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, nullptr, nullptr, ids_out_dev,
-                       (hipStream_t)stream);
+    return generate_uniform(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, s, repetition_penalty, ids_out_dev, stream);
 }
 
 int mgea_decoder_generate_rows(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
                                int32_t n_steps, const mgea_row_sampler* rows, int32_t* ids_out_dev, void* stream) {
-    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
-    std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, nullptr, ids_out_dev, (hipStream_t)stream);
+    return generate_rows(h, rows_request("decoder_generate_rows", prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, nullptr, ids_out_dev), stream);
 }
 
 int mgea_decoder_generate_rows_biased(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
                                       int32_t* ids_out_dev, void* stream) {
-    MGEA_REQUIRE(rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
-    // what the records alone decide is checked before anything else is looked at (do_generate checks it again with the sampler records)
-    if (logits_rows) {
-        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows: empty batch");
-        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows"));
-    }
-    MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_generate_rows: NULL argument");
-    std::lock_guard<std::mutex> lk(h->mu);
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream);
+    return generate_rows(h, rows_request("decoder_generate_rows", prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev), stream);
 }
 
 int mgea_decoder_generate_rows_scored(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
                                       const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
                                       float* choice_logprobs_out_dev, void* stream) {
-    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev && logprobs_out_dev, MGEA_EINVAL, "decoder_generate_rows_scored: NULL argument");
-    if (logits_rows) {
-        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_scored: empty batch");
-        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_scored"));
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream, &io);
+    GenRequest q = rows_request("decoder_generate_rows_scored", prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev);
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream, true);
+}
+
+int mgea_decoder_generate_rows_grammar(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                       const int32_t* start_states, const int32_t* forced_ids_dev, int32_t* ids_out_dev,
+                                       float* logprobs_out_dev, float* choice_logprobs_out_dev, void* stream) {
+    GenRequest q = rows_request("decoder_generate_rows_grammar", prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev);
+    q.start_states = start_states;
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_generate_rows_guided(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                      const int32_t* start_states, const mgea_row_guidance* guide, const int32_t* forced_ids_dev,
+                                      int32_t* ids_out_dev, float* logprobs_out_dev, float* choice_logprobs_out_dev, void* stream) {
+    GenRequest q = rows_request("decoder_generate_rows_guided", prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev);
+    q.start_states = start_states; q.guide = guide;
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_generate_rows_scheduled(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                         int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                         const int32_t* start_states, const mgea_row_guidance* guide, const mgea_row_schedule* sched,
+                                         int32_t n_seg_max, const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
+                                         float* choice_logprobs_out_dev, void* stream) {
+    GenRequest q = rows_request("decoder_generate_rows_scheduled", prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev);
+    q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max;
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream);
 }
 
 int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, const int32_t* next_host, int32_t n_state, int32_t n_class,
@@ -1547,7 +1517,7 @@ int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, cons
     hipStream_t st = (hipStream_t)stream;
     if (n_state == 0) {   // clear
         MGEA_CHECK_HIP(hipStreamSynchronize(st));
-        h->graphs.drop_form(StepForm::GRAMMAR);
+        h->graphs.drop_if([](const StepGraphs::Key& k) { return k.kind.form == StepForm::GRAMMAR; });
         h->gram_n_state = h->gram_n_class = 0;
         return MGEA_OK;
     }
@@ -1576,7 +1546,7 @@ int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, cons
     }
     if (n_state != h->gram_n_state || n_class != h->gram_n_class) {
         MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying
-        h->graphs.drop_form(StepForm::GRAMMAR);   // their kernel arguments carry the table's shape
+        h->graphs.drop_if([](const StepGraphs::Key& k) { return k.kind.form == StepForm::GRAMMAR; });   // their kernel arguments carry the table's shape
     }
     MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_class, class_of_host, (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, st));
     MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_next, next_host, (size_t)n_state * n_class * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -1588,78 +1558,23 @@ int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, cons
     return MGEA_OK;
 }
 
-int mgea_decoder_generate_rows_grammar(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
-                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
-                                       const int32_t* start_states, const int32_t* forced_ids_dev, int32_t* ids_out_dev,
-                                       float* logprobs_out_dev, float* choice_logprobs_out_dev, void* stream) {
-    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows_grammar: NULL argument");
-    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
-                 "decoder_generate_rows_grammar: forced ids and choice log-probabilities need logprobs_out_dev");
-    if (logits_rows) {
-        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_grammar: empty batch");
-        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_grammar"));
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
-                       logprobs_out_dev ? &io : nullptr, start_states);
-}
-
-int mgea_decoder_generate_rows_guided(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
-                                      int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
-                                      const int32_t* start_states, const mgea_row_guidance* guide, const int32_t* forced_ids_dev,
-                                      int32_t* ids_out_dev, float* logprobs_out_dev, float* choice_logprobs_out_dev, void* stream) {
-    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows_guided: NULL argument");
-    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
-                 "decoder_generate_rows_guided: forced ids and choice log-probabilities need logprobs_out_dev");
-    if (logits_rows) {
-        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_guided: empty batch");
-        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_guided"));
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
-                       logprobs_out_dev ? &io : nullptr, start_states, guide);
-}
-
-int mgea_decoder_generate_rows_scheduled(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
-                                         int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
-                                         const int32_t* start_states, const mgea_row_guidance* guide, const mgea_row_schedule* sched,
-                                         int32_t n_seg_max, const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
-                                         float* choice_logprobs_out_dev, void* stream) {
-    MGEA_REQUIRE(h && rows && prompt_ids_dev && ids_out_dev, MGEA_EINVAL, "decoder_generate_rows_scheduled: NULL argument");
-    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
-                 "decoder_generate_rows_scheduled: forced ids and choice log-probabilities need logprobs_out_dev");
-    MGEA_REQUIRE(n_seg_max >= 1 && n_seg_max <= MGEA_SCHEDULE_MAX_SEGMENTS, MGEA_EINVAL, "decoder_generate_rows_scheduled: n_seg_max %d outside [1, %d]",
-                 n_seg_max, MGEA_SCHEDULE_MAX_SEGMENTS);
-    MGEA_REQUIRE(sched || n_seg_max == 1, MGEA_EINVAL, "decoder_generate_rows_scheduled: %d prompt variants but no schedules", n_seg_max);
-    if (logits_rows) {
-        MGEA_REQUIRE(B > 0, MGEA_EINVAL, "decoder_generate_rows_scheduled: empty batch");
-        MGEA_TRY(check_row_logits(logits_rows, B, n_steps, "decoder_generate_rows_scheduled"));
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    const ScoreIo io{forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev};
-    return do_generate(h, prompt_ids_dev, lens_dev, B, Tp, n_steps, nullptr, 1.0f, rows, logits_rows, ids_out_dev, (hipStream_t)stream,
-                       logprobs_out_dev ? &io : nullptr, start_states, guide, sched, n_seg_max);
-}
-
 int mgea_decoder_schedule_info(mgea_decoder* h, int64_t* out, void* stream) {
     MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_schedule_info: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     out[0] = out[1] = 0;
-    if (!h->last_scheduled) return MGEA_OK;
+    if (!h->last.scheduled) return MGEA_OK;
     hipStream_t st = (hipStream_t)stream;
     int32_t n = 0;
     MGEA_CHECK_HIP(hipMemcpyAsync(&n, h->cond_switches, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     MGEA_CHECK_HIP(hipStreamSynchronize(st));
-    out[0] = h->sched_steps; out[1] = n;
+    out[0] = h->last.sched_steps; out[1] = n;
     return MGEA_OK;
 }
 
 int mgea_decoder_segments(mgea_decoder* h, int32_t* out_dev, void* stream) {
     MGEA_REQUIRE(h && out_dev, MGEA_EINVAL, "decoder_segments: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    MGEA_REQUIRE(h->last_scheduled && h->cur_batch > 0, MGEA_EINVAL, "decoder_segments: the last generate() was not scheduled");
+    MGEA_REQUIRE(h->last.scheduled && h->cur_batch > 0, MGEA_EINVAL, "decoder_segments: the last generate() was not scheduled");
     MGEA_CHECK_HIP(hipMemcpyAsync(out_dev, h->cond_cur_seg, (size_t)h->cur_batch * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MGEA_OK;
 }
@@ -1667,7 +1582,7 @@ int mgea_decoder_segments(mgea_decoder* h, int32_t* out_dev, void* stream) {
 int mgea_decoder_guidance_info(mgea_decoder* h, int64_t* out) {
     MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_guidance_info: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    out[0] = h->guide_pairs; out[1] = h->guide_steps;
+    out[0] = h->last.guide_pairs; out[1] = h->last.guide_steps;
     return MGEA_OK;
 }
 
@@ -1677,7 +1592,7 @@ int mgea_decoder_set_window(mgea_decoder* h, int32_t sink_pages, int32_t ring_pa
     hipStream_t st = (hipStream_t)stream;
     const auto& c = h->cfg;
     auto clear = [&]() {
-        h->graphs.drop_windowed();
+        h->graphs.drop_if([](const StepGraphs::Key& k) { return k.kind.windowed; });
         h->dev_win.release();
         h->whist = mgea_decoder::Hist{nullptr, nullptr, nullptr, nullptr, 0};
         h->win_S = h->win_R = h->win_max_steps = 0;
@@ -1743,14 +1658,14 @@ int mgea_decoder_grammar_states(mgea_decoder* h, int32_t* out_dev, void* stream)
 int mgea_decoder_grammar_info(mgea_decoder* h, int64_t* out) {
     MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_grammar_info: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    out[0] = h->gram_n_state; out[1] = h->gram_n_class; out[2] = h->gram_uploads; out[3] = h->gram_steps;
+    out[0] = h->gram_n_state; out[1] = h->gram_n_class; out[2] = h->gram_uploads; out[3] = h->last.gram_steps;
     return MGEA_OK;
 }
 
 int mgea_decoder_presence(mgea_decoder* h, uint32_t* bits_out_dev, void* stream) {
     MGEA_REQUIRE(h && bits_out_dev, MGEA_EINVAL, "decoder_presence: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    MGEA_REQUIRE(h->last_penalized && h->cur_batch > 0, MGEA_EINVAL, "decoder_presence: the last generate() applied no penalty");
+    MGEA_REQUIRE(h->last.penalized && h->cur_batch > 0, MGEA_EINVAL, "decoder_presence: the last generate() applied no penalty");
     MGEA_CHECK_HIP(hipMemcpyAsync(bits_out_dev, h->presence, (size_t)h->cur_batch * presence_words(h->cfg.vocab) * sizeof(uint32_t),
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MGEA_OK;
@@ -1814,13 +1729,13 @@ int mgea_decoder_stats(mgea_decoder* h, int64_t* out) {
     std::lock_guard<std::mutex> lk(h->mu);
     // the ABI's order (include/mgea.h), written down here and nowhere else
     out[0] = h->n.graph_nodes;
-    out[1] = h->n.graph_replays;
+    out[1] = h->last.graph_replays;
     out[2] = h->graphs.inserted();        // graph_instantiates: lifetime captures + instantiations
-    out[3] = h->n.scored_steps;
+    out[3] = h->last.scored_steps;
     out[4] = (int64_t)h->graphs.size();   // graphs_cached
     out[5] = h->n.prefill16_forwards;
-    out[6] = h->n.penalized_steps;
-    out[7] = h->n.biased_steps;
+    out[6] = h->last.penalized_steps;
+    out[7] = h->last.biased_steps;
     return MGEA_OK;
 }
 

@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "gen_plan.h"   // StepKind
+
 // the three handle types, as hip_runtime_api.h declares them (so that this header compiles without it)
 typedef struct ihipEvent_t* hipEvent_t;
 typedef struct ihipGraph* hipGraph_t;
@@ -17,8 +19,6 @@ namespace mgea {
 // hipEventDestroy; hipGraphExecDestroy, then hipGraphDestroy (capi.hip)
 void event_destroy(hipEvent_t ev);
 void graph_destroy(hipGraph_t graph, hipGraphExec_t exec);
-
-enum class StepForm;   // common.h
 
 // One event, null until the caller creates it (hipEventCreate(&e.ev)), destroyed with its owner.
 struct Event {
@@ -35,15 +35,10 @@ struct StepGraphs {
     // two per (batch, form, scored): the single step and the 8-step graph -- (5 forms + 4 scored) x 2 = 18 for one batch size, two batch sizes whole
     // (the graphs of a windowed engine and of guided and scheduled generations share the cache and its LRU)
     static constexpr size_t CAP = 36;
+    // one captured launch sequence: that many steps of that StepKind (gen_plan.h) over that many rows
     struct Key {
-        int batch; StepForm form; bool scored; int steps;
-        bool windowed = false;   // the steps open with the KV window's evict launch and file into the windowed histories (decoder.hip)
-        bool guided = false;     // the steps run the guidance-mix launch between the head and the sampler (guidance.hip)
-        bool scheduled = false;  // the steps open with the launch that applies the rows' prompt schedules (recondition.hip)
-        bool operator==(const Key& o) const {
-            return batch == o.batch && form == o.form && scored == o.scored && steps == o.steps && windowed == o.windowed &&
-                   guided == o.guided && scheduled == o.scheduled;
-        }
+        int batch; int steps; StepKind kind;
+        bool operator==(const Key& o) const { return batch == o.batch && steps == o.steps && kind == o.kind; }
     };
     struct Entry { Key key; hipGraph_t graph; hipGraphExec_t exec; int64_t nodes; uint64_t last_use; };
 
@@ -79,23 +74,11 @@ struct StepGraphs {
         for (Entry& e : entries) graph_destroy(e.graph, e.exec);
         entries.clear();
     }
-    void drop_form(StepForm form) {
+    // destroys the entries whose key `pred` accepts; the others keep their stamps
+    template <class Pred>
+    void drop_if(Pred pred) {
         for (size_t i = entries.size(); i-- > 0;)
-            if (entries[i].key.form == form) {
-                graph_destroy(entries[i].graph, entries[i].exec);
-                entries.erase(entries.begin() + (long)i);
-            }
-    }
-    void drop_windowed() {
-        for (size_t i = entries.size(); i-- > 0;)
-            if (entries[i].key.windowed) {
-                graph_destroy(entries[i].graph, entries[i].exec);
-                entries.erase(entries.begin() + (long)i);
-            }
-    }
-    void drop_scheduled() {
-        for (size_t i = entries.size(); i-- > 0;)
-            if (entries[i].key.scheduled) {
+            if (pred(entries[i].key)) {
                 graph_destroy(entries[i].graph, entries[i].exec);
                 entries.erase(entries.begin() + (long)i);
             }

@@ -262,46 +262,14 @@ int launch_grammar_allow(const int32_t* next, int n_state, int n_class, uint32_t
     return MGEA_OK;
 }
 
-int check_row_logits(const mgea_row_logits* lrows, int B, int n_steps, const char* who) {
-    for (int b = 0; b < B; ++b) {
-        const mgea_row_logits& l = lrows[b];
-        MGEA_REQUIRE(l.reserved == 0, MGEA_EINVAL, "%s: row %d: mgea_row_logits.reserved must be 0", who, b);
-        MGEA_REQUIRE(l.min_new_tokens >= 0 && (n_steps < 0 || l.min_new_tokens <= n_steps), MGEA_EINVAL,
-                     "%s: row %d: min_new_tokens %d outside [0, %d]", who, b, l.min_new_tokens, n_steps < 0 ? 0x7fffffff : n_steps);
-    }
-    return MGEA_OK;
-}
-
-int check_row_samplers(const mgea_row_sampler* rows, int B, int V, int n_steps, const char* who) {
-    MGEA_REQUIRE(rows, MGEA_EINVAL, "%s: rows is NULL", who);
-    for (int b = 0; b < B; ++b) {
-        const mgea_row_sampler& r = rows[b];
-        MGEA_REQUIRE(std::isfinite(r.temperature) && r.temperature > 0.f, MGEA_EINVAL, "%s: row %d: temperature must be finite and > 0 (got %g)",
-                     who, b, (double)r.temperature);
-        MGEA_REQUIRE(r.top_k >= 0 && r.top_k <= V, MGEA_EINVAL, "%s: row %d: top_k %d outside [0, %d]", who, b, r.top_k, V);
-        MGEA_REQUIRE(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f, MGEA_EINVAL,
-                     "%s: row %d: repetition_penalty must be finite and > 0 (got %g)", who, b, (double)r.repetition_penalty);
-        MGEA_REQUIRE(n_steps < 0 || (r.max_new_tokens >= 0 && r.max_new_tokens <= n_steps), MGEA_EINVAL,
-                     "%s: row %d: max_new_tokens %d outside [0, %d]", who, b, r.max_new_tokens, n_steps);
-    }
-    return MGEA_OK;
-}
-
-// The form: greedy only if every row is, penalized if any row is (p = 1 rows are unchanged by it: x * 1, x / 1 exact), biased if any row
-// has a bias or a min_new_tokens.
 RowRecords build_row_records(const mgea_row_sampler* rows, const mgea_row_logits* lrows, int B, int n_steps, SamplerParams* out) {
-    bool all_greedy = true, pen = false, biased = false, stop = false;
     for (int b = 0; b < B; ++b) {
         out[b] = sampler_params(rows[b]);
-        all_greedy = all_greedy && rows[b].top_k == 1;
-        pen = pen || rows[b].repetition_penalty != 1.0f;
-        stop = stop || rows[b].eos_id >= 0 || (rows[b].max_new_tokens > 0 && rows[b].max_new_tokens < n_steps);
         if (!lrows) continue;
         out[b].bias_on = lrows[b].bias_dev ? 1 : 0;
         out[b].min_new = lrows[b].min_new_tokens;
-        biased = biased || lrows[b].bias_dev || lrows[b].min_new_tokens > 0;
     }
-    return RowRecords{step_form(all_greedy, pen, biased), pen, stop};
+    return row_records(rows, lrows, B, n_steps);
 }
 
 }  // namespace mgea

@@ -411,6 +411,12 @@ class ScoredGeneration:
     logprobs: torch.Tensor
     choice_logprobs: torch.Tensor
 
+    def first_rows(self, n: int, scored: bool = True):
+        """Rows [0, n) -- the callers' rows of a batch with shadow rows behind them; scored=False: their ids alone."""
+        if not scored:
+            return self.ids[:n]
+        return ScoredGeneration(self.ids[:n], self.logprobs[:n], self.choice_logprobs[:n])
+
 
 def pack_force_ids(force_ids, B: int, n_steps: int, vocab: int):
     """Forced ids as an int32 [B, n_steps] matrix, -1 = the step is free.  force_ids: None (-> None), B id lists (ragged allowed,
@@ -947,37 +953,51 @@ class DecoderEngine:
         B, Tp = ids.shape
         if len(rows) != B:
             raise ValueError(f"{B} prompts but {len(rows)} sampler rows")
+        n_steps = self._resolve_n_steps(rows, n_steps)
+        return self._run_rows(ids, lens, rows, n_steps, check_ids=check_ids, check_bias=check_bias).ids
+
+    @staticmethod
+    def _resolve_n_steps(rows, n_steps: Optional[int]) -> int:
+        """n_steps, or for None the largest max_new_tokens of the rows (every row then needs one > 0)."""
         if n_steps is None:
             budgets = [int(r.max_new_tokens) for r in rows]
             if min(budgets) <= 0:
                 raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
             n_steps = max(budgets)
-        n_steps = int(n_steps)
+        return int(n_steps)
+
+    def _run_rows(self, ids, lens, rows, n_steps: int, force_ids=None, scored: bool = False, guide=None, srecs=None,
+                  n_seg_max: int = 1, check_ids: bool = True, check_bias: bool = True) -> ScoredGeneration:
+        """What generate_rows, generate_scored, generate_guided and generate_scheduled share: ids [B, Tp] (scheduled: [n_seg_max, B,
+        Tp]) and lens from _prompt_ids, one RowSampling per row of B.  Packs the rows' records, logit records, forced ids and grammar
+        start states (their ValueErrors, in that order), uploads on the engine's stream and makes the native call -- always
+        mgea_decoder_generate_rows_scheduled, the superset, with NULL for what the caller does not use: it then runs exactly what
+        the narrower entry point would.  Returns all B rows [B, n_steps]; logprobs / choice_logprobs are None unless scored."""
+        B, Tp = ids.shape[-2:]
         recs = pack_rows(rows, self.vocab, n_steps)
+        forced = pack_force_ids(force_ids, B, n_steps, self.vocab)
         lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
         starts = self._start_states(rows)
-        checked = self._check_ids(ids)
+        checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
         with self._on_stream():
             ids = ids.to(self.device).contiguous()
             lens = None if lens is None else lens.to(self.device).contiguous()
-            out = torch.empty(B, max(n_steps, 1), dtype=torch.int32, device=self.device)
-            if starts is not None:
-                for t in keep:
-                    t.record_stream(self.stream)
-                check(self.lib.mgea_decoder_generate_rows_grammar(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, None,
-                                                                  ptr(out), None, None, self._sp()))
-            elif lrecs is None:
-                check(self.lib.mgea_decoder_generate_rows(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, ptr(out), self._sp()))
-            else:
-                for t in keep:   # uploaded on the caller's stream, read by the engine's
-                    t.record_stream(self.stream)
-                check(self.lib.mgea_decoder_generate_rows_biased(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, ptr(out),
-                                                                 self._sp()))
+            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
+            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
+                forced.record_stream(self.stream)
+            w = max(n_steps, 1)
+            out = torch.empty(B, w, dtype=torch.int32, device=self.device)
+            lp = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
+            ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
+            for t in keep:   # uploaded on the caller's stream, read by the engine's
+                t.record_stream(self.stream)
+            check(self.lib.mgea_decoder_generate_rows_scheduled(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
+                                                                srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
         self._cur_batch = B
         self._epoch += 1
         if check_ids and not checked:
             self.id_errors()
-        return out[:, :n_steps]
+        return ScoredGeneration(out[:, :n_steps], lp[:, :n_steps] if scored else None, ch[:, :n_steps] if scored else None)
 
     def generate_scored(self, prompts, rows: Sequence[RowSampling], n_steps: Optional[int] = None, force_ids=None,
                         check_ids: bool = True, check_bias: bool = True) -> ScoredGeneration:
@@ -992,40 +1012,8 @@ class DecoderEngine:
         B, Tp = ids.shape
         if len(rows) != B:
             raise ValueError(f"{B} prompts but {len(rows)} sampler rows")
-        if n_steps is None:
-            budgets = [int(r.max_new_tokens) for r in rows]
-            if min(budgets) <= 0:
-                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
-            n_steps = max(budgets)
-        n_steps = int(n_steps)
-        recs = pack_rows(rows, self.vocab, n_steps)
-        forced = pack_force_ids(force_ids, B, n_steps, self.vocab)
-        lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
-        starts = self._start_states(rows)
-        checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
-        with self._on_stream():
-            ids = ids.to(self.device).contiguous()
-            lens = None if lens is None else lens.to(self.device).contiguous()
-            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
-            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
-                forced.record_stream(self.stream)
-            n = max(n_steps, 1)
-            out = torch.empty(B, n, dtype=torch.int32, device=self.device)
-            lp = torch.zeros(B, n, dtype=torch.float32, device=self.device)
-            ch = torch.zeros(B, n, dtype=torch.float32, device=self.device)
-            for t in keep:   # uploaded on the caller's stream, read by the engine's
-                t.record_stream(self.stream)
-            if starts is not None:
-                check(self.lib.mgea_decoder_generate_rows_grammar(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts,
-                                                                  ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
-            else:
-                check(self.lib.mgea_decoder_generate_rows_scored(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, ptr(forced),
-                                                                 ptr(out), ptr(lp), ptr(ch), self._sp()))
-        self._cur_batch = B
-        self._epoch += 1
-        if check_ids and not checked:
-            self.id_errors()
-        return ScoredGeneration(out[:, :n_steps], lp[:, :n_steps], ch[:, :n_steps])
+        n_steps = self._resolve_n_steps(rows, n_steps)
+        return self._run_rows(ids, lens, rows, n_steps, force_ids, True, check_ids=check_ids, check_bias=check_bias)
 
     def generate_guided(self, prompts, negative_prompts, rows: Sequence[RowSampling], guidance_scale=1.5,
                         n_steps: Optional[int] = None, force_ids=None, scored: bool = False, check_ids: bool = True,
@@ -1053,43 +1041,13 @@ class DecoderEngine:
             return self.generate_rows(prompts, rows, n_steps, check_ids, check_bias)
         ids, lens = _prompt_ids(all_prompts)
         B, Tp = ids.shape
-        if n_steps is None:
-            budgets = [int(r.max_new_tokens) for r in rows_all]
-            if min(budgets) <= 0:
-                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
-            n_steps = max(budgets)
-        n_steps = int(n_steps)
+        n_steps = self._resolve_n_steps(rows_all, n_steps)
         if self.window is None and Tp + n_steps > self.max_ctx:
             raise ValueError(f"prompt width {Tp} + {n_steps} steps exceed max_ctx {self.max_ctx}: a guided generation is never capped "
                              "(set a window)")
-        recs = pack_rows(rows_all, self.vocab, n_steps)
-        forced = pack_force_ids(forced_in, B, n_steps, self.vocab)
-        lrecs, keep = pack_row_logits(rows_all, self.vocab, self.device, check_bias)
-        starts = self._start_states(rows_all)
         guide = (_lib.RowGuidance * B)(*[_lib.RowGuidance(shadow_row=u, scale=s) for u, s in zip(shadow, scales)])
-        checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
-        with self._on_stream():
-            ids = ids.to(self.device).contiguous()
-            lens = None if lens is None else lens.to(self.device).contiguous()
-            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
-            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
-                forced.record_stream(self.stream)
-            w = max(n_steps, 1)
-            out = torch.empty(B, w, dtype=torch.int32, device=self.device)
-            lp = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
-            ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
-            for t in keep:   # uploaded on the caller's stream, read by the engine's
-                t.record_stream(self.stream)
-            check(self.lib.mgea_decoder_generate_rows_guided(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
-                                                             ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
-        self._cur_batch = B
-        self._epoch += 1
-        if check_ids and not checked:
-            self.id_errors()
-        n = B if all_rows else n
-        if scored:
-            return ScoredGeneration(out[:n, :n_steps], lp[:n, :n_steps], ch[:n, :n_steps])
-        return out[:n, :n_steps]
+        got = self._run_rows(ids, lens, rows_all, n_steps, forced_in, scored, guide, check_ids=check_ids, check_bias=check_bias)
+        return got.first_rows(B if all_rows else n, scored)
 
     def guidance_info(self):
         """The guidance pairs and the guided decode steps of the last generation (both 0 if it was not guided)."""
@@ -1132,46 +1090,17 @@ class DecoderEngine:
         Tp = ids.shape[2]
         if Tp > KV_PAGE_TOKENS:
             raise ValueError(f"prompt width {Tp} exceeds one page of {KV_PAGE_TOKENS} tokens")
-        if n_steps is None:
-            budgets = [int(r.max_new_tokens) for r in rows_all]
-            if min(budgets) <= 0:
-                raise ValueError("n_steps=None needs max_new_tokens > 0 on every row")
-            n_steps = max(budgets)
-        n_steps = int(n_steps)
+        n_steps = self._resolve_n_steps(rows_all, n_steps)
         guided = any(u >= 0 for u in shadow)
         if self.window is not None:
             self.window.check_call(Tp, n_steps)
         elif guided and Tp + n_steps > self.max_ctx:
             raise ValueError(f"prompt width {Tp} + {n_steps} steps exceed max_ctx {self.max_ctx}: a guided generation is never capped "
                              "(set a window)")
-        recs = pack_rows(rows_all, self.vocab, n_steps)
-        forced = pack_force_ids(forced_in, B, n_steps, self.vocab)
-        lrecs, keep = pack_row_logits(rows_all, self.vocab, self.device, check_bias)
-        starts = self._start_states(rows_all)
         guide = (_lib.RowGuidance * B)(*[_lib.RowGuidance(shadow_row=u, scale=s) for u, s in zip(shadow, scales)]) if guided else None
         srecs = (_lib.RowSchedule * B)(*[s.record() for s in scheds])
-        checked = self._check_ids(ids.reshape(-1, Tp)) and (forced is None or not forced.is_cuda)
-        with self._on_stream():
-            ids = ids.to(self.device).contiguous()
-            lens = None if lens is None else lens.to(self.device).contiguous()
-            forced = None if forced is None or n_steps == 0 else forced.to(self.device).contiguous()
-            if forced is not None:   # a device matrix was packed on the caller's stream and is read by the engine's
-                forced.record_stream(self.stream)
-            w = max(n_steps, 1)
-            out = torch.empty(B, w, dtype=torch.int32, device=self.device)
-            lp = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
-            ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
-            for t in keep:   # uploaded on the caller's stream, read by the engine's
-                t.record_stream(self.stream)
-            check(self.lib.mgea_decoder_generate_rows_scheduled(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
-                                                                srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
-        self._cur_batch = B
-        self._epoch += 1
-        if check_ids and not checked:
-            self.id_errors()
-        if scored:
-            return ScoredGeneration(out[:n, :n_steps], lp[:n, :n_steps], ch[:n, :n_steps])
-        return out[:n, :n_steps]
+        got = self._run_rows(ids, lens, rows_all, n_steps, forced_in, scored, guide, srecs, n_seg_max, check_ids, check_bias)
+        return got.first_rows(n, scored)
 
     def schedule_info(self):
         """The scheduled decode steps and the switches (rows x times a row's prompt K | V was replaced) of the last generation, both 0

@@ -30,6 +30,7 @@ void event_destroy(hipEvent_t ev) {
 using mgea::Event;
 using mgea::StepForm;
 using mgea::StepGraphs;
+using mgea::StepKind;
 
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -39,7 +40,7 @@ using mgea::StepGraphs;
         }                                                               \
     } while (0)
 
-// the cache never looks inside a form: two values of the enumeration common.h defines
+// the cache never looks inside a form: two values of the enumeration gen_plan.h defines
 const StepForm FORM_A = static_cast<StepForm>(1), FORM_B = static_cast<StepForm>(4);
 
 struct Pair { hipGraph_t graph; hipGraphExec_t exec; };
@@ -57,7 +58,10 @@ hipGraph_t put(StepGraphs& c, const StepGraphs::Key& k, int64_t nodes = 31) {
     c.insert(k, p.graph, p.exec, nodes);
     return p.graph;
 }
-StepGraphs::Key key(int batch, StepForm form = FORM_A, bool scored = false, int steps = 1) { return {batch, form, scored, steps}; }
+StepGraphs::Key key(int batch, StepForm form = FORM_A, bool scored = false, int steps = 1, bool windowed = false, bool scheduled = false) {
+    return {batch, steps, StepKind{form, scored, windowed, false, scheduled}};
+}
+const auto is_form_b = [](const StepGraphs::Key& k) { return k.kind.form == FORM_B; };
 
 int main() {
     const size_t CAP = StepGraphs::CAP;
@@ -131,14 +135,14 @@ int main() {
         }
         CHECK(c.size() == CAP && c.full());
         g_destroyed.clear();
-        c.drop_form(FORM_B);
+        c.drop_if(is_form_b);
         CHECK(c.size() == 12 && g_destroyed.size() == 24 && g_live_pairs == 12 && c.inserted() == 36);
         for (hipGraph_t d : g_destroyed) {
             bool is_b = false;
             for (hipGraph_t x : gb) is_b = is_b || x == d;
             CHECK(is_b);
         }
-        c.drop_form(FORM_B);   // none left: nothing happens
+        c.drop_if(is_form_b);   // none left: nothing happens
         CHECK(c.size() == 12 && g_destroyed.size() == 24);
         g_destroyed.clear();
         for (int b = 0; b < 24; ++b) put(c, key(200 + b));   // refill: no eviction yet
@@ -147,6 +151,28 @@ int main() {
         CHECK(g_destroyed.size() == 12);
         for (size_t i = 0; i < g_destroyed.size() && i < ga.size(); ++i) CHECK(g_destroyed[i] == ga[i]);
         CHECK(c.size() == CAP && c.inserted() == 72 && g_live_pairs == (int)CAP);
+    }
+    CHECK(g_live_pairs == 0);
+
+    // windowed and scheduled entries go by their own flag alone: a key that differs in nothing else stays, and so does its stamp
+    {
+        StepGraphs c;
+        const hipGraph_t plain = put(c, key(3)), win = put(c, key(3, FORM_A, false, 1, true)), win8 = put(c, key(3, FORM_B, true, 8, true));
+        const hipGraph_t sch = put(c, key(3, FORM_A, false, 1, false, true)), both = put(c, key(3, FORM_A, false, 1, true, true));
+        CHECK(c.size() == 5 && c.find(key(3, FORM_A, false, 1, true))->graph == win && c.find(key(3))->graph == plain);
+        g_destroyed.clear();
+        c.drop_if([](const StepGraphs::Key& k) { return k.kind.windowed; });
+        CHECK(c.size() == 2 && g_destroyed.size() == 3 && g_live_pairs == 2 && c.inserted() == 5);
+        for (hipGraph_t d : g_destroyed) CHECK(d == win || d == win8 || d == both);
+        CHECK(c.find(key(3)) && c.find(key(3, FORM_A, false, 1, false, true)) && !c.find(key(3, FORM_A, false, 1, true)));
+        const hipGraph_t both2 = put(c, key(3, FORM_A, false, 1, true, true));
+        g_destroyed.clear();
+        c.drop_if([](const StepGraphs::Key& k) { return k.kind.scheduled; });
+        CHECK(c.size() == 1 && g_destroyed.size() == 2 && g_live_pairs == 1);
+        for (hipGraph_t d : g_destroyed) CHECK(d == sch || d == both2);
+        CHECK(c.find(key(3)) && c.find(key(3))->graph == plain);
+        c.drop_if([](const StepGraphs::Key& k) { return k.kind.scheduled; });   // none left: nothing happens
+        CHECK(c.size() == 1 && g_destroyed.size() == 2);
     }
     CHECK(g_live_pairs == 0);
 

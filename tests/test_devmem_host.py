@@ -2,7 +2,8 @@
 (csrc/hipres.h).  tests/native/*_test.cpp define the runtime functions an owner calls over malloc / free -- with a "fail the k-th
 call" counter for the allocations -- and are built with AddressSanitizer (leak detection included) and UBSan.  Failure paths of the
 engines' allocations cannot be reached on a GPU without exhausting it, and a graph cache is slow to fill there; this is where they
-are covered."""
+are covered.  The host plan of a generation (csrc/gen_plan.h) is built and run the same way: its refusals are plain arithmetic on
+host records, which a GPU test could only reach one refused call at a time."""
 import os
 import subprocess
 
@@ -33,3 +34,8 @@ def test_devgroup_under_asan_and_ubsan(tmp_path):
 @pytest.mark.skipif(torch.cuda.is_available(), reason="sanitizer run: CPU machines only")
 def test_stepgraphs_under_asan_and_ubsan(tmp_path):
     run_sanitized(tmp_path, "stepgraphs")   # StepGraphs and Event (csrc/hipres.h)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="sanitizer run: CPU machines only")
+def test_gen_plan_under_asan_and_ubsan(tmp_path):
+    run_sanitized(tmp_path, "gen_plan")   # plan_generation (csrc/gen_plan.h): kinds, flags, reserve and refusals of a tiny engine

@@ -1,4 +1,4 @@
-"""The four launch sequences of the decode step's tail (StepForm in csrc/common.h: greedy, sampled, penalized, biased), on the fused
+"""The four launch sequences of the decode step's tail (StepForm in csrc/gen_plan.h: greedy, sampled, penalized, biased), on the fused
 5-launch path (decoder_tiny8h, d_model 256) and the unfused one (decoder_tiny, d_model 128): captured graphs against eager launches,
 the graph cache keyed on the form alone, and the sampler's two ways of receiving its scalars (by value, device records).
 12 steps with the default 8 steps per graph: one 8-step graph launch, then the single-step graph four times."""
