@@ -388,6 +388,46 @@ int mgea_decoder_schedule_info(mgea_decoder* h, int64_t* out /* [2] */, void* st
 /* The rows' current segments cur_seg -> out_dev [B] (device int32).  MGEA_EINVAL if the last generation was not scheduled. */
 int mgea_decoder_segments(mgea_decoder* h, int32_t* out_dev, void* stream);
 
+/* Truncation rules beyond top-k and top-p (build-defined in the same sense as top-p: the reference has none; the semantics are
+ * HuggingFace's, warper by warper).  At every decode step of a row, steps 1 to 4 of mgea_row_logits run first, then / temperature,
+ * top-k and top-p exactly as without a record; the four stages below then apply IN THIS ORDER to the set K kept so far, each seeing
+ * p = the softmax over what the stages before it kept:
+ *   1. min_p          (MinPLogitsWarper)    remove i where p_i < min_p * max(p);
+ *   2. typical_p      (TypicalLogitsWarper) lp = log p, H = -sum_K p_i lp_i, d_i = |-lp_i - H| (p_i = 0 adds nothing to H and has d =
+ *                     +inf); d* = the smallest value with mass{i in K : d_i <= d*} >= typical_p, the largest d if even K weighs less;
+ *                     keep {i in K : d_i <= d*}.  The row's most likely id is NOT protected (HF's min_tokens_to_keep = 1 protects the
+ *                     most typical id there); the id at d* survives, so K never becomes empty;
+ *   3. epsilon_cutoff (EpsilonLogitsWarper) remove i where p_i < epsilon; the largest remaining logit always stays (lowest id among
+ *                     equals);
+ *   4. eta_cutoff     (EtaLogitsWarper)     eta' = min(eta, sqrt(eta) * exp(-H)), H the entropy of the current p; remove i where
+ *                     p_i < eta'; the same one-entry protection.
+ * The final softmax, the Philox draw, the scored sampler's "choice" log-probability and the tail then run over the final K.  0 switches
+ * a stage off, typical_p == 1 too.  A top_k == 1 row stays the exact argmax and ignores the record.  A banned id (-inf) has mass 0 and
+ * d = +inf and is never drawn.  H and the normalisers are fixed-order block sums and the typical-p boundary is found over the 2^-40
+ * fixed-point masses of top-p, so the same (logits, records, seed, stream, step) give the same id on every run and launch path.
+ * Ranges (host check, MGEA_EINVAL naming the row): min_p and typical_p in [0, 1], epsilon_cutoff and eta_cutoff in [0, 1), all finite. */
+typedef struct mgea_row_truncation {
+    float min_p, typical_p, epsilon_cutoff, eta_cutoff;
+} mgea_row_truncation;
+
+/* mgea_decoder_generate_rows_scheduled with one mgea_row_truncation per row, trunc [B] (host memory, read before the call returns).
+ * trunc == NULL IS mgea_decoder_generate_rows_scheduled, and a batch in which no non-greedy row has a stage switched on is what it is
+ * without the records: the same form, the same graphs, the same ids.  Otherwise the generation is truncated: its steps take the
+ * BIASED form at least (GRAMMAR if a row has a start state; presence bitmaps cover every row, a penalty of 1 changes nothing, never
+ * the greedy head) with the truncating sampler; "truncated" is part of the step-graph key, and the records live in a device array the
+ * handle owns, so a request with other values replays the cached graphs.  A guidance shadow row gets its conditional row's record. */
+int mgea_decoder_generate_rows_truncated(mgea_decoder* h, const int32_t* prompt_ids_dev /* [n_seg_max][B][Tp] */, const int32_t* lens_dev,
+                                         int32_t B, int32_t Tp, int32_t n_steps, const mgea_row_sampler* rows,
+                                         const mgea_row_logits* logits_rows /* NULL ok */,
+                                         const int32_t* start_states /* host [B], -1 = none; NULL ok */,
+                                         const mgea_row_guidance* guide /* host [B]; NULL ok */,
+                                         const mgea_row_schedule* sched /* host [B]; NULL ok */, int32_t n_seg_max,
+                                         const int32_t* forced_ids_dev /* NULL ok */, int32_t* ids_out_dev,
+                                         float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                         const mgea_row_truncation* trunc /* host [B]; NULL ok */, void* stream);
+/* out[0] the truncated decode steps and [1] the rows with a stage switched on of the last generation (both 0 if it was not truncated). */
+int mgea_decoder_truncation_info(mgea_decoder* h, int64_t* out /* [2] */);
+
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
  * generate applied no penalty (a biased generation keeps the bitmaps too). */
@@ -744,6 +784,19 @@ int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, c
                                 const mgea_row_logits* logits_rows, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
                                 int32_t n_class, const int32_t* states_in_dev, int64_t step, int32_t* ids_out_dev, float* probs_out_dev,
                                 int32_t* states_out_dev, void* stream);
+/* One sampler launch as a truncated generation's steps run it (mgea_row_truncation), on caller buffers: trunc [B] (host) or NULL.
+ * The other arguments are those of mgea_op_sample_rows_biased, _scored (forced_ids_dev, logprobs_out_dev, choice_logprobs_out_dev; a
+ * NULL logprobs_out_dev = unscored, and then the other two must be NULL) and _grammar (class_of_dev NULL = no grammar, and then the
+ * other grammar arguments are ignored), in any combination.  trunc == NULL is the op it extends: _grammar, _scored or _biased (the
+ * scored grammar launch exists here alone).  With records the launch is the truncating sampler of the form (empty presence bitmaps
+ * where presence_dev is NULL and no row is penalized); rows whose stages are all off, and top_k == 1 rows, compute what they compute
+ * without it.  Synchronises `stream`. */
+int mgea_op_sample_rows_truncated(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                                  const mgea_row_logits* logits_rows /* NULL ok */, const mgea_row_truncation* trunc /* NULL ok */,
+                                  int64_t step, int32_t* ids_out_dev, float* probs_out_dev, const int32_t* forced_ids_dev /* NULL ok */,
+                                  float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                  const int32_t* class_of_dev /* NULL = no grammar */, const int32_t* next_dev, int32_t n_state,
+                                  int32_t n_class, const int32_t* states_in_dev, int32_t* states_out_dev, void* stream);
 /* The kernel that opens a windowed decode step (mgea_decoder_set_window, the eviction rule), alone on caller buffers: page_table_dev
  * [B][max_pages], ctx_len_dev / done_dev / evictions_dev [B] int32 (device).  A row with done == 0 and ctx_len == 64 (S + R) - 1
  * rotates its entries [S, S + R) left by one, ctx_len - 64, evictions + 1; every other row is left as it is.  MGEA_EINVAL for

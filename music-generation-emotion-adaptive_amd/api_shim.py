@@ -24,13 +24,17 @@ def create_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, t
 
 
 def create_windowed_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                        window=(1, None)):
+                        window=(1, None),
+                        min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
     """create_app with a KV window (create_app keeps its parameter list; create_batched_app takes the same keyword).
     window = (sink_pages, ring_pages), ring_pages None = all the remaining pages: the model gets that window (GPTWithKV.set_window,
     max_steps = seq_len) and seq_len may exceed the engine's context -- a piece of more than max_ctx tokens, the prompt's
     conditioning tokens pinned in the sink while the oldest generated tokens leave (build-defined mechanics; the reference's loop
-    has no context limit either, api_cache.py:159-184)."""
-    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, window=window)
+    has no context limit either, api_cache.py:159-184).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, window=window,
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
 def create_constrained_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
@@ -48,15 +52,19 @@ def create_constrained_app(model, seq_len: int, temperature: float = 1.0, top_k:
 
 
 def create_grammar_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                       constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar="tracks"):
+                       constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar="tracks",
+                       min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
     """create_constrained_app under a token grammar (create_constrained_app keeps its parameter list; create_batched_app and
     create_best_of_app take the same keyword).  grammar (build-defined, the reference samples the raw vocabulary): None = none, or
     "tracks" = generate_music.grammar.track_grammar of the vocabulary -- after an instrument only a note may follow, a track's START
     times never go back, control tokens are not drawn.  Every request starts in the state its prompt leads to (OPEN: the prompt names
     the instruments); the response carries X-Grammar.  It composes with constrain="scale": the bias bans the out-of-scale notes, the
-    grammar orders the rest."""
+    grammar orders the rest.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
-                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar)
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar,
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
 def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
@@ -74,27 +82,34 @@ def create_batched_app(model, seq_len: int, temperature: float = 1.0, top_k: int
 
 
 def create_best_of_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                       best_of: int = 4, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None):
+                       best_of: int = 4, constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None,
+                       min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
     """create_constrained_app whose requests draw best_of candidates in one batch and return the most likely one
     (generate_music.generate.generate_best_of: highest mean raw log-probability per generated token).  best_of is capped by the
     model's max_batch (ValueError here beyond it).  The response adds X-Best-Of and, when anything was generated, X-Mean-Logprob.  Build-defined: the reference
-    draws one sequence per request."""
+    draws one sequence per request.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
     best_of = int(best_of)
     if best_of < 1 or best_of > int(model.max_batch):
         raise ValueError(f"best_of {best_of} outside [1, max_batch={model.max_batch}]")
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
-                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, best_of=best_of, grammar=grammar)
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, best_of=best_of, grammar=grammar,
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
 def create_guided_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
-                      constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None, guidance_scale: float = 1.5):
+                      constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None, guidance_scale: float = 1.5,
+                      min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
     """create_grammar_app under classifier-free guidance (create_grammar_app keeps its parameter list; grammar defaults to None here).
     Every request runs as a pair of rows -- its prompt, and the prompt without the emotion's [BPM] and [KEY_SIGNATURE] tokens
     (generate_music.guidance.unconditional_prompt) -- and draws each id from guidance_scale * logp(prompt) + (1 - guidance_scale) *
     logp(the other): above 1 the piece follows the emotion's tempo and key more strongly than the model alone would, 1 is the
     conditional distribution, 0 ignores the emotion tokens (generate_music.generate.sample_kvcache_guided; build-defined, the
     reference has no guidance).  guidance_scale must be finite and >= 0 and the model needs max_batch >= 2 (ValueError here).  The
-    response carries X-Guidance-Scale."""
+    response carries X-Guidance-Scale.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
     import math
     guidance_scale = float(guidance_scale)
     if not (math.isfinite(guidance_scale) and guidance_scale >= 0):
@@ -102,12 +117,14 @@ def create_guided_app(model, seq_len: int, temperature: float = 1.0, top_k: int 
     if int(model.max_batch) < 2:
         raise ValueError(f"a guided request is a pair of rows: max_batch={model.max_batch} is too small")
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
-                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale)
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale,
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
 def create_transition_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
                           constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar="tracks",
-                          guidance_scale=None):
+                          guidance_scale=None,
+                          min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
     """create_guided_app for a piece that follows the emotions of its text (create_guided_app keeps its parameter list; grammar
     defaults to "tracks" and guidance_scale to None = no guidance here).  The text goes through
     emotion_analysis.inference.analyze_emotion_transitions: one emotion, one EATS parameter set and one prompt variant per sentence
@@ -116,7 +133,9 @@ def create_transition_app(model, seq_len: int, temperature: float = 1.0, top_k: 
     a range of note START classes, so every track walks through the emotions in musical time
     (generate_music.generate.sample_kvcache_transitions; build-defined, the reference labels the sentences and stops there); with
     grammar=None the segments are ranges of steps.  constrain="scale" keeps the FIRST sentence's key.  The response carries X-Emotions
-    (the sentences' labels, comma-separated; X-Emotion is the first) and X-Segments."""
+    (the sentences' labels, comma-separated; X-Emotion is the first) and X-Segments.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
     if guidance_scale is not None:
         import math
         guidance_scale = float(guidance_scale)
@@ -126,14 +145,33 @@ def create_transition_app(model, seq_len: int, temperature: float = 1.0, top_k: 
             raise ValueError(f"a guided request is a pair of rows: max_batch={model.max_batch} is too small")
     return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
                       out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale,
-                      transitions=True)
+                      transitions=True,
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
+
+
+def create_truncated_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                         constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None,
+                         min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, batch_requests: bool = False, max_batch=None,
+                         window=None):
+    """create_grammar_app (grammar defaults to None here) with HuggingFace's further truncation rules for every request: min_p,
+    typical_p, epsilon_cutoff, eta_cutoff, None = off, applied in this order behind top-k and top-p inside the engine's sampler
+    (mgea.decoder.Truncation; a value out of range is a ValueError here).  create_app, create_constrained_app and
+    create_batched_app keep their parameter lists; every other create_*_app takes the same four keywords.  batch_requests=True
+    serves concurrent requests as batches as create_batched_app does (max_batch, window: as there), each request with its record."""
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=bool(batch_requests),
+                      max_batch=max_batch, constrain=constrain, out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens,
+                      grammar=grammar, window=window,
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
                out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None, guidance_scale=None,
-               transitions=False):
+               transitions=False, truncation=None):
+    from mgea.decoder import Truncation
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
+    trunc_kw = {k: v for k, v in (truncation or {}).items() if v is not None}   # empty: every call below is what it was
+    Truncation(**trunc_kw).check()
     if constrain not in CONSTRAINTS:
         raise ValueError(f"constrain must be one of {CONSTRAINTS}, got {constrain!r}")
     if grammar not in GRAMMARS:
@@ -219,7 +257,7 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             tokens, _, means, best = gen.generate_best_of(model, gen_prompt, best_of, max_len=seq_len, temperature=temperature,
                                                           top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                                           logit_bias=bias, min_new_tokens=int(min_new_tokens), return_all=True,
-                                                          grammar=tg)
+                                                          grammar=tg, **trunc_kw)
             extra["X-Best-Of"] = str(best_of)
             if means[best] > float("-inf"):   # (nothing generated -- seq_len within the prompt -- has no mean)
                 extra["X-Mean-Logprob"] = f"{means[best]:.6f}"
@@ -231,7 +269,8 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             tokens = gen.sample_kvcache_transitions(model, variants, [max(len(seg), 1) for seg, _ in sentences], max_len=seq_len,
                                                     temperature=temperature, top_k=top_k, device="cpu", top_p=top_p,
                                                     repetition_penalty=repetition_penalty, logit_bias=bias,
-                                                    min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale)
+                                                    min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale,
+                                                    **trunc_kw)
             extra["X-Emotions"] = ",".join(lb for _, lb in sentences)
             extra["X-Segments"] = str(len(sentences))
             if guidance_scale is not None:
@@ -239,17 +278,19 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
         elif guidance_scale is not None:   # the request and its unconditional twin as one pair of rows
             tokens = gen.sample_kvcache_guided(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu",
                                                top_p=top_p, repetition_penalty=repetition_penalty, logit_bias=bias,
-                                               min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale)
+                                               min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale,
+                                               **trunc_kw)
             extra["X-Guidance-Scale"] = f"{guidance_scale:g}"
         elif app.state.batcher is not None:   # the same request, served inside whatever batch is forming
             fut = app.state.batcher.submit(gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, top_p=top_p,
-                                           repetition_penalty=repetition_penalty, **more)
+                                           repetition_penalty=repetition_penalty, **more, **trunc_kw)
             tokens = fut.result()
             extra["X-Batch-Rows"] = str(fut.batch_rows)
         else:
-            call = gen.sample_kvcache_grammar if tg is not None else gen.sample_kvcache_biased if more else gen.sample_kvcache
+            call = gen.sample_kvcache_truncated if trunc_kw else gen.sample_kvcache_grammar if tg is not None else \
+                gen.sample_kvcache_biased if more else gen.sample_kvcache
             tokens = call(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu", top_p=top_p,
-                          repetition_penalty=repetition_penalty, **more)   # :204
+                          repetition_penalty=repetition_penalty, **more, **trunc_kw)   # :204
         if app.state.on_tokens is not None:
             app.state.on_tokens(tokens)
         midi = tokens_to_midi(tokens)                                         # :208-221 (+ pm.write)

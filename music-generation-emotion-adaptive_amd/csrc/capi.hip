@@ -117,7 +117,7 @@ static SampleCall op_sample_call(const float* logits_dev, int B, int V, int64_t 
 // mgea_op_sample_rows(_biased, _scored): the rows' records and bias vectors to device memory, one sampler launch (defined at the end)
 static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                           const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev, float* probs_out_dev, const ScoreArgs& score,
-                          void* stream, const GrammarArgs* grammar = nullptr);
+                          void* stream, const GrammarArgs* grammar = nullptr, const mgea_row_truncation* trunc = nullptr);
 
 extern "C" {
 
@@ -521,6 +521,28 @@ int mgea_op_sample_rows_grammar(const float* logits_dev, int32_t B, int32_t V, c
     return op_sample_rows(logits_dev, B, V, rows, presence_dev, lrows, step, ids_out_dev, probs_out_dev, ScoreArgs{}, stream, &g);
 }
 
+int mgea_op_sample_rows_truncated(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
+                                  const mgea_row_logits* lrows, const mgea_row_truncation* trunc, int64_t step, int32_t* ids_out_dev,
+                                  float* probs_out_dev, const int32_t* forced_ids_dev, float* logprobs_out_dev,
+                                  float* choice_logprobs_out_dev, const int32_t* class_of_dev, const int32_t* next_dev, int32_t n_state,
+                                  int32_t n_class, const int32_t* states_in_dev, int32_t* states_out_dev, void* stream) {
+    MGEA_REQUIRE(logprobs_out_dev || (!forced_ids_dev && !choice_logprobs_out_dev), MGEA_EINVAL,
+                 "op_sample_rows_truncated: forced ids and choice log-probabilities need logprobs_out_dev");
+    MGEA_REQUIRE(!logprobs_out_dev || ids_out_dev, MGEA_EINVAL, "op_sample_rows_truncated: a scored launch needs ids_out_dev");
+    const ScoreArgs score = logprobs_out_dev ? ScoreArgs{forced_ids_dev, 0, logprobs_out_dev, choice_logprobs_out_dev, 0, nullptr} : ScoreArgs{};
+    if (!class_of_dev) return op_sample_rows(logits_dev, B, V, rows, presence_dev, lrows, step, ids_out_dev, probs_out_dev, score, stream, nullptr, trunc);
+    MGEA_REQUIRE(next_dev && states_in_dev && (states_out_dev || !ids_out_dev), MGEA_EINVAL,
+                 "op_sample_rows_truncated: NULL table or state argument");
+    MGEA_REQUIRE(n_class >= 1 && n_class <= MGEA_GRAMMAR_MAX_CLASSES && n_state >= 1 && n_state <= MGEA_GRAMMAR_MAX_STATES &&
+                     (int64_t)n_state * n_class <= MGEA_GRAMMAR_MAX_CELLS,
+                 MGEA_EINVAL, "op_sample_rows_truncated: n_state %d x n_class %d exceed the caps", n_state, n_class);
+    if (states_out_dev)   // rows the sampler does not move keep their state (mgea_op_sample_rows_grammar)
+        MGEA_CHECK_HIP(hipMemcpyAsync(states_out_dev, states_in_dev, (size_t)(B > 0 ? B : 0) * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream));
+    const GrammarArgs g{class_of_dev, next_dev, nullptr, states_in_dev, states_out_dev, nullptr, n_state, n_class, 0, nullptr};
+    return op_sample_rows(logits_dev, B, V, rows, presence_dev, lrows, step, ids_out_dev, probs_out_dev, score, stream, &g, trunc);
+}
+
 // ---- the DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call (tests) ----
 int mgea_op_attention_cls(const float* q_dev, const void* qkv_dev, int32_t kv_dtype, const int32_t* mask_dev,
                           const int32_t* cu_seqlens_dev, float* out_dev, int32_t B, int32_t S, int32_t n_head, int32_t head_dim,
@@ -800,10 +822,12 @@ int mgea_op_row_budgets(const mgea_sampler_config* s, const mgea_row_sampler* ro
 
 static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                           const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev, float* probs_out_dev, const ScoreArgs& score,
-                          void* stream, const GrammarArgs* grammar) {
+                          void* stream, const GrammarArgs* grammar, const mgea_row_truncation* trunc) {
     MGEA_REQUIRE(logits_dev && rows && B > 0, MGEA_EINVAL, "op_sample_rows: NULL argument or empty batch");
     MGEA_TRY(check_row_samplers(rows, B, V, -1, "op_sample_rows"));
     if (lrows) MGEA_TRY(check_row_logits(lrows, B, -1, "op_sample_rows"));
+    int n_trunc = 0;
+    if (trunc) MGEA_TRY(check_row_truncation(trunc, rows, B, "op_sample_rows_truncated", &n_trunc));
     std::vector<SamplerParams> rec((size_t)B);
     const RowRecords rr = build_row_records(rows, lrows, B, -1, rec.data());
     const bool biased = rr.form == StepForm::BIASED;
@@ -814,7 +838,7 @@ static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const m
     DevGroup tmp;   // frees both on return: nothing is enqueued before the allocations, and the stream is synchronised after
     MGEA_REQUIRE(tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) == MGEA_OK, MGEA_EHIP,
                  "hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)) failed: %s (%s:%d)", hipGetErrorString(hipGetLastError()), __FILE__, __LINE__);
-    MGEA_REQUIRE(!(biased || grammar) || tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) == MGEA_OK, MGEA_ENOMEM,
+    MGEA_REQUIRE(!(biased || grammar || trunc) || tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) == MGEA_OK, MGEA_ENOMEM,
                  "op_sample_rows: allocation of the bias rows failed");
     // the grammar form is built on the biased one: it brings its allow bitmask, and empty bitmaps where no row is penalized
     uint32_t *allow_dev = nullptr, *pres_tmp = nullptr;
@@ -822,6 +846,14 @@ static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const m
         const size_t nw = (size_t)grammar->n_state * grammar_words(grammar->n_class), np = (size_t)B * presence_words(V);
         MGEA_REQUIRE(tmp.alloc(&allow_dev, nw * sizeof(uint32_t)) == MGEA_OK && (presence_dev || tmp.alloc(&pres_tmp, np * sizeof(uint32_t)) == MGEA_OK),
                      MGEA_ENOMEM, "op_sample_rows: allocation of the grammar's bitmask failed");
+    }
+    // so is the truncating form; its records travel like the sampler's
+    mgea_row_truncation* trunc_dev = nullptr;
+    if (trunc) {
+        const size_t np = (size_t)B * presence_words(V);
+        MGEA_REQUIRE(tmp.alloc(&trunc_dev, (size_t)B * sizeof(mgea_row_truncation)) == MGEA_OK &&
+                         (presence_dev || pres_tmp || tmp.alloc(&pres_tmp, np * sizeof(uint32_t)) == MGEA_OK),
+                     MGEA_ENOMEM, "op_sample_rows: allocation of the truncation records failed");
     }
     SampleCall c = op_sample_call(logits_dev, B, V, step, ids_out_dev, probs_out_dev);
     c.params_dev = rec_dev;   // every scalar comes from the records
@@ -835,9 +867,14 @@ static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const m
         c.grammar.allow = allow_dev;
         c.grammar.words = grammar_words(grammar->n_class);
         c.presence = presence_dev ? const_cast<uint32_t*>(presence_dev) : pres_tmp;
-        if (pres_tmp) copied = copied && hipMemsetAsync(pres_tmp, 0, (size_t)B * presence_words(V) * sizeof(uint32_t), st) == hipSuccess;
         copied = copied && launch_grammar_allow(grammar->next, grammar->n_state, grammar->n_class, allow_dev, st) == MGEA_OK;
     }
+    if (trunc) {
+        c.trunc = TruncArgs{trunc_dev};
+        c.presence = presence_dev ? const_cast<uint32_t*>(presence_dev) : pres_tmp;
+        copied = copied && hipMemcpyAsync(trunc_dev, trunc, (size_t)B * sizeof(mgea_row_truncation), hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+    if (pres_tmp) copied = copied && hipMemsetAsync(pres_tmp, 0, (size_t)B * presence_words(V) * sizeof(uint32_t), st) == hipSuccess;
     for (int b = 0; biased && copied && b < B; ++b)
         if (lrows[b].bias_dev)
             copied = hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st) ==

@@ -267,6 +267,10 @@ struct GrammarArgs {
     int32_t n_state, n_class, words;
     int32_t* err_flag;
 };
+// The rows' truncation records (mgea_row_truncation, include/mgea.h: the rule), device [B]: the truncating sampler applies min-p,
+// typical-p, the epsilon and the eta cutoff, in this order, to what top-k and top-p kept.  A row whose record switches nothing on, and
+// a top_k == 1 row, skip all of it (block-uniform) and compute what the form computes without the argument.
+struct TruncArgs { const mgea_row_truncation* rows; };
 // allow[s][w] from next [n_state][n_class] (step_tail.hip)
 int launch_grammar_allow(const int32_t* next, int n_state, int n_class, uint32_t* allow, hipStream_t st);
 // The unfused path's second half: advance_kernel files the sampler's per-step values at the row's step (0 for a finished row).
@@ -290,6 +294,8 @@ struct SampleCall {
     ScoreArgs score;
     // GRAMMAR form (grammar.class_of != NULL; needs records, presence and bias): the rows' automaton (GrammarArgs)
     GrammarArgs grammar;
+    // truncating form (trunc.rows != NULL; needs records, presence and bias): the rows' min-p / typical-p / epsilon / eta records (TruncArgs)
+    TruncArgs trunc;
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
 // Classifier-free guidance between paired rows of logits [B, V], in place (guidance.hip): for every row c with u = partner[c] in [0, B),

@@ -93,7 +93,7 @@ struct mgea_decoder {
     // The handle's other HIP resources, declared behind the device groups, so that they go first (members die in reverse order):
     // the graphs, the pinned staging arrays and the events, then the device memory.
     Event stage_free;        // recorded after the copy out of samp_stage / gram_stage: they may be rewritten once it has completed
-    PinnedGroup pinned;      // samp_stage, gram_stage, guide_stage, cond_stage
+    PinnedGroup pinned;      // samp_stage, gram_stage, guide_stage, cond_stage, trunc_stage
 
     // KV pool
     KvPool kv{};
@@ -164,6 +164,10 @@ struct mgea_decoder {
     int32_t* guide_partner = nullptr;
     float* guide_scale = nullptr;
     int32_t* guide_stage = nullptr;
+    // Truncation (mgea_decoder_generate_rows_truncated; TruncArgs, common.h): trunc_dev [max_batch] holds the rows' min-p / typical-p /
+    // epsilon / eta records.  Allocated at create behind the guidance vectors and filled per call through the pinned trunc_stage (free
+    // under stage_free like the records), so the truncated graphs hold a stable pointer and a request with other values replays them.
+    mgea_row_truncation *trunc_dev = nullptr, *trunc_stage = nullptr;
     // Emotion transitions (mgea_decoder_generate_rows_scheduled; recondition.hip).  Everything here belongs to dev_cond and is allocated by
     // the first scheduled call, never by create: cond_store holds the K | V of positions [0, len_b) of every prompt variant (cond_bytes
     // of it; a call that needs more synchronises, drops the scheduled graphs and regrows the whole group), cond_sched [max_batch] the
@@ -195,7 +199,7 @@ struct mgea_decoder {
         bool penalized = false;   // it applied a penalty (or a bias): presence holds its rows
         bool scheduled = false;   // it was scheduled: cond_cur_seg / cond_switches hold its rows
         int64_t graph_replays = 0, scored_steps = 0, penalized_steps = 0, biased_steps = 0, gram_steps = 0, guide_pairs = 0, guide_steps = 0,
-                sched_steps = 0;
+                sched_steps = 0, trunc_steps = 0, trunc_rows = 0;
     } last;
     // what mgea_decoder_stats reports of the handle's lifetime, besides the graph cache's own two figures
     struct Counters { int64_t graph_nodes = 0, prefill16_forwards = 0; } n;
@@ -543,6 +547,10 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
     if (k.kind.form == StepForm::GRAMMAR)
         sc.grammar = GrammarArgs{h->gram_class, h->gram_next, h->gram_allow, h->gram_state, h->gram_state, h->done,
                                  h->gram_n_state, h->gram_n_class, grammar_words(h->gram_n_class), h->err_flag};
+    if (k.kind.truncated) {
+        MGEA_REQUIRE(form_has_bias(k.kind.form), MGEA_EINVAL, "internal: a truncated step takes the biased or the grammar form");
+        sc.trunc = TruncArgs{h->trunc_dev};
+    }
     const int hs = hi.stride;
     if (k.kind.scored)   // fused tail: the sampler files both values at the row's step; otherwise per-step vectors that advance_kernel files
         sc.score = ScoreArgs{hi.forced, hs, k.primed ? hi.lp : h->lp_step, k.primed ? hi.ch : h->ch_step, hs, h->err_flag};
@@ -1083,12 +1091,16 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         h->pinned.alloc(&h->gram_stage, nb) ||
         // (and the guidance pairs after the grammar's)
         g.alloc(&h->guide_partner, nb) || g.alloc(&h->guide_scale, cfg->max_batch * sizeof(float)) ||
-        h->pinned.alloc(&h->guide_stage, 2 * nb))
+        h->pinned.alloc(&h->guide_stage, 2 * nb) ||
+        // (and the truncation records after the guidance pairs)
+        g.alloc(&h->trunc_dev, cfg->max_batch * sizeof(mgea_row_truncation)) ||
+        h->pinned.alloc(&h->trunc_stage, cfg->max_batch * sizeof(mgea_row_truncation)))
         return fail(MGEA_ENOMEM, "state allocation failed");
     if (hipMemset(h->forced, 0xff, nhist * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->guide_partner, 0xff, nb) != hipSuccess || hipMemset(h->guide_scale, 0, cfg->max_batch * sizeof(float)) != hipSuccess ||
         hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->gram_state, 0xff, nb) != hipSuccess ||
+        hipMemset(h->trunc_dev, 0, cfg->max_batch * sizeof(mgea_row_truncation)) != hipSuccess ||
         hipMemset(h->page_table, 0, nb * h->max_pages) != hipSuccess || hipMemset(h->ctx_len, 0, nb) != hipSuccess ||
         hipMemset(h->done, 0, nb) != hipSuccess || hipMemset(h->row_step, 0, nb) != hipSuccess ||
         hipMemset(h->cur_ids, 0, nb) != hipSuccess || hipMemset(h->n_done, 0, 16) != hipSuccess ||
@@ -1188,7 +1200,8 @@ GenLimits gen_limits(const mgea_decoder* h) {
 // A guidance shadow row runs on its conditional row's inputs -- same inputs, same id -- and this is the one place that hands them over.
 // `part` names what the caller has just filled for the callers' rows:
 //   PRESENCE  the seeded bitmaps: a pair's set is the conditional prompt plus the generated ids, and both tails add the same ids
-//   RECORDS   the pinned staging arrays: the sampler record -- seed, Philox stream, budget and all -- and the grammar start state
+//   RECORDS   the pinned staging arrays: the sampler record -- seed, Philox stream, budget and all --, the grammar start state and the
+//             truncation record
 //   BIAS      the engine's bias rows: the shadow adds its conditional row's vector (its record says bias_on as that one's does)
 //   FORCED    the engine's forced-id rows: the shadow is told the ids its conditional row is told
 enum class Mirror { PRESENCE, RECORDS, BIAS, FORCED };
@@ -1208,6 +1221,7 @@ int mirror_shadow_rows(mgea_decoder* h, const GenRequest& q, const GenPlan& p, M
         case Mirror::RECORDS:
             h->samp_stage[u] = h->samp_stage[b];
             if (p.grammar) h->gram_stage[u] = q.start_states[b];
+            if (p.truncated) h->trunc_stage[u] = h->trunc_stage[b];
             break;
         case Mirror::BIAS:
             if (h->samp_stage[b].bias_on)
@@ -1277,6 +1291,7 @@ int gen_stage(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_
         MGEA_CHECK_HIP(hipEventSynchronize(h->stage_free.ev));
         build_row_records(q.rows, q.lrows, B, q.n_steps, h->samp_stage);
         for (int b = 0; p.grammar && b < B; ++b) h->gram_stage[b] = q.start_states[b];
+        for (int b = 0; p.truncated && b < B; ++b) h->trunc_stage[b] = q.trunc[b];
         MGEA_TRY(mirror_shadow_rows(h, q, p, Mirror::RECORDS, st));
         for (int b = 0; p.biased && b < B; ++b)
             if (q.lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
@@ -1286,6 +1301,8 @@ int gen_stage(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_
         MGEA_CHECK_HIP(hipMemcpyAsync(h->samp_dev, h->samp_stage, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
         if (p.grammar)
             MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (p.truncated)
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->trunc_dev, h->trunc_stage, (size_t)B * sizeof(mgea_row_truncation), hipMemcpyHostToDevice, st));
         if (p.kind.guided) {   // the pairs and their scales: the guided graphs read the engine's two vectors
             float* scale_stage = reinterpret_cast<float*>(h->guide_stage + c.max_batch);
             for (int b = 0; b < B; ++b) {
@@ -1401,6 +1418,8 @@ int do_generate(mgea_decoder* h, const GenRequest& q, hipStream_t st) {
     last.guide_pairs = p.n_pairs;
     last.guide_steps = p.kind.guided ? launched : 0;
     last.sched_steps = p.kind.scheduled ? launched : 0;
+    last.trunc_steps = p.truncated ? launched : 0;
+    last.trunc_rows = p.truncated ? p.n_trunc : 0;
     h->last = last;
     return gen_finish(h, q, p, launched, st);
 }
@@ -1508,6 +1527,25 @@ int mgea_decoder_generate_rows_scheduled(mgea_decoder* h, const int32_t* prompt_
     q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max;
     q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
     return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_generate_rows_truncated(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                         int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                         const int32_t* start_states, const mgea_row_guidance* guide, const mgea_row_schedule* sched,
+                                         int32_t n_seg_max, const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
+                                         float* choice_logprobs_out_dev, const mgea_row_truncation* trunc, void* stream) {
+    GenRequest q = rows_request(trunc ? "decoder_generate_rows_truncated" : "decoder_generate_rows_scheduled", prompt_ids_dev, lens_dev, B, Tp,
+                                n_steps, rows, logits_rows, ids_out_dev);
+    q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max; q.trunc = trunc;
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_truncation_info(mgea_decoder* h, int64_t* out) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_truncation_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->last.trunc_steps; out[1] = h->last.trunc_rows;
+    return MGEA_OK;
 }
 
 int mgea_decoder_set_grammar(mgea_decoder* h, const int32_t* class_of_host, const int32_t* next_host, int32_t n_state, int32_t n_class,

@@ -49,11 +49,13 @@ inline bool form_has_bias(StepForm f) { return f == StepForm::BIASED || f == Ste
 //   windowed   the step opens with the KV window's evict launch and files into the windowed histories (kv_window.hip)
 //   guided     the guidance-mix launch over the logits, between the head and the sampler (guidance.hip; never GREEDY)
 //   scheduled  behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip)
+//   truncated  the truncating sampler over the rows' mgea_row_truncation records (BIASED or GRAMMAR form only)
 struct StepKind {
     StepForm form;
-    bool scored = false, windowed = false, guided = false, scheduled = false;
+    bool scored = false, windowed = false, guided = false, scheduled = false, truncated = false;
     bool operator==(const StepKind& o) const {
-        return form == o.form && scored == o.scored && windowed == o.windowed && guided == o.guided && scheduled == o.scheduled;
+        return form == o.form && scored == o.scored && windowed == o.windowed && guided == o.guided && scheduled == o.scheduled &&
+               truncated == o.truncated;
     }
 };
 
@@ -155,6 +157,29 @@ inline int check_row_schedules(const mgea_row_schedule* sched, int B, int n_seg_
     return MGEA_OK;
 }
 
+// Does the record switch a stage on?  (0 = off; typical_p == 1 is off too: everything weighs 1)
+inline bool truncation_on(const mgea_row_truncation& t) {
+    return t.min_p > 0.f || (t.typical_p > 0.f && t.typical_p < 1.f) || t.epsilon_cutoff > 0.f || t.eta_cutoff > 0.f;
+}
+// host check of trunc[0, B) (mgea_decoder_generate_rows_truncated, mgea_op_sample_rows_truncated): MGEA_EINVAL naming the first bad row;
+// *n_rows = the non-greedy rows (rows NULL: all rows) with a stage switched on
+inline int check_row_truncation(const mgea_row_truncation* trunc, const mgea_row_sampler* rows, int B, const char* who, int* n_rows) {
+    *n_rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_truncation& t = trunc[b];
+        MGEA_REQUIRE(std::isfinite(t.min_p) && t.min_p >= 0.f && t.min_p <= 1.f, MGEA_EINVAL, "%s: row %d: min_p %g outside [0, 1]", who, b,
+                     (double)t.min_p);
+        MGEA_REQUIRE(std::isfinite(t.typical_p) && t.typical_p >= 0.f && t.typical_p <= 1.f, MGEA_EINVAL, "%s: row %d: typical_p %g outside [0, 1]",
+                     who, b, (double)t.typical_p);
+        MGEA_REQUIRE(std::isfinite(t.epsilon_cutoff) && t.epsilon_cutoff >= 0.f && t.epsilon_cutoff < 1.f, MGEA_EINVAL,
+                     "%s: row %d: epsilon_cutoff %g outside [0, 1)", who, b, (double)t.epsilon_cutoff);
+        MGEA_REQUIRE(std::isfinite(t.eta_cutoff) && t.eta_cutoff >= 0.f && t.eta_cutoff < 1.f, MGEA_EINVAL,
+                     "%s: row %d: eta_cutoff %g outside [0, 1)", who, b, (double)t.eta_cutoff);
+        if (truncation_on(t) && !(rows && rows[b].top_k == 1)) *n_rows += 1;
+    }
+    return MGEA_OK;
+}
+
 // Everything a generation is asked for.  prompt_ids, lens, forced and the three outputs are DEVICE memory, as in the C ABI; the records
 // are host memory.
 struct GenRequest {
@@ -175,6 +200,7 @@ struct GenRequest {
     const mgea_row_guidance* guide = nullptr;
     const mgea_row_schedule* sched = nullptr;
     int n_seg_max = 1;
+    const mgea_row_truncation* trunc = nullptr;   // [B] the rows' truncation records (any non-greedy row with a stage on makes it truncated)
     const int32_t* forced = nullptr;        // [B][n_steps] ids the rows must take, -1 = free (scored only)
     int32_t* ids_out = nullptr;             // [B][n_steps]
     float* logprobs_out = nullptr;          // [B][n_steps]; not NULL makes the generation scored
@@ -199,6 +225,8 @@ struct GenPlan {
     bool capped;           // rows stop where their KV pages end (launch_clamp_budgets, parking)
     int n_pairs;           // guidance pairs: conditional rows with a shadow row
     int n_sched;           // scheduled rows: more than one prompt variant
+    int n_trunc;           // truncated rows: non-greedy rows with a truncation stage switched on
+    bool truncated;        // n_trunc > 0: the steps run the truncating sampler
     int reserve;           // tokens of KV pages every row gets
 };
 
@@ -232,6 +260,8 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
                          c.gram_n_state);
             p.grammar = true;
         }
+        if (q.trunc) MGEA_TRY(check_row_truncation(q.trunc, q.rows, B, "decoder_generate_rows_truncated", &p.n_trunc));
+        p.truncated = p.n_trunc > 0;
         if (q.guide) MGEA_TRY(check_row_guidance(q.guide, B, &p.n_pairs));
         if (q.sched) {   // (n_seg_max itself: checked by the entry point)
             MGEA_TRY(check_row_schedules(q.sched, B, q.n_seg_max, q.start_states, c.gram_n_state, q.guide, &p.n_sched));
@@ -261,8 +291,13 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
     const bool scored = q.scored(), guided = p.n_pairs > 0;
     // scoring and guidance need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
     // the lowest id)
-    const StepForm form = p.grammar ? StepForm::GRAMMAR : (scored || guided) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED : rr.form;
-    p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0};
+    // truncation lives in the <PENALTY, BIAS> sampler family, as the grammar does: the BIASED form at least (bitmaps over every row, a
+    // penalty of 1 and a record without bias_on change nothing)
+    const StepForm form = p.grammar           ? StepForm::GRAMMAR
+                          : p.truncated     ? StepForm::BIASED
+                          : (scored || guided) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED
+                                              : rr.form;
+    p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0, p.truncated};
     *out = p;
     return MGEA_OK;
 }

@@ -36,6 +36,11 @@
 // and a row that has produced fewer than its record's min_new ids has x[eos_id] = -inf.  A banned entry is an ordinary logit from there
 // on: its key is the smallest a real entry can have, exp(-inf - max) is exactly 0, so it carries no mass, is never drawn, and may sit
 // among the top_k kept when fewer than top_k ids are admissible.  A row without a bias is not touched (no + 0).
+// Truncation (the instantiations with a TruncArgs argument, PENALTY and BIAS ones only; HF MinP / Typical / Epsilon / Eta warpers --
+// build-defined, the reference has none; the rule: include/mgea.h, mgea_row_truncation): behind top-k and top-p a row whose record
+// switches them on applies min-p, typical-p, the epsilon and the eta cutoff, in this order, each over the softmax of what is kept so
+// far.  The three thresholds clear keys after one block reduction; typical-p is a band, found as the mass boundary under the key of
+// -|(-log p) - H| with the fixed-point masses and the bisection of top-p.  A row with nothing switched on, and a top_k == 1 row, skip it.
 #include <cmath>
 #include <type_traits>
 
@@ -70,6 +75,17 @@ __device__ __forceinline__ float block_sum_f(float v, float* red /* [SAMP_NW] */
     float t = 0.f;
 #pragma unroll
     for (int w = 0; w < SAMP_NW; ++w) t += red[w];          // fixed order: deterministic
+    return t;
+}
+
+__device__ __forceinline__ float block_max_f(float v, float* red /* [SAMP_NW] */) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = red[0];
+#pragma unroll
+    for (int w = 1; w < SAMP_NW; ++w) t = fmaxf(t, red[w]);
     return t;
 }
 
@@ -304,7 +320,7 @@ __device__ __forceinline__ float* score_lds() {
     __shared__ float s[3];
     return s;
 }
-// the argument of type T among a kernel's optional trailing arguments (ScoreArgs, GrammarArgs), T{} when it was not passed
+// the argument of type T among a kernel's optional trailing arguments (ScoreArgs, GrammarArgs, TruncArgs), T{} when it was not passed
 template <typename T>
 __device__ __forceinline__ T extra_arg() { return T{}; }
 template <typename T, typename A, typename... R>
@@ -349,6 +365,9 @@ __device__ __forceinline__ void grammar_advance_row(const GrammarArgs& gr, int b
 //   * the state's row of the allow bitmask (<= 128 words) is staged in LDS next to the presence words, under the penalty's barrier;
 //     every thread folds its ids' verdicts into one 64-bit word (MAXE <= 64), which is all that stays live until the mask is applied.
 // A row with state -1 skips all of it (block-uniform) and computes what the BIAS form computes.
+// TRUNC (the instantiations with a TruncArgs argument, PENALTY and BIAS ones only; common.h): between top-p and the final distribution
+// the row's record may clear further keys; every stage works on the registers the row already occupies (key, whi, wlo), so the wide
+// instantiation stays without scratch.  After typical-p the row's maximum may be gone: mx is re-derived from the kept set.
 template <int MAXE, bool PENALTY, bool BIAS, typename... Score>
 __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict__ logits, int V, SamplerParams pv,
                                                     const SamplerParams* __restrict__ pd,
@@ -360,11 +379,15 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     // part under `if constexpr`, the code, are those of the kernel before there was a scored form
     constexpr bool SCORED = (std::is_same_v<Score, ScoreArgs> || ...);
     constexpr bool GRAMMAR = (std::is_same_v<Score, GrammarArgs> || ...);
-    static_assert(sizeof...(Score) == (SCORED ? 1 : 0) + (GRAMMAR ? 1 : 0), "at most one ScoreArgs, then at most one GrammarArgs");
+    constexpr bool TRUNC = (std::is_same_v<Score, TruncArgs> || ...);
+    static_assert(sizeof...(Score) == (SCORED ? 1 : 0) + (GRAMMAR ? 1 : 0) + (TRUNC ? 1 : 0),
+                  "at most one ScoreArgs, then at most one GrammarArgs, then at most one TruncArgs");
     static_assert(!GRAMMAR || (PENALTY && BIAS), "the GRAMMAR form is built on the BIASED one");
+    static_assert(!TRUNC || (PENALTY && BIAS), "the truncating form is built on the BIASED one");
     static_assert(MAXE <= 64, "the grammar's verdicts of a thread fit one 64-bit word");
     [[maybe_unused]] const ScoreArgs sc = extra_arg<ScoreArgs>(score...);
     [[maybe_unused]] const GrammarArgs gr = extra_arg<GrammarArgs>(score...);
+    [[maybe_unused]] const TruncArgs ta = extra_arg<TruncArgs>(score...);
     constexpr int NT = SAMP_NT, NW = SAMP_NW;
     static_assert(SAMP_KFAST == 64, "wave_publish_ge fills one slot per lane");
     __shared__ unsigned long long red64[2 * NW];
@@ -666,6 +689,107 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
         }
     }
 
+    if constexpr (TRUNC) {
+        // ---- min-p, typical-p, epsilon and eta cutoff over what top-k and top-p kept, in this order; every stage sees the softmax over
+        // what the stages before it kept (mgea_row_truncation, include/mgea.h).  The record is block-uniform; a row that switches
+        // nothing on, and a top_k == 1 row, go straight to the final distribution with the keys they have.
+        const mgea_row_truncation tr = ta.rows[b];
+        const bool typical_on = tr.typical_p > 0.f && tr.typical_p < 1.f;
+        if (top_k != 1 && (tr.min_p > 0.f || typical_on || tr.epsilon_cutoff > 0.f || tr.eta_cutoff > 0.f)) {
+            // from here on the kept set is {j : key[j] != 0}: the threshold goes into the keys, so that a stage removes an entry by
+            // clearing its key and typical-p may put its own key there
+#pragma unroll
+            for (int j = 0; j < MAXE; ++j) key[j] = key[j] >= keep_key ? key[j] : 0u;
+            keep_key = 0u;
+            __shared__ int s_first;
+            // 1. min-p: p_i < min_p * max(p) <=> exp(x_i - mx) < min_p (the normaliser cancels; mx is kept so far, and stays: 1 >= min_p)
+            if (tr.min_p > 0.f) {
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) key[j] = (key[j] != 0u && __expf(x[j] - mx) < tr.min_p) ? 0u : key[j];
+            }
+            // 2. typical-p: a band around the entropy, not a threshold.  The entries' keys become the order-preserving keys of -d_i and
+            // their fixed-point masses go into whi / wlo, so the smallest d* that holds the mass is the mass boundary under that key.
+            if (typical_on) {
+                float z = 0.f;
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) z += key[j] != 0u ? __expf(x[j] - mx) : 0.f;
+                z = block_sum_f(z, redf);
+                const float invZ = 1.0f / z, logZ = __logf(z);
+                float h = 0.f;
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) {
+                    const float pj = key[j] != 0u ? __expf(x[j] - mx) * invZ : 0.f;
+                    h += pj > 0.f ? pj * ((x[j] - mx) - logZ) : 0.f;   // p = 0 adds nothing (never 0 * -inf)
+                }
+                const float H = -block_sum_f(h, redf);
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) {
+                    whi[j] = wlo[j] = 0u;
+                    if (key[j] != 0u) {
+                        const float nlp = logZ - (x[j] - mx);   // -log p_i; +inf for a banned id, whose d is +inf
+                        key[j] = fkey(-fabsf(nlp - H));         // >= fkey(-inf) > 0: still "kept"
+                        mass_fixed(__expf(x[j] - mx) * invZ, whi[j], wlo[j]);
+                    }
+                }
+                const unsigned long long target = (unsigned long long)((double)tr.typical_p * 1099511627776.0);
+                const uint32_t band = bisect_boundary<true, MAXE>(key, whi, wlo, 0u, target, red64);   // 0: even everything weighs less
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) key[j] = key[j] >= band ? key[j] : 0u;
+                // the row's maximum may have left: everything below works from the kept set's own maximum
+                float m2 = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) m2 = key[j] != 0u ? fmaxf(m2, x[j]) : m2;
+                mx = block_max_f(m2, redf);
+            }
+            // 3. and 4., the two probability floors: p_i < floor leaves, but the largest remaining logit stays (lowest id among equals)
+            for (int stage = 0; stage < 2; ++stage) {
+                const float cut = stage == 0 ? tr.epsilon_cutoff : tr.eta_cutoff;
+                if (!(cut > 0.f)) continue;   // block-uniform
+                float z = 0.f;
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) z += key[j] != 0u ? __expf(x[j] - mx) : 0.f;
+                z = block_sum_f(z, redf);
+                const float invZ = 1.0f / z;
+                float floor_p = cut;
+                if (stage == 1) {   // eta' = min(eta, sqrt(eta) * exp(-H)), H the entropy of the current distribution
+                    const float logZ = __logf(z);
+                    float h = 0.f;
+#pragma unroll
+                    for (int j = 0; j < MAXE; ++j) {
+                        const float pj = key[j] != 0u ? __expf(x[j] - mx) * invZ : 0.f;
+                        h += pj > 0.f ? pj * ((x[j] - mx) - logZ) : 0.f;
+                    }
+                    const float H = -block_sum_f(h, redf);
+                    floor_p = fminf(cut, sqrtf(cut) * __expf(-H));
+                }
+                // even the maximum (exp(0) / Z) is below the floor: it alone stays, the lowest id of its equals (block-uniform, rare)
+                const bool none = invZ < floor_p;
+                int first = -1;
+                if (none) {
+                    int mine = 0x7fffffff;
+#pragma unroll
+                    for (int j = MAXE - 1; j >= 0; --j) mine = (key[j] != 0u && x[j] == mx) ? j : mine;   // the thread's lowest
+                    mine = mine != 0x7fffffff ? tid + NT * mine : mine;
+                    if (tid == 0) s_first = 0x7fffffff;
+                    __syncthreads();
+                    if (mine != 0x7fffffff) atomicMin(&s_first, mine);
+                    __syncthreads();
+                    first = s_first;
+                    __syncthreads();   // s_first may be rewritten by the next stage
+                }
+                // (the survivor as (owner thread, register index): one compare per thread and a uniform one per register -- spelt as
+                // tid + NT * j == first, the 56 ids are hoisted out of the stage loop and the wide instantiation spills)
+                const bool owner = first >= 0 && tid == (first & (NT - 1));
+                const int fj = first >= 0 ? first / NT : -1;
+#pragma unroll
+                for (int j = 0; j < MAXE; ++j) {
+                    const bool out = none ? !(owner && j == fj) : __expf(x[j] - mx) * invZ < floor_p;
+                    key[j] = out ? 0u : key[j];
+                }
+            }
+        }
+    }
+
     // ---- final distribution over the kept set; CDF order = thread-major (t, then t + NT, ...): any fixed order gives
     // the same distribution
     float e[MAXE];
@@ -785,6 +909,38 @@ int launch_sample(const SampleCall& c, hipStream_t st) {
                                      : (narrow ? sample_kernel<36, false, true> : sample_kernel<56, false, true>))
                        : (c.presence ? (narrow ? sample_kernel<36, true, false> : sample_kernel<56, true, false>)
                                      : (narrow ? sample_kernel<36, false, false> : sample_kernel<56, false, false>));
+    if (c.trunc.rows) {
+        // the truncating sampler: the <PENALTY, BIAS> family alone, with and without ScoreArgs and GrammarArgs
+        const bool gram = c.grammar.class_of != nullptr, scored = c.score.logprob != nullptr;
+        const GrammarArgs& g = c.grammar;
+        MGEA_REQUIRE(c.bias && c.presence && c.params_dev, MGEA_EINVAL, "sampler: the truncating form needs records, presence bitmaps and the bias buffer");
+        MGEA_REQUIRE(!gram || (g.next && g.allow && g.state_in && g.n_state > 0 && g.n_class > 0 && g.n_class <= MGEA_GRAMMAR_MAX_CLASSES &&
+                               g.words == grammar_words(g.n_class) && (!c.ids_out || g.state_out)),
+                     MGEA_EINVAL, "sampler: bad grammar arguments");
+        MGEA_REQUIRE(scored || !c.score.forced, MGEA_EINVAL, "sampler: forced ids need the scored form");
+        MGEA_REQUIRE(!scored || c.ids_out, MGEA_EINVAL, "sampler: a scored launch draws ids");
+        const dim3 grid(c.B), block(SAMP_NT);
+        const int ft = tail ? 1 : 0, ws = tune(TUNE_SAMPLER_WAVE_SELECT);
+        auto tkern = narrow ? sample_kernel<36, true, true, TruncArgs> : sample_kernel<56, true, true, TruncArgs>;
+        auto tskern = narrow ? sample_kernel<36, true, true, ScoreArgs, TruncArgs> : sample_kernel<56, true, true, ScoreArgs, TruncArgs>;
+        auto tgkern = narrow ? sample_kernel<36, true, true, GrammarArgs, TruncArgs> : sample_kernel<56, true, true, GrammarArgs, TruncArgs>;
+        auto tgskern = narrow ? sample_kernel<36, true, true, ScoreArgs, GrammarArgs, TruncArgs>
+                              : sample_kernel<56, true, true, ScoreArgs, GrammarArgs, TruncArgs>;
+        if (gram && scored)
+            hipLaunchKernelGGL(tgskern, grid, block, 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host, c.ids_out,
+                               c.probs_out, t, ft, ws, c.presence, c.bias, c.score, g, c.trunc);
+        else if (gram)
+            hipLaunchKernelGGL(tgkern, grid, block, 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host, c.ids_out,
+                               c.probs_out, t, ft, ws, c.presence, c.bias, g, c.trunc);
+        else if (scored)
+            hipLaunchKernelGGL(tskern, grid, block, 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host, c.ids_out,
+                               c.probs_out, t, ft, ws, c.presence, c.bias, c.score, c.trunc);
+        else
+            hipLaunchKernelGGL(tkern, grid, block, 0, st, c.logits, V, c.params, c.params_dev, c.row_step_dev, c.step_host, c.ids_out,
+                               c.probs_out, t, ft, ws, c.presence, c.bias, c.trunc);
+        MGEA_CHECK_HIP(hipGetLastError());
+        return MGEA_OK;
+    }
     if (c.grammar.class_of) {
         const GrammarArgs& g = c.grammar;
         MGEA_REQUIRE(c.bias && c.presence && c.params_dev, MGEA_EINVAL, "sampler: the grammar form needs records, presence bitmaps and the bias buffer");

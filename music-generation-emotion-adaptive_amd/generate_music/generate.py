@@ -24,12 +24,13 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from mgea.decoder import DecoderEngine, RowSampling, geometry_from_state_dict, remap_state_dict  # noqa: F401
+from mgea.decoder import DecoderEngine, RowSampling, Truncation, geometry_from_state_dict, remap_state_dict  # noqa: F401
 
 __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab", "encode", "decode",
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
            "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
-           "generate_batch_biased", "generate_sequence_biased", "sample_kvcache_grammar", "generate_batch_grammar", "score_sequence", "generate_best_of", "pick_best",
+           "generate_batch_biased", "generate_sequence_biased", "sample_kvcache_grammar", "generate_batch_grammar", "sample_kvcache_truncated",
+           "generate_sequence_truncated", "generate_batch_truncated", "score_sequence", "generate_best_of", "pick_best",
            "mean_logprobs", "sample_kvcache_guided", "generate_requests_guided"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
@@ -219,11 +220,11 @@ def _use_grammar(eng, grammar) -> None:
         eng.set_grammar(grammar)
 
 
-def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, grammar=None, **kw):
+def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, grammar=None, truncation=None, **kw):
     """eng.generate(), or eng.generate_biased() when a bias or a minimum length is set (capped at the steps there are); with a
-    grammar, generate_rows() with the same record on every row (stream = the row's index: the draws of generate()) and each row's
-    start state walked from its prompt"""
-    if grammar is not None:
+    grammar or a Truncation, generate_rows() with the same record on every row (stream = the row's index: the draws of generate())
+    and, under a grammar, each row's start state walked from its prompt"""
+    if grammar is not None or truncation is not None:
         from .grammar import start_state
         _use_grammar(eng, grammar)
         B = len(ids)
@@ -235,7 +236,8 @@ def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, grammar=None
         rows = [RowSampling(temperature=kw.get("temperature", 1.0), top_k=kw.get("top_k", 50), top_p=kw.get("top_p"),
                             repetition_penalty=kw.get("repetition_penalty"), eos_id=kw.get("eos_id", -1), seed=kw.get("seed", 0),
                             logit_bias=per_row[b], min_new_tokens=min(int(min_new_tokens), n_steps),
-                            grammar_state=start_state(grammar, ids[b])) for b in range(B)]
+                            grammar_state=None if grammar is None else start_state(grammar, ids[b]), truncation=truncation)
+                for b in range(B)]
         return eng.generate_rows(ids, rows, n_steps)
     if logit_bias is None and not min_new_tokens:
         return eng.generate(ids, n_steps, **kw)
@@ -275,12 +277,15 @@ def sample_kvcache_biased(model, prompt: Sequence[str], max_len=512, temperature
 
 def sample_kvcache_grammar(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
                            top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
-                           logit_bias=None, min_new_tokens: int = 0, grammar=None) -> List[str]:
+                           logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                           min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
     """sample_kvcache_biased under a token grammar (sample_kvcache_biased keeps its parameter list).  grammar (a
     mgea.decoder.TokenGrammar, e.g. generate_music.grammar.track_grammar; None = none: then this IS sample_kvcache_biased)
     constrains what may FOLLOW what: the row starts in the state its prompt leads to (generate_music.grammar.start_state), every
     step is masked by the row's current state, and the state moves on the device.  It composes with logit_bias: the bias bans ids,
-    the grammar orders the rest."""
+    the grammar orders the rest.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     m = _as_model(model)
     eng = m._need()
     ids = [tok2id[t] for t in prompt]          # KeyError for an unknown token, like api_cache.py:162
@@ -292,7 +297,8 @@ def sample_kvcache_grammar(model, prompt: Sequence[str], max_len=512, temperatur
     eos = tok2id.get("[END_SEQUENCE]", -1)
     out = _engine_generate(eng, [ids], n_steps, logit_bias, min_new_tokens, grammar, temperature=temperature, top_k=top_k,
                            top_p=top_p, eos_id=eos, seed=_draw_seed() if seed is None else seed,
-                           repetition_penalty=repetition_penalty)
+                           repetition_penalty=repetition_penalty,
+                           truncation=Truncation.of(min_p, typical_p, epsilon_cutoff, eta_cutoff))
     gen = [int(i) for i in out[0].cpu().tolist() if i >= 0]
     return [id2tok[i] for i in ids + gen]
 
@@ -331,9 +337,12 @@ def generate_batch_biased(model, prompts: Sequence[Sequence[str]], max_len=512, 
 
 def generate_batch_grammar(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
                            top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
-                           logit_bias=None, min_new_tokens: int = 0, grammar=None) -> List[List[str]]:
+                           logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                           min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
     """generate_batch_biased under a token grammar (None = none), as in sample_kvcache_grammar: every row starts in the state of its
-    own prompt."""
+    own prompt.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     m = _as_model(model)
     eng = m._need()
     ids = [[tok2id[t] for t in p] for p in prompts]
@@ -341,8 +350,43 @@ def generate_batch_grammar(model, prompts: Sequence[Sequence[str]], max_len=512,
     eos = tok2id.get("[END_SEQUENCE]", -1)
     out = _engine_generate(eng, ids, max(n_steps, 0), logit_bias, min_new_tokens, grammar, temperature=temperature, top_k=top_k,
                            top_p=top_p, eos_id=eos, seed=_draw_seed() if seed is None else seed,
-                           repetition_penalty=repetition_penalty).cpu().tolist()
+                           repetition_penalty=repetition_penalty,
+                           truncation=Truncation.of(min_p, typical_p, epsilon_cutoff, eta_cutoff)).cpu().tolist()
     return [[id2tok[i] for i in p + [g for g in row if g >= 0]] for p, row in zip(ids, out)]
+
+
+def sample_kvcache_truncated(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
+                             top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                             logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                             min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
+    """sample_kvcache with HuggingFace's further truncation rules (sample_kvcache and sample_kvcache_biased keep their parameter
+    lists; sample_kvcache_grammar takes the same four keywords): min_p, typical_p (locally typical sampling), epsilon_cutoff and
+    eta_cutoff, None = off, applied in this order behind top-k and top-p inside the engine's sampler (mgea.decoder.Truncation;
+    build-defined, the reference has none).  With none of them this is sample_kvcache_grammar, the same engine call."""
+    return sample_kvcache_grammar(model, prompt, max_len, temperature, top_k, device, top_p, seed, repetition_penalty, logit_bias,
+                                  min_new_tokens, grammar,
+                                  min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+
+
+def generate_sequence_truncated(model_or_weights, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50,
+                                device=_DEFAULT_DEVICE, top_p: Optional[float] = None, seed: Optional[int] = None, n_head: int = 8,
+                                repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                                min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
+    """generate_sequence with the four truncation keywords: sample_kvcache_truncated on a model object or a weights dict."""
+    return sample_kvcache_truncated(_as_model(model_or_weights, n_head, device), prompt, max_len, temperature, top_k, device, top_p,
+                                    seed, repetition_penalty, logit_bias, min_new_tokens, grammar,
+                                    min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+
+
+def generate_batch_truncated(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
+                             top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                             logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                             min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
+    """generate_batch with the four truncation keywords of sample_kvcache_truncated, the same values on every row
+    (generate_batch_grammar takes them too; generate_requests takes one value per prompt)."""
+    return generate_batch_grammar(model, prompts, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias,
+                                  min_new_tokens, grammar,
+                                  min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
 
 
 def score_sequence(model, prompt_tokens: Sequence[str], continuation_tokens: Sequence[str]) -> List[float]:
@@ -383,13 +427,15 @@ def pick_best(ids, logprobs) -> int:
 
 def generate_best_of(model, prompt: Sequence[str], n: int, max_len=512, temperature=1.0, top_k=50, top_p: Optional[float] = None,
                      seed: Optional[int] = None, repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0,
-                     return_all: bool = False, grammar=None):
+                     return_all: bool = False, grammar=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
     """sample_kvcache_biased n times in ONE batch, keeping the most likely candidate: the n rows share the prompt, the settings and
     the seed and draw from Philox streams 0 .. n - 1 (row 0 is the sample_kvcache run of that seed); the one with the highest mean
     raw log-probability per generated token (pick_best) is returned as prompt + generated tokens.  n is capped by the model's
     max_batch (ValueError beyond it).  return_all=True returns (tokens, candidates, means, best): every candidate's tokens, their
     mean log-probabilities and the index kept.  grammar (a TokenGrammar or None): every candidate starts in the state of the prompt.
-    Build-defined: the reference draws one sequence and returns no scores."""
+    Build-defined: the reference draws one sequence and returns no scores.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     m = _as_model(model)
     n = int(n)
     if n < 1 or n > m.max_batch:
@@ -411,7 +457,7 @@ def generate_best_of(model, prompt: Sequence[str], n: int, max_len=512, temperat
         gstate = start_state(grammar, ids)
     rows = [RowSampling(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, eos_id=eos,
                         seed=seed, stream=b, logit_bias=logit_bias, min_new_tokens=min(int(min_new_tokens), n_steps),
-                        grammar_state=gstate)
+                        grammar_state=gstate, truncation=Truncation.of(min_p, typical_p, epsilon_cutoff, eta_cutoff))
             for b in range(n)]
     res = eng.generate_scored([ids] * n, rows, n_steps)
     out, lps = res.ids.cpu().tolist(), res.logprobs.cpu().tolist()
@@ -431,7 +477,8 @@ def _per_prompt(value, n: int, name: str) -> list:
 
 def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
                       top_p: Optional[float] = None, seed=None, repetition_penalty=None, logit_bias=None,
-                      min_new_tokens=0, grammar=None) -> List[List[str]]:
+                      min_new_tokens=0, grammar=None,
+                      min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
     """Independent sample_kvcache requests served by one batched generation (up to the engine's max_batch rows per
     generation; more prompts take several).  Every argument may be a scalar or a list with one value per prompt.  Prompt i
     gets max_len_i - len(prompt_i) new tokens and stops after [END_SEQUENCE], like sample_kvcache; a seed of None is drawn
@@ -441,7 +488,9 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     the batch size (kernel choice), not on the other requests.  logit_bias (one vector -- a dict, a host array or a device
     tensor [vocab] -- for every prompt, or a list with one per prompt, None = none) and min_new_tokens (capped at the prompt's
     budget) travel in the rows' records.  grammar (ONE TokenGrammar for all the prompts, or None) makes every row start in the state
-    of its own prompt."""
+    of its own prompt.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     m = _as_model(model)
     eng = m._need()
     n = len(prompts)
@@ -453,6 +502,8 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
     biases = _per_prompt(logit_bias, n, "logit_bias")
     mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
+    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
+                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
     budgets = [L - len(p) for L, p in zip(max_lens, ids)]
     for L, p in zip(max_lens, ids):
@@ -470,7 +521,7 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
         gstates = [start_state(grammar, p) for p in ids]
     rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
                            max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i])
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
             for i in live}
     gen: Dict[int, List[int]] = {}
     for c0 in range(0, len(live), eng.max_batch):
@@ -484,27 +535,34 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
 def sample_kvcache_guided(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
                           top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
                           logit_bias=None, min_new_tokens: int = 0, grammar=None, guidance_scale: float = 1.5,
-                          negative_prompt: Optional[Sequence[str]] = None) -> List[str]:
+                          negative_prompt: Optional[Sequence[str]] = None,
+                          min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
     """sample_kvcache_grammar under classifier-free guidance (sample_kvcache_grammar keeps its parameter list): the request runs as a
     pair of rows, the prompt and negative_prompt -- None = the prompt without its [BPM] and [KEY_SIGNATURE] tokens
     (generate_music.guidance.unconditional_prompt) -- and every id is drawn from guidance_scale * logp(prompt) +
     (1 - guidance_scale) * logp(negative_prompt): 1 = the conditional distribution (not the same draws as sample_kvcache: a batch of
     two takes other kernels), above 1 the emotion tokens weigh more, 0 = the negative prompt alone.  Everything else -- penalty, bias,
     minimum length, grammar, the seed's Philox stream -- is the request's, applied to the mixed distribution.  Build-defined
-    (DecoderEngine.generate_guided); the model needs max_batch >= 2."""
+    (DecoderEngine.generate_guided); the model needs max_batch >= 2.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     return generate_requests_guided(model, [prompt], max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias,
                                     min_new_tokens, grammar, guidance_scale,
-                                    None if negative_prompt is None else [list(negative_prompt)])[0]
+                                    None if negative_prompt is None else [list(negative_prompt)],
+                                    min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)[0]
 
 
 def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
                              top_p: Optional[float] = None, seed=None, repetition_penalty=None, logit_bias=None, min_new_tokens=0,
-                             grammar=None, guidance_scale=1.5, negative_prompts=None) -> List[List[str]]:
+                             grammar=None, guidance_scale=1.5, negative_prompts=None,
+                             min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
     """generate_requests under classifier-free guidance: every request is a pair of rows (sample_kvcache_guided), so one generation
     serves up to max_batch // 2 of them.  guidance_scale: one value or one per prompt; negative_prompts: None = every prompt without
     its [BPM] / [KEY_SIGNATURE] tokens, else one token list per prompt (a None entry = that one's default).  Unlike generate_requests
     a request that would run past the engine's context is refused (RuntimeError) also where only its budget would be cut: a guided
-    generation is never capped (a KV window lifts the limit)."""
+    generation is never capped (a KV window lifts the limit).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     from .guidance import unconditional_prompt
     m = _as_model(model)
     eng = m._need()
@@ -517,6 +575,8 @@ def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=51
     pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
     biases = _per_prompt(logit_bias, n, "logit_bias")
     mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
+    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
+                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     scales = [float(v) for v in _per_prompt(guidance_scale, n, "guidance_scale")]
     negs = [None] * n if negative_prompts is None else list(negative_prompts)
     if len(negs) != n:
@@ -539,7 +599,7 @@ def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=51
         gstates = [start_state(grammar, p) for p in ids]
     rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
                            max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i])
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
             for i in live}
     gen: Dict[int, List[int]] = {}
     per = eng.max_batch // 2
@@ -559,7 +619,8 @@ def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=51
 def sample_kvcache_transitions(model, prompts: Sequence[Sequence[str]], shares=None, max_len=512, temperature=1.0, top_k=50,
                                device="cpu", top_p: Optional[float] = None, seed: Optional[int] = None,
                                repetition_penalty: Optional[float] = None, logit_bias=None, min_new_tokens: int = 0, grammar=None,
-                               guidance_scale: Optional[float] = None, negative_prompt: Optional[Sequence[str]] = None) -> List[str]:
+                               guidance_scale: Optional[float] = None, negative_prompt: Optional[Sequence[str]] = None,
+                               min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
     """sample_kvcache_guided for a piece whose conditioning changes on the way (sample_kvcache_guided keeps its parameter list).
     prompts: 1 to 8 variants of ONE prompt, equal in length (generate_music.transitions.transition_prompts: the first with other
     [BPM] / [KEY_SIGNATURE] tokens); shares: the segments' relative lengths (None = equal).  The generation starts from prompts[0];
@@ -568,19 +629,25 @@ def sample_kvcache_transitions(model, prompts: Sequence[Sequence[str]], shares=N
     track passes through all the emotions in musical time; without one they are ranges of steps (transitions.step_thresholds).
     guidance_scale None = no guidance; a number pairs the request with negative_prompt as sample_kvcache_guided does (the shadow row
     does not switch: it has no emotion tokens).  Returns prompts[0] + the generated tokens.  Build-defined
-    (DecoderEngine.generate_scheduled)."""
+    (DecoderEngine.generate_scheduled).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     return generate_requests_transitions(model, [prompts], None if shares is None else [shares], max_len, temperature, top_k, top_p,
                                          seed, repetition_penalty, logit_bias, min_new_tokens, grammar, guidance_scale,
-                                         None if negative_prompt is None else [list(negative_prompt)])[0]
+                                         None if negative_prompt is None else [list(negative_prompt)],
+                                         min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)[0]
 
 
 def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequence[str]]], shares=None, max_len=512,
                                   temperature=1.0, top_k=50, top_p: Optional[float] = None, seed=None, repetition_penalty=None,
                                   logit_bias=None, min_new_tokens=0, grammar=None, guidance_scale=None,
-                                  negative_prompts=None) -> List[List[str]]:
+                                  negative_prompts=None,
+                                  min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
     """generate_requests_guided whose requests each bring the variants of their prompt (sample_kvcache_transitions) and, in shares, one
     list of relative segment lengths per request (None = equal).  guidance_scale None: no request is guided and a generation serves
-    max_batch of them; otherwise every request is a pair and the limits of generate_requests_guided hold."""
+    max_batch of them; otherwise every request is a pair and the limits of generate_requests_guided hold.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     from mgea.decoder import RowSchedule
     from .guidance import unconditional_prompt
     from .transitions import start_thresholds, step_thresholds
@@ -602,6 +669,8 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
     pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
     biases = _per_prompt(logit_bias, n, "logit_bias")
     mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
+    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
+                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     guided = guidance_scale is not None
     scales = [float(v) for v in _per_prompt(guidance_scale if guided else 0.0, n, "guidance_scale")]
     negs = [None] * n if negative_prompts is None else list(negative_prompts)
@@ -633,7 +702,7 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
             RowSchedule(tuple(step_thresholds(budgets[i], sh)), 0)
     rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps_[i], repetition_penalty=pens[i], eos_id=eos,
                            max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i])
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
             for i in live}
     gen: Dict[int, List[int]] = {}
     per = eng.max_batch // 2 if guided else eng.max_batch

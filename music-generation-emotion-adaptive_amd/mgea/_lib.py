@@ -56,6 +56,11 @@ class RowSchedule(C.Structure):
     _fields_ = [("n_segments", C.c_int32), ("key", C.c_int32), ("threshold", C.c_int32 * 7), ("reserved", C.c_int32)]
 
 
+class RowTruncation(C.Structure):
+    """mgea_row_truncation: one batch row's min-p / typical-p / epsilon / eta settings (mgea_decoder_generate_rows_truncated)."""
+    _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -125,6 +130,10 @@ PROTOTYPES = {
     "mgea_decoder_guidance_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_generate_rows_scheduled": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
                                                       C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P, _P]),
+    "mgea_decoder_generate_rows_truncated": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
+                                                      C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P,
+                                                      C.POINTER(RowTruncation), _P]),
+    "mgea_decoder_truncation_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_schedule_info": (C.c_int, [_P, C.POINTER(_I64), _P]),
     "mgea_decoder_segments": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_set_window": (C.c_int, [_P, _I32, _I32, _I32, _P]),
@@ -184,6 +193,8 @@ PROTOTYPES = {
                                       _P, _P, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,
                                               _P, _P, _P]),
+    "mgea_op_sample_rows_truncated": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), C.POINTER(RowTruncation), _I64,
+                                                _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "mgea_op_attention_cls": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_bert_embed": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "mgea_op_gather_cls": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),

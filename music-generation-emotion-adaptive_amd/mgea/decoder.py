@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DecoderConfig, RowLogits, RowSampler, SamplerConfig, check, ptr
+from ._lib import DecoderConfig, RowLogits, RowSampler, RowTruncation, SamplerConfig, check, ptr
 
 _LAYER_TENSORS = ["ln1.weight", "ln1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
                   "attn.out_proj.bias", "ln2.weight", "ln2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
@@ -306,6 +306,45 @@ class KVWindow:
 
 
 @dataclasses.dataclass
+class Truncation:
+    """One batch row's truncation rules beyond top-k and top-p (mgea_row_truncation, include/mgea.h), HuggingFace's names and
+    semantics.  They apply after temperature, top-k and top-p, in this order, each to the softmax over what the stages before it kept:
+    min_p, typical_p (locally typical sampling; it may remove the most likely id), epsilon_cutoff, eta_cutoff.  None or 0 = off;
+    typical_p 1 is off too.  A greedy row (top_k 1) ignores them."""
+    min_p: Optional[float] = None
+    typical_p: Optional[float] = None
+    epsilon_cutoff: Optional[float] = None
+    eta_cutoff: Optional[float] = None
+
+    def values(self):
+        return tuple(0.0 if v is None else float(v) for v in (self.min_p, self.typical_p, self.epsilon_cutoff, self.eta_cutoff))
+
+    @property
+    def on(self) -> bool:
+        m, t, e, h = self.values()
+        return m > 0 or 0 < t < 1 or e > 0 or h > 0
+
+    def check(self, row: int = 0) -> None:
+        """ValueError naming the row for what the native call would refuse (MGEA_EINVAL)."""
+        m, t, e, h = self.values()
+        for name, v, closed in (("min_p", m, True), ("typical_p", t, True), ("epsilon_cutoff", e, False), ("eta_cutoff", h, False)):
+            v32 = float(np.float32(v)) if math.isfinite(v) else v
+            if not (math.isfinite(v) and 0 <= v32 and (v32 <= 1 if closed else v32 < 1)):
+                raise ValueError(f"row {row}: {name} {v} outside [0, 1{']' if closed else ')'}")
+
+    def record(self) -> RowTruncation:
+        m, t, e, h = self.values()
+        return RowTruncation(min_p=m, typical_p=t, epsilon_cutoff=e, eta_cutoff=h)
+
+    @classmethod
+    def of(cls, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> Optional["Truncation"]:
+        """The record of the four keyword arguments of the generate surface, or None when all of them are None."""
+        if min_p is None and typical_p is None and epsilon_cutoff is None and eta_cutoff is None:
+            return None
+        return cls(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+
+
+@dataclasses.dataclass
 class RowSampling:
     """One batch row's sampler settings (mgea_row_sampler, include/mgea.h) for DecoderEngine.generate_rows / ops.sample_rows.
     top_k None or 0 = no cut, 1 = greedy (the exact argmax, no temperature division); top_p None = no nucleus cut;
@@ -313,7 +352,8 @@ class RowSampling:
     generate() uses).  The row draws its step-t number from Philox counter (stream, t) under key seed.
     logit_bias (None, a dict id -> bias, a host array or a device tensor [vocab]; -inf bans an id) is added to the row's penalized
     logits at every step; min_new_tokens > 0 bans eos_id until the row has produced that many ids (mgea_row_logits).
-    grammar_state (None = the row is not constrained): the row's start state in the engine's TokenGrammar (DecoderEngine.set_grammar)."""
+    grammar_state (None = the row is not constrained): the row's start state in the engine's TokenGrammar (DecoderEngine.set_grammar).
+    truncation (None = none): the row's Truncation -- min-p, typical-p, epsilon and eta cutoff behind top-k and top-p."""
     temperature: float = 1.0
     top_k: Optional[int] = 50
     top_p: Optional[float] = None
@@ -327,9 +367,12 @@ class RowSampling:
     # the eleventh constructor argument, after min_new_tokens, and an ordinary attribute afterwards (dataclasses.replace keeps it).  An
     # InitVar rather than a field: dataclasses.fields() stays the ten sampler and logits settings the native records are packed from
     grammar_state: dataclasses.InitVar[Optional[int]] = None
+    # the twelfth, carried the same way
+    truncation: dataclasses.InitVar[Optional[Truncation]] = None
 
-    def __post_init__(self, grammar_state):
+    def __post_init__(self, grammar_state, truncation=None):
         self.grammar_state = grammar_state
+        self.truncation = truncation
 
     def check(self, row: int, vocab: int, n_steps: Optional[int] = None) -> None:
         """ValueError naming the row for what the native call would refuse (MGEA_EINVAL)."""
@@ -351,6 +394,10 @@ class RowSampling:
         m = int(self.min_new_tokens)
         if m < 0 or (n_steps is not None and m > n_steps):
             raise ValueError(f"row {row}: min_new_tokens {m} outside [0, {'n_steps' if n_steps is None else n_steps}]")
+        if self.truncation is not None:
+            if not isinstance(self.truncation, Truncation):
+                raise ValueError(f"row {row}: truncation must be a Truncation, got {type(self.truncation).__name__}")
+            self.truncation.check(row)
 
     def record(self, row: int) -> RowSampler:
         pen = self.repetition_penalty
@@ -400,6 +447,20 @@ def pack_row_logits(rows: Sequence[RowSampling], vocab: int, device, check: bool
             keep.append(dev)
         recs[b].bias_dev = dev.data_ptr()
     return recs, keep
+
+
+def pack_truncation(rows: Sequence[RowSampling]):
+    """The rows' Truncation records as the C array mgea_row_truncation[B] (rows without one: all off), or None when no row sets one --
+    the caller then makes the call without records.  Every record is checked (ValueError naming the row)."""
+    rows = list(rows)
+    if all(getattr(r, "truncation", None) is None for r in rows):
+        return None
+    recs = (RowTruncation * len(rows))()
+    for b, r in enumerate(rows):
+        if r.truncation is not None:
+            r.truncation.check(b)
+            recs[b] = r.truncation.record()
+    return recs
 
 
 @dataclasses.dataclass
@@ -972,12 +1033,14 @@ class DecoderEngine:
         Tp]) and lens from _prompt_ids, one RowSampling per row of B.  Packs the rows' records, logit records, forced ids and grammar
         start states (their ValueErrors, in that order), uploads on the engine's stream and makes the native call -- always
         mgea_decoder_generate_rows_scheduled, the superset, with NULL for what the caller does not use: it then runs exactly what
-        the narrower entry point would.  Returns all B rows [B, n_steps]; logprobs / choice_logprobs are None unless scored."""
+        the narrower entry point would -- or, when a row carries a Truncation, mgea_decoder_generate_rows_truncated, the same call
+        with the rows' truncation records.  Returns all B rows [B, n_steps]; logprobs / choice_logprobs are None unless scored."""
         B, Tp = ids.shape[-2:]
         recs = pack_rows(rows, self.vocab, n_steps)
         forced = pack_force_ids(force_ids, B, n_steps, self.vocab)
         lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
         starts = self._start_states(rows)
+        trecs = pack_truncation(rows)
         checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
         with self._on_stream():
             ids = ids.to(self.device).contiguous()
@@ -991,8 +1054,13 @@ class DecoderEngine:
             ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
             for t in keep:   # uploaded on the caller's stream, read by the engine's
                 t.record_stream(self.stream)
-            check(self.lib.mgea_decoder_generate_rows_scheduled(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
-                                                                srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
+            if trecs is None:
+                check(self.lib.mgea_decoder_generate_rows_scheduled(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
+                                                                    srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
+            else:
+                check(self.lib.mgea_decoder_generate_rows_truncated(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
+                                                                    srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), trecs,
+                                                                    self._sp()))
         self._cur_batch = B
         self._epoch += 1
         if check_ids and not checked:
@@ -1048,6 +1116,12 @@ class DecoderEngine:
         guide = (_lib.RowGuidance * B)(*[_lib.RowGuidance(shadow_row=u, scale=s) for u, s in zip(shadow, scales)])
         got = self._run_rows(ids, lens, rows_all, n_steps, forced_in, scored, guide, check_ids=check_ids, check_bias=check_bias)
         return got.first_rows(B if all_rows else n, scored)
+
+    def truncation_info(self):
+        """The truncated decode steps of the last generation and its rows with a truncation stage on (both 0 if it was not truncated)."""
+        out = (C.c_int64 * 2)()
+        check(self.lib.mgea_decoder_truncation_info(self.h, out))
+        return {"steps": int(out[0]), "rows": int(out[1])}
 
     def guidance_info(self):
         """The guidance pairs and the guided decode steps of the last generation (both 0 if it was not guided)."""

@@ -849,6 +849,64 @@ def sample_rows_grammar(logits: torch.Tensor, rows, grammar, states, step=0, wan
     return (ids, s_out, probs) if want_probs else (ids, s_out)
 
 
+def sample_rows_truncated(logits: torch.Tensor, rows, truncation=None, step=0, want_probs=False, presence=None, scored=False,
+                          forced=None, grammar=None, states=None):
+    """sample_rows() through the truncating sampler (mgea_op_sample_rows_truncated): behind temperature, top-k and top-p, row b applies
+    min-p, typical-p, the epsilon and the eta cutoff of its mgea.decoder.Truncation, in this order (include/mgea.h,
+    mgea_row_truncation).  truncation: None = the rows' own `truncation` attributes, one Truncation for every row, or one (or None)
+    per row; with none anywhere this is the op it extends.  scored / forced as in sample_rows_scored, grammar / states as in
+    sample_rows_grammar, in any combination.  Returns ids, then (logprobs, choice_logprobs) if scored, then states_out if a grammar
+    is given, then probs if want_probs -- a tuple unless ids stands alone."""
+    import dataclasses
+    from .decoder import Truncation, pack_row_logits, pack_rows, pack_truncation
+    rows = list(rows)
+    if truncation is not None:
+        per = [truncation] * len(rows) if isinstance(truncation, Truncation) else list(truncation)
+        if len(per) != len(rows):
+            raise ValueError(f"{len(rows)} sampler rows but {len(per)} truncation records")
+        rows = [dataclasses.replace(r, truncation=t) for r, t in zip(rows, per)]
+    lib = _lib.load()
+    logits = _dev(logits.float())
+    B, V = logits.shape
+    dev = logits.device
+    recs = pack_rows(rows, V)
+    if len(recs) != B:
+        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
+    trecs = pack_truncation(rows)
+    bits = None
+    if presence is not None or any(r.repetition_penalty != 1.0 for r in recs):
+        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
+        bits = torch.from_numpy(words.view(np.int32)).to(dev)
+    lrecs, keep = pack_row_logits(rows, V, dev)
+    ids = torch.empty(B, dtype=torch.int32, device=dev)
+    probs = torch.empty(B, V, dtype=torch.float32, device=dev) if want_probs else None
+    f = lp = ch = cls = nxt = s_in = s_out = None
+    if forced is not None and not scored:
+        raise ValueError("forced ids need scored=True")
+    if scored:
+        if forced is not None:
+            f = torch.as_tensor(forced).to(device=dev, dtype=torch.int32).contiguous()
+            if f.shape != (B,):
+                raise ValueError(f"forced must hold {B} ids, got {list(f.shape)}")
+        lp = torch.empty(B, dtype=torch.float32, device=dev)
+        ch = torch.empty(B, dtype=torch.float32, device=dev)
+    n_state = n_class = 0
+    if grammar is not None:
+        grammar.check(V)
+        st = np.asarray(list(states), dtype=np.int64).reshape(-1)
+        if st.shape != (B,) or st.min() < -1 or st.max() >= grammar.n_state:
+            raise ValueError(f"states must be {B} values in [-1, {grammar.n_state})")
+        cls = torch.from_numpy(grammar.class_of).to(dev)
+        nxt = torch.from_numpy(grammar.next).to(dev)
+        s_in = torch.from_numpy(st.astype(np.int32)).to(dev)
+        s_out = torch.empty(B, dtype=torch.int32, device=dev)
+        n_state, n_class = grammar.n_state, grammar.n_class
+    check(lib.mgea_op_sample_rows_truncated(ptr(logits), B, V, recs, ptr(bits), lrecs, trecs, int(step), ptr(ids), ptr(probs), ptr(f), ptr(lp),
+                                            ptr(ch), ptr(cls), ptr(nxt), n_state, n_class, ptr(s_in), ptr(s_out), stream_ptr()))
+    out = (ids,) + ((lp, ch) if scored else ()) + ((s_out,) if grammar is not None else ()) + ((probs,) if want_probs else ())
+    return out[0] if len(out) == 1 else out
+
+
 def tile_weights(w: torch.Tensor) -> torch.Tensor:
     """W [N,K] row-major -> the fragment-ordered layout the skinny GEMM reads (rows padded to 32)."""
     lib = _lib.load()
