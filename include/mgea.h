@@ -160,7 +160,12 @@ int mgea_decoder_generate_penalized(mgea_decoder* h, const int32_t* prompt_ids_d
  *   temperature > 0 and finite; 0 <= top_k <= vocab (0 = no cut, 1 = greedy); top_p as in mgea_sampler_config;
  *   repetition_penalty finite and > 0 (1 = none); eos_id -1 = none;
  *   max_new_tokens: the row's step budget, 0 <= max_new_tokens <= n_steps (0 = n_steps): the row finishes after that many ids;
- *   seed, stream: the row's Philox4x32-10 stream.  Row b draws its step-t number from counter {stream, t, 0, const} under key seed.
+ *   seed, stream: the row's Philox4x32-10 stream.  Row b draws its step-t number from counter {stream, t, 0, const} under key seed:
+ *     counter words {stream, low 32 bits of t, bits 32..63 of t, const} with const = 0x6d676561 (a generation's t is an int32 that
+ *     starts at 0, so word 2 is 0 there; the mgea_op_sample* calls take a 64-bit step), key words (low 32 bits of seed, high 32 bits
+ *     of seed), and u = (word 0 of the output >> 8) * 2^-24, a multiple of 2^-24 in [0, 1).  The row takes the id whose interval of
+ *     the cumulative distribution over the kept ids holds u.  The ORDER in which that cumulative sum runs over the ids is unspecified
+ *     (any fixed order gives the same distribution); only the distribution is promised, not the id a given u selects.
  * mgea_decoder_generate is the special case seed_b = seed, stream_b = b, no budget, the same settings on every row.  A row's ids
  * therefore depend on its own record, its prompt and on B (the batch size picks the GEMM / attention forms, whose sums run in other
  * orders) -- not on its index in the batch, nor on the other rows' records: the same (prompt, record) at rows 0 and 5 of a batch of B
@@ -744,8 +749,9 @@ int mgea_op_tile_weights_f16(const float* w_dev, int32_t N, int32_t K, void* out
  * c2[n] = sum_k beta[k] W[n,k] + bias[n] (bias_dev NULL: + 0), fp64 sums of exact products, rounded once. */
 int mgea_op_ln_vectors(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* bias_dev, int32_t N, int32_t K,
                        float* c1_out_dev, float* c2_out_dev, void* stream);
-/* Sampler on a logits matrix [B,V]; step selects the Philox counter.  probs_out_dev [B,V] or NULL
- * receives the pre-multinomial distribution. */
+/* Sampler on a logits matrix [B,V]; step selects the Philox counter: row b draws from counter {b, step, step >> 32, const} under key
+ * s->seed (the words, const = 0x6d676561, the key (seed low, seed high) and u = (word 0 >> 8) * 2^-24: mgea_row_sampler; the order of
+ * the cumulative sum is unspecified).  probs_out_dev [B,V] or NULL receives the pre-multinomial distribution. */
 int mgea_op_sample(const float* logits_dev, int32_t B, int32_t V, const mgea_sampler_config* s,
                    int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream);
 /* mgea_op_sample on the repetition-penalized logits (mgea_decoder_generate_penalized): presence_dev [B][ceil(V / 32)] uint32 holds
@@ -756,8 +762,8 @@ int mgea_op_sample_penalized(const float* logits_dev, int32_t B, int32_t V, cons
                              int32_t* ids_out_dev, float* probs_out_dev, void* stream);
 
 /* mgea_op_sample with one record per row (rows [B], host): row b reads rows[b] (max_new_tokens and eos_id are ignored) and draws from
- * counter {rows[b].stream, step, step >> 32, const} under key rows[b].seed.  presence_dev as in mgea_op_sample_penalized, needed only
- * if some row's repetition_penalty is not 1 (rows with penalty 1 are then unchanged: x * 1 and x / 1 are exact).  top_k == 1 rows take
+ * counter {rows[b].stream, step, step >> 32, const = 0x6d676561} under key rows[b].seed (low half, high half).  presence_dev as in
+ * mgea_op_sample_penalized, needed only if some row's repetition_penalty is not 1 (rows with penalty 1 are then unchanged: x * 1 and x / 1 are exact).  top_k == 1 rows take
  * the exact argmax of their (penalized) row, without the temperature division.  Synchronises `stream` before it returns. */
 int mgea_op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                         int64_t step, int32_t* ids_out_dev, float* probs_out_dev, void* stream);
