@@ -89,7 +89,17 @@ typedef struct mgea_decoder_config {
  * the lowest id); otherwise softmax(logits/temperature + (-1e10 outside top-k)) -- exactly top_k
  * entries survive like topk + scatter_ (api_cache.py:172-175), equal logits at the boundary by lowest id -- optionally cut
  * to the top_p nucleus, then one multinomial draw per row from a Philox4x32-10 stream keyed by
- * (seed, row, step) -- matches torch.multinomial in distribution only. */
+ * (seed, row, step) -- matches torch.multinomial in distribution only.
+ * The selection, over x = logits / temperature (one fp32 division per entry):
+ *   top-k (0 < top_k < vocab, otherwise off): every entry greater than the top_k-th largest is kept, then the entries EQUAL to it by
+ *     ascending id until exactly top_k are kept -- ties go to the lowest ids.  -inf is an ordinary value: with fewer than top_k
+ *     finite entries, -inf entries are among the kept, with probability exactly 0.
+ *   top-p (0 < top_p < 1, otherwise off), over what top-k kept: keep {x >= boundary}, the boundary being the largest x at which the
+ *     mass of {x >= boundary} reaches top_p (a mass equal to top_p has reached it) -- an entry is kept iff the mass of the strictly
+ *     larger entries is below top_p.  Equal entries are kept or dropped whole, and at least one id is kept.  The masses are the fp32
+ *     softmax of the kept entries floored to 2^-40, summed as integers, so the boundary does not depend on the order of summation;
+ *     against exact arithmetic it may move by entries whose cumulative mass lies within 2e-5 of top_p.
+ *   +0.0 ranks above -0.0 (the order is that of the entries' order-preserving integer keys). */
 typedef struct mgea_sampler_config {
     float    temperature;  /* > 0 */
     int32_t  top_k;        /* 0 = no top-k cut */
