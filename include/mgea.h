@@ -443,6 +443,53 @@ int mgea_decoder_generate_rows_truncated(mgea_decoder* h, const int32_t* prompt_
 /* out[0] the truncated decode steps and [1] the rows with a stage switched on of the last generation (both 0 if it was not truncated). */
 int mgea_decoder_truncation_info(mgea_decoder* h, int64_t* out /* [2] */);
 
+/* Emotion blends: weighted groups of rows mixed in the sampler (build-defined; the reference returns a distribution over emotions
+ * from predict_top_k_labels and has nothing downstream that uses more than its arg-max).  The N-row form of mgea_row_guidance: a
+ * GROUP is 2 to MGEA_BLEND_MAX_ROWS rows that name one LEADER -- the same prompt with another emotion's conditioning tokens each --,
+ * with member rows m_0 < m_1 < ... < m_{K-1} in ascending row index (the leader wherever it falls) and weights w_k that sum to 1.
+ * At every decode step, on the raw head logits of the K rows,
+ *   0. (blend) a_k = log_softmax(x_{m_k}), each row's maximum and log-sum-exp reduced exactly as the guidance mix reduces them;
+ *      g = w_0 a_0, then g += w_k a_k in ascending k, fp32 (deterministic from run to run); g replaces the logits of ALL K rows;
+ *   1.-7. the steps of the guided contract run on g: penalty, bias, grammar, EOS ban, / temperature, top-k, top-p, the truncation
+ *      stages, the Philox draw, forced ids and the scored outputs with x := g.
+ * One id is drawn per group and fed to all its rows, without a hand-off: before the first step the engine overwrites every
+ * non-leader member's sampler record (seed, Philox stream and budget included), truncation record, bias vector, grammar start state,
+ * forced ids and -- after the prompts have seeded them -- presence bitmap with its leader's.  A group's repetition-penalty set is
+ * therefore the LEADER's prompt plus the generated ids, and what the caller passes in a member's own records is validated and then
+ * ignored.  Everything else stays the row's own: its prompt, KV pages, ctx_len and window evictions.  Weights are any finite values
+ * (an affine combination: classifier-free guidance is the group (s, 1 - s); a negative weight moves away from a member). */
+#define MGEA_BLEND_MAX_ROWS 8
+typedef struct mgea_row_blend {
+    int32_t leader;   /* the row index of the row's group leader in [0, B); a leader names itself; -1 = the row is in no group */
+    float   weight;   /* finite; read only where leader >= 0 */
+} mgea_row_blend;
+
+/* mgea_decoder_generate_rows_truncated with one mgea_row_blend per row, blend [B] (host memory, read before the call returns).
+ * blend == NULL, or every leader == -1, IS mgea_decoder_generate_rows_truncated: the same launches, the same graphs, the same ids.
+ * Checked on the host before anything is enqueued (MGEA_EINVAL naming the row): leader in [-1, B); the named leader names itself; a
+ * group has 2 to MGEA_BLEND_MAX_ROWS rows; every weight of a grouped row is finite; a group's weights, summed in double, are within
+ * 1e-3 of 1 (a blend is an affine combination, not a hidden temperature); a grouped row is neither the conditional nor the shadow
+ * row of a guidance pair and has n_segments == 1.  Pairs and groups on disjoint rows of one batch are allowed: the step then has both
+ * launches.  Otherwise the generation is blended: every step is the unblended launch sequence with ONE more launch, the blend mix,
+ * between the head GEMM and the sampler; "blended" is part of the step-graph key (unblended calls capture and replay what they always
+ * did), and the leaders and weights live in device vectors the handle owns, so a request with other groups or weights replays the
+ * cached graphs.  A blended generation never takes the greedy form: all-greedy rows run as top_k == 1 records of the sampled form.
+ * ids_out_dev holds every row; a member's line equals its leader's.  Rows outside every group keep the ids they get in an unblended
+ * batch of that size and form.  A blended call that would be capped -- Tp + n_steps > max_ctx without a KV window -- is refused with
+ * MGEA_ECAPACITY, as a guided one is. */
+int mgea_decoder_generate_rows_blended(mgea_decoder* h, const int32_t* prompt_ids_dev /* [n_seg_max][B][Tp] */, const int32_t* lens_dev,
+                                       int32_t B, int32_t Tp, int32_t n_steps, const mgea_row_sampler* rows,
+                                       const mgea_row_logits* logits_rows /* NULL ok */,
+                                       const int32_t* start_states /* host [B], -1 = none; NULL ok */,
+                                       const mgea_row_guidance* guide /* host [B]; NULL ok */,
+                                       const mgea_row_schedule* sched /* host [B]; NULL ok */, int32_t n_seg_max,
+                                       const int32_t* forced_ids_dev /* NULL ok */, int32_t* ids_out_dev,
+                                       float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                       const mgea_row_truncation* trunc /* host [B]; NULL ok */,
+                                       const mgea_row_blend* blend /* host [B]; NULL ok */, void* stream);
+/* out[0] the groups, [1] the grouped rows and [2] the blended decode steps of the last generation (all 0 if it was not blended). */
+int mgea_decoder_blend_info(mgea_decoder* h, int64_t* out /* [3] */);
+
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
  * generate applied no penalty (a biased generation keeps the bitmaps too). */
@@ -824,6 +871,11 @@ int mgea_op_window_evict(int32_t* page_table_dev, int32_t max_pages, int32_t sin
  * both rows; every other row is left as it is.  partner_dev int32 [B], scale_dev fp32 [B] (device).  The caller guarantees the pair
  * rules of mgea_decoder_generate_rows_guided and finite logits; V <= 14336, else MGEA_EINVAL. */
 int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* partner_dev, const float* scale_dev, void* stream);
+/* The blend mix of a blended decode step (mgea_row_blend, step 0), alone and IN PLACE on logits_dev [B, V] fp32: for every row L with
+ * leader_dev[L] == L, the rows with leader_dev[b] == L in ascending order give g = sum_k weight_dev[m_k] * log_softmax(row m_k), added
+ * in that order, written into all of them; every other row is left as it is.  leader_dev int32 [B], weight_dev fp32 [B] (device).
+ * The caller guarantees the group rules of mgea_decoder_generate_rows_blended and finite logits; V <= 14336, else MGEA_EINVAL. */
+int mgea_op_blend_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* leader_dev, const float* weight_dev, void* stream);
 /* The two kernels of a scheduled generation (mgea_row_schedule), alone on caller buffers.  pool_dev: a KV pool
  * [n_layer][n_pages][K | V][H][64 x dh] of fp32 (f16 == 0) or fp16 (f16 == 1) elements in the page layouts of csrc/common.h; row b's
  * logical page 0 is physical page b when arith_batch > 0 and page_table_dev[b * max_pages] otherwise.  store_dev: the conditioning

@@ -164,9 +164,45 @@ def create_truncated_app(model, seq_len: int, temperature: float = 1.0, top_k: i
                       truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
+def create_blended_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                       constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None, top_emotions: int = 3,
+                       min_prob: float = 0.05, guidance_scale=None,
+                       min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+    """create_grammar_app for a piece conditioned on the text's emotion DISTRIBUTION, not on its arg-max alone (grammar defaults to
+    None here).  The text goes through emotion_analysis.inference.predict_top_k_labels(text, top_emotions); the labels with a
+    probability of at least min_prob are kept (the first always), each gives one EATS parameter set and one prompt -- the first
+    label's instruments, that label's [BPM] and [KEY_SIGNATURE] tokens (generate_music.blend.blend_prompts) --, and the request runs
+    as one group of rows that draws every id from sum_k w_k * logp(prompt k), w = the kept probabilities normalised
+    (generate_music.generate.sample_kvcache_blended; build-defined, the reference has no consumer of its top-k labels).
+    guidance_scale (None = none) adds the prompt without emotion tokens as one more member with weight 1 - guidance_scale and
+    multiplies the others by guidance_scale.  constrain="scale" keeps the FIRST label's key.  top_emotions (+ 1 with a scale) must be
+    in [1, 8] and fit into the model's max_batch (ValueError here).  The response carries X-Emotions (the kept labels,
+    comma-separated; X-Emotion is the first) and X-Blend-Weights (the members' weights, comma-separated).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
+    import math
+    from generate_music.blend import MAX_ROWS
+    top_emotions, min_prob = int(top_emotions), float(min_prob)
+    if guidance_scale is not None:
+        guidance_scale = float(guidance_scale)
+        if not (math.isfinite(guidance_scale) and guidance_scale >= 0):
+            raise ValueError(f"guidance_scale {guidance_scale} must be finite and >= 0")
+    group = top_emotions + (guidance_scale is not None)
+    if top_emotions < 1 or group > MAX_ROWS:
+        raise ValueError(f"top_emotions {top_emotions}{'' if guidance_scale is None else ' + the unconditional prompt'} outside [1, {MAX_ROWS}] rows")
+    if not (math.isfinite(min_prob) and 0 <= min_prob <= 1):
+        raise ValueError(f"min_prob {min_prob} outside [0, 1]")
+    if int(model.max_batch) < group:
+        raise ValueError(f"a blended request is a group of up to {group} rows: max_batch={model.max_batch} is too small")
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, guidance_scale=guidance_scale,
+                      blend=(top_emotions, min_prob),
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
+
+
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
                out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None, guidance_scale=None,
-               transitions=False, truncation=None):
+               transitions=False, truncation=None, blend=None):
     from mgea.decoder import Truncation
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
@@ -236,7 +272,11 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
         if transitions:   # one emotion per sentence; the first one's is the request's as far as the reference's steps go
             from generate_music.transitions import MAX_SEGMENTS
             sentences = inference.analyze_emotion_transitions(prompt)[:MAX_SEGMENTS]
-        label = sentences[0][1] if sentences else inference.predict(prompt)   # api_cache.py:189
+        emotions = []
+        if blend is not None:   # the text's most probable labels; those below min_prob go, the first never
+            top = inference.predict_top_k_labels(prompt, blend[0])
+            emotions = [top[0]] + [(lb, p) for lb, p in top[1:] if p >= blend[1]]
+        label = emotions[0][0] if emotions else sentences[0][1] if sentences else inference.predict(prompt)   # api_cache.py:189
         mapping = EATS.get_music_params(label)                                # :190
         bpm_tok = gen.closest_bpm_token(mapping["bpm"])                       # :194
         key = gen.normalize_key_signature(mapping["key"])                     # :195
@@ -261,6 +301,19 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
             extra["X-Best-Of"] = str(best_of)
             if means[best] > float("-inf"):   # (nothing generated -- seq_len within the prompt -- has no mean)
                 extra["X-Mean-Logprob"] = f"{means[best]:.6f}"
+        elif blend is not None:   # one prompt per kept label, all of them one group of rows
+            from generate_music.blend import blend_prompts, blend_weights
+            # (the first label's parameters are the request's own: get_music_params may draw, and member 0 is gen_prompt itself)
+            params = [mapping] + list(EATS.get_music_params([lb for lb, _ in emotions[1:]]))
+            members = blend_prompts(gen_prompt, params, unconditional=guidance_scale is not None)
+            weights = blend_weights([p for _, p in emotions], guidance_scale)
+            tokens = gen.sample_kvcache_blended(model, members, weights, max_len=seq_len, temperature=temperature, top_k=top_k,
+                                                top_p=top_p, repetition_penalty=repetition_penalty, device="cpu", logit_bias=bias,
+                                                min_new_tokens=int(min_new_tokens), grammar=tg, **trunc_kw)
+            extra["X-Emotions"] = ",".join(lb for lb, _ in emotions)
+            extra["X-Blend-Weights"] = ",".join(f"{w:.4f}" for w in weights)
+            if guidance_scale is not None:
+                extra["X-Guidance-Scale"] = f"{guidance_scale:g}"
         elif transitions:   # one prompt variant per sentence, switched at the segments' boundaries
             from generate_music.transitions import transition_prompts
             sentences = sentences or [(prompt, label)]

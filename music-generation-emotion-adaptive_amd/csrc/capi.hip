@@ -479,6 +479,10 @@ int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t*
     return launch_guidance_mix(logits_dev, B, V, partner_dev, scale_dev, (hipStream_t)stream);
 }
 
+int mgea_op_blend_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* leader_dev, const float* weight_dev, void* stream) {
+    return launch_blend_mix(logits_dev, B, V, leader_dev, weight_dev, (hipStream_t)stream);
+}
+
 int mgea_op_recondition(void* pool_dev, int32_t n_layer, int32_t n_pages, int32_t H, int32_t dh, int32_t f16, int32_t arith_batch,
                         const int32_t* page_table_dev, int32_t max_pages, void* store_dev, int32_t n_seg_max, int32_t slot_tokens,
                         int32_t* meta_dev, int32_t* len_dev, int32_t B, int32_t gather_seg, const int32_t* lens_dev,

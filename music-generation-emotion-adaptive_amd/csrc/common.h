@@ -303,6 +303,12 @@ int launch_sample(const SampleCall& c, hipStream_t st);
 // partner stay as they are.  partner / scale: device [B].  The caller guarantees that no row is the partner of two rows and that a
 // partner has no partner itself (one workgroup per pair is then the only one that touches its two rows).
 int launch_guidance_mix(float* logits, int B, int V, const int32_t* partner, const float* scale, hipStream_t st);
+// Emotion blends between grouped rows of logits [B, V], in place (blend.hip): for every row L with leader[L] == L, the rows b with
+// leader[b] == L in ascending order m_0 < ... < m_{K-1} give g = sum_k weight[m_k] * log_softmax(row m_k) (added in that order), which
+// goes into ALL K rows; rows whose leader is < 0 stay as they are.  leader / weight: device [B].  The caller guarantees that a named
+// leader names itself and that a group has at most MGEA_BLEND_MAX_ROWS rows (one workgroup per group is then the only one that touches
+// its rows).
+int launch_blend_mix(float* logits, int B, int V, const int32_t* leader, const float* weight, hipStream_t st);
 // Emotion transitions (recondition.hip; the rule and the store's layout: include/mgea.h, mgea_row_schedule / mgea_op_recondition).
 // gather: positions [0, lens[b]) (lens NULL: Tp) of logical page 0 of every row, layer and head -> the slots of segment `seg` of the
 // conditioning store, and the layout words / the rows' lengths -> meta [4] / cond_len [B].  apply: the launch that opens a scheduled

@@ -93,7 +93,7 @@ struct mgea_decoder {
     // The handle's other HIP resources, declared behind the device groups, so that they go first (members die in reverse order):
     // the graphs, the pinned staging arrays and the events, then the device memory.
     Event stage_free;        // recorded after the copy out of samp_stage / gram_stage: they may be rewritten once it has completed
-    PinnedGroup pinned;      // samp_stage, gram_stage, guide_stage, cond_stage, trunc_stage
+    PinnedGroup pinned;      // samp_stage, gram_stage, guide_stage, cond_stage, trunc_stage, blend_stage
 
     // KV pool
     KvPool kv{};
@@ -168,6 +168,13 @@ struct mgea_decoder {
     // epsilon / eta records.  Allocated at create behind the guidance vectors and filled per call through the pinned trunc_stage (free
     // under stage_free like the records), so the truncated graphs hold a stable pointer and a request with other values replays them.
     mgea_row_truncation *trunc_dev = nullptr, *trunc_stage = nullptr;
+    // Emotion blends (mgea_decoder_generate_rows_blended; blend.hip): blend_leader [max_batch] holds every row's group leader (-1 = in no
+    // group), blend_weight [max_batch] its weight.  Allocated at create behind the truncation records and filled per call through the
+    // pinned blend_stage ([max_batch] leaders, then [max_batch] weights; free under stage_free like the records), so the blended graphs
+    // hold stable pointers and a request with other groups or weights replays them.
+    int32_t* blend_leader = nullptr;
+    float* blend_weight = nullptr;
+    int32_t* blend_stage = nullptr;
     // Emotion transitions (mgea_decoder_generate_rows_scheduled; recondition.hip).  Everything here belongs to dev_cond and is allocated by
     // the first scheduled call, never by create: cond_store holds the K | V of positions [0, len_b) of every prompt variant (cond_bytes
     // of it; a call that needs more synchronises, drops the scheduled graphs and regrows the whole group), cond_sched [max_batch] the
@@ -199,7 +206,7 @@ struct mgea_decoder {
         bool penalized = false;   // it applied a penalty (or a bias): presence holds its rows
         bool scheduled = false;   // it was scheduled: cond_cur_seg / cond_switches hold its rows
         int64_t graph_replays = 0, scored_steps = 0, penalized_steps = 0, biased_steps = 0, gram_steps = 0, guide_pairs = 0, guide_steps = 0,
-                sched_steps = 0, trunc_steps = 0, trunc_rows = 0;
+                sched_steps = 0, trunc_steps = 0, trunc_rows = 0, blend_groups = 0, blend_rows = 0, blend_steps = 0;
     } last;
     // what mgea_decoder_stats reports of the handle's lifetime, besides the graph cache's own two figures
     struct Counters { int64_t graph_nodes = 0, prefill16_forwards = 0; } n;
@@ -527,7 +534,8 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
     const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, hi.ids, hi.stride, k.pv.eos_id, k.pd};
     const TailArgs t = tail_args(h, s, k.primed ? k.qkv0 : nullptr);
     if (k.kind.form == StepForm::GREEDY) {
-        MGEA_REQUIRE(!k.kind.scored && !k.kind.guided, MGEA_EINVAL, "internal: a scored or guided step never takes the greedy form");
+        MGEA_REQUIRE(!k.kind.scored && !k.kind.guided && !k.kind.blended, MGEA_EINVAL,
+                     "internal: a scored, guided or blended step never takes the greedy form");
         if (k.primed)
             PROF(PC_SAMPLE, launch_argmax_advance_embed(h->pmax_val, h->pmax_idx, n_partials, t, h->sampled, B, st));
         else if (n_partials > 0)
@@ -538,6 +546,8 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
     }
     // guided: every pair's two logits rows become the pair's mixed row, in place, before the sampler reads them
     if (k.kind.guided) PROF(PC_SAMPLE, launch_guidance_mix(lg, B, V, h->guide_partner, h->guide_scale, st));
+    // blended: every group's logits rows become the group's mixed row (pairs and groups share no row: either order gives the same rows)
+    if (k.kind.blended) PROF(PC_SAMPLE, launch_blend_mix(lg, B, V, h->blend_leader, h->blend_weight, st));
     uint32_t* pres = form_has_presence(k.kind.form) ? h->presence : nullptr;
     SampleCall sc{};
     sc.logits = lg; sc.B = B; sc.V = V;
@@ -659,6 +669,7 @@ int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
 // windowed: the step opens with the KV window's evict launch, in front of every append of the step (the rule and why it keeps the
 // previous tail's layer-0 K | V alive: kv_window.hip); the node does not depend on the step's form.
 // guided: the step mixes the pairs' logits rows between the head and the sampler (enqueue_tail); one more node, whatever the pairs are.
+// blended: likewise the groups' logits rows, in a launch of its own behind the pairs'; one more node, whatever the groups are.
 // scheduled: behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip): a row whose segment changes
 // gets the new variant's K | V over positions [0, len_b) of its pages before anything of the step reads them; one more node, whatever
 // the records say.  (The previous tail's layer-0 K | V of the fed token sits at position ctx_len >= len_b: never in its way.)
@@ -1094,13 +1105,17 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         h->pinned.alloc(&h->guide_stage, 2 * nb) ||
         // (and the truncation records after the guidance pairs)
         g.alloc(&h->trunc_dev, cfg->max_batch * sizeof(mgea_row_truncation)) ||
-        h->pinned.alloc(&h->trunc_stage, cfg->max_batch * sizeof(mgea_row_truncation)))
+        h->pinned.alloc(&h->trunc_stage, cfg->max_batch * sizeof(mgea_row_truncation)) ||
+        // (and the blend groups after the truncation records)
+        g.alloc(&h->blend_leader, nb) || g.alloc(&h->blend_weight, cfg->max_batch * sizeof(float)) ||
+        h->pinned.alloc(&h->blend_stage, 2 * nb))
         return fail(MGEA_ENOMEM, "state allocation failed");
     if (hipMemset(h->forced, 0xff, nhist * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->guide_partner, 0xff, nb) != hipSuccess || hipMemset(h->guide_scale, 0, cfg->max_batch * sizeof(float)) != hipSuccess ||
         hipMemset(h->attn_split.count, 0, MGEA_ATTN_SPLIT_ITEMS * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->gram_state, 0xff, nb) != hipSuccess ||
         hipMemset(h->trunc_dev, 0, cfg->max_batch * sizeof(mgea_row_truncation)) != hipSuccess ||
+        hipMemset(h->blend_leader, 0xff, nb) != hipSuccess || hipMemset(h->blend_weight, 0, cfg->max_batch * sizeof(float)) != hipSuccess ||
         hipMemset(h->page_table, 0, nb * h->max_pages) != hipSuccess || hipMemset(h->ctx_len, 0, nb) != hipSuccess ||
         hipMemset(h->done, 0, nb) != hipSuccess || hipMemset(h->row_step, 0, nb) != hipSuccess ||
         hipMemset(h->cur_ids, 0, nb) != hipSuccess || hipMemset(h->n_done, 0, 16) != hipSuccess ||
@@ -1197,7 +1212,8 @@ GenLimits gen_limits(const mgea_decoder* h) {
     return GenLimits{c.vocab, c.max_batch, c.max_ctx, c.block_mode, h->win_S, h->win_R, h->win_max_steps, h->gram_n_state};
 }
 
-// A guidance shadow row runs on its conditional row's inputs -- same inputs, same id -- and this is the one place that hands them over.
+// A guidance shadow row runs on its conditional row's inputs -- same inputs, same id --, a non-leader member of a blend group on its
+// leader's, and this is the one place that hands them over.
 // `part` names what the caller has just filled for the callers' rows:
 //   PRESENCE  the seeded bitmaps: a pair's set is the conditional prompt plus the generated ids, and both tails add the same ids
 //   RECORDS   the pinned staging arrays: the sampler record -- seed, Philox stream, budget and all --, the grammar start state and the
@@ -1206,13 +1222,17 @@ GenLimits gen_limits(const mgea_decoder* h) {
 //   FORCED    the engine's forced-id rows: the shadow is told the ids its conditional row is told
 enum class Mirror { PRESENCE, RECORDS, BIAS, FORCED };
 int mirror_shadow_rows(mgea_decoder* h, const GenRequest& q, const GenPlan& p, Mirror part, hipStream_t st) {
-    if (!p.kind.guided) return MGEA_OK;
+    if (!p.kind.guided && !p.kind.blended) return MGEA_OK;
     const size_t V = (size_t)h->cfg.vocab, pw = (size_t)presence_words(h->cfg.vocab);
     const mgea_decoder::Hist hi = h->hist(p.kind.windowed);
     const size_t hs = (size_t)hi.stride;
-    for (int b = 0; b < q.B; ++b) {
-        const int32_t u = q.guide[b].shadow_row;
-        if (u < 0) continue;
+    // row u takes what row b has: u = b's shadow row, or u = a member of the group b leads (a row is never both: plan_generation)
+    for (int u = 0; u < q.B; ++u) {
+        int b = -1;
+        if (p.kind.blended && q.blend[u].leader >= 0 && q.blend[u].leader != u) b = q.blend[u].leader;
+        for (int c = 0; p.kind.guided && b < 0 && c < q.B; ++c)
+            if (q.guide[c].shadow_row == u) b = c;
+        if (b < 0) continue;
         switch (part) {
         case Mirror::PRESENCE:
             MGEA_CHECK_HIP(hipMemcpyAsync(h->presence + (size_t)u * pw, h->presence + (size_t)b * pw, pw * sizeof(uint32_t),
@@ -1311,6 +1331,15 @@ int gen_stage(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_
             }
             MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_partner, h->guide_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
             MGEA_CHECK_HIP(hipMemcpyAsync(h->guide_scale, scale_stage, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
+        }
+        if (p.kind.blended) {   // the groups and their weights: the blended graphs read the engine's two vectors
+            float* weight_stage = reinterpret_cast<float*>(h->blend_stage + c.max_batch);
+            for (int b = 0; b < B; ++b) {
+                h->blend_stage[b] = q.blend[b].leader;
+                weight_stage[b] = q.blend[b].leader >= 0 ? q.blend[b].weight : 0.f;
+            }
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->blend_leader, h->blend_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->blend_weight, weight_stage, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
         }
         if (p.kind.scheduled) {
             for (int b = 0; b < B; ++b) h->cond_stage[b] = q.sched[b];
@@ -1420,6 +1449,9 @@ int do_generate(mgea_decoder* h, const GenRequest& q, hipStream_t st) {
     last.sched_steps = p.kind.scheduled ? launched : 0;
     last.trunc_steps = p.truncated ? launched : 0;
     last.trunc_rows = p.truncated ? p.n_trunc : 0;
+    last.blend_groups = p.n_groups;
+    last.blend_rows = p.n_blend_rows;
+    last.blend_steps = p.kind.blended ? launched : 0;
     h->last = last;
     return gen_finish(h, q, p, launched, st);
 }
@@ -1437,7 +1469,7 @@ int generate_uniform(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32
     return do_generate(h, q, (hipStream_t)stream);
 }
 
-// The six mgea_decoder_generate_rows* entry points: what all of them take, then their one prologue.  What the records alone decide
+// The mgea_decoder_generate_rows* entry points: what all of them take, then their one prologue.  What the records alone decide
 // is checked before the handle is looked at (plan_generation checks it again, with the sampler records).
 GenRequest rows_request(const char* who, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
                         const mgea_row_sampler* rows, const mgea_row_logits* lrows, int32_t* ids_out_dev) {
@@ -1539,6 +1571,28 @@ int mgea_decoder_generate_rows_truncated(mgea_decoder* h, const int32_t* prompt_
     q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max; q.trunc = trunc;
     q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
     return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_generate_rows_blended(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                       int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                       const int32_t* start_states, const mgea_row_guidance* guide, const mgea_row_schedule* sched,
+                                       int32_t n_seg_max, const int32_t* forced_ids_dev, int32_t* ids_out_dev, float* logprobs_out_dev,
+                                       float* choice_logprobs_out_dev, const mgea_row_truncation* trunc, const mgea_row_blend* blend,
+                                       void* stream) {
+    GenRequest q = rows_request(blend   ? "decoder_generate_rows_blended"
+                                : trunc ? "decoder_generate_rows_truncated"
+                                        : "decoder_generate_rows_scheduled",
+                                prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev);
+    q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max; q.trunc = trunc; q.blend = blend;
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_blend_info(mgea_decoder* h, int64_t* out) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_blend_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->last.blend_groups; out[1] = h->last.blend_rows; out[2] = h->last.blend_steps;
+    return MGEA_OK;
 }
 
 int mgea_decoder_truncation_info(mgea_decoder* h, int64_t* out) {

@@ -50,12 +50,13 @@ inline bool form_has_bias(StepForm f) { return f == StepForm::BIASED || f == Ste
 //   guided     the guidance-mix launch over the logits, between the head and the sampler (guidance.hip; never GREEDY)
 //   scheduled  behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip)
 //   truncated  the truncating sampler over the rows' mgea_row_truncation records (BIASED or GRAMMAR form only)
+//   blended    the blend-mix launch over the logits, next to the guidance mix (blend.hip; never GREEDY)
 struct StepKind {
     StepForm form;
-    bool scored = false, windowed = false, guided = false, scheduled = false, truncated = false;
+    bool scored = false, windowed = false, guided = false, scheduled = false, truncated = false, blended = false;
     bool operator==(const StepKind& o) const {
         return form == o.form && scored == o.scored && windowed == o.windowed && guided == o.guided && scheduled == o.scheduled &&
-               truncated == o.truncated;
+               truncated == o.truncated && blended == o.blended;
     }
 };
 
@@ -180,6 +181,48 @@ inline int check_row_truncation(const mgea_row_truncation* trunc, const mgea_row
     return MGEA_OK;
 }
 
+// host check of blend[0, B) (mgea_decoder_generate_rows_blended): MGEA_EINVAL naming the first bad row; *n_groups = the groups, *n_rows
+// = the grouped rows.  guide and sched (each NULL = absent) have passed their own checks.
+inline int check_row_blend(const mgea_row_blend* blend, int B, const mgea_row_guidance* guide, const mgea_row_schedule* sched, int* n_groups,
+                           int* n_rows) {
+    const char* who = "decoder_generate_rows_blended";
+    *n_groups = *n_rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t l = blend[b].leader;
+        MGEA_REQUIRE(l >= -1 && l < B, MGEA_EINVAL, "%s: row %d: leader %d outside [-1, %d)", who, b, l, B);
+        if (l < 0) continue;
+        MGEA_REQUIRE(blend[l].leader == l, MGEA_EINVAL, "%s: row %d: its leader row %d does not name itself (leader %d)", who, b, l,
+                     blend[l].leader);
+        MGEA_REQUIRE(std::isfinite(blend[b].weight), MGEA_EINVAL, "%s: row %d: weight %g must be finite", who, b, (double)blend[b].weight);
+    }
+    std::vector<char> paired((size_t)B, 0);   // conditional and shadow rows of the guidance pairs
+    for (int b = 0; guide && b < B; ++b)
+        if (guide[b].shadow_row >= 0 && guide[b].shadow_row < B) paired[(size_t)b] = paired[(size_t)guide[b].shadow_row] = 1;
+    std::vector<int> size((size_t)B, 0);
+    std::vector<double> sum((size_t)B, 0.0);
+    for (int b = 0; b < B; ++b) {
+        const int32_t l = blend[b].leader;
+        if (l < 0) continue;
+        MGEA_REQUIRE(!paired[(size_t)b], MGEA_EINVAL, "%s: row %d is in a blend group and in a guidance pair", who, b);
+        MGEA_REQUIRE(!sched || sched[b].n_segments == 1, MGEA_EINVAL, "%s: row %d is in a blend group and has %d segments (a grouped row has one)",
+                     who, b, sched ? sched[b].n_segments : 1);
+        size[(size_t)l] += 1;
+        MGEA_REQUIRE(size[(size_t)l] <= MGEA_BLEND_MAX_ROWS, MGEA_EINVAL, "%s: row %d: the group of leader row %d has more than %d rows", who, b,
+                     l, MGEA_BLEND_MAX_ROWS);
+        sum[(size_t)l] += (double)blend[b].weight;
+        *n_rows += 1;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (blend[b].leader != b) continue;
+        MGEA_REQUIRE(size[(size_t)b] >= 2, MGEA_EINVAL, "%s: row %d: a group of %d row (a group has 2 to %d)", who, b, size[(size_t)b],
+                     MGEA_BLEND_MAX_ROWS);
+        MGEA_REQUIRE(std::fabs(sum[(size_t)b] - 1.0) <= 1e-3, MGEA_EINVAL,
+                     "%s: row %d: the weights of its group sum to %g, not 1 (a blend is an affine combination)", who, b, sum[(size_t)b]);
+        *n_groups += 1;
+    }
+    return MGEA_OK;
+}
+
 // Everything a generation is asked for.  prompt_ids, lens, forced and the three outputs are DEVICE memory, as in the C ABI; the records
 // are host memory.
 struct GenRequest {
@@ -201,6 +244,7 @@ struct GenRequest {
     const mgea_row_schedule* sched = nullptr;
     int n_seg_max = 1;
     const mgea_row_truncation* trunc = nullptr;   // [B] the rows' truncation records (any non-greedy row with a stage on makes it truncated)
+    const mgea_row_blend* blend = nullptr;        // [B] the rows' blend groups (any leader >= 0 makes it blended)
     const int32_t* forced = nullptr;        // [B][n_steps] ids the rows must take, -1 = free (scored only)
     int32_t* ids_out = nullptr;             // [B][n_steps]
     float* logprobs_out = nullptr;          // [B][n_steps]; not NULL makes the generation scored
@@ -228,6 +272,8 @@ struct GenPlan {
     int n_trunc;           // truncated rows: non-greedy rows with a truncation stage switched on
     bool truncated;        // n_trunc > 0: the steps run the truncating sampler
     int reserve;           // tokens of KV pages every row gets
+    int n_groups;          // blend groups: leaders
+    int n_blend_rows;      // rows in a blend group, leaders included
 };
 
 // Every host check of a generation, then its plan.  Calls no HIP function and touches no handle.
@@ -268,10 +314,15 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
             MGEA_REQUIRE(p.n_sched == 0 || Tp <= MGEA_KV_PAGE_TOKENS, MGEA_ECAPACITY,
                          "decoder_generate_rows_scheduled: prompt width %d exceeds one page of %d tokens", Tp, MGEA_KV_PAGE_TOKENS);
         }
+        if (q.blend) MGEA_TRY(check_row_blend(q.blend, B, q.guide, q.sched, &p.n_groups, &p.n_blend_rows));
         // A guided pair must run the same steps: rows stopped where their pages end (launch_clamp_budgets) would get budgets of their own
         // prompt lengths.  Under a window nothing is clamped, and each row of a pair evicts on its own schedule.
         MGEA_REQUIRE(p.n_pairs == 0 || windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY,
                      "decoder_generate_rows_guided: prompt width %d + %d steps exceed max_ctx %d (a guided generation is never capped; set a window)",
+                     Tp, n_steps, c.max_ctx);
+        // (and so must the rows of a blend group)
+        MGEA_REQUIRE(p.n_groups == 0 || windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY,
+                     "decoder_generate_rows_blended: prompt width %d + %d steps exceed max_ctx %d (a blended generation is never capped; set a window)",
                      Tp, n_steps, c.max_ctx);
         // every row needs lens[b] + its budget; rows past the reservation are stopped there on the device (launch_clamp_budgets)
         // (a window holds every row for as long as it runs: nothing to stop)
@@ -288,16 +339,16 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
     p.may_stop_early = rr.may_stop_early || p.capped;
     p.any_penalty = rr.any_penalty;
     p.biased = rr.form == StepForm::BIASED;
-    const bool scored = q.scored(), guided = p.n_pairs > 0;
-    // scoring and guidance need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
+    const bool scored = q.scored(), guided = p.n_pairs > 0, blended = p.n_groups > 0;
+    // scoring, guidance and blends need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
     // the lowest id)
     // truncation lives in the <PENALTY, BIAS> sampler family, as the grammar does: the BIASED form at least (bitmaps over every row, a
     // penalty of 1 and a record without bias_on change nothing)
     const StepForm form = p.grammar           ? StepForm::GRAMMAR
                           : p.truncated     ? StepForm::BIASED
-                          : (scored || guided) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED
+                          : (scored || guided || blended) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED
                                               : rr.form;
-    p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0, p.truncated};
+    p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0, p.truncated, blended};
     *out = p;
     return MGEA_OK;
 }

@@ -31,7 +31,7 @@ __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab
            "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
            "generate_batch_biased", "generate_sequence_biased", "sample_kvcache_grammar", "generate_batch_grammar", "sample_kvcache_truncated",
            "generate_sequence_truncated", "generate_batch_truncated", "score_sequence", "generate_best_of", "pick_best",
-           "mean_logprobs", "sample_kvcache_guided", "generate_requests_guided"]
+           "mean_logprobs", "sample_kvcache_guided", "generate_requests_guided", "sample_kvcache_blended", "generate_requests_blended"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
 tok2id: Dict[str, int] = {}
@@ -715,6 +715,92 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
         out = eng.generate_scheduled([ids[i] for i in part], [rows[i] for i in part], [scheds[i] for i in part], steps,
                                      negative_prompts=[neg_ids[i] for i in part] if guided else None,
                                      guidance_scale=[scales[i] for i in part]).cpu().tolist()
+        for i, row in zip(part, out):
+            gen[i] = [g for g in row if g >= 0]
+    return [[id2tok[t] for t in ids[i][0] + gen.get(i, [])] for i in range(n)]
+
+
+def sample_kvcache_blended(model, prompts: Sequence[Sequence[str]], weights: Sequence[float], max_len=512, temperature=1.0, top_k=50,
+                           top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, device="cpu",
+                           seed: Optional[int] = None, logit_bias=None, min_new_tokens: int = 0, grammar=None,
+                           min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
+    """sample_kvcache_grammar for one piece conditioned on several emotions at once.  prompts: 1 to 8 variants of ONE request
+    (generate_music.blend.blend_prompts: the same instruments, another emotion's [BPM] / [KEY_SIGNATURE] tokens each, optionally the
+    prompt without them as the last), weights: one finite weight per variant, summing to 1 (blend.blend_weights).  The request runs
+    as a group of rows and every id is drawn from sum_k weights[k] * logp(prompts[k]), renormalised; everything else -- penalty (over
+    prompts[0] and the generated ids), bias, minimum length, grammar, the seed's Philox stream -- is the request's, applied to the
+    blended distribution.  Returns prompts[0] + the generated tokens.  Build-defined (DecoderEngine.generate_blended); the model needs
+    max_batch >= len(prompts).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation)."""
+    return generate_requests_blended(model, [prompts], [weights], max_len, temperature, top_k, top_p, repetition_penalty, seed, logit_bias,
+                                     min_new_tokens, grammar, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                                     eta_cutoff=eta_cutoff)[0]
+
+
+def generate_requests_blended(model, prompt_groups: Sequence[Sequence[Sequence[str]]], weights, max_len=512, temperature=1.0, top_k=50,
+                              top_p: Optional[float] = None, repetition_penalty=None, seed=None, logit_bias=None, min_new_tokens=0,
+                              grammar=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
+    """generate_requests whose requests each bring a group of prompt variants and one weight per variant (sample_kvcache_blended): a
+    request of K variants is K rows, and one generation serves as many whole requests as fit into max_batch.  Every other argument is
+    a scalar or a list with one value per request.  Like a guided request, a blended one that would run past the engine's context
+    is refused (RuntimeError) also where only its budget would be cut: a blended generation is never capped (a KV window lifts the
+    limit).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
+    in this order (mgea.decoder.Truncation)."""
+    m = _as_model(model)
+    eng = m._need()
+    n = len(prompt_groups)
+    groups = [[list(v) for v in g] for g in prompt_groups]
+    weights = list(weights)
+    if len(weights) != n:
+        raise ValueError(f"weights: {len(weights)} lists for {n} requests")
+    for i, g in enumerate(groups):
+        if not g:
+            raise ValueError(f"request {i}: no prompt")
+        if len(weights[i]) != len(g):
+            raise ValueError(f"request {i}: {len(weights[i])} weights for {len(g)} prompts")
+        if len(g) > eng.max_batch:
+            raise ValueError(f"request {i}: a group of {len(g)} rows needs a model with max_batch >= {len(g)}")
+    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
+    temps = _per_prompt(temperature, n, "temperature")
+    ks = _per_prompt(top_k, n, "top_k")
+    ps = _per_prompt(top_p, n, "top_p")
+    seeds = _per_prompt(seed, n, "seed")
+    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
+    biases = _per_prompt(logit_bias, n, "logit_bias")
+    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
+    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
+                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
+    ids = [[[tok2id[t] for t in v] for v in g] for g in groups]   # KeyError for an unknown token, like api_cache.py:162
+    budgets = [L - len(g[0]) for L, g in zip(max_lens, ids)]
+    for i in range(n):
+        if mins[i] < 0:
+            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
+    eos = tok2id.get("[END_SEQUENCE]", -1)
+    live = [i for i in range(n) if budgets[i] > 0]
+    gstates = [None] * n
+    if grammar is not None:
+        from .grammar import start_state
+        _use_grammar(eng, grammar)
+        gstates = [start_state(grammar, g[0]) for g in ids]
+    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
+                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
+            for i in live}
+    gen: Dict[int, List[int]] = {}
+    c0 = 0
+    while c0 < len(live):   # as many whole requests as fit into max_batch rows
+        part, used = [], 0
+        while c0 + len(part) < len(live) and used + len(ids[live[c0 + len(part)]]) <= eng.max_batch:
+            used += len(ids[live[c0 + len(part)]])
+            part.append(live[c0 + len(part)])
+        c0 += len(part)
+        steps = max(budgets[i] for i in part)
+        width = max(len(v) for i in part for v in ids[i])
+        if _no_window(eng) and width + steps > eng.max_ctx:
+            raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
+        out = eng.generate_blended([ids[i] for i in part], [list(weights[i]) for i in part], [rows[i] for i in part], steps).cpu().tolist()
         for i, row in zip(part, out):
             gen[i] = [g for g in row if g >= 0]
     return [[id2tok[t] for t in ids[i][0] + gen.get(i, [])] for i in range(n)]

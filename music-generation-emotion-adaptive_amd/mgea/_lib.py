@@ -61,6 +61,14 @@ class RowTruncation(C.Structure):
     _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
 
 
+class RowBlend(C.Structure):
+    """mgea_row_blend: one batch row's blend group and weight (mgea_decoder_generate_rows_blended)."""
+    _fields_ = [("leader", C.c_int32), ("weight", C.c_float)]
+
+
+BLEND_MAX_ROWS = 8
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -134,6 +142,10 @@ PROTOTYPES = {
                                                       C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P,
                                                       C.POINTER(RowTruncation), _P]),
     "mgea_decoder_truncation_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "mgea_decoder_generate_rows_blended": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
+                                                    C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P,
+                                                    C.POINTER(RowTruncation), C.POINTER(RowBlend), _P]),
+    "mgea_decoder_blend_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_schedule_info": (C.c_int, [_P, C.POINTER(_I64), _P]),
     "mgea_decoder_segments": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_set_window": (C.c_int, [_P, _I32, _I32, _I32, _P]),
@@ -189,6 +201,7 @@ PROTOTYPES = {
     "mgea_op_sample_rows_scored": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _I64, _P, _P, _P, _P, _P, _P]),
     "mgea_op_window_evict": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "mgea_op_guidance_mix": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "mgea_op_blend_mix": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
     "mgea_op_recondition": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
                                       _P, _P, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,

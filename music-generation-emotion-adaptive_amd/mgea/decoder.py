@@ -594,6 +594,105 @@ def pack_guided(prompts, negative_prompts, rows, guidance_scale, max_batch: int,
     return all_prompts, all_rows, shadow, scales, force_ids
 
 
+BLEND_MAX_ROWS = _lib.BLEND_MAX_ROWS
+
+
+def check_blend(leader, weights, B: int, shadow_rows=None) -> None:
+    """The group rules of mgea_decoder_generate_rows_blended (include/mgea.h, mgea_row_blend) as ValueErrors naming the row: leader in
+    [-1, B), a named leader names itself, a group has 2 to BLEND_MAX_ROWS rows, a grouped row's weight is finite (as the float32 the
+    record holds), a group's weights sum to 1 within 1e-3, and -- with the batch's shadow_rows (check_guidance) -- a grouped row is
+    neither the conditional nor the shadow row of a guidance pair.  Pure host code."""
+    leader = [int(l) for l in leader]
+    if len(leader) != B or len(weights) != B:
+        raise ValueError(f"blend: {len(leader)} leaders and {len(weights)} weights for {B} rows")
+    f32_max = float(np.finfo(np.float32).max)
+    for b, l in enumerate(leader):
+        if not -1 <= l < B:
+            raise ValueError(f"row {b}: leader {l} outside [-1, {B})")
+        if l < 0:
+            continue
+        if leader[l] != l:
+            raise ValueError(f"row {b}: its leader row {l} does not name itself (leader {leader[l]})")
+        w = float(weights[b])
+        if not (math.isfinite(w) and abs(w) <= f32_max):
+            raise ValueError(f"row {b}: weight {weights[b]} must be finite")
+    paired = set()
+    for b, u in enumerate([] if shadow_rows is None else [int(u) for u in shadow_rows]):
+        if u >= 0:
+            paired.update((b, u))
+    size, total = {}, {}
+    for b, l in enumerate(leader):
+        if l < 0:
+            continue
+        if b in paired:
+            raise ValueError(f"row {b} is in a blend group and in a guidance pair")
+        size[l] = size.get(l, 0) + 1
+        if size[l] > BLEND_MAX_ROWS:
+            raise ValueError(f"row {b}: the group of leader row {l} has more than {BLEND_MAX_ROWS} rows")
+        total[l] = total.get(l, 0.0) + float(np.float32(weights[b]))
+    for l in sorted(size):
+        if size[l] < 2:
+            raise ValueError(f"row {l}: a group of {size[l]} row (a group has 2 to {BLEND_MAX_ROWS})")
+        if not abs(total[l] - 1.0) <= 1e-3:
+            raise ValueError(f"row {l}: the weights of its group sum to {total[l]:g}, not 1 (a blend is an affine combination)")
+
+
+def pack_blended(prompt_groups, weights, rows, max_batch: int, force_ids=None):
+    """The host half of DecoderEngine.generate_blended (no device): n groups of 1 to BLEND_MAX_ROWS prompts become one batch -- group
+    i's first prompt, its leader, at row i, then the other members of every group in the order of their leaders, each with its
+    leader's RowSampling (the engine samples a member with its leader's record anyway).  weights[i]: one value per prompt of group i;
+    a group of one prompt is a plain row (its weight is not read).  force_ids (None, n id lists as in pack_force_ids, or an int tensor
+    [n, steps]): a member gets its leader's ids.  Returns (prompts, rows, leader, weight, force_ids) of the whole batch.
+    ValueError naming the group or the row: an empty group or prompt, more than BLEND_MAX_ROWS prompts, a weight count that differs
+    from the group's, a member that would not fit into max_batch, and what check_blend refuses."""
+    groups = []
+    for g in prompt_groups:
+        g = g.tolist() if isinstance(g, torch.Tensor) else list(g)
+        groups.append([list(p.tolist() if isinstance(p, torch.Tensor) else p) for p in g]
+                      if g and isinstance(g[0], (list, tuple, torch.Tensor)) else [list(g)])
+    rows = list(rows)
+    n = len(groups)
+    weights = list(weights)
+    if len(rows) != n or len(weights) != n:
+        raise ValueError(f"{n} prompt groups but {len(rows)} sampler rows and {len(weights)} weight lists")
+    if n > int(max_batch):
+        raise ValueError(f"{n} prompt groups exceed max_batch {max_batch}")
+    total = sum(len(g) for g in groups)
+    all_prompts, all_rows = [None] * n, list(rows)
+    leader, weight, src = [-1] * n, [0.0] * n, list(range(n))
+    for i, g in enumerate(groups):
+        w = [float(v) for v in (weights[i].tolist() if hasattr(weights[i], "tolist") else weights[i])]
+        if not 1 <= len(g) <= BLEND_MAX_ROWS:
+            raise ValueError(f"group {i}: {len(g)} prompts outside [1, {BLEND_MAX_ROWS}]")
+        if any(len(p) < 1 for p in g):
+            raise ValueError(f"group {i}: empty prompt")
+        if len(w) != len(g):
+            raise ValueError(f"group {i}: {len(w)} weights for {len(g)} prompts")
+        all_prompts[i] = g[0]
+        if len(g) == 1:
+            continue
+        leader[i], weight[i] = i, w[0]
+        for p, wk in zip(g[1:], w[1:]):
+            u = len(all_prompts)
+            if u >= int(max_batch):
+                raise ValueError(f"group {i}: its member row {u} does not fit: {total} prompts in {n} groups exceed max_batch {max_batch}")
+            all_prompts.append(p)
+            all_rows.append(rows[i])
+            leader.append(i)
+            weight.append(wk)
+            src.append(i)
+    if isinstance(force_ids, torch.Tensor):
+        if force_ids.dim() == 2 and len(src) > n:
+            force_ids = force_ids[torch.tensor(src, device=force_ids.device)]
+    elif force_ids is not None:
+        force_ids = list(force_ids)
+        if len(force_ids) != n:
+            raise ValueError(f"{n} prompt groups but {len(force_ids)} force_ids rows")
+        force_ids = [force_ids[i] for i in src]
+    check_blend(leader, weight, len(all_prompts))
+    return all_prompts, all_rows, leader, weight, force_ids
+
+
 SCHEDULE_MAX_SEGMENTS = 8
 
 
@@ -1028,13 +1127,14 @@ class DecoderEngine:
         return int(n_steps)
 
     def _run_rows(self, ids, lens, rows, n_steps: int, force_ids=None, scored: bool = False, guide=None, srecs=None,
-                  n_seg_max: int = 1, check_ids: bool = True, check_bias: bool = True) -> ScoredGeneration:
+                  n_seg_max: int = 1, check_ids: bool = True, check_bias: bool = True, blend=None) -> ScoredGeneration:
         """What generate_rows, generate_scored, generate_guided and generate_scheduled share: ids [B, Tp] (scheduled: [n_seg_max, B,
         Tp]) and lens from _prompt_ids, one RowSampling per row of B.  Packs the rows' records, logit records, forced ids and grammar
         start states (their ValueErrors, in that order), uploads on the engine's stream and makes the native call -- always
         mgea_decoder_generate_rows_scheduled, the superset, with NULL for what the caller does not use: it then runs exactly what
         the narrower entry point would -- or, when a row carries a Truncation, mgea_decoder_generate_rows_truncated, the same call
-        with the rows' truncation records.  Returns all B rows [B, n_steps]; logprobs / choice_logprobs are None unless scored."""
+        with the rows' truncation records, or, with blend records, mgea_decoder_generate_rows_blended, the end of the chain.
+        Returns all B rows [B, n_steps]; logprobs / choice_logprobs are None unless scored."""
         B, Tp = ids.shape[-2:]
         recs = pack_rows(rows, self.vocab, n_steps)
         forced = pack_force_ids(force_ids, B, n_steps, self.vocab)
@@ -1054,7 +1154,11 @@ class DecoderEngine:
             ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
             for t in keep:   # uploaded on the caller's stream, read by the engine's
                 t.record_stream(self.stream)
-            if trecs is None:
+            if blend is not None:
+                check(self.lib.mgea_decoder_generate_rows_blended(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
+                                                                  srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), trecs, blend,
+                                                                  self._sp()))
+            elif trecs is None:
                 check(self.lib.mgea_decoder_generate_rows_scheduled(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
                                                                     srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), self._sp()))
             else:
@@ -1116,6 +1220,42 @@ class DecoderEngine:
         guide = (_lib.RowGuidance * B)(*[_lib.RowGuidance(shadow_row=u, scale=s) for u, s in zip(shadow, scales)])
         got = self._run_rows(ids, lens, rows_all, n_steps, forced_in, scored, guide, check_ids=check_ids, check_bias=check_bias)
         return got.first_rows(B if all_rows else n, scored)
+
+    def generate_blended(self, prompt_groups, weights, rows: Sequence[RowSampling], n_steps: Optional[int] = None, force_ids=None,
+                         scored: bool = False, check_ids: bool = True, check_bias: bool = True, all_rows: bool = False):
+        """generate_rows() whose rows are emotion blends (mgea_decoder_generate_rows_blended; build-defined).  prompt_groups[i]: 1 to
+        BLEND_MAX_ROWS prompts -- the same request conditioned on another emotion each --, weights[i]: one finite weight per prompt,
+        summing to 1.  The engine runs the group as that many rows (its first prompt at row i, the others behind the callers' rows)
+        and at every step the group draws ONE id from sum_k w_k * logp(prompt k), renormalised; the mix comes before the repetition
+        penalty (over the FIRST prompt and the generated ids), the bias, the grammar and the truncation rules, which are row i's.
+        A group of K prompts costs K rows of max_batch and one more launch per step; a call in which every group has one prompt is
+        generate_rows / generate_scored itself.  Returns the leaders' lines only: int32 [n, n_steps], or with scored=True a
+        ScoredGeneration whose logprobs are those of the blended distribution; all_rows=True returns the members too (pack_blended).
+        force_ids as in generate_scored (scored=True only).  ValueError naming the row or group for what the native call would
+        refuse, a batch beyond max_batch and a capped generation (prompt width + n_steps > max_ctx without a window) included."""
+        if force_ids is not None and not scored:
+            raise ValueError("force_ids need scored=True")
+        all_prompts, rows_all, leader, weight, forced_in = pack_blended(prompt_groups, weights, rows, self.max_batch, force_ids)
+        n = len(leader) - sum(1 for b, l in enumerate(leader) if l >= 0 and l != b)
+        if all(l < 0 for l in leader):   # nothing is blended: the calls there always were
+            if scored:
+                return self.generate_scored(all_prompts, rows_all, n_steps, force_ids, check_ids, check_bias)
+            return self.generate_rows(all_prompts, rows_all, n_steps, check_ids, check_bias)
+        ids, lens = _prompt_ids(all_prompts)
+        B, Tp = ids.shape
+        n_steps = self._resolve_n_steps(rows_all, n_steps)
+        if self.window is None and Tp + n_steps > self.max_ctx:
+            raise ValueError(f"prompt width {Tp} + {n_steps} steps exceed max_ctx {self.max_ctx}: a blended generation is never capped "
+                             "(set a window)")
+        blend = (_lib.RowBlend * B)(*[_lib.RowBlend(leader=l, weight=w) for l, w in zip(leader, weight)])
+        got = self._run_rows(ids, lens, rows_all, n_steps, forced_in, scored, check_ids=check_ids, check_bias=check_bias, blend=blend)
+        return got.first_rows(B if all_rows else n, scored)
+
+    def blend_info(self):
+        """The groups, the grouped rows and the blended decode steps of the last generation (all 0 if it was not blended)."""
+        out = (C.c_int64 * 3)()
+        check(self.lib.mgea_decoder_blend_info(self.h, out))
+        return dict(groups=int(out[0]), rows=int(out[1]), blended_steps=int(out[2]))
 
     def truncation_info(self):
         """The truncated decode steps of the last generation and its rows with a truncation stage on (both 0 if it was not truncated)."""

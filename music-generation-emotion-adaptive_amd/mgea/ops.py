@@ -456,6 +456,26 @@ def guidance_mix(logits: torch.Tensor, partner, scale) -> torch.Tensor:
     return out
 
 
+def blend_mix(logits: torch.Tensor, leader, weight) -> torch.Tensor:
+    """The mix launch of a blended decode step (mgea_op_blend_mix), alone, on a COPY of logits [>= B, V] (B = len(leader); rows behind
+    B are guard rows the kernel must not touch): the rows b with leader[b] == L, in ascending order, all become
+    sum_k weight[m_k] * log_softmax(row m_k).  leader / weight: B ints (-1 = in no group) and B floats, checked on the host like a
+    blended call's groups (mgea.decoder.check_blend: ValueError naming the row).  Returns the copy."""
+    from .decoder import check_blend
+    lib = _lib.load()
+    leader = [int(v) for v in (leader.tolist() if hasattr(leader, "tolist") else leader)]
+    weight = [float(v) for v in (weight.tolist() if hasattr(weight, "tolist") else weight)]
+    B = len(leader)
+    if logits.dim() != 2 or logits.shape[0] < B or len(weight) != B or B < 1:
+        raise RuntimeError("blend_mix: logits must be [>= B, V] with B = len(leader) = len(weight) >= 1")
+    check_blend(leader, weight, B)
+    out = logits.to(device="cuda", dtype=torch.float32).contiguous().clone()
+    l = torch.tensor(leader, dtype=torch.int32, device="cuda")
+    w = torch.tensor(weight, dtype=torch.float32, device="cuda")
+    check(lib.mgea_op_blend_mix(ptr(out), B, out.shape[1], ptr(l), ptr(w), stream_ptr()))
+    return out
+
+
 # ---- the DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call (mgea_op_* of the same names: tests only) ----
 _DTYPE_ROWS = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
 
