@@ -114,6 +114,62 @@ static SampleCall op_sample_call(const float* logits_dev, int B, int V, int64_t 
     return c;
 }
 
+// The temporaries of one rows launch (mgea_op_sample_rows*, kind 4 of mgea_op_step_tail): the rows' device records, their bias rows
+// (row b at b * V; rows without one are never read), the grammar's allow bitmask, the truncation records, and an all-zero presence
+// bitmap where a grammar or a truncating launch got none from the caller (both forms are built on the PENALTY one).  The group frees
+// them on return; the caller synchronises the stream first.  The callers keep their own argument checks and return codes.
+struct RowsStage {
+    SamplerParams* rec_dev = nullptr;
+    float* bias_dev = nullptr;
+    uint32_t *allow_dev = nullptr, *pres_tmp = nullptr;
+    mgea_row_truncation* trunc_dev = nullptr;
+    DevGroup tmp;   // (declared after the pointers it fills)
+    hipError_t hip_err = hipSuccess;   // fill(): the enqueue that failed
+
+    enum { RECORDS = 1, BIAS, GRAMMAR, TRUNC };
+    static const char* what(int bad) { return bad == RECORDS ? "records" : bad == BIAS ? "bias rows" : bad == GRAMMAR ? "grammar's bitmask" : "truncation records"; }
+    // Allocates, in this order and before anything is enqueued: records, bias rows, allow bitmask, truncation records, the stand-in
+    // bitmap.  0, or which allocation failed.
+    int alloc(int B, int V, bool records, bool bias, const GrammarArgs* g, bool trunc, bool caller_bitmap) {
+        const size_t np = (size_t)B * presence_words(V) * sizeof(uint32_t);
+        if (records && tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) != MGEA_OK) return RECORDS;
+        if (bias && tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) != MGEA_OK) return BIAS;
+        if (g && (tmp.alloc(&allow_dev, (size_t)g->n_state * grammar_words(g->n_class) * sizeof(uint32_t)) != MGEA_OK ||
+                  (!caller_bitmap && tmp.alloc(&pres_tmp, np) != MGEA_OK)))
+            return GRAMMAR;
+        if (trunc && (tmp.alloc(&trunc_dev, (size_t)B * sizeof(mgea_row_truncation)) != MGEA_OK ||
+                      (!caller_bitmap && !pres_tmp && tmp.alloc(&pres_tmp, np) != MGEA_OK)))
+            return TRUNC;
+        return 0;
+    }
+    // Enqueues what fills them -- records, allow bitmask (its own kernel), truncation records, the zeroed bitmap, the bias rows of
+    // lrows (device-to-device, one copy per row that has one) -- stopping at the first failure, and writes them into c.  MGEA_OK,
+    // launch_grammar_allow's code, or MGEA_EHIP with hip_err set.
+    int fill(SampleCall& c, int B, int V, const SamplerParams* rec, const mgea_row_logits* lrows, const GrammarArgs* g,
+             const mgea_row_truncation* trunc, hipStream_t st) {
+        c.params_dev = rec_dev;   // every scalar comes from the records
+        c.bias = bias_dev;
+        if (pres_tmp) c.presence = pres_tmp;
+        if (rec_dev && (hip_err = hipMemcpyAsync(rec_dev, rec, (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st)) != hipSuccess) return MGEA_EHIP;
+        if (g) {
+            c.grammar = *g;
+            c.grammar.allow = allow_dev;
+            c.grammar.words = grammar_words(g->n_class);
+            MGEA_TRY(launch_grammar_allow(g->next, g->n_state, g->n_class, allow_dev, st));
+        }
+        if (trunc) {
+            c.trunc = TruncArgs{trunc_dev};
+            if ((hip_err = hipMemcpyAsync(trunc_dev, trunc, (size_t)B * sizeof(mgea_row_truncation), hipMemcpyHostToDevice, st)) != hipSuccess) return MGEA_EHIP;
+        }
+        if (pres_tmp && (hip_err = hipMemsetAsync(pres_tmp, 0, (size_t)B * presence_words(V) * sizeof(uint32_t), st)) != hipSuccess) return MGEA_EHIP;
+        for (int b = 0; lrows && b < B; ++b)
+            if (lrows[b].bias_dev && (hip_err = hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float),
+                                                               hipMemcpyDeviceToDevice, st)) != hipSuccess)
+                return MGEA_EHIP;
+        return MGEA_OK;
+    }
+};
+
 // mgea_op_sample_rows(_biased, _scored): the rows' records and bias vectors to device memory, one sampler launch (defined at the end)
 static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const mgea_row_sampler* rows, const uint32_t* presence_dev,
                           const mgea_row_logits* lrows, int64_t step, int32_t* ids_out_dev, float* probs_out_dev, const ScoreArgs& score,
@@ -692,22 +748,29 @@ int mgea_op_step_tail(const mgea_step_tail_args* a, void* stream) {
     if (kind == 4)   // launch_sample's own refusals, taken before anything is enqueued
         MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB && t.C % 4 == 0 && t.C <= 4096 && tail_qkv0_ok(t), MGEA_EINVAL,
                      "op_step_tail: sampler: vocab %d or the fused tail's shape is refused", V);
-    // the rows' records -> a temporary device buffer (freed on return: the stream is synchronised first)
+    // the rows' records, and the sampler's other temporaries -> device buffers (freed on return: the stream is synchronised first)
     std::vector<SamplerParams> rec;
-    SamplerParams* rec_dev = nullptr;
-    float* bias_dev = nullptr;
-    uint32_t *allow_dev = nullptr, *pres_tmp = nullptr;
-    DevGroup tmp;
+    RowsStage stage;
     const mgea_row_logits* lrows = kind == 4 ? a->logits_rows : nullptr;
+    // as mgea_op_sample_rows_grammar builds it: the allow bitmask by its own kernel, empty bitmaps where none came
+    const GrammarArgs g{a->class_of_dev, a->next_dev, nullptr, a->states_dev, a->states_dev, a->done_dev,
+                        a->n_state, a->n_class, grammar_words(a->n_class), a->err_flag_dev};
+    SampleCall c{};
+    c.logits = a->logits_dev; c.B = B; c.V = V; c.ids_out = a->sampled_dev; c.row_step_dev = a->row_step_dev;
+    c.tail = &t;
+    c.presence = a->presence_dev;
     if (a->rows) {
         MGEA_TRY(check_row_samplers(a->rows, B, kind == 4 ? V : MGEA_SAMPLER_MAX_VOCAB, -1, "op_step_tail"));
         if (lrows) MGEA_TRY(check_row_logits(lrows, B, -1, "op_step_tail"));
         rec.resize((size_t)B);
         build_row_records(a->rows, lrows, B, -1, rec.data());
         for (int b = 0; a->ctx_cap && b < B; ++b) rec[b].ctx_cap = a->ctx_cap[b];
-        MGEA_REQUIRE(tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) == MGEA_OK, MGEA_ENOMEM, "op_step_tail: allocation of the records failed");
-        MGEA_CHECK_HIP(hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st));
-        t.s.params = rec_dev;
+        const int bad = stage.alloc(B, V, true, lrows || grammar, grammar ? &g : nullptr, false, a->presence_dev != nullptr);
+        MGEA_REQUIRE(!bad, MGEA_ENOMEM, "op_step_tail: allocation of the %s failed", RowsStage::what(bad));
+        const int rc = stage.fill(c, B, V, rec.data(), lrows, grammar ? &g : nullptr, nullptr, st);
+        if (stage.hip_err != hipSuccess) MGEA_CHECK_HIP(stage.hip_err);   // (as before the helper: this path does not synchronise)
+        if (rc != MGEA_OK) return op_finish(rc, st);
+        t.s.params = stage.rec_dev;
     }
     if (kind == 0) return op_finish(launch_argmax_advance(a->pval_dev, a->pidx_dev, a->n_tiles, t.s, a->sampled_dev, B, st), st);
     if (kind == 1) return op_finish(launch_argmax_advance_embed(a->pval_dev, a->pidx_dev, a->n_tiles, t, a->sampled_dev, B, st), st);
@@ -717,31 +780,7 @@ int mgea_op_step_tail(const mgea_step_tail_args* a, void* stream) {
     }
     if (kind == 3) return op_finish(launch_embed_qkv0(a->cur_ids_dev, a->ctx_len_dev, t, B, a->err_flag_dev, st), st);
     // kind 4: the sampler with its fused tail
-    SampleCall c{};
-    c.logits = a->logits_dev; c.B = B; c.V = V; c.ids_out = a->sampled_dev; c.params_dev = rec_dev; c.row_step_dev = a->row_step_dev;
-    c.tail = &t;
-    c.presence = a->presence_dev;
-    if (lrows || grammar) {
-        MGEA_REQUIRE(tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) == MGEA_OK, MGEA_ENOMEM, "op_step_tail: allocation of the bias rows failed");
-        for (int b = 0; lrows && b < B; ++b)
-            if (lrows[b].bias_dev)
-                MGEA_CHECK_HIP(hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st));
-        c.bias = bias_dev;
-    }
     if (scored) c.score = ScoreArgs{a->forced_dev, a->forced_stride, a->logprob_hist_dev, a->choice_hist_dev, a->hist_stride, a->err_flag_dev};
-    if (grammar) {   // as mgea_op_sample_rows_grammar builds it: the allow bitmask by its own kernel, empty bitmaps where none came
-        const size_t nw = (size_t)a->n_state * grammar_words(a->n_class), np = (size_t)B * presence_words(V);
-        MGEA_REQUIRE(tmp.alloc(&allow_dev, nw * sizeof(uint32_t)) == MGEA_OK && (c.presence || tmp.alloc(&pres_tmp, np * sizeof(uint32_t)) == MGEA_OK),
-                     MGEA_ENOMEM, "op_step_tail: allocation of the grammar's bitmask failed");
-        if (pres_tmp) {
-            MGEA_CHECK_HIP(hipMemsetAsync(pres_tmp, 0, np * sizeof(uint32_t), st));
-            c.presence = pres_tmp;
-        }
-        c.grammar = GrammarArgs{a->class_of_dev, a->next_dev, allow_dev, a->states_dev, a->states_dev, a->done_dev,
-                                a->n_state, a->n_class, grammar_words(a->n_class), a->err_flag_dev};
-        const int rc = launch_grammar_allow(a->next_dev, a->n_state, a->n_class, allow_dev, st);
-        if (rc != MGEA_OK) return op_finish(rc, st);
-    }
     return op_finish(launch_sample(c, st), st);
 }
 
@@ -837,57 +876,22 @@ static int op_sample_rows(const float* logits_dev, int32_t B, int32_t V, const m
     const bool biased = rr.form == StepForm::BIASED;
     MGEA_REQUIRE(!rr.any_penalty || presence_dev, MGEA_EINVAL, "op_sample_rows: a row is penalized but presence_dev is NULL");
     hipStream_t st = (hipStream_t)stream;
-    SamplerParams* rec_dev = nullptr;
-    float* bias_dev = nullptr;   // the rows' vectors, row b at b * V (rows without one are never read)
-    DevGroup tmp;   // frees both on return: nothing is enqueued before the allocations, and the stream is synchronised after
-    MGEA_REQUIRE(tmp.alloc(&rec_dev, (size_t)B * sizeof(SamplerParams)) == MGEA_OK, MGEA_EHIP,
-                 "hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)) failed: %s (%s:%d)", hipGetErrorString(hipGetLastError()), __FILE__, __LINE__);
-    MGEA_REQUIRE(!(biased || grammar || trunc) || tmp.alloc(&bias_dev, (size_t)B * V * sizeof(float)) == MGEA_OK, MGEA_ENOMEM,
-                 "op_sample_rows: allocation of the bias rows failed");
-    // the grammar form is built on the biased one: it brings its allow bitmask, and empty bitmaps where no row is penalized
-    uint32_t *allow_dev = nullptr, *pres_tmp = nullptr;
-    if (grammar) {
-        const size_t nw = (size_t)grammar->n_state * grammar_words(grammar->n_class), np = (size_t)B * presence_words(V);
-        MGEA_REQUIRE(tmp.alloc(&allow_dev, nw * sizeof(uint32_t)) == MGEA_OK && (presence_dev || tmp.alloc(&pres_tmp, np * sizeof(uint32_t)) == MGEA_OK),
-                     MGEA_ENOMEM, "op_sample_rows: allocation of the grammar's bitmask failed");
-    }
-    // so is the truncating form; its records travel like the sampler's
-    mgea_row_truncation* trunc_dev = nullptr;
-    if (trunc) {
-        const size_t np = (size_t)B * presence_words(V);
-        MGEA_REQUIRE(tmp.alloc(&trunc_dev, (size_t)B * sizeof(mgea_row_truncation)) == MGEA_OK &&
-                         (presence_dev || pres_tmp || tmp.alloc(&pres_tmp, np * sizeof(uint32_t)) == MGEA_OK),
-                     MGEA_ENOMEM, "op_sample_rows: allocation of the truncation records failed");
-    }
+    // the grammar and the truncating form are built on the biased one: both bring the bias buffer, and empty bitmaps where none came
+    RowsStage stage;   // nothing is enqueued before the allocations, and the stream is synchronised before they are freed
+    const int bad = stage.alloc(B, V, true, biased || grammar || trunc, grammar, trunc != nullptr, presence_dev != nullptr);
+    MGEA_REQUIRE(bad != RowsStage::RECORDS, MGEA_EHIP, "hipMalloc((void**)&rec_dev, (size_t)B * sizeof(SamplerParams)) failed: %s (%s:%d)",
+                 hipGetErrorString(hipGetLastError()), __FILE__, __LINE__);
+    MGEA_REQUIRE(!bad, MGEA_ENOMEM, "op_sample_rows: allocation of the %s failed", RowsStage::what(bad));
     SampleCall c = op_sample_call(logits_dev, B, V, step, ids_out_dev, probs_out_dev);
-    c.params_dev = rec_dev;   // every scalar comes from the records
-    c.presence = rr.any_penalty ? const_cast<uint32_t*>(presence_dev) : nullptr;   // (a bias alone needs no bitmap here: nothing is written)
-    c.bias = bias_dev;
+    // (a bias alone needs no bitmap here: nothing is written)
+    c.presence = (rr.any_penalty || grammar || trunc) ? const_cast<uint32_t*>(presence_dev) : nullptr;
     c.score = score;
     int rc = MGEA_EHIP;
-    bool copied = hipMemcpyAsync(rec_dev, rec.data(), (size_t)B * sizeof(SamplerParams), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (grammar) {
-        c.grammar = *grammar;
-        c.grammar.allow = allow_dev;
-        c.grammar.words = grammar_words(grammar->n_class);
-        c.presence = presence_dev ? const_cast<uint32_t*>(presence_dev) : pres_tmp;
-        copied = copied && launch_grammar_allow(grammar->next, grammar->n_state, grammar->n_class, allow_dev, st) == MGEA_OK;
-    }
-    if (trunc) {
-        c.trunc = TruncArgs{trunc_dev};
-        c.presence = presence_dev ? const_cast<uint32_t*>(presence_dev) : pres_tmp;
-        copied = copied && hipMemcpyAsync(trunc_dev, trunc, (size_t)B * sizeof(mgea_row_truncation), hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (pres_tmp) copied = copied && hipMemsetAsync(pres_tmp, 0, (size_t)B * presence_words(V) * sizeof(uint32_t), st) == hipSuccess;
-    for (int b = 0; biased && copied && b < B; ++b)
-        if (lrows[b].bias_dev)
-            copied = hipMemcpyAsync(bias_dev + (size_t)b * V, lrows[b].bias_dev, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st) ==
-                     hipSuccess;
-    if (copied)
+    if (stage.fill(c, B, V, rec.data(), biased ? lrows : nullptr, grammar, trunc, st) == MGEA_OK)
         rc = launch_sample(c, st);
     else
         set_error("op_sample_rows: copy of the records failed");
-    const hipError_t e = hipStreamSynchronize(st);   // rec, rec_dev and bias_dev are freed on return
+    const hipError_t e = hipStreamSynchronize(st);   // rec and the stage's buffers are freed on return
     MGEA_TRY(rc);
     MGEA_CHECK_HIP(e);
     return MGEA_OK;
