@@ -683,6 +683,20 @@ int mgea_op_layernorm_bf16(const void* x_dev, const float* w_dev, const float* b
 int mgea_op_gemm_f16_ln(const void* a_dev, const void* w_dev, const float* bias_dev, const void* res_dev, void* out_dev,
                         int32_t M, int32_t N, int32_t K, int32_t epi, const float* rowstat_dev, const float* c1_dev,
                         const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream);
+/* The two calls above as ONE entry point that can launch what the engines launch: leading dimensions of its own (in elements:
+ * a [M, K] with row stride lda, w [N, K] with ldw, out [M, N] with ldc -- fp32 elements for epi 6 -- and res_dev, when given, with
+ * the row stride of out), so that a, w and out may be column or row slices of wider buffers (the last DistilBERT layer and the
+ * decoder's K | V prefill write N = 2D columns into the middle of a [M, 3D] buffer); f16 != 0: fp16 operands and the rules of
+ * mgea_op_gemm_f16_ln, else bf16 and those of mgea_op_gemm_bf16_ln; reverse != 0: ask the persistent kernel to walk every XCD's run
+ * of tiles from its end, as the engines' FC2 does (honoured while the switch bf16_gemm_reverse is set; the other kernels ignore it).
+ * lda % 8 == 0, ldw % 8 == 0, ldc % 4 == 0 (% 8 for everything but the 128 x 128 kernel), lda >= K, ldw >= K, ldc >= N; the
+ * operand pointers 16-byte aligned.  Nothing outside rows [0, M) x columns [0, N) of out is written.
+ * info_out [3] (host, or NULL): [0] the kernel family that ran (0 128 x 128 register-staged, 1 ring, 2 persistent, 3 two
+ * workgroups per CU), [1] half_tiles as above, [2] the persistent kernel's tail word: bits 0-1 the tail schedule (switch
+ * bf16_gemm_tail), bit 2 set when the tiles are walked in reverse (0 for the other families). */
+int mgea_op_gemm16(const void* a_dev, int32_t lda, const void* w_dev, int32_t ldw, const float* bias_dev, const void* res_dev, void* out_dev,
+                   int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t f16, int32_t reverse, const float* rowstat_dev,
+                   const float* c1_dev, const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream);
 /* mgea_op_f32_to_bf16 / mgea_op_fold_ln_bf16 with the 16-bit type as an argument (MGEA_DTYPE_BF16: exactly those calls). */
 int mgea_op_f32_to_16(const float* src_dev, void* dst_dev, int64_t n, int32_t dtype, void* stream);
 int mgea_op_fold_ln_16(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* bias_dev, int32_t N, int32_t K,

@@ -303,6 +303,19 @@ int mgea_op_gemm_f16_ln(const void* a_dev, const void* w_dev, const float* bias_
     return rc;
 }
 
+int mgea_op_gemm16(const void* a_dev, int32_t lda, const void* w_dev, int32_t ldw, const float* bias_dev, const void* res_dev, void* out_dev,
+                   int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t f16, int32_t reverse, const float* rowstat_dev,
+                   const float* c1_dev, const float* ln_g_dev, const float* ln_b_dev, float* stats_out_dev, int32_t* info_out, void* stream) {
+    MGEA_REQUIRE(a_dev && w_dev && out_dev, MGEA_EINVAL, "op_gemm16: NULL argument");
+    MGEA_REQUIRE(lda >= K && ldw >= K && ldc >= N, MGEA_EINVAL, "op_gemm16: lda %d / ldw %d below K = %d or ldc %d below N = %d", lda, ldw, K, ldc, N);
+    const BfEpiLn ln{rowstat_dev, c1_dev, ln_g_dev, ln_b_dev, stats_out_dev};
+    GemmBf16Info gi{-1, 0, 0};
+    const int rc = launch_gemm_bf16(a_dev, lda, w_dev, ldw, bias_dev, res_dev, out_dev, ldc, M, N, K, epi, (hipStream_t)stream, &gi,
+                                    epi >= BEPI_LNFOLD ? &ln : nullptr, f16 != 0, reverse != 0);
+    if (info_out) { info_out[0] = gi.kernel; info_out[1] = gi.half_tiles; info_out[2] = gi.tail_mode; }
+    return rc;
+}
+
 int mgea_op_f32_to_16(const float* src_dev, void* dst_dev, int64_t n, int32_t dtype, void* stream) {
     MGEA_REQUIRE(src_dev && dst_dev && n > 0 && (dtype == MGEA_DTYPE_BF16 || dtype == MGEA_DTYPE_F16), MGEA_EINVAL, "op_f32_to_16: bad argument");
     return launch_f32_to_bf16(src_dev, dst_dev, n, (hipStream_t)stream, dtype == MGEA_DTYPE_F16);

@@ -370,8 +370,9 @@ struct BfEpiLn { const float* rowstat; const float* c1; const float* ln_g; const
 // What a launch_gemm_bf16 call ran, from its plan (optional out-parameter; the engines count these for mgea_bert_stats): kernel = the
 // G16_* family (0 the register-staged 128 x 128 kernel, 1 a ring kernel, 2 the persistent phase-interleaved 256 x 256 kernel, 3 the
 // two-workgroups-per-CU 256 x 128 kernel, switch bf16_gemm_tile = 5 only); half_tiles = 1 when the persistent kernel cuts the tiles
-// left over after its full rounds into two 128-row halves (gemm16.hip, "HALF-TILE TAIL").
-struct GemmBf16Info { int kernel; int half_tiles; };
+// left over after its full rounds into two 128-row halves (gemm16.hip, "HALF-TILE TAIL"); tail_mode = the persistent kernel's tail word
+// (Gemm16Plan.tail_mode: bits 0-1 the tail schedule, bit 2 the reversed walk; 0 for the other families).
+struct GemmBf16Info { int kernel; int half_tiles; int tail_mode; };
 // f16 != 0: _Float16 operands / outputs (persistent kernel, epilogues 3 / 4 / 5, and 6 = fp32 output).  reverse != 0: ask the persistent
 // kernel to walk its tiles from the end of every XCD's run (switch bf16_gemm_reverse; for a GEMM whose A operand is the previous
 // kernel's large output: see the kernel).

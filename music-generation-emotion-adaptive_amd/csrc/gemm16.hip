@@ -1242,7 +1242,7 @@ int launch_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float
     const char* why = "";
     MGEA_REQUIRE(plan_gemm16(c, gemm16_switches(), di.n_cu, &p, &why) == 0, MGEA_EINVAL, "16-bit gemm M=%d N=%d K=%d ldc=%d epilogue %d%s: %s",
                  M, N, K, ldc, epi, f16 ? " (fp16)" : "", why);
-    if (info) { info->kernel = p.family; info->half_tiles = p.half_tiles; }
+    if (info) { info->kernel = p.family; info->half_tiles = p.half_tiles; info->tail_mode = p.tail_mode; }
     const KernelRef k = gemm16_kernel(p);
     MGEA_REQUIRE(k.fn, MGEA_EINVAL, "16-bit gemm: no kernel for plan family %d, epilogue %d", p.family, epi);
     if (p.shmem) MGEA_TRY(set_max_dynamic_lds(k.fn, p.shmem, di.dev, k.lds_raised));

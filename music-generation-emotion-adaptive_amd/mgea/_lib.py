@@ -179,6 +179,7 @@ PROTOTYPES = {
     "mgea_op_attention_bf16": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_layernorm_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _P]),
     "mgea_op_gemm_f16_ln": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32), _P]),
+    "mgea_op_gemm16": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32), _P]),
     "mgea_op_f32_to_16": (C.c_int, [_P, _P, _I64, _I32, _P]),
     "mgea_op_fold_ln_16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "mgea_op_attention16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P]),

@@ -183,6 +183,58 @@ def gemm_f16_ln(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     return (out, stats) if stats is not None else out
 
 
+def gemm16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+           gelu: bool = False, ln: Optional[dict] = None, f32_out: bool = False, reverse: bool = False,
+           info: Optional[list] = None, epi: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """gemm_bf16 / gemm_f16_ln as the engines launch them (mgea_op_gemm16): the type is a's (bf16 or fp16), and the leading
+    dimensions are the tensors' row strides, so a [M, K], w [N, K], res and out [M, N] may be column or row slices of wider buffers.
+    Nothing is copied: every operand must already be a device tensor of the right type with inner stride 1, res with the row stride
+    of out (the kernels have one ldc for both).  ln, gelu, f32_out, epi as in gemm_f16_ln (ln["stats"] may be the caller's buffer);
+    reverse asks for the persistent kernel's reversed tile walk.  info receives [kernel, half_tiles, tail_mode]."""
+    lib = _lib.load()
+    f16 = _dtype16(a) == _lib.DTYPE_F16
+    if w.dtype != a.dtype or a.ndim != 2 or w.ndim != 2 or w.shape[1] != a.shape[1]:
+        raise RuntimeError(f"gemm16: a {tuple(a.shape)} {a.dtype} and w {tuple(w.shape)} {w.dtype} do not multiply")
+    M, K = a.shape
+    N = w.shape[0]
+    rowstat = c1 = g = be = stats = None
+    e = 6 if f32_out else 2 if res is not None else 1 if gelu else 0
+    if ln is not None:
+        rowstat = ln.get("rowstat")
+        if "c1" in ln:
+            e, c1 = (4 if gelu else 3), ln["c1"]
+        else:
+            e, g, be = 5, ln["g"], ln["b"]
+            if isinstance(ln.get("stats"), torch.Tensor):
+                stats = ln["stats"]
+            elif ln.get("stats"):
+                stats = torch.zeros(M, N // 256, 2, dtype=torch.float32, device=a.device)
+    if epi is not None:
+        e = int(epi)
+    out_dtype = torch.float32 if e == 6 else a.dtype
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=a.device)
+    if out.dtype != out_dtype or tuple(out.shape) != (M, N):
+        raise RuntimeError(f"gemm16: out {tuple(out.shape)} {out.dtype}, [{M}, {N}] {out_dtype} expected")
+    mats = [("a", a), ("w", w), ("out", out)]
+    if res is not None:
+        if res.dtype != a.dtype or tuple(res.shape) != (M, N) or res.stride(0) != out.stride(0):
+            raise RuntimeError("gemm16: res must have the type of a and the shape and row stride of out")
+        mats.append(("res", res))
+    for name, t in mats:
+        if t.device.type != "cuda" or t.stride(1) != 1 or t.data_ptr() % 16:
+            raise RuntimeError(f"gemm16: {name} must be a device tensor with inner stride 1 on a 16-byte boundary")
+    for name, t in (("bias", bias), ("rowstat", rowstat), ("c1", c1), ("g", g), ("b", be), ("stats", stats)):
+        if t is not None and not (t.device.type == "cuda" and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+            raise RuntimeError(f"gemm16: {name} must be a contiguous fp32 device tensor on a 16-byte boundary")
+    io = (C.c_int32 * 3)(-1, -1, -1)
+    check(lib.mgea_op_gemm16(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(res), ptr(out), out.stride(0), M, N, K, e,
+                             int(f16), int(bool(reverse)), ptr(rowstat), ptr(c1), ptr(g), ptr(be), ptr(stats), io, stream_ptr()))
+    if info is not None:
+        info[:] = [int(io[0]), int(io[1]), int(io[2])]
+    return (out, stats) if stats is not None else out
+
+
 def f32_to_16(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """fp32 -> bf16 / fp16 by the library's convert kernel (round to nearest even)."""
     lib = _lib.load()
