@@ -638,10 +638,19 @@ int mgea_op_gemm_f32(const float* a_dev, const float* w_dev, const float* bias_d
 int mgea_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev,
                       int32_t M, int32_t C, float eps, void* stream);
 /* Non-causal attention over a packed qkv buffer [B*T, 3C] (q | k | v, head h at column h*dh);
- * key validity = (t < lens[b] if lens) && (mask[b,t] != 0 if mask).  out [B*T, C]. */
+ * key validity = (t < lens[b] if lens) && (mask[b,t] != 0 if mask).  out [B*T, C]; a row b without a valid key gives zero rows. */
 int mgea_op_attention_f32(const float* qkv_dev, const int32_t* lens_dev, const int32_t* mask_dev,
                           float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
                           void* stream);
+/* The same kernel with every argument its launcher takes (test only).  A query row without a valid key gives a ZERO output row (as
+ * mgea_op_attention_cls does), here and above.
+ *   cu_seqlens_dev [B + 1] int32 or NULL: packed rows -- qkv / out are [cu[B], 3C / C], sequence b is rows cu[b] .. cu[b + 1] - 1, all
+ *               real, T = the longest sequence; refused together with lens_dev, mask_dev or tiled_out.
+ *   tiled_out   != 0: out_dev is the k-tiled activation buffer of the fused decode path (mgea_op_tile_rows): whole 64-row groups of
+ *               64 * C floats, B * T <= 512 rows; only the floats of rows < B * T are written.
+ *   out_dev     caller-provided in both forms; nothing outside the rows above is written (rows t >= lens[b] ARE written). */
+int mgea_op_attention_f32_ex(const float* qkv_dev, const int32_t* lens_dev, const int32_t* mask_dev, const int32_t* cu_seqlens_dev,
+                             float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t tiled_out, void* stream);
 /* bf16 perf-mode kernels (MGEA_DTYPE_BF16 engines); bf16 buffers are raw 16-bit storage.
  * gemm: out[M,N] = epi(a[M,K] @ w[N,K]^T + bias), fp32 accumulate; epi 0 bias, 1 bias+GELU,
  * 2 bias+residual(res_dev [M,N] bf16).  K % 64 == 0, N % 4 == 0.  attention: head_dim 64 only. */
@@ -732,6 +741,22 @@ int mgea_op_attention_paged(const float* qkv_dev, const void* pages_dev, int32_t
                             const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev, const int32_t* lens_dev,
                             float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t no_split, int32_t* info_out,
                             void* stream);
+/* The same launch with the arguments the engine varies (test only).  pages_dev holds n_layer layers of n_pages pages each, layer l at
+ * element l * n_pages * 2 * n_head * 64 * head_dim (the decoder's layer stride); the kernel reads layer `layer`.  tiled_out != 0:
+ * out_dev is a k-tiled activation buffer (mgea_op_tile_rows; B * T <= 512 rows), only the floats of rows < B * T are written.
+ * split_part_dev / split_count_dev (both or neither; ignored with no_split): the CALLER's split-context scratch, of at least the
+ * sizes mgea_op_attn_split_scratch() answers -- part [256 items][16 splits][head_dim + 2] floats (acc[head_dim], max, sum), count
+ * [256] int32.  The call neither allocates nor zeroes it: the counters are zeroed once by whoever owns them and every launch leaves
+ * them zero; the partials need no initial value.  Without them the call brings its own zeroed scratch, as above.
+ * mgea_op_attn_split_count: the launcher's host-side choice of workgroups per (row, head, query) for a launch that has a scratch
+ * (switch attn_split; 1 = the unsplit kernel) -- what info_out[0] reports. */
+int mgea_op_attn_split_count(int32_t B, int32_t n_head, int32_t T, int32_t max_pages);
+int mgea_op_attn_split_scratch(int32_t head_dim, int64_t* part_floats_out, int64_t* count_ints_out);
+int mgea_op_attention_paged_ex(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
+                               int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
+                               const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                               int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
+                               int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream);
 /* Layouts of the fused decode path.  The skinny GEMM reads both operands in MFMA-fragment order so that
  * every wave load is 1 KB of consecutive bytes (see csrc/common.h):
  *   tile_weights: W [N,K] row-major -> out_dev [mgea_op_tiled_weight_floats(N,K)] (rows padded to 32);

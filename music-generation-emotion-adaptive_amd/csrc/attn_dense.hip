@@ -12,7 +12,8 @@
 //   O^T = V^T P^T: k-step s of the MFMA takes key 4g+s from register s of the S^T accumulator and
 //         V[key 4g+s][d] from LDS; O^T leaves d in registers -> 16-byte output stores.
 // Keys are valid when (t < lens[b] if lens) && (mask[b,t] != 0 if mask); invalid keys get p = 0
-// exactly (HF adds finfo.min before softmax: same result unless a row has no valid key).
+// exactly (HF adds finfo.min before softmax: same result unless a row has no valid key).  A row b with no valid key at all gives
+// all-zero output rows (the sum of its p is 0; attn_cls.hip has the same contract), never 0 * inf.
 #include "common.h"
 
 namespace mgea {
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256) void attn_dense_kernel(const float* __restrict
     lsum += __shfl_xor(lsum, 16, 64);
     lsum += __shfl_xor(lsum, 32, 64);
     if (q_in) {
-        const float inv = 1.0f / lsum;
+        const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;   // no valid key: a zero row
 #pragma unroll
         for (int dt = 0; dt < DC; ++dt) {
             const int n = h * DH + dt * 16 + 4 * g;

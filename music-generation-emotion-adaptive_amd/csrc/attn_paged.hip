@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void attn_paged_kernel(const float* __restrict
             den = fmaf(f, s_l[w], den);
         }
     }
-    constexpr int PS = attn_part_floats(DH);   // floats per partial: acc[DH], max, sum (+ 2 of padding: 16-byte rows)
+    constexpr int PS = attn_part_floats(DH);   // floats per partial: acc[DH], max, sum -- DH + 2, no padding
     const int64_t item = (int64_t)bh * T + t;
     float* part = sp.part + item * sp.max_split * PS;
     if (!SPLIT || active == 1) {   // the only workgroup of this query: done

@@ -235,6 +235,15 @@ int mgea_op_attention_f32(const float* qkv_dev, const int32_t* lens_dev, const i
     return launch_attn_dense(qkv_dev, lens_dev, mask_dev, out_dev, B, T, n_head, head_dim, 0, (hipStream_t)stream);
 }
 
+int mgea_op_attention_f32_ex(const float* qkv_dev, const int32_t* lens_dev, const int32_t* mask_dev, const int32_t* cu_seqlens_dev,
+                             float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t tiled_out, void* stream) {
+    MGEA_REQUIRE(qkv_dev && out_dev, MGEA_EINVAL, "op_attention: NULL argument");
+    // (cu with lens / mask / tiled_out is the launcher's refusal; here only what keeps a k-tiled out inside the size mgea.h documents)
+    MGEA_REQUIRE(!tiled_out || cu_seqlens_dev || ((int64_t)B * T <= MGEA_FUSED_MAX_ROWS && ((n_head * head_dim) % 32 == 0 || (int64_t)B * T <= 64)),
+                 MGEA_EINVAL, "op_attention: a k-tiled out holds at most %d rows (64 when its width is no multiple of 32)", MGEA_FUSED_MAX_ROWS);
+    return launch_attn_dense(qkv_dev, lens_dev, mask_dev, out_dev, B, T, n_head, head_dim, tiled_out != 0, (hipStream_t)stream, cu_seqlens_dev);
+}
+
 int mgea_op_f32_to_bf16(const float* src_dev, void* dst_dev, int64_t n, void* stream) {
     MGEA_REQUIRE(src_dev && dst_dev && n > 0, MGEA_EINVAL, "op_f32_to_bf16: bad argument");
     return launch_f32_to_bf16(src_dev, dst_dev, n, (hipStream_t)stream);
@@ -368,26 +377,53 @@ int mgea_op_attention_paged(const float* qkv_dev, const void* pages_dev, int32_t
                             const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev, const int32_t* lens_dev,
                             float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t no_split, int32_t* info_out,
                             void* stream) {
+    return mgea_op_attention_paged_ex(qkv_dev, pages_dev, n_pages, 1, 0, dtype, arith_batch, page_table_dev, max_pages, ctx_len_dev, lens_dev,
+                                      out_dev, B, T, n_head, head_dim, 0, no_split, nullptr, 0, nullptr, 0, info_out, stream);
+}
+
+int mgea_op_attn_split_count(int32_t B, int32_t n_head, int32_t T, int32_t max_pages) { return attn_split_count(B, n_head, T, max_pages); }
+
+int mgea_op_attn_split_scratch(int32_t head_dim, int64_t* part_floats_out, int64_t* count_ints_out) {
+    MGEA_REQUIRE(head_dim > 0 && part_floats_out && count_ints_out, MGEA_EINVAL, "op_attn_split_scratch: bad argument");
+    *part_floats_out = (int64_t)MGEA_ATTN_SPLIT_ITEMS * MGEA_ATTN_MAX_SPLIT * attn_part_floats(head_dim);
+    *count_ints_out = MGEA_ATTN_SPLIT_ITEMS;
+    return MGEA_OK;
+}
+
+int mgea_op_attention_paged_ex(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
+                               int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
+                               const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                               int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
+                               int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream) {
     MGEA_REQUIRE(qkv_dev && pages_dev && page_table_dev && ctx_len_dev && out_dev && B > 0 && T > 0 && n_head > 0 && n_pages > 0 &&
                      max_pages > 0 && (dtype == MGEA_DTYPE_F32 || dtype == MGEA_DTYPE_F16),
                  MGEA_EINVAL, "op_attention_paged: bad argument");
+    MGEA_REQUIRE(n_layer > 0 && layer >= 0 && layer < n_layer, MGEA_EINVAL, "op_attention_paged: layer %d of %d", layer, n_layer);
     MGEA_REQUIRE(arith_batch == 0 || (arith_batch >= B && (int64_t)max_pages * arith_batch <= n_pages), MGEA_EINVAL,
                  "op_attention_paged: arith_batch %d must be >= B with max_pages * arith_batch <= n_pages", arith_batch);
+    MGEA_REQUIRE(!tiled_out || ((int64_t)B * T <= MGEA_FUSED_MAX_ROWS && ((n_head * head_dim) % 32 == 0 || (int64_t)B * T <= 64)), MGEA_EINVAL,
+                 "op_attention_paged: a k-tiled out holds at most %d rows (64 when its width is no multiple of 32)", MGEA_FUSED_MAX_ROWS);
+    // n_layer layers of n_pages pages each, the stride the decoder sets (decoder.hip: n_pages * 2 * n_head * page elements)
     const KvPool pool = op_pool(pages_dev, n_pages, n_head, head_dim, dtype == MGEA_DTYPE_F16, arith_batch);
     hipStream_t st = (hipStream_t)stream;
     AttnSplit sp{nullptr, nullptr, MGEA_ATTN_MAX_SPLIT, MGEA_ATTN_SPLIT_ITEMS};
     DevGroup tmp;   // frees the scratch on return: the stream is synchronised first
-    if (!no_split) {
-        const size_t part_bytes = (size_t)sp.max_items * sp.max_split * attn_part_floats(head_dim) * sizeof(float);
-        MGEA_REQUIRE(tmp.alloc(&sp.part, part_bytes) == MGEA_OK, MGEA_ENOMEM, "op_attention_paged: allocation of the split partials failed");
+    const size_t part_floats = (size_t)sp.max_items * sp.max_split * attn_part_floats(head_dim);
+    if (!no_split && (split_part_dev || split_count_dev)) {   // the caller's scratch: neither allocated nor zeroed here (mgea.h)
+        MGEA_REQUIRE(split_part_dev && split_count_dev && split_part_floats >= (int64_t)part_floats && split_count_ints >= sp.max_items, MGEA_EINVAL,
+                     "op_attention_paged: the split scratch needs %lld floats and %d counters", (long long)part_floats, sp.max_items);
+        sp.part = split_part_dev;
+        sp.count = split_count_dev;
+    } else if (!no_split) {
+        MGEA_REQUIRE(tmp.alloc(&sp.part, part_floats * sizeof(float)) == MGEA_OK, MGEA_ENOMEM, "op_attention_paged: allocation of the split partials failed");
         MGEA_REQUIRE(tmp.alloc(&sp.count, (size_t)sp.max_items * sizeof(int32_t)) == MGEA_OK, MGEA_ENOMEM,
                      "op_attention_paged: allocation of the split counters failed");
         MGEA_CHECK_HIP(hipMemsetAsync(sp.count, 0, (size_t)sp.max_items * sizeof(int32_t), st));
     }
     // what the launcher will decide from the same arguments (attn_paged.hip): workgroups per (row, head, query)
     if (info_out) info_out[0] = no_split ? 1 : attn_split_count(B, n_head, T, max_pages);
-    const int rc = launch_attn_paged(qkv_dev, pool, 0, page_table_dev, max_pages, ctx_len_dev, lens_dev, out_dev, B, T, n_head * head_dim, 0,
-                                     st, no_split ? nullptr : &sp);
+    const int rc = launch_attn_paged(qkv_dev, pool, layer, page_table_dev, max_pages, ctx_len_dev, lens_dev, out_dev, B, T, n_head * head_dim,
+                                     tiled_out != 0, st, no_split ? nullptr : &sp);
     const hipError_t e = hipStreamSynchronize(st);
     MGEA_TRY(rc);
     MGEA_CHECK_HIP(e);

@@ -171,6 +171,7 @@ PROTOTYPES = {
     "mgea_op_gemm_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "mgea_op_layernorm": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _P]),
     "mgea_op_attention_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_attention_f32_ex": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),
     "mgea_op_gemm_bf16": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_gemm_bf16_ln": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32), _P]),
@@ -186,6 +187,10 @@ PROTOTYPES = {
     "mgea_op_kv_scatter_f16": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_dec_embed_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "mgea_op_attention_paged": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, C.POINTER(_I32), _P]),
+    "mgea_op_attn_split_count": (C.c_int, [_I32, _I32, _I32, _I32]),
+    "mgea_op_attn_split_scratch": (C.c_int, [_I32, C.POINTER(_I64), C.POINTER(_I64)]),
+    "mgea_op_attention_paged_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
+                                             _P, _I64, _P, _I64, C.POINTER(_I32), _P]),
     "mgea_op_tiled_weight_floats": (C.c_int64, [_I32, _I32]),
     "mgea_op_tile_weights": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "mgea_op_tile_rows": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),

@@ -45,16 +45,35 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float) -> 
 
 
 def attention(qkv: torch.Tensor, n_head: int, lens: Optional[torch.Tensor] = None,
-              mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """qkv [B,T,3C] -> [B,T,C]; non-causal, keys valid per lens / mask."""
+              mask: Optional[torch.Tensor] = None, cu: Optional[torch.Tensor] = None, tiled: bool = False,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qkv [B,T,3C] -> [B,T,C]; non-causal, keys valid per lens / mask.  cu [B + 1] (packed rows): qkv [cu[B], 3C] -> [cu[B], C], T = the
+    longest sequence.  tiled: the output is the flat k-tiled buffer of tiled_floats(B * T, C) floats (untile_rows reads it).  out: a
+    caller buffer of that many floats (B * T * C row-major), written in place and returned.  What the launcher refuses (cu with lens,
+    mask or tiled) is left to the launcher."""
     lib = _lib.load()
     qkv = _dev(qkv.float())
-    B, T, C3 = qkv.shape
-    Cd = C3 // 3
-    out = torch.empty(B, T, Cd, dtype=torch.float32, device=qkv.device)
+    Cd = qkv.shape[-1] // 3
+    c32 = None
+    if cu is not None:
+        c32 = _dev(cu.to(torch.int32))
+        seq = (cu[1:] - cu[:-1]).cpu()
+        B, T = int(seq.numel()), int(seq.max())
+        if qkv.ndim != 2 or int(cu[-1]) != qkv.shape[0]:
+            raise RuntimeError("packed attention: qkv must be [cu[B], 3C]")
+        rows = qkv.shape[0]
+    else:
+        B, T = qkv.shape[0], qkv.shape[1]
+        rows = B * T
+    if out is None:
+        out = (torch.empty(tiled_floats(rows, Cd), dtype=torch.float32, device=qkv.device) if tiled
+               else torch.empty(*qkv.shape[:-1], Cd, dtype=torch.float32, device=qkv.device))
+    else:
+        _buf(out, tiled_floats(rows, Cd) if tiled else rows * Cd, torch.float32, "attention: out")
     l32 = None if lens is None else _dev(lens.to(torch.int32))
     m32 = None if mask is None else _dev(mask.to(torch.int32))
-    check(lib.mgea_op_attention_f32(ptr(qkv), ptr(l32), ptr(m32), ptr(out), B, T, n_head, Cd // n_head, stream_ptr()))
+    check(lib.mgea_op_attention_f32_ex(ptr(qkv), ptr(l32), ptr(m32), ptr(c32), ptr(out), B, T, n_head, Cd // n_head, int(bool(tiled)),
+                                       stream_ptr()))
     return out
 
 
@@ -388,10 +407,15 @@ def dec_embed_f16(ids: torch.Tensor, tok_emb: torch.Tensor, pos_emb: torch.Tenso
 
 def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_table: torch.Tensor, ctx_len: torch.Tensor,
                     lens: Optional[torch.Tensor] = None, arith_batch: int = 0, split: bool = True,
-                    info: Optional[list] = None) -> torch.Tensor:
+                    info: Optional[list] = None, layer: int = 0, n_layer: int = 1, tiled: bool = False,
+                    out: Optional[torch.Tensor] = None, scratch=None) -> torch.Tensor:
     """The decode / extend attention over one layer of device KV pages (fp32 or fp16 tensor): the queries are columns 0..C-1 of the
     fp32 qkv [B, T, 3C]; row b attends to its ctx_len[b] + (lens[b] or T) cached tokens.  split=False: never the split-context form.
-    info: a list that receives [workgroups per (row, head, query)] of the launch (1 = the unsplit kernel)."""
+    info: a list that receives [workgroups per (row, head, query)] of the launch (1 = the unsplit kernel).
+    pages holds n_layer layers of pages (one after the other, as in the decoder's pool) and the kernel reads `layer`.  tiled: the
+    output is the flat k-tiled buffer of tiled_floats(B * T, C) floats.  out: a caller buffer of that size (B * T * C row-major),
+    written in place and returned.  scratch = (part, count) from attn_split_scratch(): the caller's split-context scratch, which the
+    call neither allocates nor zeroes."""
     lib = _lib.load()
     qkv = _dev(qkv.float())
     B, T, C3 = qkv.shape
@@ -399,7 +423,7 @@ def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_ta
     dh = Cd // n_head
     if pages.dtype not in (torch.float32, torch.float16) or not pages.is_contiguous() or pages.device != qkv.device:
         raise RuntimeError("attention_paged: pages must be a contiguous fp32 or fp16 device tensor")
-    n_pages = pages.numel() // kv_page_elems(1, n_head, dh)
+    n_pages = pages.numel() // (kv_page_elems(1, n_head, dh) * int(n_layer))
     pt = _dev(page_table.to(torch.int32))
     if pt.shape[0] != B or int(pt.min()) < 0 or int(pt.max()) >= n_pages:
         raise RuntimeError("attention_paged: page table must be [B, max_pages] with entries in [0, n_pages)")
@@ -408,14 +432,39 @@ def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_ta
     need = int(((cl.cpu() + (T if lens is None else l32.cpu()) + _lib.KV_PAGE_TOKENS - 1) // _lib.KV_PAGE_TOKENS).max())
     if need > pt.shape[1]:
         raise RuntimeError(f"attention_paged: a row needs {need} pages, the table has {pt.shape[1]}")
-    out = torch.empty(B, T, Cd, dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = (torch.empty(tiled_floats(B * T, Cd), dtype=torch.float32, device=qkv.device) if tiled
+               else torch.empty(B, T, Cd, dtype=torch.float32, device=qkv.device))
+    else:
+        _buf(out, tiled_floats(B * T, Cd) if tiled else B * T * Cd, torch.float32, "attention_paged: out")
+    part = count = None
+    if scratch is not None:
+        part, count = scratch
+        _buf(part, 1, torch.float32, "attention_paged: scratch part")
+        _buf(count, 1, torch.int32, "attention_paged: scratch count")
     io = (C.c_int32 * 1)(-1)
-    check(lib.mgea_op_attention_paged(ptr(qkv), ptr(pages), n_pages, _lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32,
-                                      int(arith_batch), ptr(pt), pt.shape[1], ptr(cl), ptr(l32), ptr(out), B, T, n_head, dh,
-                                      int(not split), io, stream_ptr()))
+    check(lib.mgea_op_attention_paged_ex(ptr(qkv), ptr(pages), n_pages, int(n_layer), int(layer),
+                                         _lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32, int(arith_batch), ptr(pt),
+                                         pt.shape[1], ptr(cl), ptr(l32), ptr(out), B, T, n_head, dh, int(bool(tiled)), int(not split),
+                                         ptr(part), 0 if part is None else part.numel(), ptr(count), 0 if count is None else count.numel(),
+                                         io, stream_ptr()))
     if info is not None:
         info[:] = [int(io[0])]
     return out
+
+
+def attn_split_count(B: int, n_head: int, T: int, max_pages: int) -> int:
+    """the launcher's choice of workgroups per (row, head, query) for a paged launch that has a split scratch (host arithmetic)"""
+    return int(_lib.load().mgea_op_attn_split_count(int(B), int(n_head), int(T), int(max_pages)))
+
+
+def attn_split_scratch(head_dim: int, device="cuda"):
+    """-> (part, count): a split-context scratch for attention_paged(scratch=...) -- part [items, splits, head_dim + 2] fp32 filled
+    with poison, count [items] int32 ZERO (the one zeroing the kernel's contract asks for)."""
+    pf, ci = C.c_int64(0), C.c_int64(0)
+    check(_lib.load().mgea_op_attn_split_scratch(int(head_dim), C.byref(pf), C.byref(ci)))
+    part = poison(pf.value, device=device).view(ci.value, -1, int(head_dim) + 2)
+    return part, torch.zeros(ci.value, dtype=torch.int32, device=device)
 
 
 def window_evict(page_table: torch.Tensor, sink_pages: int, ring_pages: int, ctx_len: torch.Tensor, done: torch.Tensor,

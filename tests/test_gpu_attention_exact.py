@@ -31,18 +31,18 @@ FAMILIES = ("pointer", "poison", "histogram")
 
 
 # ---- the input families (host, fp64 holding 16-bit-exact values) --------------------------------------------------------------
-def _code(idx, dh):
-    """+-1 code of the key index: bit j on dims j r .. j r + r - 1, r = dh // NBITS; the remaining dims are 0"""
-    r = dh // NBITS
-    bits = ((np.asarray(idx)[..., None] >> np.arange(NBITS)) & 1) * 2 - 1
+def _code(idx, dh, nbits=NBITS):
+    """+-1 code of the key index: bit j on dims j r .. j r + r - 1, r = dh // nbits; the remaining dims are 0"""
+    r = dh // nbits
+    bits = ((np.asarray(idx)[..., None] >> np.arange(nbits)) & 1) * 2 - 1
     out = np.zeros(np.asarray(idx).shape + (dh,))
-    out[..., :NBITS * r] = np.repeat(bits, r, axis=-1)
+    out[..., :nbits * r] = np.repeat(bits, r, axis=-1)
     return out
 
 
-def _beta(dh):
+def _beta(dh, nbits=NBITS):
     """smallest power of two with a scaled score gap 2 r beta / sqrt(dh) >= 20 between key pi(i) and any other key"""
-    r = dh // NBITS
+    r = dh // nbits
     return 2.0 ** math.ceil(math.log2(20.0 * math.sqrt(dh) / (2 * r)))
 
 
@@ -72,13 +72,15 @@ def _v_rows(B, T, H, dh, b0=0):
     return ((7 * t + 3 * d + 5 * h + 11 * b) % 33 - 16) / 8.0
 
 
-def _family(family, valid, H, dh, Tq=None, b0=0, q_targets=None):
+def _family(family, valid, H, dh, Tq=None, b0=0, q_targets=None, nbits=NBITS):
     """-> q [B, Tq, H, dh], k, v [B, T, H, dh], expected [B, Tq, H, dh] (fp64 arrays).  valid [B, T] bool; Tq queries per row (None: T).
-    q_targets[b][h][i] (pointer only): the key query (b, h, i) points at; None: cycle through _targets()."""
+    q_targets[b][h][i] (pointer only): the key query (b, h, i) points at; None: cycle through _targets().
+    nbits: index bits of the pointer code (rows of up to 2^nbits keys); the default keeps every earlier case bit-identical."""
     B, T = valid.shape
+    assert T <= 2 ** nbits, f"{T} keys need more than {nbits} index bits"
     Tq = T if Tq is None else Tq
     if family == "pointer":
-        k = np.broadcast_to(_code(np.arange(T), dh)[None, :, None, :], (B, T, H, dh)).copy()
+        k = np.broadcast_to(_code(np.arange(T), dh, nbits)[None, :, None, :], (B, T, H, dh)).copy()
         v = _v_rows(B, T, H, dh, b0)
         pi = np.zeros((B, Tq, H), dtype=np.int64)
         for b in range(B):
@@ -89,7 +91,7 @@ def _family(family, valid, H, dh, Tq=None, b0=0, q_targets=None):
                     L = _targets(valid[b])
                     pi[b, :, h] = [L[(i + 3 * h) % len(L)] for i in range(Tq)]
         assert all(valid[b, pi[b]].all() for b in range(B))
-        q = _beta(dh) * _code(pi, dh)
+        q = _beta(dh, nbits) * _code(pi, dh, nbits)
         exp = np.stack([np.stack([v[b, pi[b, :, h], h] for h in range(H)], 1) for b in range(B)])
         return q, k, v, exp
     if family == "poison":
@@ -100,7 +102,7 @@ def _family(family, valid, H, dh, Tq=None, b0=0, q_targets=None):
         return q, k, v, np.ones((B, Tq, H, dh))
     assert family == "histogram"
     q = np.zeros((B, Tq, H, dh))
-    k = np.broadcast_to(_code(np.arange(T), dh)[None, :, None, :], (B, T, H, dh)).copy()
+    k = np.broadcast_to(_code(np.arange(T), dh, nbits)[None, :, None, :], (B, T, H, dh)).copy()
     v = np.zeros((B, T, H, dh))
     exp = np.zeros((B, Tq, H, dh))
     for b in range(B):
@@ -348,22 +350,27 @@ def _page_setup(B, n_head, dh, pdtype, arith, seed):
     return image, table, (B if arith else 0)
 
 
-@functools.lru_cache(maxsize=None)
-def _paged_cases(family, lens_total, Tq, H, dh):
-    """the launches of one family: one Case per round of pointer targets (a launch has only B * H * Tq queries)"""
+def _paged_case_iter(family, lens_total, Tq, H, dh, nbits=NBITS):
+    """the launches of one family, one at a time: one Case per round of pointer targets (a launch has only B * H * Tq queries); K | V
+    are the same in every round"""
     L = max(lens_total)
     valid = np.arange(L)[None, :] < np.asarray(lens_total)[:, None]
     if family != "pointer":
-        return [Case(family, valid, H, dh, Tq=Tq)]
+        yield Case(family, valid, H, dh, Tq=Tq, nbits=nbits)
+        return
     per_row = [_targets(valid[b], extra=[127, 128, 255, 256, 511, 512, 767, 768, (n - 1) // 64 * 64, n - 2])
                for b, n in enumerate(lens_total)]
     per_launch = H * Tq
     rounds = max((len(t) + per_launch - 1) // per_launch for t in per_row)
-    out = []
     for r in range(rounds):
         tg = [[[t[(r * per_launch + h * Tq + i) % len(t)] for i in range(Tq)] for h in range(H)] for t in per_row]
-        out.append(Case(family, valid, H, dh, Tq=Tq, q_targets=tg))
-    return out
+        yield Case(family, valid, H, dh, Tq=Tq, q_targets=tg, nbits=nbits)
+
+
+@functools.lru_cache(maxsize=None)
+def _paged_cases(family, lens_total, Tq, H, dh, nbits=NBITS):
+    """the launches of one family, kept (the small shapes are shared between tests)"""
+    return list(_paged_case_iter(family, lens_total, Tq, H, dh, nbits))
 
 
 def _run_paged(case, pdtype, arith, split, ctx_len, lens, seed):
