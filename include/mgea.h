@@ -490,6 +490,62 @@ int mgea_decoder_generate_rows_blended(mgea_decoder* h, const int32_t* prompt_id
 /* out[0] the groups, [1] the grouped rows and [2] the blended decode steps of the last generation (all 0 if it was not blended). */
 int mgea_decoder_blend_info(mgea_decoder* h, int64_t* out /* [3] */);
 
+/* Windowed penalties over token CLASSES (build-defined; the reference has only the id-level repetition_penalty).  In this vocabulary
+ * an id is a whole note line with its absolute START, so an id recurs only as a literal duplicate: what a listener hears as
+ * repetition -- the same pitches, the same rhythm -- lives in attributes of the id.  The engine holds one map class_of [vocab] int32
+ * with values in [-1, n_class), 1 <= n_class <= vocab (mgea_decoder_set_penalty_classes); an id of class -1 is in no class: it is
+ * never counted and never penalised (instruments, EOS, control tokens).  With the identity map the rule is the frequency_penalty /
+ * presence_penalty over ids of other engines.
+ * Row b at t = row_step[b], not finished, with a record that is on (frequency != 0 || presence != 0); g_0 .. g_{t-1} the ids the
+ * row's steps took (a forced id is a taken id; prompt tokens are conditioning tokens and are NOT counted):
+ *   lo  = window > 0 ? max(0, t - window) : 0
+ *   n_c = #{ j in [lo, t) : class_of[g_j] == c }, an exact integer (a history entry outside [0, vocab) is skipped)
+ *   for every id i with c = class_of[i] >= 0 and n_c > 0, in fp32, three separately rounded operations, never contracted:
+ *     m = frequency * (float)n_c;   d = m + presence;   x[i] = x[i] - d
+ * and nothing else is written, bit for bit: a finished row, a row whose record is off, t == 0, ids of class -1 and ids of classes
+ * with n_c == 0 keep their logits.  This is STEP 0b of the per-step order: behind the guidance and blend mixes of step 0, in front
+ * of step 1, the id-level repetition penalty; the result is the row the sampler reads.  In a scored generation logprobs_out is
+ * therefore the log-softmax of the class-penalised row, as it is of the mixed row under guidance.  Negative values favour the
+ * counted classes.  Under a KV window the counts follow the row's id history, not its cache: tokens whose pages were evicted still
+ * count while they are inside `window`.  A guidance shadow row takes its conditional row's record and a blend member its leader's
+ * (their histories are the same ids), so the rows of a pair or group keep computing one function. */
+#define MGEA_CLASS_PENALTY_MAX_WINDOW 4096
+typedef struct mgea_row_class_penalty {
+    float   frequency;   /* finite, |.| <= 1e4 */
+    float   presence;    /* finite, |.| <= 1e4 */
+    int32_t window;      /* the last `window` generated ids are counted; 0 = all of them */
+    int32_t reserved;    /* 0 */
+} mgea_row_class_penalty;
+
+/* Sets (copies) the class map: class_of_host [vocab] with values in [-1, n_class), 1 <= n_class <= vocab, else MGEA_EINVAL naming
+ * the first bad id.  class_of_host == NULL clears it.  The map and the rows' device records are allocated by this call and by nothing
+ * else.  Synchronises `stream` and drops the class-penalised step graphs (n_class travels in their kernel arguments). */
+int mgea_decoder_set_penalty_classes(mgea_decoder* h, const int32_t* class_of_host, int32_t n_class, void* stream);
+
+/* mgea_decoder_generate_rows_blended with one mgea_row_class_penalty per row, cpen [B] (host memory, read before the call returns).
+ * cpen == NULL, or every record off, IS mgea_decoder_generate_rows_blended: the same launches, the same graphs, the same ids.
+ * Checked on the host before anything is enqueued (MGEA_EINVAL naming the row): both values finite with |.| <= 1e4; window in
+ * [0, MGEA_CLASS_PENALTY_MAX_WINDOW]; reserved == 0; a row that is on with window == 0 needs n_steps <=
+ * MGEA_CLASS_PENALTY_MAX_WINDOW; a row that is on needs a class map.  Otherwise every step is the launch sequence it would be
+ * with ONE more launch, the class penalty (class_penalty.hip), behind the mixes and in front of the sampler; "class_penalized" is
+ * part of the step-graph key, and the records live in a device vector the handle owns, so a request with other values, windows or
+ * rows replays the cached graphs.  A class-penalised generation never takes the greedy form: all-greedy rows run as top_k == 1
+ * records of the sampled form. */
+int mgea_decoder_generate_rows_class_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev /* [n_seg_max][B][Tp] */,
+                                               const int32_t* lens_dev, int32_t B, int32_t Tp, int32_t n_steps,
+                                               const mgea_row_sampler* rows, const mgea_row_logits* logits_rows /* NULL ok */,
+                                               const int32_t* start_states /* host [B], -1 = none; NULL ok */,
+                                               const mgea_row_guidance* guide /* host [B]; NULL ok */,
+                                               const mgea_row_schedule* sched /* host [B]; NULL ok */, int32_t n_seg_max,
+                                               const int32_t* forced_ids_dev /* NULL ok */, int32_t* ids_out_dev,
+                                               float* logprobs_out_dev /* NULL = unscored */, float* choice_logprobs_out_dev /* NULL ok */,
+                                               const mgea_row_truncation* trunc /* host [B]; NULL ok */,
+                                               const mgea_row_blend* blend /* host [B]; NULL ok */,
+                                               const mgea_row_class_penalty* cpen /* host [B]; NULL ok */, void* stream);
+/* out[0] the n_class of the map that is set (0 = none), [1] the rows that were on and [2] the class-penalised decode steps of the
+ * last generation (both 0 if it was not class-penalised). */
+int mgea_decoder_class_penalty_info(mgea_decoder* h, int64_t* out /* [3] */);
+
 /* The presence bitmaps of the last penalized generation -> bits_out_dev [B][ceil(vocab / 32)] uint32 (device): bit id & 31 of word
  * id >> 5 of row b is set iff id is in seen_b (including the step at which the row drew eos_id).  MGEA_EINVAL if the last
  * generate applied no penalty (a biased generation keeps the bitmaps too). */
@@ -915,6 +971,13 @@ int mgea_op_guidance_mix(float* logits_dev, int32_t B, int32_t V, const int32_t*
  * in that order, written into all of them; every other row is left as it is.  leader_dev int32 [B], weight_dev fp32 [B] (device).
  * The caller guarantees the group rules of mgea_decoder_generate_rows_blended and finite logits; V <= 14336, else MGEA_EINVAL. */
 int mgea_op_blend_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* leader_dev, const float* weight_dev, void* stream);
+/* The class penalty of a class-penalised decode step (mgea_row_class_penalty, step 0b), alone and IN PLACE on logits_dev [B, V] fp32.
+ * class_of_dev int32 [V] with values in [-1, n_class); hist_dev int32 [B][stride], row b's taken ids at hist_dev[b * stride + j];
+ * row_step_dev / done_dev int32 [B] (device); recs_host [B] (host, checked like a call's records, MGEA_EINVAL naming the row).  The
+ * caller guarantees row_step[b] <= stride.  V <= 14336, 1 <= n_class <= V, stride > 0, else MGEA_EINVAL.  Synchronises `stream`. */
+int mgea_op_class_penalty(float* logits_dev, int32_t B, int32_t V, const int32_t* class_of_dev, int32_t n_class, const int32_t* hist_dev,
+                          int32_t stride, const int32_t* row_step_dev, const int32_t* done_dev, const mgea_row_class_penalty* recs_host,
+                          void* stream);
 /* The two kernels of a scheduled generation (mgea_row_schedule), alone on caller buffers.  pool_dev: a KV pool
  * [n_layer][n_pages][K | V][H][64 x dh] of fp32 (f16 == 0) or fp16 (f16 == 1) elements in the page layouts of csrc/common.h; row b's
  * logical page 0 is physical page b when arith_batch > 0 and page_table_dev[b * max_pages] otherwise.  store_dev: the conditioning

@@ -200,9 +200,33 @@ def create_blended_app(model, seq_len: int, temperature: float = 1.0, top_k: int
                       truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
 
 
+def create_varied_app(model, seq_len: int, temperature: float = 1.0, top_k: int = 50, top_p=None, repetition_penalty=None,
+                      constrain=None, out_of_scale_bias=float("-inf"), min_new_tokens: int = 0, grammar=None, classes="pitch",
+                      frequency_penalty: float = 0.0, presence_penalty: float = 0.0, penalty_window: int = 32,
+                      min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+    """create_grammar_app (grammar defaults to None here) with a windowed penalty over an attribute of the notes for every request
+    (generate_music.generate.sample_kvcache_varied; build-defined, the reference has only the id-level repetition_penalty).
+    classes: "pitch", "pitch_class", "duration", "pitch_duration" or "id" (generate_music.variety.token_classes); with n_c the number
+    of the last penalty_window generated tokens (0 = all of them) of class c, every token of a class with n_c > 0 loses
+    frequency_penalty * n_c + presence_penalty from its logit; negative values keep the piece near what it has been using.  A value
+    that is not finite or beyond +-1e4, a window outside [0, 4096] and an unknown `classes` are ValueErrors here.  The response
+    carries X-Penalty-Classes, X-Frequency-Penalty, X-Presence-Penalty and X-Penalty-Window.
+    min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off): HuggingFace's further cuts behind top-k and top-p, for every request
+    (mgea.decoder.Truncation; a value out of range is a ValueError here)."""
+    from generate_music.variety import KINDS
+    from mgea.decoder import ClassPenalty
+    if classes not in KINDS:
+        raise ValueError(f"classes must be one of {KINDS}, got {classes!r}")
+    cp = ClassPenalty(float(frequency_penalty), float(presence_penalty), int(penalty_window))
+    cp.check(0, max(int(seq_len), 0))
+    return _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests=False, constrain=constrain,
+                      out_of_scale_bias=out_of_scale_bias, min_new_tokens=min_new_tokens, grammar=grammar, variety=(classes, cp),
+                      truncation=dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
+
+
 def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, batch_requests, max_batch=None, constrain=None,
                out_of_scale_bias=float("-inf"), min_new_tokens=0, best_of=0, grammar=None, window=None, guidance_scale=None,
-               transitions=False, truncation=None, blend=None):
+               transitions=False, truncation=None, blend=None, variety=None):
     from mgea.decoder import Truncation
     from mgea.ops import check_repetition_penalty
     check_repetition_penalty(repetition_penalty)   # a bad value fails here, not at the first request
@@ -334,6 +358,17 @@ def _build_app(model, seq_len, temperature, top_k, top_p, repetition_penalty, ba
                                                min_new_tokens=int(min_new_tokens), grammar=tg, guidance_scale=guidance_scale,
                                                **trunc_kw)
             extra["X-Guidance-Scale"] = f"{guidance_scale:g}"
+        elif variety is not None:   # the request's own row, its logits lowered by the classes of its recent notes
+            classes, cp = variety
+            tokens = gen.sample_kvcache_varied(model, gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, device="cpu",
+                                               top_p=top_p, repetition_penalty=repetition_penalty, logit_bias=bias,
+                                               min_new_tokens=int(min_new_tokens), grammar=tg, classes=classes,
+                                               frequency_penalty=cp.frequency, presence_penalty=cp.presence,
+                                               penalty_window=cp.window, **trunc_kw)
+            extra["X-Penalty-Classes"] = classes
+            extra["X-Frequency-Penalty"] = f"{cp.frequency:g}"
+            extra["X-Presence-Penalty"] = f"{cp.presence:g}"
+            extra["X-Penalty-Window"] = str(cp.window)
         elif app.state.batcher is not None:   # the same request, served inside whatever batch is forming
             fut = app.state.batcher.submit(gen_prompt, max_len=seq_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                            repetition_penalty=repetition_penalty, **more, **trunc_kw)

@@ -588,6 +588,33 @@ int mgea_op_blend_mix(float* logits_dev, int32_t B, int32_t V, const int32_t* le
     return launch_blend_mix(logits_dev, B, V, leader_dev, weight_dev, (hipStream_t)stream);
 }
 
+int mgea_op_class_penalty(float* logits_dev, int32_t B, int32_t V, const int32_t* class_of_dev, int32_t n_class, const int32_t* hist_dev,
+                          int32_t stride, const int32_t* row_step_dev, const int32_t* done_dev, const mgea_row_class_penalty* recs_host,
+                          void* stream) {
+    MGEA_REQUIRE(logits_dev && class_of_dev && hist_dev && row_step_dev && done_dev && recs_host && B > 0, MGEA_EINVAL,
+                 "op_class_penalty: NULL argument or empty batch");
+    MGEA_REQUIRE(V > 0 && V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "op_class_penalty: vocab %d exceeds the sampler's row (%d)", V,
+                 MGEA_SAMPLER_MAX_VOCAB);
+    MGEA_REQUIRE(n_class >= 1 && n_class <= V, MGEA_EINVAL, "op_class_penalty: n_class %d outside [1, %d]", n_class, V);
+    MGEA_REQUIRE(stride > 0, MGEA_EINVAL, "op_class_penalty: history stride %d must be > 0", stride);
+    int n_on = 0;
+    MGEA_TRY(check_row_class_penalty(recs_host, B, -1, n_class, "op_class_penalty", &n_on));
+    hipStream_t st = (hipStream_t)stream;
+    mgea_row_class_penalty* recs_dev = nullptr;
+    DevGroup g;   // nothing is enqueued before the allocation, and the stream is synchronised before it is freed
+    MGEA_REQUIRE(g.alloc(&recs_dev, (size_t)B * sizeof(mgea_row_class_penalty)) == MGEA_OK, MGEA_ENOMEM,
+                 "op_class_penalty: allocation of the records failed");
+    int rc = MGEA_EHIP;
+    if (hipMemcpyAsync(recs_dev, recs_host, (size_t)B * sizeof(mgea_row_class_penalty), hipMemcpyHostToDevice, st) == hipSuccess)
+        rc = launch_class_penalty(logits_dev, B, V, class_of_dev, n_class, hist_dev, stride, row_step_dev, done_dev, recs_dev, st);
+    else
+        set_error("op_class_penalty: copy of the records failed");
+    const hipError_t e = hipStreamSynchronize(st);
+    MGEA_TRY(rc);
+    MGEA_CHECK_HIP(e);
+    return MGEA_OK;
+}
+
 int mgea_op_recondition(void* pool_dev, int32_t n_layer, int32_t n_pages, int32_t H, int32_t dh, int32_t f16, int32_t arith_batch,
                         const int32_t* page_table_dev, int32_t max_pages, void* store_dev, int32_t n_seg_max, int32_t slot_tokens,
                         int32_t* meta_dev, int32_t* len_dev, int32_t B, int32_t gather_seg, const int32_t* lens_dev,

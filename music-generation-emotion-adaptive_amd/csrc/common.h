@@ -309,6 +309,12 @@ int launch_guidance_mix(float* logits, int B, int V, const int32_t* partner, con
 // leader names itself and that a group has at most MGEA_BLEND_MAX_ROWS rows (one workgroup per group is then the only one that touches
 // its rows).
 int launch_blend_mix(float* logits, int B, int V, const int32_t* leader, const float* weight, hipStream_t st);
+// Windowed penalties over token classes on logits [B, V], in place (class_penalty.hip; the rule: include/mgea.h, mgea_row_class_penalty):
+// row b, not finished and with recs[b] on, counts the classes class_of[.] of hist[b * stride + j], j in the last recs[b].window of
+// [0, row_step[b]), and subtracts frequency * n_c + presence from every id of a counted class.  class_of [V] in [-1, n_class); recs,
+// row_step, done: device [B].  The caller guarantees row_step[b] <= stride.
+int launch_class_penalty(float* logits, int B, int V, const int32_t* class_of, int n_class, const int32_t* hist, int stride,
+                         const int32_t* row_step, const int32_t* done, const mgea_row_class_penalty* recs, hipStream_t st);
 // Emotion transitions (recondition.hip; the rule and the store's layout: include/mgea.h, mgea_row_schedule / mgea_op_recondition).
 // gather: positions [0, lens[b]) (lens NULL: Tp) of logical page 0 of every row, layer and head -> the slots of segment `seg` of the
 // conditioning store, and the layout words / the rows' lengths -> meta [4] / cond_len [B].  apply: the launch that opens a scheduled

@@ -90,10 +90,12 @@ struct mgea_decoder {
     DevGroup dev_p16_mats;   // Prefill16's matrices p16.w / p16.vec, kept across refresh_weights
     DevGroup dev_win;        // the KV window's histories and eviction counters: mgea_decoder_set_window, until the window changes
     DevGroup dev_cond;       // the conditioning store, the rows' schedules and segments: scheduled generations only (ensure_cond)
+    DevGroup dev_cpen;       // the penalty class map and the rows' class-penalty records: mgea_decoder_set_penalty_classes, until it is cleared
     // The handle's other HIP resources, declared behind the device groups, so that they go first (members die in reverse order):
     // the graphs, the pinned staging arrays and the events, then the device memory.
     Event stage_free;        // recorded after the copy out of samp_stage / gram_stage: they may be rewritten once it has completed
     PinnedGroup pinned;      // samp_stage, gram_stage, guide_stage, cond_stage, trunc_stage, blend_stage
+    PinnedGroup pinned_cpen; // cpen_stage: with dev_cpen
 
     // KV pool
     KvPool kv{};
@@ -175,6 +177,13 @@ struct mgea_decoder {
     int32_t* blend_leader = nullptr;
     float* blend_weight = nullptr;
     int32_t* blend_stage = nullptr;
+    // Windowed penalties over token classes (mgea_decoder_generate_rows_class_penalized; class_penalty.hip).  Everything here belongs to
+    // dev_cpen / pinned_cpen and is allocated by mgea_decoder_set_penalty_classes, never by create: cpen_class [vocab] the map (values in
+    // [-1, cpen_n_class)), cpen_dev [max_batch] the rows' records, filled per call through the pinned cpen_stage (free under stage_free
+    // like the records), so the class-penalised graphs hold stable pointers and a request with other values or windows replays them.
+    int32_t* cpen_class = nullptr;
+    mgea_row_class_penalty *cpen_dev = nullptr, *cpen_stage = nullptr;
+    int cpen_n_class = 0;
     // Emotion transitions (mgea_decoder_generate_rows_scheduled; recondition.hip).  Everything here belongs to dev_cond and is allocated by
     // the first scheduled call, never by create: cond_store holds the K | V of positions [0, len_b) of every prompt variant (cond_bytes
     // of it; a call that needs more synchronises, drops the scheduled graphs and regrows the whole group), cond_sched [max_batch] the
@@ -206,7 +215,7 @@ struct mgea_decoder {
         bool penalized = false;   // it applied a penalty (or a bias): presence holds its rows
         bool scheduled = false;   // it was scheduled: cond_cur_seg / cond_switches hold its rows
         int64_t graph_replays = 0, scored_steps = 0, penalized_steps = 0, biased_steps = 0, gram_steps = 0, guide_pairs = 0, guide_steps = 0,
-                sched_steps = 0, trunc_steps = 0, trunc_rows = 0, blend_groups = 0, blend_rows = 0, blend_steps = 0;
+                sched_steps = 0, trunc_steps = 0, trunc_rows = 0, blend_groups = 0, blend_rows = 0, blend_steps = 0, cpen_rows = 0, cpen_steps = 0;
     } last;
     // what mgea_decoder_stats reports of the handle's lifetime, besides the graph cache's own two figures
     struct Counters { int64_t graph_nodes = 0, prefill16_forwards = 0; } n;
@@ -534,8 +543,8 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
     const StepState s{h->cur_ids, h->ctx_len, h->done, h->row_step, h->n_done, hi.ids, hi.stride, k.pv.eos_id, k.pd};
     const TailArgs t = tail_args(h, s, k.primed ? k.qkv0 : nullptr);
     if (k.kind.form == StepForm::GREEDY) {
-        MGEA_REQUIRE(!k.kind.scored && !k.kind.guided && !k.kind.blended, MGEA_EINVAL,
-                     "internal: a scored, guided or blended step never takes the greedy form");
+        MGEA_REQUIRE(!k.kind.scored && !k.kind.guided && !k.kind.blended && !k.kind.class_penalized, MGEA_EINVAL,
+                     "internal: a scored, guided, blended or class-penalised step never takes the greedy form");
         if (k.primed)
             PROF(PC_SAMPLE, launch_argmax_advance_embed(h->pmax_val, h->pmax_idx, n_partials, t, h->sampled, B, st));
         else if (n_partials > 0)
@@ -548,6 +557,9 @@ int enqueue_tail(mgea_decoder* h, const StepCall& k, float* lg, int n_partials, 
     if (k.kind.guided) PROF(PC_SAMPLE, launch_guidance_mix(lg, B, V, h->guide_partner, h->guide_scale, st));
     // blended: every group's logits rows become the group's mixed row (pairs and groups share no row: either order gives the same rows)
     if (k.kind.blended) PROF(PC_SAMPLE, launch_blend_mix(lg, B, V, h->blend_leader, h->blend_weight, st));
+    // class-penalised: behind the mixes (step 0b), every row that is on subtracts its windowed class counts from the row the sampler reads
+    if (k.kind.class_penalized)
+        PROF(PC_SAMPLE, launch_class_penalty(lg, B, V, h->cpen_class, h->cpen_n_class, hi.ids, hi.stride, h->row_step, h->done, h->cpen_dev, st));
     uint32_t* pres = form_has_presence(k.kind.form) ? h->presence : nullptr;
     SampleCall sc{};
     sc.logits = lg; sc.B = B; sc.V = V;
@@ -670,6 +682,7 @@ int ensure_qkv0(mgea_decoder* h, int path, hipStream_t st) {
 // previous tail's layer-0 K | V alive: kv_window.hip); the node does not depend on the step's form.
 // guided: the step mixes the pairs' logits rows between the head and the sampler (enqueue_tail); one more node, whatever the pairs are.
 // blended: likewise the groups' logits rows, in a launch of its own behind the pairs'; one more node, whatever the groups are.
+// class_penalized: the class-penalty launch behind both mixes; one more node, whatever the records are.
 // scheduled: behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip): a row whose segment changes
 // gets the new variant's K | V over positions [0, len_b) of its pages before anything of the step reads them; one more node, whatever
 // the records say.  (The previous tail's layer-0 K | V of the fed token sits at position ctx_len >= len_b: never in its way.)
@@ -1209,15 +1222,15 @@ int ensure_cond(mgea_decoder* h, int64_t bytes, hipStream_t st) {
 // do_generate runs a GenRequest (gen_plan.h) in five phases, each a function of the request and its plan; the caller holds h->mu.
 GenLimits gen_limits(const mgea_decoder* h) {
     const auto& c = h->cfg;
-    return GenLimits{c.vocab, c.max_batch, c.max_ctx, c.block_mode, h->win_S, h->win_R, h->win_max_steps, h->gram_n_state};
+    return GenLimits{c.vocab, c.max_batch, c.max_ctx, c.block_mode, h->win_S, h->win_R, h->win_max_steps, h->gram_n_state, h->cpen_n_class};
 }
 
 // A guidance shadow row runs on its conditional row's inputs -- same inputs, same id --, a non-leader member of a blend group on its
 // leader's, and this is the one place that hands them over.
 // `part` names what the caller has just filled for the callers' rows:
 //   PRESENCE  the seeded bitmaps: a pair's set is the conditional prompt plus the generated ids, and both tails add the same ids
-//   RECORDS   the pinned staging arrays: the sampler record -- seed, Philox stream, budget and all --, the grammar start state and the
-//             truncation record
+//   RECORDS   the pinned staging arrays: the sampler record -- seed, Philox stream, budget and all --, the grammar start state, the
+//             truncation record and the class-penalty record (the rows are fed the same ids: the same counts, the same function)
 //   BIAS      the engine's bias rows: the shadow adds its conditional row's vector (its record says bias_on as that one's does)
 //   FORCED    the engine's forced-id rows: the shadow is told the ids its conditional row is told
 enum class Mirror { PRESENCE, RECORDS, BIAS, FORCED };
@@ -1242,6 +1255,7 @@ int mirror_shadow_rows(mgea_decoder* h, const GenRequest& q, const GenPlan& p, M
             h->samp_stage[u] = h->samp_stage[b];
             if (p.grammar) h->gram_stage[u] = q.start_states[b];
             if (p.truncated) h->trunc_stage[u] = h->trunc_stage[b];
+            if (p.kind.class_penalized) h->cpen_stage[u] = h->cpen_stage[b];
             break;
         case Mirror::BIAS:
             if (h->samp_stage[b].bias_on)
@@ -1312,6 +1326,7 @@ int gen_stage(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_
         build_row_records(q.rows, q.lrows, B, q.n_steps, h->samp_stage);
         for (int b = 0; p.grammar && b < B; ++b) h->gram_stage[b] = q.start_states[b];
         for (int b = 0; p.truncated && b < B; ++b) h->trunc_stage[b] = q.trunc[b];
+        for (int b = 0; p.kind.class_penalized && b < B; ++b) h->cpen_stage[b] = q.cpen[b];
         MGEA_TRY(mirror_shadow_rows(h, q, p, Mirror::RECORDS, st));
         for (int b = 0; p.biased && b < B; ++b)
             if (q.lrows[b].bias_dev)   // the row's vector -> its row of the engine's buffer, which the graphs point at
@@ -1323,6 +1338,8 @@ int gen_stage(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStream_
             MGEA_CHECK_HIP(hipMemcpyAsync(h->gram_state, h->gram_stage, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (p.truncated)
             MGEA_CHECK_HIP(hipMemcpyAsync(h->trunc_dev, h->trunc_stage, (size_t)B * sizeof(mgea_row_truncation), hipMemcpyHostToDevice, st));
+        if (p.kind.class_penalized)
+            MGEA_CHECK_HIP(hipMemcpyAsync(h->cpen_dev, h->cpen_stage, (size_t)B * sizeof(mgea_row_class_penalty), hipMemcpyHostToDevice, st));
         if (p.kind.guided) {   // the pairs and their scales: the guided graphs read the engine's two vectors
             float* scale_stage = reinterpret_cast<float*>(h->guide_stage + c.max_batch);
             for (int b = 0; b < B; ++b) {
@@ -1452,6 +1469,8 @@ int do_generate(mgea_decoder* h, const GenRequest& q, hipStream_t st) {
     last.blend_groups = p.n_groups;
     last.blend_rows = p.n_blend_rows;
     last.blend_steps = p.kind.blended ? launched : 0;
+    last.cpen_rows = p.n_cpen;
+    last.cpen_steps = p.kind.class_penalized ? launched : 0;
     h->last = last;
     return gen_finish(h, q, p, launched, st);
 }
@@ -1586,6 +1605,71 @@ int mgea_decoder_generate_rows_blended(mgea_decoder* h, const int32_t* prompt_id
     q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max; q.trunc = trunc; q.blend = blend;
     q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
     return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_generate_rows_class_penalized(mgea_decoder* h, const int32_t* prompt_ids_dev, const int32_t* lens_dev, int32_t B, int32_t Tp,
+                                               int32_t n_steps, const mgea_row_sampler* rows, const mgea_row_logits* logits_rows,
+                                               const int32_t* start_states, const mgea_row_guidance* guide, const mgea_row_schedule* sched,
+                                               int32_t n_seg_max, const int32_t* forced_ids_dev, int32_t* ids_out_dev,
+                                               float* logprobs_out_dev, float* choice_logprobs_out_dev, const mgea_row_truncation* trunc,
+                                               const mgea_row_blend* blend, const mgea_row_class_penalty* cpen, void* stream) {
+    GenRequest q = rows_request(cpen    ? "decoder_generate_rows_class_penalized"
+                                : blend ? "decoder_generate_rows_blended"
+                                : trunc ? "decoder_generate_rows_truncated"
+                                        : "decoder_generate_rows_scheduled",
+                                prompt_ids_dev, lens_dev, B, Tp, n_steps, rows, logits_rows, ids_out_dev);
+    q.start_states = start_states; q.guide = guide; q.sched = sched; q.n_seg_max = n_seg_max; q.trunc = trunc; q.blend = blend; q.cpen = cpen;
+    q.forced = forced_ids_dev; q.logprobs_out = logprobs_out_dev; q.choice_out = choice_logprobs_out_dev;
+    return generate_rows(h, q, stream);
+}
+
+int mgea_decoder_class_penalty_info(mgea_decoder* h, int64_t* out) {
+    MGEA_REQUIRE(h && out, MGEA_EINVAL, "decoder_class_penalty_info: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->cpen_n_class; out[1] = h->last.cpen_rows; out[2] = h->last.cpen_steps;
+    return MGEA_OK;
+}
+
+int mgea_decoder_set_penalty_classes(mgea_decoder* h, const int32_t* class_of_host, int32_t n_class, void* stream) {
+    MGEA_REQUIRE(h, MGEA_EINVAL, "decoder_set_penalty_classes: NULL handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const int V = h->cfg.vocab;
+    auto clear = [&]() {
+        h->graphs.drop_if([](const StepGraphs::Key& k) { return k.kind.class_penalized; });
+        h->dev_cpen.release();
+        h->pinned_cpen.release();
+        h->cpen_n_class = 0;
+    };
+    if (!class_of_host) {   // clear
+        if (!h->cpen_class) return MGEA_OK;
+        MGEA_CHECK_HIP(hipStreamSynchronize(st));   // a dropped exec may still be replaying, a freed map still be read
+        clear();
+        return MGEA_OK;
+    }
+    MGEA_REQUIRE(V <= MGEA_SAMPLER_MAX_VOCAB, MGEA_EINVAL, "decoder_set_penalty_classes: vocab %d exceeds the sampler's row (%d)", V,
+                 MGEA_SAMPLER_MAX_VOCAB);
+    MGEA_REQUIRE(n_class >= 1 && n_class <= V, MGEA_EINVAL, "decoder_set_penalty_classes: n_class %d outside [1, %d]", n_class, V);
+    for (int i = 0; i < V; ++i)
+        MGEA_REQUIRE(class_of_host[i] >= -1 && class_of_host[i] < n_class, MGEA_EINVAL,
+                     "decoder_set_penalty_classes: class_of[%d] = %d outside [-1, %d)", i, class_of_host[i], n_class);
+    MGEA_CHECK_HIP(hipStreamSynchronize(st));   // the class-penalised graphs carry n_class; a replay may still be reading the old map
+    h->graphs.drop_if([](const StepGraphs::Key& k) { return k.kind.class_penalized; });
+    if (!h->cpen_class) {
+        const size_t mb = (size_t)h->cfg.max_batch;
+        if (h->dev_cpen.alloc(&h->cpen_class, (size_t)V * sizeof(int32_t)) ||
+            h->dev_cpen.alloc(&h->cpen_dev, mb * sizeof(mgea_row_class_penalty)) ||
+            h->pinned_cpen.alloc(&h->cpen_stage, mb * sizeof(mgea_row_class_penalty))) {
+            clear();
+            set_error("decoder_set_penalty_classes: allocation of the class map failed");
+            return MGEA_ENOMEM;
+        }
+        MGEA_CHECK_HIP(hipMemsetAsync(h->cpen_dev, 0, mb * sizeof(mgea_row_class_penalty), st));
+    }
+    MGEA_CHECK_HIP(hipMemcpyAsync(h->cpen_class, class_of_host, (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    MGEA_CHECK_HIP(hipStreamSynchronize(st));   // the caller's map is host memory of unknown lifetime
+    h->cpen_n_class = n_class;
+    return MGEA_OK;
 }
 
 int mgea_decoder_blend_info(mgea_decoder* h, int64_t* out) {

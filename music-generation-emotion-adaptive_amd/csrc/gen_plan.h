@@ -51,12 +51,14 @@ inline bool form_has_bias(StepForm f) { return f == StepForm::BIASED || f == Ste
 //   scheduled  behind the evict launch, the launch that applies the rows' prompt schedules (recondition.hip)
 //   truncated  the truncating sampler over the rows' mgea_row_truncation records (BIASED or GRAMMAR form only)
 //   blended    the blend-mix launch over the logits, next to the guidance mix (blend.hip; never GREEDY)
+//   class_penalized  the class-penalty launch over the logits, behind the two mixes (class_penalty.hip; never GREEDY)
 struct StepKind {
     StepForm form;
     bool scored = false, windowed = false, guided = false, scheduled = false, truncated = false, blended = false;
+    bool class_penalized = false;   // trailing and defaulted: StepKind is aggregate-initialised
     bool operator==(const StepKind& o) const {
         return form == o.form && scored == o.scored && windowed == o.windowed && guided == o.guided && scheduled == o.scheduled &&
-               truncated == o.truncated && blended == o.blended;
+               truncated == o.truncated && blended == o.blended && class_penalized == o.class_penalized;
     }
 };
 
@@ -223,6 +225,31 @@ inline int check_row_blend(const mgea_row_blend* blend, int B, const mgea_row_gu
     return MGEA_OK;
 }
 
+// Is the record on?  (a row that is off is never written: class_penalty.hip)
+inline bool class_penalty_on(const mgea_row_class_penalty& r) { return r.frequency != 0.f || r.presence != 0.f; }
+// host check of cpen[0, B) (mgea_decoder_generate_rows_class_penalized, mgea_op_class_penalty): MGEA_EINVAL naming the first bad row;
+// *n_rows = the rows that are on.  n_steps < 0 skips the check of window == 0 against the steps; n_class = the engine's map (0 = none).
+inline int check_row_class_penalty(const mgea_row_class_penalty* cpen, int B, int n_steps, int n_class, const char* who, int* n_rows) {
+    *n_rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const mgea_row_class_penalty& r = cpen[b];
+        MGEA_REQUIRE(std::isfinite(r.frequency) && std::fabs(r.frequency) <= 1e4f, MGEA_EINVAL,
+                     "%s: row %d: frequency %g must be finite and within +-1e4", who, b, (double)r.frequency);
+        MGEA_REQUIRE(std::isfinite(r.presence) && std::fabs(r.presence) <= 1e4f, MGEA_EINVAL,
+                     "%s: row %d: presence %g must be finite and within +-1e4", who, b, (double)r.presence);
+        MGEA_REQUIRE(r.window >= 0 && r.window <= MGEA_CLASS_PENALTY_MAX_WINDOW, MGEA_EINVAL, "%s: row %d: window %d outside [0, %d]", who, b,
+                     r.window, MGEA_CLASS_PENALTY_MAX_WINDOW);
+        MGEA_REQUIRE(r.reserved == 0, MGEA_EINVAL, "%s: row %d: mgea_row_class_penalty.reserved must be 0", who, b);
+        if (!class_penalty_on(r)) continue;
+        MGEA_REQUIRE(r.window > 0 || n_steps <= MGEA_CLASS_PENALTY_MAX_WINDOW, MGEA_EINVAL,
+                     "%s: row %d: window 0 (the whole history) with %d steps: above %d steps a row that is on needs a window", who, b, n_steps,
+                     MGEA_CLASS_PENALTY_MAX_WINDOW);
+        MGEA_REQUIRE(n_class > 0, MGEA_EINVAL, "%s: row %d has a class penalty but no class map is set (set_penalty_classes)", who, b);
+        *n_rows += 1;
+    }
+    return MGEA_OK;
+}
+
 // Everything a generation is asked for.  prompt_ids, lens, forced and the three outputs are DEVICE memory, as in the C ABI; the records
 // are host memory.
 struct GenRequest {
@@ -245,6 +272,7 @@ struct GenRequest {
     int n_seg_max = 1;
     const mgea_row_truncation* trunc = nullptr;   // [B] the rows' truncation records (any non-greedy row with a stage on makes it truncated)
     const mgea_row_blend* blend = nullptr;        // [B] the rows' blend groups (any leader >= 0 makes it blended)
+    const mgea_row_class_penalty* cpen = nullptr; // [B] the rows' class penalties (any record that is on makes it class-penalised)
     const int32_t* forced = nullptr;        // [B][n_steps] ids the rows must take, -1 = free (scored only)
     int32_t* ids_out = nullptr;             // [B][n_steps]
     float* logprobs_out = nullptr;          // [B][n_steps]; not NULL makes the generation scored
@@ -257,6 +285,7 @@ struct GenLimits {
     int vocab, max_batch, max_ctx, block_mode;
     int win_S, win_R, win_max_steps;
     int gram_n_state;
+    int cpen_n_class = 0;   // the n_class of the penalty class map (mgea_decoder_set_penalty_classes); 0: none is set
 };
 
 // What the host decides about a generation before its first launch.
@@ -274,6 +303,7 @@ struct GenPlan {
     int reserve;           // tokens of KV pages every row gets
     int n_groups;          // blend groups: leaders
     int n_blend_rows;      // rows in a blend group, leaders included
+    int n_cpen;            // rows whose class-penalty record is on
 };
 
 // Every host check of a generation, then its plan.  Calls no HIP function and touches no handle.
@@ -315,6 +345,8 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
                          "decoder_generate_rows_scheduled: prompt width %d exceeds one page of %d tokens", Tp, MGEA_KV_PAGE_TOKENS);
         }
         if (q.blend) MGEA_TRY(check_row_blend(q.blend, B, q.guide, q.sched, &p.n_groups, &p.n_blend_rows));
+        if (q.cpen)
+            MGEA_TRY(check_row_class_penalty(q.cpen, B, n_steps, c.cpen_n_class, "decoder_generate_rows_class_penalized", &p.n_cpen));
         // A guided pair must run the same steps: rows stopped where their pages end (launch_clamp_budgets) would get budgets of their own
         // prompt lengths.  Under a window nothing is clamped, and each row of a pair evicts on its own schedule.
         MGEA_REQUIRE(p.n_pairs == 0 || windowed || Tp + n_steps <= c.max_ctx, MGEA_ECAPACITY,
@@ -339,16 +371,16 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
     p.may_stop_early = rr.may_stop_early || p.capped;
     p.any_penalty = rr.any_penalty;
     p.biased = rr.form == StepForm::BIASED;
-    const bool scored = q.scored(), guided = p.n_pairs > 0, blended = p.n_groups > 0;
-    // scoring, guidance and blends need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
+    const bool scored = q.scored(), guided = p.n_pairs > 0, blended = p.n_groups > 0, cpen = p.n_cpen > 0;
+    // scoring, guidance, blends and class penalties need the logits row: all-greedy rows run as top_k == 1 records of the SAMPLED form (the exact argmax, ties to
     // the lowest id)
     // truncation lives in the <PENALTY, BIAS> sampler family, as the grammar does: the BIASED form at least (bitmaps over every row, a
     // penalty of 1 and a record without bias_on change nothing)
     const StepForm form = p.grammar           ? StepForm::GRAMMAR
                           : p.truncated     ? StepForm::BIASED
-                          : (scored || guided || blended) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED
+                          : (scored || guided || blended || cpen) && rr.form == StepForm::GREEDY ? StepForm::SAMPLED
                                               : rr.form;
-    p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0, p.truncated, blended};
+    p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0, p.truncated, blended, cpen};
     *out = p;
     return MGEA_OK;
 }

@@ -31,7 +31,8 @@ __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab
            "generate_sequence", "generate_requests", "sample", "tok2id", "id2tok", "sample_kvcache_biased",
            "generate_batch_biased", "generate_sequence_biased", "sample_kvcache_grammar", "generate_batch_grammar", "sample_kvcache_truncated",
            "generate_sequence_truncated", "generate_batch_truncated", "score_sequence", "generate_best_of", "pick_best",
-           "mean_logprobs", "sample_kvcache_guided", "generate_requests_guided", "sample_kvcache_blended", "generate_requests_blended"]
+           "mean_logprobs", "sample_kvcache_guided", "generate_requests_guided", "sample_kvcache_blended", "generate_requests_blended",
+           "sample_kvcache_varied"]
 
 # module globals like the reference's (api_cache.py:34-35); filled by load_checkpoint / set_vocab
 tok2id: Dict[str, int] = {}
@@ -478,7 +479,7 @@ def _per_prompt(value, n: int, name: str) -> list:
 def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temperature=1.0, top_k=50,
                       top_p: Optional[float] = None, seed=None, repetition_penalty=None, logit_bias=None,
                       min_new_tokens=0, grammar=None,
-                      min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[List[str]]:
+                      min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, class_penalty=None) -> List[List[str]]:
     """Independent sample_kvcache requests served by one batched generation (up to the engine's max_batch rows per
     generation; more prompts take several).  Every argument may be a scalar or a list with one value per prompt.  Prompt i
     gets max_len_i - len(prompt_i) new tokens and stops after [END_SEQUENCE], like sample_kvcache; a seed of None is drawn
@@ -490,7 +491,9 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     budget) travel in the rows' records.  grammar (ONE TokenGrammar for all the prompts, or None) makes every row start in the state
     of its own prompt.
     min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
-    in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
+    in this order (mgea.decoder.Truncation); with none of them this is the call it always was.
+    class_penalty (one mgea.decoder.ClassPenalty for every prompt, or a list with one per prompt, None = none): the row's windowed
+    penalty over the classes of the engine's map (DecoderEngine.set_penalty_classes; generate_music.variety.token_classes)."""
     m = _as_model(model)
     eng = m._need()
     n = len(prompts)
@@ -504,6 +507,7 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
     truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
                                              _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
+    cpens = _per_prompt(class_penalty, n, "class_penalty")
     ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
     budgets = [L - len(p) for L, p in zip(max_lens, ids)]
     for L, p in zip(max_lens, ids):
@@ -521,7 +525,8 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
         gstates = [start_state(grammar, p) for p in ids]
     rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
                            max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
+                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i],
+                           class_penalty=cpens[i])
             for i in live}
     gen: Dict[int, List[int]] = {}
     for c0 in range(0, len(live), eng.max_batch):
@@ -530,6 +535,45 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
         for i, row in zip(part, out):
             gen[i] = [g for g in row if g >= 0]
     return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]
+
+
+def sample_kvcache_varied(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
+                          top_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+                          logit_bias=None, min_new_tokens: int = 0, grammar=None, classes="pitch", frequency_penalty: float = 0.0,
+                          presence_penalty: float = 0.0, penalty_window: int = 32,
+                          min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
+    """sample_kvcache_grammar with a windowed penalty over an ATTRIBUTE of the notes (sample_kvcache_grammar keeps its parameter
+    list).  classes: which attribute -- "pitch", "pitch_class", "duration", "pitch_duration" or "id"
+    (generate_music.variety.token_classes over the module's vocabulary) -- or a ready map, vocab ints with -1 = in no class.  With n_c
+    the number of the last penalty_window generated tokens (0 = all of them, up to 4096 steps) of class c, every token of a class
+    with n_c > 0 loses frequency_penalty * n_c + presence_penalty from its logit before the id-level repetition penalty, the bias,
+    the grammar and the cuts; negative values keep the piece near the classes it has been using.  Both 0: the run that
+    sample_kvcache_grammar makes.  The map becomes the engine's (DecoderEngine.set_penalty_classes) and stays set.  Build-defined:
+    the reference has only the id-level repetition_penalty."""
+    from mgea.decoder import ClassPenalty
+    cp = ClassPenalty(frequency_penalty, presence_penalty, penalty_window)
+    cp.check(0)
+    if cp.on:
+        _use_penalty_classes(_as_model(model)._need(), classes)
+    return generate_requests(model, [prompt], max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias, min_new_tokens,
+                             grammar, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
+                             class_penalty=cp if cp.on else None)[0]
+
+
+def _use_penalty_classes(eng, classes) -> None:
+    """Make `classes` (a kind of variety.token_classes, or a ready map) the engine's penalty class map: uploaded when it is not
+    what was set through here last."""
+    import numpy as np
+    from .variety import token_classes
+    key = classes if isinstance(classes, str) else None
+    m = token_classes(tok2id, classes) if key is not None else np.asarray(classes)
+    if len(m) < eng.vocab:   # ids no token names are in no class
+        m = np.concatenate([m, np.full(eng.vocab - len(m), -1, m.dtype)])
+    last = getattr(eng, "_variety_classes", None)
+    if last is not None and last[0] == key and np.array_equal(last[1], m) and eng.class_penalty_info()["n_class"] > 0:
+        return
+    eng.set_penalty_classes(m)
+    eng._variety_classes = (key, m)
 
 
 def sample_kvcache_guided(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",

@@ -69,6 +69,14 @@ class RowBlend(C.Structure):
 BLEND_MAX_ROWS = 8
 
 
+class RowClassPenalty(C.Structure):
+    """mgea_row_class_penalty: one batch row's windowed penalty over token classes (mgea_decoder_generate_rows_class_penalized)."""
+    _fields_ = [("frequency", C.c_float), ("presence", C.c_float), ("window", C.c_int32), ("reserved", C.c_int32)]
+
+
+CLASS_PENALTY_MAX_WINDOW = 4096
+
+
 class BertConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("max_pos", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
                 ("n_layers", C.c_int32), ("hidden", C.c_int32), ("num_labels", C.c_int32),
@@ -146,6 +154,11 @@ PROTOTYPES = {
                                                     C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P,
                                                     C.POINTER(RowTruncation), C.POINTER(RowBlend), _P]),
     "mgea_decoder_blend_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "mgea_decoder_set_penalty_classes": (C.c_int, [_P, _P, _I32, _P]),
+    "mgea_decoder_generate_rows_class_penalized": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.POINTER(RowSampler), C.POINTER(RowLogits), _P,
+                                                            C.POINTER(RowGuidance), C.POINTER(RowSchedule), _I32, _P, _P, _P, _P,
+                                                            C.POINTER(RowTruncation), C.POINTER(RowBlend), C.POINTER(RowClassPenalty), _P]),
+    "mgea_decoder_class_penalty_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_schedule_info": (C.c_int, [_P, C.POINTER(_I64), _P]),
     "mgea_decoder_segments": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_set_window": (C.c_int, [_P, _I32, _I32, _I32, _P]),
@@ -208,6 +221,7 @@ PROTOTYPES = {
     "mgea_op_window_evict": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "mgea_op_guidance_mix": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
     "mgea_op_blend_mix": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "mgea_op_class_penalty": (C.c_int, [_P, _I32, _I32, _P, _I32, _P, _I32, _P, _P, C.POINTER(RowClassPenalty), _P]),
     "mgea_op_recondition": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
                                       _P, _P, _P]),
     "mgea_op_sample_rows_grammar": (C.c_int, [_P, _I32, _I32, C.POINTER(RowSampler), _P, C.POINTER(RowLogits), _P, _P, _I32, _I32, _P, _I64, _P,

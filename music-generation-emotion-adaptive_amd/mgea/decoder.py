@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DecoderConfig, RowLogits, RowSampler, RowTruncation, SamplerConfig, check, ptr
+from ._lib import DecoderConfig, RowClassPenalty, RowLogits, RowSampler, RowTruncation, SamplerConfig, check, ptr
 
 _LAYER_TENSORS = ["ln1.weight", "ln1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
                   "attn.out_proj.bias", "ln2.weight", "ln2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
@@ -344,6 +344,49 @@ class Truncation:
         return cls(min_p, typical_p, epsilon_cutoff, eta_cutoff)
 
 
+CLASS_PENALTY_MAX_WINDOW = _lib.CLASS_PENALTY_MAX_WINDOW
+CLASS_PENALTY_MAX_VALUE = 1e4
+
+
+@dataclasses.dataclass
+class ClassPenalty:
+    """One batch row's windowed penalty over token classes (mgea_row_class_penalty, include/mgea.h): with n_c the number of the row's
+    last `window` generated ids (0 = all of them) whose class in the engine's map (DecoderEngine.set_penalty_classes) is c, every id
+    of a class with n_c > 0 loses frequency * n_c + presence from its logit, behind the guidance and blend mixes and in front of the
+    id-level repetition penalty.  Negative values favour the counted classes.  Both 0 = off: the row is not touched."""
+    frequency: float = 0.0
+    presence: float = 0.0
+    window: int = 0
+
+    @property
+    def on(self) -> bool:
+        return float(np.float32(self.frequency)) != 0.0 or float(np.float32(self.presence)) != 0.0
+
+    def check(self, row: int = 0, n_steps: Optional[int] = None, n_class: Optional[int] = None) -> None:
+        """ValueError naming the row for what the native call would refuse (MGEA_EINVAL): a value that is not finite or beyond
+        +-1e4 (as the float32 the record holds), a window outside [0, CLASS_PENALTY_MAX_WINDOW] and, for a row that is on, window 0
+        with more than CLASS_PENALTY_MAX_WINDOW steps (n_steps given) and an engine without a class map (n_class given and 0)."""
+        for name, v in (("frequency", self.frequency), ("presence", self.presence)):
+            v = float(v)
+            with np.errstate(over="ignore"):   # (a double beyond float32 is inf as the record's float: refused below)
+                v32 = float(np.float32(v))
+            if not (math.isfinite(v) and abs(v32) <= CLASS_PENALTY_MAX_VALUE):
+                raise ValueError(f"row {row}: {name} {v} must be finite and within +-1e4")
+        w = int(self.window)
+        if w != self.window or not 0 <= w <= CLASS_PENALTY_MAX_WINDOW:
+            raise ValueError(f"row {row}: window {self.window} outside [0, {CLASS_PENALTY_MAX_WINDOW}]")
+        if not self.on:
+            return
+        if w == 0 and n_steps is not None and n_steps > CLASS_PENALTY_MAX_WINDOW:
+            raise ValueError(f"row {row}: window 0 (the whole history) with {n_steps} steps: above {CLASS_PENALTY_MAX_WINDOW} steps "
+                             "a row that is on needs a window")
+        if n_class is not None and n_class <= 0:
+            raise ValueError(f"row {row} has a class penalty but no class map is set (set_penalty_classes)")
+
+    def record(self) -> RowClassPenalty:
+        return RowClassPenalty(frequency=float(self.frequency), presence=float(self.presence), window=int(self.window), reserved=0)
+
+
 @dataclasses.dataclass
 class RowSampling:
     """One batch row's sampler settings (mgea_row_sampler, include/mgea.h) for DecoderEngine.generate_rows / ops.sample_rows.
@@ -353,7 +396,8 @@ class RowSampling:
     logit_bias (None, a dict id -> bias, a host array or a device tensor [vocab]; -inf bans an id) is added to the row's penalized
     logits at every step; min_new_tokens > 0 bans eos_id until the row has produced that many ids (mgea_row_logits).
     grammar_state (None = the row is not constrained): the row's start state in the engine's TokenGrammar (DecoderEngine.set_grammar).
-    truncation (None = none): the row's Truncation -- min-p, typical-p, epsilon and eta cutoff behind top-k and top-p."""
+    truncation (None = none): the row's Truncation -- min-p, typical-p, epsilon and eta cutoff behind top-k and top-p.
+    class_penalty (None = none): the row's ClassPenalty over the engine's class map (DecoderEngine.set_penalty_classes)."""
     temperature: float = 1.0
     top_k: Optional[int] = 50
     top_p: Optional[float] = None
@@ -369,10 +413,13 @@ class RowSampling:
     grammar_state: dataclasses.InitVar[Optional[int]] = None
     # the twelfth, carried the same way
     truncation: dataclasses.InitVar[Optional[Truncation]] = None
+    # the thirteenth, carried the same way
+    class_penalty: dataclasses.InitVar[Optional[ClassPenalty]] = None
 
-    def __post_init__(self, grammar_state, truncation=None):
+    def __post_init__(self, grammar_state, truncation=None, class_penalty=None):
         self.grammar_state = grammar_state
         self.truncation = truncation
+        self.class_penalty = class_penalty
 
     def check(self, row: int, vocab: int, n_steps: Optional[int] = None) -> None:
         """ValueError naming the row for what the native call would refuse (MGEA_EINVAL)."""
@@ -398,6 +445,11 @@ class RowSampling:
             if not isinstance(self.truncation, Truncation):
                 raise ValueError(f"row {row}: truncation must be a Truncation, got {type(self.truncation).__name__}")
             self.truncation.check(row)
+        cp = getattr(self, "class_penalty", None)
+        if cp is not None:
+            if not isinstance(cp, ClassPenalty):
+                raise ValueError(f"row {row}: class_penalty must be a ClassPenalty, got {type(cp).__name__}")
+            cp.check(row, n_steps)
 
     def record(self, row: int) -> RowSampler:
         pen = self.repetition_penalty
@@ -460,6 +512,24 @@ def pack_truncation(rows: Sequence[RowSampling]):
         if r.truncation is not None:
             r.truncation.check(b)
             recs[b] = r.truncation.record()
+    return recs
+
+
+def pack_class_penalty(rows: Sequence[RowSampling], n_steps: Optional[int] = None, n_class: Optional[int] = None):
+    """The rows' ClassPenalty records as the C array mgea_row_class_penalty[B] (rows without one: off), or None when no row carries
+    one that is on -- the caller then makes the call it always made.  Every record is checked (ValueError naming the row; n_steps
+    and n_class as in ClassPenalty.check)."""
+    rows = list(rows)
+    cps = [getattr(r, "class_penalty", None) for r in rows]
+    for b, cp in enumerate(cps):
+        if cp is not None:
+            cp.check(b, n_steps, n_class)
+    if not any(cp is not None and cp.on for cp in cps):
+        return None
+    recs = (RowClassPenalty * len(rows))()
+    for b, cp in enumerate(cps):
+        if cp is not None:
+            recs[b] = cp.record()
     return recs
 
 
@@ -832,6 +902,7 @@ class DecoderEngine:
         check(self.lib.mgea_decoder_create(C.byref(self.cfg), ptr(self.arena), C.byref(h)))
         self.h = h
         self.grammar: Optional[TokenGrammar] = None
+        self._cpen_n_class = 0   # the n_class of the penalty class map (set_penalty_classes); 0: none is set
         self.window: Optional[KVWindow] = None
         self._cur_batch = 0
         self._epoch = 0  # bumps whenever the native cache is reset (guards stale `presents`)
@@ -946,6 +1017,39 @@ class DecoderEngine:
         out = (C.c_int64 * 4)()
         check(self.lib.mgea_decoder_grammar_info(self.h, out))
         return dict(n_state=out[0], n_class=out[1], uploads=out[2], grammar_steps=out[3])
+
+    # ------------------------------------------------------------------ penalty classes
+    def set_penalty_classes(self, class_of) -> None:
+        """Set the map from ids to penalty classes (mgea_decoder_set_penalty_classes), or None to clear it.  class_of: vocab ints in
+        [-1, n_class), n_class = the largest class + 1; -1 = the id is in no class, never counted and never penalised.  One map per
+        engine, shared by the rows; a row takes part through RowSampling.class_penalty.  ValueError naming the offending id."""
+        if class_of is None:
+            with self._on_stream():
+                check(self.lib.mgea_decoder_set_penalty_classes(self.h, None, 0, self._sp()))
+            self._cpen_n_class = 0
+            return
+        m = np.ascontiguousarray(np.asarray(class_of.cpu() if isinstance(class_of, torch.Tensor) else class_of), dtype=np.int64)
+        if m.ndim != 1 or m.shape[0] != self.vocab:
+            raise ValueError(f"class_of must hold one class per id: {self.vocab} values, got shape {tuple(m.shape)}")
+        if m.shape[0] > 14336:
+            raise ValueError(f"penalty classes need a vocabulary of at most 14336 ids, got {m.shape[0]}")
+        n_class = int(m.max()) + 1
+        bad = np.nonzero(m < -1)[0]
+        if bad.size:
+            raise ValueError(f"class_of[{int(bad[0])}] = {int(m[bad[0]])} is below -1")
+        if n_class < 1:
+            raise ValueError("class_of puts no id into a class")
+        m32 = m.astype(np.int32)
+        with self._on_stream():
+            check(self.lib.mgea_decoder_set_penalty_classes(self.h, m32.ctypes.data_as(C.c_void_p), n_class, self._sp()))
+        self._cpen_n_class = n_class
+
+    def class_penalty_info(self):
+        """The n_class of the map that is set (0 = none), and the rows that were on and the class-penalised decode steps of the last
+        generation (both 0 if it was not class-penalised)."""
+        out = (C.c_int64 * 3)()
+        check(self.lib.mgea_decoder_class_penalty_info(self.h, out))
+        return dict(n_class=int(out[0]), rows=int(out[1]), class_penalized_steps=int(out[2]))
 
     # ------------------------------------------------------------------ KV window
     def set_window(self, sink_pages: int = 1, ring_pages: Optional[int] = None, max_steps: Optional[int] = None) -> None:
@@ -1133,7 +1237,8 @@ class DecoderEngine:
         start states (their ValueErrors, in that order), uploads on the engine's stream and makes the native call -- always
         mgea_decoder_generate_rows_scheduled, the superset, with NULL for what the caller does not use: it then runs exactly what
         the narrower entry point would -- or, when a row carries a Truncation, mgea_decoder_generate_rows_truncated, the same call
-        with the rows' truncation records, or, with blend records, mgea_decoder_generate_rows_blended, the end of the chain.
+        with the rows' truncation records, or, with blend records, mgea_decoder_generate_rows_blended, or, when a row carries a
+        ClassPenalty that is on, mgea_decoder_generate_rows_class_penalized, the end of the chain.
         Returns all B rows [B, n_steps]; logprobs / choice_logprobs are None unless scored."""
         B, Tp = ids.shape[-2:]
         recs = pack_rows(rows, self.vocab, n_steps)
@@ -1141,6 +1246,7 @@ class DecoderEngine:
         lrecs, keep = pack_row_logits(rows, self.vocab, self.device, check_bias)
         starts = self._start_states(rows)
         trecs = pack_truncation(rows)
+        crecs = pack_class_penalty(rows, n_steps, self._cpen_n_class)
         checked = self._check_ids(ids) and (forced is None or not forced.is_cuda)
         with self._on_stream():
             ids = ids.to(self.device).contiguous()
@@ -1154,7 +1260,11 @@ class DecoderEngine:
             ch = torch.zeros(B, w, dtype=torch.float32, device=self.device) if scored else None
             for t in keep:   # uploaded on the caller's stream, read by the engine's
                 t.record_stream(self.stream)
-            if blend is not None:
+            if crecs is not None:
+                check(self.lib.mgea_decoder_generate_rows_class_penalized(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts,
+                                                                          guide, srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch),
+                                                                          trecs, blend, crecs, self._sp()))
+            elif blend is not None:
                 check(self.lib.mgea_decoder_generate_rows_blended(self.h, ptr(ids), ptr(lens), B, Tp, n_steps, recs, lrecs, starts, guide,
                                                                   srecs, n_seg_max, ptr(forced), ptr(out), ptr(lp), ptr(ch), trecs, blend,
                                                                   self._sp()))

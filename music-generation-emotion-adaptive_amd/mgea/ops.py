@@ -577,6 +577,38 @@ def blend_mix(logits: torch.Tensor, leader, weight) -> torch.Tensor:
     return out
 
 
+def class_penalty(logits: torch.Tensor, class_of, hist, row_step, done, recs) -> torch.Tensor:
+    """The class-penalty launch of a class-penalised decode step (mgea_op_class_penalty), alone, on a COPY of logits [>= B, V] (B =
+    len(recs); rows behind B are guard rows the kernel must not touch).  class_of: V ints in [-1, n_class), n_class = the largest
+    class + 1 (at least 1); hist: int [B, stride], row b's taken ids; row_step / done: B ints; recs: B mgea.decoder.ClassPenalty
+    (checked on the host: ValueError naming the row).  Returns the copy."""
+    lib = _lib.load()
+    recs = list(recs)
+    B = len(recs)
+    hist = torch.as_tensor(hist, dtype=torch.int32)
+    class_of = torch.as_tensor(class_of, dtype=torch.int32)
+    row_step = torch.as_tensor(row_step, dtype=torch.int32)
+    done = torch.as_tensor(done, dtype=torch.int32)
+    if logits.dim() != 2 or logits.shape[0] < B or B < 1 or hist.dim() != 2 or hist.shape[0] != B or hist.shape[1] < 1:
+        raise RuntimeError("class_penalty: logits must be [>= B, V] and hist [B, stride >= 1] with B = len(recs) >= 1")
+    V = logits.shape[1]
+    if class_of.dim() != 1 or class_of.shape[0] != V or row_step.shape != (B,) or done.shape != (B,):
+        raise RuntimeError("class_penalty: class_of must be [V], row_step and done [B]")
+    if int(row_step.max()) > hist.shape[1] or int(row_step.min()) < 0:
+        raise ValueError(f"class_penalty: row_step outside [0, stride = {hist.shape[1]}]")
+    if int(class_of.min()) < -1:
+        raise ValueError("class_penalty: class_of below -1")
+    n_class = max(int(class_of.max()) + 1, 1)
+    for b, r in enumerate(recs):
+        r.check(b)
+    crecs = (_lib.RowClassPenalty * B)(*[r.record() for r in recs])
+    out = logits.to(device="cuda", dtype=torch.float32).contiguous().clone()
+    dev = [t.to("cuda").contiguous() for t in (class_of, hist, row_step, done)]
+    check(lib.mgea_op_class_penalty(ptr(out), B, V, ptr(dev[0]), n_class, ptr(dev[1]), hist.shape[1], ptr(dev[2]), ptr(dev[3]), crecs,
+                                    stream_ptr()))
+    return out
+
+
 # ---- the DistilBERT row, [CLS] and split-K epilogue kernels, one launch per call (mgea_op_* of the same names: tests only) ----
 _DTYPE_ROWS = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
 

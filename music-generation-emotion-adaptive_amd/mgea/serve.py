@@ -47,14 +47,16 @@ class RequestBatcher:
 
     def submit(self, prompt_tokens: Sequence[str], max_len=512, temperature=1.0, top_k=50, top_p=None,
                repetition_penalty=None, seed: Optional[int] = None, logit_bias=None, min_new_tokens: int = 0,
-               grammar=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> "Future[List[str]]":
+               grammar=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
+               class_penalty=None) -> "Future[List[str]]":
         """Queue one sample_kvcache request; the future's result is its prompt + generated tokens.  Unknown tokens raise KeyError
         and a bad repetition penalty, logit_bias (a dict id -> bias, a host array or a device tensor [vocab]; a host one is checked
         in full, a device one for its shape) or min_new_tokens ValueError here, in the caller's thread.  A seed of None is drawn here too, so
         torch.manual_seed in the caller makes it reproducible whatever the batch it lands in.  grammar (a mgea.decoder.TokenGrammar or
         None, checked here): the engine holds one grammar at a time, so a batch serves requests that share the grammar object (or have
         none); a request with another one goes into the next batch.  min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off;
-        mgea.decoder.Truncation, checked here) travel in the request's own record."""
+        mgea.decoder.Truncation, checked here) travel in the request's own record, and so does class_penalty (a
+        mgea.decoder.ClassPenalty or None, checked here; the class map is the engine's: DecoderEngine.set_penalty_classes)."""
         import generate_music.generate as gen
         from .ops import check_repetition_penalty
         tokens = list(prompt_tokens)
@@ -73,10 +75,12 @@ class RequestBatcher:
             grammar.check(self.model._need().vocab)
         from .decoder import Truncation
         Truncation(min_p, typical_p, epsilon_cutoff, eta_cutoff).check()
+        if class_penalty is not None:
+            class_penalty.check(0)
         kwargs = dict(max_len=int(max_len), temperature=temperature, top_k=top_k, top_p=top_p,
                       repetition_penalty=repetition_penalty, seed=gen._draw_seed() if seed is None else int(seed),
                       logit_bias=logit_bias, min_new_tokens=int(min_new_tokens), min_p=min_p, typical_p=typical_p,
-                      epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+                      epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, class_penalty=class_penalty)
         fut: Future = Future()
         with self._cv:
             if self._closed:
