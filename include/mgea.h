@@ -888,7 +888,8 @@ typedef struct mgea_decode_gemm_args {
     const int32_t* ctx_len_dev;   /* [M / T] */
     const int32_t* lens_dev;      /* [M / T] or NULL */
     int32_t n_pages, page_dtype, n_head, head_dim, layer, max_pages, T;
-    int32_t reserved;             /* 0 */
+    int32_t arith_batch;          /* 0: every page id comes from the table; > 0: the pool carries the decoder's allocation rule, logical
+                                     page j of row b = physical j * arith_batch + b (the table must agree): >= M / T, max_pages * arith_batch <= n_pages */
     /* LOGITS */
     float* partials_dev;
 } mgea_decode_gemm_args;

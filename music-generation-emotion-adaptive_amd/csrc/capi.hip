@@ -475,7 +475,8 @@ int mgea_op_skinny_logits_partials(int32_t M, int32_t N, int32_t K) {
 // test-only: any decode-GEMM plan on caller buffers (mgea.h).  Fills the argument block, plans, launches that plan, synchronises.
 int mgea_op_decode_gemm(const mgea_decode_gemm_args* g, int32_t* plan_out, void* stream) {
     for (int i = 0; plan_out && i < MGEA_DECODE_GEMM_PLAN_INTS; ++i) plan_out[i] = -1;
-    MGEA_REQUIRE(g && g->a_dev && g->w_dev && g->M > 0 && g->N > 0 && g->K > 0 && !g->reserved, MGEA_EINVAL, "op_decode_gemm: bad argument");
+    MGEA_REQUIRE(g && g->a_dev && g->w_dev && g->M > 0 && g->N > 0 && g->K > 0, MGEA_EINVAL, "op_decode_gemm: bad argument");
+    MGEA_REQUIRE(g->epi == EPI_QKV ? g->arith_batch >= 0 : g->arith_batch == 0, MGEA_EINVAL, "op_decode_gemm: arith_batch %d (QKV only, >= 0)", g->arith_batch);
     const int epi = g->epi;
     MGEA_REQUIRE(epi >= EPI_QKV && epi <= EPI_LOGITS, MGEA_EINVAL, "op_decode_gemm: bad epilogue %d", epi);
     MGEA_REQUIRE(epi == EPI_LOGITS ? g->partials_dev != nullptr : g->out_dev != nullptr, MGEA_EINVAL,
@@ -493,7 +494,9 @@ int mgea_op_decode_gemm(const mgea_decode_gemm_args* g, int32_t* plan_out, void*
                          g->head_dim > 0 && g->head_dim % 8 == 0 && g->layer >= 0 && g->T >= 1 && g->M % g->T == 0 &&
                          g->N == 3 * g->n_head * g->head_dim && (g->page_dtype == MGEA_DTYPE_F32 || g->page_dtype == MGEA_DTYPE_F16),
                      MGEA_EINVAL, "op_decode_gemm: bad QKV argument (N = 3 * n_head * head_dim, M a multiple of T, fp32 or fp16 pages)");
-        a.pool = op_pool(g->pages_dev, g->n_pages, g->n_head, g->head_dim, g->page_dtype == MGEA_DTYPE_F16, 0);
+        MGEA_REQUIRE(g->arith_batch == 0 || (g->arith_batch >= g->M / g->T && (int64_t)g->max_pages * g->arith_batch <= g->n_pages), MGEA_EINVAL,
+                     "op_decode_gemm: arith_batch %d must be >= M / T with max_pages * arith_batch <= n_pages", g->arith_batch);
+        a.pool = op_pool(g->pages_dev, g->n_pages, g->n_head, g->head_dim, g->page_dtype == MGEA_DTYPE_F16, g->arith_batch);
         a.layer = g->layer; a.page_table = g->page_table_dev; a.max_pages = g->max_pages; a.ctx_len = g->ctx_len_dev;
         a.lens = g->lens_dev; a.T = g->T; a.C = g->n_head * g->head_dim;
     }

@@ -544,7 +544,7 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 // in the barriers; the sampler's workgroup has SAMP_NT = 256):
 // the sampler-loop bookkeeping of api_cache.py:179-181 (append, EOS stop) and the NEXT step's embedding
 // x[b] = tok_emb[fed] + pos_emb[pos] (k-tiled) with its LayerNorm statistics (two equal half-row partials).
-// st_* = the row's state as loaded by thread 0 at kernel start.  sh: >= 7 floats of shared scratch.
+// st_* = the row's state and what stops it (row_stops) as loaded by thread 0 at kernel start.  sh: >= 7 floats of shared scratch.
 // With the qkv0 table (TailArgs::qkv0) the embedding goes through embed_qkv0_row instead and has no statistics.
 // PENALTY: also set the token's bit in the row's presence bitmap (presence_words(vocab) words per row) while the row is not finished:
 // one writer per row, read by a later kernel, so a plain read-modify-write of the word.
@@ -561,8 +561,18 @@ __device__ __forceinline__ void kv_store4(const KvPool& pool, int layer, int phy
 // Every row's NEXT position is therefore *len_out, the parked row's too: advance_embed_row embeds at it and embed_qkv0_row caches at it,
 // as the unfused pair (advance_kernel, then an embedding kernel that reads ctx_len) does.  The rule is written out, and every caller
 // held to it, in tests/step_tail_util.py and tests/test_gpu_step_tail.py.
+// What stops row b: its record's eos_id, max_new and ctx_cap, or without records the by-value eos_id and no budget.  A caller loads
+// them with the rest of the row's state (row_stops, beside row_step / cur_ids / ctx_len / done), finished rows included -- the
+// record is in bounds for every row and a finished row does not use it -- so that no load stands between the new token and the
+// stores that depend on it.
+struct RowStops { int eos, max_new, cap; };
+__device__ __forceinline__ RowStops row_stops(const mgea::StepState& s, int b) {
+    RowStops r{s.eos_id, mgea::MGEA_NO_BUDGET, mgea::MGEA_NO_BUDGET};
+    if (s.params) { r.eos = s.params[b].eos_id; r.max_new = s.params[b].max_new; r.cap = s.params[b].ctx_cap; }
+    return r;
+}
 __device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int tok, int step, int fed, int len, int done,
-                                            int* len_out = nullptr) {
+                                            const RowStops& stops, int* len_out = nullptr) {
     int out = -1, next_len = len;
     if (!done) {
         out = tok;
@@ -570,8 +580,7 @@ __device__ __forceinline__ int end_row_step(const mgea::StepState& s, int b, int
         next_len = len + 1;
         s.cur_ids[b] = tok;
         s.ctx_len[b] = len + 1;
-        int eos = s.eos_id, max_new = mgea::MGEA_NO_BUDGET, cap = mgea::MGEA_NO_BUDGET;
-        if (s.params) { eos = s.params[b].eos_id; max_new = s.params[b].max_new; cap = s.params[b].ctx_cap; }
+        const int eos = stops.eos, max_new = stops.max_new, cap = stops.cap;
         if (tok == eos || step + 1 == max_new) {
             const bool park = len + 1 >= cap;
             s.done[b] = park ? 2 : 1;
@@ -617,13 +626,14 @@ __device__ __forceinline__ void embed_qkv0_row(int b, int id, int pos, int len, 
 
 template <bool PENALTY = false>
 __device__ __forceinline__ void advance_embed_row(int b, int tok, const mgea::TailArgs& t, int32_t* sampled, int st_step, int st_fed,
-                                                  int st_len, int st_done, float* sh, uint32_t* presence = nullptr) {
+                                                  int st_len, int st_done, const RowStops& st_stops, float* sh,
+                                                  uint32_t* presence = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int* shi = reinterpret_cast<int*>(sh);
     if (tid == 0) {
         sampled[b] = tok;
         int next_len;
-        const int fed = end_row_step(t.s, b, tok, st_step, st_fed, st_len, st_done, &next_len);
+        const int fed = end_row_step(t.s, b, tok, st_step, st_fed, st_len, st_done, st_stops, &next_len);
         const int len = next_len;   // the position the row is fed at = its ctx_len as the next step reads it (a row parked in this step: st_len)
         shi[6] = next_len;
         if constexpr (PENALTY) {

@@ -474,6 +474,7 @@ int run_blocks_fused(mgea_decoder* h, int B, int T, const int32_t* lens, bool us
         a.stats_in = h->stats; a.n_part = n_part; a.part_cnt = part_cnt;
         a.out = h->qkv; a.ldo = 3 * C;
         a.pool = h->kv; a.layer = l; a.page_table = h->page_table; a.max_pages = h->max_pages; a.ctx_len = h->ctx_len;
+        if (!tune(TUNE_ATTN_ARITH_PAGES)) a.pool.arith_batch = 0;   // (as the attention: the switch sends every page id through the table)
         a.lens = lens; a.T = T; a.C = C;
         if (l > 0 || !qkv0_primed) PROF(PC_GEMM, decode_gemm(h, l, 0, a, gv, st));
         if (kv_only_last && l + 1 == c.n_layer) break;       // (run_blocks: the logits are dropped, the last block's K | V are appended)

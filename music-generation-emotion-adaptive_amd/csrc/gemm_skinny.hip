@@ -54,9 +54,23 @@ __device__ __forceinline__ float row16_sum(float v) {
 // shows that a kernel with this memory shape, LDS reduction, read-modify-write epilogue and MFMA chain costs ~3.0 us in a graph
 // chain where the generic instruction stream (NCH = 0: any K, any wave count) took 3.9.  Same chunks per wave, same MFMA order,
 // same wave-order reduction: bit-identical results.
+// "Up front" is the compiled order only behind a scheduling barrier.  The LayerNorm forms always had one (the statistics' exact
+// wait needs it); without one hipcc feeds the chunks in among the MFMAs to save registers (NCH 2: one chunk, four MFMAs, then the
+// second chunk; NCH 8: about six of the 32 loads in flight at a time, 14 dependent waits in the K chain) -- a chain of dependent
+// round trips.  BARRIER puts it behind the request block of the 16-row forms without LayerNorm too (MT * NT = 1: out-projection
+// and FC2 of a decode step of up to 64 rows, the launches profiles/epilogue_inputs_ab.txt measures: FC2 6.31 -> 5.70 us): every
+// operand chunk is in flight before the first MFMA and the waits of the K chain only count down (tools/prologue_chain.py --whole).
+// The taller forms without LayerNorm keep the compiler's order: all chunks up front cost them 200+ VGPRs (one workgroup per CU)
+// where their grids have more workgroups than CUs, and nothing measures that trade.
+// The epilogue's own inputs (bias, c1, the residual float4) are deliberately requested BEHIND the K loop, one more round trip:
+// requested with the operands -- in front of them or behind them -- they measured slower (same record: +0.9 us per step alone,
+// +1.8 .. 2.5 us at 8 and 16 rows).  Vector loads return in issue order, so a residual line that comes from far away holds every
+// operand behind it back, or drags its wait into the K chain; behind the last MFMA its latency runs under the MFMA drain, the LDS
+// reduction and the barrier.
 template <int EPI, bool LN, int MT, int NT, bool F16, int NCH>
 __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
     constexpr int ROWS = 16 * MT, COLS = 16 * NT;
+    constexpr bool BARRIER = LN || (NCH > 0 && MT * NT == 1);
     // LDS row pitch of the partial tiles: + 4 floats, so that the 16 rows one ds_write_b128 of a wave touches do not
     // all start in the same bank (unpadded: 8-way conflicts at 16 columns, 16-way at 32)
     constexpr int PITCH = COLS + 4;
@@ -201,7 +215,8 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
         else if (d < nchunk) load_chunk(d, d);
     }
     // QKV epilogue, first hop of its page lookup (branch-free, behind the operand loads): where the row's
-    // new token goes.  The second hop and the other epilogue operands are requested after the K loop.
+    // new token goes.  With the pool's allocation rule (KvPool::arith_batch) the page id follows from it by arithmetic; without
+    // one the second hop, the page table, is requested after the K loop with the other epilogue operands.
     const int e_lr = tid / (4 * NT), e_q = tid % (4 * NT);   // this thread's first epilogue item
     const int e_row = m0 + e_lr, e_n = n0 + 4 * e_q;
     int e_ctx = 0, e_len = 0;
@@ -210,8 +225,10 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
         e_ctx = a.ctx_len[pb];
         e_len = (a.lens ? a.lens : a.ctx_len)[pb];
     }
+    // every load above is in flight before the first MFMA (hipcc otherwise feeds the chunks in among the MFMAs); LN: and the
+    // merge below waits for the statistics alone, with an exact vmcnt
+    if (BARRIER) __builtin_amdgcn_sched_barrier(0);
     if (LN) {
-        __builtin_amdgcn_sched_barrier(0);   // loads above, merge below: the wait for the statistics is then an exact vmcnt
         // merge the partials while the operand loads are in flight (results are only needed in the epilogue, behind the
         // workgroup barrier): every partial covers the same number of columns (part_cnt), so
         //   mean = average of the tile means,  M2 = sum M2_t + part_cnt * sum (mean_t - mean)^2
@@ -262,7 +279,8 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
         if (EPI == EPI_RES && e_row < a.M) e_x = ld4(a.out + tiled_off(e_row, e_n, a.N));
         if (EPI == EPI_QKV && e_row < a.M && e_n >= a.C) {
             const int page = (e_ctx + e_row % a.T) >> 6;
-            if (page < a.max_pages) e_phys = a.page_table[(e_row / a.T) * a.max_pages + page];
+            if (page < a.max_pages)
+                e_phys = a.pool.arith_batch > 0 ? page * a.pool.arith_batch + e_row / a.T : a.page_table[(e_row / a.T) * a.max_pages + page];
         }
     }
     // partial tile of this wave -> LDS: D[i = column 4g + r][j = row c]
@@ -332,7 +350,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyArgs a) {
                 const int pos = (first ? e_ctx : a.ctx_len[b]) + tt;
                 const int page = pos >> 6, slot = pos & 63;
                 if (page < a.max_pages) {
-                    const int phys = first ? e_phys : a.page_table[b * a.max_pages + page];
+                    const int phys = first ? e_phys : a.pool.arith_batch > 0 ? page * a.pool.arith_batch + b : a.page_table[b * a.max_pages + page];
                     const int isv = n >= 2 * a.C;
                     const int nn = n - (isv ? 2 * a.C : a.C);
                     kv_store4(a.pool, a.layer, phys, isv, nn / a.pool.dh, slot, nn % a.pool.dh, v);

@@ -345,7 +345,7 @@ __device__ __forceinline__ int32_t step_of(const int32_t* row_step, int64_t step
     return row_step ? row_step[b] : (int32_t)step_host;
 }
 // the row's loop state, read by thread 0 at kernel start for the fused tail
-struct RowLoop { int step, fed, len, done; };
+struct RowLoop { int step, fed, len, done; RowStops stops; };
 // GRAMMAR (the instantiations with a GrammarArgs argument, PENALTY and BIAS ones only; common.h): a row whose state s is >= 0 and which
 // is not finished loses every id whose class s bans, x[i] = -inf, after the bias and before the EOS ban; its thread 0 then stores the
 // state behind the id the step commits.  The state is one scalar load at kernel start; -1 = no grammar on this row (or the row is
@@ -834,7 +834,7 @@ __device__ __forceinline__ void commit_id(int b, int id, const GrammarArgs& gr, 
     if constexpr (SCORED) {
         if (!fuse_tail) __syncthreads();   // (the fused tail has barriers of its own before thread 0 reads the mass)
     }
-    if (fuse_tail) advance_embed_row<PENALTY>(b, id, tail, ids_out, st.step, st.fed, st.len, st.done, sh_tail, presence);
+    if (fuse_tail) advance_embed_row<PENALTY>(b, id, tail, ids_out, st.step, st.fed, st.len, st.done, st.stops, sh_tail, presence);
     else if (threadIdx.x == 0) ids_out[b] = id;
 }
 // SCORED (the instantiations with a ScoreArgs argument; common.h): the row also reports how likely its id was, and may be told its id.
@@ -933,9 +933,10 @@ __global__ __launch_bounds__(SAMP_NT) void sample_kernel(const float* __restrict
     const int top_k = pv.top_k;
     const uint64_t seed = ((uint64_t)pv.seed_hi << 32) | pv.seed_lo;
     const float* lg = logits + (int64_t)b * V;
-    RowLoop st{0, 0, 0, 0};
+    RowLoop st{0, 0, 0, 0, RowStops{0, 0, 0}};
     if (fuse_tail && tid == 0) {
         st.step = tail.s.row_step[b]; st.fed = tail.s.cur_ids[b]; st.len = tail.s.ctx_len[b]; st.done = tail.s.done[b];
+        st.stops = row_stops(tail.s, b);
     }
     [[maybe_unused]] int forced = -1;
     if constexpr (SCORED) forced = forced_id(sc, row_step, step_host, b);

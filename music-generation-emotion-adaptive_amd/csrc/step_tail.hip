@@ -29,7 +29,7 @@ __global__ __launch_bounds__(64) void argmax_advance_kernel(const float* __restr
     if (lane == 0) {
         const int tok = bi == 0x7fffffff ? 0 : bi;
         sampled[b] = tok;
-        end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], s.done[b]);
+        end_row_step(s, b, tok, s.row_step[b], s.cur_ids[b], s.ctx_len[b], s.done[b], row_stops(s, b));
     }
 }
 
@@ -55,7 +55,10 @@ __global__ __launch_bounds__(256) void argmax_advance_embed_kernel(const float* 
     const int b = blockIdx.x + zero, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the row's bookkeeping state is requested together with the partials (one round trip instead of two): four scalar loads by every
     // wave -- only thread 0 uses them, but loaded by it alone they were awaited, as that thread's values, in front of the partials' loads
+    // -- and with them what stops the row (its record's eos_id, max_new and ctx_cap: finished rows load them too, in bounds and unused):
+    // loaded behind the argmax they were one more dependent round trip in front of the barrier that releases the gather
     const int st_step = t.s.row_step[b], st_fed = t.s.cur_ids[b], st_len = t.s.ctx_len[b], st_done = t.s.done[b];
+    const RowStops st_stops = row_stops(t.s, b);
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = tid; i < n_tiles; i += 256) {
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void argmax_advance_embed_kernel(const float* 
             if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
         tok = bi == 0x7fffffff ? 0 : bi;
     }
-    advance_embed_row(b, tok, t, sampled, st_step, st_fed, st_len, st_done, sh);
+    advance_embed_row(b, tok, t, sampled, st_step, st_fed, st_len, st_done, st_stops, sh);
 }
 
 int launch_argmax_advance_embed(const float* pval, const int32_t* pidx, int n_tiles, const TailArgs& t, int32_t* sampled, int B,
@@ -121,7 +124,7 @@ template <bool PENALTY>
 __device__ __forceinline__ void advance_row(int b, const int32_t* __restrict__ sampled, const StepState& s, uint32_t* __restrict__ presence,
                                             int V, int* step_out, int* done_out) {
     const int done = s.done[b], tok = sampled[b], step = s.row_step[b];
-    end_row_step(s, b, tok, step, s.cur_ids[b], s.ctx_len[b], done);   // ctx_len + 1: the token fed this step now sits in the cache
+    end_row_step(s, b, tok, step, s.cur_ids[b], s.ctx_len[b], done, row_stops(s, b));   // ctx_len + 1: the token fed this step now sits in the cache
     if constexpr (PENALTY) {
         if (!done && (unsigned)tok < (unsigned)V) {
             uint32_t* w = presence + (int64_t)b * presence_words(V) + (tok >> 5);

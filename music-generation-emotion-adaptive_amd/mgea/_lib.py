@@ -94,7 +94,7 @@ class DecodeGemmArgs(C.Structure):
                 ("stats_in_dev", _P), ("n_part", _I32), ("part_cnt", _I32), ("out_dev", _P), ("stats_out_dev", _P),
                 ("pages_dev", _P), ("page_table_dev", _P), ("ctx_len_dev", _P), ("lens_dev", _P),
                 ("n_pages", _I32), ("page_dtype", _I32), ("n_head", _I32), ("head_dim", _I32), ("layer", _I32), ("max_pages", _I32),
-                ("T", _I32), ("reserved", _I32), ("partials_dev", _P)]
+                ("T", _I32), ("arith_batch", _I32), ("partials_dev", _P)]
 
 
 class StepTailArgs(C.Structure):

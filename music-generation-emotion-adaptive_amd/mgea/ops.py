@@ -1189,7 +1189,8 @@ def decode_gemm(epi: int, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch
                 want_out: bool = True):
     """One decode-step GEMM through mgea_op_decode_gemm on prepared device buffers: a = k-tiled activations (tile_rows), w = the
     row-major matrix (rowmajor), the tiled copy (tile_weights / fold_ln) or fp16 fragments (w_f16, tile_weights_f16).  epi 0 QKV
-    (kv = dict(pages, n_pages, n_head, head_dim, layer, page_table [B, max_pages], ctx_len [B], lens=None, T=1); pages: the device
+    (kv = dict(pages, n_pages, n_head, head_dim, layer, page_table [B, max_pages], ctx_len [B], lens=None, T=1, arith_batch=0 -- > 0: the
+    pool carries the decoder's allocation rule, page j of row b = j * arith_batch + b, which the table must repeat); pages: the device
     image of >= layer + 1 layers, written in place), 1 RES (out = the k-tiled residual, updated in place), 2 ACT, 3 LOGITS.
     Buffers not passed are allocated: out (QKV / LOGITS row-major [M, N] filled with NaN, ACT k-tiled zeros), stats_out for RES,
     the LOGITS partials pre-filled with POISON_BITS.  Returns (out, extras, plan): extras holds stats_out [M, N / 16, 2] (RES) or
@@ -1261,6 +1262,7 @@ def decode_gemm(epi: int, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch
         g.pages_dev, g.page_table_dev, g.ctx_len_dev, g.lens_dev = ptr(pages), ptr(pt), ptr(cl), ptr(l32)
         g.n_pages, g.page_dtype = n_pages, (_lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32)
         g.n_head, g.head_dim, g.layer, g.max_pages, g.T = H, dh, layer, pt.shape[1], T
+        g.arith_batch = int(kv.get("arith_batch", 0))
     if epi == _lib.EPI_LOGITS:
         R = max(64, M)
         need = 2 * R * max((N + 15) // 16, 512)

@@ -5,6 +5,7 @@
                                                                  (mangled) symbol contains one of the substrings (none: every kernel)
     python tools/prologue_chain.py --bench                       the seven kernels of the B = 64 f32 decode step
     python tools/prologue_chain.py --asm FILE.s [SUBSTRING ...]  an assembly listing made elsewhere
+    python tools/prologue_chain.py --whole ...                   (with any of the above) the walk goes on to s_endpgm
 
 The compiler lays basic blocks out in an order of its own (the attention kernel's final merge stands in front of its page loop), so
 the listing is cut into basic blocks and walked along its branches.  The multiply-add that ends the prologue is the first FMA / MFMA
@@ -16,6 +17,11 @@ run (wave 0's early K page) is part of that list; the labels tell the blocks apa
 Last come the counts.  A wait is *dependent* when a load of its kind was issued since the previous wait of that kind: one memory
 round trip the wave cannot overlap with what follows.  They are counted per way through the blocks; the fewest and the most are
 printed (scalar: lgkmcnt behind scalar loads; vector: vmcnt behind vector loads).
+
+--whole reports the kernel to its end instead: over the ways that run from the entry THROUGH the first multiply-add to an s_endpgm
+(a workgroup that leaves before it has no operands to wait for), the fewest and the most dependent vector waits, and the number of
+vector load instructions that stand behind the first multiply-add in execution order -- requests no earlier result can hide.  A
+loop's body counts once (its back edge is not followed).
 
 Only load, wait and branch mnemonics (and the FMA / MFMA that ends the prologue) are matched; register writes are followed only as
 far as needed to know which scalar pairs still hold the kernel-argument pointer.
@@ -210,6 +216,97 @@ def prologue_blocks(blocks):
     return [i for i in topo if i in to_target], target, fwd
 
 
+def whole_counts(body):
+    """--whole: ((fewest, most) dependent vector waits over the ways entry -> first multiply-add -> s_endpgm, vector loads behind the
+    first multiply-add, [the vmcnt waits and vector-load groups in execution order as text]); None without a multiply-add."""
+    blocks = basic_blocks(body)
+    if not blocks:
+        return None
+    before, target, fwd = prologue_blocks(blocks)
+    if target is None:
+        return None
+    after = _reach([target], fwd)
+    # a topological order of the blocks behind the target
+    indeg = {i: 0 for i in after}
+    for u in after:
+        for v in fwd[u]:
+            if v in after:
+                indeg[v] += 1
+    tail = []
+    ready = [target]
+    while ready:
+        u = ready.pop()
+        tail.append(u)
+        for v in fwd[u]:
+            if v in after:
+                indeg[v] -= 1
+                if indeg[v] == 0:
+                    ready.append(v)
+    # (back edges are not followed, so the forward edges form a DAG and no block is both in front of and behind the target;
+    # the filter keeps the walk free of repeats whatever the layout)
+    walk = [i for i in before if i != target and i not in after] + tail
+    inset_before = set(before)
+    late, trace = 0, []
+    per_block = {}
+    for i in walk:
+        ev, seen_fma = [], i != target
+        for s in blocks[i][1]:
+            if not seen_fma and FMA.match(s):
+                seen_fma = True
+                ev.append(("fma",))
+                continue
+            m = VLOAD.match(s)
+            if m:
+                ev.append(("vload", m.group(1)))
+                if i in after and seen_fma:
+                    late += 1
+                continue
+            m = WAIT.match(s)
+            if m and "vmcnt" in m.group(1):
+                ev.append(("wait", m.group(1).strip()))
+        per_block[i] = ev
+    best = {walk[0]: {False: (0, 0)}}
+    ends = []
+    for i in walk:
+        states = best.get(i)
+        if not states:
+            continue
+        out = {}
+        for pending, (lo, hi) in states.items():
+            for e in per_block[i]:
+                if e[0] == "vload":
+                    pending = True
+                elif e[0] == "wait" and pending:
+                    lo, hi, pending = lo + 1, hi + 1, False
+            o = out.get(pending)
+            out[pending] = (min(lo, o[0]), max(hi, o[1])) if o else (lo, hi)
+        last = blocks[i][1][-1] if blocks[i][1] else ""
+        if i in after and last.startswith("s_endpgm"):
+            ends += list(out.values())
+        for v in fwd[i]:
+            if (i in after and v in after) or (i not in after and v in inset_before):
+                dst = best.setdefault(v, {})
+                for pending, (lo, hi) in out.items():
+                    o = dst.get(pending)
+                    dst[pending] = (min(lo, o[0]), max(hi, o[1])) if o else (lo, hi)
+    for i in walk:
+        n = 0
+        for e in per_block[i] + [("end",)]:
+            if e[0] == "vload":
+                n += 1
+                continue
+            if n:
+                trace.append("%d vector load%s" % (n, "" if n == 1 else "s"))
+                n = 0
+            if e[0] == "wait":
+                trace.append("WAIT " + e[1])
+            elif e[0] == "fma":
+                trace.append("first multiply-add")
+    if not ends:
+        return None
+    return (min(e[0] for e in ends), max(e[1] for e in ends)), late, trace
+
+
 def block_events(instrs, karg, kernarg_base, stop_at_fma):
     """Events of one block; karg (the scalar pairs holding the kernel-argument pointer) is updated in place."""
     ev = []
@@ -358,6 +455,25 @@ def format_events(ev):
     return out
 
 
+def report_whole(text, wanted):
+    kernels = split_kernels(text)
+    lines = []
+    for sym in sorted(kernels):
+        if wanted and not any(w in sym for w in wanted):
+            continue
+        lines.append("== " + sym)
+        w = whole_counts(kernels[sym][0])
+        if w is None:
+            lines += ["  no multiply-add on a way to s_endpgm", ""]
+            continue
+        (lo, hi), late, trace = w
+        lines.append("  vector loads and vmcnt waits to s_endpgm, blocks in execution order: " + "; ".join(trace))
+        lines.append("  dependent vector waits over the ways through the first multiply-add to s_endpgm, fewest .. most: %d .. %d" % (lo, hi))
+        lines.append("  vector loads behind the first multiply-add: %d" % late)
+        lines.append("")
+    return lines
+
+
 def report(text, wanted):
     kernels = split_kernels(text)
     lines = []
@@ -393,11 +509,13 @@ def main():
     ap.add_argument("--asm", action="store_true", help="FILE is an assembly listing")
     ap.add_argument("--bench", action="store_true", help="the seven kernels of the benchmark step")
     ap.add_argument("--csrc", default=CSRC, help="source directory for --bench")
+    ap.add_argument("--whole", action="store_true", help="walk to s_endpgm: dependent vector waits and vector loads behind the first multiply-add")
     a = ap.parse_args()
+    rep = report_whole if a.whole else report
     if a.bench:
         for f, syms in BENCH:
             print("# " + f)
-            print("\n".join(report(compile_to_asm(os.path.join(a.csrc, f)), syms)))
+            print("\n".join(rep(compile_to_asm(os.path.join(a.csrc, f)), syms)))
         return 0
     if not a.file:
         ap.error("FILE or --bench")
@@ -406,7 +524,7 @@ def main():
             text = f.read()
     else:
         text = compile_to_asm(a.file)
-    print("\n".join(report(text, a.kernels)))
+    print("\n".join(rep(text, a.kernels)))
     return 0
 
 
