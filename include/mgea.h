@@ -51,6 +51,20 @@ extern "C" {
 
 #define MGEA_POS_REFERENCE 0 /* pos_emb[:T] per call: every decode step uses row 0 (api_cache.py:99) */
 #define MGEA_POS_ABSOLUTE  1 /* true positions (build-defined extra, parity unpinned) */
+#define MGEA_POS_CAUSAL    2 /* a standard causal GPT: true positions, a causal mask, every token fed once.  MGEA_BLOCK_PRELN_GELU only.
+                                - position of a token = its index in the row; positions past the table clamp to its last row, as
+                                  MGEA_POS_ABSOLUTE does;
+                                - mgea_decoder_forward appends all T tokens, token t attending the cache and the new tokens <= t, and
+                                  returns their causal logits; forward(a) then forward(b) is forward(a | b);
+                                - mgea_decoder_step feeds what it is given at position ctx_len (T == 1: the kernels of every other mode);
+                                - the generate calls prefill the prompt WITHOUT its last token (a prompt of one token prefills nothing)
+                                  and the first step feeds that token at position len - 1, so after n steps a row's context is
+                                  len - 1 + n.  The budget and capacity checks are those of the other modes (Tp + n_steps against
+                                  max_ctx): one slot per row conservative here;
+                                - mgea_decoder_generate_rows_scheduled (and a schedule given to the calls that extend it) is refused with
+                                  MGEA_EINVAL, as are mgea_decoder_set_window and the qkv0 table, which need MGEA_POS_REFERENCE;
+                                - MGEA_DTYPE_F16: every prefill runs on the fp32-activation path with fp16 pages; the 16-bit flash
+                                  prefill has no causal form, so mgea_decoder_stats out[5] stays 0. */
 
 #define MGEA_KV_PAGE_TOKENS 64 /* tokens per KV page (one wave64 tile) */
 
@@ -594,6 +608,13 @@ int mgea_decoder_window_info(mgea_decoder* h, int32_t* out /* [3] */, int32_t* e
 /* Current cached length of each row -> lens_out_dev [B] (device int32).  Under a KV window (mgea_decoder_set_window) that is the
  * tokens the row's pages hold after its evictions, not the tokens it has seen. */
 int mgea_decoder_context_lengths(mgea_decoder* h, int32_t* lens_out_dev, void* stream);
+/* Test only: a copy of one layer of the engine's KV pages and of its page table, as the attention reads them (stream-ordered, device to
+ * device).  info_out [4] (host): [0] pages per layer, [1] the table's row stride max_pages, [2] bytes per element (4, or 2 on
+ * MGEA_DTYPE_F16 engines), [3] bytes of one layer of pages.  pages_out_dev (pages_bytes >= info_out[3]) receives the layer -- page p
+ * holds K then V, per head, in the layouts of mgea_op_attention_paged -- and page_table_out_dev [max_batch * max_pages] the table;
+ * both NULL: only info_out is filled. */
+int mgea_decoder_kv_pages(mgea_decoder* h, int32_t layer, void* pages_out_dev, int64_t pages_bytes, int32_t* page_table_out_dev,
+                          int64_t* info_out, void* stream);
 
 /* Per-kernel-class timing for bench.py's roofline leg: with stride n > 0 every n-th decode step of
  * generate() runs eagerly (not from the graph) with a hipEvent pair around each launch, recorded on
@@ -707,6 +728,17 @@ int mgea_op_attention_f32(const float* qkv_dev, const int32_t* lens_dev, const i
  *   out_dev     caller-provided in both forms; nothing outside the rows above is written (rows t >= lens[b] ARE written). */
 int mgea_op_attention_f32_ex(const float* qkv_dev, const int32_t* lens_dev, const int32_t* mask_dev, const int32_t* cu_seqlens_dev,
                              float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim, int32_t tiled_out, void* stream);
+/* The causal form of the same kernel (test only; MGEA_POS_CAUSAL engines launch it for a prefill into an empty cache): query i sees the
+ * keys t <= i with t < lens_dev[b] (NULL: T).  No mask and no packed rows.  tiled_out and the zero rows of lens_dev[b] == 0 as above.
+ * Switch attn_causal_walk: the walk of the grid -- 1 (default) (row, head) pairs fastest and blocks last to first, 2 the non-causal
+ * kernel's order, block index fastest. */
+int mgea_op_attention_f32_causal(const float* qkv_dev, const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head,
+                                 int32_t head_dim, int32_t tiled_out, void* stream);
+/* out_dev[m] = logits_dev[m * ld + targets_dev[m]] - logsumexp(logits_dev[m * ld .. + V)) for m < M, fp32, the maximum and the sum
+ * taken in a fixed order.  targets_dev[m] < 0: out_dev[m] = 0 (row not scored); targets_dev[m] >= V reads entry V - 1.  ld >= V.
+ * Stream-ordered, no synchronisation. */
+int mgea_op_logprob_gather(const float* logits_dev, int64_t ld, const int32_t* targets_dev, float* out_dev, int32_t M, int32_t V,
+                           void* stream);
 /* bf16 perf-mode kernels (MGEA_DTYPE_BF16 engines); bf16 buffers are raw 16-bit storage.
  * gemm: out[M,N] = epi(a[M,K] @ w[N,K]^T + bias), fp32 accumulate; epi 0 bias, 1 bias+GELU,
  * 2 bias+residual(res_dev [M,N] bf16).  K % 64 == 0, N % 4 == 0.  attention: head_dim 64 only. */
@@ -813,6 +845,14 @@ int mgea_op_attention_paged_ex(const float* qkv_dev, const void* pages_dev, int3
                                const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
                                int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
                                int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream);
+/* The causal form (test only; MGEA_POS_CAUSAL engines launch it when they extend a cache by T > 1 tokens): query (b, t) attends to the
+ * ctx_len_dev[b] + t + 1 tokens up to itself.  T == 1 launches the kernels of mgea_op_attention_paged_ex.  The split-context form is
+ * taken for T == 1 only (mgea_op_attn_split_count), so info_out[0] is 1 for every T > 1 and the causal form has no split kernel. */
+int mgea_op_attention_paged_causal(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
+                                   int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
+                                   const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                                   int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
+                                   int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream);
 /* Layouts of the fused decode path.  The skinny GEMM reads both operands in MFMA-fragment order so that
  * every wave load is 1 KB of consecutive bytes (see csrc/common.h):
  *   tile_weights: W [N,K] row-major -> out_dev [mgea_op_tiled_weight_floats(N,K)] (rows padded to 32);

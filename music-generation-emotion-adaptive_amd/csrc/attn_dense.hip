@@ -1,4 +1,4 @@
-// Dense non-causal attention over a packed qkv buffer [B*T, 3C] (q | k | v), exact-fp32 MFMA.
+// Dense attention over a packed qkv buffer [B*T, 3C] (q | k | v), exact-fp32 MFMA; non-causal, and causal for MGEA_POS_CAUSAL engines.
 // Used for the decoder prefill without past (the reference never masks: api_cache.py:68, so the
 // prompt is attended bidirectionally) and for DistilBERT's self-attention with its additive
 // padding mask (emotion_analysis/inference.py:16-17 -> transformers MultiHeadSelfAttention).
@@ -18,7 +18,30 @@
 
 namespace mgea {
 
-template <int DH>
+// CAUSAL (MGEA_POS_CAUSAL engines; no mask, no packed rows): query i sees the keys t <= i with t < lens[b].  The workgroup of the queries
+// q0 .. q0 + 63 stops behind key tile q0 / 64, the diagonal one; only there is the lane's query index compared with its four key
+// indices, the tiles in front of it take the sValid path as they are.  The last query block has T / 64 times the keys of the first.
+// CAUSAL is 0 (off), 1 (the default) or 2: the walk of the grid over (query block, head, row), the value of switch attn_causal_walk.
+// The non-causal instantiations are the kernels they were, instruction for instruction (profiles/causal_kernel_diff.txt).
+// Walk 2 is the non-causal kernel's: block = blockIdx.x.  Workgroups are observed to be dealt to the 8 XCDs round-robin by their linear
+// id, so with the block index fastest the 16 blocks of a (row, head) at T = 1024 land on all 8 XCDs: every XCD's L2 fetches that pair's
+// K | V, and XCD k gets blocks k and k + 8 of every pair -- 10 key tiles on one XCD, 24 on another.  Measured, that form is no faster than
+// the unmasked kernel (profiles/causal_prefill_ab.txt); it is kept as the A/B's other side.  In walk 1 the linear id counts the
+// (row, head) pairs fastest and the blocks slowest, last block first: with a multiple of 8 pairs all blocks of a pair run on ONE XCD,
+// whose L2 alone fetches its K | V, every XCD gets the same mix of blocks, and the longest blocks start first.  Any placement is
+// correct: the mapping is a bijection of the grid.
+template <int CAUSAL>
+__device__ __forceinline__ void dense_work_item(unsigned& qblock, int& h, int& b) {
+    qblock = blockIdx.x; h = blockIdx.y; b = blockIdx.z;
+    if (CAUSAL == 1) {
+        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), pairs = gridDim.y * gridDim.z;
+        const unsigned bh = lin % pairs;
+        qblock = gridDim.x - 1 - lin / pairs;
+        h = bh % gridDim.y;
+        b = bh / gridDim.y;
+    }
+}
+template <int DH, int CAUSAL>
 __global__ __launch_bounds__(256) void attn_dense_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ lens,
                                                         const int32_t* __restrict__ mask, float* __restrict__ out,
                                                         int T_pad, int H, float scale, int tiled_out, const int32_t* __restrict__ cu) {
@@ -30,8 +53,10 @@ __global__ __launch_bounds__(256) void attn_dense_kernel(const float* __restrict
     __shared__ int sValid[64];
 
     const int C = H * DH;
-    const int b = blockIdx.z, h = blockIdx.y;
-    const int q0 = blockIdx.x * 64;
+    unsigned qblock;
+    int b, h;
+    dense_work_item<CAUSAL>(qblock, h, b);
+    const int q0 = qblock * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     // packed rows (cu != NULL, DistilBERT on unpadded batches): sequence b = rows cu[b] .. cu[b + 1] - 1, all real; the grid is sized
@@ -57,7 +82,7 @@ __global__ __launch_bounds__(256) void attn_dense_kernel(const float* __restrict
     for (int dt = 0; dt < DC; ++dt) oacc[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float mx = -INFINITY, lsum = 0.f;
 
-    const int ntiles = (T + 63) >> 6;
+    const int ntiles = CAUSAL ? (q0 >> 6) + 1 : (T + 63) >> 6;   // q0 < T: the diagonal tile exists
     for (int kt0 = 0; kt0 < ntiles; ++kt0) {
         const int k0 = kt0 * 64;
         __syncthreads();  // previous tile fully consumed
@@ -104,6 +129,11 @@ __global__ __launch_bounds__(256) void attn_dense_kernel(const float* __restrict
             sc[kt][1] = vl.y ? sc[kt][1] : -INFINITY;
             sc[kt][2] = vl.z ? sc[kt][2] : -INFINITY;
             sc[kt][3] = vl.w ? sc[kt][3] : -INFINITY;
+            if (CAUSAL && kt0 + 1 == ntiles) {   // the diagonal tile (k0 == q0): key kt*16 + 4g + r against query wave*16 + c
+                const int ahead = kt * 16 + 4 * g - (wave * 16 + c);   // key r is visible while ahead + r <= 0
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[kt][r] = ahead + r <= 0 ? sc[kt][r] : -INFINITY;
+            }
             tmax = fmaxf(tmax, fmaxf(fmaxf(sc[kt][0], sc[kt][1]), fmaxf(sc[kt][2], sc[kt][3])));
         }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
@@ -155,15 +185,31 @@ __global__ __launch_bounds__(256) void attn_dense_kernel(const float* __restrict
 }
 
 int launch_attn_dense(const float* qkv, const int32_t* lens, const int32_t* mask, float* out, int B, int T, int H,
-                      int dh, int tiled_out, hipStream_t st, const int32_t* cu) {
+                      int dh, int tiled_out, hipStream_t st, const int32_t* cu, int causal) {
+    MGEA_REQUIRE(!(causal && (mask || cu)), MGEA_EINVAL, "attention: the causal form takes no mask and no packed rows");
     MGEA_REQUIRE(!(cu && (lens || mask || tiled_out)), MGEA_EINVAL, "attention: packed rows carry no lengths / mask");
     MGEA_REQUIRE(B > 0 && T > 0 && B <= 65535 && H <= 65535, MGEA_EINVAL, "attention: bad shape B=%d T=%d H=%d", B, T, H);
     const float scale = 1.0f / sqrtf((float)dh);
     dim3 grid(ceil_div(T, 64), H, B);
+    if (causal) {
+        const bool block_order = tune(TUNE_ATTN_CAUSAL_WALK) == 2;
+#define MGEA_DENSE_CAUSAL(DH) do { if (block_order) hipLaunchKernelGGL((attn_dense_kernel<DH, 2>), grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); \
+                                   else hipLaunchKernelGGL((attn_dense_kernel<DH, 1>), grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); } while (0)
+        switch (dh) {
+            case 32: MGEA_DENSE_CAUSAL(32); break;
+            case 64: MGEA_DENSE_CAUSAL(64); break;
+            case 96: MGEA_DENSE_CAUSAL(96); break;
+            default:
+                MGEA_REQUIRE(false, MGEA_EINVAL, "attention: head_dim %d not supported (32, 64, 96)", dh);
+        }
+#undef MGEA_DENSE_CAUSAL
+        MGEA_CHECK_HIP(hipGetLastError());
+        return MGEA_OK;
+    }
     switch (dh) {
-        case 32: hipLaunchKernelGGL(attn_dense_kernel<32>, grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); break;
-        case 64: hipLaunchKernelGGL(attn_dense_kernel<64>, grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); break;
-        case 96: hipLaunchKernelGGL(attn_dense_kernel<96>, grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); break;
+        case 32: hipLaunchKernelGGL((attn_dense_kernel<32, 0>), grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); break;
+        case 64: hipLaunchKernelGGL((attn_dense_kernel<64, 0>), grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); break;
+        case 96: hipLaunchKernelGGL((attn_dense_kernel<96, 0>), grid, dim3(256), 0, st, qkv, lens, mask, out, T, H, scale, tiled_out, cu); break;
         default:
             MGEA_REQUIRE(false, MGEA_EINVAL, "attention: head_dim %d not supported (32, 64, 96)", dh);
     }

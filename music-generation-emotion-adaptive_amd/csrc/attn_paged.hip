@@ -42,12 +42,22 @@ __device__ __forceinline__ float kv_elem(const f32x4& raw, int j) {
 // (Round 4 also built the merge INTO the consumer -- the kernel leaving partials only and the single-stream out-projection GEMV merging
 // them while loading its row, no counter at all: attention 6.35 -> 5.24 us and the GEMV 4.8 -> 5.3 in the kernel trace, but the B = 1 step
 // 174 us against 167.5 for the last-arriver merge, measured three times interleaved; removed.)
-template <int DH, bool F16, bool SPLIT>
+// CAUSAL (MGEA_POS_CAUSAL engines extending a cache by T > 1 tokens): query (b, t) sees the ctx_len[b] + t + 1 tokens up to itself instead
+// of all ctx_len[b] + n_new; the page count and the clamped last page follow from that one length (unsplit form only: the launcher
+// splits single-query launches, which are never causal launches).  Page 0
+// still holds a token of the row (t + 1 >= 1), so wave 0's early request stays valid.  A decode step (T == 1, t + 1 == n_new) is launched
+// as the non-causal kernel it always was.  The flag travels in the first template argument, head_dim + ATTN_PAGED_CAUSAL: every
+// non-causal instantiation keeps its symbol (tools and tests find kernels by their mangled names) and is the kernel it was,
+// instruction for instruction (profiles/causal_kernel_diff.txt).
+constexpr int ATTN_PAGED_CAUSAL = 1 << 16;
+template <int DHC, bool F16, bool SPLIT>
 __global__ __launch_bounds__(256) void attn_paged_kernel(const float* __restrict__ qkv, KvPool pool, int layer,
                                                         const int32_t* __restrict__ page_table, int max_pages,
                                                         const int32_t* __restrict__ ctx_len,
                                                         const int32_t* __restrict__ lens, float* __restrict__ out,
                                                         int H, int T, int C, float scale, int tiled_out, AttnSplit sp) {
+    constexpr int DH = DHC & (ATTN_PAGED_CAUSAL - 1);
+    constexpr bool CAUSAL = (DHC & ATTN_PAGED_CAUSAL) != 0;
     constexpr int G = F16 ? 8 : 4;     // elements per 16-byte group
     constexpr int EB = F16 ? 2 : 4;    // bytes per element
     constexpr int NCH = DH / G;        // 16-byte chunks per head row
@@ -132,7 +142,7 @@ __global__ __launch_bounds__(256) void attn_paged_kernel(const float* __restrict
         if (threadIdx.x < DH && zsplit == 0) *optr(threadIdx.x) = 0.f;
         return;
     }
-    const int len = c_len + n_new;  // tokens visible to this query (whole cache, no mask)
+    const int len = CAUSAL ? c_len + t + 1 : c_len + n_new;  // tokens visible to this query (non-causal: the whole cache, no mask)
     const int npages = (len + 63) >> 6;
     const int active = SPLIT ? min(nsplit, (npages + 3) >> 2) : 1;   // splits that have a page
     if (SPLIT && zsplit >= active) return;
@@ -297,7 +307,7 @@ int attn_split_count(int B, int H, int T, int max_pages) {
 
 int launch_attn_paged(const float* qkv, const KvPool& pool, int layer, const int32_t* page_table, int max_pages,
                       const int32_t* ctx_len, const int32_t* lens, float* out, int B, int T, int C, int tiled_out,
-                      hipStream_t st, const AttnSplit* split) {
+                      hipStream_t st, const AttnSplit* split, int causal) {
     const int H = pool.H, dh = pool.dh;
     MGEA_REQUIRE(H * dh == C, MGEA_EINVAL, "attention: n_head*head_dim != d_model");
     MGEA_REQUIRE(T <= 65535, MGEA_EINVAL, "attention: too many new tokens per row (%d)", T);
@@ -308,7 +318,10 @@ int launch_attn_paged(const float* qkv, const KvPool& pool, int layer, const int
     MGEA_REQUIRE(ns == 1 || (ns <= split->max_split && B * H * T <= split->max_items), MGEA_EINVAL, "attention: split scratch too small");
     dim3 grid(B * H, T, ns);
     const AttnSplit sp = split ? *split : AttnSplit{};
-#define MGEA_ATTN(DH, F) do { if (ns > 1) hipLaunchKernelGGL((attn_paged_kernel<DH, F, true>), grid, dim3(256), 0, st, qkv, pool_k, layer, page_table, max_pages, ctx_len, lens, out, H, T, C, scale, tiled_out, sp); \
+    const bool causal_form = causal && T > 1;   // T == 1: t + 1 == n_new, the kernels a step always launched.  T > 1 is never split
+    MGEA_REQUIRE(!causal_form || ns == 1, MGEA_EINVAL, "attention: the causal form has no split-context kernel");   // (attn_split_count)
+#define MGEA_ATTN(DH, F) do { if (causal_form) hipLaunchKernelGGL((attn_paged_kernel<DH + ATTN_PAGED_CAUSAL, F, false>), grid, dim3(256), 0, st, qkv, pool_k, layer, page_table, max_pages, ctx_len, lens, out, H, T, C, scale, tiled_out, sp); \
+                              else if (ns > 1) hipLaunchKernelGGL((attn_paged_kernel<DH, F, true>), grid, dim3(256), 0, st, qkv, pool_k, layer, page_table, max_pages, ctx_len, lens, out, H, T, C, scale, tiled_out, sp); \
                               else hipLaunchKernelGGL((attn_paged_kernel<DH, F, false>), grid, dim3(256), 0, st, qkv, pool_k, layer, page_table, max_pages, ctx_len, lens, out, H, T, C, scale, tiled_out, sp); } while (0)
     if (pool.f16) {
         switch (dh) {

@@ -60,6 +60,7 @@ const TuneEntry kTune[] = {
     {TUNE_DECODER_GRAPH_STEPS, "decoder_graph_steps", "MGEA_DECODER_GRAPH_STEPS", 8},
     {TUNE_ATTN_ARITH_PAGES, "attn_arith_pages", "MGEA_ATTN_ARITH_PAGES", 1},
     {TUNE_DECODER_QKV0_TABLE, "decoder_qkv0_table", "MGEA_DECODER_QKV0_TABLE", 1},
+    {TUNE_ATTN_CAUSAL_WALK, "attn_causal_walk", "MGEA_ATTN_CAUSAL_WALK", 1},
 };
 static_assert(sizeof(kTune) / sizeof(kTune[0]) == TUNE_COUNT, "one table row per switch");
 std::atomic<int> g_tune[TUNE_COUNT];
@@ -244,6 +245,19 @@ int mgea_op_attention_f32_ex(const float* qkv_dev, const int32_t* lens_dev, cons
     return launch_attn_dense(qkv_dev, lens_dev, mask_dev, out_dev, B, T, n_head, head_dim, tiled_out != 0, (hipStream_t)stream, cu_seqlens_dev);
 }
 
+int mgea_op_attention_f32_causal(const float* qkv_dev, const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head,
+                                 int32_t head_dim, int32_t tiled_out, void* stream) {
+    MGEA_REQUIRE(qkv_dev && out_dev, MGEA_EINVAL, "op_attention: NULL argument");
+    MGEA_REQUIRE(!tiled_out || ((int64_t)B * T <= MGEA_FUSED_MAX_ROWS && ((n_head * head_dim) % 32 == 0 || (int64_t)B * T <= 64)),
+                 MGEA_EINVAL, "op_attention: a k-tiled out holds at most %d rows (64 when its width is no multiple of 32)", MGEA_FUSED_MAX_ROWS);
+    return launch_attn_dense(qkv_dev, lens_dev, nullptr, out_dev, B, T, n_head, head_dim, tiled_out != 0, (hipStream_t)stream, nullptr, 1);
+}
+
+int mgea_op_logprob_gather(const float* logits_dev, int64_t ld, const int32_t* targets_dev, float* out_dev, int32_t M, int32_t V,
+                           void* stream) {
+    return launch_logprob_gather(logits_dev, ld, targets_dev, out_dev, M, V, (hipStream_t)stream);
+}
+
 int mgea_op_f32_to_bf16(const float* src_dev, void* dst_dev, int64_t n, void* stream) {
     MGEA_REQUIRE(src_dev && dst_dev && n > 0, MGEA_EINVAL, "op_f32_to_bf16: bad argument");
     return launch_f32_to_bf16(src_dev, dst_dev, n, (hipStream_t)stream);
@@ -390,11 +404,12 @@ int mgea_op_attn_split_scratch(int32_t head_dim, int64_t* part_floats_out, int64
     return MGEA_OK;
 }
 
-int mgea_op_attention_paged_ex(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
-                               int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
-                               const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
-                               int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
-                               int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream) {
+// mgea_op_attention_paged_ex and _causal: one body, the launcher's causal flag apart
+static int op_attention_paged(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
+                              int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
+                              const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                              int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
+                              int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream, int causal) {
     MGEA_REQUIRE(qkv_dev && pages_dev && page_table_dev && ctx_len_dev && out_dev && B > 0 && T > 0 && n_head > 0 && n_pages > 0 &&
                      max_pages > 0 && (dtype == MGEA_DTYPE_F32 || dtype == MGEA_DTYPE_F16),
                  MGEA_EINVAL, "op_attention_paged: bad argument");
@@ -423,11 +438,31 @@ int mgea_op_attention_paged_ex(const float* qkv_dev, const void* pages_dev, int3
     // what the launcher will decide from the same arguments (attn_paged.hip): workgroups per (row, head, query)
     if (info_out) info_out[0] = no_split ? 1 : attn_split_count(B, n_head, T, max_pages);
     const int rc = launch_attn_paged(qkv_dev, pool, layer, page_table_dev, max_pages, ctx_len_dev, lens_dev, out_dev, B, T, n_head * head_dim,
-                                     tiled_out != 0, st, no_split ? nullptr : &sp);
+                                     tiled_out != 0, st, no_split ? nullptr : &sp, causal);
     const hipError_t e = hipStreamSynchronize(st);
     MGEA_TRY(rc);
     MGEA_CHECK_HIP(e);
     return MGEA_OK;
+}
+
+int mgea_op_attention_paged_ex(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
+                               int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
+                               const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                               int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
+                               int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream) {
+    return op_attention_paged(qkv_dev, pages_dev, n_pages, n_layer, layer, dtype, arith_batch, page_table_dev, max_pages, ctx_len_dev, lens_dev,
+                              out_dev, B, T, n_head, head_dim, tiled_out, no_split, split_part_dev, split_part_floats, split_count_dev,
+                              split_count_ints, info_out, stream, 0);
+}
+
+int mgea_op_attention_paged_causal(const float* qkv_dev, const void* pages_dev, int32_t n_pages, int32_t n_layer, int32_t layer, int32_t dtype,
+                                   int32_t arith_batch, const int32_t* page_table_dev, int32_t max_pages, const int32_t* ctx_len_dev,
+                                   const int32_t* lens_dev, float* out_dev, int32_t B, int32_t T, int32_t n_head, int32_t head_dim,
+                                   int32_t tiled_out, int32_t no_split, float* split_part_dev, int64_t split_part_floats,
+                                   int32_t* split_count_dev, int64_t split_count_ints, int32_t* info_out, void* stream) {
+    return op_attention_paged(qkv_dev, pages_dev, n_pages, n_layer, layer, dtype, arith_batch, page_table_dev, max_pages, ctx_len_dev, lens_dev,
+                              out_dev, B, T, n_head, head_dim, tiled_out, no_split, split_part_dev, split_part_floats, split_count_dev,
+                              split_count_ints, info_out, stream, 1);
 }
 
 /* ablation / micro-benchmark hook for the fused skinny GEMM (tools/skinny_bench.py): EPI_ACT or

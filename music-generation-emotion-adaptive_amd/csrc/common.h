@@ -49,6 +49,7 @@ enum { TUNE_BF16_GEMM_TILE = 0,   // 0 = the launcher's choice; 1 128x128 / 2 25
        TUNE_DECODER_GRAPH_STEPS,  // decode steps per hipGraph launch of mgea_decoder_generate: 1, 2, 4, 8 (default) or 16; the single-step graph serves the remainder (round 4: 289.4 -> 287.6 us per step at B = 64, 168.3 -> 163.4 at B = 1)
        TUNE_ATTN_ARITH_PAGES,     // 1 (default): the decode attention computes physical page ids (j * batch + b, the decoder's own allocation) instead of loading them from the page table -- one dependent scalar load less per page; 0: always the table
        TUNE_DECODER_QKV0_TABLE,   // 1 (default): f32 engines in the reference's position mode keep layer 0's q | k | v of every token id in a [vocab][3 C] table and the step's tail gathers the row, so the layer-0 in-projection launch leaves the step (decoder.hip, "qkv0 table"; +vocab * 3 C * 4 bytes per engine and decode path); 0: the launch.  Read by mgea_decoder_create()
+       TUNE_ATTN_CAUSAL_WALK,     // the causal dense attention's walk of its grid = the kernel's CAUSAL template value: 1 (default) (row, head) pairs fastest and blocks last to first, so that a pair's blocks share an XCD and its L2; 2 the non-causal kernel's order, block index fastest (attn_dense.hip; A/B: profiles/causal_prefill_ab.txt)
        TUNE_COUNT };
 int tune(int key);
 
@@ -168,10 +169,12 @@ struct AttnSplit { float* part; int32_t* count; int max_split, max_items; };
 int attn_split_count(int B, int H, int T, int max_pages);
 int launch_attn_paged(const float* qkv, const KvPool& pool, int layer, const int32_t* page_table,
                       int max_pages, const int32_t* ctx_len, const int32_t* lens, float* out, int B, int T,
-                      int C, int tiled_out, hipStream_t st, const AttnSplit* split = nullptr);
+                      int C, int tiled_out, hipStream_t st, const AttnSplit* split = nullptr, int causal = 0);
+// causal != 0 with T > 1: query (b, t) sees ctx_len[b] + t + 1 tokens, not all T new ones (T == 1: the same launch either way)
 // dense non-causal attention over the qkv buffer itself (prefill without past, BERT)
 int launch_attn_dense(const float* qkv, const int32_t* lens, const int32_t* mask, float* out, int B, int T,
-                      int H, int dh, int tiled_out, hipStream_t st, const int32_t* cu = nullptr);   // cu: packed rows (T = the longest sequence)
+                      int H, int dh, int tiled_out, hipStream_t st, const int32_t* cu = nullptr, int causal = 0);   // cu: packed rows (T = the longest sequence)
+// causal != 0: query i sees the keys t <= i with t < lens[b]; refuses mask and cu
 
 // The sampler's scalars as the kernels read them from DEVICE memory: one 48-byte record per row, [max_batch] per engine.  A captured
 // decode-step graph holds only the pointer, so one graph serves every request whatever its seed / temperature / top-k / top-p / EOS id
@@ -357,6 +360,10 @@ int launch_window_evict(int32_t* page_table, int max_pages, int S, int R, int32_
 int launch_add_lens(int32_t* ctx_len, const int32_t* lens, int T, int B, hipStream_t st);
 // cur_ids[b] = ids[b, (lens ? lens[b] : T) - 1]
 int launch_take_last(const int32_t* ids, const int32_t* lens, int32_t* cur_ids, int B, int T, hipStream_t st);
+// lens_m1[b] = (lens ? lens[b] : T) - 1, never below 0: what a causal engine prefills of a prompt (its last token is fed by the first step)
+int launch_lens_minus_one(const int32_t* lens, int32_t* lens_m1, int T, int B, hipStream_t st);
+// out[m] = logits[m][targets[m]] - logsumexp(logits[m]) over V entries of a row of stride ld; targets[m] < 0 gives 0, >= V clamps
+int launch_logprob_gather(const float* logits, int64_t ld, const int32_t* targets, float* out, int M, int V, hipStream_t st);
 int launch_gather_rows(const float* src, int ld_src, float* dst, int ld_dst, int rows, int row_step, int C,
                        hipStream_t st, const int32_t* row_idx = nullptr);   // row_idx: source row of output row r (instead of r * row_step)
 int launch_lora_merge(float* w, const float* a, const float* b, int out_dim, int in_dim, int r, float scale,

@@ -60,6 +60,8 @@ int validate(const mgea_decoder_config* c) {
     MGEA_REQUIRE(c->dtype == MGEA_DTYPE_F32 || c->dtype == MGEA_DTYPE_F16, MGEA_EINVAL,
                  "decoder dtype %d not supported (MGEA_DTYPE_F32 or MGEA_DTYPE_F16)", c->dtype);
     MGEA_REQUIRE(c->block_mode == MGEA_BLOCK_PRELN_GELU || c->block_mode == MGEA_BLOCK_POSTLN_RELU, MGEA_EINVAL, "bad block_mode");
+    MGEA_REQUIRE(c->pos_mode != MGEA_POS_CAUSAL || c->block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL,
+                 "MGEA_POS_CAUSAL needs the KV-cache block mode (the post-LN twin has no cache to extend)");
     if (c->dtype == MGEA_DTYPE_F16) {   // the fp16 mode lives on the fused decode path (tiled fp16 matrices, fp16 KV pages)
         MGEA_REQUIRE(c->block_mode == MGEA_BLOCK_PRELN_GELU, MGEA_EINVAL, "MGEA_DTYPE_F16 needs the KV-cache block mode");
         MGEA_REQUIRE((c->d_model % 128) == 0 && c->d_model >= 256 && c->d_model <= 1024, MGEA_EINVAL,
@@ -68,6 +70,9 @@ int validate(const mgea_decoder_config* c) {
     }
     return MGEA_OK;
 }
+// "use true positions": both modes that are not the reference's (every site that adds a position asks here)
+bool true_positions(const mgea_decoder_config& c) { return c.pos_mode == MGEA_POS_ABSOLUTE || c.pos_mode == MGEA_POS_CAUSAL; }
+bool causal(const mgea_decoder_config& c) { return c.pos_mode == MGEA_POS_CAUSAL; }
 }  // namespace
 
 struct mgea_decoder {
@@ -106,6 +111,7 @@ struct mgea_decoder {
     int32_t *ctx_len = nullptr, *cur_ids = nullptr, *done = nullptr, *row_step = nullptr, *n_done = nullptr,
             *sampled = nullptr, *ids_hist = nullptr;
     int ids_hist_stride = 0;
+    int32_t* lens_m1 = nullptr;   // [max_batch], MGEA_POS_CAUSAL engines only: the prompt lengths a generation prefills (gen_prefill)
     // host mirror
     int cur_batch = 0, reserved_len = 0, host_max_len = 0, host_min_len = 0;
     // workspace
@@ -383,9 +389,9 @@ int run_blocks(mgea_decoder* h, int B, int T, const int32_t* lens, bool use_cach
         if (kv_only_last && scatter && l + 1 == c.n_layer) break;
         if (use_cache_attn) {
             PROF(PC_ATTN_PAGED, launch_attn_paged(h->qkv, h->kv, l, h->page_table, h->max_pages, h->ctx_len, lens, h->att, B, T,
-                                       C, 0, st, &h->attn_split));
+                                       C, 0, st, &h->attn_split, causal(c)));
         } else {
-            PROF(PC_ATTN_DENSE, launch_attn_dense(h->qkv, lens, nullptr, h->att, B, T, c.n_head, h->dh, 0, st));
+            PROF(PC_ATTN_DENSE, launch_attn_dense(h->qkv, lens, nullptr, h->att, B, T, c.n_head, h->dh, 0, st, nullptr, causal(c)));
         }
         MGEA_TRY(gemm(h, h->att, C, h->lw(l, L_OUTW), M, C, C, &S, st));
         if (post) {
@@ -479,9 +485,9 @@ int run_blocks_fused(mgea_decoder* h, int B, int T, const int32_t* lens, bool us
         if (l > 0 || !qkv0_primed) PROF(PC_GEMM, decode_gemm(h, l, 0, a, gv, st));
         if (kv_only_last && l + 1 == c.n_layer) break;       // (run_blocks: the logits are dropped, the last block's K | V are appended)
         if (use_cache_attn) {
-            PROF(PC_ATTN_PAGED, launch_attn_paged(h->qkv, h->kv, l, h->page_table, h->max_pages, h->ctx_len, lens, h->att, B, T, C, 1, st, &h->attn_split));
+            PROF(PC_ATTN_PAGED, launch_attn_paged(h->qkv, h->kv, l, h->page_table, h->max_pages, h->ctx_len, lens, h->att, B, T, C, 1, st, &h->attn_split, causal(c)));
         } else {
-            PROF(PC_ATTN_DENSE, launch_attn_dense(h->qkv, lens, nullptr, h->att, B, T, c.n_head, h->dh, 1, st));
+            PROF(PC_ATTN_DENSE, launch_attn_dense(h->qkv, lens, nullptr, h->att, B, T, c.n_head, h->dh, 1, st, nullptr, causal(c)));
         }
         // out_proj + residual (+ stats for ln2)
         SkinnyArgs o{};
@@ -524,7 +530,7 @@ struct StepCall {
 // What the kernel that embeds the next step's token works on; qkv0: the table of the step's path, or NULL (TailArgs, common.h)
 TailArgs tail_args(const mgea_decoder* h, const StepState& s, const float* qkv0) {
     const auto& c = h->cfg;
-    TailArgs t{s, h->w(T_TOK), h->w(T_POS), h->x, h->stats, c.d_model, c.vocab, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE};
+    TailArgs t{s, h->w(T_TOK), h->w(T_POS), h->x, h->stats, c.d_model, c.vocab, c.seq_len, true_positions(c)};
     if (qkv0) {
         t.qkv0 = qkv0; t.qkv = h->qkv;
         t.pool = h->kv; t.page_table = h->page_table; t.max_pages = h->max_pages;
@@ -589,7 +595,7 @@ int enqueue_step_fused(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     const int B = k.B, C = c.d_model, V = c.vocab;
     if (!k.primed)
         PROF(PC_ROWOP, launch_embed_stats(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->stats, B, 1, C, V,
-                                          c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
+                                          c.seq_len, true_positions(c), h->err_flag, st));
     MGEA_REQUIRE(!k.qkv0 || k.primed, MGEA_EINVAL, "internal: the qkv0 table serves primed steps only");
     MGEA_TRY(run_blocks_fused(h, B, 1, nullptr, true, st, false, k.qkv0 != nullptr));
     SkinnyArgs a{};
@@ -609,7 +615,7 @@ int enqueue_step(mgea_decoder* h, const StepCall& k, hipStream_t st) {
     if (fused_ok(h, B)) return enqueue_step_fused(h, k, st);
     PROF(PC_ROWOP, launch_embed_ln(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                              post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, 1, C,
-                             V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
+                             V, c.seq_len, true_positions(c), h->err_flag, st));
     MGEA_TRY(run_blocks(h, B, 1, nullptr, true, true, st));
     int S = 1;
     MGEA_TRY(gemm(h, h->x, C, h->head_w(), B, V, C, &S, st));
@@ -706,7 +712,7 @@ int prime_gen(mgea_decoder* h, int B, hipStream_t st) {
     if (const float* tab = qkv0_table(h, B))
         return launch_embed_qkv0(h->cur_ids, h->ctx_len, tail_args(h, StepState{}, tab), B, h->err_flag, st);
     return launch_embed_stats(h->cur_ids, nullptr, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->stats, B, 1, c.d_model, c.vocab,
-                              c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st);
+                              c.seq_len, true_positions(c), h->err_flag, st);
 }
 
 // The captured graph of `steps` decode steps of `kind` over B rows: from the cache, or captured + instantiated now (least recently used
@@ -764,6 +770,7 @@ int step_graph(mgea_decoder* h, int B, const StepKind& kind, int steps, hipStrea
 bool prefill16_ok(const mgea_decoder* h, int64_t M, bool cache_attn, const float* logits_out) {
     const auto& c = h->cfg;
     if (!h->f16 || cache_attn || c.block_mode != MGEA_BLOCK_PRELN_GELU || !tune(TUNE_DECODER_PREFILL16)) return false;
+    if (causal(c)) return false;   // attn16.hip has no causal form: a causal engine's prefills stay on the fp32-activation path
     if (h->dh != 64 || c.d_model % 256 != 0 || c.d_ff % 256 != 0 || c.d_model > 2048) return false;
     if (logits_out && c.vocab % 4 != 0) return false;
     // worth it from the size at which the smallest GEMM (N = d_model) fills the chip with 256 x 256 tiles; switch value 2 (tests)
@@ -841,7 +848,7 @@ int run_prefill16(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int 
     void *xc = p.x0, *xo = p.x1;
     const float *id_g = p.ident + p.rows * 2, *id_b = id_g + C;
     PROF(PC_ROWOP, launch_dec_embed_f16(ids, lens, h->ctx_len, h->w(T_TOK), h->w(T_POS), xc, p.rowstat, lens ? p.mask : nullptr, c.ln_eps, B, T,
-                                        C, V, c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
+                                        C, V, c.seq_len, true_positions(c), h->err_flag, st));
     // K | V of the real tokens reach the fp16 KV pages from inside the attention kernel of their layer (attn16.hip: it has those rows in LDS
     // anyway; round 3 ran a scatter kernel per layer that re-read them from the qkv buffer, on a side stream under the attention).  Only a
     // last block that stops at its K | V (kv_only_last: no attention runs) still uses the scatter kernel.
@@ -933,12 +940,12 @@ int do_forward(mgea_decoder* h, const int32_t* ids, const int32_t* lens, int B, 
         MGEA_TRY(run_prefill16(h, ids, lens, B, T, logits_out, st, kv_only_last));   // computes the logits itself (fp32 output of its head GEMM)
     } else if (fused_ok(h, (int)M)) {
         MGEA_TRY(launch_embed_stats(ids, lens, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->stats, B, T, C, V,
-                                    c.seq_len, c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
+                                    c.seq_len, true_positions(c), h->err_flag, st));
         MGEA_TRY(run_blocks_fused(h, B, T, lens, cache_attn, st, kv_only_last));
     } else {
         MGEA_TRY(launch_embed_ln(ids, lens, h->ctx_len, h->w(T_TOK), h->w(T_POS), h->x, h->xn,
                                  post ? nullptr : h->lw(0, L_LN1W), post ? nullptr : h->lw(0, L_LN1B), c.ln_eps, B, T, C,
-                                 V, c.seq_len, (!post) && c.pos_mode == MGEA_POS_ABSOLUTE, h->err_flag, st));
+                                 V, c.seq_len, (!post) && true_positions(c), h->err_flag, st));
         MGEA_TRY(run_blocks(h, B, T, lens, cache_attn, !post, st, kv_only_last));
     }
     if (p16) {
@@ -1137,6 +1144,11 @@ int mgea_decoder_create(const mgea_decoder_config* cfg, const float* arena_dev, 
         return fail(MGEA_EHIP, "state memset failed");
     int rc = ensure_ws(h, cfg->max_batch > 64 ? cfg->max_batch : 64);
     if (rc == MGEA_OK && fused_geometry(*cfg)) rc = build_tiled_weights(h, nullptr);
+    // (causal engines only, and last in the group: every other engine allocates what it always did, in the same order)
+    if (rc == MGEA_OK && causal(*cfg) && g.alloc(&h->lens_m1, nb)) {
+        set_error("decoder_create: state allocation failed");
+        rc = MGEA_ENOMEM;
+    }
     if (rc != MGEA_OK) {
         mgea_decoder_destroy(h);
         return rc;
@@ -1301,7 +1313,15 @@ int gen_prefill(mgea_decoder* h, const GenRequest& q, const GenPlan& p, hipStrea
         h->kv.arith_batch = 0;
         MGEA_CHECK_HIP(hipMemsetAsync(h->win_evict, 0, (size_t)c.max_batch * sizeof(int32_t), st));
     }
-    MGEA_TRY(do_forward(h, q.prompt_ids, q.lens, B, Tp, nullptr, st));
+    if (causal(c)) {
+        // Every token is fed once: the prefill takes the prompts without their last tokens (same ids, width and stride, lengths - 1), and
+        // the first step feeds the last token at position len - 1.  A prompt of one token prefills nothing.
+        MGEA_TRY(launch_lens_minus_one(q.lens, h->lens_m1, Tp, B, st));
+        if (Tp > 1) MGEA_TRY(do_forward(h, q.prompt_ids, h->lens_m1, B, Tp, nullptr, st));
+        MGEA_TRY(launch_take_last(q.prompt_ids, q.lens, h->cur_ids, B, Tp, st));
+    } else {
+        MGEA_TRY(do_forward(h, q.prompt_ids, q.lens, B, Tp, nullptr, st));
+    }
     if (p.kind.scheduled) {   // the generation's own prefill is segment 0; every row starts there
         MGEA_TRY(gather(0));
         MGEA_CHECK_HIP(hipMemsetAsync(h->cond_cur_seg, 0, (size_t)c.max_batch * sizeof(int32_t), st));
@@ -1447,6 +1467,8 @@ int gen_finish(mgea_decoder* h, const GenRequest& q, const GenPlan& p, int launc
 int do_generate(mgea_decoder* h, const GenRequest& q, hipStream_t st) {
     GenPlan p;
     MGEA_TRY(plan_generation(q, gen_limits(h), &p));
+    // (the conditioning store's [0, len) contract would need its own treatment where the last prompt token is not cached)
+    MGEA_REQUIRE(!(causal(h->cfg) && q.sched), MGEA_EINVAL, "decoder_generate_rows_scheduled: MGEA_POS_CAUSAL engines take no prompt schedules");
     mgea_decoder::LastGen last;
     h->last = last;   // a call that fails from here on reports nothing
     MGEA_TRY(gen_prefill(h, q, p, st));
@@ -1853,6 +1875,26 @@ int mgea_decoder_context_lengths(mgea_decoder* h, int32_t* lens_out_dev, void* s
     std::lock_guard<std::mutex> lk(h->mu);
     MGEA_CHECK_HIP(hipMemcpyAsync(lens_out_dev, h->ctx_len, (size_t)(h->cur_batch > 0 ? h->cur_batch : 0) * sizeof(int32_t),
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MGEA_OK;
+}
+
+int mgea_decoder_kv_pages(mgea_decoder* h, int32_t layer, void* pages_out_dev, int64_t pages_bytes, int32_t* page_table_out_dev,
+                          int64_t* info_out, void* stream) {
+    MGEA_REQUIRE(h && info_out, MGEA_EINVAL, "decoder_kv_pages: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    const auto& c = h->cfg;
+    MGEA_REQUIRE(h->kv.base, MGEA_EINVAL, "decoder_kv_pages needs the KV-cache block mode");
+    MGEA_REQUIRE(layer >= 0 && layer < c.n_layer, MGEA_EINVAL, "decoder_kv_pages: layer %d of %d", layer, c.n_layer);
+    const int64_t bytes = h->kv.layer_stride * (int64_t)h->kv.elt_bytes();
+    info_out[0] = h->kv.n_pages; info_out[1] = h->max_pages; info_out[2] = h->kv.elt_bytes(); info_out[3] = bytes;
+    if (!pages_out_dev && !page_table_out_dev) return MGEA_OK;   // the sizes only
+    MGEA_REQUIRE(pages_out_dev && page_table_out_dev && pages_bytes >= bytes, MGEA_EINVAL, "decoder_kv_pages: a layer of pages is %lld bytes",
+                 (long long)bytes);
+    hipStream_t st = (hipStream_t)stream;
+    MGEA_CHECK_HIP(hipMemcpyAsync(pages_out_dev, static_cast<const char*>(h->kv.base) + (int64_t)layer * bytes, (size_t)bytes,
+                                  hipMemcpyDeviceToDevice, st));
+    MGEA_CHECK_HIP(hipMemcpyAsync(page_table_out_dev, h->page_table, (size_t)c.max_batch * h->max_pages * sizeof(int32_t),
+                                  hipMemcpyDeviceToDevice, st));
     return MGEA_OK;
 }
 

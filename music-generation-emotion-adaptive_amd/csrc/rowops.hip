@@ -379,6 +379,21 @@ int launch_take_last(const int32_t* ids, const int32_t* lens, int32_t* cur_ids, 
     return MGEA_OK;
 }
 
+// what a causal engine prefills of a prompt: everything but its last token, which the first step feeds (a prompt of one token: nothing)
+__global__ void lens_minus_one_kernel(const int32_t* lens, int32_t* lens_m1, int T, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) {
+        int n = lens ? lens[b] : T;
+        n = n < 1 ? 1 : (n > T ? T : n);   // as take_last reads it
+        lens_m1[b] = n - 1;
+    }
+}
+int launch_lens_minus_one(const int32_t* lens, int32_t* lens_m1, int T, int B, hipStream_t st) {
+    hipLaunchKernelGGL(lens_minus_one_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, lens, lens_m1, T, B);
+    MGEA_CHECK_HIP(hipGetLastError());
+    return MGEA_OK;
+}
+
 __global__ void gather_rows_kernel(const float* __restrict__ src, int ld_src, float* __restrict__ dst, int ld_dst,
                                    int row_step, int C, const int32_t* __restrict__ row_idx) {
     const int64_t r = blockIdx.x;

@@ -96,11 +96,14 @@ class GPTWithKV:
     block_mode = "kv"
 
     def __init__(self, vocab_size, seq_len, d_model, n_head, n_layer, max_batch: int = 8,
-                 max_ctx: Optional[int] = None, device: str = _DEFAULT_DEVICE, dtype: str = "f32"):
+                 max_ctx: Optional[int] = None, device: str = _DEFAULT_DEVICE, dtype: str = "f32", causal: bool = False):
         self.vocab_size, self.seq_len, self.d_model = int(vocab_size), int(seq_len), int(d_model)
         self.n_head, self.n_layer = int(n_head), int(n_layer)
         self.max_batch, self.max_ctx, self.device = int(max_batch), max_ctx, device
         self.dtype = dtype   # "f32" = the reference's arithmetic (parity mode); "f16" = fp16 matrices + KV (mgea.decoder)
+        # causal: a checkpoint trained WITH a causal mask (a standard GPT) -- true positions, masked prefill, every token fed once
+        # (DecoderEngine pos_mode="causal"); False: the reference's model as api_cache.py evaluates it
+        self.causal = bool(causal)
         self.engine: Optional[DecoderEngine] = None
         self._epoch = -1
         self._window = None   # set_window's arguments, applied to every engine load_state_dict builds
@@ -117,7 +120,8 @@ class GPTWithKV:
             self.engine.close()
         max_ctx = self.max_ctx if self.max_ctx is not None else max(self.seq_len, 1)
         self.engine = DecoderEngine(sd, n_head=self.n_head, max_batch=self.max_batch, max_ctx=max_ctx,
-                                    device=self.device, block_mode=self.block_mode, dtype=self.dtype)
+                                    device=self.device, block_mode=self.block_mode, dtype=self.dtype,
+                                    pos_mode="causal" if self.causal else "reference")
         if self._window is not None:
             self.engine.set_window(*self._window)
         return "<All keys matched successfully>"
@@ -127,6 +131,8 @@ class GPTWithKV:
         beyond the engine's context -- the prompt stays cached, the oldest generated tokens leave a 64-token page at a time, as
         the reference's own loop has no context limit (api_cache.py:159-184).  sink_pages 0 clears it.  Kept across
         load_state_dict."""
+        if self.causal and int(sink_pages) != 0:   # before any engine is built (load_checkpoint(window=, causal=True) ends here)
+            raise ValueError("window: a causal model has no KV window (a step's position is its cached length); it needs causal=False")
         self._window = None if int(sink_pages) == 0 else (int(sink_pages), ring_pages, max_steps)
         if self.engine is not None:
             self.engine.set_window(sink_pages, ring_pages, max_steps)
@@ -179,15 +185,16 @@ class GPT(GPTWithKV):
 
 
 def load_checkpoint(path, n_head: int = 8, device: str = _DEFAULT_DEVICE, max_batch: int = 8,
-                    max_ctx: Optional[int] = None, window=None):
+                    max_ctx: Optional[int] = None, window=None, causal: bool = False):
     """api_cache.py:26-37,108-138 in one call: torch.load(weights_only=True), geometry from tensor
     shapes, GPTWithKV + remapped weights.  Returns (model, tok2id, id2tok, SEQ_LEN, D_MODEL) and
-    installs the vocabulary in this module.  window (None, or (sink_pages, ring_pages[, max_steps])): GPTWithKV.set_window."""
+    installs the vocabulary in this module.  window (None, or (sink_pages, ring_pages[, max_steps])): GPTWithKV.set_window.
+    causal=True: the checkpoint was trained with a causal mask; it is served as a standard causal GPT (GPTWithKV(causal=True))."""
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     geo = geometry_from_state_dict(ckpt["model"])
     set_vocab(ckpt["vocab"])
     m = GPTWithKV(vocab_size=len(tok2id), seq_len=geo["seq_len"], d_model=geo["d_model"], n_head=n_head,
-                  n_layer=geo["n_layer"], max_batch=max_batch, max_ctx=max_ctx, device=device)
+                  n_layer=geo["n_layer"], max_batch=max_batch, max_ctx=max_ctx, device=device, causal=causal)
     if window is not None:
         m.set_window(*window)
     m.load_state_dict(remap_state_dict(ckpt["model"]))
@@ -392,7 +399,9 @@ def generate_batch_truncated(model, prompts: Sequence[Sequence[str]], max_len=51
 
 def score_sequence(model, prompt_tokens: Sequence[str], continuation_tokens: Sequence[str]) -> List[float]:
     """The log-probability (natural log, raw head logits: no temperature, no top-k) of every token of continuation_tokens as
-    sample_kvcache would come to it after prompt_tokens: a teacher-forced run of the decode steps (DecoderEngine.score).
+    sample_kvcache would come to it after prompt_tokens: a teacher-forced run of the decode steps (DecoderEngine.score) -- or, for a
+    causal model, ONE masked prefill of prompt + continuation (DecoderEngine.score_prefill; beyond seq_len tokens, the position table,
+    a causal model too is scored step by step).
     Build-defined -- the reference returns no scores.  sum() of the result is the continuation's log-likelihood, exp(-mean) its
     perplexity."""
     eng = _as_model(model)._need()
@@ -402,7 +411,7 @@ def score_sequence(model, prompt_tokens: Sequence[str], continuation_tokens: Seq
         return []
     if _no_window(eng) and len(ids) + len(cont) > eng.max_ctx:
         raise RuntimeError(f"prompt + continuation = {len(ids) + len(cont)} tokens exceed the engine's reserved context {eng.max_ctx}")
-    lp, _ = eng.score([ids], [cont])
+    lp, _ = eng.score_prefill([ids], [cont]) if eng.causal else eng.score([ids], [cont])
     return [float(v) for v in lp[0].cpu().tolist()]
 
 

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("MGEA_LIB_PATH") or os.path.join(_HERE, "libmgea_hip.s
 OK, EINVAL, ENOMEM, EHIP, ECAPACITY, ENODEVICE = 0, -1, -2, -3, -4, -5
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 BLOCK_PRELN_GELU, BLOCK_POSTLN_RELU = 0, 1
-POS_REFERENCE, POS_ABSOLUTE = 0, 1
+POS_REFERENCE, POS_ABSOLUTE, POS_CAUSAL = 0, 1, 2
 KV_PAGE_TOKENS = 64
 
 
@@ -167,6 +167,7 @@ PROTOTYPES = {
     "mgea_decoder_grammar_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_presence": (C.c_int, [_P, _P, _P]),
     "mgea_decoder_context_lengths": (C.c_int, [_P, _P, _P]),
+    "mgea_decoder_kv_pages": (C.c_int, [_P, _I32, _P, _I64, _P, C.POINTER(_I64), _P]),
     "mgea_decoder_stats": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_qkv0_table_bytes": (C.c_int, [_P, C.POINTER(_I64)]),
     "mgea_decoder_error_flags": (C.c_int, [_P, C.POINTER(_I32), _P]),
@@ -185,6 +186,8 @@ PROTOTYPES = {
     "mgea_op_layernorm": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _P]),
     "mgea_op_attention_f32": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_attention_f32_ex": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_attention_f32_causal": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "mgea_op_logprob_gather": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _P]),
     "mgea_op_f32_to_bf16": (C.c_int, [_P, _P, _I64, _P]),
     "mgea_op_gemm_bf16": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "mgea_op_gemm_bf16_ln": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32), _P]),
@@ -204,6 +207,8 @@ PROTOTYPES = {
     "mgea_op_attn_split_scratch": (C.c_int, [_I32, C.POINTER(_I64), C.POINTER(_I64)]),
     "mgea_op_attention_paged_ex": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
                                              _P, _I64, _P, _I64, C.POINTER(_I32), _P]),
+    "mgea_op_attention_paged_causal": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
+                                                 _P, _I64, _P, _I64, C.POINTER(_I32), _P]),
     "mgea_op_tiled_weight_floats": (C.c_int64, [_I32, _I32]),
     "mgea_op_tile_weights": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "mgea_op_tile_rows": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),

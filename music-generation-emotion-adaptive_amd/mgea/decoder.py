@@ -856,6 +856,11 @@ def _prompt_ids(prompts):
 class DecoderEngine:
     """One native decoder handle on one GPU."""
 
+    # pos_mode "causal" (MGEA_POS_CAUSAL in include/mgea.h): a standard causal GPT -- true positions, a causal mask in every prefill,
+    # every token fed once; "reference": the reference's unmasked model with position row 0 on every step
+    POS_MODES = {"reference": _lib.POS_REFERENCE, "absolute": _lib.POS_ABSOLUTE, "causal": _lib.POS_CAUSAL}
+    SCORE_PREFILL_LOGITS_BYTES = 256 << 20   # score_prefill: the cap of one chunk's logits buffer
+
     def __init__(self, state_dict: Optional[Dict], n_head: int = 8, max_batch: int = 64, max_ctx: Optional[int] = None,
                  device="cuda:0", block_mode: str = "kv", pos_mode: str = "reference", geometry: Optional[Dict] = None,
                  arena: Optional[torch.Tensor] = None, ln_eps: float = 1e-5, dtype: str = "f32"):
@@ -866,7 +871,10 @@ class DecoderEngine:
         what differs from an fp32 run of THAT model is only activation and KV rounding (tests/test_gpu_f16.py)."""
         if dtype not in ("f32", "f16"):
             raise ValueError("decoder dtype must be 'f32' or 'f16'")
+        if pos_mode not in self.POS_MODES:
+            raise ValueError("decoder pos_mode must be 'reference', 'absolute' or 'causal'")
         self.dtype = dtype
+        self.causal = pos_mode == "causal"
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -880,7 +888,7 @@ class DecoderEngine:
                                  n_layer=self.n_layer, d_ff=self.d_ff, max_batch=self.max_batch, max_ctx=self.max_ctx,
                                  dtype=_lib.DTYPE_F16 if dtype == "f16" else _lib.DTYPE_F32,
                                  block_mode=_lib.BLOCK_PRELN_GELU if block_mode == "kv" else _lib.BLOCK_POSTLN_RELU,
-                                 pos_mode=_lib.POS_REFERENCE if pos_mode == "reference" else _lib.POS_ABSOLUTE,
+                                 pos_mode=self.POS_MODES[pos_mode],
                                  ln_eps=ln_eps)
         n = C.c_int32(0)
         total = C.c_int64(0)
@@ -1067,7 +1075,7 @@ class DecoderEngine:
             ring_pages = min(self.max_ctx // KV_PAGE_TOKENS - int(sink_pages), WINDOW_MAX_RING)
         w = KVWindow(int(sink_pages), int(ring_pages), int(16 * self.max_ctx if max_steps is None else max_steps))
         w.check(self.max_ctx)
-        if self.cfg.block_mode != _lib.BLOCK_PRELN_GELU or self.cfg.pos_mode != _lib.POS_REFERENCE:
+        if self.cfg.block_mode != _lib.BLOCK_PRELN_GELU or self.cfg.pos_mode != _lib.POS_REFERENCE:   # (causal engines too)
             raise ValueError("window: needs the KV-cache block mode and the reference's position mode")
         with self._on_stream():
             check(self.lib.mgea_decoder_set_window(self.h, w.sink_pages, w.ring_pages, w.max_steps, self._sp()))
@@ -1143,6 +1151,22 @@ class DecoderEngine:
             out = torch.empty(self._cur_batch, dtype=torch.int32, device=self.device)
             check(self.lib.mgea_decoder_context_lengths(self.h, ptr(out), self._sp()))
         return out
+
+    def kv_rows(self, layer: int, lens: Sequence[int]):
+        """Test only (mgea_decoder_kv_pages): the cached K and V of layer `layer`, read back through the page table: a list over the
+        rows b < len(lens) of (k, v) CPU tensors [lens[b], n_head, head_dim] in the pages' dtype (fp32, or fp16 on f16 engines)."""
+        from . import ops
+        info = (C.c_int64 * 4)()
+        check(self.lib.mgea_decoder_kv_pages(self.h, int(layer), None, 0, None, info, self._sp()))
+        n_pages, max_pages, eb, nbytes = (int(x) for x in info)
+        with self._on_stream():
+            image = torch.empty(nbytes // eb, dtype=torch.float16 if eb == 2 else torch.float32, device=self.device)
+            table = torch.empty(self.max_batch * max_pages, dtype=torch.int32, device=self.device)
+            check(self.lib.mgea_decoder_kv_pages(self.h, int(layer), ptr(image), nbytes, ptr(table), info, self._sp()))
+        torch.cuda.synchronize(self.device)
+        image, table = image.cpu(), table.cpu().view(self.max_batch, max_pages).numpy()
+        dh = self.d_model // self.n_head
+        return [ops.kv_pages_read(image, table, b, int(n), self.n_head, dh) for b, n in enumerate(lens)]
 
     # ------------------------------------------------------------------ sample_kvcache surface
     def generate(self, prompts, n_steps: int, temperature: float = 1.0, top_k: Optional[int] = 50,
@@ -1459,6 +1483,56 @@ class DecoderEngine:
         rows = [dataclasses.replace(r, max_new_tokens=len(c)) for r, c in zip(rows, conts)]
         res = self.generate_scored(prompts, rows, max(len(c) for c in conts), force_ids=conts)
         return res.logprobs, res.logprobs.sum(dim=1)
+
+    def score_prefill(self, prompts, continuations):
+        """score() in ONE causal prefill per chunk of rows instead of one decode step per token; causal engines only (ValueError
+        otherwise: a prefill of any other mode is bidirectional).  Resets, forwards prompt | continuation with logits and gathers the
+        log-probability of token t + 1 from the logits at position t (mgea_op_logprob_gather).  The batch rows are chunked so that a
+        chunk's logits buffer [rows, T, vocab] fp32 stays under SCORE_PREFILL_LOGITS_BYTES (256 MiB; one row at least) and under
+        max_batch rows.  prompts and continuations: B non-empty id lists each (ragged allowed).  Returns what score() returns:
+        (raw logprobs float32 [B, Tc] on the device, 0 past a row's length; their per-row sums [B]).
+        One forward takes at most seq_len tokens per row (the position table; mgea_decoder_forward refuses more), while decode steps
+        clamp positions and run on to max_ctx: a call with a row of more than seq_len tokens is scored by score(), step by step."""
+        from . import ops
+        if not self.causal:
+            raise ValueError("score_prefill needs a pos_mode='causal' engine (any other prefill is bidirectional); use score()")
+        prompts, conts = [list(p) for p in prompts], [list(c) for c in continuations]
+        if not conts or len(prompts) != len(conts):
+            raise ValueError(f"{len(prompts)} prompts but {len(conts)} continuations")
+        if min(len(p) for p in prompts) < 1:
+            raise ValueError("empty prompt")
+        if min(len(c) for c in conts) < 1:
+            raise ValueError("empty continuation")
+        if max(len(p) + len(c) for p, c in zip(prompts, conts)) > self.seq_len:
+            return self.score(prompts, conts)
+        B, Tc = len(conts), max(len(c) for c in conts)
+        out = torch.zeros(B, Tc, dtype=torch.float32, device=self.device)
+        b0 = 0
+        while b0 < B:
+            # rows of this chunk: as many as the cap allows at the width of the chunk's first row (widths only shrink the count)
+            n, T = 0, 0
+            while b0 + n < B and n < self.max_batch:
+                Tn = max(T, len(prompts[b0 + n]) + len(conts[b0 + n]))
+                if n > 0 and (n + 1) * Tn * self.vocab * 4 > self.SCORE_PREFILL_LOGITS_BYTES:
+                    break
+                n, T = n + 1, Tn
+            rows = [prompts[b] + conts[b] for b in range(b0, b0 + n)]
+            ids, lens = _prompt_ids(rows)
+            # targets[b, t] = the token at t + 1 where that is a continuation token, -1 (not scored) elsewhere
+            tg = torch.full((n, T), -1, dtype=torch.int32)
+            for i, b in enumerate(range(b0, b0 + n)):
+                lp, lc = len(prompts[b]), len(conts[b])
+                tg[i, lp - 1:lp - 1 + lc] = torch.tensor(conts[b], dtype=torch.int32)
+            self._check_ids(ids)
+            self.reset(n, T)
+            logits = self.forward(ids, lens)
+            with self._on_stream():
+                lp_all = ops.logprob_gather(logits.view(n * T, self.vocab), tg.view(-1).to(self.device)).view(n, T)
+                for i, b in enumerate(range(b0, b0 + n)):
+                    lp, lc = len(prompts[b]), len(conts[b])
+                    out[b, :lc] = lp_all[i, lp - 1:lp - 1 + lc]
+            b0 += n
+        return out, out.sum(dim=1)
 
     def presence(self) -> torch.Tensor:
         """bool [B, vocab] on the device: the ids each row of the last (penalized) generate() has seen -- its real prompt

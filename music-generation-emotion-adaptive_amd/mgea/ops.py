@@ -46,8 +46,9 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float) -> 
 
 def attention(qkv: torch.Tensor, n_head: int, lens: Optional[torch.Tensor] = None,
               mask: Optional[torch.Tensor] = None, cu: Optional[torch.Tensor] = None, tiled: bool = False,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """qkv [B,T,3C] -> [B,T,C]; non-causal, keys valid per lens / mask.  cu [B + 1] (packed rows): qkv [cu[B], 3C] -> [cu[B], C], T = the
+              out: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
+    """qkv [B,T,3C] -> [B,T,C]; non-causal, keys valid per lens / mask.  causal: query i sees the keys t <= i that lens leaves valid
+    (mgea_op_attention_f32_causal; mask and cu are the launcher's refusal, RuntimeError).  cu [B + 1] (packed rows): qkv [cu[B], 3C] -> [cu[B], C], T = the
     longest sequence.  tiled: the output is the flat k-tiled buffer of tiled_floats(B * T, C) floats (untile_rows reads it).  out: a
     caller buffer of that many floats (B * T * C row-major), written in place and returned.  What the launcher refuses (cu with lens,
     mask or tiled) is left to the launcher."""
@@ -72,8 +73,37 @@ def attention(qkv: torch.Tensor, n_head: int, lens: Optional[torch.Tensor] = Non
         _buf(out, tiled_floats(rows, Cd) if tiled else rows * Cd, torch.float32, "attention: out")
     l32 = None if lens is None else _dev(lens.to(torch.int32))
     m32 = None if mask is None else _dev(mask.to(torch.int32))
+    if causal:
+        if mask is not None or cu is not None:   # what launch_attn_dense answers to causal with a mask or packed rows
+            raise RuntimeError("attention: the causal form takes no mask and no packed rows")
+        check(lib.mgea_op_attention_f32_causal(ptr(qkv), ptr(l32), ptr(out), B, T, n_head, Cd // n_head, int(bool(tiled)), stream_ptr()))
+        return out
     check(lib.mgea_op_attention_f32_ex(ptr(qkv), ptr(l32), ptr(m32), ptr(c32), ptr(out), B, T, n_head, Cd // n_head, int(bool(tiled)),
                                        stream_ptr()))
+    return out
+
+
+attention_f32 = attention   # (the C entry point's name)
+
+
+def logprob_gather(logits: torch.Tensor, targets, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m] = logits[m, targets[m]] - logsumexp(logits[m]) (mgea_op_logprob_gather): logits [M, V] fp32 on the device, rows of any
+    stride; targets [M] ints, < 0 = not scored (0).  A target >= V in HOST targets (a list or a CPU tensor) is a RuntimeError, the
+    library's MGEA_EINVAL; device targets are not read back and clamp to V - 1.  out: a caller buffer of at least M floats."""
+    if logits.device.type != "cuda" or logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("logprob_gather: logits must be a [M, V] fp32 device tensor with unit column stride")
+    M, V = logits.shape
+    t = targets if isinstance(targets, torch.Tensor) else torch.tensor(list(targets), dtype=torch.int32)
+    if t.numel() != M:
+        raise RuntimeError(f"logprob_gather: {M} rows but {t.numel()} targets")
+    if t.device.type != "cuda" and M and int(t.max()) >= V:
+        raise RuntimeError(f"logprob_gather: target {int(t.max())} outside the vocabulary of {V}")
+    t32 = t.to(device=logits.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=logits.device)
+    else:
+        _buf(out, M, torch.float32, "logprob_gather: out")
+    check(_lib.load().mgea_op_logprob_gather(ptr(logits), logits.stride(0), ptr(t32), ptr(out), M, V, stream_ptr()))
     return out
 
 
@@ -408,14 +438,15 @@ def dec_embed_f16(ids: torch.Tensor, tok_emb: torch.Tensor, pos_emb: torch.Tenso
 def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_table: torch.Tensor, ctx_len: torch.Tensor,
                     lens: Optional[torch.Tensor] = None, arith_batch: int = 0, split: bool = True,
                     info: Optional[list] = None, layer: int = 0, n_layer: int = 1, tiled: bool = False,
-                    out: Optional[torch.Tensor] = None, scratch=None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, scratch=None, causal: bool = False) -> torch.Tensor:
     """The decode / extend attention over one layer of device KV pages (fp32 or fp16 tensor): the queries are columns 0..C-1 of the
     fp32 qkv [B, T, 3C]; row b attends to its ctx_len[b] + (lens[b] or T) cached tokens.  split=False: never the split-context form.
     info: a list that receives [workgroups per (row, head, query)] of the launch (1 = the unsplit kernel).
     pages holds n_layer layers of pages (one after the other, as in the decoder's pool) and the kernel reads `layer`.  tiled: the
     output is the flat k-tiled buffer of tiled_floats(B * T, C) floats.  out: a caller buffer of that size (B * T * C row-major),
     written in place and returned.  scratch = (part, count) from attn_split_scratch(): the caller's split-context scratch, which the
-    call neither allocates nor zeroes."""
+    call neither allocates nor zeroes.  causal: query (b, t) attends to its ctx_len[b] + t + 1 tokens, not to all the new ones
+    (mgea_op_attention_paged_causal; T == 1 is the same launch either way)."""
     lib = _lib.load()
     qkv = _dev(qkv.float())
     B, T, C3 = qkv.shape
@@ -443,11 +474,12 @@ def attention_paged(qkv: torch.Tensor, n_head: int, pages: torch.Tensor, page_ta
         _buf(part, 1, torch.float32, "attention_paged: scratch part")
         _buf(count, 1, torch.int32, "attention_paged: scratch count")
     io = (C.c_int32 * 1)(-1)
-    check(lib.mgea_op_attention_paged_ex(ptr(qkv), ptr(pages), n_pages, int(n_layer), int(layer),
-                                         _lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32, int(arith_batch), ptr(pt),
-                                         pt.shape[1], ptr(cl), ptr(l32), ptr(out), B, T, n_head, dh, int(bool(tiled)), int(not split),
-                                         ptr(part), 0 if part is None else part.numel(), ptr(count), 0 if count is None else count.numel(),
-                                         io, stream_ptr()))
+    fn = lib.mgea_op_attention_paged_causal if causal else lib.mgea_op_attention_paged_ex
+    check(fn(ptr(qkv), ptr(pages), n_pages, int(n_layer), int(layer),
+             _lib.DTYPE_F16 if pages.dtype == torch.float16 else _lib.DTYPE_F32, int(arith_batch), ptr(pt),
+             pt.shape[1], ptr(cl), ptr(l32), ptr(out), B, T, n_head, dh, int(bool(tiled)), int(not split),
+             ptr(part), 0 if part is None else part.numel(), ptr(count), 0 if count is None else count.numel(),
+             io, stream_ptr()))
     if info is not None:
         info[:] = [int(io[0])]
     return out

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Is the device code of two builds of csrc/ the same?  Needs no GPU.
-  python3 tools/kernel_diff.py PARENT_BUILD_DIR CHANGE_BUILD_DIR [--moved OLD=NEW1,NEW2] [--out FILE]
+  python3 tools/kernel_diff.py PARENT_BUILD_DIR CHANGE_BUILD_DIR [--moved OLD=NEW1,NEW2] [--rename REGEX=REPL ...] [--out FILE]
 For every *.o of both directories the gfx950 code object is taken out of the fat binary (llvm-objcopy --dump-section .hip_fatbin,
 clang-offload-bundler --unbundle).  Objects present under one name on both sides are compared by sha256.  For --moved OLD=NEW,...
 the kernels of OLD.o are looked up in the NEW objects and compared symbol by symbol: the disassembled instruction text (addresses
 and encodings dropped, so that a branch reads as its distance) and the resource record of the kernel descriptor
 (.amdhsa_ directives of llvm-objdump's disassembly of the .rodata descriptor: VGPRs, SGPRs, LDS, scratch, kernel-argument size).
+--rename REGEX=REPL (repeatable) rewrites the PARENT's symbol names before they are looked up: a kernel that gained a template parameter
+has a new mangled name and is still compared instruction by instruction.
 A plain per-symbol diff; exit status 1 if anything differs."""
 import argparse, hashlib, os, re, subprocess, sys, tempfile
 
@@ -61,6 +63,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent"); ap.add_argument("change")
     ap.add_argument("--moved", default="")
+    ap.add_argument("--rename", action="append", default=[])
     ap.add_argument("--out")
     a = ap.parse_args()
     old_name, new_names = (a.moved.split("=")[0], a.moved.split("=")[1].split(",")) if a.moved else (None, [])
@@ -83,6 +86,9 @@ def main():
         bad += len(extra)
         lines += [f"{n}.o  only in the change" for n in extra]
         old = kernels(code_object(os.path.join(a.parent, old_name + ".o"), tmp)) if old_name else {}
+        for r in a.rename:
+            pat, repl = r.split("=", 1)
+            old = {re.sub(pat, repl, k): v for k, v in old.items()}
         new, where = {}, {}
         for n in new_names:
             for k, v in kernels(code_object(os.path.join(a.change, n + ".o"), tmp)).items():
