@@ -1,5 +1,6 @@
 """CPU checks of what the causal-mode GPU tests stand on (tests/causal_util.py): the input families against fp64 at every shape the GPU
-tests use, CausalRef against the golden-pinned oracle and against itself, and the host rules of a causal generation's prefill."""
+tests use, CausalRef against the golden-pinned oracle and against itself, the host rules of a causal generation's prefill, and the oracle of the
+generation forms (causal_step_logits, walk) with the input conditions of every case test_gpu_causal_forms.py runs."""
 import numpy as np
 import pytest
 import torch
@@ -108,6 +109,80 @@ def test_greedy_feeds_every_token_once(tiny):
         full = torch.tensor(outs[b][:-1]).view(1, -1)
         lg, _, _ = ref.forward(full)
         assert float((lg[0, len(p) - 1:] - sl[b]).abs().max()) < 1e-5
+
+
+def test_step_logits_are_the_rows_of_one_masked_forward(tiny):
+    """causal_step_logits (prefill without the last token, feed it, feed the ids) = ONE masked forward over prompt + fed at positions
+    len - 1 + s, to the 1e-5 the cached and the uncached CausalRef are held to; a one-token prompt prefills nothing"""
+    sd, _ = tiny
+    ref = U.CausalRef(sd, n_head=2)
+    prompts = [[3], [1, 5], [1, 7, 20, 33, 34], [int(v) for v in synth.integers(9, "causal_host", (30,), 0, 97)]]
+    fed = [[int(v) for v in row] for row in synth.integers(10, "causal_host", (4, 8), 0, 97)]
+    got = U.causal_step_logits(ref, prompts, fed)
+    assert got.shape == (4, 8, 97) and got.dtype == torch.float32
+    assert U.CausalSteps(ref, prompts).rows[0] == [None, None]
+    for b, p in enumerate(prompts):
+        whole, _, _ = ref.forward(torch.tensor([p + fed[b][:-1]]))
+        assert float((whole[0, len(p) - 1:] - got[b]).abs().max()) < 1e-5
+
+
+def test_step_logits_with_every_switch_off_are_oracle_logps(tiny):
+    """the reference-mode loop the other generation tests hard-code (prefill the whole prompt, re-feed its last token): bit for bit"""
+    from test_gpu_guidance import oracle_logps
+    sd, ref = tiny
+    off = U.CausalRef(sd, n_head=2, true_pos=False, causal_mask=False, feed_once=False)
+    prompts = [[3], [1, 5], [1, 7, 20, 33, 34]]
+    fed = [[int(v) for v in row] for row in synth.integers(11, "causal_host", (3, 6), 0, 97)]
+    got = U.causal_step_logits(off, prompts, fed)
+    for b, p in enumerate(prompts):
+        assert torch.equal(torch.log_softmax(got[b].double(), dim=1), oracle_logps(ref, p, fed[b]))
+
+
+def test_walk_without_a_form_is_generate_greedy(tiny):
+    sd, _ = tiny
+    ref = U.CausalRef(sd, n_head=2)
+    prompts = [[3], [1, 5], [1, 7, 20, 33, 34]]
+    want, sl = ref.generate_greedy(prompts, 8, return_logits=True)
+    res = U.walk(ref, [[p] for p in prompts], [(1.0,)] * 3, 8)
+    assert [p + ids for p, ids in zip(prompts, res["ids"])] == want
+    lp = torch.log_softmax(sl.double(), -1).gather(2, torch.tensor(res["ids"])[..., None])[..., 0]
+    assert float((lp - torch.from_numpy(res["logprobs"])).abs().max()) < 1e-5
+
+
+@pytest.mark.parametrize("name", U.FORMS)
+@pytest.mark.parametrize("kind", ["tiny", "fused"])
+def test_form_cases_meet_their_input_conditions(kind, name):
+    """what test_gpu_causal_forms.py assumes of its inputs (causal_util.input_conditions): greedy top-2 gaps of at least
+    5 x W x F32_TOL at every (row, step), so the GPU tests demand exact ids; the placed forced ids and the mixes move the checked values
+    by ten bounds.  The 5-token prompt's last id occurs nowhere else in it."""
+    groups, weights, _ = U.form_case(kind, name)
+    prompts = U.form_prompts(kind, U.FORM_SEEDS[kind, name])
+    assert [len(p) for p in prompts] == list(U.FORM_LENS) and prompts[2][-1] not in prompts[2][:-1]
+    assert [g[0] for g in groups] == (prompts[1:] if name == "composed" else prompts)
+    assert U.F32_TOL == 2e-4 and list(U.gap_floor(weights)) == [5 * U.mix_weight(w) * 2e-4 for w in weights]
+    assert U.input_conditions(kind, name) == []
+    if name in ("penalty", "bias", "grammar", "guided", "blended", "cpen"):
+        forced, res = U.draw_forced(kind, name)
+        _, _, form = U.form_case(kind, name)
+        assert all(len(f) == U.FORM_STEPS and min(f) >= 0 for f in forced) and np.isfinite(res["choice"]).all()
+        assert form.eos is None or all(e not in f for e, f in zip(form.eos, forced))
+
+
+def test_forced_ids_place_the_last_prompt_id_and_its_class():
+    from test_gpu_class_penalty import map12
+    for kind in ("tiny", "fused"):
+        forced, _ = U.draw_forced(kind, "penalty")
+        groups, _, _ = U.form_case(kind, "penalty")
+        assert forced[2][0] == groups[2][0][-1]
+        forced, _ = U.draw_forced(kind, "cpen")
+        groups, _, form = U.form_case(kind, "cpen")
+        placed = 0
+        for b, g in enumerate(groups):
+            c = form.class_of[g[0][-1]]
+            if c >= 0:
+                assert form.class_of[forced[b][0]] == c and forced[b][0] != g[0][-1]
+                placed += 1
+        assert placed >= 2 and np.array_equal(form.class_of, map12(len(form.class_of)))
 
 
 def test_prefill_lens_rule():

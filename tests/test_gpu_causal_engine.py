@@ -51,7 +51,7 @@ def tokens(kind, B, T, tag="ids"):
 def _close_engines():
     yield
     for k, v in list(_cache.items()):
-        if k[0] != "ref":
+        if k[0] not in ("ref", "ref16"):
             v.close()
     _cache.clear()
 
@@ -241,6 +241,81 @@ def test_score_prefill_past_the_position_table_scores_step_by_step():
     lp1, _ = eng.score_prefill([prompt], [cont[:n - 40]])
     w1, _ = eng.score([prompt], [cont[:n - 40]])
     assert float((lp1.cpu() - w1.cpu()).abs().max()) < 4e-4
+
+
+def reference16():
+    """the model the fp16 engine serves: CausalRef on the `fused` weights with the five matrix kinds rounded to fp16 (test_gpu_f16.rounded)"""
+    from test_gpu_f16 import rounded
+    if ("ref16", "fused") not in _cache:
+        _cache[("ref16", "fused")] = U.CausalRef(rounded(_sd("fused")), n_head=GEO["fused"]["n_head"])
+    return _cache[("ref16", "fused")]
+
+
+def test_f16_prefill_logits_against_the_rounded_causal_reference():
+    """the fp16 causal engine's numbers: an fp32 dense causal prefill on fp16 matrices, [3, 70] ragged (70, 33, 1), held to
+    test_gpu_f16.F16_LOGIT_TOL against the oracle on the rounded weights.  Observed on MI355X: 7.3e-4."""
+    from test_gpu_f16 import F16_LOGIT_TOL
+    eng, ref = engine("fused", dtype="f16"), reference16()
+    idx, lens = tokens("fused", 3, 70), torch.tensor([70, 33, 1])
+    got = eng.reset_and_prefill(idx, lens).cpu()
+    valid = torch.arange(70)[None, :] < lens[:, None]
+    want, _, _ = ref.forward(idx, None, None, valid)
+    worst = float((got - want).abs()[valid].max())
+    print(f"[causal f16] prefill 3x70 ragged: max |logits - CausalRef(rounded)| = {worst:.3e}")
+    assert worst < F16_LOGIT_TOL
+
+
+@pytest.mark.parametrize("a", [64, 65])
+def test_f16_prefills_compose_each_side_against_the_oracle(a):
+    """forward(ids[:, :a]) then forward(ids[:, a:]) -- the fp16 causal PAGED kernel extending fp16 pages that the fp32 dense causal
+    prefill wrote -- and the one-shot forward, each against the oracle on the rounded weights (the two runs differ from each other by
+    the rounding of the first a tokens' K and V, so they are not compared at an fp32 bound), and one further step from either cache.
+    Observed on MI355X: 7.3e-4 for one forward and for two (a = 64 and 65), 4.5e-4 .. 5.1e-4 for the step behind them."""
+    from test_gpu_f16 import F16_LOGIT_TOL
+    eng, ref = engine("fused", dtype="f16"), reference16()
+    B, T = 3, 80
+    idx = tokens("fused", B, T, "compose")
+    nxt = tokens("fused", B, 1, "compose_next")[:, 0]
+    want, cache, valid = ref.forward(idx)
+    want_step, _, _ = ref.forward(nxt.view(B, 1), cache, valid)
+    samp = eng.sampler(1.0, 1)
+    whole = eng.reset_and_prefill(idx).cpu()
+    _, step_whole = eng.step(nxt.to(torch.int32), samp, want_logits=True)
+    eng.reset(B)
+    parts = torch.cat([eng.forward(idx[:, :a]).cpu(), eng.forward(idx[:, a:]).cpu()], 1)
+    assert eng.context_lengths().cpu().tolist() == [T] * B
+    _, step_parts = eng.step(nxt.to(torch.int32), samp, want_logits=True)
+    d = {"one forward": float((whole - want).abs().max()), "two forwards": float((parts - want).abs().max()),
+         "step behind one": float((step_whole.cpu() - want_step[:, -1]).abs().max()),
+         "step behind two": float((step_parts.cpu() - want_step[:, -1]).abs().max())}
+    print(f"[causal f16] compose a={a}: max |logits - CausalRef(rounded)|: " + ", ".join(f"{k} {v:.3e}" for k, v in d.items()))
+    assert max(d.values()) < F16_LOGIT_TOL, d
+    assert not torch.equal(parts[:, a:], whole[:, a:]), "the paged form read the same K and V as the dense one: no fp16 page was read"
+
+
+def test_f16_teacher_forced_steps_against_the_rounded_causal_reference():
+    """40 teacher-forced steps through generate_scored(force_ids = the oracle's greedy ids) behind the ragged prompts of 1, 2, 5 and 65
+    tokens: raw log-probabilities within 2 x F16_LOGIT_TOL of the oracle on the rounded weights (one bound for the logit, one for the
+    log-sum, as test_gpu_logprobs) -- and, the control of the reference-mode test, more than 1e-4 from the UNROUNDED model's: the mode
+    is not a no-op.  Observed on MI355X: 3.7e-4 against the rounded model, 4.6e-4 against the unrounded one."""
+    from mgea.decoder import RowSampling
+    from test_gpu_f16 import F16_LOGIT_TOL
+    eng, ref = engine("fused", dtype="f16"), reference16()
+    prompts, n = _prompts("fused"), 40
+    outs, sl = ref.generate_greedy(prompts, n, return_logits=True)
+    forced = [o[len(p):] for o, p in zip(outs, prompts)]
+    res = eng.generate_scored(prompts, [RowSampling(top_k=1, eos_id=-1) for _ in prompts], n, force_ids=forced)
+    assert res.ids.cpu().tolist() == forced
+    assert eng.context_lengths().cpu().tolist() == [len(p) - 1 + n for p in prompts]
+    got = res.logprobs.cpu().double()
+    want = torch.log_softmax(sl.double(), -1).gather(2, torch.tensor(forced)[..., None])[..., 0]
+    d = float((got - want).abs().max())
+    sl32 = U.causal_step_logits(reference("fused"), prompts, forced)
+    want32 = torch.log_softmax(sl32.double(), -1).gather(2, torch.tensor(forced)[..., None])[..., 0]
+    d32 = float((got - want32).abs().max())
+    print(f"[causal f16] 4 rows x {n} teacher-forced steps: max |logprob - oracle(rounded)| = {d:.3e}, against the unrounded model {d32:.3e}")
+    assert d <= 2 * F16_LOGIT_TOL
+    assert d32 > 1e-4
 
 
 def test_f16_causal_engine_never_takes_the_16_bit_prefill():
