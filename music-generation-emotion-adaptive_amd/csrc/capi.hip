@@ -12,6 +12,7 @@
 #include "common.h"
 #include "devmem.h"
 #include "hipres.h"
+#include "rowtable.h"
 
 namespace mgea {
 static thread_local char g_err[512] = "";
@@ -27,6 +28,10 @@ bool dev_malloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSucce
 void dev_free(void* p) { (void)hipFree(p); }
 bool pinned_malloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, 0) == hipSuccess; }
 void pinned_free(void* p) { (void)hipHostFree(p); }
+int upload_async(void* dst, const void* src, size_t bytes, hipStream_t st) {
+    MGEA_CHECK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+    return MGEA_OK;
+}
 void event_destroy(hipEvent_t ev) { (void)hipEventDestroy(ev); }
 void graph_destroy(hipGraph_t graph, hipGraphExec_t exec) {
     if (exec) (void)hipGraphExecDestroy(exec);   // (NULL: a graph whose capture or instantiation failed)

@@ -48,7 +48,7 @@ enum { TUNE_BF16_GEMM_TILE = 0,   // 0 = the launcher's choice; 1 128x128 / 2 25
        TUNE_ATTN_SPLIT,           // the decode step's attention of at most this many (row, head) pairs spreads each pair's KV pages over several workgroups, the last one to arrive merges their partials (default 64 = 8 rows of 8 heads: measured +3..5 % tokens/s at 1-8 rows, nothing at 16, -3.5 % at 32; 0: always one workgroup per pair)
        TUNE_DECODER_GRAPH_STEPS,  // decode steps per hipGraph launch of mgea_decoder_generate: 1, 2, 4, 8 (default) or 16; the single-step graph serves the remainder (round 4: 289.4 -> 287.6 us per step at B = 64, 168.3 -> 163.4 at B = 1)
        TUNE_ATTN_ARITH_PAGES,     // 1 (default): the decode attention computes physical page ids (j * batch + b, the decoder's own allocation) instead of loading them from the page table -- one dependent scalar load less per page; 0: always the table
-       TUNE_DECODER_QKV0_TABLE,   // 1 (default): f32 engines in the reference's position mode keep layer 0's q | k | v of every token id in a [vocab][3 C] table and the step's tail gathers the row, so the layer-0 in-projection launch leaves the step (decoder.hip, "qkv0 table"; +vocab * 3 C * 4 bytes per engine and decode path); 0: the launch.  Read by mgea_decoder_create()
+       TUNE_DECODER_QKV0_TABLE,   // 1 (default): f32 engines in the reference's position mode keep layer 0's q | k | v of every token id in a [vocab][3 C] table and the step's tail gathers the row, so the layer-0 in-projection launch leaves the step (decoder_handle.h, "qkv0 table"; +vocab * 3 C * 4 bytes per engine and decode path); 0: the launch.  Read by mgea_decoder_create()
        TUNE_ATTN_CAUSAL_WALK,     // the causal dense attention's walk of its grid = the kernel's CAUSAL template value: 1 (default) (row, head) pairs fastest and blocks last to first, so that a pair's blocks share an XCD and its L2; 2 the non-causal kernel's order, block index fastest (attn_dense.hip; A/B: profiles/causal_prefill_ab.txt)
        TUNE_COUNT };
 int tune(int key);
@@ -231,7 +231,7 @@ struct TailArgs {
     const float* tok_emb; const float* pos_emb;
     float* x; float* stats;     // k-tiled residual stream and its LayerNorm partials (fused decode path)
     int C, vocab, pos_rows, absolute_pos;
-    // qkv0 != NULL (decoder.hip, "qkv0 table"): row [id] of the [vocab][3 C] table is layer 0's q | k | v of the embedding, so the tail also
+    // qkv0 != NULL (decoder_handle.h, "qkv0 table"): row [id] of the [vocab][3 C] table is layer 0's q | k | v of the embedding, so the tail also
     // does what the next step's layer-0 in-projection launch would have done -- the row into qkv [B][3 C], its K | V into layer 0's page --
     // and leaves out the embedding's LayerNorm statistics, which only that launch read.
     const float* qkv0; float* qkv;

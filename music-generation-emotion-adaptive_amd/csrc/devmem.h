@@ -44,6 +44,19 @@ struct BufGroup {
         fields.clear();
     }
 
+    // Frees the buffer of one field, nulls it and forgets it: for an owner of two buffers whose second allocation failed.
+    template <typename T>
+    void drop(T** field) {
+        void** f = reinterpret_cast<void**>(field);
+        for (size_t i = fields.size(); i-- > 0;) {
+            if (fields[i] != f) continue;
+            if (*f) Free(*f);
+            *f = nullptr;
+            fields.erase(fields.begin() + (long)i);
+            return;
+        }
+    }
+
 private:
     std::vector<void**> fields;
 };

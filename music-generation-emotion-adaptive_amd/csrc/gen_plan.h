@@ -1,6 +1,6 @@
 // What a generation is asked for (GenRequest), which launch sequence its steps take (StepKind) and everything the host decides before
 // the first launch (GenPlan): plan_generation holds every refusal of mgea_decoder_generate* that needs no device, in one order, and
-// derives the plan from the host records alone; do_generate (decoder.hip) runs exactly that plan.  Plain C++17, no HIP include and no
+// derives the plan from the host records alone; do_generate (decoder_generate.hip) runs exactly that plan.  Plain C++17, no HIP include and no
 // handle: tests/native/gen_plan_test.cpp compiles it for the host alone.
 #pragma once
 #include <stdint.h>
@@ -383,6 +383,18 @@ inline int plan_generation(const GenRequest& q, const GenLimits& c, GenPlan* out
     p.kind = StepKind{form, scored, windowed, guided, p.n_sched > 0, p.truncated, blended, cpen};
     *out = p;
     return MGEA_OK;
+}
+
+// Which row's inputs each row of a planned generation runs on, -1 = its own.  A non-leader member of a blend group takes its leader's,
+// otherwise a guidance shadow row its conditional row's (a row is never both: check_row_blend).  Same inputs -- records, bias vector,
+// forced ids, presence bitmap --, same id.  guide / blend: the request's records, NULL = absent.
+inline std::vector<int> mirror_sources(const mgea_row_guidance* guide, const mgea_row_blend* blend, int B) {
+    std::vector<int> src((size_t)B, -1);
+    for (int b = B - 1; guide && b >= 0; --b)   // (descending: of two rows naming one shadow, which the plan refuses, the lower would win)
+        if (guide[b].shadow_row >= 0 && guide[b].shadow_row < B) src[(size_t)guide[b].shadow_row] = b;
+    for (int u = 0; blend && u < B; ++u)
+        if (blend[u].leader >= 0 && blend[u].leader != u) src[(size_t)u] = blend[u].leader;
+    return src;
 }
 
 }  // namespace mgea

@@ -1,7 +1,7 @@
 // plan_generation (csrc/gen_plan.h) and the rows' blend records (mgea_row_blend) on the CPU: blended => kind.blended and never the
 // GREEDY form, both flags for a batch with a guidance pair and a group, the refusals with the row their message names, the capped call,
-// NULL or all -1 records => the truncated plan there was before, and the step-graph key.  set_error is this file's own: it keeps the
-// last message.  Run by tests/test_blend_host.py; exit status 0 and "blend_plan ok" = every check held.
+// NULL or all -1 records => the truncated plan there was before, the step-graph key, and mirror_sources, the row whose inputs each
+// row of a batch with pairs and groups takes.  set_error is this file's own: it keeps the last message.  Run by tests/test_blend_host.py; exit status 0 and "blend_plan ok" = every check held.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -216,6 +216,70 @@ int main() {
         CHECK(planned(r).capped);
         int g = -1, n = -1;
         CHECK(check_row_blend(r.blend.data(), 4, nullptr, nullptr, &g, &n) == MGEA_OK && g == 0 && n == 0);
+    }
+    // ---- mirror_sources: the row whose inputs each row takes -- a member its leader, a shadow its conditional row, -1 otherwise
+    {
+        using V = std::vector<int>;
+        const mgea_row_guidance g0{-1, 0.f};
+        Req r(6, 50);
+        CHECK(mirror_sources(nullptr, nullptr, 6) == V(6, -1));                      // no pairs, no groups
+        r.guide.assign(6, g0);
+        r.with_blend();
+        CHECK(mirror_sources(r.guide.data(), r.blend.data(), 6) == V(6, -1));        // records that name nobody
+        r.guide[2] = {5, 1.5f};
+        CHECK(mirror_sources(r.guide.data(), nullptr, 6) == (V{-1, -1, -1, -1, -1, 2}));   // one pair
+        CHECK(mirror_sources(r.guide.data(), r.blend.data(), 6) == (V{-1, -1, -1, -1, -1, 2}));
+        r.guide[2] = g0;
+        r.guide[0] = {4, 1.5f};                                                      // a pair and a group in one batch of 6
+        r.group(1, {1, 2, 5}, {0.6f, 0.3f, 0.1f});
+        CHECK(planned(r).kind.guided && planned(r).kind.blended);
+        CHECK(mirror_sources(r.guide.data(), r.blend.data(), 6) == (V{-1, -1, 1, -1, 0, 1}));
+        CHECK(mirror_sources(nullptr, r.blend.data(), 6) == (V{-1, -1, 1, -1, -1, 1}));
+    }
+    {   // one group of MGEA_BLEND_MAX_ROWS rows whose leader is its last row: every other member points at it, a leader never at itself
+        const int n = MGEA_BLEND_MAX_ROWS;
+        Req r(n + 2, 50);
+        std::vector<int> members;
+        for (int i = 0; i < n; ++i) members.push_back(i + 1);
+        r.group(n, members, std::vector<float>((size_t)n, 1.f / (float)n));
+        CHECK(planned(r).n_blend_rows == n);
+        const std::vector<int> src = mirror_sources(nullptr, r.blend.data(), n + 2);
+        for (int u = 0; u < n + 2; ++u) CHECK(src[(size_t)u] == (u >= 1 && u < n ? n : -1));
+        for (int u = 0; u < n + 2; ++u) CHECK(src[(size_t)u] != u);
+    }
+    {   // B = 64 with 32 pairs (the conditional rows and the shadows each in a scrambled order), and the same with two of the pairs
+        // turned into groups: the list equals the double loop that stood in mirror_shadow_rows before it had one
+        const int B = 64;
+        std::vector<mgea_row_guidance> guide((size_t)B, mgea_row_guidance{-1, 0.f});
+        std::vector<mgea_row_blend> blend((size_t)B, kNone);
+        for (int i = 0; i < 32; ++i) guide[(size_t)((i * 7) % 32)] = {32 + (i * 11) % 32, 1.0f + 0.01f * (float)i};   // 7 and 11 are units mod 32
+        for (int pass = 0; pass < 2; ++pass) {
+            const GenLimits lim{100, 80, 128, MGEA_BLOCK_PRELN_GELU, 0, 0, 0, 0};
+            Req r(B, 50);
+            r.guide = guide;
+            if (pass == 1) {   // two pairs less, their four rows in two groups
+                r.guide[0] = r.guide[7] = mgea_row_guidance{-1, 0.f};
+                r.with_blend();
+                r.group(guide[0].shadow_row, {0, guide[0].shadow_row}, {0.5f, 0.5f});
+                r.group(7, {7, guide[7].shadow_row}, {0.25f, 0.75f});
+            }
+            const GenPlan p = planned(r, lim);
+            CHECK(p.n_pairs == (pass ? 30 : 32) && p.n_groups == (pass ? 2 : 0));
+            const GenRequest& q = r.get();
+            std::vector<int> want((size_t)B, -1);
+            for (int u = 0; u < q.B; ++u) {   // the loop as it stood in mirror_shadow_rows
+                int b = -1;
+                if (p.kind.blended && q.blend[u].leader >= 0 && q.blend[u].leader != u) b = q.blend[u].leader;
+                for (int c = 0; p.kind.guided && b < 0 && c < q.B; ++c)
+                    if (q.guide[c].shadow_row == u) b = c;
+                want[(size_t)u] = b;
+            }
+            const std::vector<int> got = mirror_sources(p.kind.guided ? q.guide : nullptr, p.kind.blended ? q.blend : nullptr, B);
+            CHECK(got == want);
+            int mirrored = 0;
+            for (int u = 0; u < B; ++u) mirrored += got[(size_t)u] >= 0;
+            CHECK(mirrored == 32);   // 32 shadows; 30 shadows and 2 members
+        }
     }
     if (g_failures) {
         fprintf(stderr, "%d check(s) failed\n", g_failures);

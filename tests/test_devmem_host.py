@@ -1,5 +1,5 @@
-"""The owners of the engines' HIP resources on the CPU: the buffer groups (csrc/devmem.h) and the decoder's step-graph cache and events
-(csrc/hipres.h).  tests/native/*_test.cpp define the runtime functions an owner calls over malloc / free -- with a "fail the k-th
+"""The owners of the engines' HIP resources on the CPU: the buffer groups (csrc/devmem.h), the decoder's step-graph cache and events
+(csrc/hipres.h) and its per-row record tables (csrc/rowtable.h).  tests/native/*_test.cpp define the runtime functions an owner calls over malloc / free -- with a "fail the k-th
 call" counter for the allocations -- and are built with AddressSanitizer (leak detection included) and UBSan.  Failure paths of the
 engines' allocations cannot be reached on a GPU without exhausting it, and a graph cache is slow to fill there; this is where they
 are covered.  The host plan of a generation (csrc/gen_plan.h) is built and run the same way: its refusals are plain arithmetic on
@@ -34,6 +34,11 @@ def test_devgroup_under_asan_and_ubsan(tmp_path):
 @pytest.mark.skipif(torch.cuda.is_available(), reason="sanitizer run: CPU machines only")
 def test_stepgraphs_under_asan_and_ubsan(tmp_path):
     run_sanitized(tmp_path, "stepgraphs")   # StepGraphs and Event (csrc/hipres.h)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="sanitizer run: CPU machines only")
+def test_rowtable_under_asan_and_ubsan(tmp_path):
+    run_sanitized(tmp_path, "rowtable")   # RowTable (csrc/rowtable.h): failed allocations, set / copy_row / upload ranges, release
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="sanitizer run: CPU machines only")

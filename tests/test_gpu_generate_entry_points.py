@@ -3,7 +3,9 @@ called directly through ctypes, then again through mgea_decoder_generate_rows_sc
 calls -- with NULL (or n_seg_max = 1) for what it lacks.  Both calls must give the same ids, log-probabilities and report, bit for
 bit, and the second one must replay the first one's graphs: the same step kind, so the same graph key.
 On the fused path (decoder_tiny8h, d_model 256) and the unfused one (decoder_tiny, d_model 128); 12 steps = one 8-step graph launch
-plus four single-step replays, as in test_gpu_step_forms.py."""
+plus four single-step replays, as in test_gpu_step_forms.py.
+In the library every one of these entry points builds its request in one file-local function (csrc/decoder_generate.hip:
+generate_rows), so what this test holds is the argument order and the NULL defaults of each exported signature."""
 import ctypes as C
 
 import numpy as np

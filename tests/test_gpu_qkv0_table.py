@@ -1,4 +1,4 @@
-"""Layer 0's q | k | v from the per-token table (switch decoder_qkv0_table; csrc/decoder.hip, "qkv0 table"): an engine created with the
+"""Layer 0's q | k | v from the per-token table (switch decoder_qkv0_table; csrc/decoder_handle.h, "qkv0 table"): an engine created with the
 switch on and one created with it off produce the same bits -- ids, log-probabilities, error flags -- in every step form, across a page
 boundary, for rows that stop, with a full cache and on both decode paths (3..64 rows: MFMA kernels; 1..2 rows: dot products), and the
 form is not taken where it must not be (more than 64 rows, absolute positions, fp16 engines, mgea_decoder_step)."""
