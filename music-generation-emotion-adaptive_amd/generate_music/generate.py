@@ -24,7 +24,8 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from mgea.decoder import DecoderEngine, RowSampling, Truncation, geometry_from_state_dict, remap_state_dict  # noqa: F401
+from mgea.decoder import (DecoderEngine, RowSampling, Truncation, geometry_from_state_dict, remap_state_dict,  # noqa: F401
+                          split_logit_bias)
 
 __all__ = ["GPTWithKV", "GPT", "remap_state_dict", "load_checkpoint", "set_vocab", "encode", "decode",
            "closest_bpm_token", "normalize_key_signature", "FAMILY_TO_INSTRUMENTS", "note_re", "sample_kvcache",
@@ -236,11 +237,7 @@ def _engine_generate(eng, ids, n_steps, logit_bias, min_new_tokens, grammar=None
         from .grammar import start_state
         _use_grammar(eng, grammar)
         B = len(ids)
-        per_row = [logit_bias] * B
-        if logit_bias is not None and not isinstance(logit_bias, dict) and getattr(logit_bias, "ndim", 1) == 2:
-            if logit_bias.shape[0] != B:
-                raise ValueError(f"logit_bias must be [{eng.vocab}] or [{B}, {eng.vocab}], got {list(logit_bias.shape)}")
-            per_row = [logit_bias[b] for b in range(B)]
+        per_row = split_logit_bias(logit_bias, B, eng.vocab)
         rows = [RowSampling(temperature=kw.get("temperature", 1.0), top_k=kw.get("top_k", 50), top_p=kw.get("top_p"),
                             repetition_penalty=kw.get("repetition_penalty"), eos_id=kw.get("eos_id", -1), seed=kw.get("seed", 0),
                             logit_bias=per_row[b], min_new_tokens=min(int(min_new_tokens), n_steps),
@@ -503,9 +500,24 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     in this order (mgea.decoder.Truncation); with none of them this is the call it always was.
     class_penalty (one mgea.decoder.ClassPenalty for every prompt, or a list with one per prompt, None = none): the row's windowed
     penalty over the classes of the engine's map (DecoderEngine.set_penalty_classes; generate_music.variety.token_classes)."""
-    m = _as_model(model)
-    eng = m._need()
-    n = len(prompts)
+    eng = _as_model(model)._need()
+    ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
+    budgets, live, rows = _request_rows(eng, ids, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias, min_new_tokens,
+                                        grammar, min_p, typical_p, epsilon_cutoff, eta_cutoff, class_penalty, refuse_max_len=True)
+    return _serve(eng, ids, budgets, live, lambda i: 1,
+                  lambda part, steps: eng.generate_rows([ids[i] for i in part], [rows[i] for i in part], steps))
+
+
+def _request_rows(eng, ids, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias, min_new_tokens, grammar,
+                  min_p, typical_p, epsilon_cutoff, eta_cutoff, class_penalty=None, refuse_max_len=False):
+    """The request table of the generate_requests* functions.  ids: each request's prompt -- its first variant -- as ids; every other
+    argument a scalar for all the requests or a list with one value per request (grammar: ONE TokenGrammar or None).  Returns
+    (budgets, live, rows): every request's max_len - len(prompt), the indices of those with a budget left, and {index: RowSampling}
+    for them -- budget, seed (None = drawn here, in ascending order: a spent request draws none), Philox stream 0, min_new_tokens
+    capped at the budget, the state its prompt leads to in the grammar, which becomes the engine's.
+    refuse_max_len: a live request whose max_len exceeds the engine's context is refused here, before anything reaches the engine
+    (generate_requests; the forms that cost more rows than one check prompt width + steps per generation, _check_fits)."""
+    n = len(ids)
     max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
     temps = _per_prompt(temperature, n, "temperature")
     ks = _per_prompt(top_k, n, "top_k")
@@ -517,16 +529,15 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
     truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
                                              _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     cpens = _per_prompt(class_penalty, n, "class_penalty")
-    ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
     budgets = [L - len(p) for L, p in zip(max_lens, ids)]
-    for L, p in zip(max_lens, ids):
-        if _no_window(eng) and L > len(p) and L > eng.max_ctx:
-            raise RuntimeError(f"max_len={L} exceeds the engine's reserved context {eng.max_ctx}")
-    eos = tok2id.get("[END_SEQUENCE]", -1)
     live = [i for i in range(n) if budgets[i] > 0]
+    for i in live if refuse_max_len and _no_window(eng) else ():
+        if max_lens[i] > eng.max_ctx:
+            raise RuntimeError(f"max_len={max_lens[i]} exceeds the engine's reserved context {eng.max_ctx}")
     for i in range(n):
         if mins[i] < 0:
             raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
+    eos = tok2id.get("[END_SEQUENCE]", -1)
     gstates = [None] * n
     if grammar is not None:
         from .grammar import start_state
@@ -537,13 +548,33 @@ def generate_requests(model, prompts: Sequence[Sequence[str]], max_len=512, temp
                            logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i],
                            class_penalty=cpens[i])
             for i in live}
+    return budgets, live, rows
+
+
+def _serve(eng, ids, budgets, live, cost, run) -> List[List[str]]:
+    """The serving loop of the generate_requests* functions: the live requests, in order, are cut into generations of as many whole
+    requests as fit into the engine's max_batch rows -- cost(i): the rows request i takes -- and run(part, steps), the form's engine
+    call for the requests `part` and their largest budget, returns their ids [len(part), steps].  Returns every request's prompt
+    (ids[i]) + what it generated, as tokens; a request that is not live is its prompt."""
     gen: Dict[int, List[int]] = {}
-    for c0 in range(0, len(live), eng.max_batch):
-        part = live[c0:c0 + eng.max_batch]
-        out = eng.generate_rows([ids[i] for i in part], [rows[i] for i in part], max(budgets[i] for i in part)).cpu().tolist()
-        for i, row in zip(part, out):
-            gen[i] = [g for g in row if g >= 0]
-    return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]
+    part, used = [], 0
+    for i in live + [None]:   # (None: behind the last request)
+        if part and (i is None or used + cost(i) > eng.max_batch):
+            out = run(part, max(budgets[j] for j in part)).cpu().tolist()
+            for j, row in zip(part, out):
+                gen[j] = [g for g in row if g >= 0]
+            part, used = [], 0
+        if i is not None:
+            part.append(i)
+            used += cost(i)
+    return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(len(ids))]
+
+
+def _check_fits(eng, width: int, steps: int) -> None:
+    """A guided, scheduled or blended generation is never capped: without a KV window, prompt width + steps beyond the context is
+    refused when its generation is reached."""
+    if _no_window(eng) and width + steps > eng.max_ctx:
+        raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
 
 
 def sample_kvcache_varied(model, prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu",
@@ -617,19 +648,8 @@ def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=51
     min_p, typical_p, epsilon_cutoff, eta_cutoff (None = off; HuggingFace's names and semantics): further cuts behind top-k and top-p,
     in this order (mgea.decoder.Truncation); with none of them this is the call it always was."""
     from .guidance import unconditional_prompt
-    m = _as_model(model)
-    eng = m._need()
+    eng = _as_model(model)._need()
     n = len(prompts)
-    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
-    temps = _per_prompt(temperature, n, "temperature")
-    ks = _per_prompt(top_k, n, "top_k")
-    ps = _per_prompt(top_p, n, "top_p")
-    seeds = _per_prompt(seed, n, "seed")
-    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
-    biases = _per_prompt(logit_bias, n, "logit_bias")
-    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
-    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
-                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     scales = [float(v) for v in _per_prompt(guidance_scale, n, "guidance_scale")]
     negs = [None] * n if negative_prompts is None else list(negative_prompts)
     if len(negs) != n:
@@ -637,36 +657,16 @@ def generate_requests_guided(model, prompts: Sequence[Sequence[str]], max_len=51
     negs = [unconditional_prompt(p) if q is None else list(q) for p, q in zip(prompts, negs)]
     ids = [[tok2id[t] for t in p] for p in prompts]   # KeyError for an unknown token, like api_cache.py:162
     neg_ids = [[tok2id[t] for t in q] for q in negs]
-    budgets = [L - len(p) for L, p in zip(max_lens, ids)]
     if eng.max_batch < 2:
         raise ValueError("guided generation needs a model with max_batch >= 2 (a request is a pair of rows)")
-    for i in range(n):
-        if mins[i] < 0:
-            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
-    eos = tok2id.get("[END_SEQUENCE]", -1)
-    live = [i for i in range(n) if budgets[i] > 0]
-    gstates = [None] * n
-    if grammar is not None:
-        from .grammar import start_state
-        _use_grammar(eng, grammar)
-        gstates = [start_state(grammar, p) for p in ids]
-    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
-                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
-            for i in live}
-    gen: Dict[int, List[int]] = {}
-    per = eng.max_batch // 2
-    for c0 in range(0, len(live), per):
-        part = live[c0:c0 + per]
-        steps = max(budgets[i] for i in part)
-        width = max(max(len(ids[i]), len(neg_ids[i])) for i in part)
-        if _no_window(eng) and width + steps > eng.max_ctx:
-            raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
-        out = eng.generate_guided([ids[i] for i in part], [neg_ids[i] for i in part], [rows[i] for i in part],
-                                  [scales[i] for i in part], steps).cpu().tolist()
-        for i, row in zip(part, out):
-            gen[i] = [g for g in row if g >= 0]
-    return [[id2tok[t] for t in ids[i] + gen.get(i, [])] for i in range(n)]
+    budgets, live, rows = _request_rows(eng, ids, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias, min_new_tokens,
+                                        grammar, min_p, typical_p, epsilon_cutoff, eta_cutoff)
+
+    def run(part, steps):
+        _check_fits(eng, max(max(len(ids[i]), len(neg_ids[i])) for i in part), steps)
+        return eng.generate_guided([ids[i] for i in part], [neg_ids[i] for i in part], [rows[i] for i in part],
+                                   [scales[i] for i in part], steps)
+    return _serve(eng, ids, budgets, live, lambda i: 2, run)
 
 
 def sample_kvcache_transitions(model, prompts: Sequence[Sequence[str]], shares=None, max_len=512, temperature=1.0, top_k=50,
@@ -704,8 +704,7 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
     from mgea.decoder import RowSchedule
     from .guidance import unconditional_prompt
     from .transitions import start_thresholds, step_thresholds
-    m = _as_model(model)
-    eng = m._need()
+    eng = _as_model(model)._need()
     n = len(prompt_segments)
     segs = [[list(v) for v in ps] for ps in prompt_segments]
     for i, ps in enumerate(segs):
@@ -714,16 +713,6 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
     shares = [None] * n if shares is None else list(shares)
     if len(shares) != n:
         raise ValueError(f"shares: {len(shares)} values for {n} requests")
-    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
-    temps = _per_prompt(temperature, n, "temperature")
-    ks = _per_prompt(top_k, n, "top_k")
-    ps_ = _per_prompt(top_p, n, "top_p")
-    seeds = _per_prompt(seed, n, "seed")
-    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
-    biases = _per_prompt(logit_bias, n, "logit_bias")
-    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
-    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
-                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     guided = guidance_scale is not None
     scales = [float(v) for v in _per_prompt(guidance_scale if guided else 0.0, n, "guidance_scale")]
     negs = [None] * n if negative_prompts is None else list(negative_prompts)
@@ -735,17 +724,9 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
         if eng.max_batch < 2:
             raise ValueError("guided generation needs a model with max_batch >= 2 (a request is a pair of rows)")
         neg_ids = [[tok2id[t] for t in (unconditional_prompt(ps[0]) if q is None else list(q))] for ps, q in zip(segs, negs)]
-    budgets = [L - len(p[0]) for L, p in zip(max_lens, ids)]
-    for i in range(n):
-        if mins[i] < 0:
-            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
-    eos = tok2id.get("[END_SEQUENCE]", -1)
-    live = [i for i in range(n) if budgets[i] > 0]
-    gstates = [None] * n
-    if grammar is not None:
-        from .grammar import start_state
-        _use_grammar(eng, grammar)
-        gstates = [start_state(grammar, p[0]) for p in ids]
+    first = [p[0] for p in ids]
+    budgets, live, rows = _request_rows(eng, first, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias,
+                                        min_new_tokens, grammar, min_p, typical_p, epsilon_cutoff, eta_cutoff)
     scheds = {}
     for i in live:
         sh = [1.0] * len(ids[i]) if shares[i] is None else list(shares[i])
@@ -753,24 +734,13 @@ def generate_requests_transitions(model, prompt_segments: Sequence[Sequence[Sequ
             raise ValueError(f"request {i}: {len(sh)} shares for {len(ids[i])} prompt variants")
         scheds[i] = RowSchedule(tuple(start_thresholds(grammar, sh)), 1) if grammar is not None else \
             RowSchedule(tuple(step_thresholds(budgets[i], sh)), 0)
-    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps_[i], repetition_penalty=pens[i], eos_id=eos,
-                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
-            for i in live}
-    gen: Dict[int, List[int]] = {}
-    per = eng.max_batch // 2 if guided else eng.max_batch
-    for c0 in range(0, len(live), per):
-        part = live[c0:c0 + per]
-        steps = max(budgets[i] for i in part)
-        width = max(max(len(ids[i][0]), len(neg_ids[i] or [])) for i in part)
-        if _no_window(eng) and width + steps > eng.max_ctx:
-            raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
-        out = eng.generate_scheduled([ids[i] for i in part], [rows[i] for i in part], [scheds[i] for i in part], steps,
-                                     negative_prompts=[neg_ids[i] for i in part] if guided else None,
-                                     guidance_scale=[scales[i] for i in part]).cpu().tolist()
-        for i, row in zip(part, out):
-            gen[i] = [g for g in row if g >= 0]
-    return [[id2tok[t] for t in ids[i][0] + gen.get(i, [])] for i in range(n)]
+
+    def run(part, steps):
+        _check_fits(eng, max(max(len(first[i]), len(neg_ids[i] or [])) for i in part), steps)
+        return eng.generate_scheduled([ids[i] for i in part], [rows[i] for i in part], [scheds[i] for i in part], steps,
+                                      negative_prompts=[neg_ids[i] for i in part] if guided else None,
+                                      guidance_scale=[scales[i] for i in part])
+    return _serve(eng, first, budgets, live, lambda i: 2 if guided else 1, run)
 
 
 def sample_kvcache_blended(model, prompts: Sequence[Sequence[str]], weights: Sequence[float], max_len=512, temperature=1.0, top_k=50,
@@ -815,48 +785,15 @@ def generate_requests_blended(model, prompt_groups: Sequence[Sequence[Sequence[s
             raise ValueError(f"request {i}: {len(weights[i])} weights for {len(g)} prompts")
         if len(g) > eng.max_batch:
             raise ValueError(f"request {i}: a group of {len(g)} rows needs a model with max_batch >= {len(g)}")
-    max_lens = [int(v) for v in _per_prompt(max_len, n, "max_len")]
-    temps = _per_prompt(temperature, n, "temperature")
-    ks = _per_prompt(top_k, n, "top_k")
-    ps = _per_prompt(top_p, n, "top_p")
-    seeds = _per_prompt(seed, n, "seed")
-    pens = _per_prompt(repetition_penalty, n, "repetition_penalty")
-    biases = _per_prompt(logit_bias, n, "logit_bias")
-    mins = [int(v) for v in _per_prompt(min_new_tokens, n, "min_new_tokens")]
-    truncs = [Truncation.of(*v) for v in zip(_per_prompt(min_p, n, "min_p"), _per_prompt(typical_p, n, "typical_p"),
-                                             _per_prompt(epsilon_cutoff, n, "epsilon_cutoff"), _per_prompt(eta_cutoff, n, "eta_cutoff"))]
     ids = [[[tok2id[t] for t in v] for v in g] for g in groups]   # KeyError for an unknown token, like api_cache.py:162
-    budgets = [L - len(g[0]) for L, g in zip(max_lens, ids)]
-    for i in range(n):
-        if mins[i] < 0:
-            raise ValueError(f"min_new_tokens: {mins[i]} for prompt {i} is negative")
-    eos = tok2id.get("[END_SEQUENCE]", -1)
-    live = [i for i in range(n) if budgets[i] > 0]
-    gstates = [None] * n
-    if grammar is not None:
-        from .grammar import start_state
-        _use_grammar(eng, grammar)
-        gstates = [start_state(grammar, g[0]) for g in ids]
-    rows = {i: RowSampling(temperature=temps[i], top_k=ks[i], top_p=ps[i], repetition_penalty=pens[i], eos_id=eos,
-                           max_new_tokens=budgets[i], seed=_draw_seed() if seeds[i] is None else int(seeds[i]), stream=0,
-                           logit_bias=biases[i], min_new_tokens=min(mins[i], budgets[i]), grammar_state=gstates[i], truncation=truncs[i])
-            for i in live}
-    gen: Dict[int, List[int]] = {}
-    c0 = 0
-    while c0 < len(live):   # as many whole requests as fit into max_batch rows
-        part, used = [], 0
-        while c0 + len(part) < len(live) and used + len(ids[live[c0 + len(part)]]) <= eng.max_batch:
-            used += len(ids[live[c0 + len(part)]])
-            part.append(live[c0 + len(part)])
-        c0 += len(part)
-        steps = max(budgets[i] for i in part)
-        width = max(len(v) for i in part for v in ids[i])
-        if _no_window(eng) and width + steps > eng.max_ctx:
-            raise RuntimeError(f"prompt width {width} + {steps} new tokens exceed the engine's reserved context {eng.max_ctx}")
-        out = eng.generate_blended([ids[i] for i in part], [list(weights[i]) for i in part], [rows[i] for i in part], steps).cpu().tolist()
-        for i, row in zip(part, out):
-            gen[i] = [g for g in row if g >= 0]
-    return [[id2tok[t] for t in ids[i][0] + gen.get(i, [])] for i in range(n)]
+    first = [g[0] for g in ids]
+    budgets, live, rows = _request_rows(eng, first, max_len, temperature, top_k, top_p, seed, repetition_penalty, logit_bias,
+                                        min_new_tokens, grammar, min_p, typical_p, epsilon_cutoff, eta_cutoff)
+
+    def run(part, steps):
+        _check_fits(eng, max(len(v) for i in part for v in ids[i]), steps)
+        return eng.generate_blended([ids[i] for i in part], [list(weights[i]) for i in part], [rows[i] for i in part], steps)
+    return _serve(eng, first, budgets, live, lambda i: len(ids[i]), run)
 
 
 def sample(prompt: Sequence[str], max_len=512, temperature=1.0, top_k=50, device="cpu") -> List[str]:

@@ -954,41 +954,58 @@ def sample_rows_scored(logits: torch.Tensor, rows, step=0, want_probs=False, pre
     return _sample_rows(logits, rows, step, want_probs, presence, logit_bias, min_new_tokens, True, forced)
 
 
+def _sampler_inputs(logits: torch.Tensor, rows, presence, presence_alone: bool, forced=None, grammar=None, states=None):
+    """The front half of the row samplers (sample_rows, sample_rows_scored, sample_rows_grammar, sample_rows_truncated): the logits on
+    the device, the rows' sampler records (one per logits row), the presence words -- passed when a row's penalty is not 1 and, with
+    presence_alone, whenever presence is given --, the rows' logit records (with the tensors they point into: keep them until the call
+    has been made), the forced ids as an int32 [B] vector and the grammar's tables with the rows' states in and out, None for what the
+    call has not.  Returns (logits, recs, bits, lrecs, keep, forced, (class_of, next, states_in, states_out))."""
+    from .decoder import pack_row_logits, pack_rows
+    logits = _dev(logits.float())
+    B, V = logits.shape
+    dev = logits.device
+    if grammar is not None:
+        grammar.check(V)
+    recs = pack_rows(rows, V)
+    if len(recs) != B:
+        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
+    bits = None
+    if (presence_alone and presence is not None) or any(r.repetition_penalty != 1.0 for r in recs):
+        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
+        bits = torch.from_numpy(words.view(np.int32)).to(dev)
+    lrecs, keep = pack_row_logits(rows, V, dev)
+    if forced is not None:
+        forced = torch.as_tensor(forced).to(device=dev, dtype=torch.int32).contiguous()
+        if forced.shape != (B,):
+            raise ValueError(f"forced must hold {B} ids, got {list(forced.shape)}")
+    tables = (None, None, None, None)
+    if grammar is not None:
+        st = np.asarray(list(states), dtype=np.int64).reshape(-1)
+        if st.shape != (B,) or st.min() < -1 or st.max() >= grammar.n_state:
+            raise ValueError(f"states must be {B} values in [-1, {grammar.n_state})")
+        tables = (torch.from_numpy(grammar.class_of).to(dev), torch.from_numpy(grammar.next).to(dev),
+                  torch.from_numpy(st.astype(np.int32)).to(dev), torch.empty(B, dtype=torch.int32, device=dev))
+    return logits, recs, bits, lrecs, keep, forced, tables
+
+
 def _sample_rows(logits: torch.Tensor, rows, step, want_probs, presence, logit_bias, min_new_tokens, scored, forced):
     """sample_rows / sample_rows_scored: pack the rows, one native call."""
     import dataclasses
-    from .decoder import pack_row_logits, pack_rows
+    from .decoder import split_logit_bias
     rows = list(rows)
     if logit_bias is not None or min_new_tokens is not None:
         nb = len(rows)
-        per_row = [logit_bias] * nb
-        if logit_bias is not None and not isinstance(logit_bias, dict) and getattr(logit_bias, "ndim", 1) == 2:
-            if logit_bias.shape[0] != nb:
-                raise ValueError(f"logit_bias must be [V] or [{nb}, V], got {list(logit_bias.shape)}")
-            per_row = [logit_bias[b] for b in range(nb)]
+        per_row = split_logit_bias(logit_bias, nb)
         mins = list(min_new_tokens) if isinstance(min_new_tokens, (list, tuple)) else [min_new_tokens] * nb
         rows = [dataclasses.replace(r, logit_bias=r.logit_bias if logit_bias is None else per_row[b],
                                     min_new_tokens=r.min_new_tokens if mins[b] is None else int(mins[b]))
                 for b, r in enumerate(rows)]
     lib = _lib.load()
-    logits = _dev(logits.float())
+    logits, recs, bits, lrecs, keep, f, _ = _sampler_inputs(logits, rows, presence, False, forced if scored else None)
     B, V = logits.shape
-    recs = pack_rows(rows, V)
-    if len(recs) != B:
-        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
-    bits = None
-    if any(r.repetition_penalty != 1.0 for r in recs):
-        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
-        bits = torch.from_numpy(words.view(np.int32)).to(logits.device)
     ids = torch.empty(B, dtype=torch.int32, device=logits.device)
     probs = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_probs else None
-    lrecs, keep = pack_row_logits(rows, V, logits.device)
     if scored:
-        f = None
-        if forced is not None:
-            f = torch.as_tensor(forced).to(device=logits.device, dtype=torch.int32).contiguous()
-            if f.shape != (B,):
-                raise ValueError(f"forced must hold {B} ids, got {list(f.shape)}")
         lp = torch.empty(B, dtype=torch.float32, device=logits.device)
         ch = torch.empty(B, dtype=torch.float32, device=logits.device)
         check(lib.mgea_op_sample_rows_scored(ptr(logits), B, V, recs, ptr(bits), lrecs, int(step), ptr(ids), ptr(probs), ptr(f), ptr(lp),
@@ -1005,30 +1022,11 @@ def sample_rows_grammar(logits: torch.Tensor, rows, grammar, states, step=0, wan
     """sample_rows() under a mgea.decoder.TokenGrammar (mgea_op_sample_rows_grammar): row b in state states[b] (-1 = no grammar on
     the row) loses every id its state bans -- after its penalty and bias, before the EOS ban -- and moves to
     grammar.step(states[b], id).  The rows' own logit_bias / min_new_tokens apply.  Returns (ids, states_out[, probs])."""
-    from .decoder import pack_row_logits, pack_rows
-    rows = list(rows)
     lib = _lib.load()
-    logits = _dev(logits.float())
+    logits, recs, bits, lrecs, keep, _, (cls, nxt, s_in, s_out) = _sampler_inputs(logits, list(rows), presence, True, None, grammar, states)
     B, V = logits.shape
-    grammar.check(V)
-    recs = pack_rows(rows, V)
-    if len(recs) != B:
-        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
-    st = np.asarray(list(states), dtype=np.int64).reshape(-1)
-    if st.shape != (B,) or st.min() < -1 or st.max() >= grammar.n_state:
-        raise ValueError(f"states must be {B} values in [-1, {grammar.n_state})")
-    bits = None
-    if presence is not None or any(r.repetition_penalty != 1.0 for r in recs):
-        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
-        bits = torch.from_numpy(words.view(np.int32)).to(logits.device)
-    lrecs, keep = pack_row_logits(rows, V, logits.device)
-    dev = logits.device
-    cls = torch.from_numpy(grammar.class_of).to(dev)
-    nxt = torch.from_numpy(grammar.next).to(dev)
-    s_in = torch.from_numpy(st.astype(np.int32)).to(dev)
-    s_out = torch.empty(B, dtype=torch.int32, device=dev)
-    ids = torch.empty(B, dtype=torch.int32, device=dev)
-    probs = torch.empty(B, V, dtype=torch.float32, device=dev) if want_probs else None
+    ids = torch.empty(B, dtype=torch.int32, device=logits.device)
+    probs = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_probs else None
     check(lib.mgea_op_sample_rows_grammar(ptr(logits), B, V, recs, ptr(bits), lrecs, ptr(cls), ptr(nxt), grammar.n_state, grammar.n_class,
                                           ptr(s_in), int(step), ptr(ids), ptr(probs), ptr(s_out), stream_ptr()))
     return (ids, s_out, probs) if want_probs else (ids, s_out)
@@ -1043,49 +1041,25 @@ def sample_rows_truncated(logits: torch.Tensor, rows, truncation=None, step=0, w
     sample_rows_grammar, in any combination.  Returns ids, then (logprobs, choice_logprobs) if scored, then states_out if a grammar
     is given, then probs if want_probs -- a tuple unless ids stands alone."""
     import dataclasses
-    from .decoder import Truncation, pack_row_logits, pack_rows, pack_truncation
+    from .decoder import Truncation, pack_truncation
     rows = list(rows)
     if truncation is not None:
         per = [truncation] * len(rows) if isinstance(truncation, Truncation) else list(truncation)
         if len(per) != len(rows):
             raise ValueError(f"{len(rows)} sampler rows but {len(per)} truncation records")
         rows = [dataclasses.replace(r, truncation=t) for r, t in zip(rows, per)]
-    lib = _lib.load()
-    logits = _dev(logits.float())
-    B, V = logits.shape
-    dev = logits.device
-    recs = pack_rows(rows, V)
-    if len(recs) != B:
-        raise ValueError(f"{B} logits rows but {len(recs)} sampler rows")
-    trecs = pack_truncation(rows)
-    bits = None
-    if presence is not None or any(r.repetition_penalty != 1.0 for r in recs):
-        words = pack_presence(presence if presence is not None else [[] for _ in range(B)], B, V)
-        bits = torch.from_numpy(words.view(np.int32)).to(dev)
-    lrecs, keep = pack_row_logits(rows, V, dev)
-    ids = torch.empty(B, dtype=torch.int32, device=dev)
-    probs = torch.empty(B, V, dtype=torch.float32, device=dev) if want_probs else None
-    f = lp = ch = cls = nxt = s_in = s_out = None
     if forced is not None and not scored:
         raise ValueError("forced ids need scored=True")
-    if scored:
-        if forced is not None:
-            f = torch.as_tensor(forced).to(device=dev, dtype=torch.int32).contiguous()
-            if f.shape != (B,):
-                raise ValueError(f"forced must hold {B} ids, got {list(f.shape)}")
-        lp = torch.empty(B, dtype=torch.float32, device=dev)
-        ch = torch.empty(B, dtype=torch.float32, device=dev)
-    n_state = n_class = 0
-    if grammar is not None:
-        grammar.check(V)
-        st = np.asarray(list(states), dtype=np.int64).reshape(-1)
-        if st.shape != (B,) or st.min() < -1 or st.max() >= grammar.n_state:
-            raise ValueError(f"states must be {B} values in [-1, {grammar.n_state})")
-        cls = torch.from_numpy(grammar.class_of).to(dev)
-        nxt = torch.from_numpy(grammar.next).to(dev)
-        s_in = torch.from_numpy(st.astype(np.int32)).to(dev)
-        s_out = torch.empty(B, dtype=torch.int32, device=dev)
-        n_state, n_class = grammar.n_state, grammar.n_class
+    lib = _lib.load()
+    logits, recs, bits, lrecs, keep, f, (cls, nxt, s_in, s_out) = _sampler_inputs(logits, rows, presence, True, forced, grammar, states)
+    B, V = logits.shape
+    dev = logits.device
+    trecs = pack_truncation(rows)
+    ids = torch.empty(B, dtype=torch.int32, device=dev)
+    probs = torch.empty(B, V, dtype=torch.float32, device=dev) if want_probs else None
+    lp = torch.empty(B, dtype=torch.float32, device=dev) if scored else None
+    ch = torch.empty(B, dtype=torch.float32, device=dev) if scored else None
+    n_state, n_class = (grammar.n_state, grammar.n_class) if grammar is not None else (0, 0)
     check(lib.mgea_op_sample_rows_truncated(ptr(logits), B, V, recs, ptr(bits), lrecs, trecs, int(step), ptr(ids), ptr(probs), ptr(f), ptr(lp),
                                             ptr(ch), ptr(cls), ptr(nxt), n_state, n_class, ptr(s_in), ptr(s_out), stream_ptr()))
     out = (ids,) + ((lp, ch) if scored else ()) + ((s_out,) if grammar is not None else ()) + ((probs,) if want_probs else ())

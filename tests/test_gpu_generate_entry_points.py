@@ -1,6 +1,6 @@
-"""The six mgea_decoder_generate_rows* entry points are one request with some fields left out (GenRequest, csrc/gen_plan.h): each is
-called directly through ctypes, then again through mgea_decoder_generate_rows_scheduled -- the superset, which DecoderEngine always
-calls -- with NULL (or n_seg_max = 1) for what it lacks.  Both calls must give the same ids, log-probabilities and report, bit for
+"""The nine mgea_decoder_generate_rows* entry points are one request with some fields left out (GenRequest, csrc/gen_plan.h): each is
+called directly through ctypes, then again through mgea_decoder_generate_rows_class_penalized -- the superset at the end of the chain,
+the one call DecoderEngine._run_rows makes -- with NULL (or n_seg_max = 1) for what it lacks.  Both calls must give the same ids, log-probabilities and report, bit for
 bit, and the second one must replay the first one's graphs: the same step kind, so the same graph key.
 On the fused path (decoder_tiny8h, d_model 256) and the unfused one (decoder_tiny, d_model 128); 12 steps = one 8-step graph launch
 plus four single-step replays, as in test_gpu_step_forms.py.
@@ -17,7 +17,8 @@ from mgea import synth
 pytestmark = pytest.mark.gpu
 N_STEPS = 12
 EOS = 2
-ENTRY_POINTS = ("rows", "rows_biased", "rows_scored", "rows_grammar", "rows_guided", "rows_scheduled")
+ENTRY_POINTS = ("rows", "rows_biased", "rows_scored", "rows_grammar", "rows_guided", "rows_scheduled", "rows_truncated", "rows_blended",
+                "rows_class_penalized")
 
 
 def make(g):
@@ -34,14 +35,15 @@ def parity_grammar(vocab):
 
 
 def request(eng, g, name):
-    """Every argument of mgea_decoder_generate_rows_scheduled for the case of entry point `name`, None / 1 where that one has no such
+    """Every argument of mgea_decoder_generate_rows_class_penalized for the case of entry point `name`, None / 1 where that one has no such
     argument, as a dict; plus the tensors the records point into."""
     from mgea import _lib
-    from mgea.decoder import RowSampling, RowSchedule, pack_row_logits, pack_rows
+    from mgea.decoder import (ClassPenalty, RowSampling, RowSchedule, Truncation, pack_class_penalty, pack_row_logits, pack_rows,
+                              pack_truncation)
     p0, p1 = g["prompt0"].tolist(), g["prompt1"].tolist()
     assert len(p0) != len(p1) and all(3 <= len(p) <= 5 for p in (p0, p1))
-    paired = name in ("rows_guided", "rows_scheduled")
-    if paired:   # B = 4: two 8-token prompts, and behind them their shadow rows, the prompts without their first two tokens
+    paired = name in ("rows_guided", "rows_scheduled", "rows_blended")
+    if paired:   # B = 4: two 8-token prompts, and behind them their shadow rows (or members), the prompts without their first two tokens
         c0, c1 = (p0 + p1 + p0)[:8], (p1 + p0 + p1)[:8]
         prompts = [c0, c1, c0[2:], c1[2:]]
     else:        # B = 2: ragged prompts of 3-5 tokens
@@ -51,18 +53,28 @@ def request(eng, g, name):
     for b, p in enumerate(prompts):
         ids[b, :len(p)] = torch.tensor(p, dtype=torch.int32)
     a = dict(B=B, Tp=Tp, lens=torch.tensor([len(p) for p in prompts], dtype=torch.int32).cuda(), lrecs=None, starts=None, guide=None,
-             sched=None, n_seg_max=1, forced=None, scored=False)
+             sched=None, n_seg_max=1, forced=None, scored=False, trunc=None, blend=None, cpen=None)
     biased = name != "rows"
     bias = (np.random.default_rng(5).standard_normal(eng.vocab) * 2).astype(np.float32) if biased else None
     eos = -1 if paired else EOS   # (a row that drew its EOS id before step 5 would not switch)
     rows = [RowSampling(1.0, 20, None, 1.2 if biased else 1.0, eos, 0, 7 + b, None, bias, 3 if biased else 0) for b in range(B)]
-    if paired:   # a shadow row is a plain row (its conditional row's record replaces its own)
+    if paired:   # a shadow row, or a member, is a plain row (its conditional row's, or its leader's, record replaces its own)
         rows[2:] = [RowSampling(), RowSampling()]
+    if name == "rows_blended":   # groups {0, 2} and {1, 3}
+        a["blend"] = (_lib.RowBlend * B)(_lib.RowBlend(0, 0.6), _lib.RowBlend(1, 1.5), _lib.RowBlend(0, 0.4), _lib.RowBlend(1, -0.5))
+    elif paired:
         a["guide"] = (_lib.RowGuidance * B)(_lib.RowGuidance(2, 1.5), _lib.RowGuidance(3, 0.5), _lib.RowGuidance(-1, 0.0),
                                             _lib.RowGuidance(-1, 0.0))
+    if name == "rows_truncated":   # row 0 only; row 1 gets a record that is all off
+        rows[0].truncation = Truncation(min_p=0.05, typical_p=0.9)
+        a["trunc"] = pack_truncation(rows)
+    if name == "rows_class_penalized":   # row 0 on, row 1 an off record
+        eng.set_penalty_classes(np.arange(eng.vocab) % 4)
+        rows[0].class_penalty, rows[1].class_penalty = ClassPenalty(0.5, 1.0, 4), ClassPenalty()
+        a["cpen"] = pack_class_penalty(rows, N_STEPS, 4)
     a["recs"] = pack_rows(rows, eng.vocab, N_STEPS)
     a["lrecs"], keep = pack_row_logits(rows, eng.vocab, eng.device)
-    if name in ("rows_scored", "rows_grammar", "rows_scheduled"):
+    if name in ("rows_scored", "rows_grammar", "rows_scheduled", "rows_truncated"):
         a["scored"] = True
         forced = torch.full((B, N_STEPS), -1, dtype=torch.int32)
         forced[0, 1], forced[1, 9] = 11, 4
@@ -81,7 +93,7 @@ def request(eng, g, name):
 
 
 def call(eng, a, name):
-    """One generation through entry point `name` (the direct call) or "superset" (mgea_decoder_generate_rows_scheduled): the ids, the
+    """One generation through entry point `name` (the direct call) or "superset" (mgea_decoder_generate_rows_class_penalized): the ids, the
     log-probabilities where scored, and everything the engine reports about the call."""
     from mgea._lib import check, ptr
     lib, h, sp = eng.lib, eng.h, eng._sp()
@@ -103,9 +115,19 @@ def call(eng, a, name):
         elif name == "rows_guided":
             check(lib.mgea_decoder_generate_rows_guided(*head, a["lrecs"], a["starts"], a["guide"], *tail))
         else:
-            check(lib.mgea_decoder_generate_rows_scheduled(*head, a["lrecs"], a["starts"], a["guide"], a["sched"], a["n_seg_max"], *tail))
+            mid = (a["lrecs"], a["starts"], a["guide"], a["sched"], a["n_seg_max"], *tail[:-1])
+            if name == "rows_scheduled":
+                check(lib.mgea_decoder_generate_rows_scheduled(*head, *mid, sp))
+            elif name == "rows_truncated":
+                check(lib.mgea_decoder_generate_rows_truncated(*head, *mid, a["trunc"], sp))
+            elif name == "rows_blended":
+                check(lib.mgea_decoder_generate_rows_blended(*head, *mid, a["trunc"], a["blend"], sp))
+            else:
+                assert name in ("rows_class_penalized", "superset")
+                check(lib.mgea_decoder_generate_rows_class_penalized(*head, *mid, a["trunc"], a["blend"], a["cpen"], sp))
     eng._cur_batch = B
-    report = dict(stats=eng.stats(), grammar=eng.grammar_info(), guidance=eng.guidance_info(), schedule=eng.schedule_info())
+    report = dict(stats=eng.stats(), grammar=eng.grammar_info(), guidance=eng.guidance_info(), schedule=eng.schedule_info(),
+                  truncation=eng.truncation_info(), blend=eng.blend_info(), class_penalty=eng.class_penalty_info())
     assert eng.id_errors(raise_error=False) == 0
     return out.cpu(), None if lp is None else lp.cpu(), None if ch is None else ch.cpu(), report
 
@@ -129,6 +151,9 @@ def test_entry_point_equals_the_superset_call(golden, tag, name):
     assert (rep["schedule"]["scheduled_steps"] > 0) == (a["sched"] is not None)
     if a["sched"] is not None:
         assert rep["schedule"]["switches"] == 1
+    assert (rep["truncation"]["steps"] > 0) == (a["trunc"] is not None)
+    assert rep["blend"]["groups"] == (2 if a["blend"] is not None else 0)
+    assert (rep["class_penalty"]["class_penalized_steps"] > 0) == (a["cpen"] is not None)
     ids2, lp2, ch2, rep2 = call(eng, a, "superset")
     assert torch.equal(ids, ids2), f"{tag}: {name} and the superset call give different ids"
     if a["scored"]:
